@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — decode tokens/s of the PQ-KV attention hot path at BASELINE.json's headline config.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment re-launches itself under torch.distributed.run with N
@@ -23,10 +23,16 @@ synchronize on both sides; the window fill at the start is chosen so that ONE fl
 falls inside the timed region; N > 1 shards REQUESTS over ranks (no data-path collective: SURVEY.md 8e), value = all
 ranks' tokens / max-over-ranks time.
 
-Extra objects on the JSON line: `roofline` (dominant kernel = the fused decode-attention launch: algorithmic bytes
-per launch / mean launch duration from HIP events recorded on the launch stream), `cpu_baseline` (the reference's CPU
-PyTorch math restated in oracle/, timed on this box's cores on ONE layer-call and scaled to a step; rank 0, N = 1
-only) and `gpu_fp16_baseline` (one layer-call of the reference's fp16 full-KV recipe — torch.cat + repeat_kv + SDPA,
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step` = milliseconds of one timed
+step, `per_rank_ms_per_step`, `tail_faults`, `config`); `--dump-outputs DIR` also writes what the last timed step returned
+to its caller: DIR/attn_out.npy, float32, the attention output of every layer (layers, batch, nh, 1, d) - with N > 1 one
+file per rank, attn_out.rank<R>.npy.  Inputs are seeded, so the same arguments give the same inputs on every run.
+
+`--full` measures the rest after the timed steps (`vs_baseline` stays null without it): `config` gets the steady-state
+period and per-kind step times, and the JSON line gets the extra objects `roofline` (dominant kernel = the fused
+decode-attention launch: algorithmic bytes per launch / mean launch duration from HIP events recorded on the launch
+stream), `cpu_baseline` (the reference's CPU PyTorch math restated in oracle/, timed on the cores this process may
+use on ONE layer-call and scaled to a step; rank 0, N = 1 only) and `gpu_fp16_baseline` (one layer-call of the reference's fp16 full-KV recipe — torch.cat + repeat_kv + SDPA,
 scripts/modeldb/models/modeling_llama.py:403-443 — and of SDPA on a preallocated cache, same shape, HIP events);
 `vs_baseline` = the preallocated-cache SDPA layer-call time / this path's launch time (kernel level; BASELINE.md holds
 no published number for the metric itself; `vs_hf_recipe` is the same against the reference's own recipe),
@@ -50,6 +56,7 @@ ROOT = Path(__file__).resolve().parent
 sys.path.insert(0, str(ROOT))
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
+DUMP_BYTES_MAX = 64 << 20     # --dump-outputs: all files of a run together
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 
 
@@ -78,10 +85,17 @@ def parse(argv=None):
     ap.add_argument("--ea-launches", type=int, default=0, help="A/B: launches the encode-ahead of all layers is split into (0: the cache's choice)")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end TPOT / TTFT record (N = 1 only; ~1-2 min)")
     ap.add_argument("--e2e-cap-s", type=float, default=240.0, help="no end-to-end backend is started later than this many seconds into the e2e leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beyond the headline figure: steady-state period, per-kind step "
+                         "times, roofline, fp16 / CPU baselines, residual-tile record, e2e record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the attention outputs of the last timed step (every layer) as DIR/attn_out.npy (float32)")
     ap.add_argument("--dry-cpu", action="store_true",
                     help="rehearse the launcher / rank plumbing on CPU (gloo, no kernels): prints the same JSON line with "
                          "a sleep as the step; for the CPU tests, never a measurement")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.batch_per_gpu <= 0:
         args.batch_per_gpu = 2 if args.gpus > 1 else 1
     return args
@@ -129,6 +143,30 @@ def ranks_seen(dist, rank, ident):
     return [list(x) for x in sorted(got)]
 
 
+def dump_outputs(torch, out_dir, outs, rank, world):
+    """--dump-outputs: the attention outputs of every layer of the last step, (layers, bs, nh, 1, d) as float32 (exact for the
+    fp16 outputs), in DIR/attn_out.npy (attn_out.rank<R>.npy with N > 1 ranks).  Above a rank's share of DUMP_BYTES_MAX the file
+    holds a fixed sample instead: the elements at sorted positions drawn with seed 0 from the flattened array."""
+    import numpy as np
+    a = torch.stack(outs).float().cpu().numpy()
+    cap = DUMP_BYTES_MAX // world // a.itemsize
+    if a.size > cap:
+        a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / ("attn_out.npy" if world == 1 else f"attn_out.rank{rank}.npy"), a)
+
+
+def usable_cpus():
+    """CPUs this process may use: OMP_NUM_THREADS where the host sets an allotment, else the affinity mask (os.cpu_count() counts
+    the whole machine, and one torch thread per core of a large shared host only slows the CPU baseline down)."""
+    try:
+        n = int(os.environ.get("OMP_NUM_THREADS", "0"))
+    except ValueError:
+        n = 0
+    return n if n > 0 else len(os.sched_getaffinity(0))
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -162,23 +200,24 @@ def main():
     r0 = window_fill_at_start(cap, args.warmup + PRE, args.steps)
     total_steps = PRE + args.warmup + args.steps + 64 + 8
     g = torch.Generator(device="cpu").manual_seed(42 + rank)
+    gd = torch.Generator(device=dev).manual_seed(1042 + rank)      # device-side inputs: the same on every run
     cache = PagedPQCache(bs=bs, nh=nh, num_key_value_heads=nhk, M=M, layer_num=layers, d=d, page_size=ps,
                          extended_residual_size=cap, max_tokens=T0 + total_steps + 2 * cap, device=dev)
     cents_k = torch.randn(M, C, d // M, generator=g).half().to(dev)
     cents_v = torch.randn(M, C, d // M, generator=g).half().to(dev)
     cache.set_cent(cents_k, cents_v)
     # synthetic state: random codes in every page, random residual rows (same distributions as test_kernel.py)
-    cache.key_page_pool.copy_(torch.randint(0, C, cache.key_page_pool.shape, dtype=torch.uint8, device=dev))
-    cache.value_page_pool.copy_(torch.randint(0, C, cache.value_page_pool.shape, dtype=torch.uint8, device=dev))
+    cache.key_page_pool.copy_(torch.randint(0, C, cache.key_page_pool.shape, dtype=torch.uint8, device=dev, generator=gd))
+    cache.value_page_pool.copy_(torch.randint(0, C, cache.value_page_pool.shape, dtype=torch.uint8, device=dev, generator=gd))
     for l in range(layers):
-        cache.key_residual_cache[l].copy_(torch.randn(cache.key_residual_cache[l].shape, device=dev).half())
-        cache.value_residual_cache[l].copy_(torch.randn(cache.value_residual_cache[l].shape, device=dev).half())
+        cache.key_residual_cache[l].copy_(torch.randn(cache.key_residual_cache[l].shape, device=dev, generator=gd).half())
+        cache.value_residual_cache[l].copy_(torch.randn(cache.value_residual_cache[l].shape, device=dev, generator=gd).half())
     cache.set_host_state(([T0 + r0] * layers, [r0] * layers, [T0] * layers, [0] * layers))
     for l in range(layers):
         cache._sync_lengths(l)
-    q = [torch.randn(bs, nh, 1, d, device=dev).half() for _ in range(layers)]
-    kn = [torch.randn(bs, nhk, 1, d, device=dev).half() for _ in range(layers)]
-    vn = [torch.randn(bs, nhk, 1, d, device=dev).half() for _ in range(layers)]
+    q = [torch.randn(bs, nh, 1, d, device=dev, generator=gd).half() for _ in range(layers)]
+    kn = [torch.randn(bs, nhk, 1, d, device=dev, generator=gd).half() for _ in range(layers)]
+    vn = [torch.randn(bs, nhk, 1, d, device=dev, generator=gd).half() for _ in range(layers)]
     outs = [torch.empty(bs, nh, 1, d, device=dev, dtype=torch.float16) for _ in range(layers)]
 
     cache.encode_ahead_launches = args.ea_launches or None
@@ -238,113 +277,115 @@ def main():
     elapsed, elapsed_ranks = sharding.timed_steps_per_rank(counted_step, args.steps, torch.cuda.synchronize, dist if world > 1 else None)
     value, ms_per_step = sharding.aggregate_throughput(bs, args.steps, elapsed, world)
     flushes_timed = n_flush_steps
-    # for the record: one whole flush period (64 steps = 63 plain + 1 flush), the steady-state mix
-    elapsed64 = sharding.timed_steps(counted_step, 64, torch.cuda.synchronize, dist if world > 1 else None)
-    value64, ms64 = sharding.aggregate_throughput(bs, 64, elapsed64, world)
-    # and the two kinds of step apart (HIP events around every step of another period): what a flush step costs
-    step_ev, step_is_flush, step_kinds = [], [], []
-    for _ in range(64):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        step_is_flush.append(cache.next_step_flushes())
-        step_kinds.append(step_kind())
-        a.record()
-        one_step()
-        b.record()
-        step_ev.append((a, b))
-    torch.cuda.synchronize()
-    step_ms = [a.elapsed_time(b) for a, b in step_ev]
-    plain_ms = [t for t, f in zip(step_ms, step_is_flush) if not f]
-    flush_ms = [t for t, f in zip(step_ms, step_is_flush) if f]
-    plain_step_ms = sorted(plain_ms)[len(plain_ms) // 2] if plain_ms else None
-    flush_step_ms = sum(flush_ms) / len(flush_ms) if flush_ms else None
-    pre_ms = [t for t, k in zip(step_ms, step_kinds) if k.startswith("pre")]
-    pre_step_ms = sum(pre_ms) / len(pre_ms) if pre_ms else None
-    plain_only = [t for t, k in zip(step_ms, step_kinds) if k == "plain"]
-    if plain_only:
-        plain_step_ms = sorted(plain_only)[len(plain_only) // 2]
-
-    # ---- roofline of the dominant kernel: HIP events on the launch stream ----
-    # `achieved` uses the average launch duration over a region of nl back-to-back launches between ONE pair of events
-    # (= what rocprofv3 --kernel-trace reports as the kernel's average, profiles/rNN_kernel_stats.csv, within ~1 %).
-    # Event pairs around every single launch are reported too; they read 1.5-2 us higher on a ~20 us kernel (the cost
-    # of the two event records).  Everything is enqueued behind a long device-side sleep so that the timestamps
-    # measure GPU execution, not host enqueue latency.
-    T_now, r_now = cache._T[0], cache.residualed_tokens[0]
-    nl = max(layers, args.roofline_launches // layers * layers)
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(nl)]
-    kprep, vprep = cache._kprep, cache._vprep
-
-    def attn_launch(l):
-        ops.pq_decode_attn(q[l], cache.key_page_pool, cache.value_page_pool, kprep, vprep,
-                           cache.key_residual_cache[l], cache.value_residual_cache[l], r_now, M=M, C=C,
-                           n_tokens=T_now, resid_start=cache._rstart[l], k_page_ids=cache.page_ids[l],
-                           v_page_ids=cache.page_ids[l], page_size=ps, out=outs[l], workspace=cache._ws)
-
-    for rep in range(2):                       # first pass warms, second is measured
-        torch.cuda._sleep(int(2.0e8 if rep else 1.0e7))
-        for i in range(nl):
-            evs[i][0].record()
-            attn_launch(i % layers)
-            evs[i][1].record()
+    if args.dump_outputs:      # what the last timed step returned to its caller, before anything else runs
+        dump_outputs(torch, args.dump_outputs, outs, rank, world)
+    if args.full:
+        # for the record: one whole flush period (64 steps = 63 plain + 1 flush), the steady-state mix
+        elapsed64 = sharding.timed_steps(counted_step, 64, torch.cuda.synchronize, dist if world > 1 else None)
+        value64, ms64 = sharding.aggregate_throughput(bs, 64, elapsed64, world)
+        # and the two kinds of step apart (HIP events around every step of another period): what a flush step costs
+        step_ev, step_is_flush, step_kinds = [], [], []
+        for _ in range(64):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            step_is_flush.append(cache.next_step_flushes())
+            step_kinds.append(step_kind())
+            a.record()
+            one_step()
+            b.record()
+            step_ev.append((a, b))
         torch.cuda.synchronize()
-    durs = sorted(a.elapsed_time(b) * 1e-3 for a, b in evs)          # seconds
-    mean_dur = sum(durs) / len(durs)
-    med_dur = durs[len(durs) // 2]
-    # the same launches back to back between ONE pair of events: launch-to-launch period, no per-launch event cost
-    periods = []
-    for _ in range(3):                         # three regions; the median is reported, all three are in the line
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda._sleep(int(2.0e8))
-        e0.record()
-        for i in range(nl):
-            attn_launch(i % layers)
-        e1.record()
-        torch.cuda.synchronize()
-        periods.append(e0.elapsed_time(e1) * 1e-3 / nl)
-    period_eager = sorted(periods)[1]
-    # the same nl launches as ONE captured hipGraph, replayed: how the steps themselves are launched (round 4; VERDICT r03 item 2:
-    # rocprofv3 inside replayed steps and the eager region above disagreed by 15 % at 8 requests - the cause is the device-side
-    # sleep in front of the eager region, not the launch mode: tools/mode_probe.py).  `frac` uses this region; the eager region
-    # stays in the line as a second field.  tools/trace_phases.py splits a rocprofv3 --kernel-trace of this very command into
-    # the same phases (the sleeps are the separators; the three graph regions follow the last sleep-separated phase).
-    periods_graph = []
-    if not args.no_graph:
-        gr_roof = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(gr_roof):
+        step_ms = [a.elapsed_time(b) for a, b in step_ev]
+        plain_ms = [t for t, f in zip(step_ms, step_is_flush) if not f]
+        flush_ms = [t for t, f in zip(step_ms, step_is_flush) if f]
+        plain_step_ms = sorted(plain_ms)[len(plain_ms) // 2] if plain_ms else None
+        flush_step_ms = sum(flush_ms) / len(flush_ms) if flush_ms else None
+        pre_ms = [t for t, k in zip(step_ms, step_kinds) if k.startswith("pre")]
+        pre_step_ms = sum(pre_ms) / len(pre_ms) if pre_ms else None
+        plain_only = [t for t, k in zip(step_ms, step_kinds) if k == "plain"]
+        if plain_only:
+            plain_step_ms = sorted(plain_only)[len(plain_only) // 2]
+
+        # ---- roofline of the dominant kernel: HIP events on the launch stream ----
+        # `achieved` uses the average launch duration over a region of nl back-to-back launches between ONE pair of events
+        # (= what rocprofv3 --kernel-trace reports as the kernel's average, profiles/rNN_kernel_stats.csv, within ~1 %).
+        # Event pairs around every single launch are reported too; they read 1.5-2 us higher on a ~20 us kernel (the cost
+        # of the two event records).  Everything is enqueued behind a long device-side sleep so that the timestamps
+        # measure GPU execution, not host enqueue latency.
+        T_now, r_now = cache._T[0], cache.residualed_tokens[0]
+        nl = max(layers, args.roofline_launches // layers * layers)
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(nl)]
+        kprep, vprep = cache._kprep, cache._vprep
+
+        def attn_launch(l):
+            ops.pq_decode_attn(q[l], cache.key_page_pool, cache.value_page_pool, kprep, vprep,
+                               cache.key_residual_cache[l], cache.value_residual_cache[l], r_now, M=M, C=C,
+                               n_tokens=T_now, resid_start=cache._rstart[l], k_page_ids=cache.page_ids[l],
+                               v_page_ids=cache.page_ids[l], page_size=ps, out=outs[l], workspace=cache._ws)
+
+        for rep in range(2):                       # first pass warms, second is measured
+            torch.cuda._sleep(int(2.0e8 if rep else 1.0e7))
+            for i in range(nl):
+                evs[i][0].record()
+                attn_launch(i % layers)
+                evs[i][1].record()
+            torch.cuda.synchronize()
+        durs = sorted(a.elapsed_time(b) * 1e-3 for a, b in evs)          # seconds
+        mean_dur = sum(durs) / len(durs)
+        med_dur = durs[len(durs) // 2]
+        # the same launches back to back between ONE pair of events: launch-to-launch period, no per-launch event cost
+        periods = []
+        for _ in range(3):                         # three regions; the median is reported, all three are in the line
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda._sleep(int(2.0e8))
+            e0.record()
             for i in range(nl):
                 attn_launch(i % layers)
-        gr_roof.replay()                       # warm replay; the timed ones follow it DIRECTLY: a device-side sleep in front of a
-        torch.cuda.synchronize()               # region lets the chip drop its clocks and the ~20 ms behind it read 3-15 % slow
-        for _ in range(3):                     # (tools/mode_probe.py; that is what the eager regions above still do)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            gr_roof.replay()
             e1.record()
             torch.cuda.synchronize()
-            periods_graph.append(e0.elapsed_time(e1) * 1e-3 / nl)
-    period = sorted(periods_graph)[1] if periods_graph else period_eager
-    alg = algorithmic_bytes(bs, nh, nhk, T_now, r_now, d, M, C)
-    achieved = alg / period / 1e9
-    # every rank's own launch period (the line's roofline is rank 0's; a slow GPU shows here and in per_rank_ms_per_step)
-    period_ranks = sharding.gather_floats(period, dist if world > 1 else None)
+            periods.append(e0.elapsed_time(e1) * 1e-3 / nl)
+        period_eager = sorted(periods)[1]
+        # the same nl launches as ONE captured hipGraph, replayed: how the steps themselves are launched (round 4; VERDICT r03 item 2:
+        # rocprofv3 inside replayed steps and the eager region above disagreed by 15 % at 8 requests - the cause is the device-side
+        # sleep in front of the eager region, not the launch mode: tools/mode_probe.py).  `frac` uses this region; the eager region
+        # stays in the line as a second field.  tools/trace_phases.py splits a rocprofv3 --kernel-trace of this very command into
+        # the same phases (the sleeps are the separators; the three graph regions follow the last sleep-separated phase).
+        periods_graph = []
+        if not args.no_graph:
+            gr_roof = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gr_roof):
+                for i in range(nl):
+                    attn_launch(i % layers)
+            gr_roof.replay()                       # warm replay; the timed ones follow it DIRECTLY: a device-side sleep in front of a
+            torch.cuda.synchronize()               # region lets the chip drop its clocks and the ~20 ms behind it read 3-15 % slow
+            for _ in range(3):                     # (tools/mode_probe.py; that is what the eager regions above still do)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                gr_roof.replay()
+                e1.record()
+                torch.cuda.synchronize()
+                periods_graph.append(e0.elapsed_time(e1) * 1e-3 / nl)
+        period = sorted(periods_graph)[1] if periods_graph else period_eager
+        alg = algorithmic_bytes(bs, nh, nhk, T_now, r_now, d, M, C)
+        achieved = alg / period / 1e9
+        # every rank's own launch period (the line's roofline is rank 0's; a slow GPU shows here and in per_rank_ms_per_step)
+        period_ranks = sharding.gather_floats(period, dist if world > 1 else None)
     # a split merge that gave up on a partial writes NaN heads and counts itself (million_hip.h): must be 0 after the timed regions
     tail_faults = sharding.gather_floats(float(ops.tail_faults()), dist if world > 1 else None)
-    traffic = None
-    pmc = ROOT / "profiles" / "pmc_traffic.json"     # written from rocprofv3 --pmc passes (see profiles/README.md)
-    if pmc.exists():
-        try:
-            rec = json.loads(pmc.read_text())
-            if rec.get("ctx") == T0 and rec.get("M") == M and rec.get("batch_per_gpu") == bs:
-                traffic = rec.get("hbm_bytes_per_launch")
-        except Exception:
-            traffic = None
+    traffic = fp16 = res_tile = None
+    if args.full:
+        pmc = ROOT / "profiles" / "pmc_traffic.json"     # written from rocprofv3 --pmc passes (see profiles/README.md)
+        if pmc.exists():
+            try:
+                rec = json.loads(pmc.read_text())
+                if rec.get("ctx") == T0 and rec.get("M") == M and rec.get("batch_per_gpu") == bs:
+                    traffic = rec.get("hbm_bytes_per_launch")
+            except Exception:
+                traffic = None
 
-    fp16 = None
-    if not args.no_fp16_baseline and not args.force_generic:
-        fp16 = gpu_fp16_baseline(torch, dev, bs, nh, nhk, d, T_now + r_now)
-    res_tile = None
-    if not args.force_generic and M in (32, 64):
-        res_tile = residual_tile_record(torch, attn_launch, layers, bs, nh, nhk, d, r_now, T_now)
+        if not args.no_fp16_baseline and not args.force_generic:
+            fp16 = gpu_fp16_baseline(torch, dev, bs, nh, nhk, d, T_now + r_now)
+        if not args.force_generic and M in (32, 64):
+            res_tile = residual_tile_record(torch, attn_launch, layers, bs, nh, nhk, d, r_now, T_now)
 
     if rank == 0:
         cfg_name = "configs[2]" if (world == 1 and bs == 1) else ("configs[3]" if bs == 2 else "configs[2] shape")
@@ -370,51 +411,52 @@ def main():
                                                  "step only moves the lengths (one launch for all layers)",
                                  "ahead": f"ahead: flush launches of the flush step on a side stream, issued {args.flush_depth} layers ahead; each layer's attention waits for its own",
                                  "inline": "in-line"}[args.flush_mode],
-                       "steady_state_64_steps": {"value": round(value64, 2), "ms_per_step": round(ms64, 4),
-                                                 "note": "one whole flush period (64 steps: plain steps, one encode-ahead step, one flush / commit step)"},
-                       "plain_step_ms": round(plain_step_ms, 4) if plain_step_ms else None,
-                       "flush_step_ms": round(flush_step_ms, 4) if flush_step_ms else None,
-                       "flush_step_over_plain_step": round(flush_step_ms / plain_step_ms, 3) if plain_step_ms and flush_step_ms else None,
-                       "encode_ahead_steps_per_period": len(pre_ms),
-                       "encode_ahead_step_ms": round(pre_step_ms, 4) if pre_step_ms else None,
-                       "encode_ahead_step_over_plain_step": round(pre_step_ms / plain_step_ms, 3) if plain_step_ms and pre_step_ms else None,
                        "launch": "eager" if args.no_graph else "hipGraph replay",
                        "kernel": "generic-LUT" if args.force_generic else ("auto" if not args.kernel_policy else f"policy{args.kernel_policy}")},
-            "roofline": {"bound": "hbm", "kernel": "fused decode attention (one launch per layer-call)",
-                         "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                         "traffic_source": "profiles/pmc_traffic.json (rocprofv3 --pmc passes of this command)" if traffic else None,
-                         "algorithmic_bytes_per_launch": alg, "launch_us_mean": round(period * 1e6, 2),
-                         "launches_timed": nl,
-                         "per_rank": {"launch_us_mean": [round(x * 1e6, 2) for x in period_ranks],
-                                      "frac": [round(alg / x / 1e9 / HBM_PEAK_GBS, 4) for x in period_ranks]},
-                         "timing": ("HIP events around ONE replay of a captured hipGraph of the launches / launches (how the steps are launched); "
-                                    "median of three regions" if periods_graph else
-                                    "HIP events around a region of back-to-back eager launches / launches; median of three regions"),
-                         "launch_us_regions": [round(x * 1e6, 2) for x in (periods_graph or periods)],
-                         "eager": {"launch_us_mean": round(period_eager * 1e6, 2), "launch_us_regions": [round(x * 1e6, 2) for x in periods],
-                                   "frac": round(alg / period_eager / 1e9 / HBM_PEAK_GBS, 4),
-                                   "note": "rounds 1-3 method: the same launches enqueued one by one behind a device-side sleep (keeps the host ahead, but the "
-                                           "chip lowers its clocks during the sleep: reads 3 % slow at 1 request, 15 % at 8; profiles/r04_shapes.txt)"},
-                         "event_pair_per_launch_us_mean": round(mean_dur * 1e6, 2),
-                         "event_pair_per_launch_us_median": round(med_dur * 1e6, 2)},
         }
-        if fp16:
-            line["vs_baseline_note"] = ("kernel level, no published number in BASELINE.md: layer-call time of torch SDPA over a "
-                                        "PREALLOCATED fp16 KV cache (no cat, no repeat_kv) / fused PQ decode-attention launch time; "
-                                        "vs_hf_recipe = the same against the reference's own baseline recipe (torch.cat + repeat_kv + SDPA, "
-                                        "modeling_llama.py:403-443); the end-to-end ratio by the reference's TPOT definition is e2e.speedup_vs_hf_baseline")
-            line["vs_hf_recipe"] = round(fp16["hf_recipe_us"] / (period * 1e6), 2)
-            line["gpu_fp16_baseline"] = fp16
-        if res_tile:
-            line["roofline"]["residual_tile"] = res_tile
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(bs, nh, nhk, d, M, C, T0, r0, layers)
-        if world == 1 and not args.no_e2e and not args.force_generic and bs == 1 and M == 64 and layers == 32:
-            # free the hot-path state first: the end-to-end model brings 16 GB of weights and its own caches
-            del cache, graphs, q, kn, vn, outs
-            torch.cuda.empty_cache()
-            line["e2e"] = e2e_record(T0, args.e2e_cap_s)
+        if args.full:
+            line["config"].update({"steady_state_64_steps": {"value": round(value64, 2), "ms_per_step": round(ms64, 4),
+                                                              "note": "one whole flush period (64 steps: plain steps, one encode-ahead step, one flush / commit step)"},
+                                    "plain_step_ms": round(plain_step_ms, 4) if plain_step_ms else None,
+                                    "flush_step_ms": round(flush_step_ms, 4) if flush_step_ms else None,
+                                    "flush_step_over_plain_step": round(flush_step_ms / plain_step_ms, 3) if plain_step_ms and flush_step_ms else None,
+                                    "encode_ahead_steps_per_period": len(pre_ms),
+                                    "encode_ahead_step_ms": round(pre_step_ms, 4) if pre_step_ms else None,
+                                    "encode_ahead_step_over_plain_step": round(pre_step_ms / plain_step_ms, 3) if plain_step_ms and pre_step_ms else None})
+            line["roofline"] = {"bound": "hbm", "kernel": "fused decode attention (one launch per layer-call)",
+                                "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                                "traffic_source": "profiles/pmc_traffic.json (rocprofv3 --pmc passes of this command)" if traffic else None,
+                                "algorithmic_bytes_per_launch": alg, "launch_us_mean": round(period * 1e6, 2),
+                                "launches_timed": nl,
+                                "per_rank": {"launch_us_mean": [round(x * 1e6, 2) for x in period_ranks],
+                                             "frac": [round(alg / x / 1e9 / HBM_PEAK_GBS, 4) for x in period_ranks]},
+                                "timing": ("HIP events around ONE replay of a captured hipGraph of the launches / launches (how the steps are launched); "
+                                           "median of three regions" if periods_graph else
+                                           "HIP events around a region of back-to-back eager launches / launches; median of three regions"),
+                                "launch_us_regions": [round(x * 1e6, 2) for x in (periods_graph or periods)],
+                                "eager": {"launch_us_mean": round(period_eager * 1e6, 2), "launch_us_regions": [round(x * 1e6, 2) for x in periods],
+                                          "frac": round(alg / period_eager / 1e9 / HBM_PEAK_GBS, 4),
+                                          "note": "rounds 1-3 method: the same launches enqueued one by one behind a device-side sleep (keeps the host ahead, but the "
+                                                  "chip lowers its clocks during the sleep: reads 3 % slow at 1 request, 15 % at 8; profiles/r04_shapes.txt)"},
+                                "event_pair_per_launch_us_mean": round(mean_dur * 1e6, 2),
+                                "event_pair_per_launch_us_median": round(med_dur * 1e6, 2)}
+            if fp16:
+                line["vs_baseline_note"] = ("kernel level, no published number in BASELINE.md: layer-call time of torch SDPA over a "
+                                            "PREALLOCATED fp16 KV cache (no cat, no repeat_kv) / fused PQ decode-attention launch time; "
+                                            "vs_hf_recipe = the same against the reference's own baseline recipe (torch.cat + repeat_kv + SDPA, "
+                                            "modeling_llama.py:403-443); the end-to-end ratio by the reference's TPOT definition is e2e.speedup_vs_hf_baseline")
+                line["vs_hf_recipe"] = round(fp16["hf_recipe_us"] / (period * 1e6), 2)
+                line["gpu_fp16_baseline"] = fp16
+            if res_tile:
+                line["roofline"]["residual_tile"] = res_tile
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(bs, nh, nhk, d, M, C, T0, r0, layers)
+            if world == 1 and not args.no_e2e and not args.force_generic and bs == 1 and M == 64 and layers == 32:
+                # free the hot-path state first: the end-to-end model brings 16 GB of weights and its own caches
+                del cache, graphs, q, kn, vn, outs
+                torch.cuda.empty_cache()
+                line["e2e"] = e2e_record(T0, args.e2e_cap_s)
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()
@@ -582,7 +624,7 @@ def cpu_baseline(bs, nh, nhk, d, M, C, T, r, layers):
     ONE layer-call of the same workload, scaled by the layer count."""
     import torch
     from oracle import oracle as O
-    cores = os.cpu_count() or 1
+    cores = usable_cpus()
     torch.set_num_threads(cores)
     g = torch.Generator().manual_seed(7)
     q = torch.randn(bs, nh, 1, d, generator=g).half()

@@ -2437,3 +2437,31 @@ def test_attn_lean_kernel_many_units_per_wave_and_batch(env, oracle):
         _check(out[b:b + 1].cpu().numpy(), oracle.decode_attn(**cb), f"request {b}: T={Tb}, appended row {rb}")
     assert lengths.cpu().numpy()[:, 1].tolist() == [51, 50]
     assert ops.tail_faults() == 0
+
+
+def test_bench_plain_run_dumps_reproducible_outputs(env, tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` (a small configuration): the line holds exactly K timed steps and
+    ms_per_step and none of the --full extras; DIR/attn_out.npy holds the last timed step's outputs of every layer, finite
+    float32; a second run with the same arguments (the same seeded inputs) gives the same outputs."""
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parents[1]
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                            "--ctx", "4096", "--layers", "2", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600, cwd=str(root))
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        rec = json.loads(lines[0])
+        assert rec["steps"] == 5 and rec["warmup"] == 2 and rec["ms_per_step"] > 0 and rec["tail_faults"] == 0
+        assert rec["value"] == pytest.approx(1000.0 / rec["ms_per_step"], rel=1e-2)
+        assert "roofline" not in rec and "cpu_baseline" not in rec and "e2e" not in rec
+        a = np.load(d / "attn_out.npy")
+        assert a.dtype == np.float32 and a.shape == (2, 1, 32, 1, 128) and np.isfinite(a).all() and np.abs(a).max() > 0
+        dumps.append(a.astype(np.float64))
+    rel = np.linalg.norm(dumps[0] - dumps[1]) / np.linalg.norm(dumps[0])
+    assert rel < 1e-3, rel

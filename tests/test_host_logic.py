@@ -131,6 +131,48 @@ def test_bench_launcher_spawns_ranks_dry_cpu():
     assert rec["ms_per_step"] >= 4.0 * 0.9 and rec["value"] == pytest.approx(2 * 2 * 1000.0 / rec["ms_per_step"], rel=1e-3)
 
 
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", Path(__file__).resolve().parents[1] / "bench.py")
+    B = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(B)
+    return B
+
+
+def test_bench_plain_by_default_and_steps_honoured():
+    """A plain `bench.py --steps K --warmup W` times exactly K steps and nothing else: --full (the extra measurements) and
+    --dump-outputs are off unless asked for, and K < 1 is refused rather than divided by."""
+    B = _bench_module()
+    a = B.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    a = B.parse(["--steps", "3", "--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        B.parse(["--steps", "0"])
+
+
+def test_bench_dump_outputs_float32_and_capped(tmp_path, monkeypatch):
+    """--dump-outputs writes the per-layer outputs stacked as float32 (exact for fp16); above the byte cap a fixed seeded
+    sample of the flattened array, the same on every call."""
+    import numpy as np
+    B = _bench_module()
+    g = torch.Generator().manual_seed(0)
+    outs = [torch.randn(1, 4, 1, 8, generator=g).half() for _ in range(3)]
+    B.dump_outputs(torch, tmp_path / "a", outs, 0, 1)
+    a = np.load(tmp_path / "a" / "attn_out.npy")
+    assert a.dtype == np.float32 and a.shape == (3, 1, 4, 1, 8)
+    np.testing.assert_array_equal(a, torch.stack(outs).float().numpy())
+    B.dump_outputs(torch, tmp_path / "r", outs, 1, 2)
+    assert [p.name for p in (tmp_path / "r").iterdir()] == ["attn_out.rank1.npy"]
+    monkeypatch.setattr(B, "DUMP_BYTES_MAX", 40 * 4)
+    B.dump_outputs(torch, tmp_path / "s1", outs, 0, 1)
+    B.dump_outputs(torch, tmp_path / "s2", outs, 0, 1)
+    s1, s2 = np.load(tmp_path / "s1" / "attn_out.npy"), np.load(tmp_path / "s2" / "attn_out.npy")
+    assert s1.shape == (40,) and s1.dtype == np.float32
+    np.testing.assert_array_equal(s1, s2)
+    assert np.isin(s1, a.reshape(-1)).all()
+
+
 def test_bench_window_fill_puts_a_flush_in_the_timed_region():
     import importlib.util
     from pathlib import Path

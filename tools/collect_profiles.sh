@@ -9,10 +9,10 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-Q="--no-cpu-baseline --no-e2e --no-fp16-baseline"
+Q="--full --no-cpu-baseline --no-e2e --no-fp16-baseline"
 run() { echo "== $*"; timeout -k 10 400 "$@" || { echo "FAILED: $*"; exit 1; }; }
 # 1. the bench line itself (cpu baseline, fp16 baselines and the e2e record included)
-run python3 $ROOT/bench.py > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || exit 1
+run python3 $ROOT/bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || exit 1
 # 2. kernel stats per shape
 kt() { d=$1; shift; rm -rf $OUT/$d; run rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$d -- python3 $ROOT/bench.py --steps 64 --warmup 8 $Q "$@" > $OUT/$d.log 2>&1 || exit 1; }
 kt prof_kt
@@ -35,7 +35,7 @@ kt prof_kt_g16 --nh 128
   (cd $ROOT && python3 tools/ab_bench.py --cfg 32,20000,64 --C 128 --layers 4 | grep us/launch) || exit 1
 } > $OUT/shapes_$TAG.txt 2>&1
 # 2c. the like-for-like N = 1 point of configs[3] (2 requests per GPU)
-run python3 $ROOT/bench.py --gpus 1 --batch-per-gpu 2 --no-e2e > $OUT/bench_${TAG}_bs2.json 2> $OUT/bench_${TAG}_bs2.err || exit 1
+run python3 $ROOT/bench.py --full --gpus 1 --batch-per-gpu 2 --no-e2e > $OUT/bench_${TAG}_bs2.json 2> $OUT/bench_${TAG}_bs2.err || exit 1
 # 3. counters (eager launches so that every dispatch is attributed)
 pmc() { d=$1; shift; rm -rf $OUT/$d; run rocprofv3 --pmc "$@" --output-format csv -d $OUT/$d -- python3 $ROOT/bench.py --steps 8 --warmup 2 $Q --no-graph > $OUT/$d.log 2>&1 || exit 1; }
 pmc prof_fetch FETCH_SIZE

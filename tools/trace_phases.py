@@ -6,8 +6,8 @@ bench.py launches the attention kernel in four ways, in this order: (1) inside t
 lengths), (2) eagerly with an event pair around every launch (two passes), (3) eagerly back to back (three regions), (4) as one
 captured graph of the same launches, replayed (one warm replay + three regions).  Every region of (2)-(4) is preceded by a
 device-side sleep kernel, which this tool uses as the separator.
-    rocprofv3 --kernel-trace --output-format csv -d gpurun_out/kt -- python3 bench.py --batch-per-gpu 8 --no-e2e --no-cpu-baseline
-    python tools/trace_phases.py gpurun_out/kt [--label "8 requests"]
+    rocprofv3 --kernel-trace --output-format csv -d /tmp/kt -- python3 bench.py --full --batch-per-gpu 8 --no-e2e --no-cpu-baseline
+    python tools/trace_phases.py /tmp/kt [--label "8 requests"]
 """
 import argparse
 import csv
