@@ -273,6 +273,59 @@ int million_prefill_attn(const million_prefill_desc *desc, const void *q /* (bs,
                          million_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Chunk attention: a block of n_q new query tokens against the PQ-coded cache (chunked prefill, a second turn on an existing
+ * conversation, verification of draft tokens).  The decode entry points take one query token; million_prefill_attn takes fp16
+ * K/V only.  For query row i of head h (kv head hk = h / (nh/nh_k)):
+ *   out[b,h,i,:] = softmax_j( q[b,h,i,:] . Kall[b,hk,j,:] / sqrt(d) ) Vall[b,hk,j,:]
+ *   Kall = [ dequant(K codes, n_tokens) ; window rows (r rows of the ring from resid_start) ; chunk rows 0 .. n_c - 1 ], likewise V.
+ * Every row sees all n_tokens + r past keys; chunk key j is visible to row i iff j <= i (causal, the chunk's first row sits at
+ * position n_tokens + r).  n_c = n_q: chunked prefill (the caller then stores the chunk's K/V itself); n_c = 0: every row sees
+ * the past only (several query tokens of one position set: speculative verification).  Nothing to attend to: out = 0.
+ * Dequantisation is the gather of million_pq_decode (bit for bit); fp32 scores, softmax and accumulation; fp16 in and out.
+ * Shapes: d = 128 with M in {64, 32, 16}, d = 64 with M in {64, 32, 16}; uint8 codes, any C <= 256; any nh / nh_k >= 1, n_q >= 1;
+ * each code side row-major (bs, nh_k, T_cap, M) or paged (K pool (n_pool, page_size, M), V pool (n_pool, M, page_size)
+ * transposed) with page_size 32 / 64 / 128 and int32 or int64 ids.  Anything else: MILLION_ERR_SHAPE (no fallback).
+ * Code bytes past n_tokens, unused pool pages and window rows outside the ring's valid span are never read into a product.
+ * Host lengths only (no device-resident lengths).  The window and the chunk are read, never written. */
+typedef struct {
+    uint32_t struct_size;         /* = sizeof(million_chunk_attn_desc) */
+    int32_t bs, nh, nh_k, d, M, C;
+    int32_t n_q;                  /* query rows */
+    int32_t n_c;                  /* chunk K/V rows: 0 or n_q */
+    int32_t n_tokens;             /* T: quantised tokens per (b, hk) */
+    int32_t r;                    /* valid window rows, 0 <= r <= resid_cap */
+    int32_t resid_start;          /* first valid window row (ring buffer) */
+    int32_t resid_cap;            /* rows of the window buffers */
+    int64_t resid_stride_b, resid_stride_h;   /* fp16 elements; row stride is d */
+    int32_t k_layout, v_layout;   /* MILLION_KV_* */
+    int32_t page_size;            /* PAGED: 32, 64 or 128 */
+    int32_t n_pages_cap;          /* PAGED: row length of the page-id arrays (bs, nh_k, n_pages_cap) */
+    int32_t page_ids_i64;         /* PAGED: 0 = int32 ids, 1 = int64 */
+    int64_t k_stride_b, k_stride_h;   /* ROWMAJOR: bytes between batches / kv heads of k_codes (rows are M bytes) */
+    int64_t v_stride_b, v_stride_h;   /* ROWMAJOR: same for v_codes */
+    int64_t q_stride_b, q_stride_h, q_stride_n;     /* fp16 elements; the d elements of a row are contiguous; multiples of 8 */
+    int64_t kc_stride_b, kc_stride_h, kc_stride_n;  /* k_chunk (bs, nh_k, n_c, d) */
+    int64_t vc_stride_b, vc_stride_h, vc_stride_n;  /* v_chunk */
+    int64_t o_stride_b, o_stride_h, o_stride_n;     /* out (bs, nh, n_q, d) */
+} million_chunk_attn_desc;
+
+/* Workspace of a call: 0 when the context is not split (the kernel then writes out directly), else
+ * bs * nh_k * S * n_q * (nh/nh_k) * (d + 2) * 4 bytes, S = the split count of the past:
+ * min(ceil(256 / (bs * nh_k * ceil(n_q * (nh/nh_k) / 256))), ceil(n_tokens / 64), 64), at least 1.
+ * No initialisation is needed; the workspace holds nothing between calls.  0 for a descriptor that is not valid. */
+size_t million_chunk_attn_workspace_bytes(const million_chunk_attn_desc *desc);
+int million_pq_chunk_attn(const million_chunk_attn_desc *desc,
+                          const void *q,                /* (bs, nh, n_q, d) fp16, strided */
+                          const void *k_chunk, const void *v_chunk,   /* (bs, nh_k, n_c, d) fp16, strided; NULL when n_c = 0 */
+                          const void *k_codes, const void *v_codes,   /* ROWMAJOR tensors or page pools */
+                          const void *k_page_ids, const void *v_page_ids,   /* PAGED sides (may alias) */
+                          const void *k_cents_prepared, const void *v_cents_prepared,   /* million_prepare_cents */
+                          const void *k_resid, const void *v_resid,   /* (bs, nh_k, resid_cap, d) fp16 */
+                          void *out,                    /* (bs, nh, n_q, d) fp16, strided */
+                          void *workspace, size_t workspace_bytes,
+                          million_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Residual-window append.
  * Replaces: the two slice-assign copies of DynamicPQCache.decoding (pq_utils.py:304-312) /
  * PagedPQCache.decoding_with_pages (paged_pq_utils.py:377-380).

@@ -47,6 +47,18 @@ class PrefillDesc(ctypes.Structure):
                 ("o_stride_b", c_i64), ("o_stride_h", c_i64), ("o_stride_n", c_i64)]
 
 
+class ChunkAttnDesc(ctypes.Structure):
+    _fields_ = [("struct_size", c_u32), ("bs", c_i32), ("nh", c_i32), ("nh_k", c_i32), ("d", c_i32), ("M", c_i32), ("C", c_i32),
+                ("n_q", c_i32), ("n_c", c_i32), ("n_tokens", c_i32), ("r", c_i32), ("resid_start", c_i32), ("resid_cap", c_i32),
+                ("resid_stride_b", c_i64), ("resid_stride_h", c_i64),
+                ("k_layout", c_i32), ("v_layout", c_i32), ("page_size", c_i32), ("n_pages_cap", c_i32), ("page_ids_i64", c_i32),
+                ("k_stride_b", c_i64), ("k_stride_h", c_i64), ("v_stride_b", c_i64), ("v_stride_h", c_i64),
+                ("q_stride_b", c_i64), ("q_stride_h", c_i64), ("q_stride_n", c_i64),
+                ("kc_stride_b", c_i64), ("kc_stride_h", c_i64), ("kc_stride_n", c_i64),
+                ("vc_stride_b", c_i64), ("vc_stride_h", c_i64), ("vc_stride_n", c_i64),
+                ("o_stride_b", c_i64), ("o_stride_h", c_i64), ("o_stride_n", c_i64)]
+
+
 # every symbol include/million_hip.h declares: (restype, argtypes)
 SYMBOLS = {
     "million_version": (c_i32, []),
@@ -67,6 +79,8 @@ SYMBOLS = {
                                               c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "million_attn_kernel_kind": (c_i32, [ctypes.POINTER(AttnDesc)]),
     "million_prefill_attn": (c_i32, [ctypes.POINTER(PrefillDesc), c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "million_chunk_attn_workspace_bytes": (c_sz, [ctypes.POINTER(ChunkAttnDesc)]),
+    "million_pq_chunk_attn": (c_i32, [ctypes.POINTER(ChunkAttnDesc)] + [c_vp] * 13 + [c_sz, c_vp]),
     "million_set_force_generic": (None, [c_i32]),
     "million_debug_set_stamp_buffer": (None, [c_vp]),
     "million_debug_bad_page_ids": (c_i32, []),

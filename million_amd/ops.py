@@ -604,3 +604,114 @@ def tail_faults() -> int:
 
 def attn_kernel_kind(desc: L.AttnDesc) -> int:
     return L.load().million_attn_kernel_kind(ctypes.byref(desc))
+
+
+def chunk_attn_desc(q, k_res, *, nh_k, M, C, n_tokens, r, n_c, resid_start=0, k_paged=False, v_paged=False, page_size=0,
+                    n_pages_cap=0, page_ids_i64=False, k_codes=None, v_codes=None, k_chunk=None, v_chunk=None,
+                    out=None) -> L.ChunkAttnDesc:
+    bs, nh, n_q, d = q.shape
+    desc = L.ChunkAttnDesc()
+    desc.struct_size = ctypes.sizeof(L.ChunkAttnDesc)
+    desc.bs, desc.nh, desc.nh_k, desc.d, desc.M, desc.C = bs, nh, nh_k, d, M, C
+    desc.n_q, desc.n_c, desc.n_tokens, desc.r = n_q, n_c, n_tokens, r
+    desc.resid_start, desc.resid_cap = resid_start, k_res.shape[2]
+    desc.resid_stride_b, desc.resid_stride_h = k_res.stride(0), k_res.stride(1)
+    desc.k_layout = L.MILLION_KV_PAGED if k_paged else L.MILLION_KV_ROWMAJOR
+    desc.v_layout = L.MILLION_KV_PAGED if v_paged else L.MILLION_KV_ROWMAJOR
+    desc.page_size, desc.n_pages_cap, desc.page_ids_i64 = page_size, n_pages_cap, int(page_ids_i64)
+    if not k_paged and k_codes is not None:
+        desc.k_stride_b, desc.k_stride_h = k_codes.stride(0), k_codes.stride(1)
+    if not v_paged and v_codes is not None:
+        desc.v_stride_b, desc.v_stride_h = v_codes.stride(0), v_codes.stride(1)
+    desc.q_stride_b, desc.q_stride_h, desc.q_stride_n = q.stride(0), q.stride(1), q.stride(2)
+    if k_chunk is not None:
+        desc.kc_stride_b, desc.kc_stride_h, desc.kc_stride_n = k_chunk.stride(0), k_chunk.stride(1), k_chunk.stride(2)
+        desc.vc_stride_b, desc.vc_stride_h, desc.vc_stride_n = v_chunk.stride(0), v_chunk.stride(1), v_chunk.stride(2)
+    if out is not None:
+        desc.o_stride_b, desc.o_stride_h, desc.o_stride_n = out.stride(0), out.stride(1), out.stride(2)
+    return desc
+
+
+def chunk_attn_workspace_bytes(desc: L.ChunkAttnDesc) -> int:
+    return int(L.load().million_chunk_attn_workspace_bytes(ctypes.byref(desc)))
+
+
+def pq_chunk_attn(q: torch.Tensor, k_chunk: Optional[torch.Tensor], v_chunk: Optional[torch.Tensor], k_codes: torch.Tensor,
+                  v_codes: torch.Tensor, k_prep: torch.Tensor, v_prep: torch.Tensor, k_res: torch.Tensor, v_res: torch.Tensor,
+                  r: int, *, M: int, C: int, n_tokens: int, resid_start: int = 0, k_page_ids: Optional[torch.Tensor] = None,
+                  v_page_ids: Optional[torch.Tensor] = None, page_size: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                  workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """n_q query tokens against [the PQ codes of n_tokens tokens; r window rows of the ring from resid_start; the chunk]
+    (million_pq_chunk_attn): q (bs, nh, n_q, d) -> (bs, nh, n_q, d).  k_chunk / v_chunk (bs, nh_k, n_q, d): the chunk's own
+    K/V, attended causally (chunked prefill, a later turn of a conversation); None: every row sees the past only (draft
+    verification).  A code side is row-major (bs, nh_k, T_cap, M) when its page ids are None, else a page pool (K
+    (n_pool, page_size, M), V (n_pool, M, page_size)).  q, k_chunk, v_chunk and out may be strided (rows of d contiguous
+    elements); the default out is token-major under the (bs, nh, n_q, d) shape, as prefill_attn's.  Nothing is written
+    but `out`: storing the chunk in the cache is the caller's (DynamicPQCache.extend / PagedPQCache.extend)."""
+    _need_cuda(q, k_chunk, v_chunk, k_codes, v_codes, k_prep, v_prep, k_res, v_res, k_page_ids, v_page_ids, out, workspace)
+    if q.dtype != torch.float16 or k_res.dtype != torch.float16 or v_res.dtype != torch.float16:
+        raise RuntimeError("pq_chunk_attn: q and window buffers must be fp16")
+    if k_codes.dtype != torch.uint8 or v_codes.dtype != torch.uint8:
+        raise RuntimeError("pq_chunk_attn: codes must be uint8")
+    if q.dim() != 4:
+        raise RuntimeError("pq_chunk_attn: q must be (bs, nh, n_q, d)")
+    bs, nh, n_q, d = q.shape
+    if (k_res.dim() != 4 or k_res.shape != v_res.shape or k_res.stride() != v_res.stride() or k_res.stride(3) != 1
+            or k_res.stride(2) != d or k_res.shape[0] != bs or k_res.shape[3] != d):
+        raise RuntimeError("pq_chunk_attn: window buffers must be (bs, nh_k, cap, d), share shape / strides, dense rows")
+    nh_k = k_res.shape[1]
+    fix = lambda t: t if (t.stride(3) == 1 and all(s_ % 8 == 0 for s_ in t.stride()[:3])) else t.contiguous()
+    q = fix(q)
+    n_c = 0
+    if k_chunk is not None or v_chunk is not None:
+        if k_chunk is None or v_chunk is None:
+            raise RuntimeError("pq_chunk_attn: k_chunk and v_chunk go together")
+        if k_chunk.dtype != torch.float16 or v_chunk.dtype != torch.float16:
+            raise RuntimeError("pq_chunk_attn: chunk K/V must be fp16")
+        if k_chunk.shape != (bs, nh_k, n_q, d) or v_chunk.shape != k_chunk.shape:
+            raise RuntimeError(f"pq_chunk_attn: chunk K/V must be (bs, nh_k, n_q, d) = {(bs, nh_k, n_q, d)}, got "
+                               f"{tuple(k_chunk.shape)} {tuple(v_chunk.shape)}")
+        k_chunk, v_chunk = fix(k_chunk), fix(v_chunk)
+        n_c = n_q
+    k_paged, v_paged = k_page_ids is not None, v_page_ids is not None
+    n_pages_cap, ids64 = 0, False
+    for ids in (k_page_ids, v_page_ids):
+        if ids is None:
+            continue
+        if ids.dtype not in (torch.int32, torch.int64) or not ids.is_contiguous() or ids.dim() != 3 or ids.shape[:2] != (bs, nh_k):
+            raise RuntimeError("pq_chunk_attn: page ids must be contiguous int32/int64 (bs, nh_k, n_pages)")
+        if n_pages_cap and (ids.shape[2] != n_pages_cap or (ids.dtype == torch.int64) != ids64):
+            raise RuntimeError("pq_chunk_attn: K and V page ids must agree in dtype and length")
+        n_pages_cap, ids64 = ids.shape[2], ids.dtype == torch.int64
+    if (k_paged or v_paged) and page_size is None:
+        raise RuntimeError("pq_chunk_attn: paged codes need page_size")
+    for name, codes, paged in (("k_codes", k_codes, k_paged), ("v_codes", v_codes, v_paged)):
+        if paged:
+            if not codes.is_contiguous() or codes.dim() != 3:
+                raise RuntimeError(f"pq_chunk_attn: {name} page pool must be contiguous (n_pool, ., .)")
+        else:
+            if codes.dim() != 4 or codes.shape[3] != M or codes.shape[:2] != (bs, nh_k):
+                raise RuntimeError(f"pq_chunk_attn: {name} must be (bs, nh_k, T, M)")
+            if codes.shape[2] and (codes.stride(3) != 1 or codes.stride(2) != M):
+                raise RuntimeError(f"pq_chunk_attn: {name} rows must be dense (stride M)")
+            if n_tokens > codes.shape[2]:
+                raise RuntimeError(f"pq_chunk_attn: n_tokens exceeds {name}")
+    if not 0 <= r <= k_res.shape[2]:
+        raise RuntimeError(f"pq_chunk_attn: r={r} outside [0, {k_res.shape[2]}]")
+    if out is None:
+        out = torch.empty(bs, n_q, nh, d, dtype=torch.float16, device=q.device).transpose(1, 2)
+    elif out.shape != (bs, nh, n_q, d) or out.dtype != torch.float16 or out.stride(3) != 1:
+        raise RuntimeError("pq_chunk_attn: out must be fp16 (bs, nh, n_q, d) with contiguous rows")
+    desc = chunk_attn_desc(q, k_res, nh_k=nh_k, M=M, C=C, n_tokens=int(n_tokens), r=int(r), n_c=n_c,
+                           resid_start=int(resid_start), k_paged=k_paged, v_paged=v_paged, page_size=int(page_size or 0),
+                           n_pages_cap=n_pages_cap, page_ids_i64=ids64, k_codes=k_codes, v_codes=v_codes, k_chunk=k_chunk,
+                           v_chunk=v_chunk, out=out)
+    lib = L.load()
+    need = lib.million_chunk_attn_workspace_bytes(ctypes.byref(desc))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=q.device) if need else None
+    L.check(lib.million_pq_chunk_attn(ctypes.byref(desc), q.data_ptr(), _ptr(k_chunk), _ptr(v_chunk), k_codes.data_ptr(),
+                                      v_codes.data_ptr(), _ptr(k_page_ids), _ptr(v_page_ids), k_prep.data_ptr(), v_prep.data_ptr(),
+                                      k_res.data_ptr(), v_res.data_ptr(), out.data_ptr(), _ptr(workspace),
+                                      0 if workspace is None else workspace.numel(), _stream()), "million_pq_chunk_attn")
+    return out

@@ -240,7 +240,8 @@ class DynamicPQCache(_CacheBase):
 
     def prefill(self, query_states, key_states, value_states, layer_idx, distort_recent=False):
         """distort_recent=True attends to the DEQUANTISED prompt (perplexity-style evaluation of the quantiser,
-        pq_utils.py:222-260 docstring); leave it False when serving."""
+        pq_utils.py:222-260 docstring); leave it False when serving.  The attention sees the prompt only: on a cache that
+        already holds tokens use extend()."""
         n = key_states.size(2)
         T0 = self._T[layer_idx]
         self._append_codes((key_states, value_states), layer_idx, n)       # pq_utils.py:235-240
@@ -253,7 +254,8 @@ class DynamicPQCache(_CacheBase):
     def update(self, key_states, value_states, layer_idx, distort_recent=False):
         """The reference's non-kernel path (pq_utils.py:166-220), DynamicCache-compatible: encode and store the new
         K/V, return the full-length fp16 K/V for a dense attention — the dequantised past followed by the new rows
-        as they are (or dequantised too with distort_recent).  No residual window on this path (as in the reference)."""
+        as they are (or dequantised too with distort_recent).  No residual window on this path (as in the reference).
+        A block of new tokens on a cache that is not empty is served without the fp16 past by extend()."""
         n = key_states.size(2)
         T0 = self._T[layer_idx]
         self._append_codes((key_states, value_states), layer_idx, n)
@@ -298,6 +300,30 @@ class DynamicPQCache(_CacheBase):
                                   self._vprep, self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx],
                                   r, M=self.M, C=self.C, n_tokens=self._T[layer_idx], k_new=key_states,
                                   v_new=value_states, workspace=self._ws)
+
+    def extend(self, query_states, key_states, value_states, layer_idx):
+        """n new tokens of one layer on a cache that may already hold tokens (a later turn of a conversation, the next chunk
+        of a prompt): returns their attention over [the PQ codes; the residual window; the new rows, causally]
+        (million_pq_chunk_attn: the past is read as codes, never as fp16), then leaves the cache as prefill() of the
+        whole sequence would have - the window rows and then the new rows are encoded behind T, the window is empty.
+        On an empty cache this is prefill()."""
+        if self.nbits > 8:
+            raise NotImplementedError("extend: uint8 codes only (the chunk-attention kernel reads uint8 codes)")
+        T, r = self._T[layer_idx], self.residualed_tokens[layer_idx]
+        if T == 0 and r == 0:
+            return self.prefill(query_states, key_states, value_states, layer_idx)
+        n = key_states.size(2)
+        kres, vres = self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx]
+        out = ops.pq_chunk_attn(query_states, key_states, value_states, self._k_store[layer_idx], self._v_store[layer_idx],
+                                self._kprep, self._vprep, kres, vres, r, M=self.M, C=self.C, n_tokens=T)
+        if T + r + n > self.max_tokens:
+            raise RuntimeError(f"DynamicPQCache: {T + r + n} tokens exceed max_tokens={self.max_tokens}")
+        if r:
+            self._append_codes((kres, vres), layer_idx, r)
+        self._append_codes((key_states, value_states), layer_idx, n)
+        self.residualed_tokens[layer_idx] = 0
+        self.seen_tokens[layer_idx] += n
+        return out
 
     @property
     def pq_cache_size(self):
@@ -437,22 +463,24 @@ class PagedPQCache(_CacheBase):
         rows = np.stack([self._T_a[layer_idx], self._r_a[layer_idx], self._rs_a[layer_idx], np.zeros(self.bs, dtype=np.int64)], axis=1)
         self.lengths[layer_idx].copy_(torch.from_numpy(rows.astype(np.int32)))
 
-    def _encode_to_pages(self, K, V, layer_idx, n, *, b=None):
+    def _encode_to_pages(self, K, V, layer_idx, n, *, b=None, x_row_start=0, x_row_mod=0):
         """Encode n rows of K, V (bs or 1, nh_k, n, d) behind the T quantised tokens of every request (b = None: requests
-        in lockstep) or of request b."""
+        in lockstep) or of request b.  x_row_mod > 0: K, V are rings of x_row_mod rows read from x_row_start on."""
         sel = slice(None) if b is None else slice(b, b + 1)
         T = int(self._T_a[layer_idx, 0 if b is None else b])
         if not self.preallocate:
             self._assign_pages(layer_idx, (T + n + self.page_size - 1) // self.page_size, b)
         elif T + n > self.max_tokens:
             raise RuntimeError(f"PagedPQCache: {T + n} tokens exceed max_tokens={self.max_tokens}")
-        kw = dict(token_start=T, n=n, page_ids=self.page_ids[layer_idx][sel], page_size=self.page_size)
+        kw = dict(token_start=T, n=n, page_ids=self.page_ids[layer_idx][sel], page_size=self.page_size,
+                  x_row_start=x_row_start, x_row_mod=x_row_mod)
         ops.pq_encode_into(K, self.key_cent, self.key_page_pool, layout=L.MILLION_CODES_KPAGES, prepared=self._kprep, **kw)
         ops.pq_encode_into(V, self.value_cent, self.value_page_pool, layout=L.MILLION_CODES_VPAGES, prepared=self._vprep, **kw)
 
     def prefill(self, query_states, key_states, value_states, layer_idx, distort_recent=False):
         """Bulk encode of the prompt straight into pages (reference paged_pq_utils.py:216-320: encode,
-        torch.cat, per-page permute+contiguous); the residual window stays empty."""
+        torch.cat, per-page permute+contiguous); the residual window stays empty.  The attention sees the
+        prompt only: on a cache that already holds tokens use extend()."""
         if not self._lockstep(layer_idx):
             raise RuntimeError("PagedPQCache.prefill: requests are at different lengths; use prefill_request(b, ...)")
         n = key_states.size(2)
@@ -473,6 +501,77 @@ class PagedPQCache(_CacheBase):
         self._seen_a[layer_idx, b] += n
         self._sync_lengths(layer_idx)
         return self._prefill_attention(query_states, key_states, value_states)
+
+    # ---- extend: a block of new tokens behind the cached ones ------------------------------------------------------------
+    def _join_side(self, layer_idx, b=None):
+        """Before extend touches a layer: its pending side-stream flush (flush_ahead) is issued and waited for, and window rows
+        encoded ahead (begin_step) are complete.  extend encodes every window row again - rows encoded ahead get the same codes
+        in the same pages - so the encoded-ahead flag of the layer (of request b) is cleared."""
+        if getattr(self, "_ahead", None) is not None and layer_idx in self._ahead[0]:
+            self._ahead_issue(upto_layer=layer_idx)
+        ev = self._flush_events.pop(layer_idx, None) if self._side is not None else None
+        if ev is not None:
+            torch.cuda.current_stream().wait_event(ev)
+        if self._side is not None and self._pre_join:
+            torch.cuda.current_stream().wait_stream(self._side)
+        if b is None:
+            self._pre_a[layer_idx] = 0
+        else:
+            self._pre_a[layer_idx, b] = 0
+
+    def _extend_slot(self, query_states, key_states, value_states, layer_idx, b):
+        """b = None: every request (lockstep); else request b with batch-1 tensors."""
+        i = 0 if b is None else b
+        sel = slice(None) if b is None else slice(b, b + 1)
+        T, r, rs = int(self._T_a[layer_idx, i]), int(self._r_a[layer_idx, i]), int(self._rs_a[layer_idx, i])
+        n = key_states.size(2)
+        if T + r + n > self.max_tokens:
+            raise RuntimeError(f"PagedPQCache: {T + r + n} tokens exceed max_tokens={self.max_tokens}")
+        kres, vres = self.key_residual_cache[layer_idx][sel], self.value_residual_cache[layer_idx][sel]
+        ids = self.page_ids[layer_idx][sel]
+        out = ops.pq_chunk_attn(query_states, key_states, value_states, self.key_page_pool, self.value_page_pool, self._kprep,
+                                self._vprep, kres, vres, r, M=self.M, C=self.C, n_tokens=T, resid_start=rs, k_page_ids=ids,
+                                v_page_ids=ids, page_size=self.page_size)
+        cap = self.extended_residual_size
+        if r:      # the window in ring order, then the new rows: the codes prefill() of the whole sequence would have written
+            self._encode_to_pages(kres, vres, layer_idx, r, b=b, x_row_start=rs, x_row_mod=cap)
+            self._T_a[layer_idx, sel] += r
+        self._encode_to_pages(key_states, value_states, layer_idx, n, b=b)
+        self._T_a[layer_idx, sel] += n
+        self._r_a[layer_idx, sel] = 0
+        self._rs_a[layer_idx, sel] = 0
+        self._seen_a[layer_idx, sel] += n
+        return out
+
+    def extend(self, query_states, key_states, value_states, layer_idx):
+        """n new tokens of one layer, every request in lockstep (a later turn of the conversations, the next chunk of their
+        prompts): returns their attention over [the PQ codes in the pages; the residual window; the new rows, causally]
+        (million_pq_chunk_attn: the past is read as codes, never as fp16), then leaves the cache exactly as prefill() of
+        the whole sequence would have - the window rows (in ring order) and then the new rows are encoded into the pages
+        behind T, the window is emptied (r = 0, resid_start = 0), host and device lengths advance.  Pending encode-ahead
+        work of the layer (begin_step, flush_ahead) is joined first and its flags cleared: rows encoded ahead are encoded
+        again into the same pages with the same codes.  On an empty cache this is prefill()."""
+        if not self._lockstep(layer_idx):
+            raise RuntimeError("PagedPQCache.extend: requests are at different lengths; use extend_request(b, ...)")
+        self._join_side(layer_idx)
+        if self._T_a[layer_idx, 0] == 0 and self._r_a[layer_idx, 0] == 0:
+            return self.prefill(query_states, key_states, value_states, layer_idx)
+        out = self._extend_slot(query_states, key_states, value_states, layer_idx, None)
+        self._sync_lengths(layer_idx)
+        return out
+
+    def extend_request(self, b, query_states, key_states, value_states, layer_idx):
+        """extend() for ONE request (tensors of batch 1) in slot b; the other slots, their host and device lengths, are not
+        touched (they may keep decoding with use_dev_lengths=True).  On an empty slot this is prefill_request()."""
+        if key_states.size(0) != 1 or query_states.size(0) != 1:
+            raise RuntimeError("extend_request: tensors of batch 1")
+        self._join_side(layer_idx, b)
+        if self._T_a[layer_idx, b] == 0 and self._r_a[layer_idx, b] == 0:
+            return self.prefill_request(b, query_states, key_states, value_states, layer_idx)
+        out = self._extend_slot(query_states, key_states, value_states, layer_idx, b)
+        row = [int(self._T_a[layer_idx, b]), 0, 0, 0]
+        self.lengths[layer_idx][b].copy_(torch.tensor(row, dtype=torch.int32))
+        return out
 
     def release(self, b):
         """Request b has finished: its pages go back to the PageManager (on-demand paging; a preallocated table keeps its
@@ -510,7 +609,8 @@ class PagedPQCache(_CacheBase):
     def update(self, key_states, value_states, layer_idx, distort_recent=False):
         """The reference's non-kernel path on the paged store (paged_pq_utils.py:322-339 -> pq_utils.py:166-220): encode and
         store the new K/V rows into pages, return the full-length fp16 K/V for a dense attention - the dequantised past
-        followed by the new rows as they are (or dequantised too with distort_recent).  No residual window on this path."""
+        followed by the new rows as they are (or dequantised too with distort_recent).  No residual window on this path.
+        extend() attends a block of new tokens to the codes and the window without the fp16 past."""
         if not self._lockstep(layer_idx) or self._r_a[layer_idx, 0]:
             raise RuntimeError("PagedPQCache.update: lockstep requests and an empty residual window expected")
         n = key_states.size(2)
