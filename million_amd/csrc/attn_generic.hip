@@ -168,17 +168,40 @@ __global__ __launch_bounds__(kGenBlock) void attn_generic_kernel(AttnParams p) {
     publish_and_merge(p, b, hk, slot, part, lut, flag);   // the LUT region is dead: merge scratch
 }
 
-int launch_attn_generic(const AttnParams &p, hipStream_t s) {
+// Split policy: about one workgroup per CU over all (b, hk); a split is a multiple of 64 tokens and at
+// least 256 tokens long (the reference picks Ns from the binding name, pq_utils.py:8-22; here the
+// split count is internal and the Ns of the name is ignored).
+static void choose_splits(AttnParams &p, int min_tokens) {
+    const int bh = p.bs * p.nh_k;
+    int ns = (device_cus() + bh - 1) / bh;
+    if (ns > kMaxSplits) ns = kMaxSplits;
+    int by_len = (p.T + min_tokens - 1) / min_tokens;
+    if (by_len < 1) by_len = 1;
+    if (ns > by_len) ns = by_len;
+    if (ns < 1) ns = 1;
+    int len = (p.T + ns - 1) / ns;
+    len = (len + 63) / 64 * 64;
+    if (len < 64) len = 64;
+    ns = p.T > 0 ? (p.T + len - 1) / len : 1;
+    p.nsplit = ns;
+    p.split_len = len;
+}
+
+static void generic_setup() {
+    if (device_once(0))
+        (void)hipFuncSetAttribute((const void *)attn_generic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+}
+
+int plan_attn_generic(const AttnParams &p_in, AttnPlan &plan) {
+    AttnParams p = p_in;
+    plan.kind = 0;
     const size_t lds = sizeof(float) * ((size_t)p.M * p.C + kGenChunk + (p.G * p.d + 2 * p.G + 3) / 4 * 4 +
                                         kGenBlock + 8 + p.d) + 16;
     if (kGenBlock % p.d != 0) { set_error("generic kernel: d=%d must divide %d", p.d, kGenBlock); return MILLION_ERR_SHAPE; }
     if (lds > 160 * 1024) { set_error("generic kernel: LUT of M*C=%d floats does not fit LDS", p.M * p.C); return MILLION_ERR_SHAPE; }
-    if (device_once(0))
-        (void)hipFuncSetAttribute((const void *)attn_generic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    dim3 grid(p.nsplit + 1, p.bs * p.nh_k);
-    hipLaunchKernelGGL(attn_generic_kernel, grid, dim3(kGenBlock), lds, s, p);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("attn_generic launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
+    choose_splits(p, 256);
+    p.nslots = p.nsplit + 1;
+    plan = {(const void *)attn_generic_kernel, dim3(p.nslots, p.bs * p.nh_k), dim3(kGenBlock), lds, p, 0, generic_setup};
     return MILLION_OK;
 }
 

@@ -2095,7 +2095,7 @@ int launch_rows_reduce_check(const float *in, float *out_max, float *out_sum, hi
 
 // A split takes every nsplit-th window row and has kNW * kResRows = 128 slots for them in its waves' residual tiles:
 // windows of up to 128 rows work with any split count, longer ones (extended_residual_size 256, the reference's
-// flash_decoding_paged_v_*_Lt256 names) get at least ceil(rcap / 128) splits (launch_attn_mfma).
+// flash_decoding_paged_v_*_Lt256 names) get at least ceil(rcap / 128) splits (mfma_splits).
 // d = 64 with M = 32 / 16 (d_m = 2 / 4) and M = 64 (d_m = 1: run as d_m = 2 with every odd dim zero, attn_lean.h): the lean kernel
 // only (round 5; before: the tile kernel) - 256 centroids, up to 4 query heads per kv head
 static int g_mfma_policy = 0, g_tail_test = 0, g_lean_off = 0;      // A/B and test knobs: see set_mfma_policy below
@@ -2123,15 +2123,11 @@ static AttnParams mfma_virtual(const AttnParams &p_in) {      // the call as the
 static bool lean_d64_shape(const AttnParams &p) {
     return p.d == 64 && (p.M == 64 || p.M == 32 || p.M == 16) && (p.C == 256 || p.C == 128) && (p.G <= 4 || mfma_hparts(p) > 1) && p.rcap <= 4 * kNW * kResRows;
 }
-bool attn_mfma_shape_ok(const AttnParams &p) {
+static bool mfma_shape_ok(const AttnParams &p) {
     if (lean_d64_shape(p)) return true;
     if (p.d == 128 && p.M == 16)      // d_m = 8 form of the streaming kernel (round 4): up to 4 query heads per kv head (6 .. 16: as parts)
         return (p.C == 256 || p.C == 128) && (p.G <= 4 || mfma_hparts(p) > 1) && p.rcap <= 4 * kNW * kResRows;
     return p.d == 128 && (p.M == 64 || p.M == 32) && (p.C == 256 || p.C == 128) && p.G <= kMaxGMfma && p.rcap <= 4 * kNW * kResRows;
-}
-
-bool attn_mfma_supported(const AttnParams &p) {
-    return attn_mfma_shape_ok(p) && p.v_paged && (p.page_size == 32 || p.page_size == 64 || p.page_size == 128);
 }
 
 // host side of g_tail_faults: waits for the device, returns and clears the count (-1: the runtime refused)
@@ -2143,7 +2139,8 @@ int read_tail_faults() {
     return (int)n;
 }
 
-// A/B knob (million_set_force_generic 2): 0 = auto (streaming kernel wherever it applies), 1 = grouped kernel only
+// A/B knob (million_set_force_generic 2): 0 = auto (streaming kernel wherever it applies), 1 = grouped kernel only (C = 128 has
+// no grouped form: the streaming kernel still runs there)
 // g_tail_test (million_set_force_generic 4 / 8): the merge helpers give up at once - the last arriver's take-over path, for
 // tests: 1 = every give-up bit is set in the prologue, 2 = the helpers give up through the real path (no polls, then the atomic)
 // g_lean_off (million_set_force_generic 16): the lean kernel's shapes stay on the streaming kernel (A/B, tests of the parity-V form)
@@ -2153,8 +2150,7 @@ static const int g_mfma_form = MILLION_DEV_M32_PACKED();
 void set_mfma_policy(int policy) { g_mfma_policy = policy & 1; g_tail_test = (policy >> 1) & 3; g_lean_off = (policy >> 3) & 1; }
 
 // split policy: about one workgroup per CU; a split is at least 512 tokens long
-static int mfma_splits(const AttnParams &p) {
-    const int cus = device_cus();
+static int mfma_splits(const AttnParams &p, int cus) {
     const int bh = p.bs * p.nh_k;
     int ns = (cus + bh - 1) / bh;
     if (ns > kMaxSplits) ns = kMaxSplits;
@@ -2183,155 +2179,88 @@ static int mfma_splits(const AttnParams &p) {
 // streaming kernel: rounds per wave = ceil(T / (ns * 256 tokens)) must fit the 64 page ids a wave preloads
 static bool mfma_stream_ok(const AttnParams &p, int ns) { return p.T > 0 && (p.T + ns * 256 - 1) / (ns * 256) <= 64; }
 
-// C = 128 runs on the streaming kernel only: without it (T = 0, more than 1M tokens) the call goes back to the caller
-// the lean kernel takes the call (launch_attn_mfma): pages of 64 / 128 tokens, streaming policy
-static bool lean_takes(const AttnParams &p_in) {
-    if (!attn_mfma_supported(p_in)) return false;
-    const AttnParams p = mfma_virtual(p_in);
-    return (p.C == 256 || p.C == 128) && p.G <= 4 && p.page_size >= 64 && !g_lean_off && g_mfma_policy == 0 &&
-           mfma_stream_ok(p, mfma_splits(p)) && (p.d == 64 || (p.M == 64 || (p.M == 32 && !(g_mfma_form & 1))));
-}
-bool attn_mfma_handles(const AttnParams &p) {
-    if (p.d == 64) return lean_takes(p);      // no other MFMA kernel of this file takes d = 64: the caller goes on to the tile kernel
-    if (p.M == 16) {      // streaming kernel or not at all
-        if (!attn_mfma_supported(p) || g_mfma_policy != 0) return false;
-        const AttnParams pv = mfma_virtual(p);
-        return mfma_stream_ok(pv, mfma_splits(pv));
-    }
-    return attn_mfma_supported(p) && (p.C != 128 || mfma_stream_ok(p, mfma_splits(p)));
-}
-// the call will run the STREAMING kernel (not the grouped fallback): million_attn_kernel_kind
-bool attn_mfma_streams(const AttnParams &p) {
-    if (p.d == 64) return lean_takes(p);
-    if (!attn_mfma_supported(p) || g_mfma_policy != 0) return false;
-    const AttnParams pv = mfma_virtual(p);
-    return mfma_stream_ok(pv, mfma_splits(pv));
+// The instances this file launches, by form and layout mode (0: paged K with int32 ids and V through its id table, 1: row-major
+// K with dense V pages, 2: anything else).  The C = 128 forms and the grouped kernel have one instance for every mode.  The rows
+// keep the order in which the instances were first named before this table: it is their order in the code object.
+enum MfmaForm {
+    kGrouped64, kGrouped64NoCodes, kGrouped32, kGrouped32NoCodes,       // grouped kernel (NoCodes: T = 0)
+    kStream64, kStream32, kStream32D4, kStream16,                       // streaming kernel (D4: the d_m = 4 form of M = 32; M = 16: d_m = 8)
+    kStream16C128, kStream64C128, kStream32C128,
+    kLean64, kLean64C128, kLean32, kLean32C128,                         // lean kernel, d = 128
+    kLeanD64M32, kLeanD64M16, kLeanD64M64,                              // lean kernel, d = 64
+    kMfmaForms
+};
+#define MFMA_ONE(...) {(const void *)__VA_ARGS__, (const void *)__VA_ARGS__, (const void *)__VA_ARGS__}
+static const void *const kMfmaKernels[kMfmaForms][3] = {
+    MFMA_ONE(attn_mfma_kernel<true>),
+    MFMA_ONE(attn_mfma_kernel<false>),
+    MFMA_ONE(attn_mfma_kernel<true, 32>),
+    MFMA_ONE(attn_mfma_kernel<false, 32>),
+    {(const void *)attn_stream_kernel<64, 0>, (const void *)attn_stream_kernel<64, 1>, (const void *)attn_stream_kernel<64, 2>},
+    {(const void *)attn_stream_kernel<32, 0>, (const void *)attn_stream_kernel<32, 1>, (const void *)attn_stream_kernel<32, 2>},
+    {(const void *)attn_stream_kernel<320, 0>, (const void *)attn_stream_kernel<320, 1>, (const void *)attn_stream_kernel<320, 2>},
+    {(const void *)attn_stream_kernel<16, 0>, (const void *)attn_stream_kernel<16, 1>, (const void *)attn_stream_kernel<16, 2>},
+    MFMA_ONE(attn_stream_kernel<16, 2, 7>),
+    MFMA_ONE(attn_stream_kernel<64, 2, 7>),
+    MFMA_ONE(attn_stream_kernel<32, 2, 7>),
+    {(const void *)attn_lean_kernel<0>, (const void *)attn_lean_kernel<1>, (const void *)attn_lean_kernel<2>},
+    MFMA_ONE(attn_lean_kernel<2, 64, 128, 128, 1>),
+    {(const void *)attn_lean_kernel<0, 32>, (const void *)attn_lean_kernel<1, 32>, (const void *)attn_lean_kernel<2, 32>},
+    MFMA_ONE(attn_lean_kernel<2, 32, 128, 128, 1>),
+    {(const void *)attn_lean_kernel<0, 32, 64, 64, 3>, (const void *)attn_lean_kernel<1, 32, 64, 64, 3>, (const void *)attn_lean_kernel<2, 32, 64, 64, 3>},
+    {(const void *)attn_lean_kernel<0, 16, 64, 64, 3>, (const void *)attn_lean_kernel<1, 16, 64, 64, 3>, (const void *)attn_lean_kernel<2, 16, 64, 64, 3>},
+    {(const void *)attn_lean_kernel<0, 64, 128, 64, 3>, (const void *)attn_lean_kernel<1, 64, 128, 64, 3>, (const void *)attn_lean_kernel<2, 64, 128, 64, 3>},
+};
+#undef MFMA_ONE
+static void mfma_setup() {
+    if (device_once(1))
+        for (const auto &form : kMfmaKernels)
+            for (const void *k : form) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
 }
 
-int launch_attn_mfma(const AttnParams &p_in, hipStream_t s) {
+bool plan_attn_mfma(const AttnParams &p_in, AttnPlan &plan) {
+    if (!p_in.v_paged || !mfma_shape_ok(p_in)) return false;
     AttnParams p = mfma_virtual(p_in);      // (the identity unless the shape runs as head parts)
+    const int cus = device_cus();
+    const int ns = mfma_splits(p, cus);
+    const bool stream_ok = mfma_stream_ok(p, ns);
+    // lean kernel (round 5): 64-token units, lane = token; C = 256 and (its table copy spreads the K rows) C = 128
+    const bool lean = g_mfma_policy == 0 && stream_ok && p.G <= 4 && p.page_size >= 64 && !g_lean_off;
+    int form;
+    if (p.d == 64) {              // the lean kernel or none of this file's (the caller's next choice: the tile kernel)
+        if (!lean) return false;
+        form = p.M == 64 ? kLeanD64M64 : p.M == 32 ? kLeanD64M32 : kLeanD64M16;
+    } else if (p.M == 16) {       // d_m = 8 form: the streaming kernel or the tile kernel
+        if (!stream_ok || g_mfma_policy != 0) return false;
+        form = p.C == 128 ? kStream16C128 : kStream16;
+    } else if (lean && (p.M == 64 || !(g_mfma_form & 1))) {
+        form = p.M == 64 ? (p.C == 128 ? kLean64C128 : kLean64) : (p.C == 128 ? kLean32C128 : kLean32);
+    } else if (p.C == 128) {      // 128 centroids per subspace (reference setup.py:15): streaming kernel by run-time layout flags only
+        if (!stream_ok) return false;      // T = 0 or more than 64 rounds per wave: the tile kernel
+        form = p.M == 64 ? kStream64C128 : kStream32C128;
+    } else if (g_mfma_policy == 0 && stream_ok) {
+        // d_m = 4 form at M = 32 and up to 4 query heads: query heads replicated over the column groups of the score tile
+        form = p.M == 64 ? kStream64 : (p.G <= 4 && !(g_mfma_form & 1)) ? kStream32D4 : kStream32;
+    } else {
+        form = p.M == 64 ? (p.T > 0 ? kGrouped64 : kGrouped64NoCodes) : (p.T > 0 ? kGrouped32 : kGrouped32NoCodes);
+    }
+    const int mode = (p.k_paged && !p.v_identity && !p.ids64) ? 0 : (!p.k_paged && p.v_identity) ? 1 : 2;
     const int bh = p.bs * p.nh_k;
-    const int ns = mfma_splits(p);
     const int units = p.T > 0 ? (p.T + 31) / 32 : 1;
-    int len = 32 * ((units + ns - 1) / ns);
     p.nsplit = ns;
     p.nslots = ns;
-    p.split_len = len;
+    p.split_len = 32 * ((units + ns - 1) / ns);
     // mergers per (b, kv head): helpers only when every workgroup of the launch is resident at once (one per CU); a helper
     // that still cannot see its flags gives up and the last arriver takes over (merge_and_publish)
-    {
-        int nm = p.G < ns ? p.G : ns;
-        if (nm > 8) nm = 8;
-        p.nmerge = (long long)bh * ns <= device_cus() ? (nm > 0 ? nm : 1) : 1;
-        p.tail_test = g_tail_test;
+    int nm = p.G < ns ? p.G : ns;
+    if (nm > 8) nm = 8;
+    p.nmerge = (long long)bh * ns <= cus ? (nm > 0 ? nm : 1) : 1;
+    p.tail_test = g_tail_test;
 #if MILLION_EXP & 2
-        p.nmerge = 1;      // A/B: the primary alone
+    p.nmerge = 1;      // A/B: the primary alone
 #endif
-    }
-    if (device_once(1)) {
-        (void)hipFuncSetAttribute((const void *)attn_mfma_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_mfma_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_mfma_kernel<true, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_mfma_kernel<false, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_stream_kernel<64, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_stream_kernel<64, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_stream_kernel<64, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_stream_kernel<32, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_stream_kernel<32, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_stream_kernel<32, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_stream_kernel<320, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_stream_kernel<320, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_stream_kernel<320, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_stream_kernel<16, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_stream_kernel<16, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_stream_kernel<16, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_stream_kernel<16, 2, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_stream_kernel<64, 2, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_stream_kernel<32, 2, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_lean_kernel<0, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_lean_kernel<1, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_lean_kernel<2, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_lean_kernel<2, 64, 128, 128, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_lean_kernel<0, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_lean_kernel<1, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_lean_kernel<2, 32>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_lean_kernel<2, 32, 128, 128, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_lean_kernel<0, 32, 64, 64, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_lean_kernel<1, 32, 64, 64, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_lean_kernel<2, 32, 64, 64, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_lean_kernel<0, 16, 64, 64, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_lean_kernel<1, 16, 64, 64, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_lean_kernel<2, 16, 64, 64, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_lean_kernel<0, 64, 128, 64, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_lean_kernel<1, 64, 128, 64, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute((const void *)attn_lean_kernel<2, 64, 128, 64, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    }
-    const bool stream_ok = mfma_stream_ok(p, ns);
-    const int mode = (p.k_paged && !p.v_identity && !p.ids64) ? 0 : (!p.k_paged && p.v_identity) ? 1 : 2;
-    const dim3 grid(ns, bh), block(kNW * 64);
-    if (p.d == 64) {       // lean kernel or nothing of this file (the caller's next choice: the tile kernel)
-        if (!lean_takes(p_in)) return kAttnNotHandled;
-        if (p.M == 64) {
-            if (mode == 0) hipLaunchKernelGGL((attn_lean_kernel<0, 64, 128, 64, 3>), grid, block, kLdsBytes, s, p);
-            else if (mode == 1) hipLaunchKernelGGL((attn_lean_kernel<1, 64, 128, 64, 3>), grid, block, kLdsBytes, s, p);
-            else hipLaunchKernelGGL((attn_lean_kernel<2, 64, 128, 64, 3>), grid, block, kLdsBytes, s, p);
-        } else if (p.M == 32) {
-            if (mode == 0) hipLaunchKernelGGL((attn_lean_kernel<0, 32, 64, 64, 3>), grid, block, kLdsBytes, s, p);
-            else if (mode == 1) hipLaunchKernelGGL((attn_lean_kernel<1, 32, 64, 64, 3>), grid, block, kLdsBytes, s, p);
-            else hipLaunchKernelGGL((attn_lean_kernel<2, 32, 64, 64, 3>), grid, block, kLdsBytes, s, p);
-        } else {
-            if (mode == 0) hipLaunchKernelGGL((attn_lean_kernel<0, 16, 64, 64, 3>), grid, block, kLdsBytes, s, p);
-            else if (mode == 1) hipLaunchKernelGGL((attn_lean_kernel<1, 16, 64, 64, 3>), grid, block, kLdsBytes, s, p);
-            else hipLaunchKernelGGL((attn_lean_kernel<2, 16, 64, 64, 3>), grid, block, kLdsBytes, s, p);
-        }
-    } else
-    if (p.M == 16) {       // d_m = 8 form: the streaming kernel or the tile kernel (the caller's next choice)
-        if (!stream_ok || g_mfma_policy != 0) return kAttnNotHandled;
-        if (p.C == 128) hipLaunchKernelGGL((attn_stream_kernel<16, 2, 7>), grid, block, kLdsBytes, s, p);
-        else if (mode == 0) hipLaunchKernelGGL((attn_stream_kernel<16, 0>), grid, block, kLdsBytes, s, p);
-        else if (mode == 1) hipLaunchKernelGGL((attn_stream_kernel<16, 1>), grid, block, kLdsBytes, s, p);
-        else hipLaunchKernelGGL((attn_stream_kernel<16, 2>), grid, block, kLdsBytes, s, p);
-    } else
-    // lean kernel (round 5): 64-token units, lane = token; C = 256 and (its table copy spreads the K rows) C = 128
-    if (g_mfma_policy == 0 && stream_ok && p.M == 64 && p.G <= 4 && p.page_size >= 64 && !g_lean_off) {
-        if (p.C == 128) hipLaunchKernelGGL((attn_lean_kernel<2, 64, 128, 128, 1>), grid, block, kLdsBytes, s, p);
-        else if (mode == 0) hipLaunchKernelGGL((attn_lean_kernel<0>), grid, block, kLdsBytes, s, p);
-        else if (mode == 1) hipLaunchKernelGGL((attn_lean_kernel<1>), grid, block, kLdsBytes, s, p);
-        else hipLaunchKernelGGL((attn_lean_kernel<2>), grid, block, kLdsBytes, s, p);
-    } else if (g_mfma_policy == 0 && stream_ok && p.M == 32 && p.G <= 4 && p.page_size >= 64 && !g_lean_off && !(g_mfma_form & 1)) {      // d_m = 4
-        if (p.C == 128) hipLaunchKernelGGL((attn_lean_kernel<2, 32, 128, 128, 1>), grid, block, kLdsBytes, s, p);
-        else if (mode == 0) hipLaunchKernelGGL((attn_lean_kernel<0, 32>), grid, block, kLdsBytes, s, p);
-        else if (mode == 1) hipLaunchKernelGGL((attn_lean_kernel<1, 32>), grid, block, kLdsBytes, s, p);
-        else hipLaunchKernelGGL((attn_lean_kernel<2, 32>), grid, block, kLdsBytes, s, p);
-    } else
-    if (p.C == 128) {      // 128 centroids per subspace (reference setup.py:15): streaming kernel by run-time layout flags only
-        if (!stream_ok) return kAttnNotHandled;      // T = 0 or more than 64 rounds per wave: the caller takes the generic kernel
-        if (p.M == 64) hipLaunchKernelGGL((attn_stream_kernel<64, 2, 7>), grid, block, kLdsBytes, s, p);
-        else hipLaunchKernelGGL((attn_stream_kernel<32, 2, 7>), grid, block, kLdsBytes, s, p);
-    } else if (g_mfma_policy == 0 && stream_ok) {
-        if (p.M == 64) {
-            if (mode == 0) hipLaunchKernelGGL((attn_stream_kernel<64, 0>), grid, block, kLdsBytes, s, p);
-            else if (mode == 1) hipLaunchKernelGGL((attn_stream_kernel<64, 1>), grid, block, kLdsBytes, s, p);
-            else hipLaunchKernelGGL((attn_stream_kernel<64, 2>), grid, block, kLdsBytes, s, p);
-        } else if (p.G <= 4 && !(g_mfma_form & 1)) {      // d_m = 4 form: query heads replicated over the column groups of the score tile
-            if (mode == 0) hipLaunchKernelGGL((attn_stream_kernel<320, 0>), grid, block, kLdsBytes, s, p);
-            else if (mode == 1) hipLaunchKernelGGL((attn_stream_kernel<320, 1>), grid, block, kLdsBytes, s, p);
-            else hipLaunchKernelGGL((attn_stream_kernel<320, 2>), grid, block, kLdsBytes, s, p);
-        } else {
-            if (mode == 0) hipLaunchKernelGGL((attn_stream_kernel<32, 0>), grid, block, kLdsBytes, s, p);
-            else if (mode == 1) hipLaunchKernelGGL((attn_stream_kernel<32, 1>), grid, block, kLdsBytes, s, p);
-            else hipLaunchKernelGGL((attn_stream_kernel<32, 2>), grid, block, kLdsBytes, s, p);
-        }
-    } else if (p.M == 32) {
-        if (p.T > 0) hipLaunchKernelGGL((attn_mfma_kernel<true, 32>), dim3(ns, bh), dim3(kNW * 64), kLdsBytes, s, p);
-        else hipLaunchKernelGGL((attn_mfma_kernel<false, 32>), dim3(ns, bh), dim3(kNW * 64), kLdsBytes, s, p);
-    } else if (p.T > 0)
-        hipLaunchKernelGGL(attn_mfma_kernel<true>, dim3(ns, bh), dim3(kNW * 64), kLdsBytes, s, p);
-    else
-        hipLaunchKernelGGL(attn_mfma_kernel<false>, dim3(ns, bh), dim3(kNW * 64), kLdsBytes, s, p);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("attn_mfma launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
-    return MILLION_OK;
+    plan = {kMfmaKernels[form][mode], dim3(ns, bh), dim3(kNW * 64), kLdsBytes, p, form <= kGrouped32NoCodes ? 5 : 1, mfma_setup};
+    return true;
 }
 
 }  // namespace million

@@ -1,5 +1,5 @@
 // attn_tile.hip — fused decode attention over PQ codes for the shapes the streaming kernel does not take:
-// d = 64 with M in {16, 32, 64}, d = 128 with M = 16, and whatever launch_attn_mfma hands back (attn_tile_supported),
+// d = 64 with M in {16, 32, 64}, d = 128 with M = 16, and whatever plan_attn_mfma declines (plan_attn_tile),
 // gfx950 / CDNA4.
 //
 // Same job and same single launch as attn_mfma.hip (reference: LUT matmul + flash_decoding_split_kernel +
@@ -37,7 +37,7 @@ typedef _Float16 t4f16 __attribute__((ext_vector_type(4)));
 typedef float t4f32 __attribute__((ext_vector_type(4)));
 typedef unsigned t4u __attribute__((ext_vector_type(4)));
 
-// Waves per workgroup (template parameter TW): see launch_attn_tile.  Only the residual-window workgroup uses LDS wave tiles.
+// Waves per workgroup (template parameter TW): see plan_attn_tile.  Only the residual-window workgroup uses LDS wave tiles.
 constexpr int kTT = 16;    // tokens per wave tile
 
 template <int D>
@@ -433,20 +433,22 @@ __global__ __launch_bounds__(TW * 64, TW / 4) void attn_tile_kernel(AttnParams p
     publish_and_merge(p, b, hk, slot, part, (float *)smem, flag);
 }
 
-bool attn_tile_supported(const AttnParams &p) {
-    const bool shape = (p.d == 128 || p.d == 64) && (p.M == 16 || p.M == 32 || p.M == 64) && (p.C == 128 || p.C == 256) &&
-                       p.G <= kMaxGMfma;      // the 16 columns of the score tile: up to 16 query heads per kv head and launch (round 4)
-    if (!shape || !p.v_paged) return false;
-    return tile_lds_bytes(p.d, p.C, p.slot_floats, 16, p.G) <= 160 * 1024;
-}
-bool attn_tile_shape_ok(const AttnParams &p) {
-    AttnParams q = p;
-    q.v_paged = 1;
-    return attn_tile_supported(q);
+// The instances, by d (128, 64) and M (16, 32, 64)
+static const void *const kTileKernels[2][3] = {
+    {(const void *)attn_tile_kernel<128, 8, 16>, (const void *)attn_tile_kernel<128, 4, 8>, (const void *)attn_tile_kernel<128, 2, 8>},
+    {(const void *)attn_tile_kernel<64, 4, 16>, (const void *)attn_tile_kernel<64, 2, 16>, (const void *)attn_tile_kernel<64, 1, 16>},
+};
+static void tile_setup() {
+    if (device_once(2))
+        for (const auto &d : kTileKernels)
+            for (const void *k : d) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
-int launch_attn_tile(const AttnParams &p_in, hipStream_t s) {
+bool plan_attn_tile(const AttnParams &p_in, AttnPlan &plan) {
     AttnParams p = p_in;
+    const bool shape = (p.d == 128 || p.d == 64) && (p.M == 16 || p.M == 32 || p.M == 64) && (p.C == 128 || p.C == 256) &&
+                       p.G <= kMaxGMfma;      // the 16 columns of the score tile: up to 16 query heads per kv head and launch (round 4)
+    if (!shape || !p.v_paged || tile_lds_bytes(p.d, p.C, p.slot_floats, 16, p.G) > 160 * 1024) return false;
     // Waves per workgroup (round 4: a code tile needs no LDS of its own any more, so the codebooks alone decide how many
     // workgroups fit - one per CU at d = 128 - and the registers how many waves: 16 where the kernel stays within 128
     // registers (d = 64; d = 128 with 16-byte entries), 8 otherwise).  More waves = fewer 16-token tiles per wave and more
@@ -470,28 +472,8 @@ int launch_attn_tile(const AttnParams &p_in, hipStream_t s) {
     p.split_len = len;
     p.nslots = ns + 1;
     const size_t lds = tile_lds_bytes(p.d, p.C, p.slot_floats, waves, p.G);
-    if (device_once(2)) {
-#define TILE_ATTR(D_, DM_, TW_) (void)hipFuncSetAttribute((const void *)attn_tile_kernel<D_, DM_, TW_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-        TILE_ATTR(128, 8, 16); TILE_ATTR(128, 4, 8); TILE_ATTR(128, 2, 8);
-        TILE_ATTR(64, 4, 16); TILE_ATTR(64, 2, 16); TILE_ATTR(64, 1, 16);
-#undef TILE_ATTR
-    }
-    const dim3 grid(p.nslots, bh), block(waves * 64);
-#define TILE_LAUNCH(D_, DM_, TW_) hipLaunchKernelGGL((attn_tile_kernel<D_, DM_, TW_>), grid, block, lds, s, p)
-    const int key = p.d * 16 + p.dm;
-    switch (key) {
-    case 128 * 16 + 8: TILE_LAUNCH(128, 8, 16); break;
-    case 128 * 16 + 4: TILE_LAUNCH(128, 4, 8); break;
-    case 128 * 16 + 2: TILE_LAUNCH(128, 2, 8); break;
-    case 64 * 16 + 4: TILE_LAUNCH(64, 4, 16); break;
-    case 64 * 16 + 2: TILE_LAUNCH(64, 2, 16); break;
-    case 64 * 16 + 1: TILE_LAUNCH(64, 1, 16); break;
-    default: set_error("attn_tile: d=%d d_m=%d", p.d, p.dm); return MILLION_ERR_SHAPE;
-    }
-#undef TILE_LAUNCH
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("attn_tile launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
-    return MILLION_OK;
+    plan = {kTileKernels[p.d == 64][p.M == 16 ? 0 : p.M == 32 ? 1 : 2], dim3(p.nslots, bh), dim3(waves * 64), lds, p, 3, tile_setup};
+    return true;
 }
 
 }  // namespace million

@@ -408,22 +408,26 @@ struct EncParams {
     const int *dev_lengths;
 };
 
-// host-side launchers (defined in the .hip files)
-int launch_attn_generic(const AttnParams &p, hipStream_t s);
-constexpr int kAttnNotHandled = 1;      // launch_attn_mfma: shape fine in principle, this call is for the generic kernel
-int launch_attn_mfma(const AttnParams &p, hipStream_t s);
-int launch_attn_tile(const AttnParams &p, hipStream_t s);
-bool attn_tile_supported(const AttnParams &p);   // shape taken by the tile kernel and V already in transposed pages
-bool attn_tile_shape_ok(const AttnParams &p);    // shape taken by the tile kernel once V is transposed
+// One decode-attention launch for one query-head group, as a planner fills it in; million_api.hip launches it (attn_impl)
+// or reports its kind (million_attn_kernel_kind).
+struct AttnPlan {
+    const void *kernel;   // the kernel instance
+    dim3 grid, block;
+    size_t lds;           // dynamic LDS bytes
+    AttnParams p;         // the call as the kernel sees it: virtual kv heads, splits, slots, mergers
+    int kind;             // million_attn_kernel_kind before a transpose: 1 streaming / lean, 3 tile, 5 grouped, 0 scalar
+    void (*setup)();      // raises the dynamic-LDS limit of the kernel's family, once per device (device_once)
+};
+// Each planner declines the call (false) or fills in the plan (true); plan_attn_generic takes every call and fails only for
+// shapes its LDS cannot hold (MILLION_ERR_SHAPE).  The order in which they are asked is million_api.hip's.
+bool plan_attn_mfma(const AttnParams &p, AttnPlan &plan);    // attn_mfma.hip: the lean, streaming and grouped kernels
+bool plan_attn_tile(const AttnParams &p, AttnPlan &plan);    // attn_tile.hip
+int plan_attn_generic(const AttnParams &p, AttnPlan &plan);  // attn_generic.hip: the scalar kernel, up to kMaxG query heads
 int launch_encode(const EncParams &p, hipStream_t s);
 int launch_decode(const void *codes, const f16 *cents, f16 *out, long long n_rows, int M, int C, int dm, hipStream_t s);
 struct FlushLayers { int n_layers; long long x_ls, ids_ls, len_ls; int advance; };      // one layer: {1, 0, 0, 0, 1}
 int launch_flush(const EncParams &k, const EncParams &v, int *dev_lengths_w, int rcap, int min_r, const FlushLayers &ly, hipStream_t s);
-bool attn_mfma_shape_ok(const AttnParams &p);
 int launch_rows_reduce_check(const float *in, float *out_max, float *out_sum, hipStream_t s);
-bool attn_mfma_supported(const AttnParams &p);
-bool attn_mfma_handles(const AttnParams &p);     // supported AND launch_attn_mfma will not hand the call back (kAttnNotHandled)
-bool attn_mfma_streams(const AttnParams &p);     // ... and the streaming kernel runs (not the grouped one: T = 0, > 1M tokens)
 void set_error(const char *fmt, ...);
 
 // Per-device facts and one-time per-device setup (one process may drive several devices): CU count, and a set of

@@ -53,7 +53,6 @@ bool device_once(int family) {
     g_dev_once[dev] |= bit;
     return true;
 }
-static int num_cus() { return device_cus(); }
 
 // ---- prepare_cents: (M, C, dm) -> fp16 row image [m][c][dm], fp16 col image [c][m][dm], fp32 row image ----
 __global__ void prepare_cents_kernel(const f16 *__restrict__ src, f16 *__restrict__ dst, int M, int C, int dm) {
@@ -203,25 +202,6 @@ static int fill_attn_params(const million_attn_desc *desc, AttnParams &p) {
     p.scale_log2e = 1.4426950408889634f / sqrtf((float)p.d);
     p.slot_floats = (int)slot_floats_for(p.G, p.d);
     return MILLION_OK;
-}
-
-// Split policy: about one workgroup per CU over all (b, hk); a split is a multiple of 64 tokens and at
-// least 256 tokens long (the reference picks Ns from the binding name, pq_utils.py:8-22; here the
-// split count is internal and the Ns of the name is ignored).
-static void choose_splits(AttnParams &p, int min_tokens) {
-    const int bh = p.bs * p.nh_k;
-    int ns = (num_cus() + bh - 1) / bh;
-    if (ns > kMaxSplits) ns = kMaxSplits;
-    int by_len = (p.T + min_tokens - 1) / min_tokens;
-    if (by_len < 1) by_len = 1;
-    if (ns > by_len) ns = by_len;
-    if (ns < 1) ns = 1;
-    int len = (p.T + ns - 1) / ns;
-    len = (len + 63) / 64 * 64;
-    if (len < 64) len = 64;
-    ns = p.T > 0 ? (p.T + len - 1) / len : 1;
-    p.nsplit = ns;
-    p.split_len = len;
 }
 
 }  // namespace million
@@ -405,63 +385,59 @@ static void after_first_launch(AttnParams &p) {
     }
 }
 
+// Row-major K and V (the reference's 10-argument layout) go to the fast kernels with V in dense transposed 64-token pages,
+// which one transpose launch per call writes into workspace scratch (none when T = 0).
+static AttnParams with_v_pages(const AttnParams &p, const uint8_t *scratch) {
+    AttnParams q = p;
+    q.v_paged = 1; q.v_identity = 1; q.page_size = 64; q.ps_shift = 6;
+    q.n_pages_cap = p.T > 0 ? (p.T + 63) / 64 : 1;
+    if (p.T > 0) q.v_codes = scratch;
+    return q;
+}
+
+// The launch for the p.G <= kMaxGMfma query heads per kv head from p.g0 on: the MFMA kernels, else the tile kernel, else the
+// scalar kernel, which serves kMaxG of them (heads: how many the plan serves).
+static int plan_group(const AttnParams &p, AttnPlan &plan, int &heads) {
+    heads = p.G;
+    if (!g_force_generic && (plan_attn_mfma(p, plan) || plan_attn_tile(p, plan))) return MILLION_OK;
+    if (heads > kMaxG) heads = kMaxG;
+    return plan_attn_generic(with_heads(p, p.g0, heads), plan);
+}
+
+static int launch_plan(const AttnPlan &plan, hipStream_t stream) {
+    plan.setup();
+    void *args[] = {(void *)&plan.p};
+    (void)hipLaunchKernel(plan.kernel, plan.grid, plan.block, args, plan.lds, stream);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("attn launch (kind %d): %s", plan.kind, hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
+    return MILLION_OK;
+}
+
+// not a silent cliff: the scalar kernel is ~60x slower than the MFMA kernels.  Said once per process on
+// stderr (MILLION_QUIET=1 silences it); million_attn_kernel_kind() answers the same question without launching.
+static void warn_scalar(const AttnParams &p) {
+    if (g_force_generic) return;
+    static std::once_flag once;
+    std::call_once(once, [&] {
+        const char *q = getenv("MILLION_QUIET");
+        if (!q || !*q || *q == '0')
+            fprintf(stderr, "libmillion_hip: decode attention fell back to the scalar kernel (d=%d M=%d C=%d, k %s / v %s%s): "
+                            "~60x slower than the MFMA kernels; they take d=128 with M in {64,32} or d in {64,128} with the "
+                            "reference's other (M, C) and V in transposed pages (row-major K and V are transposed for you).\n",
+                    p.d, p.M, p.C, p.k_paged ? "paged" : "row-major", p.v_paged ? "paged" : "row-major",
+                    p.T == 0 ? ", no quantised tokens" : "");
+    });
+}
+
 int million_attn_kernel_kind(const million_attn_desc *desc) {
     AttnParams p;
     if (fill_attn_params(desc, p) != MILLION_OK) return -1;
-    if (g_force_generic) return 0;
-    if (attn_mfma_supported(p) && attn_mfma_handles(p)) return attn_mfma_streams(p) ? 1 : 5;
-    if (attn_mfma_shape_ok(p) && !p.v_paged && !p.k_paged && p.T > 0) {               // transpose + MFMA kernel
-        AttnParams pt = p;
-        pt.v_paged = 1; pt.v_identity = 1; pt.page_size = 64; pt.ps_shift = 6;
-        if (attn_mfma_handles(pt)) return attn_mfma_streams(pt) ? 2 : 5;
-    }
-    const AttnParams p8 = with_heads(p, 0, p.Gt < kMaxGMfma ? p.Gt : kMaxGMfma);      // tile kernel: up to kMaxGMfma heads per launch
-    if (attn_tile_supported(p8)) return 3;                                            // tile kernel
-    if (attn_tile_shape_ok(p8) && !p.v_paged && !p.k_paged) return 4;                 // transpose + tile kernel
-    return 0;
-}
-
-// one query-head group (p.G heads per kv head from p.g0 on): 1. the streaming / grouped MFMA kernels (d = 128,
-// M in {64, 32} with up to kMaxGMfma heads, M = 16 with up to 4); 2. the tile kernel (every other shape of the binding surface); 3. the scalar
-// kernel (both up to kMaxG heads: a bigger group the MFMA kernels hand back is split here)
-static int launch_group(const AttnParams &p, hipStream_t stream) {
-    if (!g_force_generic) {
-        if (attn_mfma_supported(p)) {
-            const int rc_fast = launch_attn_mfma(p, stream);
-            if (rc_fast != kAttnNotHandled) return rc_fast;
-        }
-    }
-    if (!g_force_generic && attn_tile_supported(p)) return launch_attn_tile(p, stream);      // up to kMaxGMfma heads per launch
-    if (p.G > kMaxG) {
-        for (int g1 = 0; g1 < p.G; g1 += kMaxG) {
-            AttnParams h = with_heads(p, p.g0 + g1, p.G - g1 < kMaxG ? p.G - g1 : kMaxG);
-            if (g1 > 0) after_first_launch(h);
-            const int rc_h = launch_group(h, stream);
-            if (rc_h != MILLION_OK) return rc_h;
-        }
-        return MILLION_OK;
-    }
-    if (!g_force_generic) {
-        if (attn_tile_supported(p)) return launch_attn_tile(p, stream);
-    }
-    if (!g_force_generic) {
-        // not a silent cliff: the scalar kernel is ~60x slower than the MFMA kernels.  Said once per process
-        // on stderr (MILLION_QUIET=1 silences it); million_attn_kernel_kind() answers the same question without launching.
-        static std::once_flag once;
-        std::call_once(once, [&] {
-            const char *q = getenv("MILLION_QUIET");
-            if (!q || !*q || *q == '0')
-                fprintf(stderr, "libmillion_hip: decode attention fell back to the scalar kernel (d=%d M=%d C=%d, k %s / v %s%s): "
-                                "~60x slower than the MFMA kernels; they take d=128 with M in {64,32} or d in {64,128} with the "
-                                "reference's other (M, C) and V in transposed pages (row-major K and V are transposed for you).\n",
-                        p.d, p.M, p.C, p.k_paged ? "paged" : "row-major", p.v_paged ? "paged" : "row-major",
-                        p.T == 0 ? ", no quantised tokens" : "");
-        });
-    }
-    AttnParams g = p;
-    choose_splits(g, 256);
-    g.nslots = g.nsplit + 1;
-    return launch_attn_generic(g, stream);
+    const bool rowmajor = !p.k_paged && !p.v_paged;
+    AttnPlan plan;
+    int heads;
+    plan_group(rowmajor ? with_v_pages(p, nullptr) : p, plan, heads);
+    if (rowmajor && p.T > 0 && (plan.kind == 1 || plan.kind == 3)) return plan.kind + 1;      // 2 / 4: after the transpose launch
+    return plan.kind;
 }
 
 static int attn_impl(const million_attn_desc *desc, const void *q, const void *k_new, const void *v_new,
@@ -507,35 +483,34 @@ static int attn_impl(const million_attn_desc *desc, const void *q, const void *k
     p.bad_ids = bad_ids_counter();
 #endif
     p.ws_part = (float *)((char *)workspace + attn_cnt_bytes(p.bs, p.nh_k) + attn_flag_bytes(p.bs, p.nh_k));
-    // The fast kernels want V in transposed pages: the reference's 10-arg row-major layout is transposed into scratch
-    // pages first (once per call, whatever the number of query-head groups below).
-    AttnParams pl = p;
-    const AttnParams p8 = with_heads(p, 0, p.Gt < kMaxGMfma ? p.Gt : kMaxGMfma);
-    if (!g_force_generic && !p.v_paged && !p.k_paged && (attn_mfma_shape_ok(p) || attn_tile_shape_ok(p8))) {
-        pl.v_paged = 1; pl.v_identity = 1; pl.page_size = 64; pl.ps_shift = 6;
-        pl.n_pages_cap = p.T > 0 ? (p.T + 63) / 64 : 1;
-        if (p.T > 0) {
-            uint8_t *scratch = (uint8_t *)workspace + attn_partial_bytes(p.bs, p.nh_k, p.G, p.d);
-            hipLaunchKernelGGL(codes_transpose_kernel, dim3(pl.n_pages_cap, p.bs * p.nh_k), dim3(256), 0, (hipStream_t)stream,
-                               p.v_codes, scratch, p.nh_k, p.T, p.M, p.v_sb, p.v_sh, pl.n_pages_cap);
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) { set_error("codes_transpose launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
-            pl.v_codes = scratch;
-        }
+    uint8_t *scratch = (uint8_t *)workspace + attn_partial_bytes(p.bs, p.nh_k, p.G, p.d);
+    const bool rowmajor = !p.k_paged && !p.v_paged;
+    AttnParams pl = rowmajor ? with_v_pages(p, scratch) : p;
+    AttnPlan plan;
+    int heads;
+    int rc_p = plan_group(pl, plan, heads);
+    if (rowmajor && plan.kind == 0) rc_p = plan_group(pl = p, plan, heads);      // the scalar kernel reads row-major V as it is
+    if (rc_p != MILLION_OK) return rc_p;
+    if (pl.v_paged && !p.v_paged && p.T > 0) {      // once per call, whatever the number of query-head groups below
+        hipLaunchKernelGGL(codes_transpose_kernel, dim3(pl.n_pages_cap, p.bs * p.nh_k), dim3(256), 0, (hipStream_t)stream,
+                           p.v_codes, scratch, p.nh_k, p.T, p.M, p.v_sb, p.v_sh, pl.n_pages_cap);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { set_error("codes_transpose launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
     }
-    // One launch of the MFMA kernels serves up to 16 query heads per kv head (the 16 columns of the score tile: Llama-3.1-405B's
-    // nh / nh_k = 16 reads its codes once), of the other kernels up to 8; bigger groups run as several launches on the same
-    // stream and workspace, each re-reading the codes.  A fused append happens in the first one: the later ones find the
-    // row in the window.
-    const AttnParams p16 = with_heads(pl, 0, p.Gt < kMaxGMfma ? p.Gt : kMaxGMfma);
-    const int step = (!g_force_generic && (attn_mfma_supported(pl) || attn_tile_supported(p16))) ? kMaxGMfma : kMaxG;
-    for (int g0 = 0; g0 < p.Gt; g0 += step) {
-        AttnParams pg = with_heads(pl, g0, p.Gt - g0 < step ? p.Gt - g0 : step);
-        if (g0 > 0) after_first_launch(pg);
-        const int rc_g = launch_group(pg, (hipStream_t)stream);
+    // One launch of the MFMA and tile kernels serves up to 16 query heads per kv head (the 16 columns of the score tile:
+    // Llama-3.1-405B's nh / nh_k = 16 reads its codes once), of the scalar kernel up to 8; bigger groups run as several
+    // launches on the same stream and workspace, each re-reading the codes.  A fused append happens in the first one: the
+    // later ones find the row in the window.
+    for (int g0 = 0;;) {
+        if (plan.kind == 0) warn_scalar(p);
+        const int rc_g = launch_plan(plan, (hipStream_t)stream);
         if (rc_g != MILLION_OK) return rc_g;
+        if ((g0 += heads) >= p.Gt) return MILLION_OK;
+        AttnParams pg = with_heads(pl, g0, p.Gt - g0 < kMaxGMfma ? p.Gt - g0 : kMaxGMfma);
+        after_first_launch(pg);
+        const int rc_n = plan_group(pg, plan, heads);
+        if (rc_n != MILLION_OK) return rc_n;
     }
-    return MILLION_OK;
 }
 
 int million_pq_decode_attn(const million_attn_desc *desc, const void *q, const void *k_codes, const void *v_codes,

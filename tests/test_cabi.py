@@ -103,6 +103,14 @@ def test_kernel_kind_policy_without_gpu(lib):
     assert kind(1, 64, 8, 4096, d=128, M=16) == 1      # 8 heads per kv head: two virtual kv heads of 4 on the streaming kernel (round 5)
     assert kind(64, 256, 32, 4096, d=128, M=16) == 3   # ... unless the virtual pairs outgrow the workspace head (2048 records)
     assert kind(1, 32, 8, 4096, C=64) == 0             # off the build matrix: scalar kernel
+    # row-major K and V with nothing quantised yet: no transpose launch; V is handed on as (empty) transposed pages
+    assert kind(1, 32, 8, 0, paged=False) == 5                  # grouped MFMA kernel (window only)
+    assert kind(1, 32, 8, 0, d=64, M=32, paged=False) == 3      # tile kernel
+    lib.million_set_force_generic(2)                   # grouped kernel only - which has no C = 128 form: the streaming kernel stays
+    try:
+        assert kind(1, 32, 8, 4096, C=128) == 1
+    finally:
+        lib.million_set_force_generic(0)
 
 
 def test_bindings_exports_reference_names():

@@ -1532,8 +1532,8 @@ def test_attn_tile_kernel_shapes(d, M, C, T, r, nh, nhk, bs, env, oracle):
 
 def test_attn_kernel_kind_mirrors_the_hand_back(env, oracle):
     """million_attn_kernel_kind answers what a call WOULD run: d = 128 / M = 64 / C = 128 is the streaming kernel's shape, but
-    with nothing quantised yet (T = 0) launch_attn_mfma hands the call to the tile kernel (kind 3); C = 256 keeps the grouped
-    MFMA kernel for that (kind 5)."""
+    with nothing quantised yet (T = 0) plan_attn_mfma declines the call and the tile kernel takes it (kind 3); C = 256 keeps the
+    grouped MFMA kernel for that (kind 5)."""
     torch, ops = env
     c = synth.attn_case(7700, 1, 8, 2, 128, 64, 128, 0, 40, Lt=128)
     t = _dev(torch, c)
