@@ -6,9 +6,9 @@
 //   every row sees the T + r past keys; chunk key j is visible to row i iff j <= i (n_c = n_q) - n_c = 0: past only.
 //
 // Design
-//   * the flash-attention tile loop of prefill_attn_kernel (csrc/prefill.hip, the plain form): S^T = K Q^T with
+//   * the flash-attention tile step of prefill_attn_kernel, shared through flash_tile.h: S^T = K Q^T with
 //     v_mfma_f32_32x32x16_f16, a query row on a lane, in-lane online softmax in the exp2 domain, O^T += V^T P^T with V^T read by
-//     ds_read_b64_tr_b16 from the same pf_off LDS image.  The G query heads of a kv head are flattened, rho = i G + g, so a
+//     ds_read_b64_tr_b16 from the same tile_off LDS image; only the mask is this kernel's own.  The G query heads of a kv head are flattened, rho = i G + g, so a
 //     workgroup of 8 waves holds 256 consecutive rows of one (b, kv head) and a wave's 32 rows have a monotone causal limit.
 //   * three producers fill ONE [64 keys][D] K and V tile image: (a) 64 tokens of codes, dequantised through both codebooks held
 //     in LDS (the row image [m][c][d_m] of million_prepare_cents: the gather of pq_decode, bit for bit); (b) window rows read
@@ -26,18 +26,11 @@
 #include <math.h>
 #include <string.h>
 
-#include "common.h"
+#include "flash_tile.h"
 
 namespace million {
 
 namespace {
-
-typedef _Float16 ca_v8h __attribute__((ext_vector_type(8)));
-typedef float ca_v16f __attribute__((ext_vector_type(16)));
-typedef unsigned ca_v4u __attribute__((ext_vector_type(4)));
-typedef short ca_v4s __attribute__((__vector_size__(4 * sizeof(short))));
-typedef __attribute__((address_space(3))) ca_v4u *ca_lds_v4u_p;
-typedef __attribute__((address_space(3))) ca_v4s *ca_lds_v4s_p;
 
 constexpr int kKeys = 64;            // keys per tile
 constexpr int kRowsWG = 256;         // flattened query rows per workgroup (8 waves x 32)
@@ -64,15 +57,6 @@ struct ChunkParams {
     int cb_bytes;                             // one codebook image in LDS (0: no code tiles)
     float scale_log2e;
 };
-
-// the LDS image of prefill.hip (pf_off): [64 keys][D] fp16, byte offset of 16-byte chunk ch of a row; conflict-free for the
-// ds_read_b128 row reads and the ds_read_b64_tr_b16 transposed reads of the 32x32x16 operands
-template <int D>
-__device__ __forceinline__ unsigned ca_off(int row, int ch) {
-    if (D == 128) return 256u * row + 16u * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
-    const int rp = row >> 1;
-    return 256u * rp + 16u * ((((row & 1) << 3) | ch) ^ (((rp & 1) << 2) | ((rp >> 2) & 3)));
-}
 
 __device__ __forceinline__ long long ca_page(const ChunkParams &p, const void *ids, int b, int hk, int pg) {
     const long long i = ((long long)b * p.nh_k + hk) * p.n_pages_cap + pg;
@@ -107,7 +91,7 @@ __device__ __forceinline__ unsigned long long ca_load_codes(const ChunkParams &p
 
 // 8 fp16 of one 16-byte chunk from NM codes through a codebook row image at LDS byte offset `tab`: NM reads of d_m fp16
 template <int DM>
-__device__ __forceinline__ ca_v4u ca_dequant(unsigned long long w, unsigned tab, int m0, int C) {
+__device__ __forceinline__ pv4u ca_dequant(unsigned long long w, unsigned tab, int m0, int C) {
     constexpr int NM = 8 / DM;
     unsigned u[4];
 #pragma unroll
@@ -116,7 +100,7 @@ __device__ __forceinline__ ca_v4u ca_dequant(unsigned long long w, unsigned tab,
         c = c < C ? c : C - 1;      // totality: a byte past the valid codes still reads a centroid
         const unsigned a = tab + 2u * (unsigned)(((m0 + e) * C + c) * DM);
         if (DM == 8) {
-            const ca_v4u x = *(const __attribute__((address_space(3))) ca_v4u *)(size_t)a;
+            const pv4u x = *(const __attribute__((address_space(3))) pv4u *)(size_t)a;
             u[0] = x[0]; u[1] = x[1]; u[2] = x[2]; u[3] = x[3];
         } else if (DM == 4) {
             typedef unsigned u2 __attribute__((ext_vector_type(2)));
@@ -129,7 +113,7 @@ __device__ __forceinline__ ca_v4u ca_dequant(unsigned long long w, unsigned tab,
             u[e >> 1] = (e & 1) ? (u[e >> 1] | (x << 16)) : x;
         }
     }
-    const ca_v4u v = {u[0], u[1], u[2], u[3]};
+    const pv4u v = {u[0], u[1], u[2], u[3]};
     return v;
 }
 
@@ -168,24 +152,19 @@ __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(ChunkParams p) 
     const int nt = p.ntT + p.ntR + ntC;
     const int t_beg = (int)((long long)s * nt / p.S), t_end = (int)((long long)(s + 1) * nt / p.S);
 
-    // ---- Q^T fragments: B operand, lane (q, h): Q[q][16 s + 8 h .. + 8] ----
-    ca_v8h qf[DS];
-    {
-        const f16 *qp = p.q + b * p.q_sb + head * p.q_sh + (long long)qi * p.q_sn + 8 * hh;
-#pragma unroll
-        for (int k = 0; k < DS; ++k) qf[k] = *(const ca_v8h *)(qp + 16 * k);
-    }
+    v8h qf[DS];
+    flash_load_q<D>(qf, p.q + b * p.q_sb + head * p.q_sh + (long long)qi * p.q_sn, hh);
     const unsigned cbK = 2u * kTileBytes, cbV = cbK + (unsigned)p.cb_bytes;
     if (t_beg < p.ntT) {      // this split dequantises: both codebooks into LDS (made visible by the loop's first barrier)
-        const ca_v4u *sk = (const ca_v4u *)p.ktab, *sv = (const ca_v4u *)p.vtab;
+        const pv4u *sk = (const pv4u *)p.ktab, *sv = (const pv4u *)p.vtab;
         for (int o = tid; o < p.cb_bytes / 16; o += kThreads) {
-            *(ca_v4u *)(ca_smem + cbK + 16 * o) = sk[o];
-            *(ca_v4u *)(ca_smem + cbV + 16 * o) = sv[o];
+            *(pv4u *)(ca_smem + cbK + 16 * o) = sk[o];
+            *(pv4u *)(ca_smem + cbV + 16 * o) = sv[o];
         }
     }
 
     // ---- producers: a tile's raw bytes (codes, or fp16 rows) into registers, then dequantised / copied into LDS ----
-    ca_v4u rk[CPT], rv[CPT];
+    pv4u rk[CPT], rv[CPT];
     auto tile_src = [&](int t, int &kind, int &j0, int &nv) {      // kind 0 codes, 1 window, 2 chunk
         if (t < p.ntT) { kind = 0; j0 = t * kKeys; nv = p.T - j0; }
         else if (t < p.ntT + p.ntR) { kind = 1; j0 = (t - p.ntT) * kKeys; nv = p.r - j0; }
@@ -198,7 +177,7 @@ __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(ChunkParams p) 
 #pragma unroll
         for (int k = 0; k < CPT; ++k) {
             const int c = tid + kThreads * k, row = c / CH, ch = c % CH;
-            const ca_v4u z = {0u, 0u, 0u, 0u};
+            const pv4u z = {0u, 0u, 0u, 0u};
             rk[k] = z;
             rv[k] = z;
             if (row < nv) {
@@ -212,11 +191,11 @@ __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(ChunkParams p) 
                     int rr = p.rs + j;
                     rr = rr < p.rcap ? rr : rr - p.rcap;
                     const long long o = b * p.res_sb + hk * p.res_sh + (long long)rr * (CH * 8) + 8 * ch;
-                    rk[k] = *(const ca_v4u *)(p.kres + o);
-                    rv[k] = *(const ca_v4u *)(p.vres + o);
+                    rk[k] = *(const pv4u *)(p.kres + o);
+                    rv[k] = *(const pv4u *)(p.vres + o);
                 } else {
-                    rk[k] = *(const ca_v4u *)(p.kc + b * p.kc_sb + hk * p.kc_sh + (long long)j * p.kc_sn + 8 * ch);
-                    rv[k] = *(const ca_v4u *)(p.vc + b * p.vc_sb + hk * p.vc_sh + (long long)j * p.vc_sn + 8 * ch);
+                    rk[k] = *(const pv4u *)(p.kc + b * p.kc_sb + hk * p.kc_sh + (long long)j * p.kc_sn + 8 * ch);
+                    rv[k] = *(const pv4u *)(p.vc + b * p.vc_sb + hk * p.vc_sh + (long long)j * p.vc_sn + 8 * ch);
                 }
             }
         }
@@ -227,17 +206,17 @@ __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(ChunkParams p) 
 #pragma unroll
         for (int k = 0; k < CPT; ++k) {
             const int c = tid + kThreads * k, row = c / CH, ch = c % CH;
-            ca_v4u kx = rk[k], vx = rv[k];
+            pv4u kx = rk[k], vx = rv[k];
             if (kind == 0 && row < nv) {
                 kx = ca_dequant<DM>((unsigned long long)rk[k][0] | ((unsigned long long)rk[k][1] << 32), cbK, ch * NM, p.C);
                 vx = ca_dequant<DM>((unsigned long long)rv[k][0] | ((unsigned long long)rv[k][1] << 32), cbV, ch * NM, p.C);
             }
-            *(ca_v4u *)(ca_smem + ca_off<D>(row, ch)) = kx;
-            *(ca_v4u *)(ca_smem + kTileBytes + ca_off<D>(row, ch)) = vx;
+            *(pv4u *)(ca_smem + tile_off<D>(row, ch)) = kx;
+            *(pv4u *)(ca_smem + kTileBytes + tile_off<D>(row, ch)) = vx;
         }
     };
 
-    ca_v16f O[NB];
+    v16f O[NB];
 #pragma unroll
     for (int i = 0; i < NB; ++i)
 #pragma unroll
@@ -255,21 +234,9 @@ __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(ChunkParams p) 
         tile_src(t, kind, j0, nv);
         const bool live = wave_live && (kind != 2 || j0 <= wave_i_hi);      // wave-uniform
         if (!live) continue;
-        // ---- S^T = K Q^T: two 32-key x 32-query tiles ----
-        ca_v16f S0, S1;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) { S0[j] = 0.f; S1[j] = 0.f; }
-#pragma unroll
-        for (int k = 0; k < DS; ++k) {
-            const ca_v8h a0 = __builtin_bit_cast(ca_v8h, *((ca_lds_v4u_p)(size_t)ca_off<D>(r32, 2 * k + hh)));
-            const ca_v8h a1 = __builtin_bit_cast(ca_v8h, *((ca_lds_v4u_p)(size_t)ca_off<D>(32 + r32, 2 * k + hh)));
-            S0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, qf[k], S0, 0, 0, 0);
-            S1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, qf[k], S1, 0, 0, 0);
-        }
-        // ---- mask (rows past the source's end; chunk keys after the row's own position), online softmax ----
         float sc[32];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) { sc[j] = S0[j]; sc[16 + j] = S1[j]; }
+        flash_scores<D, 0>(sc, qf, r32, hh);
+        // ---- mask (rows past the source's end; chunk keys after the row's own position), online softmax ----
         if (nv < kKeys || kind == 2) {
             int lim = nv - 1;                                     // last key of the tile this row sees
             if (kind == 2) lim = qi - j0 < lim ? qi - j0 : lim;
@@ -277,78 +244,14 @@ __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(ChunkParams p) 
 #pragma unroll
             for (int j = 0; j < 32; ++j) sc[j] = 32 * (j >> 4) + (j & 3) + 8 * ((j & 15) >> 2) <= rel ? sc[j] : -INFINITY;
         }
-        float mx = sc[0];
-#pragma unroll
-        for (int j = 1; j < 32; ++j) mx = fmaxf(mx, sc[j]);
-        {
-            const v2u ex = swap32_self(__float_as_uint(mx));      // both halves of the wave: the same query rows
-            const unsigned e0 = ex[0], e1 = ex[1];
-            mx = fmaxf(__uint_as_float(e0), __uint_as_float(e1));
-        }
-        const float m_new = fmaxf(m_run, mx * cs);
-        const float m_safe = m_new > -INFINITY ? m_new : 0.f;
-        if (__any(m_new > m_run && m_run > -INFINITY)) {
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_safe);
-#pragma unroll
-            for (int i = 0; i < NB; ++i)
-#pragma unroll
-                for (int j = 0; j < 16; ++j) O[i][j] *= alpha;
-            l_run *= alpha;
-        }
-        m_run = m_new;
-        float ls = 0.f;
-#pragma unroll
-        for (int j = 0; j < 32; ++j) {
-            sc[j] = __builtin_amdgcn_exp2f(fmaf(sc[j], cs, -m_safe));
-            ls += sc[j];
-        }
-        l_run += ls;
-        // ---- O^T += V^T P^T ----
-        const int qd = (lane >> 2) & 3, pp = lane & 3, g16 = (lane >> 4) & 1;
-#pragma unroll
-        for (int jt = 0; jt < 2; ++jt)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-                unsigned pw[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const h2v t2 = {(f16)sc[16 * jt + 8 * ks + 2 * e], (f16)sc[16 * jt + 8 * ks + 2 * e + 1]};
-                    pw[e] = __builtin_bit_cast(unsigned, t2);
-                }
-                const ca_v4u pwv = {pw[0], pw[1], pw[2], pw[3]};
-                const ca_v8h pb = __builtin_bit_cast(ca_v8h, pwv);
-                const int kvr0 = 32 * jt + 16 * ks + 4 * hh;
-#pragma unroll
-                for (int blk = 0; blk < NB; ++blk) {
-                    const int chn = 4 * blk + 2 * g16 + (pp >> 1);
-                    const ca_v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ca_lds_v4s_p)(size_t)(ca_off<D>(kvr0 + qd, chn) + 8 * (pp & 1) + kTileBytes));
-                    const ca_v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((ca_lds_v4s_p)(size_t)(ca_off<D>(kvr0 + 8 + qd, chn) + 8 * (pp & 1) + kTileBytes));
-                    typedef short v8s __attribute__((ext_vector_type(8)));
-                    const v8s av = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    O[blk] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(ca_v8h, av), pb, O[blk], 0, 0, 0);
-                }
-            }
+        flash_softmax(sc, O, m_run, l_run, cs);
+        flash_pv<D, kTileBytes>(O, sc, lane);
     }
     // ---- epilogue: lane (q, h) holds dims 32 blk + 8 i + 4 h + (0..3) of its row ----
-    {
-        const v2u ex = swap32_self(__float_as_uint(l_run));
-        const unsigned e0 = ex[0], e1 = ex[1];
-        l_run = __uint_as_float(e0) + __uint_as_float(e1);
-    }
+    l_run = flash_l_total(l_run);
     if (!wave_live || rho >= p.nrows) return;
     if (p.S == 1) {
-        const float inv = l_run > 0.f ? 1.0f / l_run : 0.f;
-        f16 *op = p.out + b * p.o_sb + head * p.o_sh + (long long)qi * p.o_sn + 4 * hh;
-#pragma unroll
-        for (int blk = 0; blk < NB; ++blk)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                typedef f16 h4 __attribute__((ext_vector_type(4)));
-                const h4 o = {(f16)(O[blk][4 * i] * inv), (f16)(O[blk][4 * i + 1] * inv), (f16)(O[blk][4 * i + 2] * inv),
-                              (f16)(O[blk][4 * i + 3] * inv)};
-                *(h4 *)(op + 32 * blk + 8 * i) = o;
-            }
+        flash_store_row(O, l_run, p.out + b * p.o_sb + head * p.o_sh + (long long)qi * p.o_sn, hh);
         return;
     }
     const long long wrow = (((long long)b * p.nh_k + hk) * p.S + s) * p.nrows + rho;

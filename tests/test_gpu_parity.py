@@ -2038,7 +2038,7 @@ def test_prefill_attn_32k_sampled_rows(env):
 
 def test_prefill_attn_128k_sampled_rows(env):
     """BASELINE configs[4]'s prompt length: (1, 32, 8, 131072, 128) - 4 x the rows of the 32K test, so the row / tile / key-tile
-    index arithmetic of prefill.hip (t * kKV, pf_off, kv_end_wg) runs at the size the bench times it at.  First row, last
+    index arithmetic of prefill.hip (t * kKV, tile_off, kv_end_wg) runs at the size the bench times it at.  First row, last
     row and rows at tile edges of every head against the fp64 reference (pq_utils.py:249-260: causal SDPA of the prompt)."""
     torch, ops = env
     n = 131072
