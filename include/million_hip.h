@@ -233,20 +233,19 @@ int million_transpose_v_codes(const void *v_codes, void *v_pages, int bs, int nh
  * tokens the "lean" form of it runs - csrc/attn_lean.h - which also takes d = 64 with M in {64, 32, 16} at up to 16
  * query heads per kv head: 5 and more run as ceil(G / 4) virtual kv heads of 3 / 4 query heads, while bs * nh_k * parts <= 2048),
  * 2 = the same after transposing row-major V codes into workspace scratch (one extra launch), 3 = tile MFMA kernel
- * (d = 64 on 32-token pages; d = 64 or d = 128 / M = 16 with more than 2048 virtual (b, kv head) pairs; C = 128 with no quantised
- * token yet), 4 = the same after the transpose, 5 = the grouped MFMA kernel (the streaming kernel's fallback on its M = 64 / 32,
- * C = 256 shapes: no quantised token yet, or more than 1M tokens; also after a transpose), 0 = scalar fallback (anything else the
- * descriptor allows: C not 128 / 256, paged K with row-major V, ...), -1 = bad descriptor.  Row-major K and V with n_tokens = 0
- * need no transpose launch: 1 / 3 / 5 then.  The answer is the plan million_pq_decode_attn launches for its first query-head
- * group, under the current million_set_force_generic policy. */
+ * (d = 64 on 32-token pages; d = 64 or d = 128 / M = 16 with more than 2048 virtual (b, kv head) pairs; on the streaming
+ * kernel's shapes: no quantised token yet, or more than 1M tokens per (b, kv head)), 4 = the same after the transpose,
+ * 0 = scalar fallback (anything else the descriptor allows: C not 128 / 256, paged K with row-major V, ...), -1 = bad descriptor.
+ * (5, the grouped MFMA kernel, is retired and not reused.)  Row-major K and V with n_tokens = 0 need no transpose launch: 3 then.
+ * The answer is the plan million_pq_decode_attn launches for its first query-head group, under the current
+ * million_set_force_generic policy. */
 int million_attn_kernel_kind(const million_attn_desc *desc);
-/* Kernel choice for A/B measurements and tests: 0 = auto (default), 1 = generic kernel only, 2 = MFMA grouped kernel
- * instead of the streaming one (C = 256; the grouped kernel has no C = 128 form, so C = 128 stays on the streaming kernel), 4 = auto, but the helper workgroups of the split merge give up at once (exercises the
+/* Kernel choice for A/B measurements and tests: 0 = auto (default), 1 = generic kernel only, 4 = auto, but the helper workgroups of the split merge give up at once (exercises the
  * last arriver's take-over path of the MFMA kernels' tail: every give-up bit is set before the launch's first ticket),
  * 8 = auto, but the helpers have no patience: each gives up through the real path (its atomic on the ticket word) unless
  * every workgroup has already taken its ticket, 16 = auto, but the shapes of the lean kernel (csrc/attn_lean.h) stay on the
  * streaming / tile kernels and no call runs as virtual kv heads (A/B and the tests of those kernels' forms), 64 = auto, but million_prefill_attn runs its plain
- * tile loop at d = 128 instead of the pipelined one (csrc/prefill.hip; A/B and the tests of both forms). */
+ * tile loop at d = 128 instead of the pipelined one (csrc/prefill.hip; A/B and the tests of both forms).  Any other value means auto. */
 void million_set_force_generic(int on);
 
 /* ------------------------------------------------------------------------------------------------

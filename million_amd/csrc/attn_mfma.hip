@@ -1,5 +1,5 @@
-// attn_mfma.hip — fused decode attention over PQ code pages for the headline shapes
-// (d = 128, M = 64, C = 256, transposed V pages), hand-written for gfx950 / CDNA4.
+// attn_mfma.hip — fused decode attention over PQ code pages on the matrix cores: d = 128 with M = 64 / 32 / 16 and (lean
+// kernel) d = 64, C = 256 / 128, transposed V pages, hand-written for gfx950 / CDNA4.
 //
 // Replaces (one launch): the LUT matmul + flash_decoding_split_kernel + flash_decoding_residual_kernel
 // + torch::zeros + flash_decoding_reduce_kernel of the reference (Interface.template.cu:26-120,
@@ -15,21 +15,21 @@
 //     byte fetches its 2-dim centroid from LDS straight into the A operand of
 //     v_mfma_f32_16x16x32_f16 (rows = 16 tokens, K = 32 dims), B = the query heads -> fp32 scores with
 //     exact fp16 centroids (no fp16 LUT rounding).  V side: lane = subspace m; 16 consecutive token
-//     bytes of a transposed page row are one 16-byte load; looked-up centroids are packed into the B
-//     operand of v_mfma_f32_32x32x16_f16 (K = 16 tokens, cols = 32 subspaces), A = the probabilities of
-//     the G heads, moved from the score layout with v_permlane32_swap / v_permlane16_swap;
+//     bytes of a transposed page row are one 16-byte load; the looked-up centroids are the B operand of
+//     v_mfma_f32_32x32x16_f16 (K = 16 tokens, cols = 32 subspaces) - as gathered at M = 64 ("parity-V"), packed by v_perm
+//     at M = 32 - and A = the probabilities of the G heads, moved from the score layout with v_permlane16_swap;
 //   * online softmax per wave in the exp2 domain, fp32; wave partials are merged through LDS, split
 //     partials through the workspace by the last-arriving workgroup (common.h:publish_and_merge);
 //   * the residual window (r <= 128 fp16 rows) is dealt round-robin to the splits and, inside a split, to its
 //     waves: each wave's rows are ONE 16-row MFMA tile (scores: A = the fp16 K rows; values: B = the fp16 V rows)
-//     that rides along with the wave's code units - no separate partial, no scalar FMA loop.
+//     that the wave runs before its code units - no separate partial, no scalar FMA loop.
 //   * round 4: M = 16 (d_m = 8) and M = 32 at G <= 4 run the streaming kernel in the "d_m = 8 / 4 forms" (see there): the query
 //     heads are replicated over the four column groups of the score tile, a gathered codebook entry is a lane's reduction slots of
 //     a 16x16x32 operand as it stands (K: A operand, V: B operand), 8 accumulator registers, no pack and no lane movement;
-//   * two kernels share everything above and the merge tail: attn_stream_kernel (the one that runs: value steps of
-//     unit u interleaved with the score stages of unit u + 1, online softmax per unit, any split length) and
-//     attn_mfma_kernel (groups of 4 units: score pass, softmax, value pass; the fallback for T = 0 and for splits of
-//     more than 64 units per wave, and the A/B reference).
+//   * two kernels share everything above and the merge tail: attn_stream_kernel (value steps of unit u interleaved with the
+//     score stages of unit u + 1, online softmax per unit, up to 64 rounds per wave) and attn_lean_kernel (attn_lean.h:
+//     64-token units, lane = token, up to 4 query heads per kv head).  plan_attn_mfma leaves what neither takes - T = 0,
+//     more than 64 rounds per wave - to the tile kernel (attn_tile.hip).
 #include <type_traits>
 
 #include "common.h"
@@ -56,7 +56,7 @@ constexpr int kResRows = 16;                 // residual-window rows per wave (o
 
 struct UnitCodes {
     v4u k[2];   // K code bytes: score tile g2, lane (q, c): tile row c, bytes [16q, 16q+16) of that token's code row
-                // (grouped kernel: row c = token 16 g2 + c; streaming kernel: stream_token_of_row(g2, c))
+                // (row c = token stream_token_of_row(g2, c) of the unit)
     v4u v[2];   // V code bytes: half n (32 subspaces), lane (h, c): m = 32n + c, tokens [16h, 16h+16)
 };
 
@@ -147,86 +147,18 @@ __device__ __forceinline__ v8f16 as_v8f16(unsigned a, unsigned b, unsigned c, un
 
 // ---- how the vector-memory queue is kept deep without fighting hipcc's waitcnt insertion ------------
 // Every code / codebook / q load is a plain load the compiler can count, and NONE of them sits in a
-// conditional: slots past a wave's last unit re-request the unit holding token T-1 (L2 hits).  The
+// conditional: slots past a wave's last unit re-request that unit (L2 hits).  The
 // pending-load pattern at the loop header is then identical on entry and on the back edge, and hipcc
 // emits counted waits (vmcnt(12) before a unit: the three younger units stay in flight).  Versions with
 // conditional refills, or with LDS-DMA for the tables, made hipcc wait vmcnt(0) and drained the ring.
 //
-// Page ids come through the scalar cache in ONE asm statement (issue + wait): hipcc does not pick s_load
-// for them by itself, and a vector load of an id would sit in the vmcnt queue in front of the codes.
-struct PidPair { long long k, v; int k32, v32; };
-__device__ __forceinline__ void load_pids4(const AttnParams &p, int bh, const int (&page)[4], PidPair (&o)[4]);
+// A scalar load (the device-resident lengths) is issued and waited for in ONE asm statement on purpose: an earlier
+// version split the two to overlap the latency, and hipcc, on an unrelated edit, placed SGPR copies between the two
+// statements - copies of values still in flight - which sent wild addresses to the code loads.
 
-__device__ __forceinline__ PidPair load_pids(const AttnParams &p, int bh, int page) {
-    int pg[kRing] = {page, page, page, page};
-    PidPair o[kRing];
-    load_pids4(p, bh, pg, o);
-    return o[0];
-}
-
-// The page ids of the ring's kRing first units: ONE scalar round trip.  Issue and wait live in the SAME asm
-// statement on purpose: an earlier version split them to overlap the latency and hipcc, on an unrelated
-// edit, placed SGPR copies between the two statements — copies of values still in flight — which sent
-// wild addresses to the code loads.  The statement sits after the independent vector loads have been
-// issued, so the scalar latency still overlaps with them.
-__device__ __forceinline__ void load_pids4(const AttnParams &p, int bh, const int (&page)[kRing], PidPair (&o)[kRing]) {
-    unsigned off[kRing];
-#pragma unroll
-    for (int k = 0; k < kRing; ++k) { o[k].k = 0; o[k].v = 0; o[k].k32 = 0; o[k].v32 = 0; }
-    if (p.v_identity && !p.k_paged) {           // dense scratch pages + row-major K: no id table at all
-#pragma unroll
-        for (int k = 0; k < kRing; ++k) o[k].v = bh * p.n_pages_cap + page[k];
-        return;
-    }
-#pragma unroll
-    for (int k = 0; k < kRing; ++k) off[k] = (unsigned)(bh * p.n_pages_cap + page[k]) * (p.ids64 ? 8u : 4u);
-    if (p.ids64) {
-        long long v0, v1, v2, v3;
-        asm volatile("s_load_dwordx2 %0, %4, %5\n\ts_load_dwordx2 %1, %4, %6\n\ts_load_dwordx2 %2, %4, %7\n\t"
-                     "s_load_dwordx2 %3, %4, %8\n\ts_waitcnt lgkmcnt(0)"
-                     : "=&s"(v0), "=&s"(v1), "=&s"(v2), "=&s"(v3)
-                     : "s"(p.v_ids64), "s"(off[0]), "s"(off[1]), "s"(off[2]), "s"(off[3]) : "memory");
-        o[0].v = v0; o[1].v = v1; o[2].v = v2; o[3].v = v3;
-        if (p.k_paged) {
-            asm volatile("s_load_dwordx2 %0, %4, %5\n\ts_load_dwordx2 %1, %4, %6\n\ts_load_dwordx2 %2, %4, %7\n\t"
-                         "s_load_dwordx2 %3, %4, %8\n\ts_waitcnt lgkmcnt(0)"
-                         : "=&s"(v0), "=&s"(v1), "=&s"(v2), "=&s"(v3)
-                         : "s"(p.k_ids64), "s"(off[0]), "s"(off[1]), "s"(off[2]), "s"(off[3]) : "memory");
-            o[0].k = v0; o[1].k = v1; o[2].k = v2; o[3].k = v3;
-        }
-    } else {
-        int v0, v1, v2, v3;
-        if (p.v_identity) {
-            v0 = bh * p.n_pages_cap + page[0]; v1 = bh * p.n_pages_cap + page[1];
-            v2 = bh * p.n_pages_cap + page[2]; v3 = bh * p.n_pages_cap + page[3];
-        } else {
-            asm volatile("s_load_dword %0, %4, %5\n\ts_load_dword %1, %4, %6\n\ts_load_dword %2, %4, %7\n\t"
-                         "s_load_dword %3, %4, %8\n\ts_waitcnt lgkmcnt(0)"
-                         : "=&s"(v0), "=&s"(v1), "=&s"(v2), "=&s"(v3)
-                         : "s"(p.v_ids32), "s"(off[0]), "s"(off[1]), "s"(off[2]), "s"(off[3]) : "memory");
-        }
-        o[0].v = v0; o[1].v = v1; o[2].v = v2; o[3].v = v3;
-        if (p.k_paged) {
-            asm volatile("s_load_dword %0, %4, %5\n\ts_load_dword %1, %4, %6\n\ts_load_dword %2, %4, %7\n\t"
-                         "s_load_dword %3, %4, %8\n\ts_waitcnt lgkmcnt(0)"
-                         : "=&s"(v0), "=&s"(v1), "=&s"(v2), "=&s"(v3)
-                         : "s"(p.k_ids32), "s"(off[0]), "s"(off[1]), "s"(off[2]), "s"(off[3]) : "memory");
-            o[0].k = v0; o[1].k = v1; o[2].k = v2; o[3].k = v3;
-        }
-    }
-#ifdef MILLION_DEBUG_CHECK_IDS
-#pragma unroll
-    for (int k = 0; k < kRing; ++k) {
-        if (p.k_paged) o[k].k = MILLION_CHECK_KID(p, o[k].k);
-        if (!p.v_identity) o[k].v = MILLION_CHECK_VID(p, o[k].v);
-    }
-#endif
-}
-
-// Request the 16-byte loads of one 32-token unit (see UnitCodes): two for the K bytes, two for the V bytes.
-// t_unit: multiple of 32, < T, wave-uniform.  Addresses are a wave-uniform 64-bit base (scalar ALU, forced
-// into SGPRs) plus a 32-bit per-lane offset, so that the loads take the saddr + voffset form: the per-lane
-// 64-bit pointer arithmetic of the obvious formulation was ~10 vector instructions per request.
+// Code loads address a wave-uniform 64-bit base (scalar ALU, forced into SGPRs) plus a 32-bit per-lane offset, so that
+// they take the saddr + voffset form: the per-lane 64-bit pointer arithmetic of the obvious formulation was ~10 vector
+// instructions per request.
 typedef const __attribute__((address_space(1))) uint8_t *gptr_u8;      // global address space: an integer -> pointer
                                                                        // cast would otherwise make FLAT loads
 __device__ __forceinline__ gptr_u8 uniform_ptr(const uint8_t *q) {
@@ -235,266 +167,14 @@ __device__ __forceinline__ gptr_u8 uniform_ptr(const uint8_t *q) {
     return (gptr_u8)(((unsigned long long)hi << 32) | lo);
 }
 typedef const __attribute__((address_space(1))) v4u *gptr_v4u;
-__device__ __forceinline__ void load_unit_k(const AttnParams &p, int b, int hk, const PidPair &pid, int t_unit, int T,
-                                            int lane, UnitCodes &u) {
-    const int q4 = lane >> 4, c16 = lane & 15;
-    const int inpage = t_unit - ((t_unit >> p.ps_shift) << p.ps_shift);          // a unit never straddles a page
-    const gptr_u8 base = uniform_ptr(p.k_paged ? p.k_codes + (((pid.k << p.ps_shift) + inpage) << 6)
-                                                : p.k_codes + b * p.k_sb + hk * p.k_sh + ((long long)t_unit << 6));
-    const int lim = T - 1 - t_unit;                  // rows past token T-1 re-read it (stay inside the store; masked later)
-#pragma unroll
-    for (int g2 = 0; g2 < 2; ++g2) {
-        const int row = min(16 * g2 + c16, lim);
-        const unsigned off = ((unsigned)row << 6) + 16u * q4;
-        u.k[g2] = *(gptr_v4u)(base + off);
-    }
-}
-__device__ __forceinline__ void load_unit_v(const AttnParams &p, const PidPair &pid, int t_unit, int lane, UnitCodes &u) {
-    const int h2i = lane >> 5, c32 = lane & 31;
-    const int inpage = t_unit - ((t_unit >> p.ps_shift) << p.ps_shift);
-    const gptr_u8 base = uniform_ptr(p.v_codes + (pid.v << (6 + p.ps_shift)) + inpage);
-#pragma unroll
-    for (int n = 0; n < 2; ++n) {
-        const unsigned off = ((unsigned)(32 * n + c32) << p.ps_shift) + 16u * h2i;      // loop-invariant per lane
-        u.v[n] = *(gptr_v4u)(base + off);
-    }
-}
 typedef const __attribute__((address_space(1))) v2u *gptr_v2u;
-__device__ __forceinline__ void load_unit_k(const AttnParams &p, int b, int hk, const PidPair &pid, int t_unit, int T,
-                                            int lane, UnitCodes32 &u) {
-    const int q4 = lane >> 4, c16 = lane & 15;
-    const int inpage = t_unit - ((t_unit >> p.ps_shift) << p.ps_shift);
-    const gptr_u8 base = uniform_ptr(p.k_paged ? p.k_codes + (((pid.k << p.ps_shift) + inpage) << 5)
-                                               : p.k_codes + b * p.k_sb + hk * p.k_sh + ((long long)t_unit << 5));
-    const int lim = T - 1 - t_unit;
-#pragma unroll
-    for (int g2 = 0; g2 < 2; ++g2) {
-        const int row = min(16 * g2 + c16, lim);
-        const unsigned off = ((unsigned)row << 5) + 8u * q4;
-        u.k[g2] = *(gptr_v2u)(base + off);
-    }
-}
-__device__ __forceinline__ void load_unit_v(const AttnParams &p, const PidPair &pid, int t_unit, int lane, UnitCodes32 &u) {
-    const int h2i = lane >> 5, c32 = lane & 31;
-    const int inpage = t_unit - ((t_unit >> p.ps_shift) << p.ps_shift);
-    const gptr_u8 base = uniform_ptr(p.v_codes + (pid.v << (5 + p.ps_shift)) + inpage);
-    const unsigned off = ((unsigned)c32 << p.ps_shift) + 16u * h2i;
-    u.v[0] = *(gptr_v4u)(base + off);
-}
-template <class Unit>
-__device__ __forceinline__ void load_unit_pid(const AttnParams &p, int b, int hk, const PidPair &pid, int t_unit, int T,
-                                              int lane, Unit &u) {
-    load_unit_k(p, b, hk, pid, t_unit, T, lane, u);
-    load_unit_v(p, pid, t_unit, lane, u);
-}
-template <class Unit>
-__device__ __forceinline__ void load_unit(const AttnParams &p, int b, int hk, int bh, int t_unit, int T,
-                                          int lane, Unit &u) {
-    load_unit_pid(p, b, hk, load_pids(p, bh, t_unit >> p.ps_shift), t_unit, T, lane, u);
-}
-
-// Four centroid gathers of one score step: code bytes w -> A operand words (subspaces 4s..4s+3 of this lane's quarter).
-__device__ __forceinline__ void k_gather(unsigned w, unsigned base, unsigned (&a)[4]) {
-    a[0] = lds32(base + 0 * 1024 + ((w & 0xffu) << 2));
-    a[1] = lds32(base + 1 * 1024 + (((w >> 8) & 0xffu) << 2));
-    a[2] = lds32(base + 2 * 1024 + (((w >> 16) & 0xffu) << 2));
-    a[3] = lds32(base + 3 * 1024 + ((w >> 24) << 2));
-}
-
-// Scores of one 32-token unit (MFMA 16x16x32): sc[g2*4 + rho] = scaled score (exp2 domain) of token
-// 16*g2 + 4*q' + rho for the head of this lane's column (lane & 15); -inf beyond the split's last token.
-// 8 steps (g2, s) of 4 gathers + 1 MFMA; the gathers run kDepth steps ahead of the MFMAs so that the LDS
-// queue of this wave never drains (two waves per SIMD do not hide an LDS round trip per step).
-template <bool MASK>
-__device__ __forceinline__ void score_unit(const v4u (&kc)[2], const v8f16 (&qb)[4], int t_unit, int t_end,
-                                           float scale_log2e, int lane, unsigned kbase, float (&sc)[8]) {
-    const int q4 = lane >> 4;
-    constexpr int kDepth = 3;
-    unsigned a[8][4];
-#pragma unroll
-    for (int st = 0; st < kDepth; ++st) k_gather(kc[st >> 2][st & 3], kbase + (st & 3) * 4096, a[st]);
-    v4f32 D[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-    for (int st = 0; st < 8; ++st) {
-        if (st + kDepth < 8) k_gather(kc[(st + kDepth) >> 2][(st + kDepth) & 3], kbase + ((st + kDepth) & 3) * 4096, a[st + kDepth]);
-        D[st >> 2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_v8f16(a[st][0], a[st][1], a[st][2], a[st][3]), qb[st & 3],
-                                                            D[st >> 2], 0, 0, 0);
-    }
-#pragma unroll
-    for (int g2 = 0; g2 < 2; ++g2)
-#pragma unroll
-        for (int rho = 0; rho < 4; ++rho) {
-            const float v = D[g2][rho] * scale_log2e;
-            if (MASK) {
-                const int tok = t_unit + 16 * g2 + 4 * q4 + rho;
-                sc[g2 * 4 + rho] = tok < t_end ? v : -INFINITY;
-            } else {
-                sc[g2 * 4 + rho] = v;
-            }
-        }
-}
-
-// Values of one 32-token unit: O[n][kk] (rows = heads, cols = subspaces 32n..32n+31) += P (heads x tokens) * Vhat.
-// pr[g2*4 + rho] = probability of token 16*g2 + 4*q' + rho for the head of this lane's column.
-__device__ __forceinline__ void value_unit(const v4u (&vc)[2], const float (&pr)[8], unsigned vconst0, unsigned vconst1,
-                                           v16f32 (&O)[2][2]) {
-    // probabilities -> A operand of the value MFMA (rows = heads, K = 16 tokens per step)
-    // pk[g2][i]: tokens 16*g2 + 4*q' + {2i, 2i+1} as packed fp16
-    unsigned pk[2][2];
-#pragma unroll
-    for (int g2 = 0; g2 < 2; ++g2)
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            h2 t = {(f16)pr[g2 * 4 + 2 * i], (f16)pr[g2 * 4 + 2 * i + 1]};
-            pk[g2][i] = __builtin_bit_cast(unsigned, t);
-        }
-    // step s uses tokens 16h + 8s + j: rows q' = 2s (j<4) and 2s+1 (j>=4) of group h
-    unsigned P[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const v2u x = __builtin_amdgcn_permlane32_swap(pk[0][i], pk[1][i], false, false);
-        // x[0] = {grp0 rows 0,1 | grp1 rows 0,1}  (step 0)   x[1] = {grp0 rows 2,3 | grp1 rows 2,3}  (step 1)
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const v2u y = swap16_self(x[s]);
-            // y[0] rows {0,0,2,2} of x[s] ; y[1] rows {1,1,3,3} of x[s]
-            P[s][i] = y[0];
-            P[s][2 + i] = y[1];
-        }
-    }
-    // 4 steps (n, s) of 8 gathers + 2 MFMAs; the gathers of the next step are issued before this step's MFMAs
-    unsigned e[4][8];
-#define V_GATHER(ST)                                                                                               \
-    {                                                                                                              \
-        const unsigned vconst = ((ST) >> 1) ? vconst1 : vconst0;                                                   \
-        const unsigned w0 = vc[(ST) >> 1][2 * ((ST) & 1)], w1 = vc[(ST) >> 1][2 * ((ST) & 1) + 1];                 \
-        e[ST][0] = lds32(__builtin_amdgcn_perm(w0, vconst, 0x03020400u));                                          \
-        e[ST][1] = lds32(__builtin_amdgcn_perm(w0, vconst, 0x03020500u));                                          \
-        e[ST][2] = lds32(__builtin_amdgcn_perm(w0, vconst, 0x03020600u));                                          \
-        e[ST][3] = lds32(__builtin_amdgcn_perm(w0, vconst, 0x03020700u));                                          \
-        e[ST][4] = lds32(__builtin_amdgcn_perm(w1, vconst, 0x03020400u));                                          \
-        e[ST][5] = lds32(__builtin_amdgcn_perm(w1, vconst, 0x03020500u));                                          \
-        e[ST][6] = lds32(__builtin_amdgcn_perm(w1, vconst, 0x03020600u));                                          \
-        e[ST][7] = lds32(__builtin_amdgcn_perm(w1, vconst, 0x03020700u));                                          \
-    }
-    V_GATHER(0)
-#pragma unroll
-    for (int st = 0; st < 4; ++st) {
-        if (st == 0) V_GATHER(1)
-        if (st == 1) V_GATHER(2)
-        if (st == 2) V_GATHER(3)
-        const int n = st >> 1, sidx = st & 1;
-        const v8f16 B0 = as_v8f16(__builtin_amdgcn_perm(e[st][1], e[st][0], 0x05040100u), __builtin_amdgcn_perm(e[st][3], e[st][2], 0x05040100u),
-                                  __builtin_amdgcn_perm(e[st][5], e[st][4], 0x05040100u), __builtin_amdgcn_perm(e[st][7], e[st][6], 0x05040100u));
-        const v8f16 B1 = as_v8f16(__builtin_amdgcn_perm(e[st][1], e[st][0], 0x07060302u), __builtin_amdgcn_perm(e[st][3], e[st][2], 0x07060302u),
-                                  __builtin_amdgcn_perm(e[st][5], e[st][4], 0x07060302u), __builtin_amdgcn_perm(e[st][7], e[st][6], 0x07060302u));
-        const v8f16 A = as_v8f16(P[sidx][0], P[sidx][1], P[sidx][2], P[sidx][3]);
-        O[n][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, B0, O[n][0], 0, 0, 0);
-        O[n][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, B1, O[n][1], 0, 0, 0);
-    }
-#undef V_GATHER
-}
-
-// ---- M = 32 forms of the two unit functions ------------------------------------------------------------
-// Scores: lane (q4, token) holds 8 code bytes = subspaces 8*q4 .. 8*q4+7; step s uses subspaces 8*q4 + 2s, +1 =
-// dims 32*q4 + 8s .. +8 (the SAME dim <-> k mapping as M = 64, so the query operand qb is shared); two 8-byte
-// gathers per step.
-__device__ __forceinline__ void k_gather32(unsigned w, int s, unsigned base, unsigned (&a)[4]) {
-    const unsigned sh = 16 * (s & 1);
-    const v2u lo = lds64(base + 0 * 2048 + (((w >> sh) & 0xffu) << 3));
-    const v2u hi = lds64(base + 1 * 2048 + (((w >> (sh + 8)) & 0xffu) << 3));
-    a[0] = lo[0]; a[1] = lo[1]; a[2] = hi[0]; a[3] = hi[1];
-}
-template <bool MASK>
-__device__ __forceinline__ void score_unit(const v2u (&kc)[2], const v8f16 (&qb)[4], int t_unit, int t_end,
-                                           float scale_log2e, int lane, unsigned kbase, float (&sc)[8]) {
-    const int q4 = lane >> 4;
-    constexpr int kDepth = 3;
-    unsigned a[8][4];
-#pragma unroll
-    for (int st = 0; st < kDepth; ++st) k_gather32(kc[st >> 2][(st & 3) >> 1], st & 3, kbase + (st & 3) * 4096, a[st]);
-    v4f32 D[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-    for (int st = 0; st < 8; ++st) {
-        if (st + kDepth < 8) {
-            const int t = st + kDepth;
-            k_gather32(kc[t >> 2][(t & 3) >> 1], t & 3, kbase + (t & 3) * 4096, a[t]);
-        }
-        D[st >> 2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(as_v8f16(a[st][0], a[st][1], a[st][2], a[st][3]), qb[st & 3],
-                                                            D[st >> 2], 0, 0, 0);
-    }
-#pragma unroll
-    for (int g2 = 0; g2 < 2; ++g2)
-#pragma unroll
-        for (int rho = 0; rho < 4; ++rho) {
-            const float v = D[g2][rho] * scale_log2e;
-            if (MASK) {
-                const int tok = t_unit + 16 * g2 + 4 * q4 + rho;
-                sc[g2 * 4 + rho] = tok < t_end ? v : -INFINITY;
-            } else {
-                sc[g2 * 4 + rho] = v;
-            }
-        }
-}
-// Values: lane (h, m): 16 token bytes of subspace m; an 8-byte gather brings the 4 dims of one (token, m); tile
-// O[i][j] holds dim 4m + 2i + j of the 32 subspaces (cols).  2 steps of 8 gathers + 16 packs + 4 MFMAs.
-__device__ __forceinline__ void value_unit(const v4u (&vc)[1], const float (&pr)[8], unsigned vconst0, unsigned /*vconst1*/,
-                                           v16f32 (&O)[2][2]) {
-    unsigned pk[2][2];
-#pragma unroll
-    for (int g2 = 0; g2 < 2; ++g2)
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            h2 t = {(f16)pr[g2 * 4 + 2 * i], (f16)pr[g2 * 4 + 2 * i + 1]};
-            pk[g2][i] = __builtin_bit_cast(unsigned, t);
-        }
-    unsigned P[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const v2u x = __builtin_amdgcn_permlane32_swap(pk[0][i], pk[1][i], false, false);
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            const v2u y = swap16_self(x[s]);
-            P[s][i] = y[0];
-            P[s][2 + i] = y[1];
-        }
-    }
-    unsigned e[2][2][8];      // [step][dword of the entry][token]
-#define V_GATHER32(ST)                                                                                             \
-    {                                                                                                              \
-        const unsigned w0 = vc[0][2 * (ST)], w1 = vc[0][2 * (ST) + 1];                                             \
-        const unsigned sel[4] = {0x03020400u, 0x03020500u, 0x03020600u, 0x03020700u};                              \
-        _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                                            \
-            const v2u t = lds64(__builtin_amdgcn_perm(j < 4 ? w0 : w1, vconst0, sel[j & 3]));                      \
-            e[ST][0][j] = t[0];                                                                                    \
-            e[ST][1][j] = t[1];                                                                                    \
-        }                                                                                                          \
-    }
-    V_GATHER32(0)
-#pragma unroll
-    for (int st = 0; st < 2; ++st) {
-        if (st == 0) V_GATHER32(1)
-        const v8f16 A = as_v8f16(P[st][0], P[st][1], P[st][2], P[st][3]);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const unsigned(&x)[8] = e[st][i];
-            const v8f16 B0 = as_v8f16(__builtin_amdgcn_perm(x[1], x[0], 0x05040100u), __builtin_amdgcn_perm(x[3], x[2], 0x05040100u),
-                                      __builtin_amdgcn_perm(x[5], x[4], 0x05040100u), __builtin_amdgcn_perm(x[7], x[6], 0x05040100u));
-            const v8f16 B1 = as_v8f16(__builtin_amdgcn_perm(x[1], x[0], 0x07060302u), __builtin_amdgcn_perm(x[3], x[2], 0x07060302u),
-                                      __builtin_amdgcn_perm(x[5], x[4], 0x07060302u), __builtin_amdgcn_perm(x[7], x[6], 0x07060302u));
-            O[i][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, B0, O[i][0], 0, 0, 0);
-            O[i][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A, B1, O[i][1], 0, 0, 0);
-        }
-    }
-#undef V_GATHER32
-}
 
 // ---- residual window -------------------------------------------------------------------------------
 // The window rows j = split, split + nsplit, ... < r of a split are dealt to its waves in runs of kResRows: wave w
 // owns list entries idx = 16 w + i, i < kResRows (round 3; rounds 1-2 dealt them round-robin, idx = w + 8 i: with 4-7
 // rows per split that made 4-7 waves load a whole 16-row tile - 12 requests each in the kernel's front - for ONE row;
-// now the older, faster wave 0 takes them all), as ONE 16-row MFMA tile that rides along with the code
-// units of the first group: scores with A = the fp16 K rows themselves, values with B = the fp16 V rows
+// now the older, faster wave 0 takes them all), as ONE 16-row MFMA tile that the wave runs before its code
+// units: scores with A = the fp16 K rows themselves, values with B = the fp16 V rows
 // (k = 16 rows, cols = 32 subspaces; even / odd dims by v_perm like the looked-up centroids).  Rows past the
 // list re-read the wave's first row and are masked to -inf.
 struct ResTile {
@@ -1157,240 +837,6 @@ __device__ __forceinline__ void merge_and_publish(const AttnParams &p, char *sme
 #undef STAMP
 }
 
-template <bool HAS_CODES, int MS = 64>
-__global__ __launch_bounds__(kNW * 64, 2) void attn_mfma_kernel(AttnParams p) {
-    typedef typename std::conditional<MS == 64, UnitCodes, UnitCodes32>::type Unit;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int split = blockIdx.x;
-    const int bh = blockIdx.y;
-    const int b = bh / p.nh_k, hk = bh % p.nh_k;
-    const int G = p.G;
-    typedef int v4i __attribute__((ext_vector_type(4)));
-    v4i dl = {p.T, p.r, p.rstart, 0};
-    if ((unsigned)(size_t)(__attribute__((address_space(3))) char *)smem != 0u) __builtin_trap();
-    const bool dbg_on = p.dbg != nullptr;
-#define STAMP(i) stamp_lds(dbg_on, lane, wave, i)
-    stamp_lds_clear(dbg_on, lane, wave);
-    STAMP(0);
-    const int q4 = lane >> 4, c16 = lane & 15;
-
-    // B operand of the score MFMA: the query heads (cols), K = 32 dims per step.
-    v8f16 qb[4];
-    {
-        const f16 *qv = p.q + ((long long)b * p.nh + head0(p, hk) + (c16 < G ? c16 : 0)) * 128 + 32 * q4;
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            v4u t = *(const v4u *)(qv + 8 * s);
-            if (c16 >= G) t = v4u{0, 0, 0, 0};
-            qb[s] = __builtin_bit_cast(v8f16, t);
-        }
-    }
-    // fused append: the new token's K/V row is parked in the window by the last wave of split 0; its two
-    // loads are requested here (oldest loads of that wave) and stored after the first score pass
-    const bool append_wave = p.k_new && split == 0 && wave == kNW - 1;      // wave-uniform
-    h2 new_k = {}, new_v = {};
-    if (append_wave) {
-        new_k = *(const h2 *)(p.k_new + (long long)bh * 128 + 2 * lane);
-        new_v = *(const h2 *)(p.v_new + (long long)bh * 128 + 2 * lane);
-    }
-    // ---- K codebook (8 x 16 B per thread): requested before anything that depends on a length.  Every
-    //      workgroup needs the same 64 KiB at the same time: each starts at its own chunk so that the CUs
-    //      do not walk the L2 channels in lockstep. ----
-    v4u tabk[8];
-    const int rot = (blockIdx.x + 5 * blockIdx.y) & 7;
-    {
-        const v4u *ks = (const v4u *)p.k_tab;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) tabk[i] = ks[((i + rot) & 7) * (kNW * 64) + tid];
-    }
-    if (p.dev_lengths)      // issue + wait in ONE statement (see load_pids4), after q and the table have been requested
-        asm volatile("s_load_dwordx4 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=&s"(dl) : "s"(p.dev_lengths), "s"((unsigned)b * 16u) : "memory");
-    int T = dl[0], r_old = dl[1], rstart = dl[2];
-    clamp_lengths(p, T, r_old, rstart);            // T <= the host bound the grid was sized for; r, start inside the window
-    const int r = r_old + (p.k_new ? 1 : 0);       // fused append: the new token is window row r_old
-    // The T tokens that are actually there (device-resident lengths: the host sized the grid for its BOUND on T) are
-    // dealt to the nsplit splits in whole 32-token units, as evenly as units allow: the first (units % nsplit) splits
-    // carry one unit more.  (Uniform split lengths rounded up to a page left the last splits short or empty and made
-    // most waves of the others run a fifth unit as soon as T passed 32 x 1024.)
-    const int units_total = (T + 31) >> 5;
-    const int units_q = units_total / p.nsplit, units_r = units_total - units_q * p.nsplit;
-    const int u_begin = split * units_q + (split < units_r ? split : units_r);
-    const int t_begin = u_begin << 5;
-    const int t_end = min((u_begin + units_q + (split < units_r ? 1 : 0)) << 5, T);
-    const int n_units = (t_end - t_begin + 31) >> 5;
-    const int n_mine = n_units > wave ? (n_units - wave + kNW - 1) / kNW : 0;   // units of this wave
-    const int n_pass = (n_mine + kRing - 1) / kRing;
-    // unit j of this wave starts at token t_begin + 32*(wave + j*kNW); slots past the last unit re-request
-    // the unit that holds token T-1 (HAS_CODES guarantees the host bound T >= 1; with device-resident
-    // lengths a runtime T of 0 reads page 0, which must be a valid page: million_hip.h)
-    const int T_ld = T > 0 ? T : 1;
-    const int t_last = (T_ld - 1) & ~31;
-#define UNIT_T(j) ((j) < n_mine ? t_begin + 32 * (wave + (j) * kNW) : t_last)
-
-    // ---- residual window rows of this split (list j = split, split + nsplit, ... < r), dealt to the waves
-    //      round-robin; this wave's tile is requested BEFORE the code bytes: the counted wait in front of the
-    //      K-codebook store then covers these few L2-resident rows, not the HBM-bound code loads behind them ----
-    const int rcnt = split < r ? (r - split + p.nsplit - 1) / p.nsplit : 0;
-    const bool has_res = kResRows * wave < rcnt;       // wave-uniform
-    const f16 *kr = p.k_res + b * p.res_sb + hk * p.res_sh;
-    const f16 *vr = p.v_res + b * p.res_sb + hk * p.res_sh;
-    ResTile rt;
-    if (has_res) load_res_tile<MS>(p, bh, kr, vr, wave, rcnt, split, rstart, r_old, lane, rt);
-
-    // ---- the K bytes of the whole ring, then the K codebook goes to LDS ----
-    Unit ring[kRing];
-    PidPair pid4[kRing];
-    if (HAS_CODES) {
-        int pg[kRing];
-#pragma unroll
-        for (int k = 0; k < kRing; ++k) pg[k] = UNIT_T(k) >> p.ps_shift;
-        load_pids4(p, bh, pg, pid4);        // one scalar round trip, after q and the K codebook have been requested
-#pragma unroll
-        for (int k = 0; k < kRing; ++k) load_unit_k(p, b, hk, pid4[k], UNIT_T(k), T_ld, lane, ring[k]);
-    }
-    STAMP(7);
-    {
-        v4u *ld = (v4u *)smem;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) ld[((i + rot) & 7) * (kNW * 64) + tid] = tabk[i];
-    }
-    STAMP(8);
-    __syncthreads();     // no LDS-DMA in flight: lgkmcnt(0) + s_barrier, the code bytes stay in flight
-    STAMP(1);
-    tail_mark_xcd(p, bh, split, wave, lane);      // this split's slot of the XCD census (tail)
-
-    // ---- everything else is requested BETWEEN the score units of the first group (the K bytes and the K
-    //      codebook are there; a wave that first issued all its remaining loads would sit in a blocked issue
-    //      sequence while the LDS pipe idles): after unit 0 the V bytes of units 0-1, after unit 1 those of
-    //      units 2-3, after unit 2 the V codebook ----
-    v4u tabv[8];
-#define ISSUE_AFTER_UNIT(K)                                                                                        \
-    if ((K) == 0) {                                                                                                \
-        if (HAS_CODES) {                                                                                           \
-            _Pragma("unroll") for (int k2 = 0; k2 < kRing / 2; ++k2)                                               \
-                load_unit_v(p, pid4[k2], UNIT_T(k2), lane, ring[k2]);                                              \
-        }                                                                                                          \
-    } else if ((K) == 1) {                                                                                         \
-        if (HAS_CODES) {                                                                                           \
-            _Pragma("unroll") for (int k2 = kRing / 2; k2 < kRing; ++k2)                                           \
-                load_unit_v(p, pid4[k2], UNIT_T(k2), lane, ring[k2]);                                              \
-        }                                                                                                          \
-    } else if ((K) == 2) {                                                                                         \
-        const v4u *vs = (const v4u *)p.v_tab_col;                                                                  \
-        _Pragma("unroll") for (int i = 0; i < 8; ++i) tabv[i] = vs[((i + rot) & 7) * (kNW * 64) + tid];            \
-    }
-
-    float m_run = -INFINITY, l_run = 0.f;
-    v16f32 O[2][2];
-#pragma unroll
-    for (int n = 0; n < 2; ++n)
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) O[n][kk][i] = 0.f;
-    STAMP(2);
-
-    const unsigned kbase = (unsigned)q4 * 16u * 1024u;                 // K row image: m = 16*q4 + ...
-    // V col image: entry (c, m) at c*256 + m*(2*d_m); the code byte goes to address bits 8..15 by v_perm
-    const unsigned vconst0 = (unsigned)kVBase | ((unsigned)(lane & 31) << (MS == 64 ? 2 : 3));        // m = c
-    const unsigned vconst1 = (unsigned)kVBase | ((unsigned)((lane & 31) + 32) << 2);  // m = 32 + c (M = 64 only)
-
-    // ---- groups of kRing units: SCORE pass for the whole group (K codebook only), one softmax update per
-    //      group, then the VALUE pass.  The first group also carries this wave's residual tile, and the V
-    //      codebook goes to LDS between its two passes, so the first scores are computed while V is arriving. ----
-#define GROUP(PASS, MASKV, FIRST, REFILL)                                                                          \
-    {                                                                                                              \
-        float sc[kRing][8], scr[4];                                                                                \
-        /* page ids of the units this group refills the ring with: ONE scalar round trip per group, up front (a   */  \
-        /* per-unit s_load + lgkmcnt(0) inside the value pass drained the LDS gather queue four times per group)  */  \
-        PidPair pidr[kRing];                                                                                       \
-        if (HAS_CODES && (REFILL)) {                                                                               \
-            int pgr[kRing];                                                                                        \
-            _Pragma("unroll") for (int k = 0; k < kRing; ++k) pgr[k] = UNIT_T(((PASS) + 1) * kRing + k) >> p.ps_shift; \
-            load_pids4(p, bh, pgr, pidr);                                                                          \
-        }                                                                                                          \
-        _Pragma("unroll") for (int k = 0; k < kRing; ++k) {                                                        \
-            const int j = (PASS) * kRing + k;                                                                      \
-            if (HAS_CODES && j < n_mine)                                                                           \
-                score_unit<MASKV>(ring[k].k, qb, t_begin + 32 * (wave + j * kNW), t_end, p.scale_log2e, lane,      \
-                                  kbase, sc[k]);                                                                   \
-            else                                                                                                   \
-                _Pragma("unroll") for (int i = 0; i < 8; ++i) sc[k][i] = -INFINITY;                                \
-            if (FIRST) {                                                                                           \
-                __builtin_amdgcn_sched_barrier(0);                                                                 \
-                STAMP(16 + 2 * k);                                                                                 \
-                ISSUE_AFTER_UNIT(k)                                                                                \
-                STAMP(17 + 2 * k);                                                                                 \
-                __builtin_amdgcn_sched_barrier(0);                                                                 \
-            }                                                                                                      \
-        }                                                                                                          \
-        if ((FIRST) && has_res) score_res_tile(rt, qb, p.scale_log2e, wave, rcnt, lane, scr);                      \
-        else _Pragma("unroll") for (int i = 0; i < 4; ++i) scr[i] = -INFINITY;                                     \
-        float mx = fmaxf(fmaxf(scr[0], scr[1]), fmaxf(scr[2], scr[3]));                                            \
-        _Pragma("unroll") for (int k = 0; k < kRing; ++k)                                                          \
-            _Pragma("unroll") for (int i = 0; i < 8; ++i) mx = fmaxf(mx, sc[k][i]);                                \
-        mx = rows_max(mx);                                                                                         \
-        const float m_new = fmaxf(m_run, mx);                                                                      \
-        const float m_safe = m_new > -INFINITY ? m_new : 0.f;                                                      \
-        const float alpha = fast_exp2(m_run - m_safe);                                                             \
-        if (!(FIRST) && __any(m_new > m_run && m_run > -INFINITY)) {                                               \
-            rescale_heads(O, alpha, G, lane);                                                                      \
-        }                                                                                                          \
-        float ls = 0.f;                                                                                            \
-        _Pragma("unroll") for (int k = 0; k < kRing; ++k)                                                          \
-            _Pragma("unroll") for (int i = 0; i < 8; ++i) {                                                        \
-                sc[k][i] = fast_exp2(sc[k][i] - m_safe);                                                           \
-                ls += sc[k][i];                                                                                    \
-            }                                                                                                      \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                            \
-            scr[i] = fast_exp2(scr[i] - m_safe);                                                                   \
-            ls += scr[i];                                                                                          \
-        }                                                                                                          \
-        l_run = l_run * alpha + ls;                                                                                \
-        m_run = m_new;                                                                                             \
-        if (FIRST) {                                                                                               \
-            STAMP(24);                                                                                             \
-            if (append_wave) {                                                                                     \
-                int row_n = rstart + r_old;                                                                        \
-                row_n = row_n >= p.rcap ? row_n - p.rcap : row_n;                                                  \
-                const long long o = b * p.res_sb + hk * p.res_sh + (long long)row_n * 128 + 2 * lane;              \
-                *(h2 *)(p.k_res_w + o) = new_k;                                                                    \
-                *(h2 *)(p.v_res_w + o) = new_v;                                                                    \
-            }                                                                                                      \
-            v4u *ld = (v4u *)(smem + kVBase);                                                                      \
-            _Pragma("unroll") for (int i = 0; i < 8; ++i) ld[((i + rot) & 7) * (kNW * 64) + tid] = tabv[i];        \
-            STAMP(12);                                                                                             \
-            __syncthreads();                                                                                       \
-            STAMP(13);                                                                                             \
-            if (has_res) value_res_tile(rt, scr, O);                                                               \
-        }                                                                                                          \
-        _Pragma("unroll") for (int k = 0; k < kRing; ++k) {                                                        \
-            const int j = (PASS) * kRing + k;                                                                      \
-            if (HAS_CODES && j < n_mine) value_unit(ring[k].v, sc[k], vconst0, vconst1, O);                        \
-            if (HAS_CODES && (REFILL)) load_unit_pid(p, b, hk, pidr[k], UNIT_T(j + kRing), T_ld, lane, ring[k]);   \
-        }                                                                                                          \
-    }
-
-    // group 0 (every wave, also one without units: it carries the V-codebook barrier); masked because it
-    // may be the last; refills only if more groups follow
-    GROUP(0, true, true, n_pass > 1)
-    // middle groups: full units, unconditional refills (counted waits, see the note above load_unit)
-    for (int pass = 1; pass + 1 < n_pass; ++pass) GROUP(pass, false, false, true)
-    // last group: masked, no refills
-    if (n_pass > 1) GROUP(n_pass - 1, true, false, false)
-#undef GROUP
-#undef ISSUE_AFTER_UNIT
-#undef UNIT_T
-    STAMP(3);
-    TailReq treq;
-    treq.idx = 0; treq.gen = 0; treq.cen = 0; treq.base = 0; treq.done = false;
-    merge_and_publish<MS>(p, smem, b, hk, split, G, tid, lane, wave, dbg_on, O, m_run, l_run, treq);
-#undef STAMP
-}
-
 // ---- value side of a 32-token unit in pieces, for the pipelined kernel ---------------------------------
 // The A operand of the value MFMA (rows = heads, K = 16 tokens) wants, in lane (h, head), the probabilities of tokens
 // 16h + 8s + j (token step s, j = 0..7).  The score MFMAs leave pr[4*g2 + rho] = row 4q' + rho of score tile g2 in lane
@@ -1449,11 +895,11 @@ __device__ __forceinline__ void v_step(const unsigned (&e)[8], const unsigned (&
 // =====================================================================================================
 // Pieces of the pipelined schedule (used by the streaming kernel below).
 //
-// In the grouped kernel above a wave runs "score pass of 4 units" (LDS-bound: ~7 LDS cycles per random K gather), then
-// "value pass of 4 units" (issue-bound: v_perm address + pack work and the 32x32x16 MFMAs), one after the other, and
-// with one workgroup per CU nothing else fills the idle pipe.  In the pipelined schedule both codebooks are in LDS
-// before the loop, the softmax is online PER UNIT, and the value steps of unit u are interleaved instruction by
-// instruction with the score stages of unit u + 1, so the LDS pipe and the vector/matrix issue work at the same time.
+// A score pass is LDS-bound (~7 LDS cycles per random K gather), a value pass issue-bound (v_perm address + pack work and
+// the 32x32x16 MFMAs); run one after the other, with one workgroup per CU, nothing else fills the idle pipe.  In the
+// pipelined schedule both codebooks are in LDS before the loop, the softmax is online PER UNIT, and the value steps of
+// unit u are interleaved instruction by instruction with the score stages of unit u + 1, so the LDS pipe and the
+// vector/matrix issue work at the same time.
 // =====================================================================================================
 // online softmax over N new scores of this lane's column (head): updates (m_run, l_run), rescales O when a
 // running maximum moves, turns the scores into probabilities in place
@@ -1713,7 +1159,7 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_stream_kernel(AttnParams p) 
 #pragma unroll
         for (int i = 0; i < NT; ++i) tabv[i] = vs[((i + rot) & (NT - 1)) * (kNW * 64) + tid];
     }
-    if (p.dev_lengths)      // issue + wait in ONE statement (see load_pids4); only the masks and the window depend on it
+    if (p.dev_lengths)      // issue + wait in ONE statement (see the note on the vector-memory queue); only the masks and the window depend on it
         asm volatile("s_load_dwordx4 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=&s"(dl) : "s"(p.dev_lengths), "s"((unsigned)b * 16u) : "memory");
     int T = dl[0], r_old = dl[1], rstart = dl[2];
     clamp_lengths(p, T, r_old, rstart);
@@ -2098,7 +1544,7 @@ int launch_rows_reduce_check(const float *in, float *out_max, float *out_sum, hi
 // flash_decoding_paged_v_*_Lt256 names) get at least ceil(rcap / 128) splits (mfma_splits).
 // d = 64 with M = 32 / 16 (d_m = 2 / 4) and M = 64 (d_m = 1: run as d_m = 2 with every odd dim zero, attn_lean.h): the lean kernel
 // only (round 5; before: the tile kernel) - 256 centroids, up to 4 query heads per kv head
-static int g_mfma_policy = 0, g_tail_test = 0, g_lean_off = 0;      // A/B and test knobs: see set_mfma_policy below
+static int g_tail_test = 0, g_lean_off = 0;      // test and A/B knobs: see set_mfma_policy below
 // 5 .. 16 query heads per kv head: the launch runs ceil(G / 4) VIRTUAL kv heads of ceil(G / parts) heads per real one (AttnParams::nhk_real;
 // the parts re-read the codes - from the XCD's L2 when they run together: the parts of a real head sit on one XCD).  The workspace
 // head is laid out for max(2048, bs * nh_k) pairs (million_api.hip): the virtual pairs must fit it.
@@ -2139,15 +1585,13 @@ int read_tail_faults() {
     return (int)n;
 }
 
-// A/B knob (million_set_force_generic 2): 0 = auto (streaming kernel wherever it applies), 1 = grouped kernel only (C = 128 has
-// no grouped form: the streaming kernel still runs there)
 // g_tail_test (million_set_force_generic 4 / 8): the merge helpers give up at once - the last arriver's take-over path, for
 // tests: 1 = every give-up bit is set in the prologue, 2 = the helpers give up through the real path (no polls, then the atomic)
 // g_lean_off (million_set_force_generic 16): the lean kernel's shapes stay on the streaming kernel (A/B, tests of the parity-V form)
 // development A/B (dev_switches.h; environment MILLION_M32_PACKED=1 in a MILLION_DEV_BUILD): M = 32 keeps the packed form at G <= 4
 // too.  The constant 0 in the product build.
 static const int g_mfma_form = MILLION_DEV_M32_PACKED();
-void set_mfma_policy(int policy) { g_mfma_policy = policy & 1; g_tail_test = (policy >> 1) & 3; g_lean_off = (policy >> 3) & 1; }
+void set_mfma_policy(int policy) { g_tail_test = policy & 3; g_lean_off = (policy >> 2) & 1; }
 
 // split policy: about one workgroup per CU; a split is at least 512 tokens long
 static int mfma_splits(const AttnParams &p, int cus) {
@@ -2164,9 +1608,9 @@ static int mfma_splits(const AttnParams &p, int cus) {
     if (ns < ns_window) ns = ns_window;      // (a split beyond the last unit just has no code units)
     // The streaming kernel preloads the page ids of a wave's first 64 rounds (one vector load, lane = round): a call with more
     // rounds per wave - many (b, kv head) pairs AND a long context, e.g. 16 requests x 8 kv heads at 40K tokens - gets more
-    // splits instead of the grouped kernel (round 4; rounds 2-3 dropped such calls to the grouped kernel, C = 128 even to the
-    // scalar one).  The grid then holds more workgroups than CUs; the tail's single merger waits only for workgroups that
-    // have started, so any dispatch order is fine.  64 splits x 64 rounds x 256 tokens = 1M tokens per (b, kv head).
+    // splits (round 4; rounds 2-3 dropped such calls to a slower fallback).  The grid then holds more workgroups than CUs; the
+    // tail's single merger waits only for workgroups that have started, so any dispatch order is fine.  64 splits x 64 rounds
+    // x 256 tokens = 1M tokens per (b, kv head); longer calls go to the tile kernel (plan_attn_mfma).
     if (p.T > 0 && (p.T + ns * 256 - 1) / (ns * 256) > 64) {
         while (ns < kMaxSplits && (p.T + ns * 256 - 1) / (ns * 256) > 64) ++ns;
         // more workgroups than CUs now: prefer a grid that is a whole number of chip-fulls (128 pairs: 4 splits = 2 x 256
@@ -2180,10 +1624,9 @@ static int mfma_splits(const AttnParams &p, int cus) {
 static bool mfma_stream_ok(const AttnParams &p, int ns) { return p.T > 0 && (p.T + ns * 256 - 1) / (ns * 256) <= 64; }
 
 // The instances this file launches, by form and layout mode (0: paged K with int32 ids and V through its id table, 1: row-major
-// K with dense V pages, 2: anything else).  The C = 128 forms and the grouped kernel have one instance for every mode.  The rows
+// K with dense V pages, 2: anything else).  The C = 128 forms have one instance for every mode.  The rows
 // keep the order in which the instances were first named before this table: it is their order in the code object.
 enum MfmaForm {
-    kGrouped64, kGrouped64NoCodes, kGrouped32, kGrouped32NoCodes,       // grouped kernel (NoCodes: T = 0)
     kStream64, kStream32, kStream32D4, kStream16,                       // streaming kernel (D4: the d_m = 4 form of M = 32; M = 16: d_m = 8)
     kStream16C128, kStream64C128, kStream32C128,
     kLean64, kLean64C128, kLean32, kLean32C128,                         // lean kernel, d = 128
@@ -2192,10 +1635,6 @@ enum MfmaForm {
 };
 #define MFMA_ONE(...) {(const void *)__VA_ARGS__, (const void *)__VA_ARGS__, (const void *)__VA_ARGS__}
 static const void *const kMfmaKernels[kMfmaForms][3] = {
-    MFMA_ONE(attn_mfma_kernel<true>),
-    MFMA_ONE(attn_mfma_kernel<false>),
-    MFMA_ONE(attn_mfma_kernel<true, 32>),
-    MFMA_ONE(attn_mfma_kernel<false, 32>),
     {(const void *)attn_stream_kernel<64, 0>, (const void *)attn_stream_kernel<64, 1>, (const void *)attn_stream_kernel<64, 2>},
     {(const void *)attn_stream_kernel<32, 0>, (const void *)attn_stream_kernel<32, 1>, (const void *)attn_stream_kernel<32, 2>},
     {(const void *)attn_stream_kernel<320, 0>, (const void *)attn_stream_kernel<320, 1>, (const void *)attn_stream_kernel<320, 2>},
@@ -2223,30 +1662,26 @@ bool plan_attn_mfma(const AttnParams &p_in, AttnPlan &plan) {
     AttnParams p = mfma_virtual(p_in);      // (the identity unless the shape runs as head parts)
     const int cus = device_cus();
     const int ns = mfma_splits(p, cus);
-    const bool stream_ok = mfma_stream_ok(p, ns);
+    if (!mfma_stream_ok(p, ns)) return false;      // T = 0 or more than 64 rounds per wave: the caller's next choice, the tile kernel
     // lean kernel (round 5): 64-token units, lane = token; C = 256 and (its table copy spreads the K rows) C = 128
-    const bool lean = g_mfma_policy == 0 && stream_ok && p.G <= 4 && p.page_size >= 64 && !g_lean_off;
+    const bool lean = p.G <= 4 && p.page_size >= 64 && !g_lean_off;
     int form;
-    if (p.d == 64) {              // the lean kernel or none of this file's (the caller's next choice: the tile kernel)
+    if (p.d == 64) {              // the lean kernel or none of this file's
         if (!lean) return false;
         form = p.M == 64 ? kLeanD64M64 : p.M == 32 ? kLeanD64M32 : kLeanD64M16;
-    } else if (p.M == 16) {       // d_m = 8 form: the streaming kernel or the tile kernel
-        if (!stream_ok || g_mfma_policy != 0) return false;
+    } else if (p.M == 16) {       // d_m = 8 form of the streaming kernel
         form = p.C == 128 ? kStream16C128 : kStream16;
     } else if (lean && (p.M == 64 || !(g_mfma_form & 1))) {
         form = p.M == 64 ? (p.C == 128 ? kLean64C128 : kLean64) : (p.C == 128 ? kLean32C128 : kLean32);
     } else if (p.C == 128) {      // 128 centroids per subspace (reference setup.py:15): streaming kernel by run-time layout flags only
-        if (!stream_ok) return false;      // T = 0 or more than 64 rounds per wave: the tile kernel
         form = p.M == 64 ? kStream64C128 : kStream32C128;
-    } else if (g_mfma_policy == 0 && stream_ok) {
+    } else {
         // d_m = 4 form at M = 32 and up to 4 query heads: query heads replicated over the column groups of the score tile
         form = p.M == 64 ? kStream64 : (p.G <= 4 && !(g_mfma_form & 1)) ? kStream32D4 : kStream32;
-    } else {
-        form = p.M == 64 ? (p.T > 0 ? kGrouped64 : kGrouped64NoCodes) : (p.T > 0 ? kGrouped32 : kGrouped32NoCodes);
     }
     const int mode = (p.k_paged && !p.v_identity && !p.ids64) ? 0 : (!p.k_paged && p.v_identity) ? 1 : 2;
     const int bh = p.bs * p.nh_k;
-    const int units = p.T > 0 ? (p.T + 31) / 32 : 1;
+    const int units = (p.T + 31) / 32;
     p.nsplit = ns;
     p.nslots = ns;
     p.split_len = 32 * ((units + ns - 1) / ns);
@@ -2259,7 +1694,7 @@ bool plan_attn_mfma(const AttnParams &p_in, AttnPlan &plan) {
 #if MILLION_EXP & 2
     p.nmerge = 1;      // A/B: the primary alone
 #endif
-    plan = {kMfmaKernels[form][mode], dim3(ns, bh), dim3(kNW * 64), kLdsBytes, p, form <= kGrouped32NoCodes ? 5 : 1, mfma_setup};
+    plan = {kMfmaKernels[form][mode], dim3(ns, bh), dim3(kNW * 64), kLdsBytes, p, 1, mfma_setup};
     return true;
 }
 

@@ -415,12 +415,12 @@ struct AttnPlan {
     dim3 grid, block;
     size_t lds;           // dynamic LDS bytes
     AttnParams p;         // the call as the kernel sees it: virtual kv heads, splits, slots, mergers
-    int kind;             // million_attn_kernel_kind before a transpose: 1 streaming / lean, 3 tile, 5 grouped, 0 scalar
+    int kind;             // million_attn_kernel_kind before a transpose: 1 streaming / lean, 3 tile, 0 scalar
     void (*setup)();      // raises the dynamic-LDS limit of the kernel's family, once per device (device_once)
 };
 // Each planner declines the call (false) or fills in the plan (true); plan_attn_generic takes every call and fails only for
 // shapes its LDS cannot hold (MILLION_ERR_SHAPE).  The order in which they are asked is million_api.hip's.
-bool plan_attn_mfma(const AttnParams &p, AttnPlan &plan);    // attn_mfma.hip: the lean, streaming and grouped kernels
+bool plan_attn_mfma(const AttnParams &p, AttnPlan &plan);    // attn_mfma.hip: the lean and streaming kernels
 bool plan_attn_tile(const AttnParams &p, AttnPlan &plan);    // attn_tile.hip
 int plan_attn_generic(const AttnParams &p, AttnPlan &plan);  // attn_generic.hip: the scalar kernel, up to kMaxG query heads
 int launch_encode(const EncParams &p, hipStream_t s);
@@ -437,6 +437,6 @@ bool device_once(int family);      // true exactly once per (current device, fam
 
 int read_tail_faults();             // attn_mfma.hip: merges that ran out of their poll bound since the last call (and clears)
 void set_prefill_policy(bool plain); // prefill.hip: million_set_force_generic(64) = the plain form of the prompt-attention kernel at d = 128 (A/B, tests)
-void set_mfma_policy(int policy);   // attn_mfma.hip: A/B and test knob behind million_set_force_generic(2 / 4 / 8): bit 0 = grouped kernel only, bits 2:1 = merge-helper test mode
+void set_mfma_policy(int policy);   // attn_mfma.hip: test and A/B knob behind million_set_force_generic(4 / 8 / 16): bits 1:0 = merge-helper test mode, bit 2 = lean kernel off
 
 }  // namespace million

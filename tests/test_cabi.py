@@ -66,11 +66,12 @@ def test_argument_validation_without_gpu(lib):
     assert lib.million_prepared_cents_bytes(64, 256, 2) == 64 * 256 * 2 * (2 * 2 + 4)   # two fp16 images + one fp32
 
 
-def test_kernel_kind_policy_without_gpu(lib):
+def test_kernel_kind_without_gpu(lib):
     """million_attn_kernel_kind is host logic (no launch): which kernel a descriptor gets.  Every batch x context of the
-    streaming kernel's shapes stays on it (kind 1) - calls with more than 64 rounds per wave get more splits instead of the
-    grouped (5) or scalar (0) kernel (Interface.template.cu:45,62-77: the reference has one kernel for any (bs, nh, T)) - and the
-    tile kernel (3) takes the rest of the build matrix with up to 16 query heads per kv head in one launch."""
+    streaming kernel's shapes stays on it (kind 1) up to 1M tokens per (b, kv head) - calls with more than 64 rounds per wave
+    get more splits instead of the scalar (0) kernel (Interface.template.cu:45,62-77: the reference has one kernel for any
+    (bs, nh, T)) - and the tile kernel (3) takes the rest of the build matrix with up to 16 query heads per kv head in one
+    launch, T = 0 and calls past 1M tokens included."""
     from million_amd import _lib
 
     def kind(bs, nh, nh_k, T, d=128, M=64, C=256, paged=True):
@@ -88,7 +89,8 @@ def test_kernel_kind_policy_without_gpu(lib):
     for bs, nh, nh_k, T, C in ((16, 32, 8, 40000, 256), (8, 32, 32, 32768, 256), (32, 32, 8, 20000, 128), (64, 32, 8, 131072, 256),
                                (1, 32, 8, 1000000, 256)):
         assert kind(bs, nh, nh_k, T, C=C) == 1, (bs, nh, nh_k, T, C)
-    assert kind(1, 32, 8, 0) == 5                      # nothing quantised yet: grouped MFMA kernel (window only)
+    assert kind(1, 4, 1, 1_100_000) == 3               # 68 rounds per wave at 64 splits: past the streaming limit, the tile kernel
+    assert kind(1, 32, 8, 0) == 3                      # nothing quantised yet: the tile kernel (window only)
     assert kind(1, 32, 8, 4096, paged=False) == 2      # the reference's 10-argument layout: V transposed first
     for d, M in ((128, 16), (64, 64), (64, 32), (64, 16)):
         # d_m = 8 form of the streaming kernel, and (round 5) the lean kernel's d = 64 forms (d_m = 1 / 2 / 4): up to 4 query heads per kv head
@@ -104,11 +106,15 @@ def test_kernel_kind_policy_without_gpu(lib):
     assert kind(64, 256, 32, 4096, d=128, M=16) == 3   # ... unless the virtual pairs outgrow the workspace head (2048 records)
     assert kind(1, 32, 8, 4096, C=64) == 0             # off the build matrix: scalar kernel
     # row-major K and V with nothing quantised yet: no transpose launch; V is handed on as (empty) transposed pages
-    assert kind(1, 32, 8, 0, paged=False) == 5                  # grouped MFMA kernel (window only)
+    assert kind(1, 32, 8, 0, paged=False) == 3                  # tile kernel (window only)
     assert kind(1, 32, 8, 0, d=64, M=32, paged=False) == 3      # tile kernel
-    lib.million_set_force_generic(2)                   # grouped kernel only - which has no C = 128 form: the streaming kernel stays
+    # 2 selected the retired grouped kernel: like any other unrecognised value it now means auto, at C = 256 and C = 128
+    calls = [dict(bs=1, nh=nh, nh_k=nh_k, T=T, M=M, C=C, paged=paged) for nh, nh_k, T in ((32, 8, 0), (32, 8, 4096), (4, 1, 1_100_000))
+             for M in (64, 32) for C in (256, 128) for paged in (True, False)]
+    auto = [kind(**c) for c in calls]
+    lib.million_set_force_generic(2)
     try:
-        assert kind(1, 32, 8, 4096, C=128) == 1
+        assert [kind(**c) for c in calls] == auto
     finally:
         lib.million_set_force_generic(0)
 

@@ -1437,7 +1437,7 @@ def test_attn_merge_every_workgroup_is_a_merger(env, oracle):
 @pytest.mark.parametrize("M,T,r,bs", [(64, 5000, 17, 1), (32, 40000, 128, 1), (64, 33000, 64, 2), (64, 0, 40, 1), (32, 100, 1, 1)])
 def test_attn_c128_on_mfma(M, T, r, bs, env, oracle):
     """C = 128 centroids per subspace (nbits 7; the reference compiles C in {128, 256}, setup.py:15) on the streaming MFMA
-    kernel: codebook images of half the size, same code layout; T = 0 falls back to the generic kernel."""
+    kernel: codebook images of half the size, same code layout; T = 0 goes to the tile kernel."""
     torch, ops = env
     from million_amd import _lib
     nh, nhk = 32, 8
@@ -1454,7 +1454,7 @@ def test_attn_c128_on_mfma(M, T, r, bs, env, oracle):
         assert _lib.load().million_attn_kernel_kind(ctypes.byref(desc)) == 1
 
 
-@pytest.mark.parametrize("policy", [0, 2, 1], ids=["stream", "grouped", "generic"])
+@pytest.mark.parametrize("policy", [0, 16, 1], ids=["lean", "stream", "generic"])
 def test_device_lengths_are_clamped_not_trusted(policy, env, oracle):
     """Device-resident lengths outside their ranges (T above the host bound, r above the window, ring start past the
     capacity, negative values) must become a shorter context / window, never an out-of-bounds read: the kernels clamp
@@ -1530,18 +1530,56 @@ def test_attn_tile_kernel_shapes(d, M, C, T, r, nh, nhk, bs, env, oracle):
         _check(_run_paged(torch, ops, oracle, c, M, C, 64, k_paged=False, i64=True), gold, "tile mixed i64")
 
 
-def test_attn_kernel_kind_mirrors_the_hand_back(env, oracle):
-    """million_attn_kernel_kind answers what a call WOULD run: d = 128 / M = 64 / C = 128 is the streaming kernel's shape, but
-    with nothing quantised yet (T = 0) plan_attn_mfma declines the call and the tile kernel takes it (kind 3); C = 256 keeps the
-    grouped MFMA kernel for that (kind 5)."""
+def test_attn_kernel_kind_mirrors_the_tile_hand_back(env, oracle):
+    """million_attn_kernel_kind answers what a call WOULD run: d = 128 / M = 64 is the streaming kernel's shape, but with
+    nothing quantised yet (T = 0) plan_attn_mfma declines the call and the tile kernel takes it (kind 3), at C = 128 and 256."""
     torch, ops = env
     c = synth.attn_case(7700, 1, 8, 2, 128, 64, 128, 0, 40, Lt=128)
     t = _dev(torch, c)
     kw = dict(nh_k=2, M=64, r=40, k_paged=True, v_paged=True, page_size=64)
     assert _kind(torch, ops, t["q"], t["k_res"], C=128, n_tokens=0, n_pages_cap=1, **kw) == 3
     assert _kind(torch, ops, t["q"], t["k_res"], C=128, n_tokens=4096, n_pages_cap=64, **kw) == 1
-    assert _kind(torch, ops, t["q"], t["k_res"], C=256, n_tokens=0, n_pages_cap=1, **kw) == 5      # grouped MFMA kernel (no code units)
+    assert _kind(torch, ops, t["q"], t["k_res"], C=256, n_tokens=0, n_pages_cap=1, **kw) == 3
     _check(_run_rowmajor(torch, ops, c, 64, 128), oracle.decode_attn(**c), "C=128 T=0 (tile kernel)")
+
+
+@pytest.mark.parametrize("paged", [True, False], ids=["paged", "rowmajor"])
+def test_attn_window_only_m32_c256_on_tile_kernel(paged, env, oracle):
+    """Nothing quantised yet (T = 0) at d = 128 / M = 32 / C = 256, the streaming kernel's shape: the tile kernel runs the
+    window (kind 3), as at C = 128.  M = 64 is the t0_r17 golden fixture."""
+    torch, ops = env
+    nh, nhk, ps, M, r = 32, 8, 64, 32, 17
+    c = synth.attn_case(7760, 1, nh, nhk, 128, M, 256, 0, r)
+    gold = oracle.decode_attn(**c)
+    t = _dev(torch, c)
+    if paged:
+        assert _kind(torch, ops, t["q"], t["k_res"], nh_k=nhk, M=M, C=256, n_tokens=0, r=r, k_paged=True, v_paged=True,
+                     page_size=ps, n_pages_cap=1) == 3
+        kp, vp = ops.prepare_cents(t["k_cents"], cache=False), ops.prepare_cents(t["v_cents"], cache=False)
+        ids_t = torch.zeros(1, nhk, 1, dtype=torch.int32, device="cuda")
+        pool = torch.zeros(1, ps, M, dtype=torch.uint8, device="cuda")
+        out = ops.pq_decode_attn(t["q"], pool, pool, kp, vp, t["k_res"], t["v_res"], r, M=M, C=256, n_tokens=0,
+                                 k_page_ids=ids_t, v_page_ids=ids_t, page_size=ps)
+        torch.cuda.synchronize()
+        _check(out.cpu().numpy(), gold, "T=0 M=32 paged")
+    else:
+        assert _kind(torch, ops, t["q"], t["k_res"], nh_k=nhk, M=M, C=256, n_tokens=0, r=r, k_codes=t["k_codes"],
+                     v_codes=t["v_codes"]) == 3
+        _check(_run_rowmajor(torch, ops, c, M, 256), gold, "T=0 M=32 rowmajor")
+
+
+def test_attn_past_the_streaming_limit_on_tile_kernel(env, oracle):
+    """More than 1M tokens per (b, kv head): 65 rounds per wave even at 64 splits, past the 64 page ids a streaming wave
+    preloads.  plan_attn_mfma declines the call and the tile kernel runs it (kind 3), checked against the oracle."""
+    torch, ops = env
+    nh, nhk, ps, M, r = 4, 1, 64, 64, 17
+    T = 1048576 + 4096
+    c = synth.attn_case(7770, 1, nh, nhk, 128, M, 256, T, r)
+    gold = oracle.decode_attn(**c)
+    t = _dev(torch, c)
+    assert _kind(torch, ops, t["q"], t["k_res"], nh_k=nhk, M=M, C=256, n_tokens=T, r=r, k_paged=True, v_paged=True,
+                 page_size=ps, n_pages_cap=T // ps) == 3
+    _check(_run_paged(torch, ops, oracle, c, M, 256, ps), gold, f"T={T} paged")
 
 
 @pytest.mark.parametrize("bs,nh,nhk,T,C,r", [(16, 32, 8, 40000, 256, 100), (8, 32, 32, 32768, 256, 17), (32, 32, 8, 20000, 128, 128)],
@@ -1559,7 +1597,7 @@ def test_attn_many_pairs_long_context_stay_on_streaming_kernel(bs, nh, nhk, T, C
     t = _dev(torch, c)
     desc = ops.make_attn_desc(t["q"], t["k_res"], nh_k=nhk, M=M, C=C, n_tokens=T, r=r, k_paged=True, v_paged=True,
                               page_size=ps, n_pages_cap=(T + ps - 1) // ps)
-    assert _lib.load().million_attn_kernel_kind(ctypes.byref(desc)) == 1      # streaming, not grouped (5) / scalar (0)
+    assert _lib.load().million_attn_kernel_kind(ctypes.byref(desc)) == 1      # streaming / lean, not tile (3) / scalar (0)
     _lib.load().million_debug_tail_faults()
     _check(_run_paged(torch, ops, oracle, c, M, C, ps), gold, f"bs={bs} nh_k={nhk} T={T} C={C}")
     assert _lib.load().million_debug_tail_faults() == 0

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Development helper: time the fused decode-attention launch of ONE library build at several shapes (back-to-back
-launch period over rotating layers, HIP events) and compare its output with the grouped kernel's.
+launch period over rotating layers, HIP events) and compare its output with the scalar kernel's.
     MILLION_HIP_LIB=build/ab/libmillion_exp1.so python tools/ab_bench.py [--cfg bs,T,M[,d] ...] [--vs-scalar]"""
 import argparse
 import os
@@ -80,7 +80,7 @@ for cfg in args.cfg:
         return ops.pq_decode_attn(q, kp, vp, kc, vc, kr, vr, r, M=M, C=C, n_tokens=T, k_page_ids=ids, v_page_ids=ids,
                                   page_size=ps, dev_lengths=dl)
 
-    lib.million_set_force_generic(2 if (d == 128 and M in (32, 64)) else 1)        # grouped kernel (scalar kernel off the streaming shapes) as the cross-check
+    lib.million_set_force_generic(1)        # the scalar kernel as the cross-check
     ref = run(0).float()
     lib.million_set_force_generic(args.policy)
     out = run(0).float()

@@ -19,7 +19,7 @@ tag = sys.argv[1] if len(sys.argv) > 1 else "r01"
 src = ROOT / "gpurun_out"
 out = ROOT / "profiles"
 out.mkdir(exist_ok=True)
-KERNEL = "attn_"            # the fused decode-attention launch: attn_stream_kernel (attn_mfma_kernel: fallback)
+KERNEL = "attn_"            # the fused decode-attention launch: attn_stream_kernel / attn_lean_kernel
 
 summary = {"kernel": KERNEL, "tag": tag}
 import os

@@ -19,11 +19,10 @@ ap.add_argument("--nhk", type=int, default=8)
 ap.add_argument("--bs", type=int, default=1)
 ap.add_argument("--r", type=int, default=100)
 ap.add_argument("--layers", type=int, default=8)
-ap.add_argument("--grouped", action="store_true", help="labels of the grouped kernel")
 ap.add_argument("--raw", action="store_true", help="print every stamp id that was written, ordered by mean time")
 ap.add_argument("--M", type=int, default=64)
 ap.add_argument("--dev-lengths", action="store_true")
-ap.add_argument("--policy", type=int, default=0, help="million_set_force_generic value (2 = grouped only, 3 = prefer pipelined)")
+ap.add_argument("--policy", type=int, default=0, help="million_set_force_generic value (16: the lean kernel's shapes stay on the streaming kernel)")
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
 M, C, d, ps = args.M, 256, 128, 64
@@ -74,22 +73,14 @@ for i in range(args.layers):
     last = s
 lib.million_debug_set_stamp_buffer(None)
 # stamp ids in program order, and what ends at each
-if args.grouped:     # labels of the grouped kernel (attn_mfma_kernel)
-    order = [(0, "kernel start"), (7, "q + K codebook + K bytes of the ring requested"), (8, "K codebook written to LDS"),
-             (1, "barrier 1 (K codebook)"), (2, "accumulators initialised"),
-             (16, "score unit 0"), (17, "  issue: V bytes units 0-1"), (18, "score unit 1"),
-             (19, "  issue: V bytes units 2-3"), (20, "score unit 2"), (21, "  issue: V codebook"), (22, "score unit 3"),
-             (24, "residual tile scores, softmax update"), (12, "append store, V codebook -> LDS"),
-             (13, "barrier 2"), (3, "residual tile values, value pass (+ later groups)"),
-             (4, "wave-merge barrier"), (5, "wave merge done"), (10, "partial stored, drained, barrier"), (6, "flag raised; end (mergers: poll + merge of one head)")]
-else:                # labels of the streaming kernel (attn_stream_kernel)
-    order = [(0, "kernel start"), (7, "requested: page ids, q, both codebooks, residual tile, units 0-1"),
-             (8, "codebooks written to LDS"), (1, "barrier (codebooks)"), (2, "residual tile done"),
-             (16, "prologue: scores of unit 0 (+ unit 2 requests), softmax"),
-             (17, "first whole round of 4 blocks (splits of >= 8 units per wave)"),
-             (19, "blocks of the last whole round"),
-             (3, "values of the last unit of the round (+ single units beyond the whole rounds)"),
-             (4, "wave-merge barrier"), (5, "wave merge done"), (10, "partial stored, drained, barrier"), (6, "flag raised; end (mergers: poll + merge of one head)")]
+# (labels of the streaming kernel, attn_stream_kernel)
+order = [(0, "kernel start"), (7, "requested: page ids, q, both codebooks, residual tile, units 0-1"),
+         (8, "codebooks written to LDS"), (1, "barrier (codebooks)"), (2, "residual tile done"),
+         (16, "prologue: scores of unit 0 (+ unit 2 requests), softmax"),
+         (17, "first whole round of 4 blocks (splits of >= 8 units per wave)"),
+         (19, "blocks of the last whole round"),
+         (3, "values of the last unit of the round (+ single units beyond the whole rounds)"),
+         (4, "wave-merge barrier"), (5, "wave merge done"), (10, "partial stored, drained, barrier"), (6, "flag raised; end (mergers: poll + merge of one head)")]
 s = last
 t0 = s[:, :, 0].min()
 print(f"workgroups {s.shape[0]}; kernel span (first start -> last end) per launch [us]: {[round(float(x), 2) for x in spans]}")
