@@ -194,6 +194,13 @@ size_t million_attn_workspace_bytes(const million_attn_desc *desc);
  * bs * nh_k <= 2048; a shape with more (b, kv head) pairs needs a workspace of its own. */
 int million_workspace_init(void *workspace, size_t bytes, million_stream_t stream);
 
+/* What the two decode entry points read into a product (tests/test_decode_poison_gpu.py checks it bit for bit, every kernel):
+ * code bytes past n_tokens - or past the device length - in the last live page or in a row-major tensor, the pages between the
+ * device length and the host bound, pool pages no live entry names, and window rows outside the ring's valid span (the row a
+ * fused append writes included) may hold anything, NaN and, at C = 128, bytes >= 128 included: they never reach a product and
+ * the output is bitwise the same.  Page-table entries past the live pages (up to n_pages_cap) must still be ids inside the
+ * pools: the streaming and lean kernels load the whole row of ids up front, and only in-pool ids are tested.  out needs no
+ * initialisation. */
 int million_pq_decode_attn(const million_attn_desc *desc,
                            const void *q,              /* (bs, nh, 1, d) fp16 contiguous */
                            const void *k_codes,        /* ROWMAJOR tensor or K page pool */
@@ -211,7 +218,8 @@ int million_pq_decode_attn(const million_attn_desc *desc,
  * :314-326): k_new / v_new (bs, nh_k, 1, d) fp16 are attended to as one more window row and stored into
  * row (resid_start + r) % resid_cap of k_resid / v_resid, where r = desc->r is the number of valid rows
  * BEFORE the call (r < resid_cap).  With dev_lengths the row count is read on the device and incremented
- * there once every workgroup has read it. */
+ * there once every workgroup has read it.  The contract of million_pq_decode_attn above holds; the row being written may hold
+ * anything before the call, and no other window byte is written. */
 int million_pq_decode_attn_append(const million_attn_desc *desc, const void *q, const void *k_new, const void *v_new,
                                   const void *k_codes, const void *v_codes, const void *k_page_ids,
                                   const void *v_page_ids, const void *k_cents_prepared,
@@ -344,7 +352,9 @@ int million_lengths_advance(int32_t *dev_lengths, int bs, int n_flushed, int res
 
 /* Diagnostics only.  -1 in the product build.  In a library built with -DMILLION_DEBUG_CHECK_IDS: waits for the device and
  * returns (and clears) the number of page ids outside [0, k_pool_pages) / [0, v_pool_pages) that the three decode-attention
- * kernels have met since the last call; such ids were read as page 0 instead of as out-of-bounds addresses. */
+ * kernels have met since the last call; such ids were read as page 0 instead of as out-of-bounds addresses.  The same build
+ * fills the whole LDS allocation of every decode-attention and chunk-attention workgroup with 0xFFFF (fp16 NaN) before the
+ * kernel's first LDS write, so that a read of LDS the kernel never wrote gives NaN on every run (tests/lds_poison_child.py). */
 int million_debug_bad_page_ids(void);
 /* Diagnostics: waits for the device and returns (and clears) the number of (b, kv head) merges of the MFMA decode-attention
  * kernels that gave up waiting for a split's partial (a workgroup of the launch died, or the workspace was not zeroed).  The

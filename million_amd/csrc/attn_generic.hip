@@ -43,6 +43,7 @@ __device__ __forceinline__ float block_reduce(float v, bool is_max, float *red) 
 
 __global__ __launch_bounds__(kGenBlock) void attn_generic_kernel(AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    MILLION_DEBUG_FILL_LDS(smem, p.lds_fill);
     const int tid = threadIdx.x;
     const int slot = blockIdx.x;               // [0, nsplit) code splits, nsplit = residual window
     const int bh = blockIdx.y;

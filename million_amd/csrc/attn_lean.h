@@ -31,7 +31,7 @@
 //     two tokens ANDed with the lane's dim-position masks.
 // Per 64 tokens and wave at d = 128 / M = 64: 128 LDS gathers (as before), 48 MFMAs (32 of them 4 x 4 x 4: 512 matrix-pipe cycles;
 // parity-V: 768), ~195 vector instructions (parity-V: ~300), 16 swizzles.
-// Shapes: C = 256 / 128, up to 4 query heads per kv head (d = 64: also 6 .. 16 as parts), pages of 64 or 128 tokens (or row-major K);
+// Shapes: C = 256 / 128, up to 4 query heads per kv head (d = 64: also 5 .. 16 as parts), pages of 64 or 128 tokens (or row-major K);
 // d = 128 with M = 64 / 32 and d = 64 with M = 64 / 32 / 16 (d_m = 1 as zero-padded d_m = 2, 2, 4).  Everything else stays on the streaming / tile kernels (million_set_force_generic(16)
 // keeps the lean shapes there too: A/B and tests).
 // =====================================================================================================
@@ -138,6 +138,7 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
                                  // instead of one) were measured and are slower at every shape: 24.98 vs 22.65 us at two requests,
                                  // 60.5 vs 59.8 at eight, 67.2 vs 65.1 at 8 x 36864 (profiles/r05_ab_lean.txt)
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    MILLION_DEBUG_FILL_LDS(smem, p.lds_fill);
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -295,10 +296,16 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
         v4u *ld = (v4u *)smem;
         v4u *ldv = (v4u *)(smem + kVBase);
         if ((FL & 1) && p.C == 128) {      // (wave-uniform)
-            // K row image [m][128][d_m]: row m goes to the 256-entry row stride of the C = 256 image (codes are < 128: the second half of
-            // a row is never read); V col image [c][m][d_m]: the first 128 rows, placed as for C = 256.  Pieces of the images' size only
+            // K row image [m][128][d_m]: row m goes to the 256-entry row stride of the C = 256 image (the second half of a row is read
+            // only by code bytes >= 128 - tokens past T, never valid ones - and their scores are masked by a select); V col image
+            // [c][m][d_m]: the 128 rows, placed as for C = 256 (code c at kVBase + 256 c in every form) and once more 32 KiB above,
+            // where codes 128 .. 255 land.  A code byte >= 128 of a masked token has probability 0, but 0 x (an unwritten LDS word:
+            // NaN or anything) in the value MFMA is not 0: with the copy such a byte gathers row c - 128, a finite centroid.  (An AND
+            // of every V code word with 0x7f7f7f7f does the same in the loop; the copy costs NT / 2 stores in the prologue only.)
+            // Pieces of the images' size only
             constexpr unsigned RBS = 128u * (DR / MS) * 2u;               // source bytes of a K row
             constexpr unsigned LROW = 256u * (DD / MS) * 2u;              // its LDS stride
+            constexpr unsigned VHI = 32768u;                              // V rows 128 .. 255
 #pragma unroll
             for (int i = 0; i < NT; ++i) {
                 if (((i + rot) & (NT - 1)) >= NT / 2) continue;
@@ -307,12 +314,17 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
                 if constexpr (PAD) {
                     *(v4u *)(smem + kd) = v4u{tabk[i][0] & 0xffffu, tabk[i][0] >> 16, tabk[i][1] & 0xffffu, tabk[i][1] >> 16};
                     *(v4u *)(smem + kd + 16) = v4u{tabk[i][2] & 0xffffu, tabk[i][2] >> 16, tabk[i][3] & 0xffffu, tabk[i][3] >> 16};
-                    ldv[2 * pi_] = v4u{tabv[i][0] & 0xffffu, tabv[i][0] >> 16, tabv[i][1] & 0xffffu, tabv[i][1] >> 16};
-                    ldv[2 * pi_ + 1] = v4u{tabv[i][2] & 0xffffu, tabv[i][2] >> 16, tabv[i][3] & 0xffffu, tabv[i][3] >> 16};
+                    const v4u v0 = v4u{tabv[i][0] & 0xffffu, tabv[i][0] >> 16, tabv[i][1] & 0xffffu, tabv[i][1] >> 16};
+                    const v4u v1 = v4u{tabv[i][2] & 0xffffu, tabv[i][2] >> 16, tabv[i][3] & 0xffffu, tabv[i][3] >> 16};
+                    ldv[2 * pi_] = v0;
+                    ldv[2 * pi_ + 1] = v1;
+                    ldv[2 * pi_ + VHI / 16] = v0;
+                    ldv[2 * pi_ + 1 + VHI / 16] = v1;
                 } else {
                     *(v4u *)(smem + kd) = tabk[i];
-                    if constexpr (DD == 128) ldv[pi_] = tabv[i];
-                    else *(v4u *)(smem + kVBase + ((off >> 7) << 8) + (off & 127u)) = tabv[i];
+                    const unsigned vd = DD == 128 ? off : ((off >> 7) << 8) + (off & 127u);
+                    *(v4u *)(smem + kVBase + vd) = tabv[i];
+                    *(v4u *)(smem + kVBase + VHI + vd) = tabv[i];
                 }
             }
         } else

@@ -1076,6 +1076,7 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_stream_kernel(AttnParams p) 
                                                // 1 MFMA, ~100 cycles of issue: one step ahead does not cover an LDS round trip)
     constexpr int NT = 8 >> (8 - CL2);         // 16-byte pieces of a codebook image per thread (C = 256: 64 KiB, C = 128: 32)
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    MILLION_DEBUG_FILL_LDS(smem, p.lds_fill);
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1261,6 +1262,13 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_stream_kernel(AttnParams p) 
         for (int i = 0; i < NT; ++i) ld[((i + rot) & (NT - 1)) * (kNW * 64) + tid] = tabk[i];
 #pragma unroll
         for (int i = 0; i < NT; ++i) ldv[((i + rot) & (NT - 1)) * (kNW * 64) + tid] = tabv[i];
+        // C = 128: the V col image once more 32 KiB above (code c at kVBase + 256 c), where the code bytes 128 .. 255 of masked
+        // tokens land (the gathers take the byte unmasked): they gather row c - 128, a finite centroid times probability 0 -
+        // not an unwritten LDS word, which may be NaN (0 x NaN = NaN in the value MFMA).  (K: such scores are masked by a select.)
+        if constexpr (CL2 == 7) {
+#pragma unroll
+            for (int i = 0; i < NT; ++i) ldv[((i + rot) & (NT - 1)) * (kNW * 64) + tid + 32768 / 16] = tabv[i];
+        }
     }
     STAMP(8);
     __syncthreads();
@@ -1571,7 +1579,7 @@ static bool lean_d64_shape(const AttnParams &p) {
 }
 static bool mfma_shape_ok(const AttnParams &p) {
     if (lean_d64_shape(p)) return true;
-    if (p.d == 128 && p.M == 16)      // d_m = 8 form of the streaming kernel (round 4): up to 4 query heads per kv head (6 .. 16: as parts)
+    if (p.d == 128 && p.M == 16)      // d_m = 8 form of the streaming kernel (round 4): up to 4 query heads per kv head (5 .. 16: as parts)
         return (p.C == 256 || p.C == 128) && (p.G <= 4 || mfma_hparts(p) > 1) && p.rcap <= 4 * kNW * kResRows;
     return p.d == 128 && (p.M == 64 || p.M == 32) && (p.C == 256 || p.C == 128) && p.G <= kMaxGMfma && p.rcap <= 4 * kNW * kResRows;
 }

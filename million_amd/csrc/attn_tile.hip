@@ -81,6 +81,7 @@ __global__ __launch_bounds__(TW * 64, TW / 4) void attn_tile_kernel(AttnParams p
     constexpr int NTASK = D / 64;              // residual window: V tasks per lane and tile: (d/2 dim pairs) x (2 token octets) / 64
     constexpr int kKRow = TileGeom<D>::kKRow, kVRow = TileGeom<D>::kVRow, kTile = TileGeom<D>::kTile;
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    MILLION_DEBUG_FILL_LDS(smem, p.lds_fill);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q4 = lane >> 4, c16 = lane & 15;

@@ -56,6 +56,9 @@ struct ChunkParams {
     int ntT, ntR;                             // code tiles, window tiles
     int cb_bytes;                             // one codebook image in LDS (0: no code tiles)
     float scale_log2e;
+#ifdef MILLION_DEBUG_CHECK_IDS
+    int lds_fill;                             // dynamic LDS bytes of the launch: debug_fill_lds (common.h)
+#endif
 };
 
 __device__ __forceinline__ long long ca_page(const ChunkParams &p, const void *ids, int b, int hk, int pg) {
@@ -126,6 +129,7 @@ __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(ChunkParams p) 
     constexpr int NM = 8 / DM;                    // subspaces per chunk
     constexpr unsigned kTileBytes = kKeys * 2 * D;
     extern __shared__ __attribute__((aligned(16))) char ca_smem[];      // [K tile | V tile | K codebook | V codebook]
+    MILLION_DEBUG_FILL_LDS(ca_smem, p.lds_fill);
     if ((unsigned)(size_t)(__attribute__((address_space(3))) char *)ca_smem != 0u) __builtin_trap();      // absolute LDS addressing
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -313,7 +317,13 @@ constexpr int kChunkMaxSplits = 64;
 
 template <int D, int DM>
 void launch_chunk_t(const ChunkParams &p, long long blocks, int lds, hipStream_t s) {
+#ifdef MILLION_DEBUG_CHECK_IDS
+    ChunkParams pf = p;
+    pf.lds_fill = lds;      // debug_fill_lds (common.h)
+    hipLaunchKernelGGL((chunk_attn_kernel<D, DM>), dim3((unsigned)blocks), dim3(kThreads), lds, s, pf);
+#else
     hipLaunchKernelGGL((chunk_attn_kernel<D, DM>), dim3((unsigned)blocks), dim3(kThreads), lds, s, p);
+#endif
 }
 
 void chunk_attrs_once() {

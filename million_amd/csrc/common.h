@@ -72,6 +72,9 @@ struct AttnParams {
     unsigned long long *dbg;   // diagnostic stamp buffer (million_debug_set_stamp_buffer), normally null
     int k_pool_pages, v_pool_pages;   // pages in the pools (0 = not given): read only under MILLION_DEBUG_CHECK_IDS
     int *bad_ids;                     // MILLION_DEBUG_CHECK_IDS: device counter of out-of-range page ids, else null
+#ifdef MILLION_DEBUG_CHECK_IDS
+    int lds_fill;                     // dynamic LDS bytes of the launch: debug_fill_lds below
+#endif
 };
 
 // Page ids are trusted in the product build, as in the reference.  A library built with -DMILLION_DEBUG_CHECK_IDS routes
@@ -92,6 +95,22 @@ __device__ __forceinline__ T checked_page_id(const AttnParams &p, T id, int pool
 #else
 #define MILLION_CHECK_KID(p, id, ...) (id)
 #define MILLION_CHECK_VID(p, id, ...) (id)
+#endif
+
+// The same diagnostic build makes reads of LDS a kernel never wrote deterministic: at entry every decode-attention and chunk
+// kernel fills its whole dynamic LDS allocation (`bytes`, passed in by the launcher: a kernel does not know its own size) with
+// 0xFFFF - fp16 NaN, and a NaN fp32 word - and joins a barrier before its first LDS write.  Without it such a read returns
+// whatever an earlier workgroup on the CU left there (dev_switches.h, million_hip.h: million_debug_bad_page_ids).
+#ifdef MILLION_DEBUG_CHECK_IDS
+__device__ __forceinline__ void debug_fill_lds(char *smem, int bytes) {
+    unsigned *w = (unsigned *)smem;
+    for (int i = threadIdx.x; i < (bytes >> 2); i += blockDim.x) w[i] = 0xffffffffu;
+    if (threadIdx.x == 0 && (bytes & 2)) *(unsigned short *)(smem + (bytes & ~3)) = 0xffffu;
+    __syncthreads();
+}
+#define MILLION_DEBUG_FILL_LDS(smem, bytes) ::million::debug_fill_lds((smem), (bytes))
+#else
+#define MILLION_DEBUG_FILL_LDS(smem, bytes) ((void)0)
 #endif
 
 __device__ __forceinline__ float wave_max(float v) {

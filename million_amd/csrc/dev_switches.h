@@ -22,7 +22,11 @@
 //                          packed form above; both are parity-tested through those two ranges)
 //
 // MILLION_DEBUG_CHECK_IDS is NOT a development switch: it builds the shipped diagnostic variant libmillion_hip_dbgids.so
-// (`make debug-ids`, include/million_hip.h), which the parity suite runs (tests/dbgids_child.py).
+// (`make debug-ids`, include/million_hip.h), which the parity suite runs (tests/dbgids_child.py, tests/lds_poison_child.py).
+// Besides checking page ids, its decode-attention kernels (lean, streaming, tile, scalar) and the chunk kernel fill their
+// whole dynamic LDS allocation with 0xFFFF (fp16 NaN) at entry and join a barrier before their first LDS write
+// (common.h: debug_fill_lds; the launchers pass the byte count in AttnParams / ChunkParams::lds_fill, fields that only this
+// build has): a gather from LDS the kernel never wrote then reads NaN every time instead of an earlier workgroup's data.
 #pragma once
 
 #ifndef MILLION_DEV_BUILD

@@ -406,7 +406,13 @@ static int plan_group(const AttnParams &p, AttnPlan &plan, int &heads) {
 
 static int launch_plan(const AttnPlan &plan, hipStream_t stream) {
     plan.setup();
+#ifdef MILLION_DEBUG_CHECK_IDS
+    AttnParams pf = plan.p;
+    pf.lds_fill = (int)plan.lds;      // debug_fill_lds (common.h)
+    void *args[] = {(void *)&pf};
+#else
     void *args[] = {(void *)&plan.p};
+#endif
     (void)hipLaunchKernel(plan.kernel, plan.grid, plan.block, args, plan.lds, stream);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("attn launch (kind %d): %s", plan.kind, hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
