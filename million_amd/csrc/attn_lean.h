@@ -1,9 +1,10 @@
 // attn_lean.h - the lean decode kernel (round 5).  Included by attn_mfma.hip (inside namespace million, behind the streaming
-// kernel): it shares that file's launch skeleton, residual-window helpers and L2 tail.
+// kernel, attn_stream.h): it shares that kernel's launch front (attn_front.h), wave and residual-window helpers (decode_wave.h)
+// and L2 tail (attn_tail.h).
 //
 // The streaming kernel spends its vector issue on PQ address arithmetic (two instructions per K lookup: a lane's table base depends
 // on the lane) and multiplies idle rows / columns (scores: 4 of the 16 head columns of a 16 x 16 x 32 tile, values: 8 of the 32 rows
-// of a 32 x 32 x 16 tile).  This kernel keeps the skeleton - page-strided units, ONE page-id vector load, both codebooks in LDS
+// of a 32 x 32 x 16 tile).  This kernel keeps the skeleton (by sharing it: attn_front.h) - page-strided units, ONE page-id vector load, both codebooks in LDS
 // behind one barrier, the residual tile, the fused append, the L2 tail - and replaces the core (tools/micro/lean_core.hip measures
 // it alone: 1.15-1.18 x the units per us and SIMD of the parity-V core on cache-resident codes at +0.26 GHz of in-kernel clock,
 // 1.05-1.14 x streamed from HBM; profiles/r05_core_micro.txt):
@@ -142,51 +143,15 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int split = blockIdx.x, bh = blockIdx.y;      // all splits of a (b, kv head) on one XCD: see attn_stream_kernel
-    if ((gridDim.y & 7) == 0) {
-        const int id = blockIdx.y * gridDim.x + blockIdx.x;
-        bh = id % (int)gridDim.y;
-        split = id / (int)gridDim.y;
-    }
-    const int b = bh / p.nh_k, hk = bh % p.nh_k;      // hk, bh: VIRTUAL when the launch splits the query heads of a kv head into parts
-    // real kv head / pair (what codes, page ids, window rows and the new rows are indexed by) and this workgroup's part
-    const int part = (FL & 2) ? head_part(p, hk) : 0, hkr = hk - part * p.nhk_mul;
-    const int bhr = (FL & 2) ? bh - (b * p.hparts_m1 + part) * p.nhk_mul : bh;
-    const int G = (FL & 2) && p.nhk_mul ? min(p.G, p.G_all - part * p.G) : p.G;      // (the last part of an odd head group holds fewer)
-    const bool k_paged = MODE == 0 ? true : MODE == 1 ? false : (p.k_paged != 0);
-    const bool v_ident = MODE == 0 ? false : MODE == 1 ? true : (p.v_identity != 0);
-    const bool ids64 = MODE == 2 ? (p.ids64 != 0) : false;
-    typedef int v4i __attribute__((ext_vector_type(4)));
-    v4i dl = {p.T, p.r, p.rstart, 0};
+    // ---- the launch front (attn_front.h): units of 64 tokens (pages of 64 or 128), rows of DR ----
+    LAUNCH_FRONT_PLACE(MODE, FL & 2)
     if ((unsigned)(size_t)(__attribute__((address_space(3))) char *)smem != 0u) __builtin_trap();
     const bool dbg_on = p.dbg != nullptr;
 #define STAMP(i) stamp_lds(dbg_on, lane, wave, i)
     stamp_lds_clear(dbg_on, lane, wave);
     STAMP(0);
     const int kg = lane >> 4, n16 = lane & 15, hj = lane & 3;
-
-    // ---- where this wave reads: page pg0 + j * pg_step in round j, tokens [tin, tin + 64) of it ----
-    const int ups = p.ps_shift - 6;                       // log2(units per page): pages of 64 or 128 tokens
-    const int wp = wave >> ups, uw = wave & ((1 << ups) - 1);
-    const int pg0 = wp * p.nsplit + split;
-    const int pg_step = p.nsplit << (3 - ups);
-    const int tin = uw << 6;
-    int vpk = 0, vpv = 0;      // page ids of rounds 0..63 (lane = round): the oldest loads of the wave
-    {
-        int pgl = pg0 + lane * pg_step;
-        pgl = pgl < p.n_pages_cap ? pgl : p.n_pages_cap - 1;
-        const long long idx = (long long)bhr * p.n_pages_cap + pgl;
-        if (k_paged) vpk = ids64 ? (int)p.k_ids64[idx] : p.k_ids32[idx];
-        if (v_ident) vpv = (int)idx;
-        else vpv = ids64 ? (int)p.v_ids64[idx] : p.v_ids32[idx];
-#ifdef MILLION_DEBUG_CHECK_IDS
-        {
-            const bool live = pg0 + lane * pg_step < p.n_pages_cap && ((long long)(pg0 + lane * pg_step) << p.ps_shift) < p.T;
-            if (k_paged) vpk = MILLION_CHECK_KID(p, ids64 ? (long long)p.k_ids64[idx] : (long long)vpk, live);
-            if (!v_ident) vpv = MILLION_CHECK_VID(p, ids64 ? (long long)p.v_ids64[idx] : (long long)vpv, live);
-        }
-#endif
-    }
+    LAUNCH_FRONT_PAGE_IDS(6)
     // query operand of the 4 x 4 x 4 products: register pair u, lane group kg holds the 4 dims of k-step (u, kg) of head (lane & 3).
     // A lane's pairs 2 v, 2 v + 1 are ONE 16-byte load (dims 32 v + 8 kg .. + 7), so k-step (u, lambda) covers the 4-dim group
     // sigma = 8 (u >> 1) + 2 lambda + (u & 1) (LEAN_SIGMA below; d_m = 2: subspaces 2 sigma, 2 sigma + 1; d_m = 4: subspace sigma):
@@ -206,40 +171,10 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
         Q[2 * v] = v2u{t[0], t[1]};
         Q[2 * v + 1] = v2u{t[2], t[3]};
     }
-    const bool append_wave = p.k_new && split == 0 && wave == kNW - 1 && part == 0;      // wave-uniform
-    h2 new_k = {}, new_v = {};
-    if (append_wave && 2 * lane < DR) {
-        new_k = *(const h2 *)(p.k_new + (long long)bhr * DR + 2 * lane);
-        new_v = *(const h2 *)(p.v_new + (long long)bhr * DR + 2 * lane);
-    }
-    // (128 centroids: the same loads - the second half of them reads the image that follows in the prepared buffer and is dropped
-    // by the copy into LDS below, which spreads the K rows to the 256-entry row stride the gathers use)
-    v4u tabk[NT], tabv[NT];
-    const int rot = (blockIdx.x + 5 * blockIdx.y) & (NT - 1);
-    {
-        const v4u *ks = (const v4u *)p.k_tab;
-#pragma unroll
-        for (int i = 0; i < NT; ++i) tabk[i] = ks[((i + rot) & (NT - 1)) * (kNW * 64) + tid];
-        const v4u *vs = (const v4u *)p.v_tab_col;
-#pragma unroll
-        for (int i = 0; i < NT; ++i) tabv[i] = vs[((i + rot) & (NT - 1)) * (kNW * 64) + tid];
-    }
-    if (p.dev_lengths)
-        asm volatile("s_load_dwordx4 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=&s"(dl) : "s"(p.dev_lengths), "s"((unsigned)b * 16u) : "memory");
-    int T = dl[0], r_old = dl[1], rstart = dl[2];
-    clamp_lengths(p, T, r_old, rstart);
-    const int r = r_old + (p.k_new ? 1 : 0);
-    const int t0 = (pg0 << p.ps_shift) + tin;             // first token of round 0
-    const int t_step = pg_step << p.ps_shift;             // tokens between rounds
-    const int n_mine = T > t0 ? (T - t0 + t_step - 1) / t_step : 0;      // rounds (= units) of this wave; host: <= 64
-    const int j_last = n_mine > 0 ? n_mine - 1 : 0;
-    const int T_ld = T > 0 ? T : 1;
-
-    // ---- residual window rows of this split (see load_res_tile) ----
-    const int rcnt = split < r ? (r - split + p.nsplit - 1) / p.nsplit : 0;
-    const bool has_res = kResRows * wave < rcnt;
-    const f16 *kr = p.k_res + b * p.res_sb + hkr * p.res_sh;
-    const f16 *vr = p.v_res + b * p.res_sb + hkr * p.res_sh;
+    // (128 centroids: the same codebook loads - the second half of them reads the image that follows in the prepared buffer and is
+    // dropped by the copy into LDS below, which spreads the K rows to the 256-entry row stride the gathers use)
+    LAUNCH_FRONT_NEW_ROW_AND_TABLES(DR, NT)
+    LAUNCH_FRONT_LENGTHS()
     LeanResTile<DD, DR> rt;
     v8f16 qb[DR / 32];      // the residual tile's query operand (16 x 16 x 32 layout: lane (q4, c16): head c16, dims (DD / 4) q4 + 8 s ..;
                             // d_m = 4: head c16 & 3 - the four column groups carry copies of the heads, as in the streaming kernel's form)
@@ -255,7 +190,7 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
         }
     }
 
-    // ---- one unit's 16-byte requests into ring slot SL (rounds past the wave's last unit re-request it: no load in a conditional) ----
+    // ---- one unit's 16-byte requests into ring slot SL ----
     LeanUnit<NQ> ring[RING];
     const unsigned k_lane_off = (unsigned)lane << kLog2M;
     // V, d_m = 2: x even reads subspace row 16 (kg & 1) + n, x odd the other 16 of the pair's 32; + 32 subspace rows per pi
@@ -264,7 +199,7 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
     const unsigned v_lane_off2 = ((unsigned)(n16 + (DM2 ? 16 * (1 - (kg & 1)) : 16)) << p.ps_shift) + 16u * kg;
 #define UNIT_REQ_K(SL, J)                                                                                          \
     {                                                                                                              \
-        const int jc_ = (J) < n_mine ? (J) : j_last;                                                               \
+        const int jc_ = LAUNCH_FRONT_ROUND(J);                                                                     \
         gptr_u8 kb_;                                                                                               \
         if (k_paged) {                                                                                             \
             const long long pk_ = (long long)__builtin_amdgcn_readlane(vpk, jc_);                                  \
@@ -272,14 +207,14 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
             _Pragma("unroll") for (int q_ = 0; q_ < NQ; ++q_) ring[SL].k[q_] = *(gptr_v4u)(kb_ + k_lane_off + 16u * q_); \
         } else {      /* row-major K: absolute row per lane, rows past T - 1 re-read it (masked later) */          \
             const int tu_ = t0 + jc_ * t_step;                                                                     \
-            kb_ = uniform_ptr(p.k_codes + b * p.k_sb + hkr * p.k_sh);                                               \
+            kb_ = uniform_ptr(p.k_codes + b * p.k_sb + hkr * p.k_sh);                                              \
             const unsigned ro_ = (unsigned)min(tu_ + lane, T_ld - 1) << kLog2M;                                    \
             _Pragma("unroll") for (int q_ = 0; q_ < NQ; ++q_) ring[SL].k[q_] = *(gptr_v4u)(kb_ + ro_ + 16u * q_);  \
         }                                                                                                          \
     }
 #define UNIT_REQ_V(SL, J)                                                                                          \
     {                                                                                                              \
-        const int jc_ = (J) < n_mine ? (J) : j_last;                                                               \
+        const int jc_ = LAUNCH_FRONT_ROUND(J);                                                                     \
         const long long pv_ = (long long)__builtin_amdgcn_readlane(vpv, jc_);                                      \
         const gptr_u8 vb_ = uniform_ptr(p.v_codes + (pv_ << (kLog2M + p.ps_shift)) + tin);                         \
         _Pragma("unroll") for (int x_ = 0; x_ < NQ; ++x_)                                                          \
@@ -298,14 +233,9 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
         if ((FL & 1) && p.C == 128) {      // (wave-uniform)
             // K row image [m][128][d_m]: row m goes to the 256-entry row stride of the C = 256 image (the second half of a row is read
             // only by code bytes >= 128 - tokens past T, never valid ones - and their scores are masked by a select); V col image
-            // [c][m][d_m]: the 128 rows, placed as for C = 256 (code c at kVBase + 256 c in every form) and once more 32 KiB above,
-            // where codes 128 .. 255 land.  A code byte >= 128 of a masked token has probability 0, but 0 x (an unwritten LDS word:
-            // NaN or anything) in the value MFMA is not 0: with the copy such a byte gathers row c - 128, a finite centroid.  (An AND
-            // of every V code word with 0x7f7f7f7f does the same in the loop; the copy costs NT / 2 stores in the prologue only.)
-            // Pieces of the images' size only
+            // [c][m][d_m]: the 128 rows, placed as for C = 256 and once more kVDup128 above (attn_front.h).  Pieces of the images' size only
             constexpr unsigned RBS = 128u * (DR / MS) * 2u;               // source bytes of a K row
             constexpr unsigned LROW = 256u * (DD / MS) * 2u;              // its LDS stride
-            constexpr unsigned VHI = 32768u;                              // V rows 128 .. 255
 #pragma unroll
             for (int i = 0; i < NT; ++i) {
                 if (((i + rot) & (NT - 1)) >= NT / 2) continue;
@@ -318,13 +248,13 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
                     const v4u v1 = v4u{tabv[i][2] & 0xffffu, tabv[i][2] >> 16, tabv[i][3] & 0xffffu, tabv[i][3] >> 16};
                     ldv[2 * pi_] = v0;
                     ldv[2 * pi_ + 1] = v1;
-                    ldv[2 * pi_ + VHI / 16] = v0;
-                    ldv[2 * pi_ + 1 + VHI / 16] = v1;
+                    ldv[2 * pi_ + kVDup128 / 16] = v0;
+                    ldv[2 * pi_ + 1 + kVDup128 / 16] = v1;
                 } else {
                     *(v4u *)(smem + kd) = tabk[i];
                     const unsigned vd = DD == 128 ? off : ((off >> 7) << 8) + (off & 127u);
                     *(v4u *)(smem + kVBase + vd) = tabv[i];
-                    *(v4u *)(smem + kVBase + VHI + vd) = tabv[i];
+                    *(v4u *)(smem + kVBase + kVDup128 + vd) = tabv[i];
                 }
             }
         } else
@@ -357,13 +287,7 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
     Acc8 O;
     O.t[0] = v4f32{0.f, 0.f, 0.f, 0.f};
     O.t[1] = v4f32{0.f, 0.f, 0.f, 0.f};
-    if (append_wave && 2 * lane < DR) {
-        int row_n = rstart + r_old;
-        row_n = row_n >= p.rcap ? row_n - p.rcap : row_n;
-        const long long o = b * p.res_sb + hkr * p.res_sh + (long long)row_n * DR + 2 * lane;
-        *(h2 *)(p.k_res_w + o) = new_k;
-        *(h2 *)(p.v_res_w + o) = new_v;
-    }
+    LAUNCH_FRONT_APPEND_STORE(DR)
     // lane constants of the value side.  d_m = 2: the half of a (P, P) pair this lane's row takes (parity p = bit 2 of the lane), the
     // phase masks (row z = bit 3 is fed by this lane's token group kg in phase phi iff (kg & 1) == z ^ phi), the gather constants
     // (V col image base | 4 x the lane's subspace within the pair's 32); d_m = 4: the dim-position masks, base | 8 n
@@ -440,7 +364,7 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
         if constexpr (DM2) {                                                                                       \
             a[(SG) & 7][0] = lds32(KBYTE4(SL, 2 * LEAN_SIGMA(SG)) + (2 * LEAN_SIGMA(SG)) * 1024u);                 \
             a[(SG) & 7][1] = lds32(KBYTE4(SL, 2 * LEAN_SIGMA(SG) + 1) + (2 * LEAN_SIGMA(SG) + 1) * 1024u);         \
-        } else {      /* d_m = 4: k-step = subspace sigma: one 8-byte entry = the lane's 4 dims */                   \
+        } else {      /* d_m = 4: k-step = subspace sigma: one 8-byte entry = the lane's 4 dims */                 \
             a[(SG) & 7] = lds64(KBYTE8(SL, LEAN_SIGMA(SG)) + LEAN_SIGMA(SG) * 2048u);                              \
         }                                                                                                          \
     }

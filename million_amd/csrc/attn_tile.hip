@@ -153,7 +153,7 @@ __global__ __launch_bounds__(TW * 64, TW / 4) void attn_tile_kernel(AttnParams p
             mx = fmaxf(mx, sc[v]);
         }
         // m_run is the softmax reference of head c16, moved (with the cross-lane maximum and the rescale of O, l) only
-        // when a score exceeds it by more than 2^8: the common tile needs no reduction (attn_mfma.hip: softmax_online_raw)
+        // when a score exceeds it by more than 2^8: the common tile needs no reduction (decode_wave.h: softmax_online_raw)
         if (__builtin_amdgcn_ballot_w64(mx > m_run + 8.0f)) {      // also the first tile: m_run = -inf, mx finite
             const float m_new = fmaxf(m_run, rows_max(mx));        // over the four lane rows: all 16 tokens of head c16
             const float alpha = fast_exp2_tile(m_run - m_new);

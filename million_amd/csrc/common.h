@@ -16,7 +16,7 @@ constexpr int kCntBytes = 1024;     // granule of the counter / flag blocks at t
 // Workspace head: one 128-byte record per (b, kv head), then one int per batch item (second-level ticket), then
 // 2 x kFlagWords words per (b, kv head) (split flags, XCD census line), then the split partials.  Record words (u32):
 //   [0..1]  u64 arrival ticket of the round-2 hand-off (ticket_and_merge below: tile and scalar kernels)
-//   [2]     ticket word     } L2 hand-off of the MFMA kernels (attn_mfma.hip, "Tail"): arrival count of the (b, kv head)'s
+//   [2]     ticket word     } L2 hand-off of the MFMA kernels (attn_tail.h, "Tail"): arrival count of the (b, kv head)'s
 //   [3]     generation      } workgroups in bits 31:8 (never reset: a launch counts from [4]), give-up bits of the merge helpers
 //   [4]     count base      } in bits 7:0; flags of launch n carry generation + 1
 // Every word is at rest when a launch ends (ticket [0..1] zero, give-up bits zero, generation and base advanced).
@@ -454,7 +454,7 @@ void set_error(const char *fmt, ...);
 int device_cus();
 bool device_once(int family);      // true exactly once per (current device, family 0..7)
 
-int read_tail_faults();             // attn_mfma.hip: merges that ran out of their poll bound since the last call (and clears)
+int read_tail_faults();             // attn_mfma.hip (the count: attn_tail.h g_tail_faults): merges that ran out of their poll bound since the last call (and clears)
 void set_prefill_policy(bool plain); // prefill.hip: million_set_force_generic(64) = the plain form of the prompt-attention kernel at d = 128 (A/B, tests)
 void set_mfma_policy(int policy);   // attn_mfma.hip: test and A/B knob behind million_set_force_generic(4 / 8 / 16): bits 1:0 = merge-helper test mode, bit 2 = lean kernel off
 

@@ -7,9 +7,8 @@
 // build error, so a product object can never carry a path the parity suite has not built.
 //
 //   MILLION_EXP (bit mask)
-//     attn_mfma.hip   1  touch the code lines of rounds 2 and 3 early (one dword per line)        profiles/r04_launch_floor.txt
-//                     2  the last-arriving workgroup merges alone (no helpers)                    profiles/r04_ab_merge.txt
-//                    32  "the launch without arithmetic": every request, wait, barrier and the tail stay, a unit's bytes are
+//     attn_mfma.hip   2  the last-arriving workgroup merges alone (no helpers)                    profiles/r04_ab_merge.txt
+//     attn_stream.h  32  "the launch without arithmetic": every request, wait, barrier and the tail stay, a unit's bytes are
 //                        xor-ed into a sink instead of gathered, multiplied and soft-maxed         profiles/r04_launch_floor.txt
 //     prefill.hip   (the pipelined kernel only; the plain loop's round 3-4 bits are in profiles/r03_prefill.txt, r04_prefill.txt)
 //                     4  no value products, 8 no score products

@@ -469,7 +469,7 @@ def test_dynamic_cache_decode_sequence(env, oracle):
 
 def test_rows_reduce_selfcheck(env):
     """The kernel's VALU-only row reductions (v_permlane16_swap / v_permlane32_swap) against numpy: guards the
-    hipcc pitfall of passing one SSA value as both swap operands (see attn_mfma.hip)."""
+    hipcc pitfall of passing one SSA value as both swap operands (see common.h: swap16_self)."""
     torch, ops = env
     from million_amd import _lib as L
     lib = L.load()
@@ -2380,7 +2380,7 @@ def test_cabi_bench_c_program(env):
 @pytest.mark.parametrize("policy", [0, 16], ids=["lean", "streaming-form"])
 @pytest.mark.parametrize("G", [1, 2, 3, 4])
 def test_attn_lean_kernel_unit_counts_and_forms(G, policy, env, oracle):
-    """The lean kernel (attn_mfma.hip attn_lean_kernel: 64-token units, lane = token, 4x4x4 score products, z-row value products)
+    """The lean kernel (attn_lean.h attn_lean_kernel: 64-token units, lane = token, 4x4x4 score products, z-row value products)
     takes M = 64 / C = 256 / up to 4 query heads per kv head / pages of 64 or 128 tokens; million_set_force_generic(16) keeps those
     shapes on the streaming kernel's parity-V form, which otherwise only runs at G > 4 or on 32-token pages.  Context lengths chosen
     so that a wave has 0, 1, 2, 3, 4 and 5 units (the scores-alone prologue, the block chain with its odd / even ends, the

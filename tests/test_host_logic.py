@@ -443,7 +443,7 @@ def test_make_install_pth_resolves_bindings_without_pythonpath(tmp_path):
 
 
 def test_split_merge_ticket_word_protocol_every_interleaving():
-    """The split merge of the MFMA kernels (attn_mfma.hip "Tail", common.h record word [2]): ONE word per (b, kv head) holds the
+    """The split merge of the MFMA kernels (attn_tail.h "Tail", common.h record word [2]): ONE word per (b, kv head) holds the
     arrival count (a ticket = atomic add of 256) and the give-up bits of the merge helpers (helper k: atomic OR of 1 << k).
     A helper wave out of patience ORs its bit and leaves iff the count the atomic returns is incomplete; the primary - the
     workgroup whose ticket completes the count - merges the heads of every helper whose bit its own ticket returned.  Model of

@@ -5,8 +5,8 @@
 // attn_stream_kernel; the code bytes come from a 64-KiB window per workgroup (2 MiB per XCD: L2-resident), through the same
 // 16-byte loads into the same 4-slot ring; there is no front, no page table, no tail: what is timed is the steady state of the
 // core, in units (32 tokens x 128 code bytes of one kv head, G = 4 query heads) per microsecond and SIMD.
-//   VAR 0: the shipped core (attn_mfma.hip: BLOCK = value steps of unit j | score stages of unit j + 1), 8 waves per CU
-//   VAR 1: parity-V core (attn_mfma.hip "parity-V", shipped since round 4 for M = 64): the gathered V word IS the B operand (k = token x parity-of-dim), the probabilities carry
+//   VAR 0: the shipped core (attn_stream.h: BLOCK = value steps of unit j | score stages of unit j + 1), 8 waves per CU
+//   VAR 1: parity-V core (attn_stream.h "parity-V", shipped since round 4 for M = 64): the gathered V word IS the B operand (k = token x parity-of-dim), the probabilities carry
 //          the zero pattern (rows = head x parity): no pack v_perm, 32 accumulator registers instead of 64
 // The helper functions of VAR 0 are the kernel's own (the source is included, not restated).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I million_amd/csrc -o core_micro tools/micro/core_micro.hip && ./core_micro

@@ -1,6 +1,6 @@
 // Microbenchmark (round 5): the "MFMA-lean" decode core on the harness of core_micro.hip.
 //
-// What is different from the shipped core (attn_mfma.hip: scores by v_mfma_f32_16x16x32_f16 with 4 of 16 head columns in
+// What is different from the shipped core (attn_stream.h: scores by v_mfma_f32_16x16x32_f16 with 4 of 16 head columns in
 // use, lane = (token row, quarter of the code row); values by v_mfma_f32_32x32x16_f16 with 8 of 32 rows in use):
 //   * a unit is 64 tokens (one page) and lane = token on the K side: a lane owns its token's whole 64-byte code row;
 //   * scores: v_mfma_f32_4x4x4_16B_f16 - 16 independent blocks of 4 tokens x 4 heads x 4 dims, every MAC useful at G = 4.  A = the
