@@ -130,6 +130,57 @@ int million_pq_flush_layers(const million_encode_desc *desc, const void *k_rows,
                             int advance, million_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * PQ codebook training.
+ * Replaces: train_pq (scripts/utils/pq_utils.py:586-609), which wraps faiss-cpu's IndexPQ.train: ProductQuantizer's default
+ * training, one independent Lloyd k-means per subspace - the objective million_pq_encode minimises.  train_opq (:554-584) is
+ * not covered.
+ *
+ * Arithmetic contract (the GPU and tests/kmeans_ref.py agree with it bit for bit):
+ *   Inputs.   X (n, d) fp32 or fp16 (fp16 is widened exactly), finite.  d_m = d / M in {1, 2, 4, 8}, 2 <= C <= 4096,
+ *             C <= n < 2^24; anything else: MILLION_ERR_SHAPE.
+ *   Init.     init_rows: C int32 row indices; centroid c of EVERY subspace is the sub-vector of row init_rows[c] (faiss seeds
+ *             all subspaces alike, so one permutation serves them all; indices outside [0, n) are clamped).  Or cents_init: a
+ *             caller's (M, C, d_m) fp32 table (warm start).
+ *   Assign.   Exactly million_pq_encode's rule on the fp32 table: e = x - c, sq = e * e, acc += sq sequentially in k, each one
+ *             IEEE fp32 round-to-nearest operation, no contraction; strict '<' over increasing c: the lowest index wins ties.
+ *   Update.   Points are cut into chunks of 4096 consecutive rows (a function of n alone, never of the grid).  Within a chunk
+ *             the sum of cluster (m, c) is a sequential fp32 sum in ascending row order starting from +0.0f; the chunk sums are
+ *             added sequentially in ascending chunk order.  Counts are int32.  centroid = sum / (float)count, correctly rounded.
+ *             No atomic decides any bit.
+ *   Empty clusters (faiss's split rule with its random donor made deterministic).  Per subspace, for each c with
+ *             count[c] == 0 in ascending order: the donor is the cluster with the largest current count, lowest index on ties;
+ *             centroid[c][k] = donor[k] * (1 + eps) and donor[k] *= (1 - eps) on even k, the reverse on odd k (both from the
+ *             donor's value before the split; 1 + eps and 1 - eps are formed in fp32); count[c] = count[donor] / 2,
+ *             count[donor] -= count[c].  eps = 1/1024 (desc->eps = 0 selects it).
+ *   Iterations.  niter >= 1 rounds of assign -> update -> split; the output is the table after the last round.
+ *   Outputs.  cents_out (M, C, d_m) fp32; counts_out (M, C) int32: the counts after the last round's split (optional);
+ *             objective_out[i] (optional): the sum over all (row, m) of the minimum distance of round i's assignment, each fp32
+ *             distance widened and added in fp64, in a fixed order (two runs give the same bits).
+ * Parity with faiss is NOT pinned: faiss is on none of this project's machines, and its split draws the donor at random.
+ *
+ * 3 launches per round (one more for init_rows) on `stream`; no allocation, no synchronisation.  The workspace
+ * (million_pq_train_workspace_bytes, 256-byte aligned) needs no initialisation.  x and x_stride_n must be aligned to one
+ * sub-vector (d_m elements).  cents_init may alias cents_out. */
+typedef struct {
+    uint32_t struct_size;         /* = sizeof(million_train_desc) */
+    int32_t n, d, M, C;           /* X is (n, d) */
+    int32_t niter;
+    int32_t x_is_f32;             /* 1: X is fp32, 0: fp16 */
+    int64_t x_stride_n;           /* elements between rows of X; the d elements of a row are contiguous */
+    float eps;                    /* split perturbation; 0 = 1/1024 (faiss's EPS) */
+} million_train_desc;
+
+/* 0 for a descriptor that is not valid. */
+size_t million_pq_train_workspace_bytes(const million_train_desc *desc);
+int million_pq_train(const million_train_desc *desc, const void *x,
+                     const int32_t *init_rows,     /* C row indices, or NULL    } exactly one */
+                     const float *cents_init,      /* (M, C, d_m) fp32, or NULL } of the two  */
+                     float *cents_out,             /* (M, C, d_m) fp32 */
+                     int32_t *counts_out,          /* (M, C), may be NULL */
+                     double *objective_out,        /* niter doubles, may be NULL */
+                     void *workspace, size_t workspace_bytes, million_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * PQ decode (reconstruction).
  * Replaces: sa_decode_4d (scripts/utils/pq_utils.py:501-540): out[row, m*d_m + k] = cents[m, codes[row, m], k].
  * codes: (n_rows, M) u8 contiguous (any leading dims flattened); cents: the RAW (M, C, d_m) fp16 codebook;

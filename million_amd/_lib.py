@@ -59,8 +59,15 @@ class ChunkAttnDesc(ctypes.Structure):
                 ("o_stride_b", c_i64), ("o_stride_h", c_i64), ("o_stride_n", c_i64)]
 
 
+class TrainDesc(ctypes.Structure):
+    _fields_ = [("struct_size", c_u32), ("n", c_i32), ("d", c_i32), ("M", c_i32), ("C", c_i32), ("niter", c_i32),
+                ("x_is_f32", c_i32), ("x_stride_n", c_i64), ("eps", ctypes.c_float)]
+
+
 # every symbol include/million_hip.h declares: (restype, argtypes)
 SYMBOLS = {
+    "million_pq_train_workspace_bytes": (c_sz, [ctypes.POINTER(TrainDesc)]),
+    "million_pq_train": (c_i32, [ctypes.POINTER(TrainDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "million_version": (c_i32, []),
     "million_last_error": (ctypes.c_char_p, []),
     "million_prepared_cents_bytes": (c_sz, [c_i32, c_i32, c_i32]),
