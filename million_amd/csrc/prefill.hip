@@ -185,7 +185,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_kernel(PrefillPar
 //                            first three V operands;
 //                  phase 2   the 8 value products of half h (V operands three steps ahead), each followed by one v_max3 of the running maximum over half h + 1's
 //                            raw scores; then the reference decision for half h + 1 (lazy reference as in the decode kernels: it
-//                            moves - rescale of O and l, a wave-uniform branch - only when a score exceeds it by 2^8: P <= 2^8 is an
+//                            moves - rescale of O and l, a wave-uniform branch - only when a probability would exceed 2^8: P <= 2^8 is an
 //                            exact fp16 operand; the rescale sits behind ALL value products of half h, cdna_hip_programming.md T13).
 // Whole-tile pipelining (16 + 16 products per phase) holds both score halves of two tiles, 16 probability pairs and their operands:
 // 256 registers and 41-127 spilled dwords - qf and the fragment addresses reloaded in front of every product with vmcnt(0) waits
@@ -209,13 +209,12 @@ __global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_pipe_kernel(Prefi
     const int q_pos = w.q_pos, nt = w.nt, w_pos_lo = w.w_pos_lo, w_pos_hi = w.w_pos_hi;
     v8h qf[DS];
     flash_load_q<D>(qf, prefill_q_row(p, w), hh);
-    // Q carries the softmax scale and log2 e (one more fp16 rounding of Q: rel-L2 against fp32 1.6e-4 -> 1.8e-4, bar 1e-3), and
-    // a half's score products start from -reference instead of 0: the accumulator IS the exponent, p = exp2(S') with no
-    // fused multiply-add per score (16 of ~164 vector instructions per half and wave; +2 % measured, profiles/r05_prefill.txt)
-#pragma unroll
-    for (int s = 0; s < DS; ++s)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) qf[s][e] = (f16)((float)qf[s][e] * p.scale_log2e);
+    // Q stays as it is given and a half's score products start from -reference instead of 0: the accumulator is s - reference in
+    // raw score units and p = exp2(cs * accumulator), one packed multiply per two scores.  (Until profiles/flash_numerics.txt Q
+    // carried cs, rounded to fp16 again, and the accumulator was the exponent itself: +2 % throughput, but a score error
+    // proportional to the score - worst output row 1.7e-3 / 3.4e-3 at logit standard deviation 4 / 8 against the bar of 1e-3,
+    // hidden by the whole-tensor norm: tests/test_flash_numerics_host.py.)
+    const float cs = p.scale_log2e, thr_raw = 8.0f / cs;      // P <= 2^8: the accumulator may rise to 8 / cs before the reference moves
     const int nh2 = 2 * nt;                                              // 32-key halves of this workgroup
 #if MILLION_EXP & 16384
     const bool wave_live = w.q_lo < p.n_q && wave < 4;      // diagnostic: one computing wave per SIMD (its partner only issues DMA and joins barriers)
@@ -244,7 +243,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_pipe_kernel(Prefi
     for (int i = 0; i < NB; ++i)
 #pragma unroll
         for (int j = 0; j < 16; ++j) O[i][j] = 0.f;
-    float m_ref = -INFINITY, neg_ref = 0.f, thr_rel = -INFINITY, l_run = 0.f;      // thr_rel: 8 once a reference exists (scores are relative to it)
+    float m_ref = -INFINITY, neg_ref = 0.f, thr_rel = -INFINITY, l_run = 0.f;      // raw score units; thr_rel: thr_raw once a reference exists (scores are relative to it)
     const int qd = (lane >> 2) & 3, pp = lane & 3, g16 = (lane >> 4) & 1;
 
     // wave-uniform predicates of half h (keys 32 h .. 32 h + 31) for this wave
@@ -271,7 +270,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_pipe_kernel(Prefi
         if (__any(mx > thr_rel)) {
             const float m_new = fmaxf(m_ref, mx - neg_ref);      // mx is relative to the old reference (neg_ref = -m_safe)
             const float m_safe = m_new > -INFINITY ? m_new : 0.f;
-            const float alpha = __builtin_amdgcn_exp2f(m_ref - m_safe);
+            const float alpha = __builtin_amdgcn_exp2f((m_ref - m_safe) * cs);
 #pragma unroll
             for (int i = 0; i < NB; ++i)      // alpha = 0 on the first move (O = 0 then), 1 when only another row's maximum moved
 #pragma unroll
@@ -282,7 +281,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_pipe_kernel(Prefi
 #pragma unroll
             for (int j = 0; j < 16; ++j) { Nx[j] += shift; NEG[j] = -m_safe; }
             neg_ref = -m_safe;
-            thr_rel = 8.0f;
+            thr_rel = thr_raw;
         }
     };
     // Fragment addresses as 8 + 8 lane constants with everything else in the ds_read immediates (the plain kernel keeps 16 + 32
@@ -380,7 +379,9 @@ __global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_pipe_kernel(Prefi
 #if MILLION_EXP & 256
                 const float p0 = C[2 * s] + 1.0f, p1 = C[2 * s + 1] + 1.0f;
 #else
-                const float p0 = __builtin_amdgcn_exp2f(C[2 * s]), p1 = __builtin_amdgcn_exp2f(C[2 * s + 1]);
+                typedef float f2v __attribute__((ext_vector_type(2)));
+                const f2v ex = f2v{C[2 * s], C[2 * s + 1]} * cs;      // v_pk_mul_f32; -inf (masked) stays -inf
+                const float p0 = __builtin_amdgcn_exp2f(ex[0]), p1 = __builtin_amdgcn_exp2f(ex[1]);
 #endif
                 ls += p0;
                 ls += p1;

@@ -1,0 +1,73 @@
+#!/usr/bin/env python3
+"""Development helper: prompt attention (million_prefill_attn, default policy) of TWO builds of the library in one process, same
+tensors, alternating rounds (A B A B ...), HIP events, median of the repeats of a round; and the largest difference of their outputs.
+    python tools/prefill_ab_libs.py build/ab/libmillion_parent.so million_amd/libmillion_hip.so [--rounds 5] [--out FILE]"""
+import argparse
+import ctypes
+import sys
+from pathlib import Path
+
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+from million_amd import _lib as L  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("lib_a")
+ap.add_argument("lib_b")
+ap.add_argument("--rounds", type=int, default=5)
+ap.add_argument("--out", default=None)
+args = ap.parse_args()
+dev = torch.device("cuda", 0)
+libs = [ctypes.CDLL(str(Path(p).resolve())) for p in (args.lib_a, args.lib_b)]
+for lib in libs:
+    lib.million_prefill_attn.restype = ctypes.c_int32
+    lib.million_prefill_attn.argtypes = [ctypes.POINTER(L.PrefillDesc)] + [ctypes.c_void_p] * 5
+
+
+def call(lib, q, k, v, out):
+    desc = L.PrefillDesc()
+    desc.struct_size = ctypes.sizeof(L.PrefillDesc)
+    desc.bs, desc.nh, desc.n_q, desc.d = q.shape
+    desc.nh_k, desc.n_kv, desc.q_pos0, desc.causal = k.shape[1], k.shape[2], 0, 1
+    for name, t in (("q", q), ("k", k), ("v", v), ("o", out)):
+        for i, ax in enumerate("bhn"):
+            setattr(desc, f"{name}_stride_{ax}", t.stride(i))
+    rc = lib.million_prefill_attn(ctypes.byref(desc), q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), None)
+    assert rc == 0, rc
+
+
+def timed(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        ts.append(a.elapsed_time(b))
+    return sorted(ts)[len(ts) // 2]
+
+
+lines = [f"A = {args.lib_a}   B = {args.lib_b}   (TFLOP/s = 2 d nh n (n + 1) / time; rounds alternate A, B)"]
+for (bs, nh, nhk, n) in ((1, 32, 8, 4096), (1, 32, 8, 32768), (1, 32, 32, 32768), (1, 32, 8, 131072)):
+    d = 128
+    q, k, v = (torch.randn(bs, h, n, d, device=dev).half() for h in (nh, nhk, nhk))
+    outs = [torch.empty_like(q), torch.empty_like(q)]
+    flops = 2.0 * d * nh * bs * n * (n + 1)
+    ms = [[], []]
+    for _ in range(args.rounds):
+        for i, lib in enumerate(libs):
+            ms[i].append(timed(lambda: call(lib, q, k, v, outs[i]), 20 if n <= 4096 else 5 if n <= 32768 else 3))
+    diff = (outs[0].float() - outs[1].float()).abs().max().item()
+    tf = [[flops / t / 1e9 for t in m] for m in ms]
+    best = [max(t) for t in tf]
+    lines.append(f"n={n:6d} nh_k={nhk:2d}:  A best {best[0]:7.1f} ({' '.join('%.0f' % x for x in tf[0])})   B best {best[1]:7.1f} "
+                 f"({' '.join('%.0f' % x for x in tf[1])})   B / A {best[1] / best[0] - 1:+.1%}   max |A - B| {diff:.2e}")
+    print(lines[-1], flush=True)
+    del q, k, v, outs
+    torch.cuda.empty_cache()
+if args.out:
+    Path(args.out).write_text("\n".join(lines) + "\n")
