@@ -346,7 +346,23 @@ int million_prefill_attn(const million_prefill_desc *desc, const void *q /* (bs,
  * each code side row-major (bs, nh_k, T_cap, M) or paged (K pool (n_pool, page_size, M), V pool (n_pool, M, page_size)
  * transposed) with page_size 32 / 64 / 128 and int32 or int64 ids.  Anything else: MILLION_ERR_SHAPE (no fallback).
  * Code bytes past n_tokens, unused pool pages and window rows outside the ring's valid span are never read into a product.
- * Host lengths only (no device-resident lengths).  The window and the chunk are read, never written. */
+ * The window and the chunk are read, never written.
+ * Ragged batches (both fields optional; both NULL: the host values above hold for every request, the launch is the same as
+ * without the fields):
+ *   dev_lengths: device (bs, 4) int32 rows {n_tokens, r, resid_start, ticket}, the rows of million_pq_decode_attn.  Request b
+ *     attends to T_b = row[0] codes and r_b = row[1] window rows from row[2], read by the kernel when it runs (a captured
+ *     launch follows the lengths).  desc->n_tokens is then only the BOUND the grid, the split count and the workspace are sized
+ *     for (the capacity check n_pages_cap * page_size >= n_tokens is made against it), desc->r and desc->resid_start are
+ *     ignored, the window pointers are required whenever resid_cap > 0 and codes, codebooks and ids whenever the bound is > 0.
+ *     The values are not trusted: T_b is clamped into [0, n_tokens], r_b into [0, resid_cap], a start outside [0, resid_cap)
+ *     reads as 0.  Word 3 is neither read nor written.  Every request's visible tiles are cut into the call's S ranges (a
+ *     range may be empty); page ids are read for tokens < T_b only.
+ *   dev_n_q: device (bs,) int32, the valid query rows of each request, clamped into [0, n_q]; with n_c = n_q the chunk of
+ *     request b has n_q[b] rows.  Rows i >= n_q[b] of out are written as zeros; n_q[b] = 0: the request takes no part.
+ *   What may hold anything (NaN, 0xFF, stale ids) without reaching a product or the output: code bytes at or past T_b (pages
+ *   between a request's live pages and the bound included), unused pool pages, page-table entries past a request's live
+ *   pages, window rows outside each request's ring span, q rows and chunk K/V rows at or past n_q[b], the workspace, out.
+ *   Nothing allocates or synchronises: the call may be captured into a graph. */
 typedef struct {
     uint32_t struct_size;         /* = sizeof(million_chunk_attn_desc) */
     int32_t bs, nh, nh_k, d, M, C;
@@ -367,11 +383,14 @@ typedef struct {
     int64_t kc_stride_b, kc_stride_h, kc_stride_n;  /* k_chunk (bs, nh_k, n_c, d) */
     int64_t vc_stride_b, vc_stride_h, vc_stride_n;  /* v_chunk */
     int64_t o_stride_b, o_stride_h, o_stride_n;     /* out (bs, nh, n_q, d) */
+    const int32_t *dev_lengths;   /* NULL, or device (bs, 4) {n_tokens, r, resid_start, ticket}: n_tokens above is the bound */
+    const int32_t *dev_n_q;       /* NULL, or device (bs,) valid query rows per request */
 } million_chunk_attn_desc;
 
 /* Workspace of a call: 0 when the context is not split (the kernel then writes out directly), else
  * bs * nh_k * S * n_q * (nh/nh_k) * (d + 2) * 4 bytes, S = the split count of the past:
  * min(ceil(256 / (bs * nh_k * ceil(n_q * (nh/nh_k) / 256))), ceil(n_tokens / 64), 64), at least 1.
+ * A pure function of the descriptor's host fields (with dev_lengths: of the bound n_tokens; the two device arrays are not read).
  * No initialisation is needed; the workspace holds nothing between calls.  0 for a descriptor that is not valid. */
 size_t million_chunk_attn_workspace_bytes(const million_chunk_attn_desc *desc);
 int million_pq_chunk_attn(const million_chunk_attn_desc *desc,

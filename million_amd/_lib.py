@@ -56,7 +56,8 @@ class ChunkAttnDesc(ctypes.Structure):
                 ("q_stride_b", c_i64), ("q_stride_h", c_i64), ("q_stride_n", c_i64),
                 ("kc_stride_b", c_i64), ("kc_stride_h", c_i64), ("kc_stride_n", c_i64),
                 ("vc_stride_b", c_i64), ("vc_stride_h", c_i64), ("vc_stride_n", c_i64),
-                ("o_stride_b", c_i64), ("o_stride_h", c_i64), ("o_stride_n", c_i64)]
+                ("o_stride_b", c_i64), ("o_stride_h", c_i64), ("o_stride_n", c_i64),
+                ("dev_lengths", c_vp), ("dev_n_q", c_vp)]
 
 
 class TrainDesc(ctypes.Structure):

@@ -22,6 +22,10 @@
 //     ranges, one per split (chunk_splits: host logic).  S = 1 writes fp16 out directly; otherwise each split writes
 //     unnormalised fp32 O and (m, l) per row to the workspace and chunk_merge_kernel combines them: two plain launches, no
 //     atomics, nothing in the workspace has to be initialised.
+//   * ragged batches (desc->dev_lengths / dev_n_q): the RAGGED instances read T, r, resid_start and the valid query rows of
+//     their request on the device and clamp them; grid, S and workspace are those of the bounds, every request's own tiles
+//     are cut into the S ranges (empty ranges write m = -inf, l = 0), rows past a request's n_q are stored as zeros.  The
+//     lockstep instances (RAGGED = false) are the kernel without any of it.
 //   * linear block id: kv head fastest (a kv head's codes stay on one XCD's L2), then split, then query block, then batch.
 #include <math.h>
 #include <string.h>
@@ -56,6 +60,8 @@ struct ChunkParams {
     int ntT, ntR;                             // code tiles, window tiles
     int cb_bytes;                             // one codebook image in LDS (0: no code tiles)
     float scale_log2e;
+    const int *dev_lengths;                   // RAGGED: (bs, 4) {T, r, resid_start, ticket} per request, or null (host T / r / rs)
+    const int *dev_n_q;                       // RAGGED: (bs,) valid query rows per request, or null (n_q)
 #ifdef MILLION_DEBUG_CHECK_IDS
     int lds_fill;                             // dynamic LDS bytes of the launch: debug_fill_lds (common.h)
 #endif
@@ -120,7 +126,36 @@ __device__ __forceinline__ pv4u ca_dequant(unsigned long long w, unsigned tab, i
     return v;
 }
 
-template <int D, int DM>
+// RAGGED: a request's device row, never trusted - T into [0, bound], r into [0, rcap], a start outside the ring reads as 0
+// (clamp_lengths of common.h); word 3 is not touched
+__device__ __forceinline__ void ca_load_lengths(const ChunkParams &p, int b, int &T, int &r, int &rs) {
+    T = p.dev_lengths[4 * b];
+    r = p.dev_lengths[4 * b + 1];
+    rs = p.dev_lengths[4 * b + 2];
+    T = T < 0 ? 0 : (T > p.T ? p.T : T);
+    r = r < 0 ? 0 : (r > p.rcap ? p.rcap : r);
+    rs = (unsigned)rs < (unsigned)p.rcap ? rs : 0;
+}
+__device__ __forceinline__ int ca_load_n_q(const ChunkParams &p, int b) {
+    const int n = p.dev_n_q[b];
+    return n < 0 ? 0 : (n > p.n_q ? p.n_q : n);
+}
+
+// the lane's part of an output row as zeros (the layout of flash_store_row)
+template <int NB>
+__device__ __forceinline__ void ca_store_zero_row(f16 *row, int hh) {
+    typedef f16 h4 __attribute__((ext_vector_type(4)));
+    const h4 z = {(f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f};
+#pragma unroll
+    for (int blk = 0; blk < NB; ++blk)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) *(h4 *)(row + 4 * hh + 32 * blk + 8 * i) = z;
+}
+
+// RAGGED: T, r, resid_start (dev_lengths) and the valid query rows (dev_n_q) are per request, read on the device; the grid,
+// the split count S and the workspace rows are those of the bounds p.T / p.n_q.  A request's tiles are cut into the same S
+// ranges, so a range may be empty: such a split writes m = -inf, l = 0, which the merge skips.
+template <int D, int DM, bool RAGGED>
 __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(ChunkParams p) {
     constexpr int DS = D / 16;                    // k-steps of the score product
     constexpr int NB = D / 32;                    // 32-row blocks of O^T
@@ -143,23 +178,38 @@ __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(ChunkParams p) 
     const int b = id / p.n_qb;
     const int rho_lo = qb * kRowsWG + wave * 32;   // this wave's first flattened row
     const int rho = rho_lo + r32;
-    const bool wave_live = rho_lo < p.nrows;       // wave-uniform
-    const int rho_c = rho < p.nrows ? rho : p.nrows - 1;
+    // ---- this request's lengths: the launch's own, or (RAGGED) its device row ----
+    int T = p.T, r = p.r, rs = p.rs, ntT = p.ntT, ntR = p.ntR, n_c = p.n_c, nrows = p.nrows;
+    if (RAGGED) {
+        if (p.dev_lengths) {
+            ca_load_lengths(p, b, T, r, rs);
+            ntT = (T + kKeys - 1) / kKeys;
+            ntR = (r + kKeys - 1) / kKeys;
+        }
+        if (p.dev_n_q) {
+            const int nq = ca_load_n_q(p, b);
+            nrows = nq * p.G;
+            n_c = p.n_c > 0 ? nq : 0;
+        }
+    }
+    const bool wg_live = !RAGGED || qb * kRowsWG < nrows;      // RAGGED: a block past the request's rows has no tile, its out rows are zeros
+    const bool wave_live = rho_lo < nrows;         // wave-uniform
+    const int rho_c = rho < nrows ? rho : (wg_live ? nrows - 1 : 0);
     const int qi = rho_c / p.G, head = hk * p.G + (rho_c - qi * p.G);
-    const int w_last = (rho_lo + 31 < p.nrows ? rho_lo + 31 : p.nrows - 1);
+    const int w_last = (rho_lo + 31 < nrows ? rho_lo + 31 : nrows - 1);
     const int wave_i_hi = (w_last > 0 ? w_last : 0) / p.G;                     // last query index of the wave
-    const int wg_last = qb * kRowsWG + kRowsWG - 1 < p.nrows ? qb * kRowsWG + kRowsWG - 1 : p.nrows - 1;
+    const int wg_last = qb * kRowsWG + kRowsWG - 1 < nrows ? qb * kRowsWG + kRowsWG - 1 : nrows - 1;
     const int wg_i_hi = wg_last / p.G;
     // ---- the visible tiles of this query block and this split's range of them ----
-    const int ntC_all = (p.n_c + kKeys - 1) / kKeys;
-    const int ntC = p.n_c > 0 ? (wg_i_hi / kKeys + 1 < ntC_all ? wg_i_hi / kKeys + 1 : ntC_all) : 0;
-    const int nt = p.ntT + p.ntR + ntC;
+    const int ntC_all = (n_c + kKeys - 1) / kKeys;
+    const int ntC = n_c > 0 ? (wg_i_hi / kKeys + 1 < ntC_all ? wg_i_hi / kKeys + 1 : ntC_all) : 0;
+    const int nt = wg_live ? ntT + ntR + ntC : 0;
     const int t_beg = (int)((long long)s * nt / p.S), t_end = (int)((long long)(s + 1) * nt / p.S);
 
     v8h qf[DS];
     flash_load_q<D>(qf, p.q + b * p.q_sb + head * p.q_sh + (long long)qi * p.q_sn, hh);
     const unsigned cbK = 2u * kTileBytes, cbV = cbK + (unsigned)p.cb_bytes;
-    if (t_beg < p.ntT) {      // this split dequantises: both codebooks into LDS (made visible by the loop's first barrier)
+    if ((!RAGGED || t_beg < t_end) && t_beg < ntT) {      // this split dequantises: both codebooks into LDS (made visible by the loop's first barrier)
         const pv4u *sk = (const pv4u *)p.ktab, *sv = (const pv4u *)p.vtab;
         for (int o = tid; o < p.cb_bytes / 16; o += kThreads) {
             *(pv4u *)(ca_smem + cbK + 16 * o) = sk[o];
@@ -170,9 +220,9 @@ __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(ChunkParams p) 
     // ---- producers: a tile's raw bytes (codes, or fp16 rows) into registers, then dequantised / copied into LDS ----
     pv4u rk[CPT], rv[CPT];
     auto tile_src = [&](int t, int &kind, int &j0, int &nv) {      // kind 0 codes, 1 window, 2 chunk
-        if (t < p.ntT) { kind = 0; j0 = t * kKeys; nv = p.T - j0; }
-        else if (t < p.ntT + p.ntR) { kind = 1; j0 = (t - p.ntT) * kKeys; nv = p.r - j0; }
-        else { kind = 2; j0 = (t - p.ntT - p.ntR) * kKeys; nv = p.n_c - j0; }
+        if (t < ntT) { kind = 0; j0 = t * kKeys; nv = T - j0; }
+        else if (t < ntT + ntR) { kind = 1; j0 = (t - ntT) * kKeys; nv = r - j0; }
+        else { kind = 2; j0 = (t - ntT - ntR) * kKeys; nv = n_c - j0; }
         nv = nv < kKeys ? nv : kKeys;
     };
     auto load_raw = [&](int t) {
@@ -192,7 +242,7 @@ __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(ChunkParams p) 
                     rk[k][0] = (unsigned)wk; rk[k][1] = (unsigned)(wk >> 32);
                     rv[k][0] = (unsigned)wv; rv[k][1] = (unsigned)(wv >> 32);
                 } else if (kind == 1) {
-                    int rr = p.rs + j;
+                    int rr = rs + j;
                     rr = rr < p.rcap ? rr : rr - p.rcap;
                     const long long o = b * p.res_sb + hk * p.res_sh + (long long)rr * (CH * 8) + 8 * ch;
                     rk[k] = *(const pv4u *)(p.kres + o);
@@ -253,6 +303,13 @@ __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(ChunkParams p) 
     }
     // ---- epilogue: lane (q, h) holds dims 32 blk + 8 i + 4 h + (0..3) of its row ----
     l_run = flash_l_total(l_run);
+    if (RAGGED && rho >= nrows) {      // a row past the request's n_q: zeros (S > 1: by the merge, which does not read the workspace for it)
+        if (p.S == 1 && rho < p.nrows) {
+            const int qz = rho / p.G;
+            ca_store_zero_row<NB>(p.out + b * p.o_sb + (hk * p.G + (rho - qz * p.G)) * p.o_sh + (long long)qz * p.o_sn, hh);
+        }
+        return;
+    }
     if (!wave_live || rho >= p.nrows) return;
     if (p.S == 1) {
         flash_store_row(O, l_run, p.out + b * p.o_sb + head * p.o_sh + (long long)qi * p.o_sn, hh);
@@ -276,7 +333,7 @@ __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(ChunkParams p) 
 }
 
 // ---- merge of the splits: one thread per (row, 8 dims) ----
-template <int D>
+template <int D, bool RAGGED>
 __global__ __launch_bounds__(256) void chunk_merge_kernel(ChunkParams p) {
     constexpr int TPR = D / 8;
     const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -286,6 +343,13 @@ __global__ __launch_bounds__(256) void chunk_merge_kernel(ChunkParams p) {
     const int rho = (int)(row % p.nrows);
     const long long bh = row / p.nrows;
     const int hk = (int)(bh % p.nh_k), b = (int)(bh / p.nh_k);
+    typedef f16 h8 __attribute__((ext_vector_type(8)));
+    if (RAGGED && p.dev_n_q && rho >= ca_load_n_q(p, b) * p.G) {      // past the request's n_q: no split wrote this row
+        const int qz = rho / p.G;
+        const h8 z = {(f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f};
+        *(h8 *)(p.out + b * p.o_sb + (hk * p.G + (rho - qz * p.G)) * p.o_sh + (long long)qz * p.o_sn + 8 * part) = z;
+        return;
+    }
     float mx = -INFINITY;
     for (int s = 0; s < p.S; ++s) mx = fmaxf(mx, p.ws_ml[2 * ((bh * p.S + s) * p.nrows + rho)]);
     float L = 0.f, acc[8];
@@ -305,7 +369,6 @@ __global__ __launch_bounds__(256) void chunk_merge_kernel(ChunkParams p) {
     }
     const float inv = L > 0.f ? 1.0f / L : 0.f;
     const int qi = rho / p.G, head = hk * p.G + (rho - qi * p.G);
-    typedef f16 h8 __attribute__((ext_vector_type(8)));
     h8 v;
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = (f16)(acc[e] * inv);
@@ -315,21 +378,28 @@ __global__ __launch_bounds__(256) void chunk_merge_kernel(ChunkParams p) {
 constexpr int kChunkTargetWGs = 256;     // one workgroup per MI355X CU (the LDS budget at C = 256 admits one)
 constexpr int kChunkMaxSplits = 64;
 
-template <int D, int DM>
-void launch_chunk_t(const ChunkParams &p, long long blocks, int lds, hipStream_t s) {
+template <int D, int DM, bool RAGGED>
+void launch_chunk_r(const ChunkParams &p, long long blocks, int lds, hipStream_t s) {
 #ifdef MILLION_DEBUG_CHECK_IDS
     ChunkParams pf = p;
     pf.lds_fill = lds;      // debug_fill_lds (common.h)
-    hipLaunchKernelGGL((chunk_attn_kernel<D, DM>), dim3((unsigned)blocks), dim3(kThreads), lds, s, pf);
+    hipLaunchKernelGGL((chunk_attn_kernel<D, DM, RAGGED>), dim3((unsigned)blocks), dim3(kThreads), lds, s, pf);
 #else
-    hipLaunchKernelGGL((chunk_attn_kernel<D, DM>), dim3((unsigned)blocks), dim3(kThreads), lds, s, p);
+    hipLaunchKernelGGL((chunk_attn_kernel<D, DM, RAGGED>), dim3((unsigned)blocks), dim3(kThreads), lds, s, p);
 #endif
+}
+template <int D, int DM>
+void launch_chunk_t(const ChunkParams &p, long long blocks, int lds, hipStream_t s) {
+    if (p.dev_lengths || p.dev_n_q) launch_chunk_r<D, DM, true>(p, blocks, lds, s);
+    else launch_chunk_r<D, DM, false>(p, blocks, lds, s);
 }
 
 void chunk_attrs_once() {
     if (!device_once(4)) return;
     const int mx = 160 * 1024;
-#define CA_ATTR(D, DM) (void)hipFuncSetAttribute((const void *)chunk_attn_kernel<D, DM>, hipFuncAttributeMaxDynamicSharedMemorySize, mx)
+#define CA_ATTR(D, DM)                                                                                                          \
+    (void)hipFuncSetAttribute((const void *)chunk_attn_kernel<D, DM, false>, hipFuncAttributeMaxDynamicSharedMemorySize, mx); \
+    (void)hipFuncSetAttribute((const void *)chunk_attn_kernel<D, DM, true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx)
     CA_ATTR(128, 2); CA_ATTR(128, 4); CA_ATTR(128, 8); CA_ATTR(64, 1); CA_ATTR(64, 2); CA_ATTR(64, 4);
 #undef CA_ATTR
 }
@@ -383,7 +453,9 @@ extern "C" int million_pq_chunk_attn(const million_chunk_attn_desc *desc, const 
         return MILLION_ERR_SHAPE;
     }
     if (d.n_q < 0 || (d.n_c != 0 && d.n_c != d.n_q)) { set_error("chunk_attn: n_q=%d n_c=%d (n_c must be 0 or n_q)", d.n_q, d.n_c); return MILLION_ERR_SHAPE; }
-    if (d.n_tokens < 0 || d.r < 0 || d.r > d.resid_cap || (d.r > 0 && (d.resid_start < 0 || d.resid_start >= d.resid_cap))) {
+    const bool dev_len = d.dev_lengths != nullptr;      // n_tokens is then the bound; r and resid_start are not read
+    if (d.n_tokens < 0 || d.resid_cap < 0 ||
+        (!dev_len && (d.r < 0 || d.r > d.resid_cap || (d.r > 0 && (d.resid_start < 0 || d.resid_start >= d.resid_cap))))) {
         set_error("chunk_attn: n_tokens=%d r=%d resid_start=%d resid_cap=%d", d.n_tokens, d.r, d.resid_start, d.resid_cap);
         return MILLION_ERR_ARG;
     }
@@ -399,7 +471,10 @@ extern "C" int million_pq_chunk_attn(const million_chunk_attn_desc *desc, const 
     if (d.n_q == 0) return MILLION_OK;
     if (!q || !out) { set_error("chunk_attn: null q / out"); return MILLION_ERR_ARG; }
     if (d.n_c > 0 && (!k_chunk || !v_chunk)) { set_error("chunk_attn: null chunk K / V with n_c=%d", d.n_c); return MILLION_ERR_ARG; }
-    if (d.r > 0 && (!k_resid || !v_resid)) { set_error("chunk_attn: null window with r=%d", d.r); return MILLION_ERR_ARG; }
+    if ((dev_len ? d.resid_cap > 0 : d.r > 0) && (!k_resid || !v_resid)) {
+        set_error("chunk_attn: null window with r=%d resid_cap=%d", dev_len ? -1 : d.r, d.resid_cap);
+        return MILLION_ERR_ARG;
+    }
     if (d.n_tokens > 0 && (!k_codes || !v_codes || !k_cents_prepared || !v_cents_prepared ||
                            (d.k_layout == MILLION_KV_PAGED && !k_page_ids) || (d.v_layout == MILLION_KV_PAGED && !v_page_ids))) {
         set_error("chunk_attn: null codes / prepared codebooks / page ids with n_tokens=%d", d.n_tokens);
@@ -433,7 +508,10 @@ extern "C" int million_pq_chunk_attn(const million_chunk_attn_desc *desc, const 
     p.kres = (const f16 *)k_resid; p.vres = (const f16 *)v_resid;
     p.out = (f16 *)out;
     p.bs = d.bs; p.nh = d.nh; p.nh_k = d.nh_k; p.G = d.nh / d.nh_k; p.M = d.M; p.C = d.C;
-    p.n_q = d.n_q; p.n_c = d.n_c; p.T = d.n_tokens; p.r = d.r; p.rs = d.r > 0 ? d.resid_start : 0; p.rcap = d.resid_cap;
+    p.n_q = d.n_q; p.n_c = d.n_c; p.T = d.n_tokens; p.rcap = d.resid_cap;
+    p.r = dev_len ? 0 : d.r;
+    p.rs = p.r > 0 ? d.resid_start : 0;
+    p.dev_lengths = d.dev_lengths; p.dev_n_q = d.dev_n_q;
     p.res_sb = d.resid_stride_b; p.res_sh = d.resid_stride_h;
     p.k_paged = d.k_layout == MILLION_KV_PAGED; p.v_paged = d.v_layout == MILLION_KV_PAGED;
     p.ps = d.page_size > 0 ? d.page_size : 64; p.n_pages_cap = d.n_pages_cap; p.ids64 = d.page_ids_i64 != 0;
@@ -446,7 +524,7 @@ extern "C" int million_pq_chunk_attn(const million_chunk_attn_desc *desc, const 
     p.n_qb = n_qb;
     p.S = S;
     p.ntT = (d.n_tokens + kKeys - 1) / kKeys;
-    p.ntR = (d.r + kKeys - 1) / kKeys;
+    p.ntR = (p.r + kKeys - 1) / kKeys;
     p.cb_bytes = d.n_tokens > 0 ? d.C * d.d * 2 : 0;
     p.scale_log2e = 1.4426950408889634f / sqrtf((float)d.d);
     if (S > 1) {
@@ -471,8 +549,11 @@ extern "C" int million_pq_chunk_attn(const million_chunk_attn_desc *desc, const 
     if (S > 1) {
         const long long threads = (long long)d.bs * d.nh_k * p.nrows * (d.d / 8);
         const long long mblocks = (threads + 255) / 256;
-        if (d.d == 128) hipLaunchKernelGGL(chunk_merge_kernel<128>, dim3((unsigned)mblocks), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL(chunk_merge_kernel<64>, dim3((unsigned)mblocks), dim3(256), 0, s, p);
+        const bool ragged = p.dev_lengths || p.dev_n_q;
+        if (d.d == 128 && ragged) hipLaunchKernelGGL((chunk_merge_kernel<128, true>), dim3((unsigned)mblocks), dim3(256), 0, s, p);
+        else if (d.d == 128) hipLaunchKernelGGL((chunk_merge_kernel<128, false>), dim3((unsigned)mblocks), dim3(256), 0, s, p);
+        else if (ragged) hipLaunchKernelGGL((chunk_merge_kernel<64, true>), dim3((unsigned)mblocks), dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((chunk_merge_kernel<64, false>), dim3((unsigned)mblocks), dim3(256), 0, s, p);
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("chunk_attn launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }

@@ -608,7 +608,7 @@ def attn_kernel_kind(desc: L.AttnDesc) -> int:
 
 def chunk_attn_desc(q, k_res, *, nh_k, M, C, n_tokens, r, n_c, resid_start=0, k_paged=False, v_paged=False, page_size=0,
                     n_pages_cap=0, page_ids_i64=False, k_codes=None, v_codes=None, k_chunk=None, v_chunk=None,
-                    out=None) -> L.ChunkAttnDesc:
+                    out=None, dev_lengths=None, dev_n_q=None) -> L.ChunkAttnDesc:
     bs, nh, n_q, d = q.shape
     desc = L.ChunkAttnDesc()
     desc.struct_size = ctypes.sizeof(L.ChunkAttnDesc)
@@ -629,6 +629,10 @@ def chunk_attn_desc(q, k_res, *, nh_k, M, C, n_tokens, r, n_c, resid_start=0, k_
         desc.vc_stride_b, desc.vc_stride_h, desc.vc_stride_n = v_chunk.stride(0), v_chunk.stride(1), v_chunk.stride(2)
     if out is not None:
         desc.o_stride_b, desc.o_stride_h, desc.o_stride_n = out.stride(0), out.stride(1), out.stride(2)
+    if dev_lengths is not None:
+        desc.dev_lengths = dev_lengths.data_ptr()
+    if dev_n_q is not None:
+        desc.dev_n_q = dev_n_q.data_ptr()
     return desc
 
 
@@ -640,15 +644,22 @@ def pq_chunk_attn(q: torch.Tensor, k_chunk: Optional[torch.Tensor], v_chunk: Opt
                   v_codes: torch.Tensor, k_prep: torch.Tensor, v_prep: torch.Tensor, k_res: torch.Tensor, v_res: torch.Tensor,
                   r: int, *, M: int, C: int, n_tokens: int, resid_start: int = 0, k_page_ids: Optional[torch.Tensor] = None,
                   v_page_ids: Optional[torch.Tensor] = None, page_size: Optional[int] = None, out: Optional[torch.Tensor] = None,
-                  workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  workspace: Optional[torch.Tensor] = None, dev_lengths: Optional[torch.Tensor] = None,
+                  dev_n_q: Optional[torch.Tensor] = None) -> torch.Tensor:
     """n_q query tokens against [the PQ codes of n_tokens tokens; r window rows of the ring from resid_start; the chunk]
     (million_pq_chunk_attn): q (bs, nh, n_q, d) -> (bs, nh, n_q, d).  k_chunk / v_chunk (bs, nh_k, n_q, d): the chunk's own
     K/V, attended causally (chunked prefill, a later turn of a conversation); None: every row sees the past only (draft
     verification).  A code side is row-major (bs, nh_k, T_cap, M) when its page ids are None, else a page pool (K
     (n_pool, page_size, M), V (n_pool, M, page_size)).  q, k_chunk, v_chunk and out may be strided (rows of d contiguous
     elements); the default out is token-major under the (bs, nh, n_q, d) shape, as prefill_attn's.  Nothing is written
-    but `out`: storing the chunk in the cache is the caller's (DynamicPQCache.extend / PagedPQCache.extend)."""
-    _need_cuda(q, k_chunk, v_chunk, k_codes, v_codes, k_prep, v_prep, k_res, v_res, k_page_ids, v_page_ids, out, workspace)
+    but `out`: storing the chunk in the cache is the caller's (DynamicPQCache.extend / PagedPQCache.extend).
+    Ragged batches: dev_lengths, device int32 (bs, 4) rows {T, r, resid_start, ticket} (a cache's `lengths[l]`), gives every
+    request its own lengths, read on the device when the kernel runs: n_tokens is then only the bound the launch is sized
+    for, r and resid_start are ignored; with a caller's workspace= (chunk_attn_workspace_bytes) and out= the call allocates
+    nothing and can be captured into a graph.  dev_n_q, device int32 (bs,): the valid query (and chunk) rows of each
+    request; the rows past them are returned as zeros and their q / chunk rows are never read into a product."""
+    _need_cuda(q, k_chunk, v_chunk, k_codes, v_codes, k_prep, v_prep, k_res, v_res, k_page_ids, v_page_ids, out, workspace,
+               dev_lengths, dev_n_q)
     if q.dtype != torch.float16 or k_res.dtype != torch.float16 or v_res.dtype != torch.float16:
         raise RuntimeError("pq_chunk_attn: q and window buffers must be fp16")
     if k_codes.dtype != torch.uint8 or v_codes.dtype != torch.uint8:
@@ -696,16 +707,19 @@ def pq_chunk_attn(q: torch.Tensor, k_chunk: Optional[torch.Tensor], v_chunk: Opt
                 raise RuntimeError(f"pq_chunk_attn: {name} rows must be dense (stride M)")
             if n_tokens > codes.shape[2]:
                 raise RuntimeError(f"pq_chunk_attn: n_tokens exceeds {name}")
-    if not 0 <= r <= k_res.shape[2]:
+    if dev_lengths is None and not 0 <= r <= k_res.shape[2]:
         raise RuntimeError(f"pq_chunk_attn: r={r} outside [0, {k_res.shape[2]}]")
+    for name, t, shape in (("dev_lengths", dev_lengths, (bs, 4)), ("dev_n_q", dev_n_q, (bs,))):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous() or tuple(t.shape) != shape):
+            raise RuntimeError(f"pq_chunk_attn: {name} must be contiguous int32 {shape}")
     if out is None:
         out = torch.empty(bs, n_q, nh, d, dtype=torch.float16, device=q.device).transpose(1, 2)
     elif out.shape != (bs, nh, n_q, d) or out.dtype != torch.float16 or out.stride(3) != 1:
         raise RuntimeError("pq_chunk_attn: out must be fp16 (bs, nh, n_q, d) with contiguous rows")
-    desc = chunk_attn_desc(q, k_res, nh_k=nh_k, M=M, C=C, n_tokens=int(n_tokens), r=int(r), n_c=n_c,
-                           resid_start=int(resid_start), k_paged=k_paged, v_paged=v_paged, page_size=int(page_size or 0),
+    desc = chunk_attn_desc(q, k_res, nh_k=nh_k, M=M, C=C, n_tokens=int(n_tokens), r=0 if dev_lengths is not None else int(r),
+                           n_c=n_c, resid_start=int(resid_start), k_paged=k_paged, v_paged=v_paged, page_size=int(page_size or 0),
                            n_pages_cap=n_pages_cap, page_ids_i64=ids64, k_codes=k_codes, v_codes=v_codes, k_chunk=k_chunk,
-                           v_chunk=v_chunk, out=out)
+                           v_chunk=v_chunk, out=out, dev_lengths=dev_lengths, dev_n_q=dev_n_q)
     lib = L.load()
     need = lib.million_chunk_attn_workspace_bytes(ctypes.byref(desc))
     if workspace is None or workspace.numel() < need:

@@ -573,6 +573,50 @@ class PagedPQCache(_CacheBase):
         self.lengths[layer_idx][b].copy_(torch.tensor(row, dtype=torch.int32))
         return out
 
+    def extend_ragged(self, query_states, key_states, value_states, layer_idx, n_new):
+        """extend_request() for every slot in ONE attention launch: tensors of batch bs padded to n_q = max(n_new) rows,
+        slot b owns the first n_new[b] of them (n_new: bs host ints in [0, n_q]).  The launch reads each slot's lengths from
+        `lengths[layer_idx]` on the device and n_new from a small device copy; the rows past n_new[b] - q, K and V - may
+        hold anything and their output rows are zeros.  A slot with n_new[b] > 0 is then left exactly as
+        extend_request(b, ...) with its own rows leaves it (pending encode-ahead joined, window rows encoded in ring order
+        behind T_b, the chunk rows behind those, T_b += r_b + n_b, r_b = resid_start_b = 0, its device row rewritten); an
+        empty slot is served by the same launch (the chunk only).  A slot with n_new[b] = 0 takes no part: host and device
+        lengths, pages and window stay as they are."""
+        n_new = [int(x) for x in n_new]
+        n_q = query_states.size(2)
+        if len(n_new) != self.bs or query_states.size(0) != self.bs or key_states.size(0) != self.bs or key_states.size(2) != n_q:
+            raise RuntimeError(f"extend_ragged: tensors of batch {self.bs} and one n_new per slot")
+        if any(n < 0 or n > n_q for n in n_new):
+            raise RuntimeError(f"extend_ragged: n_new outside [0, {n_q}]")
+        who = [b for b in range(self.bs) if n_new[b] > 0]
+        for b in who:      # capacity of every slot before anything is launched
+            tot = int(self._T_a[layer_idx, b] + self._r_a[layer_idx, b]) + n_new[b]
+            if tot > self.max_tokens:
+                raise RuntimeError(f"PagedPQCache: {tot} tokens exceed max_tokens={self.max_tokens}")
+        for b in who:
+            self._join_side(layer_idx, b)
+        ids = self.page_ids[layer_idx]
+        kres, vres = self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx]
+        dev_n = torch.tensor(n_new, dtype=torch.int32).to(self.device)
+        bound = int(self._T_a[layer_idx].max())
+        out = ops.pq_chunk_attn(query_states, key_states, value_states, self.key_page_pool, self.value_page_pool, self._kprep,
+                                self._vprep, kres, vres, 0, M=self.M, C=self.C, n_tokens=bound, k_page_ids=ids, v_page_ids=ids,
+                                page_size=self.page_size, dev_lengths=self.lengths[layer_idx], dev_n_q=dev_n)
+        cap = self.extended_residual_size
+        for b in who:      # the encodes stay host-driven per slot, as extend_request does them
+            sel = slice(b, b + 1)
+            r, rs, n = int(self._r_a[layer_idx, b]), int(self._rs_a[layer_idx, b]), n_new[b]
+            if r:
+                self._encode_to_pages(kres[sel], vres[sel], layer_idx, r, b=b, x_row_start=rs, x_row_mod=cap)
+                self._T_a[layer_idx, b] += r
+            self._encode_to_pages(key_states[sel, :, :n], value_states[sel, :, :n], layer_idx, n, b=b)
+            self._T_a[layer_idx, b] += n
+            self._r_a[layer_idx, b] = 0
+            self._rs_a[layer_idx, b] = 0
+            self._seen_a[layer_idx, b] += n
+            self.lengths[layer_idx][b].copy_(torch.tensor([int(self._T_a[layer_idx, b]), 0, 0, 0], dtype=torch.int32))
+        return out
+
     def release(self, b):
         """Request b has finished: its pages go back to the PageManager (on-demand paging; a preallocated table keeps its
         fixed ids for the slot's next request), its host and device lengths return to zero.  The other slots, and any

@@ -2,6 +2,8 @@
 window and chunk, ops.prefill_attn(q_pos0 = T + r).  HIP events, medians, every shape warmed up.  One JSON line per shape.
 
   python tools/chunk_bench.py [--reps 20] [--shapes all|quick]
+  python tools/chunk_bench.py --ragged [--reps 20]      four requests at 32K / 24K / 8K / 1K tokens: one ragged launch (A)
+      against four batch-1 calls with host lengths (B), and the lockstep call at 4 x 32K without / with device lengths (C)
 
 Kernel times: run under `rocprofv3 --kernel-trace --stats -- python tools/chunk_bench.py` (a run of its own)."""
 from __future__ import annotations
@@ -88,12 +90,82 @@ def run_shape(bs, n_q, T, M, reps):
     return rec
 
 
+RAGGED_T = (32768, 24576, 8192, 1024)
+RAGGED_RS = 100      # a wrapped window: R rows from ring row 100 of CAP
+
+
+def run_ragged(n_q, reps, M=64):
+    """A: one launch, per-request lengths read on the device.  B: the same work as four batch-1 calls with host lengths (what
+    PagedPQCache.extend_request does), each call's median and the four calls timed as one span.  C: the lockstep call at
+    4 x 32K, host lengths against the same values in dev_lengths (the cost of the device read)."""
+    dev = torch.device("cuda")
+    g = torch.Generator(device=dev).manual_seed(0)
+    bs, T_max = len(RAGGED_T), max(RAGGED_T)
+    kcent = torch.randn(M, C, D // M, device=dev, generator=g).half()
+    vcent = torch.randn(M, C, D // M, device=dev, generator=g).half()
+    kp, vp = ops.prepare_cents(kcent, cache=False), ops.prepare_cents(vcent, cache=False)
+    n_pg = (T_max + PS - 1) // PS
+    kpool = torch.randint(0, C, (bs * NHK * n_pg, PS, M), device=dev, dtype=torch.uint8, generator=g)
+    vpool = torch.randint(0, C, (bs * NHK * n_pg, M, PS), device=dev, dtype=torch.uint8, generator=g)
+    ids = torch.arange(bs * NHK * n_pg, device=dev, dtype=torch.int32).reshape(bs, NHK, n_pg)
+    kres = torch.randn(bs, NHK, CAP, D, device=dev, generator=g).half()
+    vres = torch.randn(bs, NHK, CAP, D, device=dev, generator=g).half()
+    q = torch.randn(bs, NH, n_q, D, device=dev, generator=g).half()
+    kc = torch.randn(bs, NHK, n_q, D, device=dev, generator=g).half()
+    vc = torch.randn(bs, NHK, n_q, D, device=dev, generator=g).half()
+    rows = lambda Ts: torch.tensor([[T, R, RAGGED_RS, 0] for T in Ts], dtype=torch.int32, device=dev)
+    dl, dl_lock = rows(RAGGED_T), rows((T_max,) * bs)
+    nq = torch.full((bs,), n_q, dtype=torch.int32, device=dev)
+    kw = dict(M=M, C=C, page_size=PS)
+    one = [tuple(t[b:b + 1] for t in (q, kc, vc, kres, vres, ids)) for b in range(bs)]
+
+    def A():
+        return ops.pq_chunk_attn(q, kc, vc, kpool, vpool, kp, vp, kres, vres, 0, n_tokens=T_max, k_page_ids=ids, v_page_ids=ids,
+                                 dev_lengths=dl, dev_n_q=nq, **kw)
+
+    def B1(b):
+        q1, kc1, vc1, kr1, vr1, id1 = one[b]
+        return ops.pq_chunk_attn(q1, kc1, vc1, kpool, vpool, kp, vp, kr1, vr1, R, n_tokens=RAGGED_T[b], resid_start=RAGGED_RS,
+                                 k_page_ids=id1, v_page_ids=id1, **kw)
+
+    def B():
+        return [B1(b) for b in range(bs)]
+
+    def C_host():
+        return ops.pq_chunk_attn(q, kc, vc, kpool, vpool, kp, vp, kres, vres, R, n_tokens=T_max, resid_start=RAGGED_RS,
+                                 k_page_ids=ids, v_page_ids=ids, **kw)
+
+    def C_dev():
+        return ops.pq_chunk_attn(q, kc, vc, kpool, vpool, kp, vp, kres, vres, 0, n_tokens=T_max, k_page_ids=ids, v_page_ids=ids,
+                                 dev_lengths=dl_lock, **kw)
+
+    out_a, out_b = A(), torch.cat(B())
+    same_lock = torch.equal(C_host(), C_dev())
+    torch.cuda.synchronize()
+    rel = ((out_a.float() - out_b.float()).norm() / out_b.float().norm()).item()
+    t_a = _median_us(A, reps)
+    t_b_each = [_median_us(lambda b=b: B1(b), reps) for b in range(bs)]
+    t_b_span = _median_us(B, reps)
+    t_ch, t_cd = _median_us(C_host, reps), _median_us(C_dev, reps)
+    t_ch2 = _median_us(C_host, reps)      # the host-length call again: this run's own scatter
+    return dict(ragged=True, n_q=n_q, T=list(RAGGED_T), r=R, resid_start=RAGGED_RS, M=M, A_one_launch_us=round(t_a, 2),
+                B_each_us=[round(t, 2) for t in t_b_each], B_sum_us=round(sum(t_b_each), 2), B_span_us=round(t_b_span, 2),
+                A_over_B_sum=round(t_a / sum(t_b_each), 3), A_over_B_max=round(t_a / max(t_b_each), 3),
+                C_lockstep_host_us=round(t_ch, 2), C_lockstep_dev_lengths_us=round(t_cd, 2), C_lockstep_host_again_us=round(t_ch2, 2),
+                C_bitwise_equal=same_lock, rel_A_vs_B=float(f"{rel:.2e}"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--ragged", action="store_true", help="the ragged batch against per-request calls (rows A / B / C)")
     ap.add_argument("--shapes", default="all", choices=["all", "quick"])
     a = ap.parse_args()
     assert torch.cuda.is_available(), "chunk_bench needs the GPU (no CPU timing)"
+    if a.ragged:
+        for n_q in (8, 64):
+            print(json.dumps(run_ragged(n_q, a.reps)), flush=True)
+        return
     shapes = [(bs, n_q, 32768, 64) for bs in (1, 4) for n_q in (1, 4, 16, 64, 512, 2048)] + [(1, 16, 131072, 32)]
     if a.shapes == "quick":
         shapes = [(1, 16, 32768, 64), (1, 2048, 32768, 64)]
