@@ -315,7 +315,24 @@ void million_set_force_generic(int on);
  * repeat_kv: the nh / nh_k query heads of a kv head share the K/V tiles of one workgroup.
  *   out[b,h,i,:] = softmax_{j <= q_pos0 + i (causal), j < n_kv}( q[b,h,i,:] . k[b,hk,j,:] / sqrt(d) ) v[b,hk,j,:],  hk = h / (nh/nh_k)
  * fp16 in / out, fp32 scores, online softmax and accumulation; d = 128 or 64.  causal = 0: every key (j < n_kv).
- * torch's is_causal=True with q_len == kv_len is q_pos0 = 0; a prompt chunk behind n_past cached fp16 rows is q_pos0 = n_past. */
+ * torch's is_causal=True with q_len == kv_len is q_pos0 = 0; a prompt chunk behind n_past cached fp16 rows is q_pos0 = n_past.
+ * Ragged batches (dev_spans, optional; NULL: the host values hold for every request, the launch is the same as without the
+ * field - same kernel instance, same grid, same bits):
+ *   dev_spans: device (bs, 4) int32 rows {n_q, n_kv, q_pos0, reserved}.  Request b has n_q_b = row[0] query rows and
+ *     n_kv_b = row[1] key / value rows, and its query row 0 sits at key position q_pos0_b = row[2], read by the kernel when it
+ *     runs (a captured launch follows the array).  desc->n_q and desc->n_kv are then only the BOUNDS the grid and every pointer
+ *     range are sized for (padded layout: request b's rows start at b * stride_b, whatever its length); desc->q_pos0 is not
+ *     read but still validated (>= 0), and a bound n_kv = 0 with n_q > 0 is still MILLION_ERR_ARG.  The values are not trusted:
+ *     n_q_b is clamped into [0, n_q], n_kv_b into [0, n_kv], q_pos0_b into [0, n_kv].  Word 3 is neither read nor written; the
+ *     array is never written.  Each request uses the formula above with its own three values (causal: j <= q_pos0_b + i and
+ *     j < n_kv_b; otherwise j < n_kv_b).
+ *   Rows i >= n_q_b of out[b] (below the bound n_q) are written as zeros; a request with n_kv_b = 0 gets zeros in every row,
+ *     with no error; n_q_b = 0: the request takes no part.  Rows at or past the bound are never written.
+ *   What may hold anything (NaN, garbage) without reaching a product or the output: q rows at or past n_q_b, K and V rows at
+ *   or past n_kv_b, out.
+ *   Bit for bit: the live rows of request b equal the call without dev_spans on that request alone (bs = 1) with the host
+ *   values (n_q_b, n_kv_b, q_pos0_b); with every row equal to the host values the call equals the call without dev_spans.
+ *   Nothing allocates or synchronises and there is no workspace: the call may be captured into a graph. */
 typedef struct {
     uint32_t struct_size;         /* = sizeof(million_prefill_desc) */
     int32_t bs, nh, nh_k, d;
@@ -326,6 +343,7 @@ typedef struct {
     int64_t k_stride_b, k_stride_h, k_stride_n;
     int64_t v_stride_b, v_stride_h, v_stride_n;
     int64_t o_stride_b, o_stride_h, o_stride_n;
+    const int32_t *dev_spans;     /* NULL, or device (bs, 4) int32 rows {n_q, n_kv, q_pos0, reserved}: n_q / n_kv above are the bounds */
 } million_prefill_desc;
 
 int million_prefill_attn(const million_prefill_desc *desc, const void *q /* (bs, nh, n_q, d) */,

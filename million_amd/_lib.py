@@ -44,7 +44,8 @@ class PrefillDesc(ctypes.Structure):
                 ("q_stride_b", c_i64), ("q_stride_h", c_i64), ("q_stride_n", c_i64),
                 ("k_stride_b", c_i64), ("k_stride_h", c_i64), ("k_stride_n", c_i64),
                 ("v_stride_b", c_i64), ("v_stride_h", c_i64), ("v_stride_n", c_i64),
-                ("o_stride_b", c_i64), ("o_stride_h", c_i64), ("o_stride_n", c_i64)]
+                ("o_stride_b", c_i64), ("o_stride_h", c_i64), ("o_stride_n", c_i64),
+                ("dev_spans", c_vp)]
 
 
 class ChunkAttnDesc(ctypes.Structure):

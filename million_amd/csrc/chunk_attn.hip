@@ -141,17 +141,6 @@ __device__ __forceinline__ int ca_load_n_q(const ChunkParams &p, int b) {
     return n < 0 ? 0 : (n > p.n_q ? p.n_q : n);
 }
 
-// the lane's part of an output row as zeros (the layout of flash_store_row)
-template <int NB>
-__device__ __forceinline__ void ca_store_zero_row(f16 *row, int hh) {
-    typedef f16 h4 __attribute__((ext_vector_type(4)));
-    const h4 z = {(f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f};
-#pragma unroll
-    for (int blk = 0; blk < NB; ++blk)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) *(h4 *)(row + 4 * hh + 32 * blk + 8 * i) = z;
-}
-
 // RAGGED: T, r, resid_start (dev_lengths) and the valid query rows (dev_n_q) are per request, read on the device; the grid,
 // the split count S and the workspace rows are those of the bounds p.T / p.n_q.  A request's tiles are cut into the same S
 // ranges, so a range may be empty: such a split writes m = -inf, l = 0, which the merge skips.
@@ -306,7 +295,7 @@ __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(ChunkParams p) 
     if (RAGGED && rho >= nrows) {      // a row past the request's n_q: zeros (S > 1: by the merge, which does not read the workspace for it)
         if (p.S == 1 && rho < p.nrows) {
             const int qz = rho / p.G;
-            ca_store_zero_row<NB>(p.out + b * p.o_sb + (hk * p.G + (rho - qz * p.G)) * p.o_sh + (long long)qz * p.o_sn, hh);
+            flash_store_zero_row<NB>(p.out + b * p.o_sb + (hk * p.G + (rho - qz * p.G)) * p.o_sh + (long long)qz * p.o_sn, hh);
         }
         return;
     }

@@ -172,4 +172,15 @@ __device__ __forceinline__ void flash_store_row(const v16f (&O)[NB], float l, f1
         }
 }
 
+// the lane's part of an output row as zeros (the layout of flash_store_row): rows past a request's own length in a ragged batch
+template <int NB>
+__device__ __forceinline__ void flash_store_zero_row(f16 *row, int hh) {
+    typedef f16 h4 __attribute__((ext_vector_type(4)));
+    const h4 z = {(f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f};
+#pragma unroll
+    for (int blk = 0; blk < NB; ++blk)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) *(h4 *)(row + 4 * hh + 32 * blk + 8 * i) = z;
+}
+
 }  // namespace million

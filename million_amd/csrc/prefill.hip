@@ -18,6 +18,10 @@
 //     in the exp2 domain plus one half-wave exchange, O^T += V^T P^T with P^T as the B operand straight from the score registers.
 //   * causal: a workgroup walks the key tiles up to its last query row's diagonal; a wave skips tiles wholly above its own
 //     rows and masks only the tiles its diagonal crosses.
+//   * ragged batches (desc->dev_spans): the RAGGED instances read n_q, n_kv and q_pos0 of their request on the device and clamp
+//     them (prefill_rows); the grid and the block order are those of the bounds, a query block at or past a request's rows
+//     stores zeros and leaves before its first DMA, rows between a request's n_q and the bound are stored as zeros.  The
+//     lockstep instances (RAGGED = false) are the kernels without any of it.
 //
 // Roofline: MFMA (2.5 PFLOP/s dense fp16).  FLOPs = 4 d nh (number of unmasked (i, j) pairs).  Per 64-key tile a wave
 // issues 32 MFMAs (32 cycles each) and reads 32 KiB of LDS (K and V^T fragments are re-read by each of the 8 waves: 256
@@ -41,6 +45,7 @@ struct PrefillParams {
     int hpw;            // query heads per workgroup (1, 2, 4, 8)
     int n_qb;           // query blocks per head (of 256 / hpw rows)
     float scale_log2e;
+    const int *dev_spans;      // RAGGED: (bs, 4) {n_q, n_kv, q_pos0, reserved} per request, or null (the host values above)
 };
 
 constexpr int kWaves = 8;         // waves per workgroup
@@ -49,10 +54,18 @@ constexpr int kKV = 64;           // keys per tile
 // The rows of a wave and the key tiles of its workgroup (both kernels)
 struct PrefillRows {
     int b, hk, head;
+    int n_q, n_kv;               // the request's query rows and key rows: p.n_q / p.n_kv, or (RAGGED) its clamped device row
     int q_lo, q_row, q_pos;      // first query row of the wave, the lane's query row, its position among the keys (causal: keys <= q_pos)
     int nt;                      // key tiles of the workgroup: up to its last row's diagonal
     int w_pos_lo, w_pos_hi;      // positions of the wave's rows
+    bool wg_live;                // RAGGED: false for a query block at or past the request's rows, or a request without keys
 };
+// RAGGED: n_q, n_kv and q_pos0 are per request, read once from its device row (scalar loads: b is workgroup-uniform) and never
+// trusted - n_q into [0, p.n_q], n_kv and q_pos0 into [0, p.n_kv]; word 3 is not touched.  The grid, n_qb and the order of the
+// query blocks are those of the bounds p.n_q / p.n_kv; everything below this function takes the request's own lengths from
+// PrefillRows, so every tile boundary, clamp and mask is a function of them alone: a request's live rows are, bit for bit,
+// those of the lockstep call on that request with the same three values.
+template <bool RAGGED>
 __device__ __forceinline__ PrefillRows prefill_rows(const PrefillParams &p, int wave, int r32) {
     PrefillRows w;
     int id = blockIdx.x;
@@ -63,30 +76,53 @@ __device__ __forceinline__ PrefillRows prefill_rows(const PrefillParams &p, int 
     id /= n_hg;
     const int qb = p.n_qb - 1 - id % p.n_qb;      // heaviest query blocks first
     w.b = id / p.n_qb;
+    int n_q = p.n_q, n_kv = p.n_kv, q_pos0 = p.q_pos0;
+    if (RAGGED) {
+        // through the constant address space: the array is not written while the kernel runs, and only so does hipcc read it with
+        // scalar loads (a plain global pointer might alias out: one vector load and three v_readfirstlane instead)
+        typedef const __attribute__((address_space(4))) int *spans_p;
+        const spans_p row = (spans_p)(p.dev_spans + 4 * (long long)w.b);
+        n_q = row[0]; n_kv = row[1]; q_pos0 = row[2];
+        n_q = n_q < 0 ? 0 : (n_q > p.n_q ? p.n_q : n_q);
+        n_kv = n_kv < 0 ? 0 : (n_kv > p.n_kv ? p.n_kv : n_kv);
+        q_pos0 = q_pos0 < 0 ? 0 : (q_pos0 > p.n_kv ? p.n_kv : q_pos0);
+    }
+    w.n_q = n_q;
+    w.n_kv = n_kv;
     const int wph = kWaves / p.hpw;               // waves per head
     const int QB = wph * 32;                      // query rows per head in this workgroup
     const int g = hg * p.hpw + wave / wph;        // query head within the kv head's group
     w.head = w.hk * p.G + g;
     w.q_lo = qb * QB + (wave % wph) * 32;
     w.q_row = w.q_lo + r32;
-    w.q_pos = p.q_pos0 + w.q_row;
-    const int wg_q_hi = qb * QB + QB - 1 < p.n_q - 1 ? qb * QB + QB - 1 : p.n_q - 1;      // last query row of the workgroup
-    int kv_end_wg = p.causal ? p.q_pos0 + wg_q_hi + 1 : p.n_kv;
-    kv_end_wg = kv_end_wg < p.n_kv ? kv_end_wg : p.n_kv;
+    w.q_pos = q_pos0 + w.q_row;
+    const int wg_q_hi = qb * QB + QB - 1 < n_q - 1 ? qb * QB + QB - 1 : n_q - 1;      // last query row of the workgroup
+    int kv_end_wg = p.causal ? q_pos0 + wg_q_hi + 1 : n_kv;
+    kv_end_wg = kv_end_wg < n_kv ? kv_end_wg : n_kv;
     w.nt = kv_end_wg > 0 ? (kv_end_wg + kKV - 1) / kKV : 0;
-    w.w_pos_lo = p.q_pos0 + w.q_lo;
-    w.w_pos_hi = p.q_pos0 + w.q_lo + 31;
+    w.w_pos_lo = q_pos0 + w.q_lo;
+    w.w_pos_hi = q_pos0 + w.q_lo + 31;
+    w.wg_live = !RAGGED || (qb * QB < n_q && n_kv > 0);
     return w;
+}
+
+// RAGGED: zeros into the lane's output row if it lies below the bound p.n_q - for a row at or past its request's n_q, and for
+// every row of a workgroup without work (wg_live = false), which leaves through this before the first load of q, the first DMA
+// and the first barrier (workgroup-uniform).
+template <int NB>
+__device__ __forceinline__ void prefill_store_dead(const PrefillParams &p, const PrefillRows &w, int hh) {
+    if (w.q_row < p.n_q) flash_store_zero_row<NB>(p.out + w.b * p.o_sb + w.head * p.o_sh + (long long)w.q_row * p.o_sn, hh);
 }
 
 // the lane's query row of Q (rows past the end read the last one: their output is not stored)
 __device__ __forceinline__ const f16 *prefill_q_row(const PrefillParams &p, const PrefillRows &w) {
-    const int qr = w.q_row < p.n_q ? w.q_row : p.n_q - 1;
+    const int qr = w.q_row < w.n_q ? w.q_row : w.n_q - 1;
     return p.q + w.b * p.q_sb + w.head * p.q_sh + (long long)qr * p.q_sn;
 }
 
 // D = 128 (the Llama head size of every BASELINE config) and D = 64 (the other head size the reference builds, setup.py:12).
-template <int D>
+// RAGGED (both kernels): the instances behind desc->dev_spans; the lockstep instances (RAGGED = false) are the kernels without any of it.
+template <int D, bool RAGGED>
 __global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_kernel(PrefillParams p) {
     constexpr int DS = D / 16;                 // k-steps of the score product
     constexpr int NB = D / 32;                 // 32-row blocks of O^T
@@ -96,9 +132,10 @@ __global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_kernel(PrefillPar
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r32 = lane & 31, hh = lane >> 5;
-    const PrefillRows w = prefill_rows(p, wave, r32);
-    const int nt = w.nt;
-    const bool wave_live = w.q_lo < p.n_q;                                                 // wave-uniform
+    const PrefillRows w = prefill_rows<RAGGED>(p, wave, r32);
+    if (RAGGED && !w.wg_live) { prefill_store_dead<NB>(p, w, hh); return; }
+    const int nt = w.nt, n_q = w.n_q, n_kv = w.n_kv;
+    const bool wave_live = w.q_lo < n_q;                                                   // wave-uniform
     v8h qf[DS];
     flash_load_q<D>(qf, prefill_q_row(p, w), hh);
 
@@ -121,7 +158,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_kernel(PrefillPar
             const int pcg = wave + kWaves * i;          // wave-uniform: pieces [0, kPieces) are K, the rest V
             const bool is_v = pcg >= kPieces;
             int kvr = t * kKV + prc[i].row;
-            kvr = kvr < p.n_kv ? kvr : p.n_kv - 1;      // clamped: rows past the end are masked below
+            kvr = kvr < n_kv ? kvr : n_kv - 1;          // clamped: rows past the end are masked below
             const f16 *src = (is_v ? vbase + (long long)kvr * p.v_sn : kbase + (long long)kvr * p.k_sn) + 8 * prc[i].ch;
             const unsigned dst = 2u * kTileBytes * buf + (is_v ? kTileBytes : 0) + 1024u * (pcg % kPieces);
             asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(src), "s"(dst) : "memory", "m0");
@@ -154,9 +191,9 @@ __global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_kernel(PrefillPar
             float sc[32];
             flash_scores<D, kb>(sc, qf, r32, hh);
             // ---- mask (only where the diagonal or the end of the keys crosses this tile) ----
-            const bool need_mask = (p.causal && kv0 + kKV - 1 > w.w_pos_lo) || kv0 + kKV > p.n_kv;      // wave-uniform
+            const bool need_mask = (p.causal && kv0 + kKV - 1 > w.w_pos_lo) || kv0 + kKV > n_kv;        // wave-uniform
             if (need_mask) {
-                const int lim = p.causal ? (w.q_pos < p.n_kv - 1 ? w.q_pos : p.n_kv - 1) : p.n_kv - 1;     // last key this row attends to
+                const int lim = p.causal ? (w.q_pos < n_kv - 1 ? w.q_pos : n_kv - 1) : n_kv - 1;           // last key this row attends to
 #pragma unroll
                 for (int j = 0; j < 32; ++j) {
                     const int kv = kv0 + 32 * (j >> 4) + (j & 3) + 8 * ((j & 15) >> 2) + 4 * hh;
@@ -174,7 +211,8 @@ __global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_kernel(PrefillPar
         if (t + 1 < nt) tile(std::integral_constant<int, 1>{}, t + 1);
     }
     l_run = flash_l_total(l_run);
-    if (wave_live && w.q_row < p.n_q) flash_store_row(O, l_run, p.out + w.b * p.o_sb + w.head * p.o_sh + (long long)w.q_row * p.o_sn, hh);
+    if (wave_live && w.q_row < n_q) flash_store_row(O, l_run, p.out + w.b * p.o_sb + w.head * p.o_sh + (long long)w.q_row * p.o_sn, hh);
+    else if (RAGGED) prefill_store_dead<NB>(p, w, hh);      // rows between the request's n_q and the bound
 }
 
 // =====================================================================================================
@@ -198,6 +236,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_kernel(PrefillPar
 // every product and behind every softmax slice fixes the order: M, 7 vector, M, 7 vector ... as written.
 // =====================================================================================================
 #define PF_PIN(x) asm volatile("" : "+v"(x))
+template <bool RAGGED>
 __global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_pipe_kernel(PrefillParams p) {
     constexpr int D = 128, DS = D / 16, NB = D / 32, kTileBytes = kKV * 2 * D;
     extern __shared__ __attribute__((aligned(16))) char pf_smem[];
@@ -205,8 +244,9 @@ __global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_pipe_kernel(Prefi
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r32 = lane & 31, hh = lane >> 5;
-    const PrefillRows w = prefill_rows(p, wave, r32);
-    const int q_pos = w.q_pos, nt = w.nt, w_pos_lo = w.w_pos_lo, w_pos_hi = w.w_pos_hi;
+    const PrefillRows w = prefill_rows<RAGGED>(p, wave, r32);
+    if (RAGGED && !w.wg_live) { prefill_store_dead<NB>(p, w, hh); return; }
+    const int q_pos = w.q_pos, nt = w.nt, w_pos_lo = w.w_pos_lo, w_pos_hi = w.w_pos_hi, n_q = w.n_q, n_kv = w.n_kv;
     v8h qf[DS];
     flash_load_q<D>(qf, prefill_q_row(p, w), hh);
     // Q stays as it is given and a half's score products start from -reference instead of 0: the accumulator is s - reference in
@@ -217,9 +257,9 @@ __global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_pipe_kernel(Prefi
     const float cs = p.scale_log2e, thr_raw = 8.0f / cs;      // P <= 2^8: the accumulator may rise to 8 / cs before the reference moves
     const int nh2 = 2 * nt;                                              // 32-key halves of this workgroup
 #if MILLION_EXP & 16384
-    const bool wave_live = w.q_lo < p.n_q && wave < 4;      // diagnostic: one computing wave per SIMD (its partner only issues DMA and joins barriers)
+    const bool wave_live = w.q_lo < n_q && wave < 4;      // diagnostic: one computing wave per SIMD (its partner only issues DMA and joins barriers)
 #else
-    const bool wave_live = w.q_lo < p.n_q;
+    const bool wave_live = w.q_lo < n_q;
 #endif
     const f16 *kbase = p.k + w.b * p.k_sb + w.hk * p.k_sh;
     const f16 *vbase = p.v + w.b * p.v_sb + w.hk * p.v_sh;
@@ -229,7 +269,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_pipe_kernel(Prefi
     for (int i = 0; i < 2; ++i) prc[i] = tile_rc<D>(64 * (wave + kWaves * i) + lane);
     auto dma_piece = [&](int t, int i, bool is_v) {      // piece wave + 8 i of tile t's K or V side -> buffer t & 1
         int kvr = t * kKV + prc[i].row;
-        kvr = kvr < p.n_kv ? kvr : p.n_kv - 1;
+        kvr = kvr < n_kv ? kvr : n_kv - 1;      // the request's own last key row: a V row past it may hold NaN, and 0 x NaN is NaN
         const f16 *src = (is_v ? vbase + (long long)kvr * p.v_sn : kbase + (long long)kvr * p.k_sn) + 8 * prc[i].ch;
         const unsigned dst = 2u * kTileBytes * (t & 1) + (is_v ? kTileBytes : 0) + 1024u * (wave + kWaves * i);
         asm volatile("s_mov_b32 m0, %1\n\tglobal_load_lds_dwordx4 %0, off" :: "v"(src), "s"(dst) : "memory", "m0");
@@ -248,10 +288,10 @@ __global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_pipe_kernel(Prefi
 
     // wave-uniform predicates of half h (keys 32 h .. 32 h + 31) for this wave
     auto live = [&](int h) { return h < nh2 && wave_live && (!p.causal || 32 * h <= w_pos_hi); };
-    auto masked = [&](int h) { return (p.causal && 32 * h + 31 > w_pos_lo) || 32 * h + 32 > p.n_kv; };
+    auto masked = [&](int h) { return (p.causal && 32 * h + 31 > w_pos_lo) || 32 * h + 32 > n_kv; };
     // raw scores of half h -> -inf where the row does not attend; compares against immediates: key = 32 h + 4 hh + (j & 3) + 8 (j >> 2) <= lim
     auto mask_half = [&](int h, v16f &S) {
-        const int lim = p.causal ? (q_pos < p.n_kv - 1 ? q_pos : p.n_kv - 1) : p.n_kv - 1;
+        const int lim = p.causal ? (q_pos < n_kv - 1 ? q_pos : n_kv - 1) : n_kv - 1;
         const int rel = lim - 32 * h - 4 * hh;
 #pragma unroll
         for (int j = 0; j < 16; ++j) S[j] = (j & 3) + 8 * (j >> 2) <= rel ? S[j] : -INFINITY;
@@ -449,22 +489,32 @@ __global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_pipe_kernel(Prefi
 #undef PF_KFRAG
 #undef PF_VFRAG
     l_run = flash_l_total(l_run);
-    if (wave_live && w.q_row < p.n_q) flash_store_row(O, l_run, p.out + w.b * p.o_sb + w.head * p.o_sh + (long long)w.q_row * p.o_sn, hh);
+    if (wave_live && w.q_row < n_q) flash_store_row(O, l_run, p.out + w.b * p.o_sb + w.head * p.o_sh + (long long)w.q_row * p.o_sn, hh);
+    else if (RAGGED) prefill_store_dead<NB>(p, w, hh);      // rows between the request's n_q and the bound
 }
 #undef PF_PIN
 
 template <int D>
 static void launch_prefill_t(const PrefillParams &p, long long blocks, int lds, hipStream_t s) {
-    hipLaunchKernelGGL((prefill_attn_kernel<D>), dim3((unsigned)blocks), dim3(kWaves * 64), lds, s, p);
+    if (p.dev_spans) hipLaunchKernelGGL((prefill_attn_kernel<D, true>), dim3((unsigned)blocks), dim3(kWaves * 64), lds, s, p);
+    else hipLaunchKernelGGL((prefill_attn_kernel<D, false>), dim3((unsigned)blocks), dim3(kWaves * 64), lds, s, p);
 }
-// dynamic-LDS attribute of the three kernels: once per device, under the library's per-device mutex (common.h: device_once)
+static void launch_prefill_pipe(const PrefillParams &p, long long blocks, int lds, hipStream_t s) {
+    if (p.dev_spans) hipLaunchKernelGGL(prefill_attn_pipe_kernel<true>, dim3((unsigned)blocks), dim3(kWaves * 64), lds, s, p);
+    else hipLaunchKernelGGL(prefill_attn_pipe_kernel<false>, dim3((unsigned)blocks), dim3(kWaves * 64), lds, s, p);
+}
+// dynamic-LDS attribute of the three kernels (lockstep and ragged instances): once per device, under the library's per-device mutex (common.h: device_once)
 static bool g_prefill_plain = false;      // A/B and tests (million_set_force_generic(64)): the plain form at d = 128 too
 void set_prefill_policy(bool plain) { g_prefill_plain = plain; }
 static void prefill_attrs_once() {
     if (!device_once(3)) return;
-    (void)hipFuncSetAttribute((const void *)prefill_attn_pipe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * kKV * 2 * 128);
-    (void)hipFuncSetAttribute((const void *)prefill_attn_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * kKV * 2 * 128);
-    (void)hipFuncSetAttribute((const void *)prefill_attn_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * kKV * 2 * 64);
+    const auto lds_attr = [](const void *kernel, int bytes) { (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); };
+    lds_attr((const void *)prefill_attn_pipe_kernel<false>, 4 * kKV * 2 * 128);
+    lds_attr((const void *)prefill_attn_pipe_kernel<true>, 4 * kKV * 2 * 128);
+    lds_attr((const void *)prefill_attn_kernel<128, false>, 4 * kKV * 2 * 128);
+    lds_attr((const void *)prefill_attn_kernel<128, true>, 4 * kKV * 2 * 128);
+    lds_attr((const void *)prefill_attn_kernel<64, false>, 4 * kKV * 2 * 64);
+    lds_attr((const void *)prefill_attn_kernel<64, true>, 4 * kKV * 2 * 64);
 }
 
 int launch_prefill(const PrefillParams &p_in, hipStream_t s) {
@@ -480,7 +530,7 @@ int launch_prefill(const PrefillParams &p_in, hipStream_t s) {
     if (blocks > 0x7fffffffLL) { set_error("prefill: %lld workgroups", blocks); return MILLION_ERR_SHAPE; }
     const int lds = 4 * kKV * 2 * p.d;      // two buffers of (K tile, V tile)
     prefill_attrs_once();
-    if (p.d == 128 && !g_prefill_plain) hipLaunchKernelGGL(prefill_attn_pipe_kernel, dim3((unsigned)blocks), dim3(kWaves * 64), lds, s, p);
+    if (p.d == 128 && !g_prefill_plain) launch_prefill_pipe(p, blocks, lds, s);
     else if (p.d == 128) launch_prefill_t<128>(p, blocks, lds, s);
     else launch_prefill_t<64>(p, blocks, lds, s);
     const hipError_t e = hipGetLastError();
@@ -516,5 +566,6 @@ extern "C" int million_prefill_attn(const million_prefill_desc *desc, const void
         return MILLION_ERR_ALIGN;
     }
     p.scale_log2e = 1.4426950408889634f / sqrtf((float)p.d);
+    p.dev_spans = desc->dev_spans;      // non-null: n_q and n_kv above are the bounds, q_pos0 is not read (validated all the same)
     return launch_prefill(p, (hipStream_t)stream);
 }

@@ -388,11 +388,22 @@ def pq_decode_attn(q: torch.Tensor, k_codes: torch.Tensor, v_codes: torch.Tensor
 
 
 def prefill_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, causal: bool = True, q_pos0: int = 0,
-                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 out: Optional[torch.Tensor] = None, dev_spans: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Prompt attention on fp16 K/V (million_prefill_attn): q (bs, nh, n_q, d), k / v (bs, nh_k, n_kv, d) -> (bs, nh, n_q, d).
     Replaces scaled_dot_product_attention(q, repeat_kv(k), repeat_kv(v), is_causal=True) of the reference's prompt pass
     (pq_utils.py:249-260) without materialising repeat_kv.  Row strides are free (transposed (bs, n, h, d) projections are
-    fine), the d elements of a row must be contiguous."""
+    fine), the d elements of a row must be contiguous.
+    dev_spans: a ragged batch - int32 (bs, 4) rows {n_q, n_kv, q_pos0, reserved} on q's device, read by the kernel when it runs
+    (a captured call follows them).  The tensors' n_q and n_kv are then the bounds of the padded layout, `q_pos0` is not used,
+    each request attends with its own three values (clamped into the bounds); rows past a request's n_q come back as zeros, a
+    request without keys as zeros, and q rows past n_q[b], K / V rows past n_kv[b] and `out` may hold anything before the call."""
+    if dev_spans is not None:      # first: what is wrong with the rows is said before anything about the tensors beside them
+        if not isinstance(dev_spans, torch.Tensor) or dev_spans.dtype != torch.int32:
+            raise RuntimeError("prefill_attn: dev_spans must be an int32 tensor")
+        if q.dim() != 4 or tuple(dev_spans.shape) != (q.shape[0], 4) or not dev_spans.is_contiguous():
+            raise RuntimeError(f"prefill_attn: dev_spans must be contiguous, of shape (bs, 4) = ({q.shape[0] if q.dim() == 4 else '?'}, 4)")
+        if not dev_spans.is_cuda or dev_spans.device != q.device:
+            raise RuntimeError("prefill_attn: dev_spans must live on the device of q (the kernel reads it there)")
     _need_cuda(q, k, v, out)
     if q.dtype != torch.float16 or k.dtype != torch.float16 or v.dtype != torch.float16:
         raise RuntimeError("prefill_attn: q, k, v must be fp16")
@@ -418,6 +429,7 @@ def prefill_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, causal: b
     desc.k_stride_b, desc.k_stride_h, desc.k_stride_n = k.stride(0), k.stride(1), k.stride(2)
     desc.v_stride_b, desc.v_stride_h, desc.v_stride_n = v.stride(0), v.stride(1), v.stride(2)
     desc.o_stride_b, desc.o_stride_h, desc.o_stride_n = out.stride(0), out.stride(1), out.stride(2)
+    desc.dev_spans = _ptr(dev_spans)
     L.check(L.load().million_prefill_attn(ctypes.byref(desc), q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _stream()),
             "million_prefill_attn")
     return out

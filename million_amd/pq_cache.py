@@ -181,10 +181,11 @@ class _CacheBase:
         else:
             self._kprep = self._vprep = None
 
-    def _prefill_attention(self, q, k, v):
+    def _prefill_attention(self, q, k, v, dev_spans=None):
         """Causal attention of the prompt on its own fp16 K/V (reference: repeat_kv + torch SDPA, pq_utils.py:249-260):
-        the MFMA flash kernel of this library (csrc/prefill.hip), the G query heads of a kv head sharing its K/V tiles."""
-        return ops.prefill_attn(q, k, v, causal=True)
+        the MFMA flash kernel of this library (csrc/prefill.hip), the G query heads of a kv head sharing its K/V tiles.
+        dev_spans: the per-request lengths of a ragged batch (ops.prefill_attn)."""
+        return ops.prefill_attn(q, k, v, causal=True, dev_spans=dev_spans)
 
 
 class DynamicPQCache(_CacheBase):
@@ -368,7 +369,8 @@ class PagedPQCache(_CacheBase):
 
     Lengths are kept per (layer, request) - on the host (numpy, (layers, bs)) and on the device (`lengths[l]`, int32
     (bs, 4)) - so that a batch slot can finish and be recycled while the others keep decoding: `release(b)` returns the
-    slot's pages and zeroes its lengths, `prefill_request(b, ...)` encodes a new prompt into it.  Requests of different
+    slot's pages and zeroes its lengths, `prefill_request(b, ...)` encodes a new prompt into it (`prefill_ragged`: several
+    slots' prompts of different lengths, one attention launch).  Requests of different
     lengths share every launch through the device-resident lengths (`use_dev_lengths=True`)."""
 
     def __init__(self, *, bs, nh, num_key_value_heads, M, layer_num, dtype=torch.uint8, nbits=8, d=128,
@@ -501,6 +503,37 @@ class PagedPQCache(_CacheBase):
         self._seen_a[layer_idx, b] += n
         self._sync_lengths(layer_idx)
         return self._prefill_attention(query_states, key_states, value_states)
+
+    def prefill_ragged(self, query_states, key_states, value_states, layer_idx, n_new):
+        """prefill_request() for every slot in ONE attention launch - the counterpart of extend_ragged for empty slots, at
+        the prompt kernel's rate: tensors of batch bs padded to n = max(n_new) rows, slot b owns the first n_new[b] of them
+        (n_new: bs host ints in [0, n]).  A slot with n_new[b] > 0 must be empty (T = r = 0; a slot that holds tokens takes
+        extend_ragged).  The launch reads the rows {n_b, n_b, 0, 0} from a small device tensor; the rows past n_new[b] - q, K
+        and V - may hold anything and their output rows are zeros.  The encodes stay host-driven per slot; slot b is then left
+        exactly as prefill_request(b, ...) with its own rows leaves it (pages, host lengths, its device row).  A slot with
+        n_new[b] = 0 takes no part: host and device lengths, pages and window stay as they are (it may be mid-decode)."""
+        n_new = [int(x) for x in n_new]
+        n = query_states.size(2)
+        if (len(n_new) != self.bs or query_states.size(0) != self.bs or key_states.size(0) != self.bs or key_states.size(2) != n
+                or value_states.shape != key_states.shape):
+            raise RuntimeError(f"prefill_ragged: tensors of batch {self.bs}, padded to the same rows, and one n_new per slot")
+        if any(x < 0 or x > n for x in n_new):
+            raise RuntimeError(f"prefill_ragged: n_new outside [0, {n}]")
+        who = [b for b in range(self.bs) if n_new[b] > 0]
+        for b in who:      # every slot's precondition and capacity before anything is launched
+            if self._T_a[layer_idx, b] or self._r_a[layer_idx, b]:
+                raise RuntimeError(f"prefill_ragged: slot {b} holds tokens (release it first, or use extend_ragged)")
+            if n_new[b] > self.max_tokens:
+                raise RuntimeError(f"PagedPQCache: {n_new[b]} tokens exceed max_tokens={self.max_tokens}")
+        spans = torch.tensor([[x, x, 0, 0] for x in n_new], dtype=torch.int32).to(self.device)
+        out = self._prefill_attention(query_states, key_states, value_states, dev_spans=spans)
+        for b in who:      # the encodes stay host-driven per slot, as prefill_request does them
+            sel, x = slice(b, b + 1), n_new[b]
+            self._encode_to_pages(key_states[sel, :, :x], value_states[sel, :, :x], layer_idx, x, b=b)
+            self._T_a[layer_idx, b] += x
+            self._seen_a[layer_idx, b] += x
+            self.lengths[layer_idx][b].copy_(torch.tensor([int(self._T_a[layer_idx, b]), 0, 0, 0], dtype=torch.int32))
+        return out
 
     # ---- extend: a block of new tokens behind the cached ones ------------------------------------------------------------
     def _join_side(self, layer_idx, b=None):

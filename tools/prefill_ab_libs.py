@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Development helper: prompt attention (million_prefill_attn, default policy) of TWO builds of the library in one process, same
 tensors, alternating rounds (A B A B ...), HIP events, median of the repeats of a round; and the largest difference of their outputs.
-    python tools/prefill_ab_libs.py build/ab/libmillion_parent.so million_amd/libmillion_hip.so [--rounds 5] [--out FILE]"""
+    python tools/prefill_ab_libs.py build/ab/libmillion_parent.so million_amd/libmillion_hip.so [--rounds 5] [--n 32768] [--out FILE]
+A build from before a trailing field of million_prefill_desc (dev_spans) is recognised by the struct_size it accepts; both builds
+get the lockstep call (dev_spans = NULL).  Each line ends with the band of the rounds' medians, lowest .. highest, of both builds."""
 import argparse
 import ctypes
 import sys
@@ -16,6 +18,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("lib_a")
 ap.add_argument("lib_b")
 ap.add_argument("--rounds", type=int, default=5)
+ap.add_argument("--n", type=int, default=None, help="only the shapes with this many tokens")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
@@ -25,9 +28,22 @@ for lib in libs:
     lib.million_prefill_attn.argtypes = [ctypes.POINTER(L.PrefillDesc)] + [ctypes.c_void_p] * 5
 
 
+def desc_bytes(lib):
+    """The struct_size this build accepts: today's, or the one without the trailing pointer (n_q = 0 returns before any launch)."""
+    for size in (ctypes.sizeof(L.PrefillDesc), ctypes.sizeof(L.PrefillDesc) - 8):
+        desc = L.PrefillDesc()
+        desc.struct_size, desc.bs, desc.nh, desc.nh_k, desc.d = size, 1, 1, 1, 128
+        if lib.million_prefill_attn(ctypes.byref(desc), 16, 16, 16, 16, None) == 0:
+            return size
+    raise RuntimeError("neither descriptor size is accepted")
+
+
+sizes = {id(lib): desc_bytes(lib) for lib in libs}
+
+
 def call(lib, q, k, v, out):
     desc = L.PrefillDesc()
-    desc.struct_size = ctypes.sizeof(L.PrefillDesc)
+    desc.struct_size = sizes[id(lib)]
     desc.bs, desc.nh, desc.n_q, desc.d = q.shape
     desc.nh_k, desc.n_kv, desc.q_pos0, desc.causal = k.shape[1], k.shape[2], 0, 1
     for name, t in (("q", q), ("k", k), ("v", v), ("o", out)):
@@ -53,6 +69,8 @@ def timed(fn, reps):
 
 lines = [f"A = {args.lib_a}   B = {args.lib_b}   (TFLOP/s = 2 d nh n (n + 1) / time; rounds alternate A, B)"]
 for (bs, nh, nhk, n) in ((1, 32, 8, 4096), (1, 32, 8, 32768), (1, 32, 32, 32768), (1, 32, 8, 131072)):
+    if args.n is not None and n != args.n:
+        continue
     d = 128
     q, k, v = (torch.randn(bs, h, n, d, device=dev).half() for h in (nh, nhk, nhk))
     outs = [torch.empty_like(q), torch.empty_like(q)]
@@ -65,7 +83,8 @@ for (bs, nh, nhk, n) in ((1, 32, 8, 4096), (1, 32, 8, 32768), (1, 32, 32, 32768)
     tf = [[flops / t / 1e9 for t in m] for m in ms]
     best = [max(t) for t in tf]
     lines.append(f"n={n:6d} nh_k={nhk:2d}:  A best {best[0]:7.1f} ({' '.join('%.0f' % x for x in tf[0])})   B best {best[1]:7.1f} "
-                 f"({' '.join('%.0f' % x for x in tf[1])})   B / A {best[1] / best[0] - 1:+.1%}   max |A - B| {diff:.2e}")
+                 f"({' '.join('%.0f' % x for x in tf[1])})   B / A {best[1] / best[0] - 1:+.1%}   max |A - B| {diff:.2e}   "
+                 f"bands A {min(tf[0]):.1f} .. {max(tf[0]):.1f}  B {min(tf[1]):.1f} .. {max(tf[1]):.1f}")
     print(lines[-1], flush=True)
     del q, k, v, outs
     torch.cuda.empty_cache()
