@@ -9,8 +9,8 @@ Every case builds two copies of the same valid data:
               (always an id inside the pool); window rows outside [resid_start, resid_start + r) - the row a fused append is
               about to write included - are fp16 NaN; out is NaN before every call.
 At C = 256, 0xFF is a valid code: a leak then gives a finite but wrong answer, which only the exact comparison of the two runs
-catches.  Checks (check_case): the kernel kind, the clean run against the fp64 oracle, the poisoned run bitwise equal to the
-clean one, the fused append's window row, the rest of the window and the device lengths."""
+catches.  Checks (check_case): the kernel kind, the clean run against the fp64 oracle (whole tensor and every head), the
+poisoned run bitwise equal to the clean one, the fused append's window row, the rest of the window and the device lengths."""
 from __future__ import annotations
 
 import ctypes
@@ -155,10 +155,13 @@ def make_desc(c: Case, lib_types):
     return d
 
 
-def build(c: Case) -> dict:
+def build(c: Case, src: dict | None = None) -> dict:
     """Both copies of a case's data plus the live masks: {"clean": {...}, "poisoned": {...}, "live": {...}, "codes": ...}.
     Arrays: q, k_cents, v_cents, k_codes, v_codes, ids (paged sides; None otherwise), k_res, v_res, k_new, v_new (append),
-    lengths (dev).  live[name] is True where the two copies must agree."""
+    lengths (dev).  live[name] is True where the two copies must agree.
+    src: the valid data from elsewhere (tests/decode_inputs.py: an input family) instead of this function's own N(0, 1) draws:
+    q (bs, nh, 1, d), k_cents, v_cents, row-major k_codes / v_codes (bs, nh_k, T, M), k_res / v_res of cap rows and, for an
+    appending case, k_new / v_new; layouts, poison and masks are built around it as around the draws."""
     rs_ = np.random.RandomState(zlib.crc32(c.name.encode()))
     f = lambda *s: rs_.standard_normal(s).astype(np.float16)
     bs, nhk, T, M, ps = c.bs, c.nhk, c.T, c.M, c.ps
@@ -168,6 +171,13 @@ def build(c: Case) -> dict:
     kres, vres = f(bs, nhk, c.cap, c.d), f(bs, nhk, c.cap, c.d)
     if c.append:
         base["k_new"], base["v_new"] = f(bs, nhk, 1, c.d), f(bs, nhk, 1, c.d)
+    if src is not None:
+        for nm in base:
+            assert src[nm].shape == base[nm].shape and src[nm].dtype == base[nm].dtype, nm
+            base[nm] = src[nm]
+        for nm, own in (("k_codes", kcodes), ("v_codes", vcodes), ("k_res", kres), ("v_res", vres)):
+            assert src[nm].shape == own.shape and src[nm].dtype == own.dtype, nm
+        kcodes, vcodes, kres, vres = src["k_codes"], src["v_codes"], src["k_res"], src["v_res"]
     clean, pois, live = dict(base), dict(base), {}
 
     # window: valid rows of the ring; everything else 0 / NaN
@@ -315,6 +325,12 @@ def run(c: Case, arrs: dict, torch, ops, lib, lib_types) -> dict:
     return res
 
 
+def head_err(out, gold) -> np.ndarray:
+    """||out - gold||_2 / ||gold||_2 over d for every (b, h) of a decode step's (bs, nh, 1, d) output: (bs, nh)."""
+    out, gold = np.asarray(out, np.float64), np.asarray(gold, np.float64)
+    return (np.linalg.norm(out - gold, axis=-1) / np.maximum(np.linalg.norm(gold, axis=-1), 1e-300))[:, :, 0]
+
+
 def _bits(a):
     return np.ascontiguousarray(a).view(np.uint16)
 
@@ -332,6 +348,10 @@ def check_case(c: Case, torch, ops, lib, lib_types, oracle) -> dict:
     rel = np.linalg.norm(o - g) / max(np.linalg.norm(g), 1e-30)
     mae = np.abs(o - g).mean()
     assert rel < REL_TOL and mae < MEAN_ABS_TOL, f"{c.name}: clean run vs oracle rel={rel:.3e} mean_abs={mae:.3e}"
+    e = head_err(o, g)      # and every head on its own
+    b_, h_ = np.unravel_index(np.argmax(e), e.shape)
+    assert e[b_, h_] < REL_TOL, (f"{c.name}: clean run, worst head (b={b_}, h={h_}) rel-L2 {e[b_, h_]:.3e} >= {REL_TOL:g}; "
+                                 f"{int((e >= REL_TOL).sum())} of {e.size} heads fail (whole tensor {rel:.3e})")
     po = pois["out"]
     n_bad = int((~np.isfinite(po.astype(np.float32))).sum())
     assert n_bad == 0, f"{c.name}: poisoned run has {n_bad} non-finite outputs"
@@ -358,4 +378,4 @@ def check_case(c: Case, torch, ops, lib, lib_types, oracle) -> dict:
             assert np.array_equal(run_["lengths"], want), f"{c.name}: lengths {run_['lengths'].tolist()} != {want.tolist()}"
     faults = ops.tail_faults()
     assert faults == 0, f"{c.name}: {faults} split merges gave up"
-    return {"rel": float(rel), "mean_abs": float(mae)}
+    return {"rel": float(rel), "mean_abs": float(mae), "worst_head": float(e[b_, h_])}

@@ -29,6 +29,7 @@ FAMILIES = {
     "gauss4-v*2^10": ("gauss", 4, 10), "gauss4-v*2^-6": ("gauss", 4, -6),
 }
 PEAKS = ("code_first", "code_last", "window_wrap", "chunk_row")
+DECODE_PEAKS = ("code_first", "code_last", "window_wrap", "appended")      # tests/decode_inputs.py: the row a fused append writes
 
 SINK_NATS = 8.0           # sink_local: key 0 lies this far above the noise, and the ramp climbs as far over the last 64 keys
 PEAK_NATS = 16.0          # peak_in: the dominating key
@@ -112,13 +113,14 @@ def prefill_inputs(name, bs, nh, nh_k, n_q, n_kv, d):
 def chunk_inputs(name, bs, nh, nh_k, d, M, C, n_q, T, r, cap, rstart, chunk, peak=None):
     """The state dict of test_chunk_attn_gpu._state / _run for family `name` over the concatenated key axis [T codes | r window
     rows from rstart in a ring of cap | the chunk's n_q rows].  peak: one of PEAKS (name is then ignored: gauss(1) plus one
-    dominating key in that segment)."""
+    dominating key in that segment; "appended": the first chunk row - at n_q = 1 the row a decode step appends)."""
     n_c = n_q if chunk else 0
     n_keys = T + r + n_c
     at = None
     if peak is not None:
         name = "peak_in:" + peak
-        at = {"code_first": min(5, T - 1), "code_last": T - 1, "window_wrap": T + (cap - rstart), "chunk_row": T + r + n_q // 2}[peak]
+        at = {"code_first": min(5, T - 1), "code_last": T - 1, "window_wrap": T + (cap - rstart), "chunk_row": T + r + n_q // 2,
+              "appended": T + r}[peak]
         assert 0 <= at < n_keys and (peak != "window_wrap" or (0 < cap - rstart < r)), "the shape has no such segment"
     rs = np.random.RandomState(_seed(name, bs, nh, nh_k, d, M, C, n_q, T, r, cap, rstart, chunk))
     sp = _spec(name, n_keys, d, at)
@@ -200,10 +202,11 @@ def row_err(out, gold):
     return np.linalg.norm(out - gold, axis=-1) / np.maximum(np.linalg.norm(gold, axis=-1), 1e-300)
 
 
-def check_rows(out, gold, what="", rows=None, unit=1.0, tol=REL_TOL):
+def check_rows(out, gold, what="", rows=None, unit=1.0, tol=REL_TOL, tag="FLASHNUM", each="row"):
     """Every output row within `tol` of gold, beside the whole-tensor bars (rel-L2 < REL_TOL, mean-abs < MEAN_ABS_TOL in units of
     `unit`, the scale of V).  rows: the query indices of axis 2 when only sampled rows are compared (for the message).
-    Prints and returns (worst row, 99th-percentile row, whole tensor)."""
+    Prints (one line, prefixed by `tag`; each: what a row of this output is called) and returns (worst row, 99th-percentile row,
+    whole tensor)."""
     out, gold = np.asarray(out, np.float64), np.asarray(gold, np.float64)
     assert out.shape == gold.shape, f"{what}: shape {out.shape} vs {gold.shape}"
     assert np.isfinite(out).all(), f"{what}: non-finite output"
@@ -212,10 +215,10 @@ def check_rows(out, gold, what="", rows=None, unit=1.0, tol=REL_TOL):
     mae = np.abs(out - gold).mean() / unit
     b, h, i = np.unravel_index(np.argmax(e), e.shape)
     worst, p99 = float(e[b, h, i]), float(np.percentile(e, 99))
-    print(f"FLASHNUM {what}: worst row {worst:.2e} p99 {p99:.2e} whole {rel:.2e}")
+    print(f"{tag} {what}: worst {each} {worst:.2e} p99 {p99:.2e} whole {rel:.2e}")
     qi = i if rows is None else int(np.asarray(rows)[i])
-    assert worst < tol, (f"{what}: worst row (b={b}, h={h}, i={qi}) rel-L2 {worst:.3e} >= {tol:g}; "
-                         f"{int((e >= tol).sum())} of {e.size} rows fail (99th percentile {p99:.3e}, whole tensor {rel:.3e})")
+    assert worst < tol, (f"{what}: worst {each} (b={b}, h={h}, i={qi}) rel-L2 {worst:.3e} >= {tol:g}; "
+                         f"{int((e >= tol).sum())} of {e.size} {each}s fail (99th percentile {p99:.3e}, whole tensor {rel:.3e})")
     assert rel < REL_TOL and mae < MEAN_ABS_TOL, f"{what}: whole tensor rel={rel:.3e} mean_abs={mae:.3e}"
     return worst, p99, rel
 

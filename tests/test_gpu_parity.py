@@ -12,7 +12,7 @@ import json
 import numpy as np
 import pytest
 
-from tests import synth
+from tests import decode_poison, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -40,6 +40,12 @@ def _check(out, gold, what=""):
     rel = np.linalg.norm(out - gold) / max(np.linalg.norm(gold), 1e-30)
     mae = np.abs(out - gold).mean()
     assert rel < REL_TOL and mae < MEAN_ABS_TOL, f"{what}: rel={rel:.3e} mean_abs={mae:.3e}"
+    if out.shape == gold.shape and (out.ndim == 3 or (out.ndim == 4 and out.shape[2] == 1)):
+        # a decode step, (bs, nh, 1, d) or (bs, nh, d): the bar holds for every (b, h) on its own
+        e = decode_poison.head_err(out.reshape(out.shape[:2] + (1, -1)), gold.reshape(out.shape[:2] + (1, -1)))
+        b, h = np.unravel_index(np.argmax(e), e.shape)
+        assert e[b, h] < REL_TOL, (f"{what}: worst head (b={b}, h={h}) rel-L2 {e[b, h]:.3e} >= {REL_TOL:g}; {int((e >= REL_TOL).sum())} of "
+                                   f"{e.size} heads fail (whole tensor {rel:.3e})")
     return rel, mae
 
 
