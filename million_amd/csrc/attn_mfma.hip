@@ -124,6 +124,8 @@ static const int g_mfma_form = MILLION_DEV_M32_PACKED();
 void set_mfma_policy(int policy) { g_tail_test = policy & 3; g_lean_off = (policy >> 2) & 1; }
 
 // split policy: about one workgroup per CU; a split is at least 512 tokens long
+// (tests/test_decode_advance.py: _mfma_grid restates this rule - without the 64-round extension - to assert that its bs = 5 shape
+//  exceeds the chip, i.e. runs with nmerge = 1; the plan cannot be queried through the C ABI.  Change both together.)
 static int mfma_splits(const AttnParams &p, int cus) {
     const int bh = p.bs * p.nh_k;
     int ns = (cus + bh - 1) / bh;

@@ -26,6 +26,35 @@
 //   * the workgroup with the highest index clears the census line and the counter and advances the generation once its
 //     own poll has seen every flag (all census reads and stores of the launch are behind those flags);
 //   * nsplit = 1: the only workgroup normalises and writes the output itself.
+//
+// Window-length advance (fused append with device-resident lengths: r += 1 once per launch and request).  r may move only
+// when every workgroup of the request has read its lengths, and exactly one workgroup may move it: the primaries of the
+// request's nh_k (virtual) kv heads take a SECOND-LEVEL ticket on ws_cnt2[b], and the one that draws nh_k - 1 puts that
+// word back to 0 and bumps r.  Through round 5 this sat at the very end of the tail, behind the primary's polls, merge and
+// `out` stores: a returning atomic on a word that primaries on eight XCDs hit, then in the last of them a store, a load
+// of r, an add and a store - two dependent fabric round trips behind the end of the launch's last merge, i.e. on the
+// critical path of every step-form launch and of no other call form (profiles/ab_decode_advance.txt).  Now:
+//   * the ticket is REQUESTED as soon as the workgroup knows that it is the primary - behind the barrier that makes its
+//     arrival index visible, in front of the flag polls and the merge.  Why that is early enough to be safe: a workgroup
+//     takes its first-level index in tail_request, which it reaches behind its codebook barrier, and every wave of it has
+//     executed LAUNCH_FRONT_LENGTHS - the only place where either MFMA kernel reads dev_lengths - in front of that barrier.
+//     So idx == ns - 1 already says that all ns workgroups of the pair have read their lengths; a workgroup that is not
+//     dispatched yet has taken no index, so no primary exists before it has.  The request's last second-level ticket
+//     therefore says the same for every pair of the request.  Nothing else in the launch reads r (the append row's slot
+//     comes from the registers of the front);
+//   * it is a buffer atomic of wave kNW - 1, issued early and looked at late, like the first-level ticket: with helpers
+//     (nm = G = 4) waves 4 - 7 of a merger have no head to merge, so that wave waits for the answer while the others poll
+//     and merge (~1.4 us) and bumps r before they are done.  With one merger (grids larger than the chip), and where the
+//     primary takes over a helper's head, wave kNW - 1 polls and merges itself: its poll loads retire in order behind the
+//     returning atomic, so the first poll's wait is also the wait for the ticket - there the round trip runs IN FRONT of
+//     the wave's poll, not beside it; what is saved in that case is the second trip (no load of r) and that the wave's
+//     merge is not in front of the request.  ns = 1: the round trip follows the output stores, as before;
+//   * the last arriver does not load r: it stores 0 to the ticket word and issues an atomic add of 1 on the RAW device word
+//     (not the clamped value the launch computed with) whose result nobody uses - nothing the end of the kernel waits for
+//     beyond what the `out` stores already cost.  The ticket word is at rest when the launch ends (common.h), so the tile
+//     and scalar kernels, which take the same ticket behind their merge (common.h: ticket_and_merge), can alternate with
+//     these on one workspace.  No spin, no poll and no wait on another workgroup was added.
+// tests/test_decode_advance.py: back-to-back step-form launches on every path, and a CPU model over every interleaving.
 // =====================================================================================================
 __device__ __forceinline__ unsigned *tail_rec(const AttnParams &p, int bh) { return (unsigned *)p.ws_cnt + (long long)bh * kRecWords; }
 __device__ __forceinline__ unsigned *tail_flags(const AttnParams &p, int bh) { return p.ws_flags + (long long)bh * (2 * kFlagWords); }
@@ -285,6 +314,27 @@ __device__ __forceinline__ void merge_and_publish(const AttnParams &p, char *sme
     }
     if (p.dbg && tid == 0)      // diagnostics: slot 12 = 1 + "stored plain (every split on this XCD)", slot 13 = 1 + arrival index
         { unsigned long long *d_ = p.dbg + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * kStampWaves * kStampSlots; d_[12] = 1 + (same_xcd ? 1 : 0); d_[13] = 1 + idx; }
+    // ---- window-length advance of a fused append with device-resident lengths: the second-level ticket (ws_cnt2[b], one per
+    //      request; all nh_k primaries of the request hit this word, from eight XCDs) is REQUESTED here, in front of the polls
+    //      and the merge, and its answer is looked at behind them (see "Window-length advance" in the header).  Wave kNW - 1 of
+    //      a primary asks: with helpers (nm = G = 4) waves 4 - 7 of a merger have no head, so the round trip runs beside the
+    //      other waves' merge and this wave bumps r while they still merge; with one merger the wave polls and merges too, and
+    //      its first poll waits for the answer as well (in-order returns).  Every lane of the wave issues the instruction; only
+    //      lane 0 of a primary's wave addresses inside the descriptor (one word; none in a workgroup that is no primary): the
+    //      hardware drops the rest. ----
+#if !(MILLION_EXP & 64)      // (A/B: no advance at all - what the step form pays for it, profiles/ab_decode_advance.txt)
+    // (kernel-uniform branch: a launch that does not advance r - plain, append-only, device lengths only - keeps the
+    //  instruction stream it had.  Without it every workgroup of those launches issued one atomic the hardware drops, and its
+    //  wait: measured +0.04 .. +0.14 us on their medians at one request, inside their band, profiles/ab_decode_advance.txt)
+    const bool adv_wave = wave == kNW - 1 && p.k_new && p.dev_lengths_w;
+    const bool adv_mine = idx == ns - 1;      // workgroup-uniform
+    int adv_t2 = 0;
+    if (adv_wave) {
+        MILLION_STAMP(p, 14);
+        __amdgpu_buffer_rsrc_t r2 = __builtin_amdgcn_make_buffer_rsrc((void *)(p.ws_cnt2 + b), 0, adv_mine ? 4 : 0, 0x00020000);
+        adv_t2 = __builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(1, r2, lane == 0 ? 0 : (1 << 20), 0, 0);
+    }
+#endif
     // ---- the merge (round 4).  The workgroup whose arrival index is ns - 1 - the PRIMARY - is responsible for every head:
     //      every workgroup it waits for has taken its index, i.e. is resident, on its way to its own flag store, and waits
     //      for nothing itself, so its polls end under ANY dispatch order and residency.  The nm - 1 workgroups that arrived
@@ -381,16 +431,18 @@ __device__ __forceinline__ void merge_and_publish(const AttnParams &p, char *sme
         __hip_atomic_fetch_and(rec + 2, ~0xffu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // give-up bits off; the count stays
         __hip_atomic_store(rec + 4, ((unsigned)tl[6] + (unsigned)ns) & 0xffffffu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(rec + 3, want, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        // fused append with device-resident lengths: every workgroup of batch b has read its lengths once all nh_k
-        // heads have got this far; the last of them advances r
-        if (p.k_new && p.dev_lengths_w) {
-            const int t2 = __hip_atomic_fetch_add(p.ws_cnt2 + b, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (t2 == p.nh_k - 1) {
-                __hip_atomic_store(p.ws_cnt2 + b, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                p.dev_lengths_w[b * 4 + 1] += 1;
-            }
-        }
     }
+#if !(MILLION_EXP & 64)
+    // the answer of the second-level ticket (requested in front of the merge): the primary that took the request's last one
+    // puts the ticket word back to rest and bumps the raw r - a store and an add that returns nothing: nobody waits for either
+    if (adv_wave) {
+        if (lane == 0 && adv_mine && adv_t2 == p.nh_k - 1) {
+            __hip_atomic_store(p.ws_cnt2 + b, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            (void)__hip_atomic_fetch_add(p.dev_lengths_w + b * 4 + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        MILLION_STAMP(p, 15);
+    }
+#endif
     if (idx == ns - 1 && wave == 0) {      // census line back to zero, behind this wave's own poll (write-through: the next launch may run anywhere)
         __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc((void *)(tail_flags(p, bh) + kFlagWords), 0, kFlagWords * 4, 0x00020000);
         __builtin_amdgcn_raw_buffer_store_b32(0u, rc, lane * 4, 0, 16 /* sc1 */);

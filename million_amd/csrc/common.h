@@ -20,6 +20,11 @@ constexpr int kCntBytes = 1024;     // granule of the counter / flag blocks at t
 //   [3]     generation      } workgroups in bits 31:8 (never reset: a launch counts from [4]), give-up bits of the merge helpers
 //   [4]     count base      } in bits 7:0; flags of launch n carry generation + 1
 // Every word is at rest when a launch ends (ticket [0..1] zero, give-up bits zero, generation and base advanced).
+// The second-level ticket (one int per batch item, both kernel families) decides who advances r after a fused append with
+// device-resident lengths: the last merger of each of the request's nh_k kv heads adds 1, the one that draws nh_k - 1 stores
+// 0 again and bumps r.  The tile and scalar kernels take it behind their merge (ticket_and_merge below); the MFMA kernels
+// request it in front of their merge and bump r with an atomic add nobody waits for (attn_tail.h, "Window-length advance").
+// Either way the word is 0 when the launch ends, so launches of both families may alternate on one workspace.
 constexpr int kRecWords = 32;
 constexpr int kFlagWords = 64;      // one flag per split (the MFMA kernels use at most kMaxSplits = 64 slots)
 

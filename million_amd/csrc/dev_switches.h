@@ -8,6 +8,8 @@
 //
 //   MILLION_EXP (bit mask)
 //     attn_mfma.hip   2  the last-arriving workgroup merges alone (no helpers)                    profiles/r04_ab_merge.txt
+//     attn_tail.h    64  a fused append with device-resident lengths does not advance r: no second-level ticket, no bump
+//                        (timing only - what the step form pays for the advance; tools/advance_probe.py)  profiles/ab_decode_advance.txt
 //     attn_stream.h  32  "the launch without arithmetic": every request, wait, barrier and the tail stay, a unit's bytes are
 //                        xor-ed into a sink instead of gathered, multiplied and soft-maxed         profiles/r04_launch_floor.txt
 //     prefill.hip   (the pipelined kernel only; the plain loop's round 3-4 bits are in profiles/r03_prefill.txt, r04_prefill.txt)

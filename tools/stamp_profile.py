@@ -22,6 +22,8 @@ ap.add_argument("--layers", type=int, default=8)
 ap.add_argument("--raw", action="store_true", help="print every stamp id that was written, ordered by mean time")
 ap.add_argument("--M", type=int, default=64)
 ap.add_argument("--dev-lengths", action="store_true")
+ap.add_argument("--append", action="store_true", help="the step's own form: fused append (k_new / v_new) with device-resident lengths; r is put back before "
+                "every launch.  Stamps 14 / 15: in front of and behind the window-length advance (attn_tail.h), reported for the primaries")
 ap.add_argument("--policy", type=int, default=0, help="million_set_force_generic value (16: the lean kernel's shapes stay on the streaming kernel)")
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
@@ -41,15 +43,19 @@ vc = ops.prepare_cents(torch.randn(M, C, d // M, device=dev).half())
 q = torch.randn(bs, nh, 1, d, device=dev).half()
 kr = torch.randn(bs, nhk, 128, d, device=dev).half()
 vr = torch.randn(bs, nhk, 128, d, device=dev).half()
-dlen = torch.tensor([[T, args.r, 0, 0]] * bs, dtype=torch.int32, device=dev) if args.dev_lengths else None
+dlen = torch.tensor([[T, args.r, 0, 0]] * bs, dtype=torch.int32, device=dev) if (args.dev_lengths or args.append) else None
+dlen0 = dlen.clone() if dlen is not None else None
+new_rows = dict(k_new=torch.randn(bs, nhk, 1, d, device=dev).half(), v_new=torch.randn(bs, nhk, 1, d, device=dev).half()) if args.append else {}
 NW, NS = 8, 32                               # common.h: kStampWaves, kStampSlots
 stamps = torch.zeros(bs * nhk * 64 * NW * NS, dtype=torch.int64, device=dev)
 
 
 def run(l):
     kp, vp, ids = states[l % args.layers]
+    if args.append:
+        dlen.copy_(dlen0)      # every launch advances r on the device
     return ops.pq_decode_attn(q, kp, vp, kc, vc, kr, vr, args.r, M=M, C=C, n_tokens=T, k_page_ids=ids, v_page_ids=ids,
-                              page_size=ps, dev_lengths=dlen)
+                              page_size=ps, dev_lengths=dlen, **new_rows)
 
 
 for i in range(2 * args.layers):
@@ -124,5 +130,13 @@ if la.shape[0]:
             print("    %-24s (%3d): barrier -> flags seen %.2f | -> end %.2f us (min %.2f max %.2f)" % (
                 name, rows.shape[0], ((rows[:, 11] - rows[:, 10]) / 100.0).mean(), ((rows[:, 6] - rows[:, 11]) / 100.0).mean(),
                 ((rows[:, 6] - rows[:, 11]) / 100.0).min(), ((rows[:, 6] - rows[:, 11]) / 100.0).max()))
+if (s[:, 0, 13] != 0).any():      # the window-length advance, in the PRIMARIES only (arrival index ns - 1: they take the second-level ticket)
+    prim_wg = s[s[:, 0, 13] == s[:, 0, 13].max()]
+    adv = prim_wg.reshape(-1, NS)
+    adv = adv[(adv[:, 14] != 0) & (adv[:, 15] != 0)]
+    if adv.shape[0]:
+        t_end = s[:, :, 6].max()
+        print("  window-length advance (stamps 14 -> 15, the ticket waves of %d primaries): mean %.2f max %.2f us; the last stamp 15 lies %.2f us before the last end of the launch" % (
+            adv.shape[0], ((adv[:, 15] - adv[:, 14]) / 100.0).mean(), ((adv[:, 15] - adv[:, 14]) / 100.0).max(), (t_end - adv[:, 15].max()) / 100.0))
 e = (s[:, 0, 6] - t0) / 100.0
 print("  end relative to first start: mean %.2f max %.2f us" % (e.mean(), e.max()))
