@@ -291,6 +291,13 @@ def make_attn_desc(q, k_res, *, nh_k, M, C, n_tokens, r, resid_start=0, k_paged=
     return desc
 
 
+def decode_workspace_bytes(q, k_res, *, nh_k, M, C, n_tokens=0, k_codes=None, v_codes=None) -> int:
+    """million_attn_workspace_bytes of a decode call of this shape: what a cache allocates (zeroed) once and hands to every
+    pq_decode_attn(workspace=).  Row-major stores (k_codes / v_codes) add the transposed-V scratch of n_tokens tokens."""
+    desc = make_attn_desc(q, k_res, nh_k=nh_k, M=M, C=C, n_tokens=n_tokens, r=0, k_codes=k_codes, v_codes=v_codes)
+    return int(L.load().million_attn_workspace_bytes(ctypes.byref(desc)))
+
+
 def _check_rowmajor(name, codes, M, n_tokens):
     if codes.dim() != 4 or codes.shape[3] != M:
         raise RuntimeError(f"pq_decode_attn: {name} must be (bs, nh_k, T, M)")

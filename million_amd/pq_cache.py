@@ -24,6 +24,7 @@ from __future__ import annotations
 import heapq
 from typing import Dict, List, Optional, Set
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -292,10 +293,10 @@ class DynamicPQCache(_CacheBase):
                           self.key_cent, self.value_cent, self.key_residual_cache[layer_idx],
                           self.value_residual_cache[layer_idx], r + 1)
         if self._ws is None:      # sized once for max_tokens (partials + transposed-V scratch of the row-major path)
-            desc = ops.make_attn_desc(query_states, self.key_residual_cache[layer_idx], nh_k=self.num_key_value_heads,
-                                      M=self.M, C=self.C, n_tokens=self.max_tokens, r=0,
-                                      k_codes=self._k_store[layer_idx], v_codes=self._v_store[layer_idx])
-            self._ws = torch.zeros(L.load().million_attn_workspace_bytes(desc), dtype=torch.uint8, device=self.device)
+            need = ops.decode_workspace_bytes(query_states, self.key_residual_cache[layer_idx], nh_k=self.num_key_value_heads,
+                                              M=self.M, C=self.C, n_tokens=self.max_tokens,
+                                              k_codes=self._k_store[layer_idx], v_codes=self._v_store[layer_idx])
+            self._ws = torch.zeros(need, dtype=torch.uint8, device=self.device)
         # append (:304-312) + attention (:314-326) in ONE launch
         return ops.pq_decode_attn(query_states, self._k_store[layer_idx], self._v_store[layer_idx], self._kprep,
                                   self._vprep, self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx],
@@ -396,7 +397,6 @@ class PagedPQCache(_CacheBase):
         self.init_cache()
 
     def init_cache(self):
-        import numpy as np
         nk, cap = self.num_key_value_heads, self.extended_residual_size
         total = self.layer_num * self.bs * nk * self.n_pages_cap
         z = lambda *s, dt: torch.zeros(*s, dtype=dt, device=self.device)
@@ -421,6 +421,8 @@ class PagedPQCache(_CacheBase):
         self._host_pids = [[[[] for _ in range(nk)] for _ in range(self.bs)] for _ in range(self.layer_num)]
         self._ws = None
         self._side, self._flush_events, self._ahead = None, {}, None
+        # knobs of begin_step (None: the defaults of _ea_groups / begin_step): steps an encode-ahead is spread over, launches per step
+        self.encode_ahead_steps = self.encode_ahead_launches = None
         if self.preallocate:
             for l in range(self.layer_num):
                 for b in range(self.bs):
@@ -435,7 +437,6 @@ class PagedPQCache(_CacheBase):
 
     @staticmethod
     def _set_rows(arr, v):
-        import numpy as np
         v = np.asarray([list(x) if hasattr(x, "__len__") else x for x in v] if not isinstance(v, np.ndarray) else v)
         arr[...] = v if v.ndim == 2 else v[:, None]
 
@@ -460,24 +461,77 @@ class PagedPQCache(_CacheBase):
             self.page_ids[layer_idx][bb, :, have:upto_pages] = t.to(self.device)
             self._pages_a[layer_idx, bb] = upto_pages
 
-    def _sync_lengths(self, layer_idx):
-        import numpy as np
-        rows = np.stack([self._T_a[layer_idx], self._r_a[layer_idx], self._rs_a[layer_idx], np.zeros(self.bs, dtype=np.int64)], axis=1)
-        self.lengths[layer_idx].copy_(torch.from_numpy(rows.astype(np.int32)))
+    # ---- the mirror transitions: every rule that moves _T_a, _r_a, _rs_a, _seen_a, _pre_a (and the device rows) is written
+    # here, once.  `sel` / `b` index the (layers, requests) arrays: a layer, (layer, request mask), a mask of both, ...
+    def _note_flushed(self, sel):
+        """A flush moved the window of the entries `sel`: its oldest page_size rows are codes behind T now."""
+        ps = self.page_size
+        self._T_a[sel] += ps
+        self._r_a[sel] -= ps
+        self._rs_a[sel] = (self._rs_a[sel] + ps) % self.extended_residual_size
+        self._pre_a[sel] = 0      # (rows encoded ahead are in their pages: flushed in line they were encoded again, same codes)
+
+    def _note_appended(self, layer_idx=slice(None)):
+        """A decode step appended one row to the window of every request of a layer (of every layer)."""
+        self._r_a[layer_idx] += 1
+        self._seen_a[layer_idx] += 1
+
+    def _note_stored(self, layer_idx, n, b=slice(None)):
+        """n new rows of request b (every request) were encoded behind T."""
+        self._T_a[layer_idx, b] += n
+        self._seen_a[layer_idx, b] += n
+
+    def _note_window_emptied(self, layer_idx, b=slice(None)):
+        """The r window rows of request b (every request) were encoded behind T, in ring order: they are seen already."""
+        self._T_a[layer_idx, b] += self._r_a[layer_idx, b]
+        self._r_a[layer_idx, b] = 0
+        self._rs_a[layer_idx, b] = 0
+
+    def _sync_lengths(self, layer_idx, b=None):
+        """The device rows of a layer - of request b alone: the others' are not touched - written from the mirror."""
+        sel = slice(None) if b is None else slice(b, b + 1)
+        T = self._T_a[layer_idx, sel]
+        rows = np.stack([T, self._r_a[layer_idx, sel], self._rs_a[layer_idx, sel], np.zeros_like(T)], axis=1)
+        self.lengths[layer_idx][sel].copy_(torch.from_numpy(rows.astype(np.int32)))
+
+    def _reserve(self, layer_idx, n, b=None, ask=False) -> bool:
+        """Room for n more tokens behind T of request b (None: every request, in lockstep).  A preallocated table is checked
+        against max_tokens, an on-demand one gets its pages now (_assign_pages raises past the capacity).  ask=True only
+        answers whether a preallocated table has the room and assigns nothing: pages on demand are begin_step's to take."""
+        T = int(self._T_a[layer_idx, 0 if b is None else b])
+        if self.preallocate:
+            if T + n > self.max_tokens:
+                if ask:
+                    return False
+                raise RuntimeError(f"PagedPQCache: {T + n} tokens exceed max_tokens={self.max_tokens}")
+        elif not ask:
+            self._assign_pages(layer_idx, (T + n + self.page_size - 1) // self.page_size, b)
+        return True
 
     def _encode_to_pages(self, K, V, layer_idx, n, *, b=None, x_row_start=0, x_row_mod=0):
         """Encode n rows of K, V (bs or 1, nh_k, n, d) behind the T quantised tokens of every request (b = None: requests
         in lockstep) or of request b.  x_row_mod > 0: K, V are rings of x_row_mod rows read from x_row_start on."""
         sel = slice(None) if b is None else slice(b, b + 1)
         T = int(self._T_a[layer_idx, 0 if b is None else b])
-        if not self.preallocate:
-            self._assign_pages(layer_idx, (T + n + self.page_size - 1) // self.page_size, b)
-        elif T + n > self.max_tokens:
-            raise RuntimeError(f"PagedPQCache: {T + n} tokens exceed max_tokens={self.max_tokens}")
+        self._reserve(layer_idx, n, b)
         kw = dict(token_start=T, n=n, page_ids=self.page_ids[layer_idx][sel], page_size=self.page_size,
                   x_row_start=x_row_start, x_row_mod=x_row_mod)
         ops.pq_encode_into(K, self.key_cent, self.key_page_pool, layout=L.MILLION_CODES_KPAGES, prepared=self._kprep, **kw)
         ops.pq_encode_into(V, self.value_cent, self.value_page_pool, layout=L.MILLION_CODES_VPAGES, prepared=self._vprep, **kw)
+
+    def _store(self, K, V, layer_idx, n, b=None, all_rows=False):
+        """The store step under every prefill / extend form, for request b (None: every request, in lockstep): the window
+        into codes when it holds rows (ring order, behind T), the n new rows behind those, the mirror, the device row of
+        request b (all_rows, or b = None: every row of the layer).  Leaves what prefill of the whole sequence would."""
+        i, sel = (0, slice(None)) if b is None else (b, slice(b, b + 1))
+        r = int(self._r_a[layer_idx, i])
+        if r:
+            self._encode_to_pages(self.key_residual_cache[layer_idx][sel], self.value_residual_cache[layer_idx][sel], layer_idx, r,
+                                  b=b, x_row_start=int(self._rs_a[layer_idx, i]), x_row_mod=self.extended_residual_size)
+            self._note_window_emptied(layer_idx, sel)
+        self._encode_to_pages(K, V, layer_idx, n, b=b)
+        self._note_stored(layer_idx, n, sel)
+        self._sync_lengths(layer_idx, None if all_rows else b)
 
     def prefill(self, query_states, key_states, value_states, layer_idx, distort_recent=False):
         """Bulk encode of the prompt straight into pages (reference paged_pq_utils.py:216-320: encode,
@@ -485,11 +539,7 @@ class PagedPQCache(_CacheBase):
         prompt only: on a cache that already holds tokens use extend()."""
         if not self._lockstep(layer_idx):
             raise RuntimeError("PagedPQCache.prefill: requests are at different lengths; use prefill_request(b, ...)")
-        n = key_states.size(2)
-        self._encode_to_pages(key_states, value_states, layer_idx, n)
-        self._T_a[layer_idx] += n
-        self._seen_a[layer_idx] += n
-        self._sync_lengths(layer_idx)
+        self._store(key_states, value_states, layer_idx, key_states.size(2))
         return self._prefill_attention(query_states, key_states, value_states)
 
     def prefill_request(self, b, query_states, key_states, value_states, layer_idx):
@@ -497,11 +547,7 @@ class PagedPQCache(_CacheBase):
         (release) starts its next request while the rest of the batch keeps decoding."""
         if key_states.size(0) != 1 or self._T_a[layer_idx, b] or self._r_a[layer_idx, b]:
             raise RuntimeError("prefill_request: tensors of batch 1 into an empty slot (release it first)")
-        n = key_states.size(2)
-        self._encode_to_pages(key_states, value_states, layer_idx, n, b=b)
-        self._T_a[layer_idx, b] += n
-        self._seen_a[layer_idx, b] += n
-        self._sync_lengths(layer_idx)
+        self._store(key_states, value_states, layer_idx, key_states.size(2), b, all_rows=True)      # (every device row: as ever)
         return self._prefill_attention(query_states, key_states, value_states)
 
     def prefill_ragged(self, query_states, key_states, value_states, layer_idx, n_new):
@@ -528,52 +574,43 @@ class PagedPQCache(_CacheBase):
         spans = torch.tensor([[x, x, 0, 0] for x in n_new], dtype=torch.int32).to(self.device)
         out = self._prefill_attention(query_states, key_states, value_states, dev_spans=spans)
         for b in who:      # the encodes stay host-driven per slot, as prefill_request does them
-            sel, x = slice(b, b + 1), n_new[b]
-            self._encode_to_pages(key_states[sel, :, :x], value_states[sel, :, :x], layer_idx, x, b=b)
-            self._T_a[layer_idx, b] += x
-            self._seen_a[layer_idx, b] += x
-            self.lengths[layer_idx][b].copy_(torch.tensor([int(self._T_a[layer_idx, b]), 0, 0, 0], dtype=torch.int32))
+            self._store(key_states[b:b + 1, :, :n_new[b]], value_states[b:b + 1, :, :n_new[b]], layer_idx, n_new[b], b)
         return out
 
     # ---- extend: a block of new tokens behind the cached ones ------------------------------------------------------------
+    def _join_flush(self, layer_idx) -> bool:
+        """The side-stream flush of a layer (flush_ahead): what is pending is issued up to this layer (keeping the side stream
+        `depth` layers ahead), the layer's own flush event is waited for.  False: the layer has no flush on the side stream."""
+        if self._ahead is not None:
+            self._ahead_issue(upto_layer=layer_idx)
+        ev = self._flush_events.pop(layer_idx, None)
+        if ev is None:
+            return False
+        torch.cuda.current_stream().wait_event(ev)
+        return True
+
     def _join_side(self, layer_idx, b=None):
         """Before extend touches a layer: its pending side-stream flush (flush_ahead) is issued and waited for, and window rows
         encoded ahead (begin_step) are complete.  extend encodes every window row again - rows encoded ahead get the same codes
         in the same pages - so the encoded-ahead flag of the layer (of request b) is cleared."""
-        if getattr(self, "_ahead", None) is not None and layer_idx in self._ahead[0]:
-            self._ahead_issue(upto_layer=layer_idx)
-        ev = self._flush_events.pop(layer_idx, None) if self._side is not None else None
-        if ev is not None:
-            torch.cuda.current_stream().wait_event(ev)
-        if self._side is not None and self._pre_join:
+        self._join_flush(layer_idx)
+        if self._pre_join:
             torch.cuda.current_stream().wait_stream(self._side)
-        if b is None:
-            self._pre_a[layer_idx] = 0
-        else:
-            self._pre_a[layer_idx, b] = 0
+        self._pre_a[layer_idx, slice(None) if b is None else b] = 0
 
     def _extend_slot(self, query_states, key_states, value_states, layer_idx, b):
         """b = None: every request (lockstep); else request b with batch-1 tensors."""
-        i = 0 if b is None else b
-        sel = slice(None) if b is None else slice(b, b + 1)
+        i, sel = (0, slice(None)) if b is None else (b, slice(b, b + 1))
         T, r, rs = int(self._T_a[layer_idx, i]), int(self._r_a[layer_idx, i]), int(self._rs_a[layer_idx, i])
         n = key_states.size(2)
         if T + r + n > self.max_tokens:
             raise RuntimeError(f"PagedPQCache: {T + r + n} tokens exceed max_tokens={self.max_tokens}")
-        kres, vres = self.key_residual_cache[layer_idx][sel], self.value_residual_cache[layer_idx][sel]
         ids = self.page_ids[layer_idx][sel]
         out = ops.pq_chunk_attn(query_states, key_states, value_states, self.key_page_pool, self.value_page_pool, self._kprep,
-                                self._vprep, kres, vres, r, M=self.M, C=self.C, n_tokens=T, resid_start=rs, k_page_ids=ids,
-                                v_page_ids=ids, page_size=self.page_size)
-        cap = self.extended_residual_size
-        if r:      # the window in ring order, then the new rows: the codes prefill() of the whole sequence would have written
-            self._encode_to_pages(kres, vres, layer_idx, r, b=b, x_row_start=rs, x_row_mod=cap)
-            self._T_a[layer_idx, sel] += r
-        self._encode_to_pages(key_states, value_states, layer_idx, n, b=b)
-        self._T_a[layer_idx, sel] += n
-        self._r_a[layer_idx, sel] = 0
-        self._rs_a[layer_idx, sel] = 0
-        self._seen_a[layer_idx, sel] += n
+                                self._vprep, self.key_residual_cache[layer_idx][sel], self.value_residual_cache[layer_idx][sel], r,
+                                M=self.M, C=self.C, n_tokens=T, resid_start=rs, k_page_ids=ids, v_page_ids=ids,
+                                page_size=self.page_size)
+        self._store(key_states, value_states, layer_idx, n, b)      # the window in ring order, then the new rows
         return out
 
     def extend(self, query_states, key_states, value_states, layer_idx):
@@ -589,9 +626,7 @@ class PagedPQCache(_CacheBase):
         self._join_side(layer_idx)
         if self._T_a[layer_idx, 0] == 0 and self._r_a[layer_idx, 0] == 0:
             return self.prefill(query_states, key_states, value_states, layer_idx)
-        out = self._extend_slot(query_states, key_states, value_states, layer_idx, None)
-        self._sync_lengths(layer_idx)
-        return out
+        return self._extend_slot(query_states, key_states, value_states, layer_idx, None)
 
     def extend_request(self, b, query_states, key_states, value_states, layer_idx):
         """extend() for ONE request (tensors of batch 1) in slot b; the other slots, their host and device lengths, are not
@@ -601,10 +636,7 @@ class PagedPQCache(_CacheBase):
         self._join_side(layer_idx, b)
         if self._T_a[layer_idx, b] == 0 and self._r_a[layer_idx, b] == 0:
             return self.prefill_request(b, query_states, key_states, value_states, layer_idx)
-        out = self._extend_slot(query_states, key_states, value_states, layer_idx, b)
-        row = [int(self._T_a[layer_idx, b]), 0, 0, 0]
-        self.lengths[layer_idx][b].copy_(torch.tensor(row, dtype=torch.int32))
-        return out
+        return self._extend_slot(query_states, key_states, value_states, layer_idx, b)
 
     def extend_ragged(self, query_states, key_states, value_states, layer_idx, n_new):
         """extend_request() for every slot in ONE attention launch: tensors of batch bs padded to n_q = max(n_new) rows,
@@ -635,19 +667,8 @@ class PagedPQCache(_CacheBase):
         out = ops.pq_chunk_attn(query_states, key_states, value_states, self.key_page_pool, self.value_page_pool, self._kprep,
                                 self._vprep, kres, vres, 0, M=self.M, C=self.C, n_tokens=bound, k_page_ids=ids, v_page_ids=ids,
                                 page_size=self.page_size, dev_lengths=self.lengths[layer_idx], dev_n_q=dev_n)
-        cap = self.extended_residual_size
         for b in who:      # the encodes stay host-driven per slot, as extend_request does them
-            sel = slice(b, b + 1)
-            r, rs, n = int(self._r_a[layer_idx, b]), int(self._rs_a[layer_idx, b]), n_new[b]
-            if r:
-                self._encode_to_pages(kres[sel], vres[sel], layer_idx, r, b=b, x_row_start=rs, x_row_mod=cap)
-                self._T_a[layer_idx, b] += r
-            self._encode_to_pages(key_states[sel, :, :n], value_states[sel, :, :n], layer_idx, n, b=b)
-            self._T_a[layer_idx, b] += n
-            self._r_a[layer_idx, b] = 0
-            self._rs_a[layer_idx, b] = 0
-            self._seen_a[layer_idx, b] += n
-            self.lengths[layer_idx][b].copy_(torch.tensor([int(self._T_a[layer_idx, b]), 0, 0, 0], dtype=torch.int32))
+            self._store(key_states[b:b + 1, :, :n_new[b]], value_states[b:b + 1, :, :n_new[b]], layer_idx, n_new[b], b)
         return out
 
     def release(self, b):
@@ -692,10 +713,7 @@ class PagedPQCache(_CacheBase):
             raise RuntimeError("PagedPQCache.update: lockstep requests and an empty residual window expected")
         n = key_states.size(2)
         T0 = int(self._T_a[layer_idx, 0])
-        self._encode_to_pages(key_states, value_states, layer_idx, n)
-        self._T_a[layer_idx] += n
-        self._seen_a[layer_idx] += n
-        self._sync_lengths(layer_idx)
+        self._store(key_states, value_states, layer_idx, n)
         upto = T0 + n if distort_recent else T0
         if upto:
             kc, vc = self._codes_rowmajor(layer_idx, upto)
@@ -724,23 +742,14 @@ class PagedPQCache(_CacheBase):
             return
         if not lock and not use_dev_lengths:
             raise RuntimeError("PagedPQCache: requests at different lengths need use_dev_lengths=True")
-        who = range(self.bs) if lock else [b for b in range(self.bs) if full[b]]
-        for b in who:
-            T = int(self._T_a[layer_idx, b])
-            if not self.preallocate:
-                self._assign_pages(layer_idx, (T + ps + ps - 1) // ps, b)
-            elif T + ps > self.max_tokens:
-                raise RuntimeError(f"PagedPQCache: {T + ps} tokens exceed max_tokens={self.max_tokens}")
+        for b in (None,) if lock else np.flatnonzero(full):
+            self._reserve(layer_idx, ps, b)
         ops.pq_flush(self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx], self.key_cent,
                      self.value_cent, self.key_page_pool, self.value_page_pool, self.page_ids[layer_idx],
                      n=ps, page_size=ps, token_start=int(self._T_a[layer_idx, 0]), x_row_start=int(self._rs_a[layer_idx, 0]),
                      dev_lengths=self.lengths[layer_idx] if use_dev_lengths else None,
                      min_r=cap if use_dev_lengths else 0)      # device lengths: only full windows flush (a captured step serves ragged batches too)
-        for b in who:
-            self._T_a[layer_idx, b] += ps
-            self._r_a[layer_idx, b] -= ps
-            self._rs_a[layer_idx, b] = (self._rs_a[layer_idx, b] + ps) % cap
-            self._pre_a[layer_idx, b] = 0      # (rows encoded ahead were encoded again: same codes, same pages)
+        self._note_flushed(layer_idx if lock else (layer_idx, full))
 
     # ---- encode-ahead: the flush without a flush step ---------------------------------------------------------------
     # The reference flushes the oldest page_size window rows when the window is full (paged_pq_utils.py:359-361).  Those
@@ -770,7 +779,7 @@ class PagedPQCache(_CacheBase):
         """Layer ranges encoded ahead per step: all layers in one step up to 32 (layer, request) pairs, else spread over
         consecutive steps (at 8 requests the attention launches leave few idle issue slots: all layers in one step made
         that step 1.6 x a plain one; 4 layers per step over 8 steps: see DESIGN.md 4.4)."""
-        n = getattr(self, "encode_ahead_steps", None)
+        n = self.encode_ahead_steps
         if n is None:
             n = -(-self.bs * self.layer_num // 32)
         n = max(1, min(int(n), self.layer_num, max(1, self.page_size - 16)))
@@ -792,22 +801,16 @@ class PagedPQCache(_CacheBase):
         if kind == "commit":
             if use_dev_lengths:
                 ops.lengths_advance(self._lengths_all.view(-1, 4), ps, cap)      # every layer, every request: one launch
-            self._T_a += ps
-            self._r_a -= ps
-            self._rs_a[:] = (self._rs_a + ps) % cap
-            self._pre_a[:] = 0
+            self._note_flushed(...)
         elif kind == "flush":
             self.flush_ahead(use_dev_lengths=use_dev_lengths)
         elif kind.startswith("pre"):
             groups = self._ea_groups()
             G0, G1 = groups[int(kind[3:] or 0)]
-            T = int(self._T_a[0, 0])
-            if not self.preallocate:
-                for l in range(G0, G1):
-                    for b in range(self.bs):
-                        self._assign_pages(l, (T + ps + ps - 1) // ps, b)
-            elif T + ps > self.max_tokens:
+            if not self._reserve(0, ps, ask=True):
                 return "plain"      # the flush step will raise, as before
+            for l in range(G0, G1):      # (pages on demand)
+                self._reserve(l, ps)
             main = torch.cuda.current_stream()
             if self._side is None:
                 self._side = torch.cuda.Stream(device=self.device)
@@ -815,7 +818,7 @@ class PagedPQCache(_CacheBase):
             with torch.cuda.stream(self._side):
                 # a grid of ONE layer's size whose workgroups walk the layers (one flush workgroup per CU at a time: what fits
                 # beside an attention workgroup), in `encode_ahead_launches` launches
-                nl_ = getattr(self, "encode_ahead_launches", None)
+                nl_ = self.encode_ahead_launches
                 if nl_ is None:
                     # replayed from a hipGraph: one launch per layer (the work trickles through the whole step: measured
                     # 1.04 x a plain step against 1.09 x for one long launch); eager: one launch (the host pays per launch)
@@ -825,7 +828,7 @@ class PagedPQCache(_CacheBase):
                 for g0 in range(G0, G1, per):
                     g1 = min(g0 + per, G1)
                     ops.pq_flush(self._kres_all[g0:g1], self._vres_all[g0:g1], self.key_cent, self.value_cent, self.key_page_pool,
-                                 self.value_page_pool, self._page_ids_all[g0:g1], n=ps, page_size=ps, token_start=T,
+                                 self.value_page_pool, self._page_ids_all[g0:g1], n=ps, page_size=ps, token_start=int(self._T_a[0, 0]),
                                  x_row_start=int(self._rs_a[0, 0]),
                                  dev_lengths=self._lengths_all[g0:g1] if use_dev_lengths else None,
                                  min_r=ps if use_dev_lengths else 0, advance=False)
@@ -849,9 +852,8 @@ class PagedPQCache(_CacheBase):
         if not todo:
             return
         main = torch.cuda.current_stream()
-        if getattr(self, "_side", None) is None:
+        if self._side is None:
             self._side = torch.cuda.Stream(device=self.device)      # (a high-priority side stream changes nothing: measured)
-            self._flush_events = {}
         self._side.wait_stream(main)      # fork: behind everything this stream has queued (the previous step's appends)
         self._ahead = (todo, use_dev_lengths, max(1, int(depth)))
         self._ahead_issue(upto_layer=-1)
@@ -887,12 +889,7 @@ class PagedPQCache(_CacheBase):
         is read on the device (the host mirror is still advanced), which makes the call graph-capturable and lets
         requests of different lengths share the launch."""
         cap = self.extended_residual_size
-        if getattr(self, "_ahead", None) is not None:
-            self._ahead_issue(upto_layer=layer_idx)                                      # keep the side stream `depth` layers ahead
-        ev = self._flush_events.pop(layer_idx, None) if getattr(self, "_side", None) is not None else None
-        if ev is not None:
-            torch.cuda.current_stream().wait_event(ev)                                   # flushed ahead on the side stream
-        elif (self._r_a[layer_idx] >= cap).any():                                        # :359-361
+        if not self._join_flush(layer_idx) and (self._r_a[layer_idx] >= cap).any():      # not flushed ahead on the side stream: :359-361
             self.flush_to_pages(layer_idx, use_dev_lengths=use_dev_lengths)
         lock = self._lockstep(layer_idx)
         if not lock and not use_dev_lengths:
@@ -900,11 +897,10 @@ class PagedPQCache(_CacheBase):
         r, rs = int(self._r_a[layer_idx, 0]), int(self._rs_a[layer_idx, 0])
         dl = self.lengths[layer_idx] if use_dev_lengths else None
         if self._ws is None:      # one workspace per cache (calls of one cache are stream-ordered)
-            desc = ops.make_attn_desc(query_states, self.key_residual_cache[layer_idx], nh_k=self.num_key_value_heads,
-                                      M=self.M, C=self.C, n_tokens=0, r=0)
-            self._ws = torch.zeros(L.load().million_attn_workspace_bytes(desc), dtype=torch.uint8, device=self.device)
-        self._r_a[layer_idx] += 1
-        self._seen_a[layer_idx] += 1
+            need = ops.decode_workspace_bytes(query_states, self.key_residual_cache[layer_idx], nh_k=self.num_key_value_heads,
+                                              M=self.M, C=self.C)
+            self._ws = torch.zeros(need, dtype=torch.uint8, device=self.device)
+        self._note_appended(layer_idx)
         # append (:377-380) + attention (:386) in ONE launch: the new row is attended to and parked in the window
         res = ops.pq_decode_attn(query_states, self.key_page_pool, self.value_page_pool, self._kprep, self._vprep,
                                  self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx], r,
@@ -961,17 +957,12 @@ class PagedPQCache(_CacheBase):
         kind = self.next_step_kind() if kind is None else kind
         cap, ps = self.extended_residual_size, self.page_size
         if kind in ("commit", "flush"):
-            full = self._r_a >= cap
-            self._T_a[full] += ps
-            self._r_a[full] -= ps
-            self._rs_a[full] = (self._rs_a[full] + ps) % cap
-            self._pre_a[full] = 0
+            self._note_flushed(self._r_a >= cap)
         elif kind.startswith("pre"):
             g0, g1 = self._ea_groups()[int(kind[3:] or 0)]
-            if not (self.preallocate and int(self._T_a[0, 0]) + ps > self.max_tokens):      # begin_step encoded nothing then
+            if self._reserve(0, ps, ask=True):      # (else begin_step encoded nothing)
                 self._pre_a[g0:g1] = 1
-        self._r_a += 1
-        self._seen_a += 1
+        self._note_appended()
 
     def get_cache_stats(self) -> Dict:
         """paged_pq_utils.py:898-939 (same keys) + the page-manager counters."""
