@@ -129,6 +129,49 @@ int million_pq_flush_layers(const million_encode_desc *desc, const void *k_rows,
                             int n_layers, int64_t rows_layer_stride, int64_t ids_layer_stride, int64_t lengths_layer_stride,
                             int advance, million_stream_t stream);
 
+/* The store step of a ragged batch: ONE call for every request, every per-request value read on the device.
+ * Replaces, behind a ragged attention launch (million_pq_chunk_attn with dev_lengths / dev_n_q, million_prefill_attn with
+ * dev_spans), the host loop of up to four million_pq_encode calls and one lengths copy per request.
+ * Request b has the row {T, r, start, word 3} in dev_lengths (bs, 4) and n_b = dev_n[b] new rows.  n_b = 0: the request takes no
+ * part - nothing of it is read beyond those words and nothing is written.  Otherwise it has r + n_b source rows: source row
+ * j < r is row (start + j) % resid_cap of its window (k_resid / v_resid (bs, nh_k, resid_cap, d), row stride d), source row
+ * j >= r is row j - r of k_new / v_new (bs, nh_k, n_bound, d); source row j becomes token T + j: its K codes go to k_pool in the
+ * MILLION_CODES_KPAGES layout, its V codes to v_pool in the MILLION_CODES_VPAGES layout, through the same page_ids
+ * (bs, nh_k, n_pages_cap) int32.  Codes are those of million_pq_encode, bit for bit (same arithmetic contract).  Then the row is
+ * advanced: T <- min(T + r + n_b, n_pages_cap * page_size), r <- 0, start <- 0; word 3 is neither read nor written.
+ * The values are not trusted: T is clamped into [0, n_pages_cap * page_size], r into [0, resid_cap], a start outside
+ * [0, resid_cap) reads as 0, n_b is clamped into [0, n_bound]; everything above, the advance included, uses the clamped values.
+ * A destination token whose page index is >= n_pages_cap drops its store.  Page ids are read only for pages that receive a token.
+ * What may hold anything (NaN, garbage, stale ids) and is never read, and what is never written: new rows at or past n_b, window
+ * rows outside each request's ring span, every row of a request with n_b = 0 (its lengths row and pages included), page-table
+ * entries past the pages written, pool bytes outside the destination tokens.
+ * Shapes: d = 128 or 64 with M in {64, 32, 16}, uint8 codes (C <= 256), page_size 32 / 64 / 128, bs * nh_k <= 32767; anything
+ * else: MILLION_ERR_SHAPE.  Both codebooks as million_prepare_cents wrote them (required: MILLION_ERR_ARG when null, like null
+ * dev_n / dev_lengths / rows / pools / page ids, and null windows with resid_cap > 0).  Rows, windows, codebooks and pools 16-byte
+ * aligned, strides multiples of 8 elements: MILLION_ERR_ALIGN otherwise.  n_bound = 0 returns MILLION_OK whatever the pointers.
+ * Capture: two launches on `stream` - the encode grid, sized by the bounds alone (ceil((resid_cap + n_bound) / 64) token blocks x
+ * subspace groups x bs * nh_k x 2 sides), then one thread per request for the advance; stream order is the only ordering.  The
+ * call allocates nothing, synchronises nothing and is a pure function of the descriptor: a captured call follows dev_lengths,
+ * dev_n, the rows and the page table as they are when it is replayed. */
+typedef struct {
+    uint32_t struct_size;         /* = sizeof(million_store_ragged_desc) */
+    int32_t bs, nh_k, d, M, C;
+    int32_t n_bound;              /* rows of k_new / v_new per (b, hk): the bound of dev_n */
+    int64_t kn_stride_b, kn_stride_h, kn_stride_n;   /* k_new, fp16 elements; the d elements of a row are contiguous */
+    int64_t vn_stride_b, vn_stride_h, vn_stride_n;   /* v_new */
+    int32_t resid_cap;            /* rows of the window buffers; 0: no window (k_resid / v_resid may be NULL) */
+    int32_t page_size;            /* 32, 64 or 128 */
+    int64_t resid_stride_b, resid_stride_h;          /* both windows, fp16 elements; row stride is d */
+    int32_t n_pages_cap;          /* row length of page_ids */
+} million_store_ragged_desc;
+
+int million_pq_store_ragged(const million_store_ragged_desc *desc, const void *k_new, const void *v_new,
+                            const void *k_resid, const void *v_resid,
+                            const void *k_cents_prepared, const void *v_cents_prepared,   /* million_prepare_cents */
+                            void *k_pool, void *v_pool, const int32_t *page_ids,
+                            int32_t *dev_lengths /* (bs, 4), advanced */, const int32_t *dev_n /* (bs,) */,
+                            million_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * PQ codebook training.
  * Replaces: train_pq (scripts/utils/pq_utils.py:586-609), which wraps faiss-cpu's IndexPQ.train: ProductQuantizer's default

@@ -61,6 +61,16 @@ class ChunkAttnDesc(ctypes.Structure):
                 ("dev_lengths", c_vp), ("dev_n_q", c_vp)]
 
 
+class StoreRaggedDesc(ctypes.Structure):
+    _fields_ = [("struct_size", c_u32), ("bs", c_i32), ("nh_k", c_i32), ("d", c_i32), ("M", c_i32), ("C", c_i32),
+                ("n_bound", c_i32),
+                ("kn_stride_b", c_i64), ("kn_stride_h", c_i64), ("kn_stride_n", c_i64),
+                ("vn_stride_b", c_i64), ("vn_stride_h", c_i64), ("vn_stride_n", c_i64),
+                ("resid_cap", c_i32), ("page_size", c_i32),
+                ("resid_stride_b", c_i64), ("resid_stride_h", c_i64),
+                ("n_pages_cap", c_i32)]
+
+
 class TrainDesc(ctypes.Structure):
     _fields_ = [("struct_size", c_u32), ("n", c_i32), ("d", c_i32), ("M", c_i32), ("C", c_i32), ("niter", c_i32),
                 ("x_is_f32", c_i32), ("x_stride_n", c_i64), ("eps", ctypes.c_float)]
@@ -90,6 +100,7 @@ SYMBOLS = {
     "million_prefill_attn": (c_i32, [ctypes.POINTER(PrefillDesc), c_vp, c_vp, c_vp, c_vp, c_vp]),
     "million_chunk_attn_workspace_bytes": (c_sz, [ctypes.POINTER(ChunkAttnDesc)]),
     "million_pq_chunk_attn": (c_i32, [ctypes.POINTER(ChunkAttnDesc)] + [c_vp] * 13 + [c_sz, c_vp]),
+    "million_pq_store_ragged": (c_i32, [ctypes.POINTER(StoreRaggedDesc)] + [c_vp] * 12),
     "million_set_force_generic": (None, [c_i32]),
     "million_debug_set_stamp_buffer": (None, [c_vp]),
     "million_debug_bad_page_ids": (c_i32, []),

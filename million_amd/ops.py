@@ -194,6 +194,61 @@ def pq_flush(k_rows: torch.Tensor, v_rows: torch.Tensor, k_cents: torch.Tensor, 
                                              n_layers, x_ls, ids_ls, len_ls, int(bool(advance)), _stream()), "million_pq_flush_layers")
 
 
+def pq_store_ragged(k_new: torch.Tensor, v_new: torch.Tensor, k_res: Optional[torch.Tensor], v_res: Optional[torch.Tensor],
+                    k_prep: torch.Tensor, v_prep: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
+                    page_ids: torch.Tensor, dev_lengths: torch.Tensor, dev_n: torch.Tensor, *, M: int, C: int, page_size: int,
+                    n_bound: Optional[int] = None) -> None:
+    """The store step of a ragged batch in one call (million_pq_store_ragged): for every request b with dev_n[b] > 0 the
+    r_b window rows of k_res / v_res (bs, nh_k, cap, d) in ring order and then the first dev_n[b] rows of k_new / v_new
+    (bs, nh_k, n, d) are encoded behind the request's T_b tokens - K pages in k_pool, transposed V pages in v_pool, through
+    page_ids (bs, nh_k, n_pages_cap) int32 - and the request's row of dev_lengths (bs, 4) int32 is advanced on the device
+    (T += r + n, r = start = 0).  Every per-request value is read on the device, so the call can be captured and replayed
+    while dev_lengths, dev_n and the rows change.  k_prep / v_prep: the prepared codebooks (prepare_cents).  n_bound: the rows of
+    k_new / v_new the grid is sized for (default: all of them); dev_n is clamped into [0, n_bound].  k_res = v_res = None: no
+    window (every r reads as 0)."""
+    _need_cuda(k_new, v_new, k_res, v_res, k_prep, v_prep, k_pool, v_pool, page_ids, dev_lengths, dev_n)
+    if k_new.dtype != torch.float16 or v_new.dtype != torch.float16 or k_pool.dtype != torch.uint8 or v_pool.dtype != torch.uint8:
+        raise RuntimeError("pq_store_ragged: new rows must be fp16, pools uint8")
+    if k_new.dim() != 4 or k_new.stride(3) != 1 or v_new.shape != k_new.shape or v_new.stride(3) != 1:
+        raise RuntimeError("pq_store_ragged: k_new / v_new must be (bs, nh_k, n, d) of one shape with a contiguous last dim")
+    bs, nhk, n_rows, d = k_new.shape
+    n_bound = n_rows if n_bound is None else int(n_bound)
+    if n_bound < 0 or n_bound > n_rows:
+        raise RuntimeError(f"pq_store_ragged: n_bound={n_bound} outside [0, {n_rows}]")
+    if (k_res is None) != (v_res is None):
+        raise RuntimeError("pq_store_ragged: K and V windows go together")
+    cap = 0
+    if k_res is not None:
+        if (k_res.dtype != torch.float16 or v_res.dtype != torch.float16 or k_res.dim() != 4 or k_res.shape != v_res.shape
+                or k_res.stride() != v_res.stride() or k_res.shape[:2] != (bs, nhk) or k_res.shape[3] != d
+                or k_res.stride(3) != 1 or k_res.stride(2) != d):
+            raise RuntimeError("pq_store_ragged: windows must be fp16 (bs, nh_k, cap, d) with dense rows, K and V alike")
+        cap = k_res.shape[2]
+    if k_prep.dtype != torch.float16 or v_prep.dtype != torch.float16 or k_prep.numel() != v_prep.numel() or k_prep.numel() != 4 * M * C * (d // M):
+        raise RuntimeError("pq_store_ragged: k_prep / v_prep must be the prepared codebooks of (M, C, d / M) (prepare_cents)")
+    if page_ids.dtype != torch.int32 or not page_ids.is_contiguous() or page_ids.dim() != 3 or page_ids.shape[:2] != (bs, nhk):
+        raise RuntimeError("pq_store_ragged: contiguous int32 page_ids (bs, nh_k, n_pages_cap) expected")
+    if not k_pool.is_contiguous() or not v_pool.is_contiguous():
+        raise RuntimeError("pq_store_ragged: page pools must be contiguous")
+    if dev_lengths.dtype != torch.int32 or dev_lengths.shape != (bs, 4) or not dev_lengths.is_contiguous():
+        raise RuntimeError("pq_store_ragged: dev_lengths must be contiguous int32 (bs, 4)")
+    if dev_n.dtype != torch.int32 or dev_n.shape != (bs,) or not dev_n.is_contiguous():
+        raise RuntimeError("pq_store_ragged: dev_n must be contiguous int32 (bs,)")
+    desc = L.StoreRaggedDesc()
+    desc.struct_size = ctypes.sizeof(L.StoreRaggedDesc)
+    desc.bs, desc.nh_k, desc.d, desc.M, desc.C, desc.n_bound = bs, nhk, d, M, C, n_bound
+    desc.kn_stride_b, desc.kn_stride_h, desc.kn_stride_n = k_new.stride(0), k_new.stride(1), k_new.stride(2)
+    desc.vn_stride_b, desc.vn_stride_h, desc.vn_stride_n = v_new.stride(0), v_new.stride(1), v_new.stride(2)
+    desc.resid_cap, desc.page_size, desc.n_pages_cap = cap, page_size, page_ids.shape[2]
+    if k_res is not None:
+        desc.resid_stride_b, desc.resid_stride_h = k_res.stride(0), k_res.stride(1)
+    L.check(L.load().million_pq_store_ragged(ctypes.byref(desc), k_new.data_ptr(), v_new.data_ptr(), _ptr(k_res), _ptr(v_res),
+                                             k_prep.data_ptr(), v_prep.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(),
+                                             page_ids.data_ptr(), dev_lengths.data_ptr(), dev_n.data_ptr(), _stream()),
+            "million_pq_store_ragged")
+    _vshadow_drop(v_pool)
+
+
 def transpose_v_codes(v_codes: torch.Tensor, n_tokens: Optional[int] = None) -> torch.Tensor:
     """Row-major V codes (bs, nh_k, T, M) u8 -> dense transposed 64-token pages ((bs*nh_k)*ceil(T/64), M, 64)."""
     _need_cuda(v_codes)

@@ -533,6 +533,27 @@ class PagedPQCache(_CacheBase):
         self._note_stored(layer_idx, n, sel)
         self._sync_lengths(layer_idx, None if all_rows else b)
 
+    def _reserve_ragged(self, layer_idx, n_new):
+        """Room for the window rows and the n_new[b] new rows of every slot that takes part, before anything is launched
+        (paging on demand: the page table is complete when the one store call reads it)."""
+        for b in range(self.bs):
+            if n_new[b] > 0:
+                self._reserve(layer_idx, int(self._r_a[layer_idx, b]) + n_new[b], b)
+
+    def _store_ragged(self, K, V, layer_idx, n_new, dev_n):
+        """_store() for every slot with n_new[b] > 0 in ONE call (ops.pq_store_ragged): the windows in ring order and the
+        first n_new[b] rows of K, V (bs, nh_k, n, d) behind each T_b, every per-slot value read from `lengths[layer_idx]` and
+        dev_n on the device, the device rows advanced there - no _sync_lengths.  The slots' pages were reserved before the
+        attention launch (_reserve_ragged); the mirror moves through the same owners as _store."""
+        who = [b for b in range(self.bs) if n_new[b] > 0]
+        ops.pq_store_ragged(K, V, self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx], self._kprep, self._vprep,
+                            self.key_page_pool, self.value_page_pool, self.page_ids[layer_idx], self.lengths[layer_idx], dev_n,
+                            M=self.M, C=self.C, page_size=self.page_size)
+        for b in who:
+            sel = slice(b, b + 1)
+            self._note_window_emptied(layer_idx, sel)
+            self._note_stored(layer_idx, n_new[b], sel)
+
     def prefill(self, query_states, key_states, value_states, layer_idx, distort_recent=False):
         """Bulk encode of the prompt straight into pages (reference paged_pq_utils.py:216-320: encode,
         torch.cat, per-page permute+contiguous); the residual window stays empty.  The attention sees the
@@ -550,14 +571,16 @@ class PagedPQCache(_CacheBase):
         self._store(key_states, value_states, layer_idx, key_states.size(2), b, all_rows=True)      # (every device row: as ever)
         return self._prefill_attention(query_states, key_states, value_states)
 
-    def prefill_ragged(self, query_states, key_states, value_states, layer_idx, n_new):
+    def prefill_ragged(self, query_states, key_states, value_states, layer_idx, n_new, device_store=False):
         """prefill_request() for every slot in ONE attention launch - the counterpart of extend_ragged for empty slots, at
         the prompt kernel's rate: tensors of batch bs padded to n = max(n_new) rows, slot b owns the first n_new[b] of them
         (n_new: bs host ints in [0, n]).  A slot with n_new[b] > 0 must be empty (T = r = 0; a slot that holds tokens takes
         extend_ragged).  The launch reads the rows {n_b, n_b, 0, 0} from a small device tensor; the rows past n_new[b] - q, K
         and V - may hold anything and their output rows are zeros.  The encodes stay host-driven per slot; slot b is then left
         exactly as prefill_request(b, ...) with its own rows leaves it (pages, host lengths, its device row).  A slot with
-        n_new[b] = 0 takes no part: host and device lengths, pages and window stay as they are (it may be mid-decode)."""
+        n_new[b] = 0 takes no part: host and device lengths, pages and window stay as they are (it may be mid-decode).
+        device_store=True: the per-slot encodes and length copies are ONE ops.pq_store_ragged call behind the attention launch
+        (an int32 device copy of n_new beside `lengths[layer_idx]`): same pages, same codes, same host and device lengths."""
         n_new = [int(x) for x in n_new]
         n = query_states.size(2)
         if (len(n_new) != self.bs or query_states.size(0) != self.bs or key_states.size(0) != self.bs or key_states.size(2) != n
@@ -571,8 +594,13 @@ class PagedPQCache(_CacheBase):
                 raise RuntimeError(f"prefill_ragged: slot {b} holds tokens (release it first, or use extend_ragged)")
             if n_new[b] > self.max_tokens:
                 raise RuntimeError(f"PagedPQCache: {n_new[b]} tokens exceed max_tokens={self.max_tokens}")
+        if device_store:
+            self._reserve_ragged(layer_idx, n_new)
         spans = torch.tensor([[x, x, 0, 0] for x in n_new], dtype=torch.int32).to(self.device)
         out = self._prefill_attention(query_states, key_states, value_states, dev_spans=spans)
+        if device_store:
+            self._store_ragged(key_states, value_states, layer_idx, n_new, torch.tensor(n_new, dtype=torch.int32).to(self.device))
+            return out
         for b in who:      # the encodes stay host-driven per slot, as prefill_request does them
             self._store(key_states[b:b + 1, :, :n_new[b]], value_states[b:b + 1, :, :n_new[b]], layer_idx, n_new[b], b)
         return out
@@ -638,7 +666,7 @@ class PagedPQCache(_CacheBase):
             return self.prefill_request(b, query_states, key_states, value_states, layer_idx)
         return self._extend_slot(query_states, key_states, value_states, layer_idx, b)
 
-    def extend_ragged(self, query_states, key_states, value_states, layer_idx, n_new):
+    def extend_ragged(self, query_states, key_states, value_states, layer_idx, n_new, device_store=False):
         """extend_request() for every slot in ONE attention launch: tensors of batch bs padded to n_q = max(n_new) rows,
         slot b owns the first n_new[b] of them (n_new: bs host ints in [0, n_q]).  The launch reads each slot's lengths from
         `lengths[layer_idx]` on the device and n_new from a small device copy; the rows past n_new[b] - q, K and V - may
@@ -646,7 +674,9 @@ class PagedPQCache(_CacheBase):
         extend_request(b, ...) with its own rows leaves it (pending encode-ahead joined, window rows encoded in ring order
         behind T_b, the chunk rows behind those, T_b += r_b + n_b, r_b = resid_start_b = 0, its device row rewritten); an
         empty slot is served by the same launch (the chunk only).  A slot with n_new[b] = 0 takes no part: host and device
-        lengths, pages and window stay as they are."""
+        lengths, pages and window stay as they are.  device_store=True: the per-slot encodes and length copies are ONE
+        ops.pq_store_ragged call behind the attention launch, on the same `lengths[layer_idx]` and device copy of n_new - same
+        pages, same codes, same host and device lengths; the device rows are advanced by the call, not written from the host."""
         n_new = [int(x) for x in n_new]
         n_q = query_states.size(2)
         if len(n_new) != self.bs or query_states.size(0) != self.bs or key_states.size(0) != self.bs or key_states.size(2) != n_q:
@@ -660,6 +690,8 @@ class PagedPQCache(_CacheBase):
                 raise RuntimeError(f"PagedPQCache: {tot} tokens exceed max_tokens={self.max_tokens}")
         for b in who:
             self._join_side(layer_idx, b)
+        if device_store:
+            self._reserve_ragged(layer_idx, n_new)
         ids = self.page_ids[layer_idx]
         kres, vres = self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx]
         dev_n = torch.tensor(n_new, dtype=torch.int32).to(self.device)
@@ -667,6 +699,9 @@ class PagedPQCache(_CacheBase):
         out = ops.pq_chunk_attn(query_states, key_states, value_states, self.key_page_pool, self.value_page_pool, self._kprep,
                                 self._vprep, kres, vres, 0, M=self.M, C=self.C, n_tokens=bound, k_page_ids=ids, v_page_ids=ids,
                                 page_size=self.page_size, dev_lengths=self.lengths[layer_idx], dev_n_q=dev_n)
+        if device_store:
+            self._store_ragged(key_states, value_states, layer_idx, n_new, dev_n)
+            return out
         for b in who:      # the encodes stay host-driven per slot, as extend_request does them
             self._store(key_states[b:b + 1, :, :n_new[b]], value_states[b:b + 1, :, :n_new[b]], layer_idx, n_new[b], b)
         return out
