@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/million_hip.h"
 
 namespace million {
@@ -431,6 +433,27 @@ struct EncParams {
     int page_size, n_pages_cap;
     const int *dev_lengths;
 };
+// tok0 (the destination token of row 0) and the ring start of request b: the host's, or words 0 and 2 of the request's device
+// length row.  Device-resident values are not trusted: a ring start outside [0, xrow_mod) becomes 0; the caller drops the
+// store of a destination token that is negative or outside the page table.
+__device__ __forceinline__ void enc_load_row(const EncParams &p, int b, int &tok0, int &xrow_start) {
+    tok0 = p.tok0; xrow_start = p.xrow_start;
+    if (p.dev_lengths) { tok0 = p.dev_lengths[b * 4 + 0]; xrow_start = p.dev_lengths[b * 4 + 2]; }
+    if (p.xrow_mod > 0 && (unsigned)xrow_start >= (unsigned)p.xrow_mod) xrow_start = 0;
+}
+
+// Host: the kernels are instantiated for the sub-vector widths d/M = 1, 2, 4, 8.  Calls f(std::integral_constant<int, d/M>)
+// and returns true; any other width: false, f is not called (the error text and code are the caller's).
+template <class F>
+inline bool dispatch_dm(int dm, F &&f) {
+    switch (dm) {
+        case 1: f(std::integral_constant<int, 1>()); return true;
+        case 2: f(std::integral_constant<int, 2>()); return true;
+        case 4: f(std::integral_constant<int, 4>()); return true;
+        case 8: f(std::integral_constant<int, 8>()); return true;
+        default: return false;
+    }
+}
 
 // One decode-attention launch for one query-head group, as a planner fills it in; million_api.hip launches it (attn_impl)
 // or reports its kind (million_attn_kernel_kind).

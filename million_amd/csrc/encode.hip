@@ -5,9 +5,8 @@
 // paged_pq_utils.py:162,173-175): codes are written straight into their final place — row-major K
 // store, K page pool, or transposed V page pool.
 //
-// Arithmetic contract (bit-exact with oracle/pq_oracle.c:pq_encode_direct): e = x - c, sq = e * e,
-// acc = sq_0 + sq_1 + ... sequentially, every operation one IEEE fp32 round-to-nearest, no FMA
-// contraction; strict '<' scan over increasing c, so the lowest index wins exact ties.
+// Arithmetic contract and the centroid scan of every kernel here: pq_scan.h (bit-exact with
+// oracle/pq_oracle.c:pq_encode_direct; the lowest index wins exact ties).
 //
 // Mapping: a wave owns 4 consecutive subspaces of 64 tokens (lane = token): the lane's 4*d_m input halfs are
 // one vector load, the 4 code bytes of a token leave as one 32-bit store (row-major / K pages) or as four
@@ -21,6 +20,7 @@
 // side; at 6 instructions per test and one 64-lane instruction per 4 cycles per SIMD (1024 SIMDs, ~2.4 GHz:
 // 39e12 lane-instructions/s) the floor is ~0.66 ms; HBM traffic (67 MB in, 17 MB out) is two orders below that.
 #include "common.h"
+#include "pq_scan.h"
 
 #pragma clang fp contract(off)
 
@@ -28,8 +28,6 @@ namespace million {
 
 constexpr int kEncBlock = 256;
 constexpr int kEncSub = 4;      // subspaces per wave
-
-typedef float v2f __attribute__((ext_vector_type(2)));
 
 // CodeT = uint8_t (C <= 256) or uint16_t (nbits 9..16: reference nbits2dtype, pq_utils.py:542-552).
 template <int DM, bool F32TAB, typename CodeT>
@@ -44,11 +42,8 @@ __global__ __launch_bounds__(kEncBlock) void pq_encode_kernel(EncParams p) {
     if (m0 >= p.M) return;
     const bool valid = t < p.n;
     const int tc = valid ? t : p.n - 1;
-    int tok0 = p.tok0, xrow_start = p.xrow_start;
-    if (p.dev_lengths) { tok0 = p.dev_lengths[b * 4 + 0]; xrow_start = p.dev_lengths[b * 4 + 2]; }
-    // device-resident values are not trusted: a ring start outside [0, xrow_mod) becomes 0, a destination token outside
-    // the page table (or negative) drops the store (below)
-    if (p.xrow_mod > 0 && (unsigned)xrow_start >= (unsigned)p.xrow_mod) xrow_start = 0;
+    int tok0, xrow_start;
+    enc_load_row(p, b, tok0, xrow_start);      // a destination token outside the page table drops the store (below)
     const int xrow = p.xrow_mod > 0 ? (xrow_start + tc) % p.xrow_mod : tc;
     const f16 *xp = p.x + b * p.xsb + hk * p.xsh + (long long)xrow * p.xsn + m0 * DM;
     const int nsub = p.M - m0 < kEncSub ? p.M - m0 : kEncSub;      // wave-uniform
@@ -63,39 +58,11 @@ __global__ __launch_bounds__(kEncBlock) void pq_encode_kernel(EncParams p) {
     for (int j = 0; j < kEncSub; ++j) {
         if (j >= nsub) break;
         const int m = m0 + j;
-        const float *__restrict__ c32 = p.cents32 + (long long)m * p.C * DM;   // wave-uniform rows
-        const f16 *__restrict__ c16 = p.cents + (long long)m * p.C * DM;
         float best = INFINITY;
         int best_c = 0;
-#pragma unroll 16
-        for (int c = 0; c < p.C; ++c) {
-            float cv[DM];
-#pragma unroll
-            for (int k = 0; k < DM; ++k) cv[k] = F32TAB ? c32[c * DM + k] : (float)c16[c * DM + k];
-            float acc = 0.f;
-            if (DM % 2 == 0) {
-                // pairs of dims as packed fp32: every lane-half is one IEEE round-to-nearest operation
-#pragma unroll
-                for (int k = 0; k < DM; k += 2) {
-                    const v2f xv = {x[j][k], x[j][k + 1]}, cc = {cv[k], cv[k + 1]};
-                    const v2f e = xv - cc;
-                    const v2f sq = e * e;
-                    acc = (k == 0) ? sq[0] : acc + sq[0];
-                    acc = acc + sq[1];
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < DM; ++k) {
-                    const float e = x[j][k] - cv[k];
-                    const float sq = e * e;
-                    acc = (k == 0) ? sq : acc + sq;
-                }
-            }
-            // strict '<', increasing c: the lowest index wins exact ties.  Written as "keep unless smaller" so that the
-            // select is (condition ? register : constant): v_cndmask takes the constant c as a literal, no v_mov
-            best_c = !(acc < best) ? best_c : c;
-            best = fminf(best, acc);
-        }
+        // wave-uniform rows
+        if constexpr (F32TAB) pq_scan_sgpr<DM>(x[j], p.cents32 + (long long)m * p.C * DM, p.C, best, best_c);
+        else pq_scan_sgpr<DM>(x[j], p.cents + (long long)m * p.C * DM, p.C, best, best_c);
         codes |= (unsigned long long)(unsigned)best_c << (kCB * j);
     }
     if (!valid) return;
@@ -149,9 +116,8 @@ __device__ __forceinline__ void encode_small_body(const EncParams &p, int m, int
     for (int e = c0 * DM + lane; e < c1 * DM; e += 64) rows[e] = (float)cm[e];      // own quarter, own wave: LDS order suffices
     const bool valid = t < p.n;
     const int tc = valid ? t : p.n - 1;
-    int tok0 = p.tok0, xrow_start = p.xrow_start;
-    if (p.dev_lengths) { tok0 = p.dev_lengths[b * 4 + 0]; xrow_start = p.dev_lengths[b * 4 + 2]; }
-    if (p.xrow_mod > 0 && (unsigned)xrow_start >= (unsigned)p.xrow_mod) xrow_start = 0;      // not trusted (see pq_encode_kernel)
+    int tok0, xrow_start;
+    enc_load_row(p, b, tok0, xrow_start);
     const int xrow = p.xrow_mod > 0 ? (xrow_start + tc) % p.xrow_mod : tc;
     const f16 *xp = p.x + b * p.xsb + hk * p.xsh + (long long)xrow * p.xsn + m * DM;
     float x[DM];
@@ -159,18 +125,7 @@ __device__ __forceinline__ void encode_small_body(const EncParams &p, int m, int
     for (int k = 0; k < DM; ++k) x[k] = (float)xp[k];
     float best = INFINITY;
     int best_c = c0;
-#pragma unroll 8
-    for (int c = c0; c < c1; ++c) {
-        float acc = 0.f;
-#pragma unroll
-        for (int k = 0; k < DM; ++k) {
-            const float e = x[k] - rows[c * DM + k];
-            const float sq = e * e;
-            acc = (k == 0) ? sq : acc + sq;
-        }
-        best_c = acc < best ? c : best_c;
-        best = fminf(best, acc);
-    }
+    pq_scan_lds<DM, 8>(x, rows, c0, c1, best, best_c);
     cand_d[w][lane] = best;
     cand_c[w][lane] = best_c;
     __syncthreads();
@@ -194,10 +149,8 @@ __device__ __forceinline__ void encode_small_body(const EncParams &p, int m, int
     }
 }
 
-// Small calls (a flush of 64 window rows: 512 (row, subspace) pairs per kv head) cannot hide the scalar-cache
-// round trips of the kernel above behind other waves: 32 dependent s_load batches of ~0.6 us each.  This variant
-// puts the centroid row into LDS with ONE vector round trip (converted to fp32 on the way) and reads it back with
-// wave-uniform (broadcast) ds_reads that pipeline; one subspace per workgroup, a quarter of the centroids per wave.
+// The kernel stays apart from its body: written as one function, every instance gets other SGPR counts and another
+// prologue from hipcc (ROCm 7.2; the record is profiles/pq_scan_refactor.txt, A.3: retry the fold after a compiler change).
 template <int DM>
 __global__ __launch_bounds__(kEncBlock) void pq_encode_small_kernel(EncParams p) {
     encode_small_body<DM>(p, blockIdx.y, blockIdx.z, blockIdx.x);
@@ -318,7 +271,10 @@ __global__ __launch_bounds__(kFlushWaves * 64) void pq_flush_kernel(FlushParams 
             __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc((void *)lw, 0, lw ? 16 : 0, 0x00020000);
             ticket = __builtin_amdgcn_raw_ptr_buffer_atomic_add_i32(1, rl, tid == 0 ? 12 : (1 << 20), 0, 0);
         }
-        // (3) scan this wave's part of the centroids
+        // (3) scan this wave's part of the centroids: pq_scan_lds<DM, DM <= 2 ? 4 : 2> (pq_scan.h), written out.  Through the
+        //     helper the d_m = 1 instance gets another instruction mix from hipcc (ROCm 7.2); so does every instance when the
+        //     lengths above go through enc_load_row.  The record is profiles/pq_scan_refactor.txt, A.3: retry both after a
+        //     compiler change, so that this second copy goes.  Until then a change to the scan is made in both places.
         float best = INFINITY;
         int best_c = c0 < C ? c0 : 0;
         if (active) {
@@ -406,12 +362,9 @@ int launch_flush(const EncParams &k, const EncParams &v, int *dev_lengths_w, int
         gz = gz < 1 ? 1 : gz > pairs ? pairs : gz;
     }
     const dim3 grid(tblocks, 2 * k.M * f.hgroups, gz);
-    switch (k.dm) {
-        case 1: hipLaunchKernelGGL((pq_flush_kernel<1>), grid, dim3(kFlushWaves * 64), 0, s, f); break;
-        case 2: hipLaunchKernelGGL((pq_flush_kernel<2>), grid, dim3(kFlushWaves * 64), 0, s, f); break;
-        case 4: hipLaunchKernelGGL((pq_flush_kernel<4>), grid, dim3(kFlushWaves * 64), 0, s, f); break;
-        case 8: hipLaunchKernelGGL((pq_flush_kernel<8>), grid, dim3(kFlushWaves * 64), 0, s, f); break;
-        default: set_error("flush: d/M=%d unsupported (1,2,4,8)", k.dm); return MILLION_ERR_SHAPE;
+    if (!dispatch_dm(k.dm, [&](auto dm) { hipLaunchKernelGGL((pq_flush_kernel<dm()>), grid, dim3(kFlushWaves * 64), 0, s, f); })) {
+        set_error("flush: d/M=%d unsupported (1,2,4,8)", k.dm);
+        return MILLION_ERR_SHAPE;
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("flush launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
@@ -439,12 +392,9 @@ int launch_encode(const EncParams &p, hipStream_t s) {
     if (p.n <= 0 || p.bs * p.nh_k <= 0) return MILLION_OK;
     const int groups = (p.M + kEncSub - 1) / kEncSub;
     dim3 grid((p.n + 63) / 64, (groups + kEncBlock / 64 - 1) / (kEncBlock / 64), p.bs * p.nh_k);
-    switch (p.dm) {
-        case 1: launch_dm<1>(p, grid, s); break;
-        case 2: launch_dm<2>(p, grid, s); break;
-        case 4: launch_dm<4>(p, grid, s); break;
-        case 8: launch_dm<8>(p, grid, s); break;
-        default: set_error("encode: d/M=%d unsupported (1,2,4,8)", p.dm); return MILLION_ERR_SHAPE;
+    if (!dispatch_dm(p.dm, [&](auto dm) { launch_dm<dm()>(p, grid, s); })) {
+        set_error("encode: d/M=%d unsupported (1,2,4,8)", p.dm);
+        return MILLION_ERR_SHAPE;
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("encode launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
@@ -503,12 +453,9 @@ int launch_decode(const void *codes, const f16 *cents, f16 *out, long long n_row
     if (n_rows <= 0) return MILLION_OK;
     long long blocks = (n_rows * M + 255) / 256;
     if (blocks > 2048) blocks = 2048;
-    switch (dm) {
-        case 1: launch_decode_dm<1>(codes, cents, out, n_rows, M, C, (unsigned)blocks, s); break;
-        case 2: launch_decode_dm<2>(codes, cents, out, n_rows, M, C, (unsigned)blocks, s); break;
-        case 4: launch_decode_dm<4>(codes, cents, out, n_rows, M, C, (unsigned)blocks, s); break;
-        case 8: launch_decode_dm<8>(codes, cents, out, n_rows, M, C, (unsigned)blocks, s); break;
-        default: set_error("decode: d/M=%d unsupported (1,2,4,8)", dm); return MILLION_ERR_SHAPE;
+    if (!dispatch_dm(dm, [&](auto w) { launch_decode_dm<w()>(codes, cents, out, n_rows, M, C, (unsigned)blocks, s); })) {
+        set_error("decode: d/M=%d unsupported (1,2,4,8)", dm);
+        return MILLION_ERR_SHAPE;
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("decode launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }

@@ -10,17 +10,17 @@
 // Per request b (values clamped, see sr_load_row): r + n_b source rows - row j < r is window row (start + j) % resid_cap,
 // row j >= r is new row j - r - and source row j becomes token T + j of the request's K pages and transposed V pages.
 //
-// Arithmetic: pq_encode_kernel's contract (encode.hip), restated - e = x - c, sq = e * e, sequential sum, every operation
-// one IEEE fp32 round-to-nearest, no contraction; strict '<' over increasing c.  Same mapping too: lane = token, a wave owns
-// 4 consecutive subspaces, the centroid rows are wave-uniform and come through the scalar cache from the fp32 image of the
-// prepared codebook.  The grid is a function of the bounds alone (ceil((resid_cap + n_bound) / 64) token blocks x subspace
-// groups x (bs * nh_k) x 2 sides), so a captured launch follows the lengths: a block at or past r_b + n_b leaves before its
-// first vector load, a straddling block clamps its dead lanes to the last live row and does not store them.  No load sits in a
-// lane-conditional: the source address is selected (window or new rows), the page index is clamped to a page that receives a
-// token of the block.  No LDS.
+// Arithmetic: the contract and the centroid scan of every encoder kernel, pq_scan_sgpr (pq_scan.h).  pq_encode_kernel's mapping
+// (encode.hip) too: lane = token, a wave owns 4 consecutive subspaces, the centroid rows are wave-uniform and come through the
+// scalar cache from the fp32 image of the prepared codebook.  The grid is a function of the bounds alone
+// (ceil((resid_cap + n_bound) / 64) token blocks x subspace groups x (bs * nh_k) x 2 sides), so a captured launch follows the
+// lengths: a block at or past r_b + n_b leaves before its first vector load, a straddling block clamps its dead lanes to the
+// last live row and does not store them.  No load sits in a lane-conditional: the source address is selected (window or new
+// rows), the page index is clamped to a page that receives a token of the block.  No LDS.
 #include <string.h>
 
 #include "common.h"
+#include "pq_scan.h"
 
 #pragma clang fp contract(off)
 
@@ -28,8 +28,6 @@ namespace million {
 
 constexpr int kSrBlock = 256;
 constexpr int kSrSub = 4;      // subspaces per wave (M is a multiple of 4 on every supported shape)
-
-typedef float sr_v2f __attribute__((ext_vector_type(2)));
 
 struct StoreRaggedSide {
     const f16 *new_rows;        // new rows (bs, nh_k, n_bound, d)
@@ -120,37 +118,9 @@ __global__ __launch_bounds__(kSrBlock) void pq_store_ragged_kernel(StoreRaggedPa
     const float *__restrict__ tab = sd.cents32;
 #pragma unroll
     for (int s = 0; s < kSrSub; ++s) {
-        const float *__restrict__ c32 = tab + (long long)(m0 + s) * p.C * DM;   // wave-uniform rows
         float best = INFINITY;
         int best_c = 0;
-#pragma unroll 16
-        for (int c = 0; c < p.C; ++c) {
-            float cv[DM];
-#pragma unroll
-            for (int k = 0; k < DM; ++k) cv[k] = c32[c * DM + k];
-            float acc = 0.f;
-            if (DM % 2 == 0) {
-                // pairs of dims as packed fp32: every lane-half is one IEEE round-to-nearest operation
-#pragma unroll
-                for (int k = 0; k < DM; k += 2) {
-                    const sr_v2f xv = {x[s][k], x[s][k + 1]}, cc = {cv[k], cv[k + 1]};
-                    const sr_v2f e = xv - cc;
-                    const sr_v2f sq = e * e;
-                    acc = (k == 0) ? sq[0] : acc + sq[0];
-                    acc = acc + sq[1];
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < DM; ++k) {
-                    const float e = x[s][k] - cv[k];
-                    const float sq = e * e;
-                    acc = (k == 0) ? sq : acc + sq;
-                }
-            }
-            // strict '<', increasing c: the lowest index wins exact ties ("keep unless smaller", as pq_encode_kernel)
-            best_c = !(acc < best) ? best_c : c;
-            best = fminf(best, acc);
-        }
+        pq_scan_sgpr<DM>(x[s], tab + (long long)(m0 + s) * p.C * DM, p.C, best, best_c);   // wave-uniform rows
         codes |= (unsigned)best_c << (8 * s);
     }
     if (!keep) return;
@@ -238,12 +208,9 @@ extern "C" int million_pq_store_ragged(const million_store_ragged_desc *desc, co
     const int groups = d.M / kSrSub;
     const dim3 grid(((long long)d.resid_cap + d.n_bound + 63) / 64, (groups + kSrBlock / 64 - 1) / (kSrBlock / 64), d.bs * d.nh_k * 2);
     hipStream_t s = (hipStream_t)stream;
-    switch (dm) {
-        case 1: hipLaunchKernelGGL((pq_store_ragged_kernel<1>), grid, dim3(kSrBlock), 0, s, p); break;
-        case 2: hipLaunchKernelGGL((pq_store_ragged_kernel<2>), grid, dim3(kSrBlock), 0, s, p); break;
-        case 4: hipLaunchKernelGGL((pq_store_ragged_kernel<4>), grid, dim3(kSrBlock), 0, s, p); break;
-        case 8: hipLaunchKernelGGL((pq_store_ragged_kernel<8>), grid, dim3(kSrBlock), 0, s, p); break;
-        default: set_error("store_ragged: d/M=%d unsupported (1,2,4,8)", dm); return MILLION_ERR_SHAPE;
+    if (!dispatch_dm(dm, [&](auto w) { hipLaunchKernelGGL((pq_store_ragged_kernel<w()>), grid, dim3(kSrBlock), 0, s, p); })) {
+        set_error("store_ragged: d/M=%d unsupported (1,2,4,8)", dm);
+        return MILLION_ERR_SHAPE;
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("store_ragged launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }

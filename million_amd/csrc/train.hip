@@ -6,10 +6,9 @@
 //
 // One iteration is three launches on the caller's stream:
 //   kmeans_assign_kernel   pq_encode_kernel's scheme (encode.hip): lane = point, a wave owns 4 consecutive subspaces of 64
-//                          points, the centroid rows are wave-uniform fp32 scalar operands.  The distance loop is restated
-//                          here, not shared: encode.hip's object stays byte-identical.  Codes leave TRANSPOSED, (M, N), so
-//                          that the update reads one subspace contiguously; each workgroup leaves one fp64 partial of the
-//                          objective.
+//                          points, the centroid rows are wave-uniform fp32 scalar operands; the distance loop is
+//                          pq_scan_sgpr (pq_scan.h).  Codes leave TRANSPOSED, (M, N), so that the update reads one
+//                          subspace contiguously; each workgroup leaves one fp64 partial of the objective.
 //   kmeans_update_kernel   one wave = (chunk of kTrainChunk rows, subspace, 64 centroids), lane = centroid.  The wave loads
 //                          64 rows at a time (lane = row: one code and one sub-vector each), then walks them in row order
 //                          with v_readlane: acc += (code == c ? x : +0.0f).  Adding +0.0f never changes a sum that started
@@ -29,6 +28,7 @@
 #include <string.h>
 
 #include "common.h"
+#include "pq_scan.h"
 
 #pragma clang fp contract(off)
 
@@ -38,8 +38,6 @@ constexpr int kTrainChunk = 4096;     // rows per partial sum of the update: dep
 constexpr int kAssignBlock = 256;
 constexpr int kAssignSub = 4;         // subspaces per wave
 constexpr int kFinishBlock = 256;
-
-typedef float tv2f __attribute__((ext_vector_type(2)));
 
 struct TrainParams {
     const void *x;               // (N, d) fp32 or fp16, row stride xsn elements
@@ -113,37 +111,9 @@ __global__ __launch_bounds__(kAssignBlock) void kmeans_assign_kernel(TrainParams
     for (int j = 0; j < kAssignSub; ++j) {
         if (j >= nsub) break;
         const int m = m0 + j;
-        const float *__restrict__ c32 = p.cents + (long long)m * p.C * DM;      // wave-uniform rows: scalar operands
         float best = INFINITY;
         int best_c = 0;
-#pragma unroll 16
-        for (int c = 0; c < p.C; ++c) {
-            float cv[DM];
-#pragma unroll
-            for (int k = 0; k < DM; ++k) cv[k] = c32[c * DM + k];
-            float acc = 0.f;
-            if (DM % 2 == 0) {
-                // pairs of dims as packed fp32: every lane-half is one IEEE round-to-nearest operation
-#pragma unroll
-                for (int k = 0; k < DM; k += 2) {
-                    const tv2f xv = {x[j][k], x[j][k + 1]}, cc = {cv[k], cv[k + 1]};
-                    const tv2f e = xv - cc;
-                    const tv2f sq = e * e;
-                    acc = (k == 0) ? sq[0] : acc + sq[0];
-                    acc = acc + sq[1];
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < DM; ++k) {
-                    const float e = x[j][k] - cv[k];
-                    const float sq = e * e;
-                    acc = (k == 0) ? sq : acc + sq;
-                }
-            }
-            // strict '<', increasing c: the lowest index wins exact ties (see pq_encode_kernel)
-            best_c = !(acc < best) ? best_c : c;
-            best = fminf(best, acc);
-        }
+        pq_scan_sgpr<DM>(x[j], p.cents + (long long)m * p.C * DM, p.C, best, best_c);      // wave-uniform rows: scalar operands
         if (valid) {
             codes[(long long)m * p.n + t] = (CodeT)best_c;
             obj += (double)best;
@@ -379,12 +349,7 @@ int million_pq_train(const million_train_desc *desc, const void *x, const int32_
     }
     for (int it = 0; it < desc->niter; ++it) {
         p.objective_out = objective_out ? objective_out + it : nullptr;
-        switch (dm) {
-            case 1: launch_iter_dm<1>(p, xf32, ga, gu, s); break;
-            case 2: launch_iter_dm<2>(p, xf32, ga, gu, s); break;
-            case 4: launch_iter_dm<4>(p, xf32, ga, gu, s); break;
-            default: launch_iter_dm<8>(p, xf32, ga, gu, s); break;
-        }
+        dispatch_dm(dm, [&](auto w) { launch_iter_dm<w()>(p, xf32, ga, gu, s); });      // train_check: dm is 1, 2, 4 or 8
         hipLaunchKernelGGL(kmeans_finish_kernel, dim3(p.M + 1), dim3(kFinishBlock), (size_t)p.C * sizeof(int), s, p);
         p.cents = cents_out;
         const hipError_t e = hipGetLastError();
