@@ -172,6 +172,64 @@ int million_pq_store_ragged(const million_store_ragged_desc *desc, const void *k
                             int32_t *dev_lengths /* (bs, 4), advanced */, const int32_t *dev_n /* (bs,) */,
                             million_stream_t stream);
 
+/* Fork a request of a paged cache: ONE call (one launch) makes n_dst batch slots a copy of slot `src`, for every layer.
+ * Serves one long prompt with several questions or sampled continuations: the prompt is encoded once; the other requests
+ * share its code pages (SHARE) or get a private copy of them (COPY), and each gets the window and the lengths row.
+ * The layout is that of million_pq_flush_layers: page_ids (layers, bs, nh_k, n_pages_cap) int32, k_resid / v_resid
+ * (layers, bs, nh_k, resid_cap, d) fp16, dev_lengths (layers, bs, 4) int32, the layers ids_layer_stride int32, rows_layer_stride
+ * fp16 elements and lengths_layer_stride int32 apart (inside a layer the arrays are dense); K pool (n_pool, page_size, M) and
+ * V pool (n_pool, M, page_size) uint8, shared by all layers.  dst_slots: device (n_dst,) int32; tail_ids: device
+ * (n_dst, layers, nh_k) int32, the private page id of each destination's partial tail page (SHARE; may be NULL in COPY mode).
+ * Per layer l - every per-request value is read on the device and not trusted:
+ *   Source row {T, r, start, word 3} = dev_lengths[l, src]: T is clamped into [0, n_pages_bound * page_size], r into
+ *     [0, resid_cap], a start outside [0, resid_cap) reads as 0.  prefix_tokens = p >= 0: T <- min(T, p), r <- 0, start <- 0 and the
+ *     window is not copied (the destination becomes the source as it was after its first p tokens, when those were all codes).
+ *   full = T / page_size, tail = T % page_size, n_live = full + (tail ? 1 : 0).
+ *   Entry e_j of page j < n_live of each destination slot and kv head h - SHARE: the source's id for j < full and
+ *     tail_ids[dst index, l, h] for the partial page j = full, and e_j is written into the destination's table row; COPY: the
+ *     destination's own entry, the table is not written.  Entries at or past n_live are neither read nor written.
+ *   Page j is copied iff e_j differs from the source's id for page j: the whole page on both sides (page_size * M bytes of the K
+ *     page, M * page_size bytes of the transposed V page).  Both ids must lie in [0, n_pool): otherwise the copy is dropped - no
+ *     fault, no error.
+ *   Without a prefix all resid_cap rows of both source windows are copied to each destination, byte for byte, ring position
+ *     for ring position.  The destination's lengths row becomes {T, r, start, 0} from the clamped values.
+ * Never touched: the source's table row, pages, windows and lengths row, and every slot that is no destination.  A destination
+ * equal to src, outside [0, bs), or named by an earlier entry of dst_slots takes no part.  Destination tables (COPY) and tail ids
+ * must name pages no other row of the call reads or writes: overlapping ids stay inside the pools but the bytes are then
+ * whatever write came last.
+ * Errors, all before any launch: null pointers (windows: only when resid_cap > 0 and there is no prefix), src outside [0, bs), a
+ * bad struct_size, mode, n_dst < 0 or n_pages_bound outside [0, n_pages_cap]: MILLION_ERR_ARG; page_size not 32 / 64 / 128, M not
+ * 16 / 32 / 64, d no positive multiple of 8: MILLION_ERR_SHAPE; pools and windows 16-byte aligned, rows_layer_stride a multiple of
+ * 8: MILLION_ERR_ALIGN otherwise.  n_dst = 0 returns MILLION_OK whatever the pointers.
+ * One launch on `stream`: 16-byte vector copies, the grid a function of the bounds alone (n_pages_bound pages per (layer,
+ * destination, kv head) in COPY mode, one in SHARE mode, the window, one table / lengths task; at most 2048 workgroups that
+ * stride over it).  The call allocates nothing, synchronises nothing, uses no atomics, flags or workspace; every destination
+ * byte is a function of source bytes and the arguments alone, so a captured call follows the device arrays. */
+enum {
+    MILLION_FORK_SHARE = 0,       /* destinations name the source's full pages; a private copy of the partial tail page only */
+    MILLION_FORK_COPY = 1         /* destinations keep the ids their table rows hold and get a copy of every live page */
+};
+
+typedef struct {
+    uint32_t struct_size;         /* = sizeof(million_fork_desc) */
+    int32_t n_layers, bs, nh_k, d, M, page_size;
+    int32_t n_pages_cap;          /* row length of page_ids */
+    int32_t n_pool;               /* pages in each pool */
+    int32_t resid_cap;            /* rows of the window buffers; 0: no window */
+    int64_t ids_layer_stride;     /* int32 between the layers of page_ids */
+    int64_t rows_layer_stride;    /* fp16 elements between the layers of k_resid / v_resid */
+    int64_t lengths_layer_stride; /* int32 between the layers of dev_lengths */
+    int32_t src, n_dst;
+    int32_t mode;                 /* MILLION_FORK_* */
+    int32_t n_pages_bound;        /* host bound of the pages a request can have, <= n_pages_cap: sizes the COPY grid, clamps T */
+    int32_t prefix_tokens;        /* -1: everything, window included; p >= 0: the first min(T, p) tokens */
+} million_fork_desc;
+
+int million_cache_fork(const million_fork_desc *desc, int32_t *page_ids, void *k_pool, void *v_pool,
+                       void *k_resid, void *v_resid, int32_t *dev_lengths /* (layers, bs, 4) */,
+                       const int32_t *dst_slots /* (n_dst,) */, const int32_t *tail_ids /* (n_dst, layers, nh_k) or NULL */,
+                       million_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * PQ codebook training.
  * Replaces: train_pq (scripts/utils/pq_utils.py:586-609), which wraps faiss-cpu's IndexPQ.train: ProductQuantizer's default

@@ -71,6 +71,16 @@ class StoreRaggedDesc(ctypes.Structure):
                 ("n_pages_cap", c_i32)]
 
 
+MILLION_FORK_SHARE, MILLION_FORK_COPY = 0, 1
+
+
+class ForkDesc(ctypes.Structure):
+    _fields_ = [("struct_size", c_u32), ("n_layers", c_i32), ("bs", c_i32), ("nh_k", c_i32), ("d", c_i32), ("M", c_i32),
+                ("page_size", c_i32), ("n_pages_cap", c_i32), ("n_pool", c_i32), ("resid_cap", c_i32),
+                ("ids_layer_stride", c_i64), ("rows_layer_stride", c_i64), ("lengths_layer_stride", c_i64),
+                ("src", c_i32), ("n_dst", c_i32), ("mode", c_i32), ("n_pages_bound", c_i32), ("prefix_tokens", c_i32)]
+
+
 class TrainDesc(ctypes.Structure):
     _fields_ = [("struct_size", c_u32), ("n", c_i32), ("d", c_i32), ("M", c_i32), ("C", c_i32), ("niter", c_i32),
                 ("x_is_f32", c_i32), ("x_stride_n", c_i64), ("eps", ctypes.c_float)]
@@ -101,6 +111,7 @@ SYMBOLS = {
     "million_chunk_attn_workspace_bytes": (c_sz, [ctypes.POINTER(ChunkAttnDesc)]),
     "million_pq_chunk_attn": (c_i32, [ctypes.POINTER(ChunkAttnDesc)] + [c_vp] * 13 + [c_sz, c_vp]),
     "million_pq_store_ragged": (c_i32, [ctypes.POINTER(StoreRaggedDesc)] + [c_vp] * 12),
+    "million_cache_fork": (c_i32, [ctypes.POINTER(ForkDesc)] + [c_vp] * 9),
     "million_set_force_generic": (None, [c_i32]),
     "million_debug_set_stamp_buffer": (None, [c_vp]),
     "million_debug_bad_page_ids": (c_i32, []),

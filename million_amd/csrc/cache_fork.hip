@@ -1,0 +1,243 @@
+// cache_fork.hip — make batch slots of a paged cache a copy of another slot in one launch (million_cache_fork), gfx950.
+//
+// One long prompt, several questions or sampled continuations: the requests share the prompt's code pages (SHARE: the page
+// table row of each destination is written with the source's ids, only the partial tail page gets a private copy) or get a
+// private copy of every page into the ids their table row already holds (COPY: a preallocated table).  The residual window
+// and the lengths row travel with it.  Everything per request is read on the device (the source's {T, r, start}, the
+// destination slots, the tables), so a captured call follows the arrays.
+//
+// The work is a list of 16-byte-vector copies, cut into TASKS that a workgroup takes one after the other (grid-stride loop,
+// grid capped at kForkMaxGrid).  Per (layer, destination, kv head) - a "row" - the tasks are, in this order:
+//   page tasks    ceil(P / G) of them, P = n_pages_bound (COPY) or 1 (SHARE: the tail page); a task owns G consecutive pages,
+//                 both sides: ~32 KiB in flight per workgroup, every load of a pass issued before its first store;
+//   window tasks  W of them, each kForkWinBytes of the K window and of the V window (none with a prefix);
+//   one meta task SHARE: the table entries below n_live; kv head 0: the destination's lengths row.
+// The task count is a function of the bounds alone.  No task reads what another writes: the source's row, table and pages
+// are only read, a destination's table is read (COPY) or written (SHARE), never both, and tail ids come from tail_ids.  So
+// there are no atomics, flags or ordering between workgroups, and no LDS beyond the task's page ids.
+// Stores are plain 16-byte vector stores: the copied lines stay in the storing XCD's L2 for the attention launch that
+// follows; write-through forms would drop them and nothing here hands bytes to a running workgroup.
+#include <string.h>
+
+#include "common.h"
+
+namespace million {
+
+constexpr int kForkBlock = 256;
+constexpr int kForkMaxGrid = 2048;        // memory-bound: a few workgroups per CU (256 CUs), grid-stride the rest
+constexpr int kForkGroupBytes = 16384;    // per side and page task: G = kForkGroupBytes / page bytes pages, 1 <= G <= kForkMaxG
+constexpr int kForkMaxG = 32;
+constexpr int kForkWinBytes = 16384;      // per side and window task
+constexpr int kForkUnroll = 8;            // 16-byte loads in flight per thread
+
+typedef unsigned fv4 __attribute__((ext_vector_type(4)));
+
+struct ForkParams {
+    int *page_ids;              // (layers, bs, nh_k, n_pages_cap)
+    uint8_t *k_pool, *v_pool;
+    uint8_t *k_win, *v_win;     // (layers, bs, nh_k, resid_cap, d) fp16, as bytes
+    int *dev_lengths;           // (layers, bs, 4)
+    const int *dst_slots;       // (n_dst,)
+    const int *tail_ids;        // (n_dst, layers, nh_k); SHARE only
+    long long ids_ls, win_ls_bytes, len_ls;
+    int n_layers, bs, nh_k, n_pages_cap, n_pool;
+    int page_bytes, pb_shift;   // page_size * M, a power of two in [512, 8192]
+    int page_size, ps_shift;
+    int win_bytes;              // resid_cap * d * 2 per (layer, slot, kv head) and side
+    int rcap;
+    int src, n_dst, share;
+    int n_pages_bound, cap_tok, prefix;
+    int G, n_ptasks, n_wtasks;  // per row: page tasks of G pages, window tasks
+    long long n_tasks;
+};
+
+// The source's row of layer l as every task reads it.  Device-resident values are not trusted: T into [0, cap_tok] (cap_tok =
+// n_pages_bound * page_size), r into [0, resid_cap], a start outside [0, resid_cap) reads as 0; then the prefix.
+__device__ __forceinline__ void fork_load_row(const ForkParams &p, int l, int &T, int &r, int &st) {
+    // through the constant address space: the source's row is never written while this kernel runs
+    typedef const __attribute__((address_space(4))) int *const_p;
+    const_p row = (const_p)(p.dev_lengths + l * p.len_ls + 4ll * p.src);
+    T = row[0]; r = row[1]; st = row[2];
+    T = T < 0 ? 0 : (T > p.cap_tok ? p.cap_tok : T);
+    r = r < 0 ? 0 : (r > p.rcap ? p.rcap : r);
+    st = (unsigned)st < (unsigned)p.rcap ? st : 0;
+    if (p.prefix >= 0) { T = T < p.prefix ? T : p.prefix; r = 0; st = 0; }
+}
+
+// Destination jd of the call: its slot, or -1 when it takes no part (outside [0, bs), the source itself, or a slot an earlier
+// entry of dst_slots names already: the first one serves it).
+__device__ __forceinline__ int fork_dst(const ForkParams &p, int jd) {
+    typedef const __attribute__((address_space(4))) int *const_p;
+    const_p slots = (const_p)p.dst_slots;
+    const int dst = slots[jd];
+    if ((unsigned)dst >= (unsigned)p.bs || dst == p.src) return -1;
+    for (int i = 0; i < jd; ++i)
+        if (slots[i] == dst) return -1;
+    return dst;
+}
+
+// 4 waves per SIMD (<= 128 registers): 4 workgroups of ~32 KiB in flight per CU.  Left to itself hipcc takes all 512 registers
+// of a 256-thread workgroup for this loop nest (one workgroup per CU).
+__global__ __launch_bounds__(kForkBlock) __attribute__((amdgpu_waves_per_eu(4))) void cache_fork_kernel(ForkParams p) {
+    __shared__ long long s_src[kForkMaxG], s_dst[kForkMaxG];      // byte offsets of the task's pages; s_dst < 0: not copied
+    const int tid = threadIdx.x;
+    const int per_row = p.n_ptasks + p.n_wtasks + 1;
+#pragma unroll 1
+    for (long long t = blockIdx.x; t < p.n_tasks; t += gridDim.x) {      // workgroup-uniform
+        const int sub = (int)(t % per_row);
+        const int row = (int)(t / per_row);
+        const int h = row % p.nh_k;
+        const int jd = (row / p.nh_k) % p.n_dst;
+        const int l = row / (p.nh_k * p.n_dst);
+        const int dst = fork_dst(p, jd);
+        if (dst < 0) continue;
+        int T, r, st;
+        fork_load_row(p, l, T, r, st);
+        const int full = T >> p.ps_shift;
+        const int n_live = full + ((T & (p.page_size - 1)) ? 1 : 0);      // <= n_pages_bound <= n_pages_cap
+        const int *src_ids = p.page_ids + l * p.ids_ls + ((long long)p.src * p.nh_k + h) * p.n_pages_cap;
+        int *dst_ids = p.page_ids + l * p.ids_ls + ((long long)dst * p.nh_k + h) * p.n_pages_cap;
+
+        if (sub < p.n_ptasks) {
+            // ---- G pages, both sides.  SHARE: the one page task of the row is the tail page, when there is one.
+            const int j0 = p.share ? full : sub * p.G;
+            const int ng = p.share ? (n_live > full ? 1 : 0) : (n_live - j0 < p.G ? n_live - j0 : p.G);
+            if (ng <= 0) continue;
+            __syncthreads();      // the previous task's readers of s_src / s_dst are done
+            if (tid < ng) {
+                const int j = j0 + tid;
+                const int sid = src_ids[j];
+                const int e = p.share ? p.tail_ids[((long long)jd * p.n_layers + l) * p.nh_k + h] : dst_ids[j];
+                const bool copy = e != sid && (unsigned)e < (unsigned)p.n_pool && (unsigned)sid < (unsigned)p.n_pool;
+                s_src[tid] = (long long)sid << p.pb_shift;
+                s_dst[tid] = copy ? (long long)e << p.pb_shift : -1;
+            }
+            __syncthreads();
+            // vector i of the task: page g = i / (2 * vpp), side (i / vpp) & 1, vector i % vpp of that page
+            const int vshift = p.pb_shift - 4;
+            const int nvec = ng << (vshift + 1);
+#pragma unroll 1
+            for (int base = 0; base < nvec; base += kForkBlock * kForkUnroll) {
+                fv4 v[kForkUnroll];
+#pragma unroll
+                for (int u = 0; u < kForkUnroll; ++u) {
+                    const int i = base + u * kForkBlock + tid;
+                    const int g = (i < nvec ? i : 0) >> (vshift + 1);
+                    const int in_page = (i & ((1 << vshift) - 1)) << 4;
+                    const uint8_t *pool = ((i >> vshift) & 1) ? p.v_pool : p.k_pool;
+                    if (i < nvec && s_dst[g] >= 0) v[u] = *(const fv4 *)(pool + s_src[g] + in_page);
+                }
+#pragma unroll
+                for (int u = 0; u < kForkUnroll; ++u) {
+                    const int i = base + u * kForkBlock + tid;
+                    const int g = (i < nvec ? i : 0) >> (vshift + 1);
+                    const int in_page = (i & ((1 << vshift) - 1)) << 4;
+                    uint8_t *pool = ((i >> vshift) & 1) ? p.v_pool : p.k_pool;
+                    if (i < nvec && s_dst[g] >= 0) *(fv4 *)(pool + s_dst[g] + in_page) = v[u];
+                }
+            }
+        } else if (sub < p.n_ptasks + p.n_wtasks) {
+            // ---- kForkWinBytes of each window, byte for byte: ring positions are kept
+            const int c0 = (sub - p.n_ptasks) * kForkWinBytes;
+            const int left = p.win_bytes - c0;
+            const int nv1 = (left < kForkWinBytes ? left : kForkWinBytes) >> 4;      // vectors per side
+            const long long so = l * p.win_ls_bytes + ((long long)p.src * p.nh_k + h) * p.win_bytes + c0;
+            const long long dof = l * p.win_ls_bytes + ((long long)dst * p.nh_k + h) * p.win_bytes + c0;
+#pragma unroll 1
+            for (int base = 0; base < 2 * nv1; base += kForkBlock * kForkUnroll) {
+                fv4 v[kForkUnroll];
+#pragma unroll
+                for (int u = 0; u < kForkUnroll; ++u) {
+                    const int i = base + u * kForkBlock + tid;
+                    const bool vside = i >= nv1;
+                    const long long o = (long long)(vside ? i - nv1 : i) << 4;
+                    if (i < 2 * nv1) v[u] = *(const fv4 *)((vside ? p.v_win : p.k_win) + so + o);
+                }
+#pragma unroll
+                for (int u = 0; u < kForkUnroll; ++u) {
+                    const int i = base + u * kForkBlock + tid;
+                    const bool vside = i >= nv1;
+                    const long long o = (long long)(vside ? i - nv1 : i) << 4;
+                    if (i < 2 * nv1) *(fv4 *)((vside ? p.v_win : p.k_win) + dof + o) = v[u];
+                }
+            }
+        } else {
+            // ---- meta: the table row (SHARE), the lengths row (once per (layer, destination))
+            if (p.share) {
+                const int tail = p.tail_ids[((long long)jd * p.n_layers + l) * p.nh_k + h];
+                for (int j = tid; j < n_live; j += kForkBlock) dst_ids[j] = j < full ? src_ids[j] : tail;
+            }
+            if (h == 0 && tid == 0) {
+                int *row_d = p.dev_lengths + l * p.len_ls + 4ll * dst;
+                row_d[0] = T; row_d[1] = r; row_d[2] = st; row_d[3] = 0;
+            }
+        }
+    }
+}
+
+}  // namespace million
+
+using namespace million;
+
+extern "C" int million_cache_fork(const million_fork_desc *desc, int32_t *page_ids, void *k_pool, void *v_pool,
+                                  void *k_resid, void *v_resid, int32_t *dev_lengths, const int32_t *dst_slots,
+                                  const int32_t *tail_ids, million_stream_t stream) {
+    if (!desc || desc->struct_size != sizeof(million_fork_desc)) { set_error("cache_fork: bad desc / struct_size"); return MILLION_ERR_ARG; }
+    const million_fork_desc &d = *desc;
+    if (d.page_size != 32 && d.page_size != 64 && d.page_size != 128) { set_error("cache_fork: page_size=%d (32, 64 or 128)", d.page_size); return MILLION_ERR_SHAPE; }
+    if (d.M != 16 && d.M != 32 && d.M != 64) { set_error("cache_fork: M=%d (16, 32 or 64)", d.M); return MILLION_ERR_SHAPE; }
+    if (d.n_layers <= 0 || d.bs <= 0 || d.nh_k <= 0 || d.d <= 0 || (d.d & 7) || d.n_pages_cap <= 0 || d.n_pool <= 0 || d.resid_cap < 0) {
+        set_error("cache_fork: n_layers=%d bs=%d nh_k=%d d=%d (a multiple of 8) n_pages_cap=%d n_pool=%d resid_cap=%d", d.n_layers, d.bs,
+                  d.nh_k, d.d, d.n_pages_cap, d.n_pool, d.resid_cap);
+        return MILLION_ERR_SHAPE;
+    }
+    if ((long long)d.n_pages_cap * d.page_size > 0x7fffffffLL || (long long)d.bs * d.nh_k * d.n_pages_cap > 0x7fffffffLL ||
+        (long long)d.resid_cap * d.d * 2 > 0x7fffffffLL || (long long)d.n_layers * d.bs * d.nh_k > 0x7fffffffLL) {
+        set_error("cache_fork: n_pages_cap=%d resid_cap=%d bs=%d nh_k=%d n_layers=%d: a row does not fit 31 bits", d.n_pages_cap, d.resid_cap,
+                  d.bs, d.nh_k, d.n_layers);
+        return MILLION_ERR_SHAPE;
+    }
+    if (d.mode != MILLION_FORK_SHARE && d.mode != MILLION_FORK_COPY) { set_error("cache_fork: mode=%d (SHARE 0, COPY 1)", d.mode); return MILLION_ERR_ARG; }
+    if (d.src < 0 || d.src >= d.bs) { set_error("cache_fork: src=%d outside [0, %d)", d.src, d.bs); return MILLION_ERR_ARG; }
+    if (d.n_dst < 0 || d.n_pages_bound < 0 || d.n_pages_bound > d.n_pages_cap || d.prefix_tokens < -1) {
+        set_error("cache_fork: n_dst=%d n_pages_bound=%d (0 .. n_pages_cap=%d) prefix_tokens=%d (>= -1)", d.n_dst, d.n_pages_bound,
+                  d.n_pages_cap, d.prefix_tokens);
+        return MILLION_ERR_ARG;
+    }
+    if (d.n_dst == 0) return MILLION_OK;      // no destination: nothing to do, whatever the pointers
+    const bool window = d.prefix_tokens < 0 && d.resid_cap > 0;
+    if (!page_ids || !k_pool || !v_pool || !dev_lengths || !dst_slots) { set_error("cache_fork: null page_ids / pools / dev_lengths / dst_slots"); return MILLION_ERR_ARG; }
+    if (window && (!k_resid || !v_resid)) { set_error("cache_fork: null window with resid_cap=%d and no prefix", d.resid_cap); return MILLION_ERR_ARG; }
+    if (d.mode == MILLION_FORK_SHARE && !tail_ids) { set_error("cache_fork: null tail_ids in SHARE mode (the private id of each partial tail page)"); return MILLION_ERR_ARG; }
+    if (((uintptr_t)k_pool | (uintptr_t)v_pool | (window ? (uintptr_t)k_resid | (uintptr_t)v_resid : 0)) & 15) {
+        set_error("cache_fork: pools and windows must be 16-byte aligned");
+        return MILLION_ERR_ALIGN;
+    }
+    if (((uintptr_t)page_ids | (uintptr_t)dev_lengths | (uintptr_t)dst_slots | (uintptr_t)tail_ids) & 3) { set_error("cache_fork: page_ids / dev_lengths / dst_slots / tail_ids must be 4-byte aligned"); return MILLION_ERR_ALIGN; }
+    if (window && (d.rows_layer_stride & 7)) { set_error("cache_fork: the windows' layer stride must be a multiple of 8 elements (16 bytes)"); return MILLION_ERR_ALIGN; }
+
+    ForkParams p;
+    memset(&p, 0, sizeof(p));
+    p.page_ids = page_ids; p.k_pool = (uint8_t *)k_pool; p.v_pool = (uint8_t *)v_pool;
+    p.k_win = (uint8_t *)k_resid; p.v_win = (uint8_t *)v_resid;
+    p.dev_lengths = dev_lengths; p.dst_slots = dst_slots; p.tail_ids = tail_ids;
+    p.ids_ls = d.ids_layer_stride; p.win_ls_bytes = d.rows_layer_stride * 2; p.len_ls = d.lengths_layer_stride;
+    p.n_layers = d.n_layers; p.bs = d.bs; p.nh_k = d.nh_k; p.n_pages_cap = d.n_pages_cap; p.n_pool = d.n_pool;
+    p.page_size = d.page_size; p.ps_shift = d.page_size == 32 ? 5 : d.page_size == 64 ? 6 : 7;
+    p.page_bytes = d.page_size * d.M;
+    p.pb_shift = p.ps_shift + (d.M == 16 ? 4 : d.M == 32 ? 5 : 6);
+    p.rcap = d.resid_cap; p.win_bytes = d.resid_cap * d.d * 2;
+    p.src = d.src; p.n_dst = d.n_dst; p.share = d.mode == MILLION_FORK_SHARE;
+    p.n_pages_bound = d.n_pages_bound; p.cap_tok = d.n_pages_bound * d.page_size; p.prefix = d.prefix_tokens;
+    p.G = kForkGroupBytes / p.page_bytes;
+    p.G = p.G < 1 ? 1 : (p.G > kForkMaxG ? kForkMaxG : p.G);
+    p.n_ptasks = p.share ? 1 : (d.n_pages_bound + p.G - 1) / p.G;
+    p.n_wtasks = window ? (p.win_bytes + kForkWinBytes - 1) / kForkWinBytes : 0;
+    p.n_tasks = (long long)d.n_layers * d.n_dst * d.nh_k * (p.n_ptasks + p.n_wtasks + 1);
+    if ((long long)d.n_layers * d.n_dst * d.nh_k > 0x7fffffffLL) { set_error("cache_fork: n_layers * n_dst * nh_k does not fit 31 bits"); return MILLION_ERR_SHAPE; }
+    const int grid = (int)(p.n_tasks < kForkMaxGrid ? p.n_tasks : kForkMaxGrid);
+    hipLaunchKernelGGL(cache_fork_kernel, dim3(grid), dim3(kForkBlock), 0, (hipStream_t)stream, p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("cache_fork launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
+    return MILLION_OK;
+}

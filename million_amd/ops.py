@@ -249,6 +249,51 @@ def pq_store_ragged(k_new: torch.Tensor, v_new: torch.Tensor, k_res: Optional[to
     _vshadow_drop(v_pool)
 
 
+def cache_fork(page_ids: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_res: torch.Tensor, v_res: torch.Tensor,
+               dev_lengths: torch.Tensor, dst_slots: torch.Tensor, tail_ids: Optional[torch.Tensor], *, src: int, share: bool,
+               n_pages_bound: Optional[int] = None, prefix_tokens: int = -1) -> None:
+    """Make the batch slots dst_slots (device int32 (n_dst,)) a copy of slot `src` in every layer, in one launch
+    (million_cache_fork): page_ids (layers, bs, nh_k, n_pages_cap) int32, k_pool (n_pool, page_size, M) / v_pool
+    (n_pool, M, page_size) uint8, k_res / v_res (layers, bs, nh_k, cap, d) fp16, dev_lengths (layers, bs, 4) int32 - the layers
+    of one cache side by side.  share=True: the destinations' table rows get the source's ids and tail_ids (device int32
+    (n_dst, layers, nh_k)) for the partial tail page, which alone is copied; share=False: every live page is copied into the
+    ids the destinations' rows hold.  The window and the lengths row follow; prefix_tokens >= 0 copies the first tokens only and
+    no window.  n_pages_bound (default: the table's row length) bounds the source's pages: it sizes the grid."""
+    _need_cuda(page_ids, k_pool, v_pool, k_res, v_res, dev_lengths, dst_slots, tail_ids)
+    if page_ids.dtype != torch.int32 or page_ids.dim() != 4 or page_ids[0].numel() and not page_ids[0].is_contiguous():
+        raise RuntimeError("cache_fork: int32 page_ids (layers, bs, nh_k, n_pages_cap), each layer contiguous, expected")
+    n_layers, bs, nhk, cap_pages = page_ids.shape
+    if (k_pool.dtype != torch.uint8 or v_pool.dtype != torch.uint8 or k_pool.dim() != 3 or not k_pool.is_contiguous() or not v_pool.is_contiguous()
+            or v_pool.shape != (k_pool.shape[0], k_pool.shape[2], k_pool.shape[1])):
+        raise RuntimeError("cache_fork: contiguous uint8 pools (n_pool, page_size, M) and (n_pool, M, page_size) expected")
+    n_pool, page_size, M = k_pool.shape
+    if (k_res.dtype != torch.float16 or v_res.dtype != torch.float16 or k_res.dim() != 5 or k_res.shape != v_res.shape or k_res.stride() != v_res.stride()
+            or k_res.shape[:3] != (n_layers, bs, nhk) or not k_res[0].is_contiguous()):
+        raise RuntimeError("cache_fork: fp16 windows (layers, bs, nh_k, cap, d), each layer contiguous, K and V alike, expected")
+    cap, d = k_res.shape[3], k_res.shape[4]
+    if dev_lengths.dtype != torch.int32 or dev_lengths.shape != (n_layers, bs, 4) or not dev_lengths[0].is_contiguous():
+        raise RuntimeError("cache_fork: int32 dev_lengths (layers, bs, 4) expected")
+    if dst_slots.dtype != torch.int32 or dst_slots.dim() != 1 or not dst_slots.is_contiguous():
+        raise RuntimeError("cache_fork: dst_slots must be contiguous int32 (n_dst,)")
+    n_dst = dst_slots.numel()
+    if tail_ids is not None and (tail_ids.dtype != torch.int32 or tail_ids.shape != (n_dst, n_layers, nhk) or not tail_ids.is_contiguous()):
+        raise RuntimeError("cache_fork: tail_ids must be contiguous int32 (n_dst, layers, nh_k)")
+    if share and tail_ids is None:
+        raise RuntimeError("cache_fork: share=True needs tail_ids")
+    desc = L.ForkDesc()
+    desc.struct_size = ctypes.sizeof(L.ForkDesc)
+    desc.n_layers, desc.bs, desc.nh_k, desc.d, desc.M, desc.page_size = n_layers, bs, nhk, d, M, page_size
+    desc.n_pages_cap, desc.n_pool, desc.resid_cap = cap_pages, n_pool, cap
+    desc.ids_layer_stride, desc.rows_layer_stride, desc.lengths_layer_stride = page_ids.stride(0), k_res.stride(0), dev_lengths.stride(0)
+    desc.src, desc.n_dst, desc.mode = int(src), n_dst, L.MILLION_FORK_SHARE if share else L.MILLION_FORK_COPY
+    desc.n_pages_bound = cap_pages if n_pages_bound is None else int(n_pages_bound)
+    desc.prefix_tokens = int(prefix_tokens)
+    L.check(L.load().million_cache_fork(ctypes.byref(desc), page_ids.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(), k_res.data_ptr(),
+                                        v_res.data_ptr(), dev_lengths.data_ptr(), dst_slots.data_ptr(), _ptr(tail_ids), _stream()),
+            "million_cache_fork")
+    _vshadow_drop(v_pool)
+
+
 def transpose_v_codes(v_codes: torch.Tensor, n_tokens: Optional[int] = None) -> torch.Tensor:
     """Row-major V codes (bs, nh_k, T, M) u8 -> dense transposed 64-token pages ((bs*nh_k)*ceil(T/64), M, 64)."""
     _need_cuda(v_codes)

@@ -113,6 +113,7 @@ class PageManager:
         self.allocated_pages: Dict[int, Dict] = {}
         self.total_allocations = self.page_reuse_count = self.total_expansions = 0
         self._ever_used: Set[int] = set()
+        self._extra_refs: Dict[int, int] = {}      # references beyond the first, shared pages only (share_page)
 
     def _expand_page_pool(self, additional_pages: Optional[int] = None):
         if additional_pages is None:
@@ -153,8 +154,37 @@ class PageManager:
                 raise RuntimeError(f"Cannot bulk-allocate {n} pages: max_pages={self.max_pages}")
         return [self.allocate_page() for _ in range(n)]
 
-    def free_page(self, page_id: int):
+    def share_page(self, page_id: int) -> int:
+        """One more owner of an allocated page (PagedPQCache.fork: requests that share a prompt's code pages); each owner
+        gives its reference back with free_page.  Returns the page's reference count."""
         if page_id not in self.allocated_pages:
+            raise RuntimeError(f"share_page: page {page_id} is not allocated")
+        self._extra_refs[page_id] = self._extra_refs.get(page_id, 0) + 1
+        return 1 + self._extra_refs[page_id]
+
+    def share_pages(self, page_ids) -> None:
+        """share_page for every id of a list (a fork shares hundreds of pages per table row); all or nothing."""
+        alloc, extra = self.allocated_pages, self._extra_refs
+        for pid in page_ids:
+            if pid not in alloc:
+                raise RuntimeError(f"share_page: page {pid} is not allocated")
+        for pid in page_ids:
+            extra[pid] = extra.get(pid, 0) + 1
+
+    def ref_count(self, page_id: int) -> int:
+        """Owners of a page: 0 for a free (or unknown) id, 1 for a page never shared."""
+        return 1 + self._extra_refs.get(page_id, 0) if page_id in self.allocated_pages else 0
+
+    def free_page(self, page_id: int):
+        """Drops one reference; the id returns to the free list with the last one."""
+        if page_id not in self.allocated_pages:
+            return
+        extra = self._extra_refs.get(page_id, 0)
+        if extra:
+            if extra == 1:
+                del self._extra_refs[page_id]
+            else:
+                self._extra_refs[page_id] = extra - 1
             return
         del self.allocated_pages[page_id]
         self.free_pages.add(page_id)
@@ -167,6 +197,11 @@ class PageManager:
                 "utilization": len(self.allocated_pages) / max(self.current_active_pages, 1),
                 "page_reuse_count": self.page_reuse_count, "total_allocations": self.total_allocations,
                 "total_expansions": self.total_expansions}
+
+    def sharing_stats(self) -> Dict:
+        """shared_pages: allocated pages with more than one owner; extra_references: owners beyond the first, over all pages
+        (the pages a cache without sharing would hold in addition)."""
+        return {"shared_pages": len(self._extra_refs), "extra_references": sum(self._extra_refs.values())}
 
 
 class _CacheBase:
@@ -706,10 +741,87 @@ class PagedPQCache(_CacheBase):
             self._store(key_states[b:b + 1, :, :n_new[b]], value_states[b:b + 1, :, :n_new[b]], layer_idx, n_new[b], b)
         return out
 
+    # ---- fork: a slot becomes a copy of another -------------------------------------------------------------------------
+    def _note_forked(self, src, dsts, n_tokens=None):
+        """The slots dsts became a copy of slot src in every layer (fork) - of its first n_tokens tokens, all of them codes,
+        when n_tokens is given.  Nothing of them is encoded ahead: their next flush is an in-line one."""
+        for arr in (self._T_a, self._r_a, self._rs_a, self._seen_a):
+            arr[:, dsts] = arr[:, [src]]
+        if n_tokens is not None:
+            self._T_a[:, dsts] = self._seen_a[:, dsts] = n_tokens
+            self._r_a[:, dsts] = self._rs_a[:, dsts] = 0
+        self._pre_a[:, dsts] = 0
+
+    def fork(self, src, dst, n_tokens=None):
+        """Slot(s) dst (one slot or a list) become a copy of slot src, in every layer and in ONE launch (ops.cache_fork): the
+        codes, the residual window and the lengths - what prefill_request of the same prompt and the same decode steps would
+        have left there, bit for bit, without the prompt pass.  n_tokens (0 .. T of the source): only the first n_tokens coded
+        tokens and no window - the slot a prompt of those tokens would have filled.
+        Paging on demand (preallocate=False) SHARES the code pages: the destinations' table rows name the source's full pages
+        (PageManager.share_page: a page returns to the free list when its last owner releases it) and only a partial tail
+        page is copied, into one fresh id per (layer, kv head, destination).  Nothing ever writes a token below a request's
+        T, so a shared page never changes under its owners.  A preallocated table keeps its fixed ids and gets a copy of
+        every live page.  Call it between steps: the source must be at the same lengths in every layer (its pending
+        encode-ahead work is joined, as extend does); every destination must be empty (release it first)."""
+        dsts = [int(dst)] if np.isscalar(dst) else [int(x) for x in dst]
+        src = int(src)
+        nk, ps, nl = self.num_key_value_heads, self.page_size, self.layer_num
+        if not 0 <= src < self.bs or not dsts or any(not 0 <= b < self.bs for b in dsts):
+            raise RuntimeError(f"fork: slots outside [0, {self.bs})")
+        if src in dsts or len(set(dsts)) != len(dsts):
+            raise RuntimeError("fork: destinations must differ from the source and from each other")
+        for b in dsts:
+            if self._T_a[:, b].any() or self._r_a[:, b].any():
+                raise RuntimeError(f"fork: slot {b} holds tokens (release it first)")
+        cols = (self._T_a[:, src], self._r_a[:, src], self._rs_a[:, src])
+        if self._ahead is not None or any((c != c[0]).any() for c in cols):
+            raise RuntimeError("fork: the source is mid-step (its layers are at different lengths); fork between steps")
+        T_src = int(self._T_a[0, src])
+        if n_tokens is not None and not 0 <= int(n_tokens) <= T_src:
+            raise RuntimeError(f"fork: n_tokens={n_tokens} outside [0, {T_src}] (the coded tokens of slot {src})")
+        T = T_src if n_tokens is None else int(n_tokens)
+        full, tail = divmod(T, ps)
+        n_live = full + (1 if tail else 0)
+        share = not self.preallocate
+        if share and tail:
+            need = nl * nk * len(dsts)
+            returned = sum(len(self._host_pids[l][b][h]) for l in range(nl) for b in dsts for h in range(nk))
+            if len(self.page_manager.free_pages) + returned < need:
+                raise RuntimeError(f"fork: {need} free pages needed for the partial tail pages, "
+                                   f"{len(self.page_manager.free_pages) + returned} left")
+        for l in range(nl):
+            self._join_side(l, src)
+        buf = list(dsts)      # one host-to-device copy: the destination slots, then the tail ids (n_dst, layers, nh_k)
+        if share:
+            pm = self.page_manager
+            for b in dsts:
+                for l in range(nl):
+                    for h in range(nk):
+                        for pid in self._host_pids[l][b][h]:      # pages of an empty slot hold no token
+                            pm.free_page(pid)
+                        mine = self._host_pids[l][src][h][:full]
+                        pm.share_pages(mine)
+                        tid = pm.allocate_page() if tail else -1
+                        if tail:
+                            mine.append(tid)
+                        buf.append(tid)
+                        self._host_pids[l][b][h] = mine
+                    self._pages_a[l, b] = n_live
+        dev = torch.tensor(buf, dtype=torch.int32).to(self.device)
+        tail_ids = dev[len(dsts):].view(len(dsts), nl, nk) if share else None
+        ops.cache_fork(self._page_ids_all, self.key_page_pool, self.value_page_pool, self._kres_all, self._vres_all,
+                       self._lengths_all, dev[:len(dsts)], tail_ids, src=src, share=share, n_pages_bound=n_live,
+                       prefix_tokens=-1 if n_tokens is None else T)
+        self._note_forked(src, dsts, None if n_tokens is None else T)
+
+    def sharing_stats(self) -> Dict:
+        """PageManager.sharing_stats: pages with more than one owner, and the owners beyond the first."""
+        return self.page_manager.sharing_stats()
+
     def release(self, b):
         """Request b has finished: its pages go back to the PageManager (on-demand paging; a preallocated table keeps its
-        fixed ids for the slot's next request), its host and device lengths return to zero.  The other slots, and any
-        captured graph (lengths are read on the device), are not touched."""
+        fixed ids for the slot's next request; a page shared through fork goes back with its last owner), its host and device
+        lengths return to zero.  The other slots, and any captured graph (lengths are read on the device), are not touched."""
         for l in range(self.layer_num):
             if not self.preallocate:
                 for h in range(self.num_key_value_heads):
