@@ -230,6 +230,69 @@ int million_cache_fork(const million_fork_desc *desc, int32_t *page_ids, void *k
                        const int32_t *dst_slots /* (n_dst,) */, const int32_t *tail_ids /* (n_dst, layers, nh_k) or NULL */,
                        million_stream_t stream);
 
+/* Swap a request of a paged cache out of, or back into, its pages: ONE call (one launch) packs n_slots requests into contiguous
+ * blobs (PACK) or restores blobs into the pages the destination slots' table rows name (UNPACK), for the layers
+ * [layer0, layer0 + n_layers_call).  The cache arrays are those of the fork call above.  slot_table: device (n_slots, 4) int32
+ * {slot, T, r, start}; blob_offsets: device (n_slots,) int64, the byte offset in `blob` of each entry's row (layer0, kv head 0).
+ *
+ * Blob format, version 1.  T coded tokens, r window rows, ring start `start`; H = nh_k, n_live = ceil(T / page_size).  The rows
+ * of (layer, kv head) follow each other layer-major; each row is row_bytes = 2 * n_live * page_size * M + 4 * r * d bytes (a
+ * multiple of 16), so the row of (l, h) starts (l * H + h) * row_bytes behind the row of (0, 0) and a range of layers is one
+ * contiguous byte range.  A row holds, in this order:
+ *   K pages   n_live pages; page j is (page_size, M) uint8 row-major, the codes of tokens [j * page_size, (j + 1) * page_size);
+ *             rows of tokens >= T are zero;
+ *   V pages   n_live pages; page j is (M, page_size) uint8, transposed as the pool stores it; columns of tokens >= T are zero;
+ *   K window  r rows of d fp16 in ring order: blob row i is ring row (start + i) % resid_cap;
+ *   V window  the same.
+ * The blob is a function of the live data and `start` alone: pool bytes past T, table entries at or past n_live and ring rows
+ * outside [start, start + r) never reach it.
+ *
+ * Per entry - the table values are authoritative (dev_lengths is not read) and, like every device-resident value, not trusted:
+ *   T is clamped into [0, n_pages_bound * page_size], r into [0, resid_cap], a start outside [0, resid_cap) reads as 0; row_bytes
+ *     follows from the clamped values.
+ *   An entry takes no part when its slot lies outside [0, bs), when its offset is negative or no multiple of 16, when its
+ *     n_layers_call * H rows do not end at or before blob_bytes.
+ *   PACK reads the cache and writes only the blob: exactly the entry's n_layers_call * H * row_bytes bytes.  A page whose table
+ *     entry lies outside [0, n_pool) packs as zeros.
+ *   UNPACK writes both whole pages (page_size * M bytes) of every page j < n_live into the id the slot's table row holds - an id
+ *     outside [0, n_pool) is skipped -, window row i to ring position (start + i) % resid_cap of both windows (other ring rows
+ *     are not touched), and dev_lengths[l, slot] = {T, r, start, 0} for the layers of the call.  It never writes the table.
+ * No fault and no error for any of these: garbage never becomes an address.  Blob ranges of different entries, and (UNPACK) the
+ * ids of different rows and the slots of different entries, must not overlap: the bytes are then whatever write came last.
+ * Errors, all before any launch: null pointers (windows: only when resid_cap > 0), a bad struct_size or direction, a layer range
+ * not inside [0, n_layers), n_slots < 0, blob_bytes < 0 or n_pages_bound outside [0, n_pages_cap]: MILLION_ERR_ARG; the geometry
+ * the fork call refuses, or a task list (below) of 2^31 or more tasks: MILLION_ERR_SHAPE; pools, windows and blob 16-byte aligned, rows_layer_stride a multiple of 8,
+ * page_ids / dev_lengths / slot_table 4-byte and blob_offsets 8-byte aligned: MILLION_ERR_ALIGN otherwise.  n_slots = 0 returns
+ * MILLION_OK whatever the pointers.
+ * One launch on `stream`: 16-byte vector copies, the grid a function of the bounds alone (n_pages_bound pages and resid_cap window
+ * rows per (layer of the call, entry, kv head), one lengths task; one workgroup per task, at most 2^20 workgroups that then stride over the list).  The call allocates
+ * nothing, synchronises nothing, uses no atomics, flags or workspace. */
+enum {
+    MILLION_SWAP_PACK = 0,        /* cache -> blob */
+    MILLION_SWAP_UNPACK = 1       /* blob -> the pages the slots' table rows name, the windows, the lengths rows */
+};
+
+typedef struct {
+    uint32_t struct_size;         /* = sizeof(million_swap_desc) */
+    int32_t direction;            /* MILLION_SWAP_* */
+    int32_t n_layers, bs, nh_k, d, M, page_size;
+    int32_t n_pages_cap;          /* row length of page_ids */
+    int32_t n_pool;               /* pages in each pool */
+    int32_t resid_cap;            /* rows of the window buffers; 0: no window */
+    int32_t layer0, n_layers_call;/* the layers this call serves */
+    int64_t ids_layer_stride;     /* int32 between the layers of page_ids */
+    int64_t rows_layer_stride;    /* fp16 elements between the layers of k_resid / v_resid */
+    int64_t lengths_layer_stride; /* int32 between the layers of dev_lengths */
+    int64_t blob_bytes;           /* bytes of `blob`: an entry that does not fit takes no part */
+    int32_t n_slots;
+    int32_t n_pages_bound;        /* host bound of the pages a request can have, <= n_pages_cap: sizes the grid, clamps T */
+} million_swap_desc;
+
+int million_cache_swap(const million_swap_desc *desc, const int32_t *page_ids, void *k_pool, void *v_pool,
+                       void *k_resid, void *v_resid, int32_t *dev_lengths /* (layers, bs, 4) */,
+                       const int32_t *slot_table /* (n_slots, 4) */, const int64_t *blob_offsets /* (n_slots,) */,
+                       void *blob, million_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * PQ codebook training.
  * Replaces: train_pq (scripts/utils/pq_utils.py:586-609), which wraps faiss-cpu's IndexPQ.train: ProductQuantizer's default

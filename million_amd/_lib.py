@@ -81,6 +81,17 @@ class ForkDesc(ctypes.Structure):
                 ("src", c_i32), ("n_dst", c_i32), ("mode", c_i32), ("n_pages_bound", c_i32), ("prefix_tokens", c_i32)]
 
 
+MILLION_SWAP_PACK, MILLION_SWAP_UNPACK = 0, 1
+
+
+class SwapDesc(ctypes.Structure):
+    _fields_ = [("struct_size", c_u32), ("direction", c_i32), ("n_layers", c_i32), ("bs", c_i32), ("nh_k", c_i32), ("d", c_i32),
+                ("M", c_i32), ("page_size", c_i32), ("n_pages_cap", c_i32), ("n_pool", c_i32), ("resid_cap", c_i32),
+                ("layer0", c_i32), ("n_layers_call", c_i32),
+                ("ids_layer_stride", c_i64), ("rows_layer_stride", c_i64), ("lengths_layer_stride", c_i64), ("blob_bytes", c_i64),
+                ("n_slots", c_i32), ("n_pages_bound", c_i32)]
+
+
 class TrainDesc(ctypes.Structure):
     _fields_ = [("struct_size", c_u32), ("n", c_i32), ("d", c_i32), ("M", c_i32), ("C", c_i32), ("niter", c_i32),
                 ("x_is_f32", c_i32), ("x_stride_n", c_i64), ("eps", ctypes.c_float)]
@@ -112,6 +123,7 @@ SYMBOLS = {
     "million_pq_chunk_attn": (c_i32, [ctypes.POINTER(ChunkAttnDesc)] + [c_vp] * 13 + [c_sz, c_vp]),
     "million_pq_store_ragged": (c_i32, [ctypes.POINTER(StoreRaggedDesc)] + [c_vp] * 12),
     "million_cache_fork": (c_i32, [ctypes.POINTER(ForkDesc)] + [c_vp] * 9),
+    "million_cache_swap": (c_i32, [ctypes.POINTER(SwapDesc)] + [c_vp] * 10),
     "million_set_force_generic": (None, [c_i32]),
     "million_debug_set_stamp_buffer": (None, [c_vp]),
     "million_debug_bad_page_ids": (c_i32, []),

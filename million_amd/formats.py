@@ -93,3 +93,24 @@ def write_fvecs(filename, vecs, mode: str = "ab") -> None:
     rec[:, 1:] = vecs.astype("<f4")
     with open(filename, mode) as f:
         f.write(rec.tobytes())
+
+
+def save_request(path, snap) -> Path:
+    """One request of a PagedPQCache (pq_cache.RequestSnapshot: swap_out / snapshot_request) as one file: `torch.save` of a
+    dict {"blob": the 1-D uint8 tensor (blob format 1, include/million_hip.h), "meta": plain ints and strings}."""
+    meta = {str(k): (v if isinstance(v, str) else int(v)) for k, v in snap.meta.items()}
+    path = Path(path)
+    torch.save({"blob": snap.blob.detach().cpu().contiguous(), "meta": meta}, path)
+    return path
+
+
+def load_request(path):
+    """The RequestSnapshot save_request wrote.  Loaded with `weights_only=True` only, like the centroid files: nothing from
+    the file is executed; a file that holds anything but a tensor, ints and strings is refused."""
+    from .pq_cache import RequestSnapshot
+    obj = torch.load(Path(path), map_location="cpu", weights_only=True)
+    if (not isinstance(obj, dict) or set(obj) != {"blob", "meta"} or not isinstance(obj["blob"], torch.Tensor) or not isinstance(obj["meta"], dict)
+            or obj["blob"].dtype != torch.uint8 or obj["blob"].dim() != 1
+            or any(not isinstance(k, str) or isinstance(v, bool) or not isinstance(v, (int, str)) for k, v in obj["meta"].items())):
+        raise ValueError(f"{path}: expected {{'blob': 1-D uint8 tensor, 'meta': dict of ints and strings}}")
+    return RequestSnapshot(obj["blob"].contiguous(), obj["meta"])

@@ -294,6 +294,61 @@ def cache_fork(page_ids: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tenso
     _vshadow_drop(v_pool)
 
 
+def cache_swap_row_bytes(T: int, r: int, page_size: int, M: int, d: int) -> int:
+    """Bytes of one (layer, kv head) row of a request blob, format 1 (million_cache_swap): the K pages and the V pages of
+    ceil(T / page_size) pages, r window rows of d fp16 per side.  Always a multiple of 16."""
+    n_live = (int(T) + page_size - 1) // page_size
+    return 2 * n_live * page_size * M + 4 * int(r) * d
+
+
+def cache_swap(direction: int, page_ids: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_res: torch.Tensor,
+               v_res: torch.Tensor, dev_lengths: torch.Tensor, slot_table: torch.Tensor, blob_offsets: torch.Tensor,
+               blob: torch.Tensor, *, layer0: int = 0, n_layers: Optional[int] = None, n_pages_bound: Optional[int] = None) -> None:
+    """Pack requests into blobs (direction = L.MILLION_SWAP_PACK) or restore blobs into the pages the slots' table rows name
+    (L.MILLION_SWAP_UNPACK), for the layers [layer0, layer0 + n_layers) (default: from layer0 on), in one launch
+    (million_cache_swap).  The cache arrays are those of cache_fork; slot_table: device int32 (n_slots, 4) {slot, T, r, start};
+    blob_offsets: device int64 (n_slots,), the byte offset in `blob` (device uint8, 1-D) of each entry's first row of layer0.
+    n_pages_bound (default: the table's row length) bounds a request's pages: it sizes the grid and clamps T."""
+    _need_cuda(page_ids, k_pool, v_pool, k_res, v_res, dev_lengths, slot_table, blob_offsets, blob)
+    if direction not in (L.MILLION_SWAP_PACK, L.MILLION_SWAP_UNPACK):
+        raise RuntimeError("cache_swap: direction must be MILLION_SWAP_PACK or MILLION_SWAP_UNPACK")
+    if page_ids.dtype != torch.int32 or page_ids.dim() != 4 or page_ids[0].numel() and not page_ids[0].is_contiguous():
+        raise RuntimeError("cache_swap: int32 page_ids (layers, bs, nh_k, n_pages_cap), each layer contiguous, expected")
+    n_all, bs, nhk, cap_pages = page_ids.shape
+    if (k_pool.dtype != torch.uint8 or v_pool.dtype != torch.uint8 or k_pool.dim() != 3 or not k_pool.is_contiguous() or not v_pool.is_contiguous()
+            or v_pool.shape != (k_pool.shape[0], k_pool.shape[2], k_pool.shape[1])):
+        raise RuntimeError("cache_swap: contiguous uint8 pools (n_pool, page_size, M) and (n_pool, M, page_size) expected")
+    n_pool, page_size, M = k_pool.shape
+    if (k_res.dtype != torch.float16 or v_res.dtype != torch.float16 or k_res.dim() != 5 or k_res.shape != v_res.shape or k_res.stride() != v_res.stride()
+            or k_res.shape[:3] != (n_all, bs, nhk) or not k_res[0].is_contiguous()):
+        raise RuntimeError("cache_swap: fp16 windows (layers, bs, nh_k, cap, d), each layer contiguous, K and V alike, expected")
+    cap, d = k_res.shape[3], k_res.shape[4]
+    if dev_lengths.dtype != torch.int32 or dev_lengths.shape != (n_all, bs, 4) or not dev_lengths[0].is_contiguous():
+        raise RuntimeError("cache_swap: int32 dev_lengths (layers, bs, 4) expected")
+    if slot_table.dtype != torch.int32 or slot_table.dim() != 2 or slot_table.shape[1] != 4 or not slot_table.is_contiguous():
+        raise RuntimeError("cache_swap: slot_table must be contiguous int32 (n_slots, 4)")
+    n_slots = slot_table.shape[0]
+    if blob_offsets.dtype != torch.int64 or blob_offsets.shape != (n_slots,) or not blob_offsets.is_contiguous():
+        raise RuntimeError("cache_swap: blob_offsets must be contiguous int64 (n_slots,)")
+    if blob.dtype != torch.uint8 or blob.dim() != 1 or not blob.is_contiguous():
+        raise RuntimeError("cache_swap: blob must be a contiguous 1-D uint8 tensor")
+    desc = L.SwapDesc()
+    desc.struct_size = ctypes.sizeof(L.SwapDesc)
+    desc.direction = int(direction)
+    desc.n_layers, desc.bs, desc.nh_k, desc.d, desc.M, desc.page_size = n_all, bs, nhk, d, M, page_size
+    desc.n_pages_cap, desc.n_pool, desc.resid_cap = cap_pages, n_pool, cap
+    desc.layer0, desc.n_layers_call = int(layer0), n_all - int(layer0) if n_layers is None else int(n_layers)
+    desc.ids_layer_stride, desc.rows_layer_stride, desc.lengths_layer_stride = page_ids.stride(0), k_res.stride(0), dev_lengths.stride(0)
+    desc.blob_bytes = blob.numel()
+    desc.n_slots = n_slots
+    desc.n_pages_bound = cap_pages if n_pages_bound is None else int(n_pages_bound)
+    L.check(L.load().million_cache_swap(ctypes.byref(desc), page_ids.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(), k_res.data_ptr(),
+                                        v_res.data_ptr(), dev_lengths.data_ptr(), slot_table.data_ptr(), blob_offsets.data_ptr(),
+                                        blob.data_ptr(), _stream()), "million_cache_swap")
+    if direction == L.MILLION_SWAP_UNPACK:
+        _vshadow_drop(v_pool)
+
+
 def transpose_v_codes(v_codes: torch.Tensor, n_tokens: Optional[int] = None) -> torch.Tensor:
     """Row-major V codes (bs, nh_k, T, M) u8 -> dense transposed 64-token pages ((bs*nh_k)*ceil(T/64), M, 64)."""
     _need_cuda(v_codes)

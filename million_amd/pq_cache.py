@@ -371,6 +371,20 @@ class DynamicPQCache(_CacheBase):
         return sum(c.numel() * c.element_size() for c in self.key_residual_cache + self.value_residual_cache)
 
 
+SNAPSHOT_VERSION = 1
+_SNAPSHOT_GEOMETRY = ("layer_num", "nh_k", "d", "M", "nbits", "page_size", "resid_cap")
+
+
+class RequestSnapshot:
+    """One request of a PagedPQCache outside its pages (swap_out / swap_in, formats.save_request): `blob`, a 1-D uint8 host
+    tensor in blob format 1 (include/million_hip.h, million_cache_swap; pinned when it comes from swap_out), and `meta`, a dict
+    of plain ints and strings: "version", the geometry (layer_num, nh_k, d, M, nbits, page_size, resid_cap), the request (T
+    coded tokens, r window rows, ring start `start`, `seen` tokens) and the sha256 of the key and value codebook bytes."""
+
+    def __init__(self, blob: torch.Tensor, meta: Dict):
+        self.blob, self.meta = blob, dict(meta)
+
+
 class _PerLayer:
     """`cache._T[l]`-style access to a (layers, requests) host array: reading gives request 0's value (all requests move in
     lockstep unless slots are recycled, see PagedPQCache.release), writing sets every request of the layer."""
@@ -752,6 +766,12 @@ class PagedPQCache(_CacheBase):
             self._r_a[:, dsts] = self._rs_a[:, dsts] = 0
         self._pre_a[:, dsts] = 0
 
+    def _note_restored(self, b, meta):
+        """Slot b holds, in every layer, the request a snapshot describes (swap_in): T coded tokens, r window rows from ring
+        row `start` on, `seen` tokens in all.  Nothing of it is encoded ahead."""
+        self._T_a[:, b], self._r_a[:, b], self._rs_a[:, b], self._seen_a[:, b] = meta["T"], meta["r"], meta["start"], meta["seen"]
+        self._pre_a[:, b] = 0
+
     def fork(self, src, dst, n_tokens=None):
         """Slot(s) dst (one slot or a list) become a copy of slot src, in every layer and in ONE launch (ops.cache_fork): the
         codes, the residual window and the lengths - what prefill_request of the same prompt and the same decode steps would
@@ -833,6 +853,136 @@ class PagedPQCache(_CacheBase):
             self.lengths[l][b].zero_()
 
     reset_request = release
+
+    # ---- swap: a request leaves its pages for host memory and comes back ---------------------------------------------------
+    def _cent_digests(self):
+        """sha256 of the key and of the value codebook bytes; computed on first use, once per pair of codebook tensors."""
+        hit = getattr(self, "_cent_sha", None)
+        if hit is None or hit[0] is not self.key_cent or hit[1] is not self.value_cent:
+            import hashlib
+            sha = lambda t: hashlib.sha256(t.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes()).hexdigest()
+            k = sha(self.key_cent)
+            hit = self._cent_sha = (self.key_cent, self.value_cent, k, k if self.value_cent is self.key_cent else sha(self.value_cent))
+        return hit[2], hit[3]
+
+    def _swap_geometry(self) -> Dict:
+        return dict(layer_num=self.layer_num, nh_k=self.num_key_value_heads, d=self.d, M=self.M, nbits=self.nbits,
+                    page_size=self.page_size, resid_cap=self.extended_residual_size)
+
+    def _swap_ranges(self, layer_bytes, staging_bytes):
+        """[(layer0, n)]: the layers in ranges of at most staging_bytes, at least one layer each."""
+        per = max(1, int(staging_bytes) // max(layer_bytes, 1))
+        return [(l0, min(per, self.layer_num - l0)) for l0 in range(0, self.layer_num, per)]
+
+    def swap_out(self, b, release=True, staging_bytes=64 << 20):
+        """Slot(s) b (one slot or a list) as RequestSnapshot(s) in host memory: the codes, the residual window and the lengths
+        of every layer, packed by ONE launch per range of layers (ops.cache_swap) into a device staging buffer of at most
+        staging_bytes (at least one layer) and copied from there into a pinned blob, everything on the current stream.  The call
+        synchronises before it returns; release=True then releases the slot(s) - pages shared through fork stay with their
+        other owners.  swap_in() of the snapshot - into any empty slot of any cache of the same geometry and codebooks, on any
+        GPU, in any process (formats.save_request) - decodes on with the bits this slot would have produced.  Call it between
+        steps, as fork: the slot must be at the same lengths in every layer (its pending encode-ahead work is joined)."""
+        one = np.isscalar(b)
+        slots = [int(b)] if one else [int(x) for x in b]
+        nk, nl = self.num_key_value_heads, self.layer_num
+        if not slots or any(not 0 <= s < self.bs for s in slots) or len(set(slots)) != len(slots):
+            raise RuntimeError(f"swap_out: distinct slots inside [0, {self.bs}) expected")
+        for s in slots:
+            cols = (self._T_a[:, s], self._r_a[:, s], self._rs_a[:, s], self._seen_a[:, s])
+            if self._ahead is not None or any((c != c[0]).any() for c in cols):
+                raise RuntimeError(f"swap_out: slot {s} is mid-step (its layers are at different lengths); swap between steps")
+        for l in range(nl):
+            for s in slots:
+                self._join_side(l, s)
+        cuda = self.device.type == "cuda"
+        k_sha, v_sha = self._cent_digests()
+        snaps, rbs = [], []
+        for s in slots:
+            T, r, st = int(self._T_a[0, s]), int(self._r_a[0, s]), int(self._rs_a[0, s])
+            rb = ops.cache_swap_row_bytes(T, r, self.page_size, self.M, self.d)
+            meta = dict(version=SNAPSHOT_VERSION, **self._swap_geometry(), T=T, r=r, start=st, seen=int(self._seen_a[0, s]),
+                        key_cent_sha256=k_sha, value_cent_sha256=v_sha)
+            snaps.append(RequestSnapshot(torch.empty(nl * nk * rb, dtype=torch.uint8, pin_memory=cuda), meta))
+            rbs.append(rb)
+        table = torch.tensor([[s, sn.meta["T"], sn.meta["r"], sn.meta["start"]] for s, sn in zip(slots, snaps)], dtype=torch.int32).to(self.device)
+        layer_bytes = nk * sum(rbs)
+        n_live = max(-(-sn.meta["T"] // self.page_size) for sn in snaps)
+        ranges = self._swap_ranges(layer_bytes, staging_bytes)
+        staging = torch.empty(max(16, ranges[0][1] * layer_bytes), dtype=torch.uint8, device=self.device)
+        for l0, n in ranges:
+            offs = np.concatenate([[0], np.cumsum([n * nk * rb for rb in rbs])]).astype(np.int64)
+            ops.cache_swap(L.MILLION_SWAP_PACK, self._page_ids_all, self.key_page_pool, self.value_page_pool, self._kres_all, self._vres_all,
+                           self._lengths_all, table, torch.from_numpy(offs[:-1].copy()).to(self.device), staging, layer0=l0, n_layers=n,
+                           n_pages_bound=n_live)
+            for i, sn in enumerate(snaps):
+                sn.blob[l0 * nk * rbs[i]:(l0 + n) * nk * rbs[i]].copy_(staging[int(offs[i]):int(offs[i + 1])], non_blocking=True)
+        if cuda:
+            torch.cuda.current_stream().synchronize()
+        if release:
+            for s in slots:
+                self.release(s)
+        return snaps[0] if one else snaps
+
+    def snapshot_request(self, b):
+        """swap_out(b, release=False): the slot keeps decoding, the snapshot is what it holds now."""
+        return self.swap_out(b, release=False)
+
+    def swap_in(self, b, snap, check_codebooks=True, staging_bytes=64 << 20):
+        """Restore a RequestSnapshot into the empty slot b: paging on demand allocates private pages for it, a preallocated table
+        uses its fixed ids; the blob goes host to device into a staging buffer of at most staging_bytes (at least one layer) and
+        ONE launch per range of layers (ops.cache_swap) writes the pages, the window rows at their ring positions and the
+        device lengths rows.  Refused, before anything changes (RuntimeError): a slot that holds tokens, a snapshot of another
+        format version or geometry, more tokens than max_tokens, fewer free pages than the request needs (on demand), a blob of
+        the wrong size, and - unless check_codebooks=False - codebooks other than the ones the codes were made with."""
+        b = int(b)
+        meta, blob = snap.meta, snap.blob
+        nk, nl, ps = self.num_key_value_heads, self.layer_num, self.page_size
+        if not 0 <= b < self.bs:
+            raise RuntimeError(f"swap_in: slot {b} outside [0, {self.bs})")
+        if self._T_a[:, b].any() or self._r_a[:, b].any():
+            raise RuntimeError(f"swap_in: slot {b} holds tokens (release it first)")
+        if meta.get("version") != SNAPSHOT_VERSION:
+            raise RuntimeError(f"swap_in: snapshot format version {meta.get('version')}, this library reads {SNAPSHOT_VERSION}")
+        mine = self._swap_geometry()
+        for key in _SNAPSHOT_GEOMETRY:
+            if meta.get(key) != mine[key]:
+                raise RuntimeError(f"swap_in: the snapshot has {key}={meta.get(key)}, this cache {mine[key]}")
+        T, r, st, seen = (int(meta[key]) for key in ("T", "r", "start", "seen"))
+        cap = self.extended_residual_size
+        if T < 0 or not 0 <= r <= cap or not 0 <= st < max(cap, 1) or seen < 0:
+            raise RuntimeError(f"swap_in: inconsistent snapshot T={T} r={r} start={st} seen={seen}")
+        if T > self.max_tokens:
+            raise RuntimeError(f"swap_in: {T} tokens exceed max_tokens={self.max_tokens}")
+        rb = ops.cache_swap_row_bytes(T, r, ps, self.M, self.d)
+        if blob.dtype != torch.uint8 or blob.dim() != 1 or blob.numel() != nl * nk * rb:
+            raise RuntimeError(f"swap_in: a uint8 blob of {nl * nk * rb} bytes expected, got {blob.dtype} {tuple(blob.shape)}")
+        n_live = -(-T // ps)
+        if not self.preallocate:
+            pm = self.page_manager
+            returned = sum(len(self._host_pids[l][b][h]) for l in range(nl) for h in range(nk))
+            room = pm.max_pages - pm.current_active_pages if pm.max_pages is not None else nl * nk * n_live      # (allocate_pages grows the pool)
+            if len(pm.free_pages) + returned + room < nl * nk * n_live:
+                raise RuntimeError(f"swap_in: {nl * nk * n_live} free pages needed, {len(pm.free_pages) + returned + room} left")
+        if check_codebooks and (meta.get("key_cent_sha256"), meta.get("value_cent_sha256")) != self._cent_digests():
+            raise RuntimeError("swap_in: the snapshot's codes were made with other codebooks (check_codebooks=False restores it anyway)")
+        if not self.preallocate:
+            for l in range(nl):
+                for h in range(nk):
+                    for pid in self._host_pids[l][b][h]:      # pages of an empty slot hold no token
+                        self.page_manager.free_page(pid)
+                    self._host_pids[l][b][h] = []
+                self._pages_a[l, b] = 0
+            for l in range(nl):
+                self._assign_pages(l, n_live, b)
+        dev = torch.tensor([b, T, r, st], dtype=torch.int32).to(self.device)
+        table, offs = dev.view(1, 4), torch.zeros(1, dtype=torch.int64, device=self.device)
+        ranges = self._swap_ranges(nk * rb, staging_bytes)
+        staging = torch.empty(max(16, ranges[0][1] * nk * rb), dtype=torch.uint8, device=self.device)
+        for l0, n in ranges:
+            staging[:n * nk * rb].copy_(blob[l0 * nk * rb:(l0 + n) * nk * rb], non_blocking=True)
+            ops.cache_swap(L.MILLION_SWAP_UNPACK, self._page_ids_all, self.key_page_pool, self.value_page_pool, self._kres_all,
+                           self._vres_all, self._lengths_all, table, offs, staging, layer0=l0, n_layers=n, n_pages_bound=n_live)
+        self._note_restored(b, meta)
 
     def cleanup(self):
         """Reference PagedPQCache.cleanup (paged_pq_utils.py:1082-1118): drop every request's codes and window; the pools
