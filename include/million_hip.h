@@ -441,6 +441,24 @@ int million_pq_decode_attn_append(const million_attn_desc *desc, const void *q, 
                                   const void *v_cents_prepared, void *k_resid, void *v_resid, void *out,
                                   void *workspace, size_t workspace_bytes, million_stream_t stream);
 
+/* Log-sum-exp.  The _lse entries below return, beside `out`, the other half of each row's softmax state:
+ *   lse = ln sum_j exp(s_j),  s_j = q . k_j / sqrt(d),
+ * over exactly the keys the row's `out` is a softmax over: the codes below T, the live window rows, the appended row, the
+ * visible rows of the chunk.  Natural log, fp32.  Nothing to attend to: -inf (`out` is 0 there, as ever).  Where a split merge
+ * gave up and wrote NaN to `out` (million_debug_tail_faults), lse is NaN too.  lse is indexed like `out` without the d axis:
+ * decode (bs, nh), chunk (bs, nh, n_q) contiguous; the rows of a ragged chunk call past the request's dev_n_q get -inf
+ * (their `out` is zeros).  The kernels hold the maximum m in the scaled exp2 domain and the denominator l relative to it:
+ * lse = (m + log2 l) ln 2, l = 0 -> -inf, stored wherever `out` is stored by the lane or thread that already holds the two;
+ * `out` is bitwise what the entry without lse writes.  Two results over DISJOINT key sets combine with million_attn_merge.
+ *
+ * million_pq_decode_attn_lse: the arguments of million_pq_decode_attn_append plus float *lse (bs, nh) after out.
+ * k_new = v_new = NULL: no append (million_pq_decode_attn).  lse = NULL: MILLION_ERR_ARG. */
+int million_pq_decode_attn_lse(const million_attn_desc *desc, const void *q, const void *k_new, const void *v_new,
+                               const void *k_codes, const void *v_codes, const void *k_page_ids,
+                               const void *v_page_ids, const void *k_cents_prepared,
+                               const void *v_cents_prepared, void *k_resid, void *v_resid, void *out, float *lse,
+                               void *workspace, size_t workspace_bytes, million_stream_t stream);
+
 /* Row-major V codes (bs, nh_k, T, M) u8 (the reference's 10-argument layout, Interface.template.cu:30) -> the dense run
  * of transposed 64-token pages ((bs*nh_k) * ceil(T/64), M, 64) that the fast kernels read with v_pages_dense = 1,
  * page_size = 64, n_pages_cap = ceil(T/64).  Replaces the per-call pad + view + transpose + contiguous of
@@ -585,6 +603,36 @@ int million_pq_chunk_attn(const million_chunk_attn_desc *desc,
                           void *out,                    /* (bs, nh, n_q, d) fp16, strided */
                           void *workspace, size_t workspace_bytes,
                           million_stream_t stream);
+/* The same with the log-sum-exp of every query row ("Log-sum-exp" above): float *lse (bs, nh, n_q) contiguous, after out. */
+int million_pq_chunk_attn_lse(const million_chunk_attn_desc *desc, const void *q, const void *k_chunk, const void *v_chunk,
+                              const void *k_codes, const void *v_codes, const void *k_page_ids, const void *v_page_ids,
+                              const void *k_cents_prepared, const void *v_cents_prepared, const void *k_resid,
+                              const void *v_resid, void *out, float *lse, void *workspace, size_t workspace_bytes,
+                              million_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Merge of partial attentions: n_parts results (out_i, lse_i) of one query over disjoint key sets -> the result over
+ * their union.  Per row:  L = max_i lse_i,  w_i = exp(lse_i - L) (0 for -inf),  out = sum w_i out_i / sum w_i in fp32,
+ * rounded once to fp16,  lse_out = L + ln sum w_i.  Every part -inf: out = 0, lse_out = -inf.  A NaN lse_i: the row is NaN.
+ * Rows are (bs, nh, n_q) with per-tensor element strides (b, h, n), so a part may be a transposed view; a row's d fp16
+ * values are contiguous.  One launch, one thread per (row, 8 dims), 16-byte loads and stores: every out stride must be
+ * a multiple of 8 elements and every out pointer 16-byte aligned (MILLION_ERR_ALIGN).  `out` may be exactly one of the parts
+ * (same pointer and strides): a thread reads its 8 dims of every part before it writes.  Any other overlap is the caller's
+ * error; lse_out overlaps no part's lse (a row's lse is read by d / 8 threads).  lse_out may be NULL.  Validation precedes any
+ * HIP call. */
+#define MILLION_MERGE_MAX_PARTS 8
+typedef struct {
+    uint32_t struct_size;
+    int32_t  n_parts;              /* 1 .. MILLION_MERGE_MAX_PARTS */
+    int32_t  bs, nh, n_q;
+    int32_t  d;                    /* 64 or 128 */
+    int64_t  out_stride[MILLION_MERGE_MAX_PARTS][3];   /* per part: element strides (b, h, n) of its fp16 out rows */
+    int64_t  lse_stride[MILLION_MERGE_MAX_PARTS][3];   /* per part: element strides (b, h, n) of its fp32 lse */
+    int64_t  res_out_stride[3], res_lse_stride[3];     /* the same for the result */
+} million_attn_merge_desc;
+
+int million_attn_merge(const million_attn_merge_desc *desc, const void *const *part_outs, const float *const *part_lses,
+                       void *out, float *lse_out /* may be NULL */, million_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Residual-window append.

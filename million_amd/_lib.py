@@ -61,6 +61,15 @@ class ChunkAttnDesc(ctypes.Structure):
                 ("dev_lengths", c_vp), ("dev_n_q", c_vp)]
 
 
+MILLION_MERGE_MAX_PARTS = 8
+
+
+class AttnMergeDesc(ctypes.Structure):
+    _fields_ = [("struct_size", c_u32), ("n_parts", c_i32), ("bs", c_i32), ("nh", c_i32), ("n_q", c_i32), ("d", c_i32),
+                ("out_stride", c_i64 * 3 * MILLION_MERGE_MAX_PARTS), ("lse_stride", c_i64 * 3 * MILLION_MERGE_MAX_PARTS),
+                ("res_out_stride", c_i64 * 3), ("res_lse_stride", c_i64 * 3)]
+
+
 class StoreRaggedDesc(ctypes.Structure):
     _fields_ = [("struct_size", c_u32), ("bs", c_i32), ("nh_k", c_i32), ("d", c_i32), ("M", c_i32), ("C", c_i32),
                 ("n_bound", c_i32),
@@ -117,10 +126,14 @@ SYMBOLS = {
                                        c_vp, c_vp, c_vp, c_sz, c_vp]),
     "million_pq_decode_attn_append": (c_i32, [ctypes.POINTER(AttnDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                               c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "million_pq_decode_attn_lse": (c_i32, [ctypes.POINTER(AttnDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                           c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "million_attn_kernel_kind": (c_i32, [ctypes.POINTER(AttnDesc)]),
     "million_prefill_attn": (c_i32, [ctypes.POINTER(PrefillDesc), c_vp, c_vp, c_vp, c_vp, c_vp]),
     "million_chunk_attn_workspace_bytes": (c_sz, [ctypes.POINTER(ChunkAttnDesc)]),
     "million_pq_chunk_attn": (c_i32, [ctypes.POINTER(ChunkAttnDesc)] + [c_vp] * 13 + [c_sz, c_vp]),
+    "million_pq_chunk_attn_lse": (c_i32, [ctypes.POINTER(ChunkAttnDesc)] + [c_vp] * 14 + [c_sz, c_vp]),
+    "million_attn_merge": (c_i32, [ctypes.POINTER(AttnMergeDesc), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_vp, c_vp]),
     "million_pq_store_ragged": (c_i32, [ctypes.POINTER(StoreRaggedDesc)] + [c_vp] * 12),
     "million_cache_fork": (c_i32, [ctypes.POINTER(ForkDesc)] + [c_vp] * 9),
     "million_cache_swap": (c_i32, [ctypes.POINTER(SwapDesc)] + [c_vp] * 10),

@@ -41,6 +41,7 @@ __device__ __forceinline__ float block_reduce(float v, bool is_max, float *red) 
     return r;
 }
 
+template <bool LSE>      // common.h, "Log-sum-exp"
 __global__ __launch_bounds__(kGenBlock) void attn_generic_kernel(AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     MILLION_DEBUG_FILL_LDS(smem, p.lds_fill);
@@ -166,7 +167,7 @@ __global__ __launch_bounds__(kGenBlock) void attn_generic_kernel(AttnParams p) {
         __syncthreads();
     }
     __syncthreads();
-    publish_and_merge(p, b, hk, slot, part, lut, flag);   // the LUT region is dead: merge scratch
+    publish_and_merge<LSE>(p, b, hk, slot, part, lut, flag);   // the LUT region is dead: merge scratch
 }
 
 // Split policy: about one workgroup per CU over all (b, hk); a split is a multiple of 64 tokens and at
@@ -190,7 +191,8 @@ static void choose_splits(AttnParams &p, int min_tokens) {
 
 static void generic_setup() {
     if (device_once(0))
-        (void)hipFuncSetAttribute((const void *)attn_generic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        for (const void *k : {(const void *)attn_generic_kernel<false>, (const void *)attn_generic_kernel<true>})
+            (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
 int plan_attn_generic(const AttnParams &p_in, AttnPlan &plan) {
@@ -202,7 +204,7 @@ int plan_attn_generic(const AttnParams &p_in, AttnPlan &plan) {
     if (lds > 160 * 1024) { set_error("generic kernel: LUT of M*C=%d floats does not fit LDS", p.M * p.C); return MILLION_ERR_SHAPE; }
     choose_splits(p, 256);
     p.nslots = p.nsplit + 1;
-    plan = {(const void *)attn_generic_kernel, dim3(p.nslots, p.bs * p.nh_k), dim3(kGenBlock), lds, p, 0, generic_setup};
+    plan = {p.lse ? (const void *)attn_generic_kernel<true> : (const void *)attn_generic_kernel<false>, dim3(p.nslots, p.bs * p.nh_k), dim3(kGenBlock), lds, p, 0, generic_setup};
     return MILLION_OK;
 }
 

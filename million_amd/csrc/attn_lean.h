@@ -122,7 +122,7 @@ __device__ __forceinline__ void lean_load_res_tile(const AttnParams &p, int bh, 
 // FL: which run-time extras the instance carries (the BASELINE shapes' instances carry none: this code runs from a cold instruction
 // cache and every branch of its prologue is on the launch's critical path - 0.25 us per launch with both compiled in everywhere):
 //   1 = may be given 128 centroids (p.C): the LDS copy spreads the K rows;  2 = may run as query-head parts (AttnParams::nhk_real)
-template <int MODE, int MS = 64, int DD = 128, int DR = DD, int FL = 0>
+template <int MODE, int MS = 64, int DD = 128, int DR = DD, int FL = 0, bool LSE = false>      // LSE: common.h, "Log-sum-exp"
 __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
     static_assert((DD == 128 && (MS == 64 || MS == 32)) || (DD == 64 && (MS == 32 || MS == 16)), "lean kernel: d_m = 2 or 4 at d = 128 / 64");
     static_assert(DR == DD || (DR == 64 && DD == 128 && MS == 64), "lean kernel: the padded form is d = 64 / M = 64 only");
@@ -594,7 +594,7 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
             O.t[1][g] = 0.f;
         }
     }
-    merge_and_publish<MSTAG, false, DR>(p, smem, b, hk, split, G, tid, lane, wave, dbg_on, O, s_m, l_row, treq);
+    merge_and_publish<MSTAG, false, DR, LSE>(p, smem, b, hk, split, G, tid, lane, wave, dbg_on, O, s_m, l_row, treq);
 #undef STAMP
 }
 

@@ -182,11 +182,29 @@ static const void *const kMfmaKernels[kMfmaForms][3] = {
     {(const void *)attn_lean_kernel<0, 16, 64, 64, 3>, (const void *)attn_lean_kernel<1, 16, 64, 64, 3>, (const void *)attn_lean_kernel<2, 16, 64, 64, 3>},
     {(const void *)attn_lean_kernel<0, 64, 128, 64, 3>, (const void *)attn_lean_kernel<1, 64, 128, 64, 3>, (const void *)attn_lean_kernel<2, 64, 128, 64, 3>},
 };
+// the same instances with LSE = true (common.h, "Log-sum-exp"): behind the others in the code object
+static const void *const kMfmaKernelsLse[kMfmaForms][3] = {
+    {(const void *)attn_stream_kernel<64, 0, 8, true>, (const void *)attn_stream_kernel<64, 1, 8, true>, (const void *)attn_stream_kernel<64, 2, 8, true>},
+    {(const void *)attn_stream_kernel<32, 0, 8, true>, (const void *)attn_stream_kernel<32, 1, 8, true>, (const void *)attn_stream_kernel<32, 2, 8, true>},
+    {(const void *)attn_stream_kernel<320, 0, 8, true>, (const void *)attn_stream_kernel<320, 1, 8, true>, (const void *)attn_stream_kernel<320, 2, 8, true>},
+    {(const void *)attn_stream_kernel<16, 0, 8, true>, (const void *)attn_stream_kernel<16, 1, 8, true>, (const void *)attn_stream_kernel<16, 2, 8, true>},
+    MFMA_ONE(attn_stream_kernel<16, 2, 7, true>),
+    MFMA_ONE(attn_stream_kernel<64, 2, 7, true>),
+    MFMA_ONE(attn_stream_kernel<32, 2, 7, true>),
+    {(const void *)attn_lean_kernel<0, 64, 128, 128, 0, true>, (const void *)attn_lean_kernel<1, 64, 128, 128, 0, true>, (const void *)attn_lean_kernel<2, 64, 128, 128, 0, true>},
+    MFMA_ONE(attn_lean_kernel<2, 64, 128, 128, 1, true>),
+    {(const void *)attn_lean_kernel<0, 32, 128, 128, 0, true>, (const void *)attn_lean_kernel<1, 32, 128, 128, 0, true>, (const void *)attn_lean_kernel<2, 32, 128, 128, 0, true>},
+    MFMA_ONE(attn_lean_kernel<2, 32, 128, 128, 1, true>),
+    {(const void *)attn_lean_kernel<0, 32, 64, 64, 3, true>, (const void *)attn_lean_kernel<1, 32, 64, 64, 3, true>, (const void *)attn_lean_kernel<2, 32, 64, 64, 3, true>},
+    {(const void *)attn_lean_kernel<0, 16, 64, 64, 3, true>, (const void *)attn_lean_kernel<1, 16, 64, 64, 3, true>, (const void *)attn_lean_kernel<2, 16, 64, 64, 3, true>},
+    {(const void *)attn_lean_kernel<0, 64, 128, 64, 3, true>, (const void *)attn_lean_kernel<1, 64, 128, 64, 3, true>, (const void *)attn_lean_kernel<2, 64, 128, 64, 3, true>},
+};
 #undef MFMA_ONE
 static void mfma_setup() {
     if (device_once(1))
-        for (const auto &form : kMfmaKernels)
-            for (const void *k : form) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
+        for (const auto *tab : {kMfmaKernels, kMfmaKernelsLse})
+            for (int f = 0; f < kMfmaForms; ++f)
+                for (const void *k : tab[f]) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
 }
 
 bool plan_attn_mfma(const AttnParams &p_in, AttnPlan &plan) {
@@ -226,7 +244,7 @@ bool plan_attn_mfma(const AttnParams &p_in, AttnPlan &plan) {
 #if MILLION_EXP & 2
     p.nmerge = 1;      // A/B: the primary alone
 #endif
-    plan = {kMfmaKernels[form][mode], dim3(ns, bh), dim3(kNW * 64), kLdsBytes, p, 1, mfma_setup};
+    plan = {(p.lse ? kMfmaKernelsLse : kMfmaKernels)[form][mode], dim3(ns, bh), dim3(kNW * 64), kLdsBytes, p, 1, mfma_setup};
     return true;
 }
 

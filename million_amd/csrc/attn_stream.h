@@ -236,7 +236,7 @@ __device__ __forceinline__ void st_vstep(const unsigned (&e)[2][8], const unsign
     v_step(e[1], Ps, O[1]);      // dims 4m + 2, 3
 }
 
-template <int MSX, int MODE, int CL2 = 8>      // MSX = M, or 320 = M 32 in the d_m = 4 form
+template <int MSX, int MODE, int CL2 = 8, bool LSE = false>      // MSX = M, or 320 = M 32 in the d_m = 4 form; LSE: common.h, "Log-sum-exp"
 __global__ __launch_bounds__(kNW * 64, 2) void attn_stream_kernel(AttnParams p) {
     constexpr int MS = MSX == 320 ? 32 : MSX;
     constexpr bool D4 = MSX == 320;            // M = 32, d_m = 4 form (see "d_m = 4 form", decode_wave.h): G <= 4, replicated query heads
@@ -602,6 +602,6 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_stream_kernel(AttnParams p) 
     if (sink == 0x9e3779b9u) sr.l += 1.f;      // never: keeps the sink (and the loads behind it) alive
 #endif
     STAMP(3);
-    merge_and_publish<MSX, PV>(p, smem, b, hk, split, G, tid, lane, wave, dbg_on, O, sr.m, sr.l, treq);
+    merge_and_publish<MSX, PV, 128, LSE>(p, smem, b, hk, split, G, tid, lane, wave, dbg_on, O, sr.m, sr.l, treq);
 #undef STAMP
 }

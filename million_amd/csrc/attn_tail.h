@@ -113,7 +113,7 @@ __device__ unsigned g_tail_faults = 0;
 // summed with DPP / row swaps.  (A two-heads-per-pass variant - both heads' loads in flight before the first reduction - paid
 // when ONE workgroup merged every head; with the helpers back each merger has one head per wave group and the second
 // instantiation only made the cold tail longer.)
-template <int DD = 128>      // DD = d: rows of 64 dims (lean kernel, d = 64) keep two of the four waves of a head busy
+template <int DD = 128, bool LSE = false>      // DD = d: rows of 64 dims (lean kernel, d = 64) keep two of the four waves of a head busy
 __device__ __forceinline__ void tail_merge_head(const AttnParams &p, int b, int hk, int g, int part, int ns, const float *src, int lane,
                                                 bool fault) {
     if (32 * part >= DD) return;      // wave-uniform
@@ -161,9 +161,12 @@ __device__ __forceinline__ void tail_merge_head(const AttnParams &p, int b, int 
         const h4 o = {(f16)acc[0], (f16)acc[1], (f16)acc[2], (f16)acc[3]};
         *(h4 *)(p.out + ((long long)b * p.nh + head0(p, hk) + g) * DD + 32 * part + 4 * q8) = o;
     }
+    // the head's lse from the maximum and the denominator every lane of this wave holds: one lane of the wave that owns the head's
+    // first 32 dims; a merge that gave up: NaN, like `out`
+    if constexpr (LSE) { if (part == 0 && lane == 0) store_lse(p, b, hk, g, fault ? __builtin_nanf("") : lse_of(ms_, den)); }
 }
 
-template <int MS = 64, bool PV = false, int DD = 128, class ACC>
+template <int MS = 64, bool PV = false, int DD = 128, bool LSE = false, class ACC>
 __device__ __forceinline__ void merge_and_publish(const AttnParams &p, char *smem, int b, int hk, int split, int G, int tid,
                                                   int lane, int wave, bool dbg_on, ACC &O, float m_run, float l_run, TailReq &treq) {
 #define STAMP(i) stamp_lds(dbg_on, lane, wave, i)
@@ -283,6 +286,7 @@ __device__ __forceinline__ void merge_and_publish(const AttnParams &p, char *sme
                 typedef f16 h4 __attribute__((ext_vector_type(4)));
                 const h4 o = {(f16)(acc[0] * inv), (f16)(acc[1] * inv), (f16)(acc[2] * inv), (f16)(acc[3] * inv)};
                 *(h4 *)(p.out + ((long long)b * p.nh + head0(p, hk)) * DD + 4 * q) = o;
+                if constexpr (LSE) { if (q % (DD / 4) == 0) store_lse(p, b, hk, g, lse_of(Ms, lsum)); }      // the head's first thread
             } else if (same_xcd) {
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, acc), rsrc, q * 16, 0, 0);
                 if (q % (DD / 4) == 0) {      // (a slot is laid out for p.G heads: the last part of an odd head group holds fewer, G < p.G)
@@ -400,7 +404,7 @@ __device__ __forceinline__ void merge_and_publish(const AttnParams &p, char *sme
                 if (state == 3) break;
                 if (__builtin_expect(state == 2, 0) && lane == 0) atomicAdd(&g_tail_faults, 1u);      // this wave's outputs are written as NaN
             }
-            tail_merge_head<DD>(p, b, hk, g, wave & 3, ns, src, lane, state == 2);
+            tail_merge_head<DD, LSE>(p, b, hk, g, wave & 3, ns, src, lane, state == 2);
         }
         // the primary also merges the heads of the helpers that gave up before it took its index (bits of its own ticket):
         // heads h, h + nm, ... of helper h, the same four-waves-per-head split
@@ -419,7 +423,7 @@ __device__ __forceinline__ void merge_and_publish(const AttnParams &p, char *sme
             for (int h = 0; h < nm - 1; ++h)
                 if (gave >> h & 1u)
                     for (int g = h; g < G; g += nm) {
-                        if ((pos & 1) == (wave >> 2)) tail_merge_head<DD>(p, b, hk, g, wave & 3, ns, src, lane, state == 2);
+                        if ((pos & 1) == (wave >> 2)) tail_merge_head<DD, LSE>(p, b, hk, g, wave & 3, ns, src, lane, state == 2);
                         ++pos;
                     }
         }

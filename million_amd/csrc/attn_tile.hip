@@ -69,7 +69,7 @@ __device__ __forceinline__ void lds_phase() {      // LDS writes of this wave be
     asm volatile("" ::: "memory");
 }
 
-template <int D, int DM, int TW>
+template <int D, int DM, int TW, bool LSE = false>      // LSE: common.h, "Log-sum-exp"
 __global__ __launch_bounds__(TW * 64, TW / 4) void attn_tile_kernel(AttnParams p) {
     constexpr int kTW = TW;
     constexpr int M = D / DM;
@@ -431,7 +431,7 @@ __global__ __launch_bounds__(TW * 64, TW / 4) void attn_tile_kernel(AttnParams p
         __syncthreads();
     }
     // merge scratch of the last arriver: the waves' partials above are dead once `part` is complete (barrier above)
-    publish_and_merge(p, b, hk, slot, part, (float *)smem, flag);
+    publish_and_merge<LSE>(p, b, hk, slot, part, (float *)smem, flag);
 }
 
 // The instances, by d (128, 64) and M (16, 32, 64)
@@ -439,10 +439,15 @@ static const void *const kTileKernels[2][3] = {
     {(const void *)attn_tile_kernel<128, 8, 16>, (const void *)attn_tile_kernel<128, 4, 8>, (const void *)attn_tile_kernel<128, 2, 8>},
     {(const void *)attn_tile_kernel<64, 4, 16>, (const void *)attn_tile_kernel<64, 2, 16>, (const void *)attn_tile_kernel<64, 1, 16>},
 };
+static const void *const kTileKernelsLse[2][3] = {      // LSE = true (common.h, "Log-sum-exp")
+    {(const void *)attn_tile_kernel<128, 8, 16, true>, (const void *)attn_tile_kernel<128, 4, 8, true>, (const void *)attn_tile_kernel<128, 2, 8, true>},
+    {(const void *)attn_tile_kernel<64, 4, 16, true>, (const void *)attn_tile_kernel<64, 2, 16, true>, (const void *)attn_tile_kernel<64, 1, 16, true>},
+};
 static void tile_setup() {
     if (device_once(2))
-        for (const auto &d : kTileKernels)
-            for (const void *k : d) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        for (const auto *tab : {kTileKernels, kTileKernelsLse})
+            for (int i = 0; i < 2; ++i)
+                for (const void *k : tab[i]) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 }
 
 bool plan_attn_tile(const AttnParams &p_in, AttnPlan &plan) {
@@ -473,7 +478,7 @@ bool plan_attn_tile(const AttnParams &p_in, AttnPlan &plan) {
     p.split_len = len;
     p.nslots = ns + 1;
     const size_t lds = tile_lds_bytes(p.d, p.C, p.slot_floats, waves, p.G);
-    plan = {kTileKernels[p.d == 64][p.M == 16 ? 0 : p.M == 32 ? 1 : 2], dim3(p.nslots, bh), dim3(waves * 64), lds, p, 3, tile_setup};
+    plan = {(p.lse ? kTileKernelsLse : kTileKernels)[p.d == 64][p.M == 16 ? 0 : p.M == 32 ? 1 : 2], dim3(p.nslots, bh), dim3(waves * 64), lds, p, 3, tile_setup};
     return true;
 }
 

@@ -62,6 +62,8 @@ struct ChunkParams {
     float scale_log2e;
     const int *dev_lengths;                   // RAGGED: (bs, 4) {T, r, resid_start, ticket} per request, or null (host T / r / rs)
     const int *dev_n_q;                       // RAGGED: (bs,) valid query rows per request, or null (n_q)
+    float *lse;                               // LSE instances: (bs, nh, n_q) fp32 log-sum-exp of each row's visible scores (million_hip.h); last, so
+                                              // that no other argument moves: the instances without it are the code they were
 #ifdef MILLION_DEBUG_CHECK_IDS
     int lds_fill;                             // dynamic LDS bytes of the launch: debug_fill_lds (common.h)
 #endif
@@ -140,11 +142,16 @@ __device__ __forceinline__ int ca_load_n_q(const ChunkParams &p, int b) {
     const int n = p.dev_n_q[b];
     return n < 0 ? 0 : (n > p.n_q ? p.n_q : n);
 }
+// the log-sum-exp slot of query row qi of head `head`: indexed like out without the d axis, contiguous
+__device__ __forceinline__ float *ca_lse_at(const ChunkParams &p, int b, int head, int qi) {
+    return p.lse + ((long long)b * p.nh + head) * p.n_q + qi;
+}
 
 // RAGGED: T, r, resid_start (dev_lengths) and the valid query rows (dev_n_q) are per request, read on the device; the grid,
 // the split count S and the workspace rows are those of the bounds p.T / p.n_q.  A request's tiles are cut into the same S
 // ranges, so a range may be empty: such a split writes m = -inf, l = 0, which the merge skips.
-template <int D, int DM, bool RAGGED>
+// LSE: the instances that also store every row's log-sum-exp (common.h, "Log-sum-exp"); the others are the kernel without it
+template <int D, int DM, bool RAGGED, bool LSE>
 __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(ChunkParams p) {
     constexpr int DS = D / 16;                    // k-steps of the score product
     constexpr int NB = D / 32;                    // 32-row blocks of O^T
@@ -296,12 +303,15 @@ __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(ChunkParams p) 
         if (p.S == 1 && rho < p.nrows) {
             const int qz = rho / p.G;
             flash_store_zero_row<NB>(p.out + b * p.o_sb + (hk * p.G + (rho - qz * p.G)) * p.o_sh + (long long)qz * p.o_sn, hh);
+            if constexpr (LSE) if (hh == 0) *ca_lse_at(p, b, hk * p.G + (rho - qz * p.G), qz) = -INFINITY;
         }
         return;
     }
     if (!wave_live || rho >= p.nrows) return;
     if (p.S == 1) {
         flash_store_row(O, l_run, p.out + b * p.o_sb + head * p.o_sh + (long long)qi * p.o_sn, hh);
+        // both half-waves hold the row's m and total l; a row without a visible key: m = -inf, l = 0
+        if constexpr (LSE) if (hh == 0) *ca_lse_at(p, b, head, qi) = lse_of(m_run > -INFINITY ? m_run : 0.f, l_run);
         return;
     }
     const long long wrow = (((long long)b * p.nh_k + hk) * p.S + s) * p.nrows + rho;
@@ -322,7 +332,7 @@ __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(ChunkParams p) 
 }
 
 // ---- merge of the splits: one thread per (row, 8 dims) ----
-template <int D, bool RAGGED>
+template <int D, bool RAGGED, bool LSE>
 __global__ __launch_bounds__(256) void chunk_merge_kernel(ChunkParams p) {
     constexpr int TPR = D / 8;
     const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -337,6 +347,7 @@ __global__ __launch_bounds__(256) void chunk_merge_kernel(ChunkParams p) {
         const int qz = rho / p.G;
         const h8 z = {(f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f};
         *(h8 *)(p.out + b * p.o_sb + (hk * p.G + (rho - qz * p.G)) * p.o_sh + (long long)qz * p.o_sn + 8 * part) = z;
+        if constexpr (LSE) if (part == 0) *ca_lse_at(p, b, hk * p.G + (rho - qz * p.G), qz) = -INFINITY;
         return;
     }
     float mx = -INFINITY;
@@ -362,33 +373,43 @@ __global__ __launch_bounds__(256) void chunk_merge_kernel(ChunkParams p) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = (f16)(acc[e] * inv);
     *(h8 *)(p.out + b * p.o_sb + head * p.o_sh + (long long)qi * p.o_sn + 8 * part) = v;
+    if constexpr (LSE) if (part == 0) *ca_lse_at(p, b, head, qi) = lse_of(mx > -INFINITY ? mx : 0.f, L);
 }
 
 constexpr int kChunkTargetWGs = 256;     // one workgroup per MI355X CU (the LDS budget at C = 256 admits one)
 constexpr int kChunkMaxSplits = 64;
 
-template <int D, int DM, bool RAGGED>
+template <int D, int DM, bool RAGGED, bool LSE>
 void launch_chunk_r(const ChunkParams &p, long long blocks, int lds, hipStream_t s) {
 #ifdef MILLION_DEBUG_CHECK_IDS
     ChunkParams pf = p;
     pf.lds_fill = lds;      // debug_fill_lds (common.h)
-    hipLaunchKernelGGL((chunk_attn_kernel<D, DM, RAGGED>), dim3((unsigned)blocks), dim3(kThreads), lds, s, pf);
+    hipLaunchKernelGGL((chunk_attn_kernel<D, DM, RAGGED, LSE>), dim3((unsigned)blocks), dim3(kThreads), lds, s, pf);
 #else
-    hipLaunchKernelGGL((chunk_attn_kernel<D, DM, RAGGED>), dim3((unsigned)blocks), dim3(kThreads), lds, s, p);
+    hipLaunchKernelGGL((chunk_attn_kernel<D, DM, RAGGED, LSE>), dim3((unsigned)blocks), dim3(kThreads), lds, s, p);
 #endif
 }
 template <int D, int DM>
 void launch_chunk_t(const ChunkParams &p, long long blocks, int lds, hipStream_t s) {
-    if (p.dev_lengths || p.dev_n_q) launch_chunk_r<D, DM, true>(p, blocks, lds, s);
-    else launch_chunk_r<D, DM, false>(p, blocks, lds, s);
+    const bool ragged = p.dev_lengths || p.dev_n_q;
+    if (p.lse) { if (ragged) launch_chunk_r<D, DM, true, true>(p, blocks, lds, s); else launch_chunk_r<D, DM, false, true>(p, blocks, lds, s); }
+    else if (ragged) launch_chunk_r<D, DM, true, false>(p, blocks, lds, s);
+    else launch_chunk_r<D, DM, false, false>(p, blocks, lds, s);
+}
+template <int D, bool RAGGED>
+void launch_chunk_merge(const ChunkParams &p, long long mblocks, hipStream_t s) {
+    if (p.lse) hipLaunchKernelGGL((chunk_merge_kernel<D, RAGGED, true>), dim3((unsigned)mblocks), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((chunk_merge_kernel<D, RAGGED, false>), dim3((unsigned)mblocks), dim3(256), 0, s, p);
 }
 
 void chunk_attrs_once() {
     if (!device_once(4)) return;
     const int mx = 160 * 1024;
 #define CA_ATTR(D, DM)                                                                                                          \
-    (void)hipFuncSetAttribute((const void *)chunk_attn_kernel<D, DM, false>, hipFuncAttributeMaxDynamicSharedMemorySize, mx); \
-    (void)hipFuncSetAttribute((const void *)chunk_attn_kernel<D, DM, true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx)
+    (void)hipFuncSetAttribute((const void *)chunk_attn_kernel<D, DM, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, mx); \
+    (void)hipFuncSetAttribute((const void *)chunk_attn_kernel<D, DM, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);  \
+    (void)hipFuncSetAttribute((const void *)chunk_attn_kernel<D, DM, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);  \
+    (void)hipFuncSetAttribute((const void *)chunk_attn_kernel<D, DM, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, mx)
     CA_ATTR(128, 2); CA_ATTR(128, 4); CA_ATTR(128, 8); CA_ATTR(64, 1); CA_ATTR(64, 2); CA_ATTR(64, 4);
 #undef CA_ATTR
 }
@@ -429,11 +450,11 @@ extern "C" size_t million_chunk_attn_workspace_bytes(const million_chunk_attn_de
     return chunk_geometry(desc, n_qb, S, ws) ? ws : 0;
 }
 
-extern "C" int million_pq_chunk_attn(const million_chunk_attn_desc *desc, const void *q, const void *k_chunk, const void *v_chunk,
-                                     const void *k_codes, const void *v_codes, const void *k_page_ids, const void *v_page_ids,
-                                     const void *k_cents_prepared, const void *v_cents_prepared, const void *k_resid,
-                                     const void *v_resid, void *out, void *workspace, size_t workspace_bytes,
-                                     million_stream_t stream) {
+static int chunk_attn_impl(const million_chunk_attn_desc *desc, const void *q, const void *k_chunk, const void *v_chunk,
+                           const void *k_codes, const void *v_codes, const void *k_page_ids, const void *v_page_ids,
+                           const void *k_cents_prepared, const void *v_cents_prepared, const void *k_resid,
+                           const void *v_resid, void *out, float *lse, void *workspace, size_t workspace_bytes,
+                           million_stream_t stream) {
     if (!desc || desc->struct_size != sizeof(million_chunk_attn_desc)) { set_error("chunk_attn: bad desc / struct_size"); return MILLION_ERR_ARG; }
     const million_chunk_attn_desc &d = *desc;
     if (d.bs <= 0 || d.nh <= 0 || d.nh_k <= 0 || d.nh % d.nh_k) { set_error("chunk_attn: bs=%d nh=%d nh_k=%d", d.bs, d.nh, d.nh_k); return MILLION_ERR_SHAPE; }
@@ -496,6 +517,7 @@ extern "C" int million_pq_chunk_attn(const million_chunk_attn_desc *desc, const 
     p.ktab = (const f16 *)k_cents_prepared; p.vtab = (const f16 *)v_cents_prepared;
     p.kres = (const f16 *)k_resid; p.vres = (const f16 *)v_resid;
     p.out = (f16 *)out;
+    p.lse = lse;
     p.bs = d.bs; p.nh = d.nh; p.nh_k = d.nh_k; p.G = d.nh / d.nh_k; p.M = d.M; p.C = d.C;
     p.n_q = d.n_q; p.n_c = d.n_c; p.T = d.n_tokens; p.rcap = d.resid_cap;
     p.r = dev_len ? 0 : d.r;
@@ -539,12 +561,32 @@ extern "C" int million_pq_chunk_attn(const million_chunk_attn_desc *desc, const 
         const long long threads = (long long)d.bs * d.nh_k * p.nrows * (d.d / 8);
         const long long mblocks = (threads + 255) / 256;
         const bool ragged = p.dev_lengths || p.dev_n_q;
-        if (d.d == 128 && ragged) hipLaunchKernelGGL((chunk_merge_kernel<128, true>), dim3((unsigned)mblocks), dim3(256), 0, s, p);
-        else if (d.d == 128) hipLaunchKernelGGL((chunk_merge_kernel<128, false>), dim3((unsigned)mblocks), dim3(256), 0, s, p);
-        else if (ragged) hipLaunchKernelGGL((chunk_merge_kernel<64, true>), dim3((unsigned)mblocks), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((chunk_merge_kernel<64, false>), dim3((unsigned)mblocks), dim3(256), 0, s, p);
+        if (d.d == 128 && ragged) launch_chunk_merge<128, true>(p, mblocks, s);
+        else if (d.d == 128) launch_chunk_merge<128, false>(p, mblocks, s);
+        else if (ragged) launch_chunk_merge<64, true>(p, mblocks, s);
+        else launch_chunk_merge<64, false>(p, mblocks, s);
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("chunk_attn launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
     return MILLION_OK;
+}
+
+extern "C" int million_pq_chunk_attn(const million_chunk_attn_desc *desc, const void *q, const void *k_chunk, const void *v_chunk,
+                                     const void *k_codes, const void *v_codes, const void *k_page_ids, const void *v_page_ids,
+                                     const void *k_cents_prepared, const void *v_cents_prepared, const void *k_resid,
+                                     const void *v_resid, void *out, void *workspace, size_t workspace_bytes,
+                                     million_stream_t stream) {
+    return chunk_attn_impl(desc, q, k_chunk, v_chunk, k_codes, v_codes, k_page_ids, v_page_ids, k_cents_prepared, v_cents_prepared,
+                           k_resid, v_resid, out, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int million_pq_chunk_attn_lse(const million_chunk_attn_desc *desc, const void *q, const void *k_chunk, const void *v_chunk,
+                                         const void *k_codes, const void *v_codes, const void *k_page_ids, const void *v_page_ids,
+                                         const void *k_cents_prepared, const void *v_cents_prepared, const void *k_resid,
+                                         const void *v_resid, void *out, float *lse, void *workspace, size_t workspace_bytes,
+                                         million_stream_t stream) {
+    if (!lse) { set_error("chunk_attn_lse: lse null"); return MILLION_ERR_ARG; }
+    if ((uintptr_t)lse & 3) { set_error("chunk_attn_lse: lse must be 4-byte aligned"); return MILLION_ERR_ALIGN; }
+    return chunk_attn_impl(desc, q, k_chunk, v_chunk, k_codes, v_codes, k_page_ids, v_page_ids, k_cents_prepared, v_cents_prepared,
+                           k_resid, v_resid, out, lse, workspace, workspace_bytes, stream);
 }

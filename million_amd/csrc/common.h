@@ -79,6 +79,8 @@ struct AttnParams {
     unsigned long long *dbg;   // diagnostic stamp buffer (million_debug_set_stamp_buffer), normally null
     int k_pool_pages, v_pool_pages;   // pages in the pools (0 = not given): read only under MILLION_DEBUG_CHECK_IDS
     int *bad_ids;                     // MILLION_DEBUG_CHECK_IDS: device counter of out-of-range page ids, else null
+    float *lse;                       // (bs, nh) fp32 log-sum-exp of each head's scores, natural log, or null (million_hip.h).  Read by the
+                                      // LSE instances of the kernels only: a call without it launches the instances it always did
 #ifdef MILLION_DEBUG_CHECK_IDS
     int lds_fill;                     // dynamic LDS bytes of the launch: debug_fill_lds below
 #endif
@@ -174,6 +176,20 @@ __device__ __forceinline__ int head0(const AttnParams &p, int hk) {
     const int part = head_part(p, hk);
     return (hk - part * p.nhk_mul) * p.Gt + p.g0 + part * p.G;
 }
+// Log-sum-exp (million_hip.h).  Every kernel is instantiated twice, LSE = false / true: the true instances also store each head's
+// lse where they store its `out`, from the maximum and the denominator the storing code already holds; the false instances are
+// the kernels as they were, instruction for instruction - the decode kernels have no scalar register to spare, and a pointer
+// carried across their loops (or parked in LDS and fetched in the tail: both were built) moved the register allocation of almost
+// every instance into more SGPR spills.  The planners pick the table by p.lse.
+// A head's lse from its maximum m (scaled exp2 domain; 0 stands in for -inf) and its denominator l relative to m:
+// ln sum_j exp(s_j) = (m + log2 l) ln 2; nothing to attend to (l = 0): -inf
+__device__ __forceinline__ float lse_of(float m, float l) {
+    return l > 0.f ? (m + __log2f(l)) * 0.6931471805599453f : -INFINITY;
+}
+// indexed like out without the d axis: right for query-head parts, for the later launches of a big group (g0) and for a last part
+__device__ __forceinline__ void store_lse(const AttnParams &p, int b, int hk, int g, float v) {
+    p.lse[(long long)b * p.nh + head0(p, hk) + g] = v;
+}
 
 // Device-resident lengths are not trusted: T is clamped to the host bound the grid was sized for, r to the window
 // capacity (minus the row a fused append is about to add), the ring start to [0, cap).  Out-of-range values become a
@@ -241,7 +257,7 @@ typedef float mv4f __attribute__((ext_vector_type(4)));
 // AUX = cache-policy bits of the loads of handed-off bytes: 16 (sc1, agent scope).  (Round 2 switched to sc0 loads when
 // the ticket said every producer had run on the merger's XCD; an sc0 load may be served by the CU's L1, which nothing
 // refreshes - tools/micro/l2_handoff.hip shows polls with sc0 loads never seeing a later store - so that path is gone.)
-template <int G_, int AUX, int kThreads = 512, int kD = 128>
+template <int G_, int AUX, int kThreads = 512, int kD = 128, bool LSE = false>
 __device__ __forceinline__ void merge_vec4(const AttnParams &p, int b, int hk, const float *src, int ns, float *scratch) {
     constexpr int nq = G_ * kD / 4;            // float4 groups of the output
     constexpr int nsg = kThreads / nq;         // slot subsets = threads per group
@@ -273,6 +289,7 @@ __device__ __forceinline__ void merge_vec4(const AttnParams &p, int b, int hk, c
             const float den = wave_sum(w0 * l0);
             const float inv = den > 0.f ? 1.0f / den : 0.f;
             if (on) scratch[lane * G_ + gg] = w0 * inv;
+            if constexpr (LSE) { if (lane == 0) store_lse(p, b, hk, gg, lse_of(ms_, den)); }
         }
     }
     __syncthreads();
@@ -301,16 +318,19 @@ __device__ __forceinline__ void merge_vec4(const AttnParams &p, int b, int hk, c
 __device__ __forceinline__ float *slot_ptr(const AttnParams &p, int b, int hk, int slot) {
     return p.ws_part + ((long long)(b * p.nh_k + hk) * p.nslots + slot) * p.slot_floats;
 }
+template <bool LSE = false>
 __device__ __forceinline__ void ticket_and_merge(const AttnParams &p, int b, int hk, float *scratch, int *flag_lds);
 
+template <bool LSE = false>
 __device__ __forceinline__ void publish_and_merge(const AttnParams &p, int b, int hk, int slot,
                                                   const float *part_lds, float *scratch, int *flag_lds) {
     const int nvals = p.G * p.d + 2 * p.G;
     float *dst = slot_ptr(p, b, hk, slot);
     for (int i = threadIdx.x; i < nvals; i += blockDim.x) st_agent(dst + i, part_lds[i]);
-    ticket_and_merge(p, b, hk, scratch, flag_lds);
+    ticket_and_merge<LSE>(p, b, hk, scratch, flag_lds);
 }
 
+template <bool LSE>
 __device__ __forceinline__ void ticket_and_merge(const AttnParams &p, int b, int hk, float *scratch, int *flag_lds) {
     const int tid = threadIdx.x;
     const int nthr = blockDim.x;
@@ -338,8 +358,8 @@ __device__ __forceinline__ void ticket_and_merge(const AttnParams &p, int b, int
     if ((nthr == 512 || nthr == 1024) && (d == 128 || d == 64) && ns <= 32 && (G == 1 || G == 2 || G == 4 || G == 8)) {      // workgroup-uniform
         MILLION_STAMP(p, 11);
 #define MILLION_MV4(G_) \
-        { if (nthr == 512) { if (d == 128) merge_vec4<G_, 16, 512, 128>(p, b, hk, src, ns, scratch); else merge_vec4<G_, 16, 512, 64>(p, b, hk, src, ns, scratch); } \
-          else { if (d == 128) merge_vec4<G_, 16, 1024, 128>(p, b, hk, src, ns, scratch); else merge_vec4<G_, 16, 1024, 64>(p, b, hk, src, ns, scratch); } }
+        { if (nthr == 512) { if (d == 128) merge_vec4<G_, 16, 512, 128, LSE>(p, b, hk, src, ns, scratch); else merge_vec4<G_, 16, 512, 64, LSE>(p, b, hk, src, ns, scratch); } \
+          else { if (d == 128) merge_vec4<G_, 16, 1024, 128, LSE>(p, b, hk, src, ns, scratch); else merge_vec4<G_, 16, 1024, 64, LSE>(p, b, hk, src, ns, scratch); } }
         if (G == 4) MILLION_MV4(4)
         else if (G == 8) MILLION_MV4(8)
         else if (G == 2) MILLION_MV4(2)
@@ -373,6 +393,7 @@ __device__ __forceinline__ void ticket_and_merge(const AttnParams &p, int b, int
             const float inv = den > 0.f ? 1.0f / den : 0.f;
             if (on) scratch[lane * G + g] = w0 * inv;
             if (ns > 64 && lane == 63) scratch[64 * G + g] = w1 * inv;
+            if constexpr (LSE) { if (lane == 0) store_lse(p, b, hk, g, lse_of(ms_, den)); }      // for the fast and the slow path below
         }
     }
     __syncthreads();

@@ -449,7 +449,7 @@ int million_attn_kernel_kind(const million_attn_desc *desc) {
 static int attn_impl(const million_attn_desc *desc, const void *q, const void *k_new, const void *v_new,
                      const void *k_codes, const void *v_codes,
                      const void *k_page_ids, const void *v_page_ids, const void *k_cents_prepared, const void *v_cents_prepared,
-                     const void *k_resid, const void *v_resid, void *out, void *workspace,
+                     const void *k_resid, const void *v_resid, void *out, float *lse, void *workspace,
                      size_t workspace_bytes, million_stream_t stream) {
     AttnParams p;
     const int rc = fill_attn_params(desc, p);
@@ -477,6 +477,7 @@ static int attn_impl(const million_attn_desc *desc, const void *q, const void *k
     p.k_tab = (const f16 *)k_cents_prepared; p.k_tab_col = p.k_tab + tab;
     p.v_tab = (const f16 *)v_cents_prepared; p.v_tab_col = p.v_tab + tab;
     p.k_res = (const f16 *)k_resid; p.v_res = (const f16 *)v_resid; p.out = (f16 *)out;
+    p.lse = lse;
     p.k_new = (const f16 *)k_new; p.v_new = (const f16 *)v_new;
     p.k_res_w = (f16 *)k_resid; p.v_res_w = (f16 *)v_resid;
     p.dev_lengths_w = (int *)desc->dev_lengths;
@@ -524,7 +525,7 @@ int million_pq_decode_attn(const million_attn_desc *desc, const void *q, const v
                            const void *k_resid, const void *v_resid, void *out, void *workspace,
                            size_t workspace_bytes, million_stream_t stream) {
     return attn_impl(desc, q, nullptr, nullptr, k_codes, v_codes, k_page_ids, v_page_ids, k_cents_prepared,
-                     v_cents_prepared, k_resid, v_resid, out, workspace, workspace_bytes, stream);
+                     v_cents_prepared, k_resid, v_resid, out, nullptr, workspace, workspace_bytes, stream);
 }
 
 int million_pq_decode_attn_append(const million_attn_desc *desc, const void *q, const void *k_new, const void *v_new,
@@ -534,7 +535,17 @@ int million_pq_decode_attn_append(const million_attn_desc *desc, const void *q, 
                                   million_stream_t stream) {
     if (!k_new || !v_new) { set_error("attn_append: k_new / v_new null"); return MILLION_ERR_ARG; }
     return attn_impl(desc, q, k_new, v_new, k_codes, v_codes, k_page_ids, v_page_ids, k_cents_prepared,
-                     v_cents_prepared, k_resid, v_resid, out, workspace, workspace_bytes, stream);
+                     v_cents_prepared, k_resid, v_resid, out, nullptr, workspace, workspace_bytes, stream);
+}
+
+int million_pq_decode_attn_lse(const million_attn_desc *desc, const void *q, const void *k_new, const void *v_new,
+                               const void *k_codes, const void *v_codes, const void *k_page_ids, const void *v_page_ids,
+                               const void *k_cents_prepared, const void *v_cents_prepared, void *k_resid, void *v_resid,
+                               void *out, float *lse, void *workspace, size_t workspace_bytes, million_stream_t stream) {
+    if (!lse) { set_error("attn_lse: lse null"); return MILLION_ERR_ARG; }
+    if ((uintptr_t)lse & 3) { set_error("attn_lse: lse must be 4-byte aligned"); return MILLION_ERR_ALIGN; }
+    return attn_impl(desc, q, k_new, v_new, k_codes, v_codes, k_page_ids, v_page_ids, k_cents_prepared,
+                     v_cents_prepared, k_resid, v_resid, out, lse, workspace, workspace_bytes, stream);
 }
 
 int million_residual_append(const void *k_new, const void *v_new, void *k_resid, void *v_resid, int bs, int nh_k,

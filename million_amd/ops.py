@@ -468,15 +468,20 @@ def pq_decode_attn(q: torch.Tensor, k_codes: torch.Tensor, v_codes: torch.Tensor
                    k_page_ids: Optional[torch.Tensor] = None, v_page_ids: Optional[torch.Tensor] = None,
                    page_size: int = 0, out: Optional[torch.Tensor] = None,
                    dev_lengths: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
-                   k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None,
+                   return_lse: bool = False, lse: Optional[torch.Tensor] = None):
     """One fused launch: score/softmax/value-reconstruct over the code store + residual window + merge.
 
     A side is row-major when its page ids are None: codes (bs, nh_k, T_cap, M) u8 — the reference's
     10-arg call (Interface.template.cu:26-38).  Paged: K pool (n_pool, page_size, M), V pool
     (n_pool, M, page_size), page ids (bs, nh_k, n_pages_cap) int32/int64 (paged_pq_utils.py:621-635 passes
     row-major K with paged V).
+
+    return_lse=True (or an lse= buffer): returns (out, lse), lse fp32 (bs, nh, 1) - the natural-log sum of exp of every head's
+    scaled scores over exactly the keys `out` is a softmax over (million_pq_decode_attn_lse; -inf where there is none).  Two
+    results over disjoint key sets combine with attn_merge.
     """
-    _need_cuda(q, k_codes, v_codes, k_prep, v_prep, k_res, v_res, k_page_ids, v_page_ids, out, dev_lengths)
+    _need_cuda(q, k_codes, v_codes, k_prep, v_prep, k_res, v_res, k_page_ids, v_page_ids, out, dev_lengths, lse)
     if q.dtype != torch.float16 or k_res.dtype != torch.float16 or v_res.dtype != torch.float16:
         raise RuntimeError("pq_decode_attn: q and residuals must be fp16")
     if k_codes.dtype != torch.uint8 or v_codes.dtype != torch.uint8:
@@ -535,6 +540,17 @@ def pq_decode_attn(q: torch.Tensor, k_codes: torch.Tensor, v_codes: torch.Tensor
         if k_new.dtype != torch.float16 or v_new.dtype != torch.float16:
             raise RuntimeError("pq_decode_attn: k_new / v_new must be fp16")
         k_new, v_new = k_new.contiguous(), v_new.contiguous()
+    if return_lse or lse is not None:
+        if lse is None:
+            lse = torch.empty(q.shape[0], q.shape[1], 1, dtype=torch.float32, device=q.device)
+        elif lse.dtype != torch.float32 or tuple(lse.shape) != (q.shape[0], q.shape[1], 1) or not lse.is_contiguous():
+            raise RuntimeError("pq_decode_attn: lse must be contiguous fp32 (bs, nh, 1)")
+        L.check(lib.million_pq_decode_attn_lse(ctypes.byref(desc), q.data_ptr(), _ptr(k_new), _ptr(v_new), _ptr(k_codes),
+                                               _ptr(v_codes), _ptr(k_page_ids), _ptr(v_page_ids), k_prep.data_ptr(),
+                                               v_prep.data_ptr(), k_res.data_ptr(), v_res.data_ptr(), out.data_ptr(),
+                                               lse.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "million_pq_decode_attn_lse")
+        return out, lse
+    if k_new is not None:
         L.check(lib.million_pq_decode_attn_append(ctypes.byref(desc), q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(),
                                                   _ptr(k_codes), _ptr(v_codes), _ptr(k_page_ids), _ptr(v_page_ids),
                                                   k_prep.data_ptr(), v_prep.data_ptr(), k_res.data_ptr(),
@@ -819,7 +835,7 @@ def pq_chunk_attn(q: torch.Tensor, k_chunk: Optional[torch.Tensor], v_chunk: Opt
                   r: int, *, M: int, C: int, n_tokens: int, resid_start: int = 0, k_page_ids: Optional[torch.Tensor] = None,
                   v_page_ids: Optional[torch.Tensor] = None, page_size: Optional[int] = None, out: Optional[torch.Tensor] = None,
                   workspace: Optional[torch.Tensor] = None, dev_lengths: Optional[torch.Tensor] = None,
-                  dev_n_q: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  dev_n_q: Optional[torch.Tensor] = None, return_lse: bool = False, lse: Optional[torch.Tensor] = None):
     """n_q query tokens against [the PQ codes of n_tokens tokens; r window rows of the ring from resid_start; the chunk]
     (million_pq_chunk_attn): q (bs, nh, n_q, d) -> (bs, nh, n_q, d).  k_chunk / v_chunk (bs, nh_k, n_q, d): the chunk's own
     K/V, attended causally (chunked prefill, a later turn of a conversation); None: every row sees the past only (draft
@@ -831,9 +847,12 @@ def pq_chunk_attn(q: torch.Tensor, k_chunk: Optional[torch.Tensor], v_chunk: Opt
     request its own lengths, read on the device when the kernel runs: n_tokens is then only the bound the launch is sized
     for, r and resid_start are ignored; with a caller's workspace= (chunk_attn_workspace_bytes) and out= the call allocates
     nothing and can be captured into a graph.  dev_n_q, device int32 (bs,): the valid query (and chunk) rows of each
-    request; the rows past them are returned as zeros and their q / chunk rows are never read into a product."""
+    request; the rows past them are returned as zeros and their q / chunk rows are never read into a product.
+    return_lse=True (or an lse= buffer): returns (out, lse), lse fp32 (bs, nh, n_q) contiguous - the natural-log sum of exp of
+    every row's scaled scores over the keys it sees (million_pq_chunk_attn_lse); -inf for a row that sees none and for the rows
+    past a request's dev_n_q."""
     _need_cuda(q, k_chunk, v_chunk, k_codes, v_codes, k_prep, v_prep, k_res, v_res, k_page_ids, v_page_ids, out, workspace,
-               dev_lengths, dev_n_q)
+               dev_lengths, dev_n_q, lse)
     if q.dtype != torch.float16 or k_res.dtype != torch.float16 or v_res.dtype != torch.float16:
         raise RuntimeError("pq_chunk_attn: q and window buffers must be fp16")
     if k_codes.dtype != torch.uint8 or v_codes.dtype != torch.uint8:
@@ -898,8 +917,60 @@ def pq_chunk_attn(q: torch.Tensor, k_chunk: Optional[torch.Tensor], v_chunk: Opt
     need = lib.million_chunk_attn_workspace_bytes(ctypes.byref(desc))
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=q.device) if need else None
+    if return_lse or lse is not None:
+        if lse is None:
+            lse = torch.empty(bs, nh, n_q, dtype=torch.float32, device=q.device)
+        elif lse.dtype != torch.float32 or tuple(lse.shape) != (bs, nh, n_q) or not lse.is_contiguous():
+            raise RuntimeError("pq_chunk_attn: lse must be contiguous fp32 (bs, nh, n_q)")
+        L.check(lib.million_pq_chunk_attn_lse(ctypes.byref(desc), q.data_ptr(), _ptr(k_chunk), _ptr(v_chunk), k_codes.data_ptr(),
+                                              v_codes.data_ptr(), _ptr(k_page_ids), _ptr(v_page_ids), k_prep.data_ptr(),
+                                              v_prep.data_ptr(), k_res.data_ptr(), v_res.data_ptr(), out.data_ptr(), lse.data_ptr(),
+                                              _ptr(workspace), 0 if workspace is None else workspace.numel(), _stream()),
+                "million_pq_chunk_attn_lse")
+        return out, lse
     L.check(lib.million_pq_chunk_attn(ctypes.byref(desc), q.data_ptr(), _ptr(k_chunk), _ptr(v_chunk), k_codes.data_ptr(),
                                       v_codes.data_ptr(), _ptr(k_page_ids), _ptr(v_page_ids), k_prep.data_ptr(), v_prep.data_ptr(),
                                       k_res.data_ptr(), v_res.data_ptr(), out.data_ptr(), _ptr(workspace),
                                       0 if workspace is None else workspace.numel(), _stream()), "million_pq_chunk_attn")
     return out
+
+
+def attn_merge(outs, lses, out: Optional[torch.Tensor] = None, lse_out: Optional[torch.Tensor] = None, return_lse: bool = False):
+    """Merge of partial attentions (million_attn_merge): outs[i] fp16 (bs, nh, n_q, d) and lses[i] fp32 (bs, nh, n_q) are the
+    results of one query over DISJOINT key sets (pq_decode_attn / pq_chunk_attn with return_lse); returns their softmax over
+    the union - with return_lse (or an lse_out buffer) (out, lse_out).  Up to 8 parts, d 64 or 128.  The tensors may be any
+    views whose rows of d are contiguous and 16-byte aligned (every other out stride a multiple of 8 elements): a transposed
+    view costs no copy.  `out` may be one of the parts (same tensor view); lse_out overlaps no part's lse.  A part whose lse
+    is -inf has weight 0; all of them: out 0, lse -inf; a NaN lse: the row is NaN."""
+    outs, lses = list(outs), list(lses)
+    P = len(outs)
+    if not 1 <= P <= L.MILLION_MERGE_MAX_PARTS or len(lses) != P:
+        raise RuntimeError(f"attn_merge: 1 .. {L.MILLION_MERGE_MAX_PARTS} parts, one lse per out")
+    _need_cuda(*outs, *lses, out, lse_out)
+    bs, nh, n_q, d = outs[0].shape
+    for o, l in zip(outs, lses):
+        if o.dtype != torch.float16 or tuple(o.shape) != (bs, nh, n_q, d) or (n_q and o.stride(3) != 1):
+            raise RuntimeError(f"attn_merge: every out must be fp16 {(bs, nh, n_q, d)} with contiguous rows")
+        if l.dtype != torch.float32 or tuple(l.shape) != (bs, nh, n_q):
+            raise RuntimeError(f"attn_merge: every lse must be fp32 {(bs, nh, n_q)}")
+    if out is None:
+        out = torch.empty(bs, nh, n_q, d, dtype=torch.float16, device=outs[0].device)
+    elif out.dtype != torch.float16 or tuple(out.shape) != (bs, nh, n_q, d) or (n_q and out.stride(3) != 1):
+        raise RuntimeError("attn_merge: out must be fp16 (bs, nh, n_q, d) with contiguous rows")
+    if lse_out is None and return_lse:
+        lse_out = torch.empty(bs, nh, n_q, dtype=torch.float32, device=outs[0].device)
+    if lse_out is not None and (lse_out.dtype != torch.float32 or tuple(lse_out.shape) != (bs, nh, n_q)):
+        raise RuntimeError("attn_merge: lse_out must be fp32 (bs, nh, n_q)")
+    desc = L.AttnMergeDesc()
+    desc.struct_size = ctypes.sizeof(L.AttnMergeDesc)
+    desc.n_parts, desc.bs, desc.nh, desc.n_q, desc.d = P, bs, nh, n_q, d
+    for i, (o, l) in enumerate(zip(outs, lses)):
+        for k in range(3):
+            desc.out_stride[i][k], desc.lse_stride[i][k] = o.stride(k), l.stride(k)
+    for k in range(3):
+        desc.res_out_stride[k] = out.stride(k)
+        desc.res_lse_stride[k] = lse_out.stride(k) if lse_out is not None else 0
+    po = (L.c_vp * P)(*[o.data_ptr() for o in outs])
+    pl = (L.c_vp * P)(*[l.data_ptr() for l in lses])
+    L.check(L.load().million_attn_merge(ctypes.byref(desc), po, pl, out.data_ptr(), _ptr(lse_out), _stream()), "million_attn_merge")
+    return (out, lse_out) if (return_lse or lse_out is not None) else out

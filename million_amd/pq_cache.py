@@ -675,8 +675,9 @@ class PagedPQCache(_CacheBase):
             torch.cuda.current_stream().wait_stream(self._side)
         self._pre_a[layer_idx, slice(None) if b is None else b] = 0
 
-    def _extend_slot(self, query_states, key_states, value_states, layer_idx, b):
-        """b = None: every request (lockstep); else request b with batch-1 tensors."""
+    def _extend_slot(self, query_states, key_states, value_states, layer_idx, b, return_lse=False, all_rows=False):
+        """b = None: every request (lockstep); else request b with batch-1 tensors.  return_lse: (out, lse) of the chunk
+        attention (ops.pq_chunk_attn); all_rows: every device row of the layer is rewritten, as prefill_request does."""
         i, sel = (0, slice(None)) if b is None else (b, slice(b, b + 1))
         T, r, rs = int(self._T_a[layer_idx, i]), int(self._r_a[layer_idx, i]), int(self._rs_a[layer_idx, i])
         n = key_states.size(2)
@@ -686,8 +687,8 @@ class PagedPQCache(_CacheBase):
         out = ops.pq_chunk_attn(query_states, key_states, value_states, self.key_page_pool, self.value_page_pool, self._kprep,
                                 self._vprep, self.key_residual_cache[layer_idx][sel], self.value_residual_cache[layer_idx][sel], r,
                                 M=self.M, C=self.C, n_tokens=T, resid_start=rs, k_page_ids=ids, v_page_ids=ids,
-                                page_size=self.page_size)
-        self._store(key_states, value_states, layer_idx, n, b)      # the window in ring order, then the new rows
+                                page_size=self.page_size, **({"return_lse": True} if return_lse else {}))
+        self._store(key_states, value_states, layer_idx, n, b, all_rows=all_rows)      # the window in ring order, then the new rows
         return out
 
     def extend(self, query_states, key_states, value_states, layer_idx):
@@ -705,15 +706,20 @@ class PagedPQCache(_CacheBase):
             return self.prefill(query_states, key_states, value_states, layer_idx)
         return self._extend_slot(query_states, key_states, value_states, layer_idx, None)
 
-    def extend_request(self, b, query_states, key_states, value_states, layer_idx):
+    def extend_request(self, b, query_states, key_states, value_states, layer_idx, return_lse=False):
         """extend() for ONE request (tensors of batch 1) in slot b; the other slots, their host and device lengths, are not
-        touched (they may keep decoding with use_dev_lengths=True).  On an empty slot this is prefill_request()."""
+        touched (they may keep decoding with use_dev_lengths=True).  On an empty slot this is prefill_request().
+        return_lse=True: returns (out, lse), lse fp32 (1, nh, n) - every row's log-sum-exp over the keys it saw
+        (ops.pq_chunk_attn).  The prompt kernel has none, so an empty slot is then served by chunk attention over the chunk
+        alone, followed by the same store: the slot, the pages and every length are left as prefill_request leaves them."""
         if key_states.size(0) != 1 or query_states.size(0) != 1:
             raise RuntimeError("extend_request: tensors of batch 1")
         self._join_side(layer_idx, b)
         if self._T_a[layer_idx, b] == 0 and self._r_a[layer_idx, b] == 0:
+            if return_lse:
+                return self._extend_slot(query_states, key_states, value_states, layer_idx, b, return_lse=True, all_rows=True)
             return self.prefill_request(b, query_states, key_states, value_states, layer_idx)
-        return self._extend_slot(query_states, key_states, value_states, layer_idx, b)
+        return self._extend_slot(query_states, key_states, value_states, layer_idx, b, return_lse=return_lse)
 
     def extend_ragged(self, query_states, key_states, value_states, layer_idx, n_new, device_store=False):
         """extend_request() for every slot in ONE attention launch: tensors of batch bs padded to n_q = max(n_new) rows,
@@ -1180,11 +1186,13 @@ class PagedPQCache(_CacheBase):
         if not todo:
             self._ahead = None
 
-    def decoding_with_pages(self, query_states, key_states, value_states, layer_idx, out=None, use_dev_lengths=False):
+    def decoding_with_pages(self, query_states, key_states, value_states, layer_idx, out=None, use_dev_lengths=False,
+                            return_lse=False, lse=None):
         """One decode step of one layer (paged_pq_utils.py:341-386): flush if the window is full, append the
         new token's K/V row, fused attention over pages + window.  With use_dev_lengths=True every length
         is read on the device (the host mirror is still advanced), which makes the call graph-capturable and lets
-        requests of different lengths share the launch."""
+        requests of different lengths share the launch.  return_lse=True (or an lse= buffer, fp32 (bs, nh, 1)): returns
+        (out, lse), every head's log-sum-exp over the keys it attended to (ops.pq_decode_attn)."""
         cap = self.extended_residual_size
         if not self._join_flush(layer_idx) and (self._r_a[layer_idx] >= cap).any():      # not flushed ahead on the side stream: :359-361
             self.flush_to_pages(layer_idx, use_dev_lengths=use_dev_lengths)
@@ -1205,7 +1213,8 @@ class PagedPQCache(_CacheBase):
                                  M=self.M, C=self.C, n_tokens=self.max_tokens if use_dev_lengths else int(self._T_a[layer_idx, 0]),
                                  resid_start=rs, k_page_ids=self.page_ids[layer_idx],
                                  v_page_ids=self.page_ids[layer_idx], page_size=self.page_size, out=out,
-                                 dev_lengths=dl, workspace=self._ws)
+                                 dev_lengths=dl, workspace=self._ws,
+                                 **({"return_lse": True, "lse": lse} if return_lse or lse is not None else {}))
         if self._pre_join and layer_idx == self.layer_num - 1:
             torch.cuda.current_stream().wait_stream(self._side)      # the step's encode-ahead launch ends with the step
             self._pre_join = False

@@ -29,6 +29,7 @@ ap.add_argument("--zero-codes", action="store_true", help="diagnostic: all code 
 ap.add_argument("--k-conflict-free", action="store_true", help="diagnostic: K codes chosen so that the 64 lanes of every K gather hit 64 different LDS banks (M = 64 streaming kernel)")
 ap.add_argument("--eager-after-sleep", action="store_true", help="rounds 1-3 timing: eager launches enqueued behind a device-side sleep (reads slow: the clocks drop during the sleep)")
 ap.add_argument("--policy", type=int, default=0, help="million_set_force_generic value for the TIMED launches (16: the lean kernel's shapes stay on the streaming kernel)")
+ap.add_argument("--lse", action="store_true", help="time the same launches through million_pq_decode_attn_lse (the LSE instances of the kernels)")
 ap.add_argument("--same-page", action="store_true", help="diagnostic: every page id = 0 (codes come from L2, not HBM)")
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
@@ -62,6 +63,7 @@ for cfg in args.cfg:
     kr = torch.randn(bs, nhk, 128, d, device=dev).half()
     vr = torch.randn(bs, nhk, 128, d, device=dev).half()
     dl = torch.tensor([[T, r, 0, 0]] * bs, dtype=torch.int32, device=dev) if args.dev_lengths else None
+    lse_kw = dict(lse=torch.empty(bs, nh, 1, dtype=torch.float32, device=dev)) if args.lse else {}
 
     if args.bindings_10arg:
         import bindings
@@ -77,8 +79,9 @@ for cfg in args.cfg:
             kcod, vcod = rm[l % len(rm)]
             return fn(q, kcod, vcod, kcent, vcent, kr, vr, r, po, pl)
         kp, vp, ids = states[l % len(states)]
-        return ops.pq_decode_attn(q, kp, vp, kc, vc, kr, vr, r, M=M, C=C, n_tokens=T, k_page_ids=ids, v_page_ids=ids,
-                                  page_size=ps, dev_lengths=dl)
+        res = ops.pq_decode_attn(q, kp, vp, kc, vc, kr, vr, r, M=M, C=C, n_tokens=T, k_page_ids=ids, v_page_ids=ids,
+                                 page_size=ps, dev_lengths=dl, **lse_kw)
+        return res[0] if args.lse else res
 
     lib.million_set_force_generic(1)        # the scalar kernel as the cross-check
     ref = run(0).float()
@@ -134,6 +137,8 @@ for cfg in args.cfg:
     if args.bindings_10arg:
         tag = tag + " 10-arg"
     extra = f"   scalar fallback {scalar:8.1f} us ({scalar / best:5.1f}x)" if scalar else ""
+    if args.lse and "lse" not in tag:
+        tag = tag + " lse"
     if args.policy and "policy" not in tag:
         tag = tag + f" policy {args.policy}"
     print(f"{tag:34s} bs={bs} nh={nh} nh_k={nhk} T={T:6d} d={d} M={M} C={C} kind={kind}: {best:6.2f} us/launch  {alg / best / 1e3:7.1f} GB/s ({alg / best / 8e6 * 100:4.1f}% of 8 TB/s)  rel diff vs cross-check {err:.1e}{extra}", flush=True)
