@@ -635,6 +635,73 @@ int million_attn_merge(const million_attn_merge_desc *desc, const void *const *p
                        void *out, float *lse_out /* may be NULL */, million_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Draft verification (speculative decoding): n <= 16 draft rows per request at consecutive positions are verified without being
+ * stored, and only the accepted ones are appended afterwards.
+ *
+ * The draft rows see the same past, so their attention over [codes below T; window] is one decode launch with the rows as
+ * query heads: q (bs, nh, n, d) contiguous, viewed as (bs, nh * n, 1, d), puts virtual head v = h * n + i under kv head
+ * v / (G * n) = h / G (G = nh / nh_k); million_pq_decode_attn_lse without k_new gives (out_a, lse_a) of every row.  (Chunk
+ * attention with n_c = 0 gives the same pair.)  million_attn_block_merge then finishes the rows in one launch: the causal
+ * attention among the block's own K/V rows, merged with the past part.  Per row (b, h, i) with i < n_b:
+ *   s_j = q_i . k_j / sqrt(d) for j <= i, fp32;  L = max(lse_a, max_j s_j);  w = exp(lse_a - L) (0 for -inf);  p_j = exp(s_j - L);
+ *   out = (w out_a + sum_j p_j v_j) / (w + sum_j p_j) in fp32, rounded once to fp16;  lse_out = L + ln(w + sum_j p_j).
+ * This is million_attn_merge's contract with the second part computed in the kernel.  A NaN lse_a: the row is NaN.
+ * dev_n (optional, device (bs,) int32): n_b, clamped into [0, n] on the device; NULL: n_b = n.  Rows i >= n_b get out = 0 and
+ * lse_out = -inf (chunk attention's convention); whatever q / k_blk / v_blk / out_a hold at those rows, NaN included, reaches
+ * no product and no live row.
+ * q, k_blk, v_blk, out_a and out have element strides (b, h, n) and rows of d contiguous fp16; lse_a and lse_out are (bs, nh, n)
+ * contiguous fp32; lse_out may be NULL.  `out` may be out_a (same pointer and strides): a lane reads its elements of out_a before
+ * it writes them.  k_stage / v_stage (optional, together): the launch copies the n block rows there, bit for bit, as rows of d
+ * at b * stage_stride_b + hk * stage_stride_h - the decode launch parks its new row in the same way; million_window_commit
+ * reads them.  d = 64 or 128, any nh / nh_k, n in 1 .. 16.  One plain launch of bs * nh single-wave workgroups: no atomics, no
+ * workspace, legal inside stream capture.  Validation precedes any HIP call: struct size, n, d, null pointers, 16-byte
+ * pointers, strides in multiples of 8 elements. */
+typedef struct {
+    uint32_t struct_size;          /* = sizeof(million_block_merge_desc) */
+    int32_t  bs, nh, nh_k;
+    int32_t  n;                    /* draft rows, 1 .. 16 */
+    int32_t  d;                    /* 64 or 128 */
+    int64_t  q_stride[3], k_stride[3], v_stride[3];   /* element strides (b, h, n); multiples of 8 */
+    int64_t  a_stride[3], o_stride[3];                /* out_a, out */
+    int64_t  stage_stride_b, stage_stride_h;          /* k_stage / v_stage; their row stride is d */
+} million_block_merge_desc;
+
+int million_attn_block_merge(const million_block_merge_desc *desc, const void *q /* (bs, nh, n, d) */,
+                             const void *k_blk, const void *v_blk /* (bs, nh_k, n, d) */,
+                             const void *out_a /* (bs, nh, n, d) */, const float *lse_a /* (bs, nh, n) */,
+                             const int32_t *dev_n /* (bs,), may be NULL */, void *out, float *lse_out /* may be NULL */,
+                             void *k_stage, void *v_stage /* may be NULL */, million_stream_t stream);
+
+/* Append the first a_b = dev_n[b] rows of k_new / v_new (layers, bs, nh_k, n_bound, d) to request b's residual window in every
+ * layer of a paged cache, exactly as a_b decode steps would have: a decode step flushes the oldest page_size window rows into
+ * the pages when the window is full and then appends.  a_b is clamped into [0, n_bound]; n_bound <= 16 and n_bound <= page_size,
+ * so a request flushes at most once.  Per (layer, b), with {T, r, start} of the request's lengths row clamped as
+ * million_pq_store_ragged clamps them:
+ *   S = [the r window rows in ring order; the a new rows];  f = page_size if r + a > resid_cap, else 0;
+ *   rows S[0, f) become tokens [T, T + f) of the K pages and the transposed V pages - the codes million_pq_flush writes, bit
+ *   for bit; the new rows with source index >= f go to ring slot (start + r + i) % resid_cap;
+ *   then T += f, r += a - f, start = (start + f) % resid_cap.  Word 3 is not touched.
+ * Two stream-ordered launches (encode; append and advance), grids sized by the bounds alone, everything per request read on the
+ * device: the call may be captured.  A request whose T + f would pass n_pages_cap * page_size is left untouched by both launches
+ * (the caller checks before the call); a page id outside [0, n_pool) drops its stores.  The layers of the page tables, windows
+ * and lengths lie side by side as for million_pq_flush_layers / million_cache_fork: ids_layer_stride (int32 entries),
+ * rows_layer_stride (fp16 elements; each layer's windows contiguous (bs, nh_k, resid_cap, d)), lengths_layer_stride (int32
+ * entries); dev_n is one (bs,) array for all layers.  Validation precedes any HIP call. */
+typedef struct {
+    uint32_t struct_size;          /* = sizeof(million_window_commit_desc) */
+    int32_t  n_layers, bs, nh_k, d, M, C;
+    int32_t  n_bound;              /* rows of k_new / v_new per request: 1 .. 16, <= page_size */
+    int32_t  page_size, n_pages_cap, n_pool, resid_cap;
+    int64_t  new_stride_l, new_stride_b, new_stride_h, new_stride_n;   /* k_new and v_new alike, fp16 elements, multiples of 8 */
+    int64_t  ids_layer_stride, rows_layer_stride, lengths_layer_stride;
+} million_window_commit_desc;
+
+int million_window_commit(const million_window_commit_desc *desc, const void *k_new, const void *v_new, void *k_resid,
+                          void *v_resid, const void *k_cents_prepared, const void *v_cents_prepared, void *k_pool,
+                          void *v_pool, const int32_t *page_ids, int32_t *dev_lengths, const int32_t *dev_n,
+                          million_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Residual-window append.
  * Replaces: the two slice-assign copies of DynamicPQCache.decoding (pq_utils.py:304-312) /
  * PagedPQCache.decoding_with_pages (paged_pq_utils.py:377-380).

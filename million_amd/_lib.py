@@ -80,6 +80,20 @@ class StoreRaggedDesc(ctypes.Structure):
                 ("n_pages_cap", c_i32)]
 
 
+class BlockMergeDesc(ctypes.Structure):
+    _fields_ = [("struct_size", c_u32), ("bs", c_i32), ("nh", c_i32), ("nh_k", c_i32), ("n", c_i32), ("d", c_i32),
+                ("q_stride", c_i64 * 3), ("k_stride", c_i64 * 3), ("v_stride", c_i64 * 3),
+                ("a_stride", c_i64 * 3), ("o_stride", c_i64 * 3),
+                ("stage_stride_b", c_i64), ("stage_stride_h", c_i64)]
+
+
+class WindowCommitDesc(ctypes.Structure):
+    _fields_ = [("struct_size", c_u32), ("n_layers", c_i32), ("bs", c_i32), ("nh_k", c_i32), ("d", c_i32), ("M", c_i32), ("C", c_i32),
+                ("n_bound", c_i32), ("page_size", c_i32), ("n_pages_cap", c_i32), ("n_pool", c_i32), ("resid_cap", c_i32),
+                ("new_stride_l", c_i64), ("new_stride_b", c_i64), ("new_stride_h", c_i64), ("new_stride_n", c_i64),
+                ("ids_layer_stride", c_i64), ("rows_layer_stride", c_i64), ("lengths_layer_stride", c_i64)]
+
+
 MILLION_FORK_SHARE, MILLION_FORK_COPY = 0, 1
 
 
@@ -134,6 +148,8 @@ SYMBOLS = {
     "million_pq_chunk_attn": (c_i32, [ctypes.POINTER(ChunkAttnDesc)] + [c_vp] * 13 + [c_sz, c_vp]),
     "million_pq_chunk_attn_lse": (c_i32, [ctypes.POINTER(ChunkAttnDesc)] + [c_vp] * 14 + [c_sz, c_vp]),
     "million_attn_merge": (c_i32, [ctypes.POINTER(AttnMergeDesc), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_vp, c_vp]),
+    "million_attn_block_merge": (c_i32, [ctypes.POINTER(BlockMergeDesc)] + [c_vp] * 11),
+    "million_window_commit": (c_i32, [ctypes.POINTER(WindowCommitDesc)] + [c_vp] * 12),
     "million_pq_store_ragged": (c_i32, [ctypes.POINTER(StoreRaggedDesc)] + [c_vp] * 12),
     "million_cache_fork": (c_i32, [ctypes.POINTER(ForkDesc)] + [c_vp] * 9),
     "million_cache_swap": (c_i32, [ctypes.POINTER(SwapDesc)] + [c_vp] * 10),

@@ -974,3 +974,103 @@ def attn_merge(outs, lses, out: Optional[torch.Tensor] = None, lse_out: Optional
     pl = (L.c_vp * P)(*[l.data_ptr() for l in lses])
     L.check(L.load().million_attn_merge(ctypes.byref(desc), po, pl, out.data_ptr(), _ptr(lse_out), _stream()), "million_attn_merge")
     return (out, lse_out) if (return_lse or lse_out is not None) else out
+
+
+def attn_block_merge(q: torch.Tensor, k_blk: torch.Tensor, v_blk: torch.Tensor, out_a: torch.Tensor, lse_a: torch.Tensor,
+                     dev_n: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, lse_out: Optional[torch.Tensor] = None,
+                     return_lse: bool = False, k_stage: Optional[torch.Tensor] = None, v_stage: Optional[torch.Tensor] = None):
+    """Finish the attention of n <= 16 draft rows per request in one launch (million_attn_block_merge): (out_a, lse_a), fp16
+    (bs, nh, n, d) and fp32 (bs, nh, n) contiguous, is every row's attention over the past (pq_decode_attn over the rows as query
+    heads, or pq_chunk_attn without a chunk, with return_lse); row i then attends causally to the block's own rows j <= i of
+    k_blk / v_blk (bs, nh_k, n, d) and the two parts are merged as attn_merge merges them.  q, k_blk, v_blk, out_a and out may be
+    any views with contiguous rows of d and the other strides multiples of 8 elements; `out` may be out_a itself.  dev_n, device
+    int32 (bs,): the live rows of each request, clamped into [0, n]; the rows past them get out = 0 and lse = -inf and their q /
+    k / v never reach a live row.  k_stage / v_stage, fp16 (bs, nh_k, >= n, d) with dense rows: the launch copies the block rows
+    there (window_commit reads them).  Returns out, or (out, lse_out) with return_lse (or an lse_out buffer)."""
+    _need_cuda(q, k_blk, v_blk, out_a, lse_a, dev_n, out, lse_out, k_stage, v_stage)
+    if q.dim() != 4 or any(t.dtype != torch.float16 for t in (q, k_blk, v_blk, out_a)):
+        raise RuntimeError("attn_block_merge: q, k_blk, v_blk and out_a must be fp16 (bs, nh | nh_k, n, d)")
+    bs, nh, n, d = q.shape
+    if k_blk.dim() != 4 or k_blk.shape[0] != bs or k_blk.shape[2:] != (n, d) or v_blk.shape != k_blk.shape or nh % k_blk.shape[1]:
+        raise RuntimeError(f"attn_block_merge: k_blk / v_blk must be (bs, nh_k, n, d) = ({bs}, nh_k, {n}, {d}), nh a multiple of nh_k")
+    nh_k = k_blk.shape[1]
+    fix = lambda t: t if (t.stride(3) == 1 and all(s_ % 8 == 0 for s_ in t.stride()[:3])) else t.contiguous()
+    q, k_blk, v_blk = fix(q), fix(k_blk), fix(v_blk)
+    if tuple(out_a.shape) != (bs, nh, n, d) or out_a.stride(3) != 1:
+        raise RuntimeError("attn_block_merge: out_a must be (bs, nh, n, d) with contiguous rows")
+    if lse_a.dtype != torch.float32 or tuple(lse_a.shape) != (bs, nh, n) or not lse_a.is_contiguous():
+        raise RuntimeError("attn_block_merge: lse_a must be contiguous fp32 (bs, nh, n)")
+    if dev_n is not None and (dev_n.dtype != torch.int32 or tuple(dev_n.shape) != (bs,) or not dev_n.is_contiguous()):
+        raise RuntimeError("attn_block_merge: dev_n must be contiguous int32 (bs,)")
+    if out is None:
+        out = torch.empty(bs, nh, n, d, dtype=torch.float16, device=q.device)
+    elif out.dtype != torch.float16 or tuple(out.shape) != (bs, nh, n, d) or out.stride(3) != 1:
+        raise RuntimeError("attn_block_merge: out must be fp16 (bs, nh, n, d) with contiguous rows")
+    if lse_out is None and return_lse:
+        lse_out = torch.empty(bs, nh, n, dtype=torch.float32, device=q.device)
+    if lse_out is not None and (lse_out.dtype != torch.float32 or tuple(lse_out.shape) != (bs, nh, n) or not lse_out.is_contiguous()):
+        raise RuntimeError("attn_block_merge: lse_out must be contiguous fp32 (bs, nh, n)")
+    if (k_stage is None) != (v_stage is None):
+        raise RuntimeError("attn_block_merge: k_stage and v_stage go together")
+    desc = L.BlockMergeDesc()
+    desc.struct_size = ctypes.sizeof(L.BlockMergeDesc)
+    desc.bs, desc.nh, desc.nh_k, desc.n, desc.d = bs, nh, nh_k, n, d
+    for k in range(3):
+        desc.q_stride[k], desc.k_stride[k], desc.v_stride[k] = q.stride(k), k_blk.stride(k), v_blk.stride(k)
+        desc.a_stride[k], desc.o_stride[k] = out_a.stride(k), out.stride(k)
+    if k_stage is not None:
+        for t in (k_stage, v_stage):
+            if (t.dtype != torch.float16 or t.dim() != 4 or t.shape[:2] != (bs, nh_k) or t.shape[2] < n or t.shape[3] != d
+                    or t.stride(3) != 1 or t.stride(2) != d or t.stride() != k_stage.stride()):
+                raise RuntimeError("attn_block_merge: k_stage / v_stage must be fp16 (bs, nh_k, >= n, d) with dense rows, alike")
+        desc.stage_stride_b, desc.stage_stride_h = k_stage.stride(0), k_stage.stride(1)
+    L.check(L.load().million_attn_block_merge(ctypes.byref(desc), q.data_ptr(), k_blk.data_ptr(), v_blk.data_ptr(), out_a.data_ptr(),
+                                              lse_a.data_ptr(), _ptr(dev_n), out.data_ptr(), _ptr(lse_out), _ptr(k_stage),
+                                              _ptr(v_stage), _stream()), "million_attn_block_merge")
+    return (out, lse_out) if (return_lse or lse_out is not None) else out
+
+
+def window_commit(k_new: torch.Tensor, v_new: torch.Tensor, k_res: torch.Tensor, v_res: torch.Tensor, k_prep: torch.Tensor,
+                  v_prep: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, page_ids: torch.Tensor,
+                  dev_lengths: torch.Tensor, dev_n: torch.Tensor, *, M: int, C: int, n_bound: Optional[int] = None) -> None:
+    """Append the first dev_n[b] rows of k_new / v_new (layers, bs, nh_k, n, d) to request b's window in every layer, exactly as
+    that many decode steps would have (million_window_commit): a request whose window would overflow first has its oldest
+    page_size rows - window rows in ring order, then new rows - encoded behind its T tokens (the codes pq_flush writes), the
+    rest of the new rows go to the ring, and the rows of dev_lengths (layers, bs, 4) advance on the device.  k_res / v_res
+    (layers, bs, nh_k, cap, d), page_ids (layers, bs, nh_k, n_pages_cap): the layers of one cache side by side, as cache_fork
+    takes them; dev_n int32 (bs,) serves every layer.  n_bound (default n): the rows the grids are sized for, at most 16 and at
+    most page_size; dev_n is clamped into [0, n_bound]."""
+    _need_cuda(k_new, v_new, k_res, v_res, k_prep, v_prep, k_pool, v_pool, page_ids, dev_lengths, dev_n)
+    if k_new.dtype != torch.float16 or v_new.dtype != torch.float16 or k_new.dim() != 5 or v_new.shape != k_new.shape or \
+            k_new.stride() != v_new.stride() or k_new.stride(4) != 1:
+        raise RuntimeError("window_commit: k_new / v_new must be fp16 (layers, bs, nh_k, n, d) of one shape and strides, contiguous rows")
+    n_layers, bs, nhk, n_rows, d = k_new.shape
+    n_bound = n_rows if n_bound is None else int(n_bound)
+    if n_bound > n_rows:
+        raise RuntimeError(f"window_commit: n_bound={n_bound} exceeds the {n_rows} rows of k_new")
+    if page_ids.dtype != torch.int32 or page_ids.dim() != 4 or page_ids.shape[:3] != (n_layers, bs, nhk) or not page_ids[0].is_contiguous():
+        raise RuntimeError("window_commit: int32 page_ids (layers, bs, nh_k, n_pages_cap), each layer contiguous, expected")
+    if (k_pool.dtype != torch.uint8 or v_pool.dtype != torch.uint8 or k_pool.dim() != 3 or not k_pool.is_contiguous() or not v_pool.is_contiguous()
+            or v_pool.shape != (k_pool.shape[0], k_pool.shape[2], k_pool.shape[1]) or k_pool.shape[2] != M):
+        raise RuntimeError("window_commit: contiguous uint8 pools (n_pool, page_size, M) and (n_pool, M, page_size) expected")
+    n_pool, page_size, _ = k_pool.shape
+    if (k_res.dtype != torch.float16 or v_res.dtype != torch.float16 or k_res.dim() != 5 or k_res.shape != v_res.shape or k_res.stride() != v_res.stride()
+            or k_res.shape[:3] != (n_layers, bs, nhk) or k_res.shape[4] != d or not k_res[0].is_contiguous()):
+        raise RuntimeError("window_commit: fp16 windows (layers, bs, nh_k, cap, d), each layer contiguous, K and V alike, expected")
+    if dev_lengths.dtype != torch.int32 or dev_lengths.shape != (n_layers, bs, 4) or not dev_lengths[0].is_contiguous():
+        raise RuntimeError("window_commit: int32 dev_lengths (layers, bs, 4) expected")
+    if dev_n.dtype != torch.int32 or dev_n.shape != (bs,) or not dev_n.is_contiguous():
+        raise RuntimeError("window_commit: dev_n must be contiguous int32 (bs,)")
+    if k_prep.dtype != torch.float16 or v_prep.dtype != torch.float16 or k_prep.numel() != v_prep.numel() or k_prep.numel() != 4 * M * C * (d // M):
+        raise RuntimeError("window_commit: k_prep / v_prep must be the prepared codebooks of (M, C, d / M) (prepare_cents)")
+    desc = L.WindowCommitDesc()
+    desc.struct_size = ctypes.sizeof(L.WindowCommitDesc)
+    desc.n_layers, desc.bs, desc.nh_k, desc.d, desc.M, desc.C, desc.n_bound = n_layers, bs, nhk, d, M, C, n_bound
+    desc.page_size, desc.n_pages_cap, desc.n_pool, desc.resid_cap = page_size, page_ids.shape[3], n_pool, k_res.shape[3]
+    desc.new_stride_l, desc.new_stride_b, desc.new_stride_h, desc.new_stride_n = k_new.stride()[:4]
+    desc.ids_layer_stride, desc.rows_layer_stride, desc.lengths_layer_stride = page_ids.stride(0), k_res.stride(0), dev_lengths.stride(0)
+    L.check(L.load().million_window_commit(ctypes.byref(desc), k_new.data_ptr(), v_new.data_ptr(), k_res.data_ptr(), v_res.data_ptr(),
+                                           k_prep.data_ptr(), v_prep.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(),
+                                           page_ids.data_ptr(), dev_lengths.data_ptr(), dev_n.data_ptr(), _stream()),
+            "million_window_commit")
+    _vshadow_drop(v_pool)

@@ -469,6 +469,8 @@ class PagedPQCache(_CacheBase):
         self._pre_join = False
         self._host_pids = [[[[] for _ in range(nk)] for _ in range(self.bs)] for _ in range(self.layer_num)]
         self._ws = None
+        # draft verification (verify / commit): the record of the running verify, the staged rows, one decode workspace per n
+        self._verify_rec, self._kstage, self._vstage, self._ws_verify = None, None, None, {}
         self._side, self._flush_events, self._ahead = None, {}, None
         # knobs of begin_step (None: the defaults of _ea_groups / begin_step): steps an encode-ahead is spread over, launches per step
         self.encode_ahead_steps = self.encode_ahead_launches = None
@@ -1222,6 +1224,143 @@ class PagedPQCache(_CacheBase):
 
     # the reference's non-paged entry point keeps working on the paged store
     decoding = decoding_with_pages
+
+    # ---- draft verification: verify n rows per request without storing them, then commit the accepted ones -----------------
+    # The draft rows of a request sit at consecutive positions and see the same past, so their attention over [codes; window]
+    # is ONE decode launch with the rows as query heads (q (bs, nh, n, d) viewed as (bs, nh n, 1, d): virtual head h n + i
+    # lies under kv head h // G); ops.attn_block_merge adds the causal part among the rows and parks their K/V in a staging
+    # buffer.  Nothing is stored before acceptance is known, so nothing is rolled back: commit() appends the accepted rows
+    # of every layer in one ops.window_commit, leaving the cache as that many decode steps would have.
+    VERIFY_MAX_ROWS = 16
+
+    def _verify_route(self, n) -> str:
+        """The route verify() takes by default, from the measurement in profiles/verify_attn.txt (tools/verify_bench.py): "heads"
+        while a kv head serves at most 64 rows (n G <= 64) - 0.19 to 0.67 of the chunk route's time at every measured shape, the
+        decode launch growing by one pass over the codes per 16 rows - else chunk attention, which is not measured against it
+        there."""
+        return "heads" if n * (self.nh // self.num_key_value_heads) <= 64 else "chunk"
+
+    def _mirror_sig(self):
+        return (self._T_a.copy(), self._r_a.copy(), self._rs_a.copy())
+
+    def verify(self, query_states, key_states, value_states, layer_idx, n_draft=None, use_dev_lengths=True, route=None,
+               return_lse=False):
+        """Attention of n <= 16 draft tokens per request over [the codes; the window; the draft rows, causally], one layer:
+        q (bs, nh, n, d), K/V (bs, nh_k, n, d) -> out (bs, nh, n, d) (and lse (bs, nh, n) with return_lse).  Pure: lengths,
+        pages, window and host mirror do not move; the rows' K/V are parked in a staging buffer of the cache for commit().
+        n_draft: bs host ints in [0, n], the rows each slot verifies (default: n); rows past them are returned as zeros
+        (lse -inf) and their q / K / V may hold anything.  route: "heads" - one decode launch over the rows as query heads,
+        then ops.attn_block_merge; "chunk" - ops.pq_chunk_attn with the rows as chunk; None: _verify_route.  A side-stream
+        flush that begin_step scheduled for the layer is joined first, as decoding_with_pages joins it."""
+        bs, nh, n, d = query_states.shape
+        nk = self.num_key_value_heads
+        if bs != self.bs or nh != self.nh or d != self.d or key_states.shape != (bs, nk, n, d) or value_states.shape != key_states.shape:
+            raise RuntimeError(f"verify: q (bs, nh, n, d) and K/V (bs, nh_k, n, d) of this cache expected, got {tuple(query_states.shape)} "
+                               f"{tuple(key_states.shape)} {tuple(value_states.shape)}")
+        if not 1 <= n <= self.VERIFY_MAX_ROWS:
+            raise RuntimeError(f"verify: {n} draft rows (1 .. {self.VERIFY_MAX_ROWS})")
+        n_draft = [n] * bs if n_draft is None else [int(x) for x in n_draft]
+        if len(n_draft) != bs or any(not 0 <= x <= n for x in n_draft):
+            raise RuntimeError(f"verify: one n_draft per slot, each in [0, {n}]")
+        route = self._verify_route(n) if route is None else route
+        if route not in ("heads", "chunk"):
+            raise RuntimeError(f"verify: route {route!r} ('heads', 'chunk' or None)")
+        self._join_flush(layer_idx)
+        if not use_dev_lengths and not self._lockstep(layer_idx):
+            raise RuntimeError("PagedPQCache: requests at different lengths need use_dev_lengths=True")
+        rec = self._verify_rec
+        sig = self._mirror_sig()
+        if rec is None or rec["n"] != n or rec["n_draft"] != n_draft or any(not np.array_equal(a, b) for a, b in zip(rec["sig"], sig)):
+            rec = self._verify_rec = {"n": n, "n_draft": n_draft, "sig": sig, "layers": set(),
+                                      "dev_n": torch.tensor(n_draft, dtype=torch.int32).to(self.device)}
+        dev_n = rec["dev_n"]
+        if self._kstage is None:
+            shape = (self.layer_num, self.bs, nk, self.VERIFY_MAX_ROWS, self.d)
+            self._kstage = torch.zeros(shape, dtype=self.scalar_t, device=self.device)
+            self._vstage = torch.zeros(shape, dtype=self.scalar_t, device=self.device)
+        ks, vs = self._kstage[layer_idx], self._vstage[layer_idx]
+        T, r, rs = int(self._T_a[layer_idx, 0]), int(self._r_a[layer_idx, 0]), int(self._rs_a[layer_idx, 0])
+        dl = self.lengths[layer_idx] if use_dev_lengths else None
+        ids = self.page_ids[layer_idx]
+        kres, vres = self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx]
+        if route == "heads":
+            qv = query_states.contiguous()
+            qh = qv.view(bs, nh * n, 1, d)
+            ws = self._ws_verify
+            if n not in ws:      # the decode launch's workspace for nh n heads: zeroed once, every call leaves it ready
+                need = ops.decode_workspace_bytes(qh, kres, nh_k=nk, M=self.M, C=self.C)
+                ws[n] = torch.zeros(need, dtype=torch.uint8, device=self.device)
+            out_a, lse_a = ops.pq_decode_attn(qh, self.key_page_pool, self.value_page_pool, self._kprep, self._vprep, kres, vres, r,
+                                              M=self.M, C=self.C, n_tokens=self.max_tokens if use_dev_lengths else T, resid_start=rs,
+                                              k_page_ids=ids, v_page_ids=ids, page_size=self.page_size, dev_lengths=dl,
+                                              workspace=ws[n], return_lse=True)
+            out_a, lse_a = out_a.view(bs, nh, n, d), lse_a.view(bs, nh, n)
+            res = ops.attn_block_merge(qv, key_states, value_states, out_a, lse_a, dev_n, out=out_a, return_lse=return_lse,
+                                       k_stage=ks, v_stage=vs)
+        else:
+            bound = int(self._T_a[layer_idx].max()) if use_dev_lengths else T
+            res = ops.pq_chunk_attn(query_states, key_states, value_states, self.key_page_pool, self.value_page_pool, self._kprep,
+                                    self._vprep, kres, vres, r, M=self.M, C=self.C, n_tokens=bound, resid_start=rs, k_page_ids=ids,
+                                    v_page_ids=ids, page_size=self.page_size, dev_lengths=dl, dev_n_q=dev_n,
+                                    **({"return_lse": True} if return_lse else {}))
+            ks[:, :, :n].copy_(key_states)
+            vs[:, :, :n].copy_(value_states)
+        rec["layers"].add(layer_idx)
+        return res
+
+    def _note_committed(self, n_accept):
+        """commit() appended n_accept[b] rows to the window of slot b in every layer, as that many decode steps: a window the
+        rows overflow was flushed once first (_note_flushed: T, r, the ring start, the encoded-ahead flag), then the append rule."""
+        cap = self.extended_residual_size
+        for b, a in enumerate(n_accept):
+            if a:
+                over = self._r_a[:, b] + a > cap
+                if over.any():
+                    self._note_flushed((over, b))
+                self._r_a[:, b] += a
+                self._seen_a[:, b] += a
+
+    def commit(self, n_accept):
+        """Append the first n_accept[b] of the rows verify() staged to the window of slot b, in every layer and in ONE call
+        (ops.window_commit), exactly as n_accept[b] decode steps with those rows would have: codes, pages, window rows, host
+        and device lengths; decoding_with_pages, begin_step, fork, swap_out and extend_* go on as after those steps.
+        n_accept: bs host ints, 0 <= n_accept[b] <= n_draft[b] of the verify() that must have run for every layer since the
+        cache last moved.  Call it between steps, as fork: refused (RuntimeError, before anything moves) mid-step, while a
+        side-stream flush is pending, without a full verify, and when a slot's flush would pass max_tokens or the free
+        pages.  A finished encode-ahead launch (begin_step) is joined first; pages on demand are taken before the launch."""
+        n_accept = [int(x) for x in n_accept]
+        rec = self._verify_rec
+        nl, ps, cap, nk = self.layer_num, self.page_size, self.extended_residual_size, self.num_key_value_heads
+        cols = (self._T_a, self._r_a, self._rs_a)
+        if self._ahead is not None or self._flush_events or any((c != c[0]).any() for c in cols):
+            raise RuntimeError("commit: the cache is mid-step (layers at different lengths, or a side-stream flush pending); commit between steps")
+        if rec is None or len(rec["layers"]) != nl or any(not np.array_equal(a, b) for a, b in zip(rec["sig"], self._mirror_sig())):
+            raise RuntimeError("commit: verify() must have run for every layer, with the same n_draft, since the cache last moved")
+        if len(n_accept) != self.bs or any(not 0 <= a <= nd for a, nd in zip(n_accept, rec["n_draft"])):
+            raise RuntimeError(f"commit: one n_accept per slot, each in [0, n_draft[b]] (n_draft = {rec['n_draft']})")
+        flush = [b for b, a in enumerate(n_accept) if a and self._r_a[0, b] + a > cap]
+        for b in flush:
+            if int(self._T_a[0, b]) + ps > self.max_tokens:
+                raise RuntimeError(f"PagedPQCache: {int(self._T_a[0, b]) + ps} tokens exceed max_tokens={self.max_tokens}")
+        if not self.preallocate and flush:
+            pm = self.page_manager
+            need = sum(max(0, -(-(int(self._T_a[l, b]) + ps) // ps) - int(self._pages_a[l, b])) for l in range(nl) for b in flush) * nk
+            room = pm.max_pages - pm.current_active_pages if pm.max_pages is not None else need
+            if len(pm.free_pages) + room < need:
+                raise RuntimeError(f"commit: {need} free pages needed, {len(pm.free_pages) + room} left")
+        if self._pre_join:
+            torch.cuda.current_stream().wait_stream(self._side)      # rows encoded ahead: a flush below encodes them again, same codes
+            self._pre_join = False
+        for b in flush:
+            for l in range(nl):
+                self._reserve(l, ps, b)
+        self._verify_rec = None
+        if not any(n_accept):
+            return
+        dev_n = torch.tensor(n_accept, dtype=torch.int32).to(self.device)
+        ops.window_commit(self._kstage, self._vstage, self._kres_all, self._vres_all, self._kprep, self._vprep, self.key_page_pool,
+                          self.value_page_pool, self._page_ids_all, self._lengths_all, dev_n, M=self.M, C=self.C, n_bound=rec["n"])
+        self._note_committed(n_accept)
 
     # ---- host mirror management for captured (hipGraph) decode steps ------------------------------
     # During stream capture the Python above runs once (advancing the host mirror) but no kernel
