@@ -50,10 +50,7 @@ __global__ __launch_bounds__(64) void attn_block_merge_kernel(BlockMergeParams p
     const int i = lane >> 2, part = lane & 3;
     const int n = p.n;
     int nb = n;
-    if (p.dev_n) {
-        nb = p.dev_n[b];
-        nb = nb < 0 ? 0 : (nb > n ? n : nb);
-    }
+    if (p.dev_n) nb = clamp_count(p.dev_n[b], n);
     nb = __builtin_amdgcn_readfirstlane(nb);
     const int ic = i < n ? i : n - 1;      // lanes past the block read its last row and store nothing
 

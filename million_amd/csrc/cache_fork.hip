@@ -51,16 +51,12 @@ struct ForkParams {
     long long n_tasks;
 };
 
-// The source's row of layer l as every task reads it.  Device-resident values are not trusted: T into [0, cap_tok] (cap_tok =
-// n_pages_bound * page_size), r into [0, resid_cap], a start outside [0, resid_cap) reads as 0; then the prefix.
+// The source's row of layer l as every task reads it: load_len_row (common.h) with T into [0, cap_tok] (cap_tok =
+// n_pages_bound * page_size) and r into [0, resid_cap]; then the prefix.
 __device__ __forceinline__ void fork_load_row(const ForkParams &p, int l, int &T, int &r, int &st) {
     // through the constant address space: the source's row is never written while this kernel runs
     typedef const __attribute__((address_space(4))) int *const_p;
-    const_p row = (const_p)(p.dev_lengths + l * p.len_ls + 4ll * p.src);
-    T = row[0]; r = row[1]; st = row[2];
-    T = T < 0 ? 0 : (T > p.cap_tok ? p.cap_tok : T);
-    r = r < 0 ? 0 : (r > p.rcap ? p.rcap : r);
-    st = (unsigned)st < (unsigned)p.rcap ? st : 0;
+    load_len_row((const_p)(p.dev_lengths + l * p.len_ls + 4ll * p.src), p.cap_tok, p.rcap, p.rcap, T, r, st);
     if (p.prefix >= 0) { T = T < p.prefix ? T : p.prefix; r = 0; st = 0; }
 }
 
@@ -184,7 +180,8 @@ extern "C" int million_cache_fork(const million_fork_desc *desc, int32_t *page_i
                                   const int32_t *tail_ids, million_stream_t stream) {
     if (!desc || desc->struct_size != sizeof(million_fork_desc)) { set_error("cache_fork: bad desc / struct_size"); return MILLION_ERR_ARG; }
     const million_fork_desc &d = *desc;
-    if (d.page_size != 32 && d.page_size != 64 && d.page_size != 128) { set_error("cache_fork: page_size=%d (32, 64 or 128)", d.page_size); return MILLION_ERR_SHAPE; }
+    int ps_shift;
+    if (!page_shift("cache_fork", d.page_size, ps_shift)) return MILLION_ERR_SHAPE;
     if (d.M != 16 && d.M != 32 && d.M != 64) { set_error("cache_fork: M=%d (16, 32 or 64)", d.M); return MILLION_ERR_SHAPE; }
     if (d.n_layers <= 0 || d.bs <= 0 || d.nh_k <= 0 || d.d <= 0 || (d.d & 7) || d.n_pages_cap <= 0 || d.n_pool <= 0 || d.resid_cap < 0) {
         set_error("cache_fork: n_layers=%d bs=%d nh_k=%d d=%d (a multiple of 8) n_pages_cap=%d n_pool=%d resid_cap=%d", d.n_layers, d.bs,
@@ -223,7 +220,7 @@ extern "C" int million_cache_fork(const million_fork_desc *desc, int32_t *page_i
     p.dev_lengths = dev_lengths; p.dst_slots = dst_slots; p.tail_ids = tail_ids;
     p.ids_ls = d.ids_layer_stride; p.win_ls_bytes = d.rows_layer_stride * 2; p.len_ls = d.lengths_layer_stride;
     p.n_layers = d.n_layers; p.bs = d.bs; p.nh_k = d.nh_k; p.n_pages_cap = d.n_pages_cap; p.n_pool = d.n_pool;
-    p.page_size = d.page_size; p.ps_shift = d.page_size == 32 ? 5 : d.page_size == 64 ? 6 : 7;
+    p.page_size = d.page_size; p.ps_shift = ps_shift;
     p.page_bytes = d.page_size * d.M;
     p.pb_shift = p.ps_shift + (d.M == 16 ? 4 : d.M == 32 ? 5 : 6);
     p.rcap = d.resid_cap; p.win_bytes = d.resid_cap * d.d * 2;

@@ -48,9 +48,9 @@ struct SwapParams {
     long long n_tasks;
 };
 
-// Entry js of the slot table as every task reads it, or false when it takes no part.  Device-resident values are not trusted:
-// T into [0, cap_tok] (cap_tok = n_pages_bound * page_size), r into [0, resid_cap], a start outside [0, resid_cap) reads as 0; the
-// slot must lie in [0, bs) and the entry's rows inside the blob, 16-byte aligned.
+// Entry js of the slot table as every task reads it, or false when it takes no part.  Its {T, r, start} are a lengths row behind
+// the slot word: load_len_row (common.h) with T into [0, cap_tok] (cap_tok = n_pages_bound * page_size) and r into [0, resid_cap];
+// the slot must lie in [0, bs) and the entry's rows inside the blob, 16-byte aligned.
 __device__ __forceinline__ bool swap_entry(const SwapParams &p, int js, int &slot, int &T, int &r, int &st, int &n_live,
                                            long long &row_bytes, long long &off) {
     // through the constant address space: the table and the offsets are never written while this kernel runs
@@ -60,9 +60,7 @@ __device__ __forceinline__ bool swap_entry(const SwapParams &p, int js, int &slo
     slot = tab[4 * js]; T = tab[4 * js + 1]; r = tab[4 * js + 2]; st = tab[4 * js + 3];
     off = ((const_pl)p.offsets)[js];
     if ((unsigned)slot >= (unsigned)p.bs) return false;
-    T = T < 0 ? 0 : (T > p.cap_tok ? p.cap_tok : T);
-    r = r < 0 ? 0 : (r > p.rcap ? p.rcap : r);
-    st = (unsigned)st < (unsigned)p.rcap ? st : 0;
+    clamp_len_row(p.cap_tok, p.rcap, p.rcap, T, r, st);
     n_live = (int)(((long long)T + p.page_size - 1) >> p.ps_shift);      // <= n_pages_bound <= n_pages_cap
     row_bytes = ((long long)n_live << (p.pb_shift + 1)) + 2ll * r * p.row_b;
     const long long rows = (long long)p.n_layers_call * p.nh_k;      // rows * row_bytes fits 62 bits: validated on the host
@@ -206,7 +204,8 @@ extern "C" int million_cache_swap(const million_swap_desc *desc, const int32_t *
                                   void *blob, million_stream_t stream) {
     if (!desc || desc->struct_size != sizeof(million_swap_desc)) { set_error("cache_swap: bad desc / struct_size"); return MILLION_ERR_ARG; }
     const million_swap_desc &d = *desc;
-    if (d.page_size != 32 && d.page_size != 64 && d.page_size != 128) { set_error("cache_swap: page_size=%d (32, 64 or 128)", d.page_size); return MILLION_ERR_SHAPE; }
+    int ps_shift;
+    if (!page_shift("cache_swap", d.page_size, ps_shift)) return MILLION_ERR_SHAPE;
     if (d.M != 16 && d.M != 32 && d.M != 64) { set_error("cache_swap: M=%d (16, 32 or 64)", d.M); return MILLION_ERR_SHAPE; }
     if (d.n_layers <= 0 || d.bs <= 0 || d.nh_k <= 0 || d.d <= 0 || (d.d & 7) || d.n_pages_cap <= 0 || d.n_pool <= 0 || d.resid_cap < 0) {
         set_error("cache_swap: n_layers=%d bs=%d nh_k=%d d=%d (a multiple of 8) n_pages_cap=%d n_pool=%d resid_cap=%d", d.n_layers, d.bs,
@@ -255,7 +254,7 @@ extern "C" int million_cache_swap(const million_swap_desc *desc, const int32_t *
     p.ids_ls = d.ids_layer_stride; p.win_ls_bytes = d.rows_layer_stride * 2; p.len_ls = d.lengths_layer_stride;
     p.blob_bytes = d.blob_bytes;
     p.bs = d.bs; p.nh_k = d.nh_k; p.n_pages_cap = d.n_pages_cap; p.n_pool = d.n_pool;
-    p.page_size = d.page_size; p.ps_shift = d.page_size == 32 ? 5 : d.page_size == 64 ? 6 : 7;
+    p.page_size = d.page_size; p.ps_shift = ps_shift;
     p.m_shift = d.M == 16 ? 4 : d.M == 32 ? 5 : 6;
     p.pb_shift = p.ps_shift + p.m_shift;
     p.row_b = d.d * 2; p.rcap = d.resid_cap; p.win_bytes = d.resid_cap * d.d * 2;

@@ -128,20 +128,8 @@ __device__ __forceinline__ pv4u ca_dequant(unsigned long long w, unsigned tab, i
     return v;
 }
 
-// RAGGED: a request's device row, never trusted - T into [0, bound], r into [0, rcap], a start outside the ring reads as 0
-// (clamp_lengths of common.h); word 3 is not touched
-__device__ __forceinline__ void ca_load_lengths(const ChunkParams &p, int b, int &T, int &r, int &rs) {
-    T = p.dev_lengths[4 * b];
-    r = p.dev_lengths[4 * b + 1];
-    rs = p.dev_lengths[4 * b + 2];
-    T = T < 0 ? 0 : (T > p.T ? p.T : T);
-    r = r < 0 ? 0 : (r > p.rcap ? p.rcap : r);
-    rs = (unsigned)rs < (unsigned)p.rcap ? rs : 0;
-}
-__device__ __forceinline__ int ca_load_n_q(const ChunkParams &p, int b) {
-    const int n = p.dev_n_q[b];
-    return n < 0 ? 0 : (n > p.n_q ? p.n_q : n);
-}
+// RAGGED: a request's valid query rows, never trusted (its lengths row: load_len_row of common.h, T into [0, the bound p.T])
+__device__ __forceinline__ int ca_load_n_q(const ChunkParams &p, int b) { return clamp_count(p.dev_n_q[b], p.n_q); }
 // the log-sum-exp slot of query row qi of head `head`: indexed like out without the d axis, contiguous
 __device__ __forceinline__ float *ca_lse_at(const ChunkParams &p, int b, int head, int qi) {
     return p.lse + ((long long)b * p.nh + head) * p.n_q + qi;
@@ -178,7 +166,7 @@ __global__ __launch_bounds__(kThreads, 1) void chunk_attn_kernel(ChunkParams p) 
     int T = p.T, r = p.r, rs = p.rs, ntT = p.ntT, ntR = p.ntR, n_c = p.n_c, nrows = p.nrows;
     if (RAGGED) {
         if (p.dev_lengths) {
-            ca_load_lengths(p, b, T, r, rs);
+            load_len_row(p.dev_lengths + 4 * b, p.T, p.rcap, p.rcap, T, r, rs);
             ntT = (T + kKeys - 1) / kKeys;
             ntR = (r + kKeys - 1) / kKeys;
         }
@@ -458,10 +446,7 @@ static int chunk_attn_impl(const million_chunk_attn_desc *desc, const void *q, c
     if (!desc || desc->struct_size != sizeof(million_chunk_attn_desc)) { set_error("chunk_attn: bad desc / struct_size"); return MILLION_ERR_ARG; }
     const million_chunk_attn_desc &d = *desc;
     if (d.bs <= 0 || d.nh <= 0 || d.nh_k <= 0 || d.nh % d.nh_k) { set_error("chunk_attn: bs=%d nh=%d nh_k=%d", d.bs, d.nh, d.nh_k); return MILLION_ERR_SHAPE; }
-    if ((d.d != 128 && d.d != 64) || (d.M != 16 && d.M != 32 && d.M != 64) || d.C < 1 || d.C > 256) {
-        set_error("chunk_attn: d=%d M=%d C=%d (d 64 / 128, M 16 / 32 / 64, C 1 .. 256)", d.d, d.M, d.C);
-        return MILLION_ERR_SHAPE;
-    }
+    if (!u8_geometry("chunk_attn", d.d, d.M, d.C)) return MILLION_ERR_SHAPE;
     if (d.n_q < 0 || (d.n_c != 0 && d.n_c != d.n_q)) { set_error("chunk_attn: n_q=%d n_c=%d (n_c must be 0 or n_q)", d.n_q, d.n_c); return MILLION_ERR_SHAPE; }
     const bool dev_len = d.dev_lengths != nullptr;      // n_tokens is then the bound; r and resid_start are not read
     if (d.n_tokens < 0 || d.resid_cap < 0 ||
@@ -475,7 +460,8 @@ static int chunk_attn_impl(const million_chunk_attn_desc *desc, const void *q, c
     }
     const bool any_paged = d.k_layout == MILLION_KV_PAGED || d.v_layout == MILLION_KV_PAGED;
     if (any_paged && d.n_tokens > 0) {
-        if (d.page_size != 32 && d.page_size != 64 && d.page_size != 128) { set_error("chunk_attn: page_size=%d (32, 64 or 128)", d.page_size); return MILLION_ERR_SHAPE; }
+        int ps_shift;      // the kernel divides by p.ps
+        if (!page_shift("chunk_attn", d.page_size, ps_shift)) return MILLION_ERR_SHAPE;
         if ((long long)d.n_pages_cap * d.page_size < d.n_tokens) { set_error("chunk_attn: %d pages of %d tokens hold fewer than n_tokens=%d", d.n_pages_cap, d.page_size, d.n_tokens); return MILLION_ERR_SHAPE; }
     }
     if (d.n_q == 0) return MILLION_OK;

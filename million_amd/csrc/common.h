@@ -191,21 +191,33 @@ __device__ __forceinline__ void store_lse(const AttnParams &p, int b, int hk, in
     p.lse[(long long)b * p.nh + head0(p, hk) + g] = v;
 }
 
-// Device-resident lengths are not trusted: T is clamped to the host bound the grid was sized for, r to the window
-// capacity (minus the row a fused append is about to add), the ring start to [0, cap).  Out-of-range values become a
-// shorter context / window, never an out-of-bounds read.
+// ---- device-resident length rows {T, r, start, _} ----
+// The one rule that makes such a row safe to read, for every kernel that reads one: T is clamped into [0, T_max], r into
+// [0, r_max], a ring start outside [0, resid_cap) reads as 0, word 3 is not touched.  Out-of-range values become a shorter
+// context / window, never an out-of-bounds access.  IntP: a plain pointer, or one in the constant address space where the row is
+// not written while the kernel runs (scalar loads).  The one reader that is not a call of this: the advance at the end of
+// pq_flush_kernel (encode.hip), which clamps T against T + n_flush and leaves r unbounded above, and whose code does not
+// survive a folded row read (profiles/pq_scan_refactor.txt A.3).
+__device__ __forceinline__ int clamp_count(int n, int bound) { return n < 0 ? 0 : (n > bound ? bound : n); }
+__device__ __forceinline__ void clamp_len_row(int T_max, int r_max, int resid_cap, int &T, int &r, int &start) {
+    T = clamp_count(T, T_max);
+    r = clamp_count(r, r_max);
+    start = (unsigned)start < (unsigned)resid_cap ? start : 0;
+}
+template <typename IntP>
+__device__ __forceinline__ void load_len_row(IntP row, int T_max, int r_max, int resid_cap, int &T, int &r, int &start) {
+    T = row[0]; r = row[1]; start = row[2];
+    clamp_len_row(T_max, r_max, resid_cap, T, r, start);
+}
+
+// Decode attention: T against the host bound the grid was sized for, r against the window capacity minus the row a fused
+// append is about to add.  (The MFMA kernels load the row themselves, attn_front.h, and clamp it here.)
 __device__ __forceinline__ void clamp_lengths(const AttnParams &p, int &T, int &r, int &rstart) {
-    T = T < 0 ? 0 : (T > p.T ? p.T : T);
-    const int rmax = p.rcap - (p.k_new ? 1 : 0);
-    r = r < 0 ? 0 : (r > rmax ? rmax : r);
-    rstart = (unsigned)rstart < (unsigned)p.rcap ? rstart : 0;
+    clamp_len_row(p.T, p.rcap - (p.k_new ? 1 : 0), p.rcap, T, r, rstart);
 }
 __device__ __forceinline__ void load_lengths(const AttnParams &p, int b, int &T, int &r, int &rstart) {
     if (p.dev_lengths) {
-        T = p.dev_lengths[b * 4 + 0];
-        r = p.dev_lengths[b * 4 + 1];
-        rstart = p.dev_lengths[b * 4 + 2];
-        clamp_lengths(p, T, r, rstart);
+        load_len_row(p.dev_lengths + b * 4, p.T, p.rcap - (p.k_new ? 1 : 0), p.rcap, T, r, rstart);
     } else {
         T = p.T; r = p.r; rstart = p.rstart;
     }
@@ -497,6 +509,28 @@ struct FlushLayers { int n_layers; long long x_ls, ids_ls, len_ls; int advance; 
 int launch_flush(const EncParams &k, const EncParams &v, int *dev_lengths_w, int rcap, int min_r, const FlushLayers &ly, hipStream_t s);
 int launch_rows_reduce_check(const float *in, float *out_max, float *out_sum, hipStream_t s);
 void set_error(const char *fmt, ...);
+
+// ---- host halves the entry points share.  `who` is the entry point's name in the message; the error code is the caller's ----
+// Pages hold 32, 64 or 128 tokens.  ps_shift is set either way (7 for anything else: million_api.hip's row-major calls).
+inline bool page_shift_quiet(int page_size, int &ps_shift) {
+    ps_shift = page_size == 32 ? 5 : page_size == 64 ? 6 : 7;
+    return page_size == 32 || page_size == 64 || page_size == 128;
+}
+inline bool page_shift(const char *who, int page_size, int &ps_shift) {
+    if (page_shift_quiet(page_size, ps_shift)) return true;
+    set_error("%s: page_size=%d (32, 64 or 128)", who, page_size);
+    return false;
+}
+// The (d, M, C) the kernels over uint8 codes are built for; d/M is then 1, 2, 4 or 8 or the dispatch says so
+inline bool u8_geometry(const char *who, int d, int M, int C) {
+    if ((d == 128 || d == 64) && (M == 16 || M == 32 || M == 64) && C >= 1 && C <= 256) return true;
+    set_error("%s: d=%d M=%d C=%d (d 64 / 128, M 16 / 32 / 64, C 1 .. 256: uint8 codes)", who, d, M, C);
+    return false;
+}
+// A prepared codebook (million_prepare_cents) is two fp16 images of M * C * dm elements, then the fp32 row image [m][c][dm]
+inline const float *prepared_cents32(const void *prepared, int M, int C, int dm) {
+    return (const float *)((const f16 *)prepared + 2 * (size_t)M * C * dm);
+}
 
 // Per-device facts and one-time per-device setup (one process may drive several devices): CU count, and a set of
 // "dynamic-LDS attribute already raised on this device" bits, one per kernel family.  Guarded by a mutex.

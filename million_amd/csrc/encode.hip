@@ -240,7 +240,7 @@ __global__ __launch_bounds__(kFlushWaves * 64) void pq_flush_kernel(FlushParams 
             // alike, before any barrier and before the ticket)
             if (f.min_r > 0 && dev_lengths[b * 4 + 1] < f.min_r) continue;
         }
-        // device-resident values are not trusted (cf. clamp_lengths): a start outside the ring becomes 0, a destination
+        // device-resident values are not trusted (cf. load_len_row): a start outside the ring becomes 0, a destination
         // outside the page table drops the store
         if (p.xrow_mod > 0 && (unsigned)xrow_start >= (unsigned)p.xrow_mod) xrow_start = 0;
         float x[DM];

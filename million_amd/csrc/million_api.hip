@@ -191,9 +191,9 @@ static int fill_attn_params(const million_attn_desc *desc, AttnParams &p) {
     p.page_size = desc->page_size; p.n_pages_cap = desc->n_pages_cap; p.ids64 = desc->page_ids_i64;
     p.v_identity = desc->v_pages_dense != 0;
     if (p.v_identity && !p.v_paged) { set_error("attn: v_pages_dense needs v_layout = PAGED"); return MILLION_ERR_ARG; }
-    p.ps_shift = p.page_size == 32 ? 5 : p.page_size == 64 ? 6 : 7;
+    const bool ps_ok = page_shift_quiet(p.page_size, p.ps_shift);
     if (p.k_paged || p.v_paged) {
-        if (p.page_size != 32 && p.page_size != 64 && p.page_size != 128) { set_error("attn: page_size=%d (32, 64, 128)", p.page_size); return MILLION_ERR_SHAPE; }
+        if (!ps_ok) { set_error("attn: page_size=%d (32, 64, 128)", p.page_size); return MILLION_ERR_SHAPE; }
         if ((long long)p.n_pages_cap * p.page_size < p.T) { set_error("attn: n_pages_cap*page_size < n_tokens"); return MILLION_ERR_ARG; }
         // the kernels index the table with 32-bit arithmetic (int64 ids: two dwords per entry)
         if (p.n_pages_cap < 0 || (long long)p.bs * p.nh_k * p.n_pages_cap > (p.ids64 ? 0x3fffffffLL : 0x7fffffffLL)) { set_error("attn: page table of %lld entries", (long long)p.bs * p.nh_k * p.n_pages_cap); return MILLION_ERR_ARG; }
@@ -268,7 +268,7 @@ static int fill_enc_params(const char *who, const million_encode_desc *desc, con
     memset(&p, 0, sizeof(p));
     p.x = (const f16 *)x; p.cents = (const f16 *)cents; p.dst = (uint8_t *)dst; p.page_ids = page_ids;
     if (desc->cents_prepared && desc->C <= 256)
-        p.cents32 = (const float *)((const f16 *)desc->cents_prepared + 2 * (size_t)desc->M * desc->C * (desc->d / (desc->M > 0 ? desc->M : 1)));
+        p.cents32 = prepared_cents32(desc->cents_prepared, desc->M, desc->C, desc->d / (desc->M > 0 ? desc->M : 1));
     p.bs = desc->bs; p.nh_k = desc->nh_k; p.n = desc->n; p.d = desc->d; p.M = desc->M; p.C = desc->C;
     if (p.bs <= 0 || p.nh_k <= 0 || p.n < 0) { set_error("%s: bs=%d nh_k=%d n=%d", who, p.bs, p.nh_k, p.n); return MILLION_ERR_SHAPE; }
     if (p.M <= 0 || p.d <= 0 || p.d % p.M) { set_error("%s: d=%d M=%d", who, p.d, p.M); return MILLION_ERR_SHAPE; }

@@ -1,5 +1,5 @@
 // pq_scan.h — the nearest-centroid scan of the PQ encoder kernels: pq_encode_kernel and pq_encode_small_kernel (encode.hip),
-// kmeans_assign_kernel (train.hip), pq_store_ragged_kernel (store_ragged.hip).  The scan is written here and nowhere else,
+// kmeans_assign_kernel (train.hip), paged_store_kernel (paged_store.h: the ragged store and the window commit).  The scan is written here and nowhere else,
 // with one exception: pq_flush_kernel (encode.hip) carries pq_scan_lds's loop in its own body (see there).
 //
 // Arithmetic contract (bit-exact with oracle/pq_oracle.c:pq_encode_direct): e = x - c, sq = e * e,

@@ -82,10 +82,9 @@ __device__ __forceinline__ PrefillRows prefill_rows(const PrefillParams &p, int 
         // scalar loads (a plain global pointer might alias out: one vector load and three v_readfirstlane instead)
         typedef const __attribute__((address_space(4))) int *spans_p;
         const spans_p row = (spans_p)(p.dev_spans + 4 * (long long)w.b);
-        n_q = row[0]; n_kv = row[1]; q_pos0 = row[2];
-        n_q = n_q < 0 ? 0 : (n_q > p.n_q ? p.n_q : n_q);
-        n_kv = n_kv < 0 ? 0 : (n_kv > p.n_kv ? p.n_kv : n_kv);
-        q_pos0 = q_pos0 < 0 ? 0 : (q_pos0 > p.n_kv ? p.n_kv : q_pos0);
+        n_q = clamp_count(row[0], p.n_q);
+        n_kv = clamp_count(row[1], p.n_kv);
+        q_pos0 = clamp_count(row[2], p.n_kv);
     }
     w.n_q = n_q;
     w.n_kv = n_kv;

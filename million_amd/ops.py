@@ -34,6 +34,16 @@ def _need_cuda(*ts):
             raise RuntimeError("million_amd ops need device tensors (no CPU fallback)")
 
 
+def _check_prepared(who: str, k_prep: torch.Tensor, v_prep: torch.Tensor, M: int, C: int, d: int) -> None:
+    if k_prep.dtype != torch.float16 or v_prep.dtype != torch.float16 or k_prep.numel() != v_prep.numel() or k_prep.numel() != 4 * M * C * (d // M):
+        raise RuntimeError(f"{who}: k_prep / v_prep must be the prepared codebooks of (M, C, d / M) (prepare_cents)")
+
+
+def _check_dev_n(who: str, dev_n: torch.Tensor, bs: int) -> None:
+    if dev_n.dtype != torch.int32 or tuple(dev_n.shape) != (bs,) or not dev_n.is_contiguous():
+        raise RuntimeError(f"{who}: dev_n must be contiguous int32 (bs,)")
+
+
 def prepare_cents(cents: torch.Tensor, cache: bool = True) -> torch.Tensor:
     """(M, C, d_m) fp16 codebook -> LDS-ready images (row image + column image), see million_prepare_cents.
 
@@ -224,16 +234,14 @@ def pq_store_ragged(k_new: torch.Tensor, v_new: torch.Tensor, k_res: Optional[to
                 or k_res.stride(3) != 1 or k_res.stride(2) != d):
             raise RuntimeError("pq_store_ragged: windows must be fp16 (bs, nh_k, cap, d) with dense rows, K and V alike")
         cap = k_res.shape[2]
-    if k_prep.dtype != torch.float16 or v_prep.dtype != torch.float16 or k_prep.numel() != v_prep.numel() or k_prep.numel() != 4 * M * C * (d // M):
-        raise RuntimeError("pq_store_ragged: k_prep / v_prep must be the prepared codebooks of (M, C, d / M) (prepare_cents)")
+    _check_prepared("pq_store_ragged", k_prep, v_prep, M, C, d)
     if page_ids.dtype != torch.int32 or not page_ids.is_contiguous() or page_ids.dim() != 3 or page_ids.shape[:2] != (bs, nhk):
         raise RuntimeError("pq_store_ragged: contiguous int32 page_ids (bs, nh_k, n_pages_cap) expected")
     if not k_pool.is_contiguous() or not v_pool.is_contiguous():
         raise RuntimeError("pq_store_ragged: page pools must be contiguous")
     if dev_lengths.dtype != torch.int32 or dev_lengths.shape != (bs, 4) or not dev_lengths.is_contiguous():
         raise RuntimeError("pq_store_ragged: dev_lengths must be contiguous int32 (bs, 4)")
-    if dev_n.dtype != torch.int32 or dev_n.shape != (bs,) or not dev_n.is_contiguous():
-        raise RuntimeError("pq_store_ragged: dev_n must be contiguous int32 (bs,)")
+    _check_dev_n("pq_store_ragged", dev_n, bs)
     desc = L.StoreRaggedDesc()
     desc.struct_size = ctypes.sizeof(L.StoreRaggedDesc)
     desc.bs, desc.nh_k, desc.d, desc.M, desc.C, desc.n_bound = bs, nhk, d, M, C, n_bound
@@ -1000,8 +1008,8 @@ def attn_block_merge(q: torch.Tensor, k_blk: torch.Tensor, v_blk: torch.Tensor, 
         raise RuntimeError("attn_block_merge: out_a must be (bs, nh, n, d) with contiguous rows")
     if lse_a.dtype != torch.float32 or tuple(lse_a.shape) != (bs, nh, n) or not lse_a.is_contiguous():
         raise RuntimeError("attn_block_merge: lse_a must be contiguous fp32 (bs, nh, n)")
-    if dev_n is not None and (dev_n.dtype != torch.int32 or tuple(dev_n.shape) != (bs,) or not dev_n.is_contiguous()):
-        raise RuntimeError("attn_block_merge: dev_n must be contiguous int32 (bs,)")
+    if dev_n is not None:
+        _check_dev_n("attn_block_merge", dev_n, bs)
     if out is None:
         out = torch.empty(bs, nh, n, d, dtype=torch.float16, device=q.device)
     elif out.dtype != torch.float16 or tuple(out.shape) != (bs, nh, n, d) or out.stride(3) != 1:
@@ -1059,10 +1067,8 @@ def window_commit(k_new: torch.Tensor, v_new: torch.Tensor, k_res: torch.Tensor,
         raise RuntimeError("window_commit: fp16 windows (layers, bs, nh_k, cap, d), each layer contiguous, K and V alike, expected")
     if dev_lengths.dtype != torch.int32 or dev_lengths.shape != (n_layers, bs, 4) or not dev_lengths[0].is_contiguous():
         raise RuntimeError("window_commit: int32 dev_lengths (layers, bs, 4) expected")
-    if dev_n.dtype != torch.int32 or dev_n.shape != (bs,) or not dev_n.is_contiguous():
-        raise RuntimeError("window_commit: dev_n must be contiguous int32 (bs,)")
-    if k_prep.dtype != torch.float16 or v_prep.dtype != torch.float16 or k_prep.numel() != v_prep.numel() or k_prep.numel() != 4 * M * C * (d // M):
-        raise RuntimeError("window_commit: k_prep / v_prep must be the prepared codebooks of (M, C, d / M) (prepare_cents)")
+    _check_dev_n("window_commit", dev_n, bs)
+    _check_prepared("window_commit", k_prep, v_prep, M, C, d)
     desc = L.WindowCommitDesc()
     desc.struct_size = ctypes.sizeof(L.WindowCommitDesc)
     desc.n_layers, desc.bs, desc.nh_k, desc.d, desc.M, desc.C, desc.n_bound = n_layers, bs, nhk, d, M, C, n_bound

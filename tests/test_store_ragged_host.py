@@ -284,10 +284,12 @@ def test_model_rows_and_scatter():
 
 # ---------------------------------------------------------------- kernel metadata -------------------------------------------
 def test_every_store_ragged_instance_has_no_scratch_no_spills_no_lds(lib):
-    out = subprocess.run([sys.executable, str(ROOT / "tools" / "kernel_meta.py"), str(ROOT / "million_amd" / "libmillion_hip.so"), "pq_store_ragged"],
+    """paged_store_kernel<DM, P> (csrc/paged_store.h): the store's instances (P = StoreRaggedParams) and the commit's (WindowCommitParams)."""
+    out = subprocess.run([sys.executable, str(ROOT / "tools" / "kernel_meta.py"), str(ROOT / "million_amd" / "libmillion_hip.so"), "paged_store_kernel"],
                          capture_output=True, text=True, check=True).stdout
-    rows = [l for l in out.splitlines() if "pq_store_ragged_kernel" in l]
-    assert sorted(l.split()[0][l.index("ILi"):][:6] for l in rows) == ["ILi1EE", "ILi2EE", "ILi4EE", "ILi8EE"], out
-    for l in rows:
-        assert l.rstrip().endswith("vgpr_spill 0 sgpr_spill 0 scratch 0 B"), l
-        assert " lds 0 B " in l, l
+    for params in ("StoreRaggedParams", "WindowCommitParams"):
+        rows = [l for l in out.splitlines() if "paged_store_kernel" in l and params in l]
+        assert sorted(l.split()[0][l.index("ILi"):][:5] for l in rows) == ["ILi1E", "ILi2E", "ILi4E", "ILi8E"], out
+        for l in rows:
+            assert l.rstrip().endswith("vgpr_spill 0 sgpr_spill 0 scratch 0 B"), l
+            assert " lds 0 B " in l, l

@@ -360,6 +360,81 @@ def test_commit_equals_single_steps(cap, preallocate, fork, env):
     print(f"cap {cap} preallocate {preallocate} fork {fork}: {rounds} rounds, rows per slot {rows_in}, T {A._T_a[0].tolist()}")
 
 
+# ---------------------------------------------------------------- 4. million_window_commit on rows nobody checked ---------------
+# {T, r, start} per slot and dev_n: layer 0 and layer 1 hold different values for the same slots, so a wrong layer stride shows.
+UNTRUSTED_ROWS = [[(-5, 1000, 64), (250, 64, 5), (10, -3, -1), (40, 10, 70)],
+                  [(10 ** 9, 62, 63), (31, 63, 60), (-7, 9999, 12), (0, 0, -5)]]
+UNTRUSTED_N = [1000, 2, -4, 3]
+WORD3 = 0x7EADBEEF
+
+
+@pytest.mark.parametrize("d,M,C", [(64, 16, 128), (128, 64, 256)])
+def test_window_commit_on_untrusted_rows(d, M, C, env, oracle):
+    """ops.window_commit on lengths rows and row counts outside their ranges: T into [0, 256], r into [0, 64], a start outside
+    [0, 64) reads as 0, dev_n into [0, 4] (tests/store_ragged_model.clamp); then verify_model.commit_closed.  Layer 0: slot 0
+    (0, 64, 0) with 4 rows flushes tokens 0..31 and becomes (32, 36, 32); slot 1 would flush past the 256-token table and slot 2
+    has no rows: both untouched, the row included; slot 3 (40, 10, 0) takes 3 rows into ring slots 10..12.  Layer 1: slot 0's T far
+    past the table (untouched), slot 1 flushes tokens 31..62 across a page boundary.  Pools, windows, lengths, dev_n: every byte."""
+    from tests import store_ragged_model as SM
+    torch, ops = env
+    layers, bs, nhk, ps, cap, npc, nb = 2, 4, 2, 32, 64, 8, 4
+    rs = np.random.RandomState(d + M)
+    f16 = lambda *s: rs.standard_normal(s).astype(np.float16)
+    k_new, v_new = f16(layers, bs, nhk, nb, d), f16(layers, bs, nhk, nb, d)
+    k_win, v_win = f16(layers, bs, nhk, cap, d), f16(layers, bs, nhk, cap, d)
+    k_cents, v_cents = f16(M, C, d // M), f16(M, C, d // M)
+    n_real = layers * bs * nhk * npc
+    n_pool = n_real + 5                                                     # spare pages no table entry names
+    ids = rs.permutation(n_pool)[:n_real].reshape(layers, bs, nhk, npc).astype(np.int32)
+    lengths = np.array([[row + (WORD3,) for row in layer] for layer in UNTRUSTED_ROWS], np.int32)
+    k_pool, v_pool = np.full((n_pool, ps, M), 0xA5, np.uint8), np.full((n_pool, M, ps), 0xA5, np.uint8)
+
+    want_len, want_kw, want_vw, want_kp, want_vp = lengths.copy(), k_win.copy(), v_win.copy(), k_pool.copy(), v_pool.copy()
+    for l in range(layers):
+        for b in range(bs):
+            T, r, st, a = SM.clamp(UNTRUSTED_ROWS[l][b] + (UNTRUSTED_N[b],), cap_tok=npc * ps, resid_cap=cap, n_bound=nb)
+            T2, r2, st2, coded, ring = VM.commit_closed(T, r, st, a, ps, cap)
+            if a == 0 or T2 > npc * ps:
+                continue                                                    # no part / a flush past the table: nothing moves
+            want_len[l, b, :3] = (T2, r2, st2)
+            for win, new, cents, side in ((k_win, k_new, k_cents, "k"), (v_win, v_new, v_cents, "v")):
+                want_w = want_kw if side == "k" else want_vw
+                for slot, e in enumerate(ring):
+                    if e is not None and e[0] == "n":
+                        want_w[l, b, :, slot] = new[l, b, :, e[1]]
+                if coded:
+                    toks = sorted(coded)
+                    src = np.stack([win[l, b, :, (st + coded[t][1]) % cap] if coded[t][0] == "w" else new[l, b, :, coded[t][1]] for t in toks], axis=1)
+                    codes = oracle.pq_encode(src[None], cents)[0]           # (nh_k, tokens, M)
+                    for j, t in enumerate(toks):
+                        for h in range(nhk):
+                            if side == "k":
+                                want_kp[ids[l, b, h, t // ps], t % ps, :] = codes[h, j]
+                            else:
+                                want_vp[ids[l, b, h, t // ps], :, t % ps] = codes[h, j]
+    # what the table above says, before the kernel is asked
+    assert want_len[0, :, :3].tolist() == [[32, 36, 32], [250, 64, 5], [10, -3, -1], [40, 13, 0]]
+    assert want_len[1, :, :3].tolist() == [[10 ** 9, 62, 63], [63, 33, 28], [-7, 9999, 12], [0, 3, 0]]
+    assert np.array_equal(want_kw[0, 0, :, :4], k_new[0, 0]) and np.array_equal(want_vw[0, 3, :, 10:13], v_new[0, 3, :, :3])
+
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    kc, vc = dev(k_cents), dev(v_cents)
+    t = dict(k_new=dev(k_new), v_new=dev(v_new), k_win=dev(k_win), v_win=dev(v_win), k_pool=dev(k_pool), v_pool=dev(v_pool),
+             ids=dev(ids), lengths=dev(lengths), dev_n=dev(np.asarray(UNTRUSTED_N, np.int32)))
+    ops.window_commit(t["k_new"], t["v_new"], t["k_win"], t["v_win"], ops.prepare_cents(kc, cache=False), ops.prepare_cents(vc, cache=False),
+                      t["k_pool"], t["v_pool"], t["ids"], t["lengths"], t["dev_n"], M=M, C=C, n_bound=nb)
+    torch.cuda.synchronize()
+    got = {k: v.cpu().numpy() for k, v in t.items()}
+    assert got["dev_n"].tolist() == UNTRUSTED_N, "dev_n is read, never written"
+    assert (got["lengths"][:, :, 3] == WORD3).all(), "word 3 of a lengths row was written"
+    assert np.array_equal(got["lengths"], want_len), f"lengths {got['lengths'][:, :, :3].tolist()}, expected {want_len[:, :, :3].tolist()}"
+    for name, want in (("k_win", want_kw), ("v_win", want_vw)):
+        assert np.array_equal(got[name].view(np.uint16), want.view(np.uint16)), f"{name}: window rows differ at (layer, slot, head, row) {np.unique(np.argwhere(got[name] != want)[:, :4], axis=0)[:8].tolist()}"
+    for name, want in (("k_pool", want_kp), ("v_pool", want_vp)):
+        assert np.array_equal(got[name], want), f"{name}: pages {np.unique(np.argwhere(got[name] != want)[:, 0])[:8].tolist()} differ"
+    assert np.array_equal(got["k_new"], k_new) and np.array_equal(got["v_new"], v_new) and np.array_equal(got["ids"], ids)
+
+
 # ---------------------------------------------------------------- 5. refusals ---------------------------------------------------
 def test_commit_refusals_move_nothing(env):
     torch, ops = env

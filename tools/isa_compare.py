@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
 """Development helper: compare every kernel of two `hipcc --cuda-device-only -S` files (parent build, new build) - what a
 refactor that must not move the code has to show.
-    python tools/isa_compare.py parent/encode.s new/encode.s
+    python tools/isa_compare.py parent/encode.s new/encode.s [--map PARENT_NAME_PART=NEW_NAME_PART ...]
+--map: a renamed kernel is compared with the parent instance it replaces - the parent's (mangled) kernel names go through
+re.sub(PARENT_NAME_PART, NEW_NAME_PART) before the two sides are matched, e.g.
+    --map '22pq_store_ragged_kernelILi(.)EEEvNS_17StoreRaggedParamsE=18paged_store_kernelILi\\1ENS_17StoreRaggedParamsEEEvT0_'
 Per kernel: VGPR / AGPR / SGPR counts, static LDS, scratch, spills, code length, the opcode histogram, and the largest basic
 block by text length, picked as tools/isa_count.py picks it, with its vector-ALU count (columns big / big_valu).  That block
 is the unrolled centroid loop where the loop is one block; where the unrolled loop is split into several blocks (d_m = 1
 through the scalar cache, the LDS kernels) it is merely the longest block - still the same block on both sides.  The histogram may differ in padding, waits,
-moves and branches (ALLOWED) only; everything else must be equal.  Exit status 1 if any kernel misses that."""
+moves and branches (ALLOWED) only, and so may the largest block; everything else must be equal.  Opcodes are counted without their encoding suffix (_e32,
+_e64, _sdwa, _dpp): the same compare in another encoding is the same instruction.  Exit status 1 if any kernel misses that."""
 import collections
 import re
 import sys
@@ -16,7 +20,10 @@ FIG = [("vgpr", r"; NumVgprs: (\d+)"), ("agpr", r"; NumAgprs: (\d+)"), ("sgpr", 
        ("scratch", r"; ScratchSize: (\d+)"), ("len", r"; codeLenInByte = (\d+)")]
 
 
-def kernels(path):
+ENC = re.compile(r"_(e32|e64|sdwa|dpp)$")
+
+
+def kernels(path, renames=()):
     s = open(path).read()
     spills = {m.group(1): (m.group(2), m.group(3)) for m in
               re.finditer(r"\.name:\s+(_Z\w+)\n(?:.*\n)*?\s+\.sgpr_spill_count:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_spill_count:\s+(\d+)", s)}
@@ -27,18 +34,27 @@ def kernels(path):
         if not end:
             continue
         body = tail[:end.start()]
-        ops = lambda text: collections.Counter(l.split()[0] for l in text.splitlines()[1:] if l.strip() and not l.strip().startswith((".", ";")) and not l.strip().endswith(":"))
+        ops = lambda text: collections.Counter(ENC.sub("", l.split()[0]) for l in text.splitlines()[1:] if l.strip() and not l.strip().startswith((".", ";")) and not l.strip().endswith(":"))
         big = ops(max(re.split(r"^\.LBB\d+_\d+:.*$", body, flags=re.M), key=len))
         fig = {k: re.search(rx, tail).group(1) for k, rx in FIG}
         fig["sgpr_spill"], fig["vgpr_spill"] = spills.get(name, ("?", "?"))
         fig["big"] = str(sum(big.values()))
         fig["big_valu"] = str(sum(v for k, v in big.items() if k.startswith("v_")))
         text = [re.sub(r"\s*;.*$", "", l).strip() for l in body.splitlines()[1:]]
-        out[name] = (fig, ops(body), [l for l in text if l])
+        for old, new in renames:
+            name = re.sub(old, new, name)
+        out[name] = (fig, ops(body), [l for l in text if l], big)
     return out
 
 
-a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
+args = sys.argv[1:]
+renames = []
+while "--map" in args:
+    i = args.index("--map")
+    renames.append(tuple(args[i + 1].split("=", 1)))
+    del args[i:i + 2]
+sys.argv[1:] = args
+a, b = kernels(sys.argv[1], renames), kernels(sys.argv[2])
 bad = 0
 cols = [k for k, _ in FIG] + ["sgpr_spill", "vgpr_spill", "big", "big_valu"]
 print(f"{sys.argv[1]} (parent) | {sys.argv[2]} (new); {len(a)} / {len(b)} kernels")
@@ -48,10 +64,12 @@ for name in sorted(set(a) | set(b)):
         print(f"{name}: only in {'parent' if name in a else 'new'}  MISS")
         bad += 1
         continue
-    (fa, ha, ta), (fb, hb, tb) = a[name], b[name]
+    (fa, ha, ta, ba), (fb, hb, tb, bb) = a[name], b[name]
     diff = {k: (ha[k], hb[k]) for k in set(ha) | set(hb) if ha[k] != hb[k]}
     hard = {k: v for k, v in diff.items() if not k.startswith(ALLOWED)}
-    figs_ok = all(fa[k] == fb[k] for k in cols if k != "len")
+    # the largest block may differ by the allowed opcodes only
+    big_ok = all(k.startswith(ALLOWED) for k in set(ba) | set(bb) if ba[k] != bb[k])
+    figs_ok = all(fa[k] == fb[k] for k in cols if k not in ("len", "big", "big_valu")) and big_ok
     verdict = "text identical" if ta == tb else "text differs" + (f", histogram differs in {dict(sorted(diff.items()))}" if diff else ", histogram equal")
     if hard or not figs_ok:
         verdict += "  MISS"
