@@ -672,6 +672,28 @@ int million_attn_block_merge(const million_block_merge_desc *desc, const void *q
                              const int32_t *dev_n /* (bs,), may be NULL */, void *out, float *lse_out /* may be NULL */,
                              void *k_stage, void *v_stage /* may be NULL */, million_stream_t stream);
 
+/* The same launch for a draft that is a tree: n <= 16 nodes in topological order (a parent before its children), several
+ * candidates under one parent, several roots allowed.  million_attn_tree_merge takes the desc and the arguments of
+ * million_attn_block_merge and dev_mask, device (bs, n) int32, contiguous, 4-byte aligned, not NULL: bit j of word (b, i) says
+ * that row i of request b sees block row j - the node's ancestors and itself.  The word is read on the device and never
+ * trusted: the kernel uses
+ *   m = (mask & ((2u << i) - 1)) | (1u << i)
+ * so a row always sees itself and never a later row or a bit at or above n, whatever the word holds.  Everything else is
+ * million_attn_block_merge's contract with "j <= i" replaced by "bit j of m": the merge with (out_a, lse_a), NaN and -inf
+ * lse_a, dev_n (the live nodes are a prefix; the key loop runs to n_b), the staging of all n block rows, out aliasing out_a.
+ * Rows i >= n_b get out = 0 and lse_out = -inf, and neither their q / k / v / out_a nor their mask words reach a live row.  A
+ * mask of chains (bits 0 .. i) gives million_attn_block_merge's result bit for bit: a masked key has weight exactly 0 and the
+ * kept terms are added in the same ascending order.  The past part (out_a, lse_a) never looks at the order among the rows, so
+ * the decode launch (or chunk attention with n_c = 0) before this call is the one of a chain.  One plain launch of bs * nh
+ * single-wave workgroups, legal inside stream capture; the mask's contents may change between replays.  Validation precedes
+ * any HIP call, as above, plus: dev_mask NULL (MILLION_ERR_ARG) or not 4-byte aligned (MILLION_ERR_ALIGN). */
+int million_attn_tree_merge(const million_block_merge_desc *desc, const void *q /* (bs, nh, n, d) */,
+                            const void *k_blk, const void *v_blk /* (bs, nh_k, n, d) */,
+                            const void *out_a /* (bs, nh, n, d) */, const float *lse_a /* (bs, nh, n) */,
+                            const int32_t *dev_n /* (bs,), may be NULL */, const int32_t *dev_mask /* (bs, n) */, void *out,
+                            float *lse_out /* may be NULL */, void *k_stage, void *v_stage /* may be NULL */,
+                            million_stream_t stream);
+
 /* Append the first a_b = dev_n[b] rows of k_new / v_new (layers, bs, nh_k, n_bound, d) to request b's residual window in every
  * layer of a paged cache, exactly as a_b decode steps would have: a decode step flushes the oldest page_size window rows into
  * the pages when the window is full and then appends.  a_b is clamped into [0, n_bound]; n_bound <= 16 and n_bound <= page_size,
@@ -700,6 +722,20 @@ int million_window_commit(const million_window_commit_desc *desc, const void *k_
                           void *v_resid, const void *k_cents_prepared, const void *v_cents_prepared, void *k_pool,
                           void *v_pool, const int32_t *page_ids, int32_t *dev_lengths, const int32_t *dev_n,
                           million_stream_t stream);
+
+/* million_window_commit for chosen rows (the accepted root-to-node path of a draft tree): the a_b = dev_n[b] new rows of request
+ * b are rows dev_rows[b][0 .. a_b) of k_new / v_new, in that order, instead of rows 0 .. a_b.  dev_rows is device (bs, n_bound)
+ * int32, contiguous, 4-byte aligned, not NULL, one array for all layers.  The source sequence becomes
+ *   S = [the r window rows in ring order; k_new[dev_rows[b][i]] for i < a_b];
+ * the flush rule, the ring slots, the lengths advance and every other word of million_window_commit's contract are unchanged,
+ * and dev_rows[b] = 0, 1, 2, ... gives its result bit for bit.  An index is clamped into [0, n_bound) on the device; the entries
+ * at or past a_b never reach a store, and neither launch reads outside dev_rows or outside the request's n_bound rows of
+ * k_new / v_new.  Two stream-ordered launches, as above; validation precedes any HIP call, plus: dev_rows NULL
+ * (MILLION_ERR_ARG) or not 4-byte aligned (MILLION_ERR_ALIGN). */
+int million_window_commit_rows(const million_window_commit_desc *desc, const void *k_new, const void *v_new, void *k_resid,
+                               void *v_resid, const void *k_cents_prepared, const void *v_cents_prepared, void *k_pool,
+                               void *v_pool, const int32_t *page_ids, int32_t *dev_lengths, const int32_t *dev_n,
+                               const int32_t *dev_rows, million_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Residual-window append.

@@ -11,8 +11,15 @@
 // four partial dot products summed across the row's four lanes; the scores of a row stay in registers (the j loop is unrolled over
 // the 16 possible keys under a wave-uniform bound).  No atomics, no workspace, no private memory; the first query head of every kv
 // head also copies the block rows to k_stage / v_stage from the registers that feed LDS.
+//
+// million_attn_tree_merge is the same kernel body for a draft that is a tree in topological order (TREE = true): row i sees the
+// block rows its ancestor-mask word names instead of the rows j <= i.  The word is one more load among the wave's first loads and
+// is sanitised before use, m = (mask & ((2u << i) - 1)) | (1u << i); j is a compile-time constant under the unrolled loop, so the
+// test is a bit test per score and the scores stay in registers.  million_attn_block_merge launches the TREE = false instances.
 #include <math.h>
 #include <string.h>
+
+#include <type_traits>
 
 #include "common.h"
 
@@ -37,8 +44,16 @@ struct BlockMergeParams {
     float scale;
 };
 
-template <int D>
-__global__ __launch_bounds__(64) void attn_block_merge_kernel(BlockMergeParams p) {
+// million_attn_tree_merge: the same block under an ancestor mask, bit j of word (b, i) = row i sees block row j
+struct TreeMergeParams : BlockMergeParams {
+    const int *dev_mask;      // (bs, n)
+};
+
+// TREE = false is the chain (row i sees j <= i), the kernel of million_attn_block_merge; TREE = true takes the row's visibility
+// from its mask word, loaded with the wave's other loads and sanitised before use: the row itself always, no later row, no bit
+// at or above 16.
+template <int D, bool TREE = false>
+__global__ __launch_bounds__(64) void attn_block_merge_kernel(std::conditional_t<TREE, TreeMergeParams, BlockMergeParams> p) {
     constexpr int DP = D / 4;       // dims per lane
     constexpr int NV = DP / 8;      // 16-byte vectors per lane and row part; also the wave's loads per side of the block
     constexpr int VPR = D / 8;      // vectors per row
@@ -70,6 +85,8 @@ __global__ __launch_bounds__(64) void attn_block_merge_kernel(BlockMergeParams p
         av[u] = *(const h8 *)(p.out_a + b * p.as[0] + h * p.as[1] + ic * p.as[2] + part * DP + 8 * u);
     }
     const float la = p.lse_a[((long long)b * p.nh + h) * n + ic];
+    unsigned vis = 0;
+    if constexpr (TREE) vis = (unsigned)p.dev_mask[(long long)b * n + ic];
 
 #pragma unroll
     for (int u = 0; u < NV; ++u) {
@@ -97,6 +114,7 @@ __global__ __launch_bounds__(64) void attn_block_merge_kernel(BlockMergeParams p
     for (int u = 0; u < NV; ++u)
 #pragma unroll
         for (int e = 0; e < 8; ++e) qf[8 * u + e] = (float)qv[u][e];
+    if constexpr (TREE) vis = (vis & ((2u << i) - 1u)) | (1u << i);      // i <= 15
     float s[kBlkRows];
     float m = -INFINITY;
 #pragma unroll
@@ -112,7 +130,9 @@ __global__ __launch_bounds__(64) void attn_block_merge_kernel(BlockMergeParams p
             }
             acc += __shfl_xor(acc, 1);
             acc += __shfl_xor(acc, 2);
-            s[j] = j <= i ? acc * p.scale : -INFINITY;
+            bool sees = j <= i;
+            if constexpr (TREE) sees = (vis >> j) & 1u;
+            s[j] = sees ? acc * p.scale : -INFINITY;
             m = fmaxf(m, s[j]);
         }
     }
@@ -162,28 +182,28 @@ __global__ __launch_bounds__(64) void attn_block_merge_kernel(BlockMergeParams p
 
 using namespace million;
 
-extern "C" int million_attn_block_merge(const million_block_merge_desc *desc, const void *q, const void *k_blk, const void *v_blk,
-                                        const void *out_a, const float *lse_a, const int32_t *dev_n, void *out, float *lse_out,
-                                        void *k_stage, void *v_stage, million_stream_t stream) {
-    if (!desc || desc->struct_size != sizeof(million_block_merge_desc)) { set_error("attn_block_merge: bad desc / struct_size"); return MILLION_ERR_ARG; }
+// Validation and parameter fill shared by the two entries; `who` names the entry in the messages.  No HIP call.
+static int block_merge_fill(const char *who, const million_block_merge_desc *desc, const void *q, const void *k_blk, const void *v_blk,
+                            const void *out_a, const float *lse_a, const int32_t *dev_n, void *out, float *lse_out, void *k_stage,
+                            void *v_stage, BlockMergeParams &p) {
+    if (!desc || desc->struct_size != sizeof(million_block_merge_desc)) { set_error("%s: bad desc / struct_size", who); return MILLION_ERR_ARG; }
     const million_block_merge_desc &d = *desc;
-    if (d.n < 1 || d.n > kBlkRows) { set_error("attn_block_merge: n=%d (1 .. %d draft rows)", d.n, kBlkRows); return MILLION_ERR_SHAPE; }
-    if (d.d != 64 && d.d != 128) { set_error("attn_block_merge: d=%d (64 / 128)", d.d); return MILLION_ERR_SHAPE; }
+    if (d.n < 1 || d.n > kBlkRows) { set_error("%s: n=%d (1 .. %d draft rows)", who, d.n, kBlkRows); return MILLION_ERR_SHAPE; }
+    if (d.d != 64 && d.d != 128) { set_error("%s: d=%d (64 / 128)", who, d.d); return MILLION_ERR_SHAPE; }
     if (d.bs <= 0 || d.nh <= 0 || d.nh_k <= 0 || d.nh % d.nh_k || (long long)d.bs * d.nh > 0x7fffffffLL) {
-        set_error("attn_block_merge: bs=%d nh=%d nh_k=%d (nh a multiple of nh_k)", d.bs, d.nh, d.nh_k);
+        set_error("%s: bs=%d nh=%d nh_k=%d (nh a multiple of nh_k)", who, d.bs, d.nh, d.nh_k);
         return MILLION_ERR_SHAPE;
     }
-    if (!q || !k_blk || !v_blk || !out_a || !lse_a || !out) { set_error("attn_block_merge: null q / k_blk / v_blk / out_a / lse_a / out"); return MILLION_ERR_ARG; }
-    if ((k_stage == nullptr) != (v_stage == nullptr)) { set_error("attn_block_merge: k_stage and v_stage go together"); return MILLION_ERR_ARG; }
+    if (!q || !k_blk || !v_blk || !out_a || !lse_a || !out) { set_error("%s: null q / k_blk / v_blk / out_a / lse_a / out", who); return MILLION_ERR_ARG; }
+    if ((k_stage == nullptr) != (v_stage == nullptr)) { set_error("%s: k_stage and v_stage go together", who); return MILLION_ERR_ARG; }
     if (((uintptr_t)q | (uintptr_t)k_blk | (uintptr_t)v_blk | (uintptr_t)out_a | (uintptr_t)out | (uintptr_t)k_stage | (uintptr_t)v_stage) & 15) {
-        set_error("attn_block_merge: q, block rows, outs and staging must be 16-byte aligned");
+        set_error("%s: q, block rows, outs and staging must be 16-byte aligned", who);
         return MILLION_ERR_ALIGN;
     }
-    if (((uintptr_t)lse_a | (uintptr_t)lse_out | (uintptr_t)dev_n) & 3) { set_error("attn_block_merge: lse_a / lse_out / dev_n must be 4-byte aligned"); return MILLION_ERR_ALIGN; }
+    if (((uintptr_t)lse_a | (uintptr_t)lse_out | (uintptr_t)dev_n) & 3) { set_error("%s: lse_a / lse_out / dev_n must be 4-byte aligned", who); return MILLION_ERR_ALIGN; }
     long long strides = d.stage_stride_b | d.stage_stride_h;
     for (int k = 0; k < 3; ++k) strides |= d.q_stride[k] | d.k_stride[k] | d.v_stride[k] | d.a_stride[k] | d.o_stride[k];
-    if (strides & 7) { set_error("attn_block_merge: fp16 strides must be multiples of 8 elements (16-byte rows)"); return MILLION_ERR_ALIGN; }
-    BlockMergeParams p;
+    if (strides & 7) { set_error("%s: fp16 strides must be multiples of 8 elements (16-byte rows)", who); return MILLION_ERR_ALIGN; }
     memset(&p, 0, sizeof(p));
     p.q = (const f16 *)q; p.k = (const f16 *)k_blk; p.v = (const f16 *)v_blk; p.out_a = (const f16 *)out_a;
     p.lse_a = lse_a; p.dev_n = dev_n; p.out = (f16 *)out; p.lse_out = lse_out;
@@ -194,11 +214,38 @@ extern "C" int million_attn_block_merge(const million_block_merge_desc *desc, co
     p.ss[0] = d.stage_stride_b; p.ss[1] = d.stage_stride_h;
     p.nh = d.nh; p.G = d.nh / d.nh_k; p.n = d.n;
     p.scale = 1.0f / sqrtf((float)d.d);
-    const dim3 grid((unsigned)(d.bs * d.nh));
+    return MILLION_OK;
+}
+
+extern "C" int million_attn_block_merge(const million_block_merge_desc *desc, const void *q, const void *k_blk, const void *v_blk,
+                                        const void *out_a, const float *lse_a, const int32_t *dev_n, void *out, float *lse_out,
+                                        void *k_stage, void *v_stage, million_stream_t stream) {
+    BlockMergeParams p;
+    const int rc = block_merge_fill("attn_block_merge", desc, q, k_blk, v_blk, out_a, lse_a, dev_n, out, lse_out, k_stage, v_stage, p);
+    if (rc != MILLION_OK) return rc;
+    const dim3 grid((unsigned)(desc->bs * desc->nh));
     hipStream_t s = (hipStream_t)stream;
-    if (d.d == 128) hipLaunchKernelGGL(attn_block_merge_kernel<128>, grid, dim3(64), 0, s, p);
+    if (desc->d == 128) hipLaunchKernelGGL(attn_block_merge_kernel<128>, grid, dim3(64), 0, s, p);
     else hipLaunchKernelGGL(attn_block_merge_kernel<64>, grid, dim3(64), 0, s, p);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("attn_block_merge launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
+    return MILLION_OK;
+}
+
+extern "C" int million_attn_tree_merge(const million_block_merge_desc *desc, const void *q, const void *k_blk, const void *v_blk,
+                                       const void *out_a, const float *lse_a, const int32_t *dev_n, const int32_t *dev_mask, void *out,
+                                       float *lse_out, void *k_stage, void *v_stage, million_stream_t stream) {
+    TreeMergeParams p;
+    const int rc = block_merge_fill("attn_tree_merge", desc, q, k_blk, v_blk, out_a, lse_a, dev_n, out, lse_out, k_stage, v_stage, p);
+    if (rc != MILLION_OK) return rc;
+    if (!dev_mask) { set_error("attn_tree_merge: null dev_mask (million_attn_block_merge is the entry without a mask)"); return MILLION_ERR_ARG; }
+    if ((uintptr_t)dev_mask & 3) { set_error("attn_tree_merge: dev_mask must be 4-byte aligned"); return MILLION_ERR_ALIGN; }
+    p.dev_mask = dev_mask;
+    const dim3 grid((unsigned)(desc->bs * desc->nh));
+    hipStream_t s = (hipStream_t)stream;
+    if (desc->d == 128) hipLaunchKernelGGL((attn_block_merge_kernel<128, true>), grid, dim3(64), 0, s, p);
+    else hipLaunchKernelGGL((attn_block_merge_kernel<64, true>), grid, dim3(64), 0, s, p);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("attn_tree_merge launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
     return MILLION_OK;
 }

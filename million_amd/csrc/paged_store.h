@@ -20,7 +20,10 @@
 // become tokens, the layer offsets, what keeps a store from a bad page (the store clamps the page index into the table, the
 // commit - whose tokens lie inside the table - tests the page id against the pool), and the row strides (per side / one set,
 // dense windows).
-// A parameter block P has: kCommit; side(vside); page_ids, dev_lengths, dev_n; bs, nh_k, d, M, C, n_bound, rcap, page_size,
+// A third parameter block, CommitRowsParams (window_commit.hip, million_window_commit_rows), is the commit's with P::kRows: new
+// row i of a request is staged row dev_rows[b][i], clamped into [0, n_bound) (ps_new_row below).  kRows is false in WindowCommitParams and
+// is not asked of the store's block; the instances of both are compiled as before.
+// A parameter block P has: kCommit (the commit's also kRows); side(vside); page_ids, dev_lengths, dev_n; bs, nh_k, d, M, C, n_bound, rcap, page_size,
 // ps_shift, n_pages_cap, cap_tok (cap_tok = n_pages_cap * page_size); the store wsb, wsh (window strides, row stride d); the
 // commit nsl, ids_ls, win_ls, len_ls (layer strides), n_pool and groups_y (grid.y per layer).
 #pragma once
@@ -57,6 +60,19 @@ template <class P>
 __device__ __forceinline__ void ps_commit_flush(const P &p, int T, int r, int a, int &f, bool &ok) {
     f = r + a > p.rcap ? p.page_size : 0;
     ok = (long long)T + f <= p.cap_tok;
+}
+
+// P::kRows: the staged row that new row i of request b is.  i is clamped into [0, n_bound) before the load and the entry after
+// it, so no lane reads outside dev_rows (bs, n_bound) or outside the request's n_bound staged rows, whatever either holds.
+template <class P>
+__device__ __forceinline__ int ps_new_row(const P &p, int b, int i) {
+    if constexpr (P::kRows) {
+        const int ic = i < 0 ? 0 : (i < p.n_bound ? i : p.n_bound - 1);
+        const int x = p.dev_rows[(long long)b * p.n_bound + ic];
+        return x < 0 ? 0 : (x < p.n_bound ? x : p.n_bound - 1);
+    } else {
+        return i;
+    }
 }
 
 template <int DM, class P>
@@ -102,7 +118,7 @@ __global__ __launch_bounds__(kPsBlock) void paged_store_kernel(P p) {
     long long off_w, off_n;
     if constexpr (COMMIT) {
         off_w = l * p.win_ls + (((long long)b * p.nh_k + hk) * p.rcap + (st + jc) % p.rcap) * p.d;
-        off_n = l * p.nsl + b * sd.nsb + hk * sd.nsh + (long long)(jc - r) * sd.nsn;
+        off_n = l * p.nsl + b * sd.nsb + hk * sd.nsh + (long long)ps_new_row(p, b, jc - r) * sd.nsn;
     } else {
         const int rmod = p.rcap > 0 ? p.rcap : 1;
         off_w = b * p.wsb + hk * p.wsh + (long long)((st + jc) % rmod) * p.d;

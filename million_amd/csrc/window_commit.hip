@@ -18,6 +18,8 @@
 //      lengths row.  It comes second because the ring slots it writes may hold rows the first launch reads; inside it every
 //      thread has read the lengths row before the barrier that precedes the one thread's write.
 // A request whose T + f would pass the page table is left untouched by both launches.
+// million_window_commit_rows (the accepted path of a draft tree) is the same two launches with one indirection: new row i of
+// request b is staged row dev_rows[b][i], index and entry clamped on the device (ps_new_row, paged_store.h; CommitRowsParams).
 #include "paged_store.h"
 
 #pragma clang fp contract(off)
@@ -31,6 +33,7 @@ constexpr int kWcMaxRows = 16;      // new rows per request, at most
 
 struct WindowCommitParams {
     static constexpr bool kCommit = true;
+    static constexpr bool kRows = false;
     const f16 *k_new, *v_new;       // (layers, bs, nh_k, n_bound, d)
     f16 *k_win, *v_win;             // (layers, bs, nh_k, rcap, d), each layer contiguous
     const float *k_cents32, *v_cents32;
@@ -49,9 +52,16 @@ struct WindowCommitParams {
     }
 };
 
+// million_window_commit_rows: new row i of request b is staged row dev_rows[b][i] (ps_new_row, paged_store.h)
+struct CommitRowsParams : WindowCommitParams {
+    static constexpr bool kRows = true;
+    const int *dev_rows;            // (bs, n_bound)
+};
+
 typedef unsigned wv4 __attribute__((ext_vector_type(4)));
 
-__global__ __launch_bounds__(kWcBlock) void window_commit_append_kernel(WindowCommitParams p) {
+template <class P>
+__device__ __forceinline__ void window_commit_append_body(const P &p) {
     const int l = blockIdx.x / p.bs, b = blockIdx.x % p.bs;
     int *row = p.dev_lengths + l * p.len_ls + 4ll * b;
     int T, r, st, a, f;
@@ -69,7 +79,7 @@ __global__ __launch_bounds__(kWcBlock) void window_commit_append_kernel(WindowCo
         const int hk = t / (2 * vpr * a);
         if (r + i < f) continue;      // the row became a token in the first launch
         const int slot = (st + r + i) % p.rcap;
-        const f16 *src = (vside ? p.v_new : p.k_new) + l * p.nsl + b * p.nsb + hk * p.nsh + (long long)i * p.nsn + 8 * col;
+        const f16 *src = (vside ? p.v_new : p.k_new) + l * p.nsl + b * p.nsb + hk * p.nsh + (long long)ps_new_row(p, b, i) * p.nsn + 8 * col;
         f16 *dst = (vside ? p.v_win : p.k_win) + l * p.win_ls + (((long long)b * p.nh_k + hk) * p.rcap + slot) * p.d + 8 * col;
         *(wv4 *)dst = *(const wv4 *)src;
     }
@@ -80,57 +90,60 @@ __global__ __launch_bounds__(kWcBlock) void window_commit_append_kernel(WindowCo
     }
 }
 
+__global__ __launch_bounds__(kWcBlock) void window_commit_append_kernel(WindowCommitParams p) { window_commit_append_body(p); }
+
+__global__ __launch_bounds__(kWcBlock) void window_commit_rows_append_kernel(CommitRowsParams p) { window_commit_append_body(p); }
+
 }  // namespace
 
 }  // namespace million
 
 using namespace million;
 
-extern "C" int million_window_commit(const million_window_commit_desc *desc, const void *k_new, const void *v_new, void *k_resid,
-                                     void *v_resid, const void *k_cents_prepared, const void *v_cents_prepared, void *k_pool,
-                                     void *v_pool, const int32_t *page_ids, int32_t *dev_lengths, const int32_t *dev_n,
-                                     million_stream_t stream) {
-    if (!desc || desc->struct_size != sizeof(million_window_commit_desc)) { set_error("window_commit: bad desc / struct_size"); return MILLION_ERR_ARG; }
+// Validation and parameter fill shared by the two entries; `who` names the entry in the messages.  No HIP call.
+static int window_commit_fill(const char *who, const million_window_commit_desc *desc, const void *k_new, const void *v_new, void *k_resid,
+                              void *v_resid, const void *k_cents_prepared, const void *v_cents_prepared, void *k_pool, void *v_pool,
+                              const int32_t *page_ids, int32_t *dev_lengths, const int32_t *dev_n, WindowCommitParams &p, int &dm) {
+    if (!desc || desc->struct_size != sizeof(million_window_commit_desc)) { set_error("%s: bad desc / struct_size", who); return MILLION_ERR_ARG; }
     const million_window_commit_desc &d = *desc;
-    if (d.n_layers <= 0 || d.bs <= 0 || d.nh_k <= 0) { set_error("window_commit: n_layers=%d bs=%d nh_k=%d", d.n_layers, d.bs, d.nh_k); return MILLION_ERR_SHAPE; }
+    if (d.n_layers <= 0 || d.bs <= 0 || d.nh_k <= 0) { set_error("%s: n_layers=%d bs=%d nh_k=%d", who, d.n_layers, d.bs, d.nh_k); return MILLION_ERR_SHAPE; }
     int ps_shift;
-    if (!u8_geometry("window_commit", d.d, d.M, d.C) || !page_shift("window_commit", d.page_size, ps_shift)) return MILLION_ERR_SHAPE;
+    if (!u8_geometry(who, d.d, d.M, d.C) || !page_shift(who, d.page_size, ps_shift)) return MILLION_ERR_SHAPE;
     if (d.n_bound < 1 || d.n_bound > kWcMaxRows || d.n_bound > d.page_size) {
-        set_error("window_commit: n_bound=%d (1 .. %d, at most page_size=%d: one flush per request)", d.n_bound, kWcMaxRows, d.page_size);
+        set_error("%s: n_bound=%d (1 .. %d, at most page_size=%d: one flush per request)", who, d.n_bound, kWcMaxRows, d.page_size);
         return MILLION_ERR_SHAPE;
     }
-    if (d.resid_cap < d.page_size || (long long)d.resid_cap * d.d > 0x7fffffffLL) { set_error("window_commit: resid_cap=%d (at least page_size=%d)", d.resid_cap, d.page_size); return MILLION_ERR_SHAPE; }
+    if (d.resid_cap < d.page_size || (long long)d.resid_cap * d.d > 0x7fffffffLL) { set_error("%s: resid_cap=%d (at least page_size=%d)", who, d.resid_cap, d.page_size); return MILLION_ERR_SHAPE; }
     if (d.n_pages_cap <= 0 || d.n_pool <= 0 || (long long)d.n_pages_cap * d.page_size + d.resid_cap + d.n_bound > 0x7fffffffLL ||
         (long long)d.bs * d.nh_k * d.n_pages_cap > 0x7fffffffLL) {
-        set_error("window_commit: n_pages_cap=%d n_pool=%d (page table of %lld entries)", d.n_pages_cap, d.n_pool, (long long)d.bs * d.nh_k * d.n_pages_cap);
+        set_error("%s: n_pages_cap=%d n_pool=%d (page table of %lld entries)", who, d.n_pages_cap, d.n_pool, (long long)d.bs * d.nh_k * d.n_pages_cap);
         return MILLION_ERR_SHAPE;
     }
-    const int dm = d.d / d.M;
+    dm = d.d / d.M;
     const int groups_y = (d.M / kPsSub + kWcBlock / 64 - 1) / (kWcBlock / 64);
     if ((long long)d.bs * d.nh_k * 2 > 65535 || (long long)d.n_layers * groups_y > 65535 || (long long)d.n_layers * d.bs > 0x7fffffffLL) {
-        set_error("window_commit: bs * nh_k = %lld (at most 32767), n_layers=%d exceed the grid", (long long)d.bs * d.nh_k, d.n_layers);
+        set_error("%s: bs * nh_k = %lld (at most 32767), n_layers=%d exceed the grid", who, (long long)d.bs * d.nh_k, d.n_layers);
         return MILLION_ERR_SHAPE;
     }
-    if (dm != 1 && dm != 2 && dm != 4 && dm != 8) { set_error("window_commit: d/M=%d unsupported (1,2,4,8)", dm); return MILLION_ERR_SHAPE; }
+    if (dm != 1 && dm != 2 && dm != 4 && dm != 8) { set_error("%s: d/M=%d unsupported (1,2,4,8)", who, dm); return MILLION_ERR_SHAPE; }
     if (d.ids_layer_stride < 0 || d.rows_layer_stride < 0 || d.lengths_layer_stride < 0 ||
         (d.n_layers > 1 && (d.lengths_layer_stride < 4LL * d.bs || d.ids_layer_stride < (long long)d.bs * d.nh_k * d.n_pages_cap ||
                             d.rows_layer_stride < (long long)d.bs * d.nh_k * d.resid_cap * d.d))) {
-        set_error("window_commit: layer strides %lld / %lld / %lld shorter than a layer", (long long)d.ids_layer_stride, (long long)d.rows_layer_stride,
+        set_error("%s: layer strides %lld / %lld / %lld shorter than a layer", who, (long long)d.ids_layer_stride, (long long)d.rows_layer_stride,
                   (long long)d.lengths_layer_stride);
         return MILLION_ERR_ARG;
     }
-    if (!dev_n || !dev_lengths) { set_error("window_commit: null dev_n / dev_lengths (every per-request value is read on the device)"); return MILLION_ERR_ARG; }
-    if (!k_new || !v_new || !k_resid || !v_resid) { set_error("window_commit: null new rows / windows"); return MILLION_ERR_ARG; }
-    if (!k_cents_prepared || !v_cents_prepared) { set_error("window_commit: null prepared codebook (million_prepare_cents: the call needs both)"); return MILLION_ERR_ARG; }
-    if (!k_pool || !v_pool || !page_ids) { set_error("window_commit: null pools / page_ids"); return MILLION_ERR_ARG; }
-    WindowCommitParams p;
-    const int rc = paged_store_fill("window_commit", p, d.bs, d.nh_k, d.d, d.M, d.C, d.n_bound, d.resid_cap, d.page_size, ps_shift, d.n_pages_cap,
+    if (!dev_n || !dev_lengths) { set_error("%s: null dev_n / dev_lengths (every per-request value is read on the device)", who); return MILLION_ERR_ARG; }
+    if (!k_new || !v_new || !k_resid || !v_resid) { set_error("%s: null new rows / windows", who); return MILLION_ERR_ARG; }
+    if (!k_cents_prepared || !v_cents_prepared) { set_error("%s: null prepared codebook (million_prepare_cents: the call needs both)", who); return MILLION_ERR_ARG; }
+    if (!k_pool || !v_pool || !page_ids) { set_error("%s: null pools / page_ids", who); return MILLION_ERR_ARG; }
+    const int rc = paged_store_fill(who, p, d.bs, d.nh_k, d.d, d.M, d.C, d.n_bound, d.resid_cap, d.page_size, ps_shift, d.n_pages_cap,
                                     (uintptr_t)k_new | (uintptr_t)v_new | (uintptr_t)k_resid | (uintptr_t)v_resid | (uintptr_t)k_cents_prepared |
                                         (uintptr_t)v_cents_prepared | (uintptr_t)k_pool | (uintptr_t)v_pool,
                                     page_ids, dev_lengths, dev_n);
     if (rc != MILLION_OK) return rc;
     if ((d.new_stride_l | d.new_stride_b | d.new_stride_h | d.new_stride_n | d.rows_layer_stride) & 7) {
-        set_error("window_commit: fp16 strides must be multiples of 8 elements (16-byte rows)");
+        set_error("%s: fp16 strides must be multiples of 8 elements (16-byte rows)", who);
         return MILLION_ERR_ALIGN;
     }
     p.k_new = (const f16 *)k_new; p.v_new = (const f16 *)v_new;
@@ -141,7 +154,20 @@ extern "C" int million_window_commit(const million_window_commit_desc *desc, con
     p.nsl = d.new_stride_l; p.nsb = d.new_stride_b; p.nsh = d.new_stride_h; p.nsn = d.new_stride_n; p.ids_ls = d.ids_layer_stride; p.win_ls = d.rows_layer_stride; p.len_ls = d.lengths_layer_stride;
     p.n_layers = d.n_layers; p.n_pool = d.n_pool;
     p.groups_y = groups_y;
-    const dim3 grid((d.page_size + 63) / 64, d.n_layers * groups_y, d.bs * d.nh_k * 2);
+    return MILLION_OK;
+}
+
+extern "C" int million_window_commit(const million_window_commit_desc *desc, const void *k_new, const void *v_new, void *k_resid,
+                                     void *v_resid, const void *k_cents_prepared, const void *v_cents_prepared, void *k_pool,
+                                     void *v_pool, const int32_t *page_ids, int32_t *dev_lengths, const int32_t *dev_n,
+                                     million_stream_t stream) {
+    WindowCommitParams p;
+    int dm;
+    const int rc = window_commit_fill("window_commit", desc, k_new, v_new, k_resid, v_resid, k_cents_prepared, v_cents_prepared, k_pool, v_pool,
+                                      page_ids, dev_lengths, dev_n, p, dm);
+    if (rc != MILLION_OK) return rc;
+    const million_window_commit_desc &d = *desc;
+    const dim3 grid((d.page_size + 63) / 64, d.n_layers * p.groups_y, d.bs * d.nh_k * 2);
     hipStream_t s = (hipStream_t)stream;
     dispatch_dm(dm, [&](auto w) { hipLaunchKernelGGL((paged_store_kernel<w(), WindowCommitParams>), grid, dim3(kWcBlock), 0, s, p); });
     hipError_t e = hipGetLastError();
@@ -149,5 +175,29 @@ extern "C" int million_window_commit(const million_window_commit_desc *desc, con
     hipLaunchKernelGGL(window_commit_append_kernel, dim3(d.n_layers * d.bs), dim3(kWcBlock), 0, s, p);
     e = hipGetLastError();
     if (e != hipSuccess) { set_error("window_commit append launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
+    return MILLION_OK;
+}
+
+extern "C" int million_window_commit_rows(const million_window_commit_desc *desc, const void *k_new, const void *v_new, void *k_resid,
+                                          void *v_resid, const void *k_cents_prepared, const void *v_cents_prepared, void *k_pool,
+                                          void *v_pool, const int32_t *page_ids, int32_t *dev_lengths, const int32_t *dev_n,
+                                          const int32_t *dev_rows, million_stream_t stream) {
+    CommitRowsParams p;
+    int dm;
+    const int rc = window_commit_fill("window_commit_rows", desc, k_new, v_new, k_resid, v_resid, k_cents_prepared, v_cents_prepared, k_pool,
+                                      v_pool, page_ids, dev_lengths, dev_n, p, dm);
+    if (rc != MILLION_OK) return rc;
+    if (!dev_rows) { set_error("window_commit_rows: null dev_rows (million_window_commit is the entry without row indices)"); return MILLION_ERR_ARG; }
+    if ((uintptr_t)dev_rows & 3) { set_error("window_commit_rows: dev_rows must be 4-byte aligned"); return MILLION_ERR_ALIGN; }
+    p.dev_rows = dev_rows;
+    const million_window_commit_desc &d = *desc;
+    const dim3 grid((d.page_size + 63) / 64, d.n_layers * p.groups_y, d.bs * d.nh_k * 2);
+    hipStream_t s = (hipStream_t)stream;
+    dispatch_dm(dm, [&](auto w) { hipLaunchKernelGGL((paged_store_kernel<w(), CommitRowsParams>), grid, dim3(kWcBlock), 0, s, p); });
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("window_commit_rows encode launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
+    hipLaunchKernelGGL(window_commit_rows_append_kernel, dim3(d.n_layers * d.bs), dim3(kWcBlock), 0, s, p);
+    e = hipGetLastError();
+    if (e != hipSuccess) { set_error("window_commit_rows append launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
     return MILLION_OK;
 }

@@ -986,7 +986,8 @@ def attn_merge(outs, lses, out: Optional[torch.Tensor] = None, lse_out: Optional
 
 def attn_block_merge(q: torch.Tensor, k_blk: torch.Tensor, v_blk: torch.Tensor, out_a: torch.Tensor, lse_a: torch.Tensor,
                      dev_n: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, lse_out: Optional[torch.Tensor] = None,
-                     return_lse: bool = False, k_stage: Optional[torch.Tensor] = None, v_stage: Optional[torch.Tensor] = None):
+                     return_lse: bool = False, k_stage: Optional[torch.Tensor] = None, v_stage: Optional[torch.Tensor] = None,
+                     dev_mask: Optional[torch.Tensor] = None):
     """Finish the attention of n <= 16 draft rows per request in one launch (million_attn_block_merge): (out_a, lse_a), fp16
     (bs, nh, n, d) and fp32 (bs, nh, n) contiguous, is every row's attention over the past (pq_decode_attn over the rows as query
     heads, or pq_chunk_attn without a chunk, with return_lse); row i then attends causally to the block's own rows j <= i of
@@ -994,8 +995,11 @@ def attn_block_merge(q: torch.Tensor, k_blk: torch.Tensor, v_blk: torch.Tensor, 
     any views with contiguous rows of d and the other strides multiples of 8 elements; `out` may be out_a itself.  dev_n, device
     int32 (bs,): the live rows of each request, clamped into [0, n]; the rows past them get out = 0 and lse = -inf and their q /
     k / v never reach a live row.  k_stage / v_stage, fp16 (bs, nh_k, >= n, d) with dense rows: the launch copies the block rows
-    there (window_commit reads them).  Returns out, or (out, lse_out) with return_lse (or an lse_out buffer)."""
-    _need_cuda(q, k_blk, v_blk, out_a, lse_a, dev_n, out, lse_out, k_stage, v_stage)
+    there (window_commit reads them).  dev_mask, device int32 (bs, n) contiguous: the draft is a tree in topological order and
+    bit j of word (b, i) says that row i sees block row j (million_attn_tree_merge); the kernel keeps bits 0 .. i and sets bit i,
+    whatever the word holds.  None: the chain, million_attn_block_merge.  Returns out, or (out, lse_out) with return_lse (or an
+    lse_out buffer)."""
+    _need_cuda(q, k_blk, v_blk, out_a, lse_a, dev_n, out, lse_out, k_stage, v_stage, dev_mask)
     if q.dim() != 4 or any(t.dtype != torch.float16 for t in (q, k_blk, v_blk, out_a)):
         raise RuntimeError("attn_block_merge: q, k_blk, v_blk and out_a must be fp16 (bs, nh | nh_k, n, d)")
     bs, nh, n, d = q.shape
@@ -1032,6 +1036,13 @@ def attn_block_merge(q: torch.Tensor, k_blk: torch.Tensor, v_blk: torch.Tensor, 
                     or t.stride(3) != 1 or t.stride(2) != d or t.stride() != k_stage.stride()):
                 raise RuntimeError("attn_block_merge: k_stage / v_stage must be fp16 (bs, nh_k, >= n, d) with dense rows, alike")
         desc.stage_stride_b, desc.stage_stride_h = k_stage.stride(0), k_stage.stride(1)
+    if dev_mask is not None:
+        if dev_mask.dtype != torch.int32 or tuple(dev_mask.shape) != (bs, n) or not dev_mask.is_contiguous() or dev_mask.device != q.device:
+            raise RuntimeError(f"attn_block_merge: dev_mask must be contiguous int32 (bs, n) = ({bs}, {n}) on the device of q")
+        L.check(L.load().million_attn_tree_merge(ctypes.byref(desc), q.data_ptr(), k_blk.data_ptr(), v_blk.data_ptr(), out_a.data_ptr(),
+                                                 lse_a.data_ptr(), _ptr(dev_n), dev_mask.data_ptr(), out.data_ptr(), _ptr(lse_out),
+                                                 _ptr(k_stage), _ptr(v_stage), _stream()), "million_attn_tree_merge")
+        return (out, lse_out) if (return_lse or lse_out is not None) else out
     L.check(L.load().million_attn_block_merge(ctypes.byref(desc), q.data_ptr(), k_blk.data_ptr(), v_blk.data_ptr(), out_a.data_ptr(),
                                               lse_a.data_ptr(), _ptr(dev_n), out.data_ptr(), _ptr(lse_out), _ptr(k_stage),
                                               _ptr(v_stage), _stream()), "million_attn_block_merge")
@@ -1040,15 +1051,18 @@ def attn_block_merge(q: torch.Tensor, k_blk: torch.Tensor, v_blk: torch.Tensor, 
 
 def window_commit(k_new: torch.Tensor, v_new: torch.Tensor, k_res: torch.Tensor, v_res: torch.Tensor, k_prep: torch.Tensor,
                   v_prep: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, page_ids: torch.Tensor,
-                  dev_lengths: torch.Tensor, dev_n: torch.Tensor, *, M: int, C: int, n_bound: Optional[int] = None) -> None:
+                  dev_lengths: torch.Tensor, dev_n: torch.Tensor, *, M: int, C: int, n_bound: Optional[int] = None,
+                  dev_rows: Optional[torch.Tensor] = None) -> None:
     """Append the first dev_n[b] rows of k_new / v_new (layers, bs, nh_k, n, d) to request b's window in every layer, exactly as
     that many decode steps would have (million_window_commit): a request whose window would overflow first has its oldest
     page_size rows - window rows in ring order, then new rows - encoded behind its T tokens (the codes pq_flush writes), the
     rest of the new rows go to the ring, and the rows of dev_lengths (layers, bs, 4) advance on the device.  k_res / v_res
     (layers, bs, nh_k, cap, d), page_ids (layers, bs, nh_k, n_pages_cap): the layers of one cache side by side, as cache_fork
     takes them; dev_n int32 (bs,) serves every layer.  n_bound (default n): the rows the grids are sized for, at most 16 and at
-    most page_size; dev_n is clamped into [0, n_bound]."""
-    _need_cuda(k_new, v_new, k_res, v_res, k_prep, v_prep, k_pool, v_pool, page_ids, dev_lengths, dev_n)
+    most page_size; dev_n is clamped into [0, n_bound].  dev_rows, device int32 (bs, n_bound) contiguous: the dev_n[b] new rows
+    of request b are rows dev_rows[b][0 .. dev_n[b]) of k_new / v_new, in that order (million_window_commit_rows: the accepted
+    path of a draft tree); an index is clamped into [0, n_bound).  None: the first dev_n[b] rows, million_window_commit."""
+    _need_cuda(k_new, v_new, k_res, v_res, k_prep, v_prep, k_pool, v_pool, page_ids, dev_lengths, dev_n, dev_rows)
     if k_new.dtype != torch.float16 or v_new.dtype != torch.float16 or k_new.dim() != 5 or v_new.shape != k_new.shape or \
             k_new.stride() != v_new.stride() or k_new.stride(4) != 1:
         raise RuntimeError("window_commit: k_new / v_new must be fp16 (layers, bs, nh_k, n, d) of one shape and strides, contiguous rows")
@@ -1075,6 +1089,15 @@ def window_commit(k_new: torch.Tensor, v_new: torch.Tensor, k_res: torch.Tensor,
     desc.page_size, desc.n_pages_cap, desc.n_pool, desc.resid_cap = page_size, page_ids.shape[3], n_pool, k_res.shape[3]
     desc.new_stride_l, desc.new_stride_b, desc.new_stride_h, desc.new_stride_n = k_new.stride()[:4]
     desc.ids_layer_stride, desc.rows_layer_stride, desc.lengths_layer_stride = page_ids.stride(0), k_res.stride(0), dev_lengths.stride(0)
+    if dev_rows is not None:
+        if dev_rows.dtype != torch.int32 or tuple(dev_rows.shape) != (bs, n_bound) or not dev_rows.is_contiguous() or dev_rows.device != k_new.device:
+            raise RuntimeError(f"window_commit: dev_rows must be contiguous int32 (bs, n_bound) = ({bs}, {n_bound}) on the device of k_new")
+        L.check(L.load().million_window_commit_rows(ctypes.byref(desc), k_new.data_ptr(), v_new.data_ptr(), k_res.data_ptr(), v_res.data_ptr(),
+                                                    k_prep.data_ptr(), v_prep.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(),
+                                                    page_ids.data_ptr(), dev_lengths.data_ptr(), dev_n.data_ptr(), dev_rows.data_ptr(),
+                                                    _stream()), "million_window_commit_rows")
+        _vshadow_drop(v_pool)
+        return
     L.check(L.load().million_window_commit(ctypes.byref(desc), k_new.data_ptr(), v_new.data_ptr(), k_res.data_ptr(), v_res.data_ptr(),
                                            k_prep.data_ptr(), v_prep.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(),
                                            page_ids.data_ptr(), dev_lengths.data_ptr(), dev_n.data_ptr(), _stream()),

@@ -29,6 +29,7 @@ import torch
 
 from . import _lib as L
 from . import ops
+from . import spec_tree
 
 
 def l2Ns(l: int) -> int:
@@ -1243,15 +1244,32 @@ class PagedPQCache(_CacheBase):
     def _mirror_sig(self):
         return (self._T_a.copy(), self._r_a.copy(), self._rs_a.copy())
 
+    def _verify_trees(self, tree, n):
+        """verify()'s tree= as bs tuples of n parents: one sequence of parents shared by every slot, or bs of them."""
+        tree = list(tree)
+        per_slot = len(tree) > 0 and all(isinstance(t, (list, tuple, np.ndarray)) for t in tree)
+        if per_slot and len(tree) != self.bs:
+            raise RuntimeError(f"verify: {len(tree)} trees for {self.bs} slots (one sequence of parents for all, or one per slot)")
+        try:
+            return tuple(tuple(spec_tree.check_parents(t, n)) for t in (tree if per_slot else [tree] * self.bs))
+        except (ValueError, TypeError) as e:
+            raise RuntimeError(f"verify: tree: {e}") from None
+
     def verify(self, query_states, key_states, value_states, layer_idx, n_draft=None, use_dev_lengths=True, route=None,
-               return_lse=False):
+               return_lse=False, tree=None):
         """Attention of n <= 16 draft tokens per request over [the codes; the window; the draft rows, causally], one layer:
         q (bs, nh, n, d), K/V (bs, nh_k, n, d) -> out (bs, nh, n, d) (and lse (bs, nh, n) with return_lse).  Pure: lengths,
         pages, window and host mirror do not move; the rows' K/V are parked in a staging buffer of the cache for commit().
         n_draft: bs host ints in [0, n], the rows each slot verifies (default: n); rows past them are returned as zeros
         (lse -inf) and their q / K / V may hold anything.  route: "heads" - one decode launch over the rows as query heads,
         then ops.attn_block_merge; "chunk" - ops.pq_chunk_attn with the rows as chunk; None: _verify_route.  A side-stream
-        flush that begin_step scheduled for the layer is joined first, as decoding_with_pages joins it."""
+        flush that begin_step scheduled for the layer is joined first, as decoding_with_pages joins it.
+        tree: the draft is a tree, not a chain - n parent indices shared by every slot, or bs such sequences; parents[i] in
+        [-1, i) (a parent precedes its children; -1: a root, several allowed).  Node i is row i and sees its ancestors and
+        itself instead of the rows j <= i (spec_tree.ancestor_masks, ops.attn_block_merge(dev_mask=)); n_draft[b] live nodes
+        are a prefix of the tree.  The attention over the past is the chain's launch - it never looks at the order among the
+        rows - on either route; "chunk" then runs chunk attention over the past only and the same masked block merge.  A
+        malformed tree is refused (RuntimeError) before anything runs; commit() then takes path=."""
         bs, nh, n, d = query_states.shape
         nk = self.num_key_value_heads
         if bs != self.bs or nh != self.nh or d != self.d or key_states.shape != (bs, nk, n, d) or value_states.shape != key_states.shape:
@@ -1265,15 +1283,21 @@ class PagedPQCache(_CacheBase):
         route = self._verify_route(n) if route is None else route
         if route not in ("heads", "chunk"):
             raise RuntimeError(f"verify: route {route!r} ('heads', 'chunk' or None)")
+        trees = None if tree is None else self._verify_trees(tree, n)
         self._join_flush(layer_idx)
         if not use_dev_lengths and not self._lockstep(layer_idx):
             raise RuntimeError("PagedPQCache: requests at different lengths need use_dev_lengths=True")
         rec = self._verify_rec
         sig = self._mirror_sig()
-        if rec is None or rec["n"] != n or rec["n_draft"] != n_draft or any(not np.array_equal(a, b) for a, b in zip(rec["sig"], sig)):
+        if (rec is None or rec["n"] != n or rec["n_draft"] != n_draft or rec.get("tree") != trees
+                or any(not np.array_equal(a, b) for a, b in zip(rec["sig"], sig))):
             rec = self._verify_rec = {"n": n, "n_draft": n_draft, "sig": sig, "layers": set(),
                                       "dev_n": torch.tensor(n_draft, dtype=torch.int32).to(self.device)}
+            if trees is not None:      # the ancestor masks, once per record
+                rec["tree"] = trees
+                rec["dev_mask"] = torch.from_numpy(np.stack([spec_tree.ancestor_masks(t) for t in trees])).to(self.device)
         dev_n = rec["dev_n"]
+        masked = {} if trees is None else {"dev_mask": rec["dev_mask"]}
         if self._kstage is None:
             shape = (self.layer_num, self.bs, nk, self.VERIFY_MAX_ROWS, self.d)
             self._kstage = torch.zeros(shape, dtype=self.scalar_t, device=self.device)
@@ -1296,7 +1320,15 @@ class PagedPQCache(_CacheBase):
                                               workspace=ws[n], return_lse=True)
             out_a, lse_a = out_a.view(bs, nh, n, d), lse_a.view(bs, nh, n)
             res = ops.attn_block_merge(qv, key_states, value_states, out_a, lse_a, dev_n, out=out_a, return_lse=return_lse,
-                                       k_stage=ks, v_stage=vs)
+                                       k_stage=ks, v_stage=vs, **masked)
+        elif trees is not None:      # chunk attention over the past only (the chunk kernel knows chains), then the masked block
+            bound = int(self._T_a[layer_idx].max()) if use_dev_lengths else T
+            out_a, lse_a = ops.pq_chunk_attn(query_states, None, None, self.key_page_pool, self.value_page_pool, self._kprep,
+                                             self._vprep, kres, vres, r, M=self.M, C=self.C, n_tokens=bound, resid_start=rs,
+                                             k_page_ids=ids, v_page_ids=ids, page_size=self.page_size, dev_lengths=dl, dev_n_q=dev_n,
+                                             return_lse=True)
+            res = ops.attn_block_merge(query_states, key_states, value_states, out_a, lse_a, dev_n, out=out_a, return_lse=return_lse,
+                                       k_stage=ks, v_stage=vs, **masked)
         else:
             bound = int(self._T_a[layer_idx].max()) if use_dev_lengths else T
             res = ops.pq_chunk_attn(query_states, key_states, value_states, self.key_page_pool, self.value_page_pool, self._kprep,
@@ -1320,16 +1352,29 @@ class PagedPQCache(_CacheBase):
                 self._r_a[:, b] += a
                 self._seen_a[:, b] += a
 
-    def commit(self, n_accept):
+    def commit(self, n_accept=None, *, path=None):
         """Append the first n_accept[b] of the rows verify() staged to the window of slot b, in every layer and in ONE call
         (ops.window_commit), exactly as n_accept[b] decode steps with those rows would have: codes, pages, window rows, host
         and device lengths; decoding_with_pages, begin_step, fork, swap_out and extend_* go on as after those steps.
         n_accept: bs host ints, 0 <= n_accept[b] <= n_draft[b] of the verify() that must have run for every layer since the
         cache last moved.  Call it between steps, as fork: refused (RuntimeError, before anything moves) mid-step, while a
         side-stream flush is pending, without a full verify, and when a slot's flush would pass max_tokens or the free
-        pages.  A finished encode-ahead launch (begin_step) is joined first; pages on demand are taken before the launch."""
-        n_accept = [int(x) for x in n_accept]
+        pages.  A finished encode-ahead launch (begin_step) is joined first; pages on demand are taken before the launch.
+        path (after verify(tree=), which needs it): bs sequences of node indices, each empty or a chain of the slot's tree from
+        a root - parents[p[0]] == -1, parents[p[k]] == p[k - 1], every node below n_draft[b]; the rows of the path are appended
+        in its order (ops.window_commit(dev_rows=)) and n_accept[b] = len(path[b]) (an n_accept given too must say the same).
+        After a verify() without a tree, path[b] can only be range(a)."""
         rec = self._verify_rec
+        if path is not None:
+            try:
+                path = [[int(x) for x in p] for p in path]
+            except TypeError:
+                raise RuntimeError("commit: path is one sequence of node indices per slot") from None
+            if n_accept is None:
+                n_accept = [len(p) for p in path]
+        elif n_accept is None:
+            raise RuntimeError("commit: n_accept or path expected")
+        n_accept = [int(x) for x in n_accept]
         nl, ps, cap, nk = self.layer_num, self.page_size, self.extended_residual_size, self.num_key_value_heads
         cols = (self._T_a, self._r_a, self._rs_a)
         if self._ahead is not None or self._flush_events or any((c != c[0]).any() for c in cols):
@@ -1338,6 +1383,20 @@ class PagedPQCache(_CacheBase):
             raise RuntimeError("commit: verify() must have run for every layer, with the same n_draft, since the cache last moved")
         if len(n_accept) != self.bs or any(not 0 <= a <= nd for a, nd in zip(n_accept, rec["n_draft"])):
             raise RuntimeError(f"commit: one n_accept per slot, each in [0, n_draft[b]] (n_draft = {rec['n_draft']})")
+        trees = rec.get("tree")
+        if path is None:
+            if trees is not None:
+                raise RuntimeError("commit: the verification was of a tree: path= names the accepted chain of every slot")
+        else:
+            if len(path) != self.bs or [len(p) for p in path] != n_accept:
+                raise RuntimeError(f"commit: one path per slot, of n_accept[b] nodes (n_accept = {n_accept})")
+            for b, p in enumerate(path):
+                if trees is None:
+                    if p != list(range(len(p))):
+                        raise RuntimeError(f"commit: path of slot {b} {p}: the verification was of a chain, whose paths are range(a)")
+                elif not spec_tree.is_path(trees[b], p, rec["n_draft"][b]):
+                    raise RuntimeError(f"commit: path of slot {b} {p} is no chain from a root of its tree {list(trees[b])} below "
+                                       f"n_draft = {rec['n_draft'][b]}")
         flush = [b for b, a in enumerate(n_accept) if a and self._r_a[0, b] + a > cap]
         for b in flush:
             if int(self._T_a[0, b]) + ps > self.max_tokens:
@@ -1358,8 +1417,14 @@ class PagedPQCache(_CacheBase):
         if not any(n_accept):
             return
         dev_n = torch.tensor(n_accept, dtype=torch.int32).to(self.device)
+        rows = {}
+        if trees is not None:
+            idx = np.zeros((self.bs, rec["n"]), np.int32)
+            for b, p in enumerate(path):
+                idx[b, :len(p)] = p
+            rows["dev_rows"] = torch.from_numpy(idx).to(self.device)
         ops.window_commit(self._kstage, self._vstage, self._kres_all, self._vres_all, self._kprep, self._vprep, self.key_page_pool,
-                          self.value_page_pool, self._page_ids_all, self._lengths_all, dev_n, M=self.M, C=self.C, n_bound=rec["n"])
+                          self.value_page_pool, self._page_ids_all, self._lengths_all, dev_n, M=self.M, C=self.C, n_bound=rec["n"], **rows)
         self._note_committed(n_accept)
 
     # ---- host mirror management for captured (hipGraph) decode steps ------------------------------
