@@ -1,6 +1,8 @@
 """Random request lifecycles of a PagedPQCache against a per-request model: the model, the script generator, the coverage
-condition and the invariant checks that tests/test_cache_life_host.py (CPU cache, launches replaced by numpy stand-ins) and
-tests/test_cache_life_gpu.py (real cache, real bits) share.  numpy only (snapshot() copies a cache's tensors to the host).
+condition, the row filler of every family of scripts and the invariant checks.  tests/cache_life_driver.py runs a script on a
+cache and says what is checked; tests/test_cache_life_host.py (CPU cache, launches replaced by numpy stand-ins) and
+tests/test_cache_life_gpu.py (real cache, real bits) name the scripts.  numpy only (snapshot() copies a cache's tensors to the
+host).
 
 The model.  Per slot b and layer: the fp16 K and V rows the request was given, in order, with the oracle's codes of every row
 (oracle.pq_encode, once per row - encode_rows: a code depends on nothing but its row and the codebook), and three integers T, r, rs -
@@ -372,47 +374,66 @@ def plan(seed, geom, rs=None):
     return calls
 
 
-def script(seed, geom, rows=True):
-    """The calls of plan(seed, geom) with their rows, standard-normal fp16, all from RandomState(seed): decode bursts q
-    (steps, layers, bs, nh, 1, d), k / v (steps, layers, bs, nh_k, 1, d); one request q (layers, 1, nh, n, d), k / v (layers, 1,
-    nh_k, n, d); ragged batches q (layers, bs, nh, max n_new, d), k / v alike, NaN in the rows past n_new[b] (they may hold
-    anything)."""
-    rs = np.random.RandomState(seed)
-    calls = plan(seed, geom, rs)
-    if not rows:
-        return calls
+def fill_rows(calls, geom, rs):
+    """The rows of every call, standard-normal fp16 drawn from rs in the calls' order: decode bursts q (steps, layers, bs, nh, 1, d),
+    k / v (steps, layers, bs, nh_k, 1, d); one request q (layers, 1, nh, n, d), k / v (layers, 1, nh_k, n, d); ragged batches and
+    verify_commit calls (tests/cache_verify_life.py) q (layers, bs, nh, n, d), k / v alike, n = max n_new or the call's, NaN in the
+    rows past n_new[b] or n_draft[b] (they may hold anything); a `reverify` call a second set after the first, q0 / k0 / v0; then
+    the rows of the call in `between`."""
     nl, bs, nh, nhk, d = geom["layer_num"], geom["bs"], geom["nh"], geom["num_key_value_heads"], geom["d"]
     f = lambda *s: rs.standard_normal(s).astype(np.float16)
-    for call in calls:
+
+    def fill(call):
         op = call["op"]
         if op == "decode":
             call["q"], call["k"], call["v"] = f(call["steps"], nl, bs, nh, 1, d), f(call["steps"], nl, bs, nhk, 1, d), f(call["steps"], nl, bs, nhk, 1, d)
         elif op in ("prefill_request", "extend_request"):
             call["q"], call["k"], call["v"] = f(nl, 1, nh, call["n"], d), f(nl, 1, nhk, call["n"], d), f(nl, 1, nhk, call["n"], d)
-        elif op in ("prefill_ragged", "extend_ragged"):
-            n = max(call["n_new"])
-            call["q"], call["k"], call["v"] = f(nl, bs, nh, n, d), f(nl, bs, nhk, n, d), f(nl, bs, nhk, n, d)
-            for b, nb in enumerate(call["n_new"]):
-                for a in (call["q"], call["k"], call["v"]):
-                    a[:, b, :, nb:] = np.nan
+        elif op in ("prefill_ragged", "extend_ragged", "verify_commit"):
+            n, counts = (call["n"], call["n_draft"]) if op == "verify_commit" else (max(call["n_new"]), call["n_new"])
+            for keys in (("q", "k", "v"), ("q0", "k0", "v0"))[:2 if call.get("reverify") else 1]:
+                call[keys[0]], call[keys[1]], call[keys[2]] = f(nl, bs, nh, n, d), f(nl, bs, nhk, n, d), f(nl, bs, nhk, n, d)
+                for b, nb in enumerate(counts):
+                    for key in keys:
+                        call[key][:, b, :, nb:] = np.nan
+            if call.get("between"):
+                fill(call["between"])
+    for call in calls:
+        fill(call)
     return calls
+
+
+def script(seed, geom, rows=True, plan=plan):
+    """The calls of plan(seed, geom), with their rows (fill_rows), all from RandomState(seed).  (plan: the generator of another
+    family of scripts - tests/cache_swap_life.py, tests/cache_verify_life.py.)"""
+    rs = np.random.RandomState(seed)
+    calls = plan(seed, geom, rs)
+    return fill_rows(calls, geom, rs) if rows else calls
 
 
 def encode_rows(calls, geom, f_k, f_v, pool):
     """call["kc"], call["vc"]: the codes of every row a script hands to the model, shaped as the rows with M in the last axis -
     each row's codes computed once, by f_k / f_v ((1, 1, n, d) fp16 -> (1, 1, n, M) uint8: oracle.pq_encode with the key / value
-    codebook), on the threads of `pool` (a concurrent.futures executor; the oracle's C loops run without the interpreter lock)."""
+    codebook), on the threads of `pool` (a concurrent.futures executor; the oracle's C loops run without the interpreter lock).
+    Of a ragged batch the rows below n_new[b], of a verify_commit those below n_accept[b] (the model takes no other); a refused
+    call's rows are nobody's, but for the decode step between its verify and its commit."""
     tasks = []
-    for call in calls:
+
+    def add(call):
+        if call.get("between"):
+            add(call["between"])
         if "k" not in call or call.get("raises"):
-            continue
+            return
+        counts = call["n_accept"] if call["op"] == "verify_commit" else call.get("n_new")
         for key, f in (("k", f_k), ("v", f_v)):
             x = call[key]
             out = call[key + "c"] = np.zeros(x.shape[:-1] + (geom["M"],), np.uint8)
-            if "n_new" in call:      # the rows past n_new[b] are nobody's
-                tasks += [(f, x[:, b, :, :n], out[:, b, :, :n]) for b, n in enumerate(call["n_new"]) if n]
+            if counts is not None:
+                tasks.extend((f, x[:, b, :, :n], out[:, b, :, :n]) for b, n in enumerate(counts) if n)
             else:
                 tasks.append((f, x, out))
+    for call in calls:
+        add(call)
 
     def run(task):
         f, x, out = task
@@ -533,6 +554,9 @@ def check_end(cache, m, geom, tables0):
         assert snap["allocated_pages"] == 0 and not snap["ref"] and len(snap["free"]) == cache.page_manager.current_active_pages
 
 
+ROW_KEYS = ("q", "k", "v", "kc", "vc", "q0", "k0", "v0")
+
+
 def describe(call):
     """A call without its rows, for messages."""
-    return ", ".join(f"{k}={v}" for k, v in call.items() if k not in ("q", "k", "v", "kc", "vc"))
+    return ", ".join(f"{k}=({describe(v)})" if k == "between" and v else f"{k}={v}" for k, v in call.items() if k not in ROW_KEYS)

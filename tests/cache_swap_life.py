@@ -8,8 +8,9 @@ import, with two more rules
 
 and a script generator of its own over the calls decode, prefill_request, extend_request, fork (whole), release, swap_out and
 swap_in.  A seed is kept only if its script meets REQUIRED (a swap of a slot with shared pages is asked of the
-on-demand geometry only - a preallocated table shares nothing - so on the GPU share-32 / seed 37 is the script that has one).  tests/test_cache_swap_life_host.py runs the scripts on a CPU cache
-whose launches are the numpy stand-ins, tests/test_cache_swap_life_gpu.py on a real one."""
+on-demand geometry only - a preallocated table shares nothing - so on the GPU share-32 / seed 37 is the script that has one).
+tests/cache_life_driver.py runs a script: for tests/test_cache_swap_life_host.py on a CPU cache whose launches are numpy
+stand-ins, for tests/test_cache_swap_life_gpu.py on a real one."""
 import numpy as np
 
 from tests import cache_life_model as LM
@@ -206,16 +207,4 @@ def plan(seed, geom, rs=None):
 
 
 def script(seed, geom, rows=True):
-    """The calls of plan(seed, geom) with their rows, shaped as LM.script shapes them, all from RandomState(seed)."""
-    rs = np.random.RandomState(seed)
-    calls = plan(seed, geom, rs)
-    if not rows:
-        return calls
-    nl, bs, nh, nhk, d = geom["layer_num"], geom["bs"], geom["nh"], geom["num_key_value_heads"], geom["d"]
-    f = lambda *s: rs.standard_normal(s).astype(np.float16)
-    for call in calls:
-        if call["op"] == "decode":
-            call["q"], call["k"], call["v"] = f(call["steps"], nl, bs, nh, 1, d), f(call["steps"], nl, bs, nhk, 1, d), f(call["steps"], nl, bs, nhk, 1, d)
-        elif call["op"] in ("prefill_request", "extend_request"):
-            call["q"], call["k"], call["v"] = f(nl, 1, nh, call["n"], d), f(nl, 1, nhk, call["n"], d), f(nl, 1, nhk, call["n"], d)
-    return calls
+    return LM.script(seed, geom, rows, plan)

@@ -27,8 +27,9 @@ scene in between, and last the refusal at a full page table, which needs a slot 
 calls, at most 30 verifies, and 150 decode steps at a window of 64 rows, 230 at one of 128: a scene that wants a full window has
 to pay for its rows, by decode steps (every slot's) or by rounds of 16 rows.
 
-A seed is kept only if its script meets REQUIRED (missing()).  tests/test_cache_verify_life_host.py runs the scripts on a CPU
-cache whose launches are numpy stand-ins, tests/test_cache_verify_life_gpu.py on a real one."""
+A seed is kept only if its script meets REQUIRED (missing()).  tests/cache_life_driver.py runs a script: for
+tests/test_cache_verify_life_host.py on a CPU cache whose launches are numpy stand-ins, for tests/test_cache_verify_life_gpu.py
+on a real one."""
 import copy
 
 import numpy as np
@@ -41,7 +42,6 @@ SEEDS = {"share-32": (0, 1), "share-64-ahead": (0, 320), "copy-32-ahead": (0, 2)
 N_CALLS, MAX_ROUNDS, MAX_HELD = 50, 30, 3      # calls (about) and verify rounds (at most) per script
 DECODE_BUDGET = {64: 150, 128: 230}      # decode steps per script, about, by the window's rows: a scene that needs a full window pays for one
 NS = (1, 2, 4, 5, 16)      # draft rows per request; 16 rows under G = 4 query heads: 64 rows per kv head
-ROW_KEYS = ("q", "k", "v", "kc", "vc", "q0", "k0", "v0")
 # the refusal kinds and the word of the cache's message each must carry
 REFUSALS = {"no_verify": "verify", "moved": "verify", "partial_layers": "verify", "over_accept": "n_accept", "max_tokens": "max_tokens"}
 
@@ -697,53 +697,7 @@ def plan(seed, geom, rs=None):
 
 
 def script(seed, geom, rows=True):
-    """The calls of plan(seed, geom) with their rows, shaped as LM.script shapes them (a verify_commit: see the header), all from
-    RandomState(seed)."""
-    rs = np.random.RandomState(seed)
-    calls = plan(seed, geom, rs)
-    if not rows:
-        return calls
-    nl, bs, nh, nhk, d = geom["layer_num"], geom["bs"], geom["nh"], geom["num_key_value_heads"], geom["d"]
-    f = lambda *s: rs.standard_normal(s).astype(np.float16)
-
-    def fill(call):
-        op = call["op"]
-        if op == "decode":
-            call["q"], call["k"], call["v"] = f(call["steps"], nl, bs, nh, 1, d), f(call["steps"], nl, bs, nhk, 1, d), f(call["steps"], nl, bs, nhk, 1, d)
-        elif op in ("prefill_request", "extend_request"):
-            call["q"], call["k"], call["v"] = f(nl, 1, nh, call["n"], d), f(nl, 1, nhk, call["n"], d), f(nl, 1, nhk, call["n"], d)
-        elif op in ("prefill_ragged", "extend_ragged", "verify_commit"):
-            n, counts = (call["n"], call["n_draft"]) if op == "verify_commit" else (max(call["n_new"]), call["n_new"])
-            for keys in (("q", "k", "v"), ("q0", "k0", "v0"))[:2 if call.get("reverify") else 1]:
-                call[keys[0]], call[keys[1]], call[keys[2]] = f(nl, bs, nh, n, d), f(nl, bs, nhk, n, d), f(nl, bs, nhk, n, d)
-                for b, nb in enumerate(counts):
-                    for key in keys:
-                        call[key][:, b, :, nb:] = np.nan
-            if call.get("between"):
-                fill(call["between"])
-    for call in calls:
-        fill(call)
-    return calls
+    return LM.script(seed, geom, rows, plan)
 
 
-def encode_rows(calls, geom, f_k, f_v, pool):
-    """LM.encode_rows for every call it knows; of a verify_commit the oracle's codes of the rows below n_accept[b] only (the
-    model takes no other), through the same "n_new" branch; the decode step between a refused call's verify and commit too."""
-    flat, shims = [], []
-    for call in calls:
-        if call["op"] != "verify_commit":
-            flat.append(call)
-            continue
-        if call.get("between"):
-            flat.append(call["between"])
-        if not call.get("raises"):
-            shims.append((call, dict(k=call["k"], v=call["v"], n_new=call["n_accept"])))
-            flat.append(shims[-1][1])
-    LM.encode_rows(flat, geom, f_k, f_v, pool)
-    for call, shim in shims:
-        call["kc"], call["vc"] = shim["kc"], shim["vc"]
-
-
-def describe(call):
-    """A call without its rows, for messages."""
-    return ", ".join(f"{k}=({describe(v)})" if k == "between" and v else f"{k}={v}" for k, v in call.items() if k not in ROW_KEYS)
+ROW_KEYS, encode_rows = LM.ROW_KEYS, LM.encode_rows      # (written once, for every family)

@@ -1,25 +1,14 @@
 """CPU tests of the random lifecycles with draft verification (tests/cache_verify_life.py): the coverage condition of every
-committed script, the model's per-slot append rule against both forms of tests/verify_model.py, and the scripts on a CPU
-PagedPQCache whose launches are the numpy stand-ins of the life and swap host tests plus three of this file's - ops.window_commit
-advances the length rows by verify_model.commit_closed, the verify launches return zeros - with lengths (device rows and host
-mirrors) and the allocator's invariants checked after every call, every refusal moving nothing, and every restored slot's live
-data against what left at swap_out.
-
-All four geometries run here: begin_step's side stream and events are replaced by objects that do nothing (a CPU cache's
-launches are the stand-ins, in program order), so the kind of every decode step the cache reports is held against the model's
-(Model.next_kind), which the coverage condition is computed on."""
-import contextlib
-
+committed script, the model's per-slot append rule against both forms of tests/verify_model.py, and every script on a CPU
+PagedPQCache (tests/cache_life_driver.py says what is checked); on the begin_step geometries the coverage condition is held
+against the kinds of decode step the cache reported too."""
 import numpy as np
 import pytest
-import torch
 
+from tests import cache_life_driver as D
 from tests import cache_life_model as LM
-from tests import cache_swap_model as SWM
 from tests import cache_verify_life as VL
 from tests import verify_model as VM
-from tests.test_cache_life_host import _cpu_cache, _stand_ins
-from tests.test_cache_swap_life_host import _live
 
 CASES = [(name, seed) for name, seeds in VL.SEEDS.items() for seed in seeds]
 
@@ -108,156 +97,11 @@ def test_append_rule_is_both_forms_of_the_commit(name):
                 assert (m.T[0], m.r[0], m.rs[0]) == (5, 9, 0) and m.n(1) == 3 * ps + r + a      # that slot only; no row is lost
 
 
-# ---------------------------------------------------------------- the scripts on a CPU cache --------------------------------
-class _Nothing:
-    """A stream or an event of a cache whose launches are host functions."""
-
-    def __init__(self, *a, **k):
-        pass
-
-    wait_stream = wait_event = record = synchronize = lambda self, *a, **k: None
-
-
-def verify_stand_ins(monkeypatch):
-    """Stand-ins of the launches verify and commit add to those of the life and swap host tests, and of the side stream."""
-    from million_amd import ops
-    step_attn = ops.pq_decode_attn      # (the life test's: the fused append advances r)
-
-    def decode_attn(q, *a, k_new=None, return_lse=False, **k):
-        if k_new is not None:
-            return step_attn(q, *a, **k)
-        out = torch.zeros_like(q)      # a verify launch appends nothing
-        return (out, torch.zeros(q.shape[:3])) if return_lse else out
-
-    def block_merge(q, k_blk, v_blk, out_a, lse_a, dev_n=None, out=None, lse_out=None, return_lse=False, k_stage=None, v_stage=None):
-        out = torch.zeros_like(q) if out is None else out
-        return (out, torch.zeros(q.shape[:3])) if return_lse else out
-
-    def window_commit(k_new, v_new, k_res, v_res, k_prep, v_prep, k_pool, v_pool, page_ids, dev_lengths, dev_n, *, M, C, n_bound=None):
-        rows, ps, cap = dev_lengths.numpy(), k_pool.shape[1], k_res.shape[3]
-        assert rows.shape[:2] == (k_res.shape[0], len(dev_n)) and int(dev_n.max()) <= n_bound <= k_new.shape[3]
-        for l in range(rows.shape[0]):
-            for b, a in enumerate(dev_n.tolist()):
-                T, r, st = VM.commit_closed(*(int(x) for x in rows[l, b, :3]), a, ps, cap)[:3]
-                assert T <= page_ids.shape[3] * ps, "a flush past the page table"
-                rows[l, b, :3] = (T, r, st)
-
-    monkeypatch.setattr(ops, "pq_decode_attn", decode_attn)
-    monkeypatch.setattr(ops, "attn_block_merge", block_merge)
-    monkeypatch.setattr(ops, "window_commit", window_commit)
-    monkeypatch.setattr(ops, "decode_workspace_bytes", lambda *a, **k: 16)
-    monkeypatch.setattr(ops, "cache_swap", SWM.as_ops_stub())
-    monkeypatch.setattr(torch.cuda, "Stream", _Nothing)
-    monkeypatch.setattr(torch.cuda, "Event", _Nothing)
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: _Nothing())
-    monkeypatch.setattr(torch.cuda, "stream", lambda s: contextlib.nullcontext())
-    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: False)
-
-
-def _same(before, after):
-    return all(np.array_equal(before[k], after[k]) if isinstance(before[k], np.ndarray) else before[k] == after[k] for k in before)
-
-
-def run_on_cpu(cache, calls, geom):
-    """Drives the cache through a script (rows of zeros: nothing reads them), the model beside it; the checks after every call.
-    -> the kinds begin_step reported."""
-    m = VL.Model(geom)
-    nl, bs, nh, nhk, d = geom["layer_num"], geom["bs"], geom["nh"], geom["num_key_value_heads"], geom["d"]
-    z = lambda *s: torch.zeros(*s, dtype=torch.float16)
-    tables0 = cache._page_ids_all.numpy().copy()
-    snaps, left, kinds = {}, {}, []
-
-    def check(what):
-        snap = LM.snapshot(cache)
-        LM.check_lengths(m, snap, what)
-        if geom["preallocate"]:
-            LM.check_allocator_preallocated(snap, tables0, what)
-        else:
-            LM.check_allocator_on_demand(m, snap, what)
-
-    def verify(call, layers):
-        for _ in range(2 if call["reverify"] else 1):
-            for l in layers:
-                cache.verify(z(bs, nh, call["n"], d), z(bs, nhk, call["n"], d), z(bs, nhk, call["n"], d), l, n_draft=call["n_draft"],
-                             route=call["route"])
-
-    def do(call, what):
-        op = call["op"]
-        if op == "decode":
-            for s in range(call["steps"]):
-                kind = None
-                if geom["begin_step"]:
-                    want = m.next_kind()
-                    kind = cache.begin_step(use_dev_lengths=True)
-                    kind = "pre" if kind.startswith("pre") else kind
-                    assert kind == want, f"{what}: step {s} is a {kind!r} step, the model expects {want!r}"
-                    kinds.append(kind)
-                for l in range(nl):
-                    cache.decoding_with_pages(z(bs, nh, 1, d), z(bs, nhk, 1, d), z(bs, nhk, 1, d), l, use_dev_lengths=True)
-                m.step(kind=kind)
-                assert np.array_equal(cache._pre_a, np.tile(m.pre, (nl, 1))), f"{what}: step {s}: encoded-ahead flags {cache._pre_a.tolist()}, model {m.pre.tolist()}"
-            return
-        if op == "verify_commit":
-            before = LM.snapshot(cache)
-            verify(call, call["layers"])
-            assert _same(before, LM.snapshot(cache)), f"{what}: verify moved something"
-            if call.get("between"):
-                m.verify(call["n"], call["n_draft"], call["layers"])
-                do(call["between"], what + ": between")
-                check(what + ": between")
-                call = dict(call, layers=[], between=None)
-            if call.get("raises"):
-                before = LM.snapshot(cache)
-                with pytest.raises(RuntimeError, match=VL.REFUSALS[call["refusal"]]):
-                    cache.commit(call["n_accept"])
-                assert _same(before, LM.snapshot(cache)), f"{what}: a refused call moved something"
-            else:
-                cache.commit(call["n_accept"])
-            m.apply(call)
-            return
-        if op == "swap_out":
-            left[call["snap"]] = _live(cache, call["b"])
-            snaps[call["snap"]] = cache.swap_out(call["b"])
-        elif op == "swap_in":
-            cache.swap_in(call["b"], snaps[call["snap"]])
-            for a, b in zip(left[call["snap"]], _live(cache, call["b"])):
-                assert np.array_equal(a, b), f"{what}: the restored slot does not hold what left"
-        elif op == "release":
-            cache.release(call["b"])
-        elif op == "fork":
-            cache.fork(call["src"], call["dst"], n_tokens=call["n_tokens"])
-        elif op in ("prefill_request", "extend_request"):
-            for l in range(nl):
-                getattr(cache, op)(call["b"], z(1, nh, call["n"], d), z(1, nhk, call["n"], d), z(1, nhk, call["n"], d), l)
-        else:
-            n = max(call["n_new"])
-            for l in range(nl):
-                getattr(cache, op)(z(bs, nh, n, d), z(bs, nhk, n, d), z(bs, nhk, n, d), l, call["n_new"], device_store=call["device_store"])
-        m.apply(call)
-
-    for i, call in enumerate(calls):
-        what = f"call {i} ({VL.describe(call)})"
-        do(call, what)
-        check(what)
-        assert np.array_equal(cache._pre_a, np.tile(m.pre, (nl, 1))), f"{what}: encoded-ahead flags {cache._pre_a.tolist()}, model {m.pre.tolist()}"
-    LM.check_end(cache, m, geom, tables0)
-    return kinds
-
-
 @pytest.mark.parametrize("name,seed", CASES, ids=[f"{n}-{s}" for n, s in CASES])
 def test_script_on_a_cpu_cache(monkeypatch, name, seed):
     geom = VL.GEOMS[name]
-    _stand_ins(monkeypatch)
-    verify_stand_ins(monkeypatch)
-    cache = _cpu_cache(geom)
-    # the stand-ins encode nothing: give every pool page and window row bytes of its own, so that a restored slot shows its request
-    g = torch.Generator().manual_seed(seed)
-    cache.key_page_pool.copy_(torch.randint(0, 256, cache.key_page_pool.shape, generator=g, dtype=torch.uint8))
-    cache.value_page_pool.copy_(torch.randint(0, 256, cache.value_page_pool.shape, generator=g, dtype=torch.uint8))
-    cache._kres_all.copy_(torch.randn(cache._kres_all.shape, generator=g).half())
-    cache._vres_all.copy_(torch.randn(cache._vres_all.shape, generator=g).half())
     calls = VL.script(seed, geom, rows=False)
-    kinds = run_on_cpu(cache, calls, geom)
+    kinds = D.run_on_cpu(monkeypatch, geom, calls, seed).kinds
     if geom["begin_step"]:      # the coverage condition on the kinds the cache reported
         cnt = VL.coverage(calls, geom, kinds=kinds)
         assert not VL.missing(cnt, geom), f"{name} seed {seed} on the reported kinds lacks (have, need): {VL.missing(cnt, geom)}"
