@@ -66,8 +66,10 @@ __global__ __launch_bounds__(kEncBlock) void pq_encode_kernel(EncParams p) {
         codes |= (unsigned long long)(unsigned)best_c << (kCB * j);
     }
     if (!valid) return;
+    // inside the page table: 0 <= tok0 and tok0 + t < n_pages_cap * page_size, decided without the sum (an untrusted tok0
+    // near INT_MAX would wrap it); the product fits an int (host check, fill_enc_params)
+    if (tok0 < 0 || (p.layout != MILLION_CODES_ROWMAJOR && tok0 > p.n_pages_cap * p.page_size - 1 - t)) return;
     const int tok = tok0 + t;
-    if (tok0 < 0 || (p.layout != MILLION_CODES_ROWMAJOR && tok / p.page_size >= p.n_pages_cap)) return;
     CodeT *dst = (CodeT *)p.dst;      // strides dsb / dsh are in bytes
     if (p.layout == MILLION_CODES_VPAGES) {
         const long long pid = p.page_ids[(long long)bh * p.n_pages_cap + tok / p.page_size];
@@ -79,7 +81,7 @@ __global__ __launch_bounds__(kEncBlock) void pq_encode_kernel(EncParams p) {
     }
     CodeT *row;
     if (p.layout == MILLION_CODES_ROWMAJOR) {
-        row = (CodeT *)(p.dst + b * p.dsb + hk * p.dsh) + (long long)tok * p.M + m0;
+        row = (CodeT *)(p.dst + b * p.dsb + hk * p.dsh) + ((long long)tok0 + t) * p.M + m0;      // (no table to clamp to: 64-bit, as the small kernel)
     } else {
         const long long pid = p.page_ids[(long long)bh * p.n_pages_cap + tok / p.page_size];
         row = dst + (pid * p.page_size + tok % p.page_size) * p.M + m0;
@@ -136,12 +138,12 @@ __device__ __forceinline__ void encode_small_body(const EncParams &p, int m, int
         const float dj = cand_d[j][lane];
         if (dj < best) { best = dj; best_c = cand_c[j][lane]; }
     }
-    const int tok = tok0 + t;
     if (tok0 < 0) return;
     if (p.layout == MILLION_CODES_ROWMAJOR) {
-        p.dst[b * p.dsb + hk * p.dsh + (long long)tok * p.M + m] = (uint8_t)best_c;
+        p.dst[b * p.dsb + hk * p.dsh + ((long long)tok0 + t) * p.M + m] = (uint8_t)best_c;
     } else {
-        if (tok / p.page_size >= p.n_pages_cap) return;
+        if (tok0 > p.n_pages_cap * p.page_size - 1 - t) return;      // tok0 + t outside the table, without the wrapping sum
+        const int tok = tok0 + t;
         const long long pid = p.page_ids[(long long)bh * p.n_pages_cap + tok / p.page_size];
         const int off = tok % p.page_size;
         if (p.layout == MILLION_CODES_KPAGES) p.dst[(pid * p.page_size + off) * p.M + m] = (uint8_t)best_c;
@@ -254,9 +256,11 @@ __global__ __launch_bounds__(kFlushWaves * 64) void pq_flush_kernel(FlushParams 
         }
         int pid;
         {
-            const int page = (tok0 + (int)blockIdx.x * 64 + lane) / p.page_size;
-            const bool ok = tok0 >= 0 && page < p.n_pages_cap;
-            pid = p.page_ids[layer * f.ids_ls + (b * p.nh_k + hkc) * p.n_pages_cap + (ok ? page : 0)];      // < 2^31 entries per layer (host check)
+            // tok0 + tl inside the table, decided without the sum (an untrusted tok0 near INT_MAX would wrap it negative)
+            const int tl = (int)blockIdx.x * 64 + lane;
+            const bool ok = tok0 >= 0 && tok0 <= p.n_pages_cap * p.page_size - 1 - tl;
+            const int page = (ok ? tok0 + tl : 0) / p.page_size;
+            pid = p.page_ids[layer * f.ids_ls + (b * p.nh_k + hkc) * p.n_pages_cap + page];      // < 2^31 entries per layer, < 2^31 tokens (host check)
         }
         // every wave has its lengths in registers (and, first layer, the codebook row is in LDS) before the barrier lets
         // thread 0 take the ticket
@@ -305,10 +309,9 @@ __global__ __launch_bounds__(kFlushWaves * 64) void pq_flush_kernel(FlushParams 
         }
         {
             const int t = blockIdx.x * 64 + lane;
-            const int tok = tok0 + t;
-            const bool tok_ok = t < p.n && tok0 >= 0 && tok / p.page_size < p.n_pages_cap;
+            const bool tok_ok = t < p.n && tok0 >= 0 && tok0 <= p.n_pages_cap * p.page_size - 1 - t;
             if (active && part == 0 && tok_ok) {
-                const int off = tok % p.page_size;
+                const int off = (tok0 + t) % p.page_size;
                 if (p.layout == MILLION_CODES_KPAGES) p.dst[((long long)pid * p.page_size + off) * p.M + m] = (uint8_t)best_c;
                 else p.dst[((long long)pid * p.M + m) * p.page_size + off] = (uint8_t)best_c;
             }
@@ -321,12 +324,13 @@ __global__ __launch_bounds__(kFlushWaves * 64) void pq_flush_kernel(FlushParams 
                 const int cap_tok = p.n_pages_cap * p.page_size;
                 int T = dl[0], r = dl[1], st = dl[2];
                 T = T < 0 ? 0 : T;
-                T = T + f.n_flush > cap_tok ? cap_tok : T + f.n_flush;
-                r = r - f.n_flush < 0 ? 0 : r - f.n_flush;
+                // no sum or difference of an untrusted word may wrap: T, r anywhere in int, n_flush and cap_tok >= 0
+                T = T > cap_tok - f.n_flush ? cap_tok : T + f.n_flush;
+                r = r < f.n_flush ? 0 : r - f.n_flush;
                 st = (unsigned)st < (unsigned)f.rcap ? st : 0;
                 dl[0] = T;
                 dl[1] = r;
-                dl[2] = (st + f.n_flush) % f.rcap;
+                dl[2] = (int)(((unsigned)st + (unsigned)f.n_flush) % (unsigned)f.rcap);
                 __hip_atomic_store(dl + 3, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }

@@ -283,6 +283,11 @@ static int fill_enc_params(const char *who, const million_encode_desc *desc, con
     if (p.layout != MILLION_CODES_ROWMAJOR) {
         if (p.layout != MILLION_CODES_KPAGES && p.layout != MILLION_CODES_VPAGES) { set_error("%s: dst_layout=%d", who, p.layout); return MILLION_ERR_ARG; }
         if (!page_ids || p.page_size <= 0) { set_error("%s: paged destination needs page_ids and page_size", who); return MILLION_ERR_ARG; }
+        // the kernels index the table and count its tokens with 32-bit arithmetic
+        if (p.n_pages_cap < 0 || (long long)p.n_pages_cap * p.page_size > 0x7fffffffLL || (long long)p.bs * p.nh_k * p.n_pages_cap > 0x7fffffffLL) {
+            set_error("%s: page table of %lld entries, %lld tokens per row", who, (long long)p.bs * p.nh_k * p.n_pages_cap, (long long)p.n_pages_cap * p.page_size);
+            return MILLION_ERR_ARG;
+        }
         if (!p.dev_lengths && (long long)p.n_pages_cap * p.page_size < (long long)p.tok0 + p.n) { set_error("%s: page table too short", who); return MILLION_ERR_ARG; }
     }
     if (p.tok0 < 0) { set_error("%s: dst_token_start=%d", who, p.tok0); return MILLION_ERR_ARG; }

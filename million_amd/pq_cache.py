@@ -468,6 +468,7 @@ class PagedPQCache(_CacheBase):
         self._seen_a, self._r_a, self._T_a, self._rs_a, self._pages_a = zi(), zi(), zi(), zi(), zi()
         self._pre_a = zi()      # 1: the oldest page_size window rows are already encoded at tokens [T, T + page_size) (begin_step)
         self._pre_join = False
+        self._dev_rows_stale = False      # a host-length step moved the mirror and not the device rows (_refresh_device_rows)
         self._host_pids = [[[[] for _ in range(nk)] for _ in range(self.bs)] for _ in range(self.layer_num)]
         self._ws = None
         # draft verification (verify / commit): the record of the running verify, the staged rows, one decode workspace per n
@@ -545,6 +546,15 @@ class PagedPQCache(_CacheBase):
         T = self._T_a[layer_idx, sel]
         rows = np.stack([T, self._r_a[layer_idx, sel], self._rs_a[layer_idx, sel], np.zeros_like(T)], axis=1)
         self.lengths[layer_idx][sel].copy_(torch.from_numpy(rows.astype(np.int32)))
+
+    def _refresh_device_rows(self):
+        """Steps with use_dev_lengths=False (decoding_with_pages, flush_to_pages, begin_step) move the host mirror only.  The
+        calls whose kernels read the device rows whatever the mode (fork: the source's row; commit: every slot's) write the
+        rows from the mirror first; after steps with device lengths there is nothing to do."""
+        if self._dev_rows_stale:
+            for l in range(self.layer_num):
+                self._sync_lengths(l)
+            self._dev_rows_stale = False
 
     def _reserve(self, layer_idx, n, b=None, ask=False) -> bool:
         """Room for n more tokens behind T of request b (None: every request, in lockstep).  A preallocated table is checked
@@ -836,6 +846,7 @@ class PagedPQCache(_CacheBase):
                         buf.append(tid)
                         self._host_pids[l][b][h] = mine
                     self._pages_a[l, b] = n_live
+        self._refresh_device_rows()      # the kernel reads the source's T, r, start from its device rows
         dev = torch.tensor(buf, dtype=torch.int32).to(self.device)
         tail_ids = dev[len(dsts):].view(len(dsts), nl, nk) if share else None
         ops.cache_fork(self._page_ids_all, self.key_page_pool, self.value_page_pool, self._kres_all, self._vres_all,
@@ -1055,6 +1066,7 @@ class PagedPQCache(_CacheBase):
                      n=ps, page_size=ps, token_start=int(self._T_a[layer_idx, 0]), x_row_start=int(self._rs_a[layer_idx, 0]),
                      dev_lengths=self.lengths[layer_idx] if use_dev_lengths else None,
                      min_r=cap if use_dev_lengths else 0)      # device lengths: only full windows flush (a captured step serves ragged batches too)
+        self._dev_rows_stale |= not use_dev_lengths
         self._note_flushed(layer_idx if lock else (layer_idx, full))
 
     # ---- encode-ahead: the flush without a flush step ---------------------------------------------------------------
@@ -1107,6 +1119,7 @@ class PagedPQCache(_CacheBase):
         if kind == "commit":
             if use_dev_lengths:
                 ops.lengths_advance(self._lengths_all.view(-1, 4), ps, cap)      # every layer, every request: one launch
+            self._dev_rows_stale |= not use_dev_lengths
             self._note_flushed(...)
         elif kind == "flush":
             self.flush_ahead(use_dev_lengths=use_dev_lengths)
@@ -1209,6 +1222,7 @@ class PagedPQCache(_CacheBase):
                                               M=self.M, C=self.C)
             self._ws = torch.zeros(need, dtype=torch.uint8, device=self.device)
         self._note_appended(layer_idx)
+        self._dev_rows_stale |= not use_dev_lengths
         # append (:377-380) + attention (:386) in ONE launch: the new row is attended to and parked in the window
         res = ops.pq_decode_attn(query_states, self.key_page_pool, self.value_page_pool, self._kprep, self._vprep,
                                  self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx], r,
@@ -1416,6 +1430,7 @@ class PagedPQCache(_CacheBase):
         self._verify_rec = None
         if not any(n_accept):
             return
+        self._refresh_device_rows()      # window_commit reads and advances every slot's device rows
         dev_n = torch.tensor(n_accept, dtype=torch.int32).to(self.device)
         rows = {}
         if trees is not None:

@@ -66,6 +66,32 @@ def test_argument_validation_without_gpu(lib):
     assert lib.million_prepared_cents_bytes(64, 256, 2) == 64 * 256 * 2 * (2 * 2 + 4)   # two fp16 images + one fp32
 
 
+@pytest.mark.parametrize("entry", ["encode", "flush"])
+@pytest.mark.parametrize("bs,nh_k,n_pages_cap,page_size,what", [
+    (1, 1, -1, 64, "negative table"),
+    (1, 1, 2 ** 25, 64, "n_pages_cap * page_size = 2^31 tokens"),
+    (1, 1, 2 ** 24, 128, "n_pages_cap * page_size = 2^31 tokens, ps = 128"),
+    (2 ** 10, 2 ** 6, 2 ** 15, 64, "bs * nh_k * n_pages_cap = 2^31 entries"),
+])
+def test_encoder_page_table_limits_without_gpu(lib, entry, bs, nh_k, n_pages_cap, page_size, what):
+    """The encoders index the page table and count its tokens in 32-bit arithmetic (encode.hip): a paged destination
+    whose table has a negative row length, 2^31 tokens per row or 2^31 entries is refused with MILLION_ERR_ARG before any launch."""
+    from million_amd import _lib
+    buf = ctypes.create_string_buffer(64)      # non-null host bytes: the checks under test run before any launch
+    ptr = ctypes.cast(buf, ctypes.c_void_p)
+    e = _lib.EncodeDesc()
+    e.struct_size = ctypes.sizeof(_lib.EncodeDesc)
+    e.bs, e.nh_k, e.n, e.d, e.M, e.C = bs, nh_k, 64, 128, 64, 256
+    e.dst_layout, e.page_size, e.n_pages_cap = _lib.MILLION_CODES_KPAGES, page_size, n_pages_cap
+    e.dev_lengths = ptr                        # device lengths: no host "table too short" check in the way
+    if entry == "encode":
+        rc = lib.million_pq_encode(ctypes.byref(e), ptr, ptr, ptr, ptr, None)
+    else:
+        rc = lib.million_pq_flush(ctypes.byref(e), ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, 128, 0, None)
+    assert rc == -3, (what, rc)
+    assert b"page table of" in lib.million_last_error(), lib.million_last_error()
+
+
 def test_kernel_kind_without_gpu(lib):
     """million_attn_kernel_kind is host logic (no launch): which kernel a descriptor gets.  Every batch x context of the
     streaming kernel's shapes stays on it (kind 1) up to 1M tokens per (b, kv head) - calls with more than 64 rounds per wave

@@ -327,6 +327,40 @@ def test_fork_shares_pages_on_demand(monkeypatch):
     assert cache._pages_a.sum() == 0 and not cache._T_a.any()
 
 
+def test_fork_after_steps_with_host_lengths_reads_fresh_device_rows(monkeypatch):
+    """Decode steps with use_dev_lengths=False move the host mirror and leave the device rows where they were; the fork kernel
+    reads the source's T, r and start from its device row.  fork must write the rows from the mirror first: the forks get the
+    source's lengths of now - and every live page of it - not those of its last step with device lengths."""
+    from million_amd import ops
+    log = []
+    cache = _cache(monkeypatch, False, log)
+    monkeypatch.setattr(ops, "decode_workspace_bytes", lambda *a, **k: 16)
+    monkeypatch.setattr(ops, "pq_flush", lambda *a, **k: None)
+    seen = []
+    monkeypatch.setattr(ops, "pq_decode_attn", lambda q, *a, dev_lengths=None, **k: (seen.append(dev_lengths), torch.zeros_like(q))[1])
+    for b in (1, 2):      # lockstep: every slot at slot 0's lengths
+        for arr in (cache._T_a, cache._r_a, cache._rs_a, cache._seen_a):
+            arr[:, b] = arr[:, 0]
+    q, x = torch.zeros(3, 8, 1, 128, dtype=torch.float16), torch.zeros(3, 2, 1, 128, dtype=torch.float16)
+    for _ in range(30):      # r: 40 -> 64 (24 steps), a flush of 32 rows (T: 70 -> 102, a fourth page), 6 more steps
+        for l in range(2):
+            cache.decoding_with_pages(q, x, x, l)
+    assert seen and all(d is None for d in seen)
+    assert cache._T_a[:, 0].tolist() == [102, 102] and cache._r_a[:, 0].tolist() == [38, 38] and cache._rs_a[:, 0].tolist() == [18, 18]
+    assert cache._lengths_all[:, 0].tolist() == [[70, 40, 50, 0]] * 2      # the device rows did not move
+    for b in (1, 2):
+        cache._T_a[:, b] = cache._r_a[:, b] = cache._rs_a[:, b] = cache._seen_a[:, b] = 0
+    cache.fork(0, [1, 2])
+    assert log[-1]["n_pages_bound"] == 4
+    assert cache._lengths_all.tolist() == [[[102, 38, 18, 0]] * 3] * 2
+    for l in range(2):
+        for h in range(2):
+            for b in (1, 2):
+                assert cache.page_ids[l][b, h, :4].tolist() == cache._host_pids[l][b][h] and len(cache._host_pids[l][b][h]) == 4
+                assert cache._host_pids[l][b][h][:3] == cache._host_pids[l][0][h][:3]
+                assert torch.equal(cache.key_page_pool[cache._host_pids[l][b][h][3]], cache.key_page_pool[cache._host_pids[l][0][h][3]])
+
+
 def test_fork_on_a_page_boundary_and_of_a_prefix(monkeypatch):
     log = []
     cache = _cache(monkeypatch, False, log)

@@ -1141,18 +1141,36 @@ def test_flush_kernel_head_groups_and_shapes(bs, nhk, d, M, C, ps, cap, n, env, 
 def test_flush_device_lengths_are_clamped_not_trusted(env, oracle):
     """Corrupt device lengths handed to the flush / encode kernels (destination token past the page table or negative,
     ring start outside the window) must drop stores or fall back to start 0 - never write outside the pools - and the
-    advanced lengths stay inside their ranges."""
+    advanced lengths stay inside their ranges.  Items 4 ..: destination tokens at the edges of int, where tok0 + lane
+    wraps (in the middle of a wave, at a page boundary, in the last lane of the last block) or tok0 is INT_MIN: nothing
+    is stored, the advance does not wrap either."""
     torch, ops = env
     from million_amd import _lib as L
-    bs, nhk, d, M, C, ps, cap, n_pages = 4, 2, 128, 64, 256, 64, 128, 3
+    bs, nhk, d, M, C, ps, cap, n_pages = 10, 2, 128, 64, 256, 64, 128, 3
+    IMAX = 2 ** 31 - 1
     rs = np.random.RandomState(77)
     ck = torch.from_numpy(rs.standard_normal((M, C, 2)).astype(np.float16)).cuda()
     kw = rs.standard_normal((bs, nhk, cap, d)).astype(np.float16)
     kwd = torch.from_numpy(kw).cuda()
-    ids = torch.arange(bs * nhk * n_pages, dtype=torch.int32).reshape(bs, nhk, n_pages).cuda()
-    bad = [[n_pages * ps + 5000, cap, 0, 0], [-64, cap, 0, 0], [ps, cap, cap + 40, 0], [ps, 10, -3, 0]]
     guard = 4      # guard pages around the pools: must stay zero
+    gi = 4096      # zero guard entries around the page tables (the tables are slices of larger tensors): must stay zero
+    n_ids = bs * nhk * n_pages
+
+    def guarded_ids(n):
+        big = torch.zeros(n + 2 * gi, dtype=torch.int32, device="cuda")
+        big[gi:gi + n] = torch.arange(n, dtype=torch.int32, device="cuda")
+        return big, big[gi:gi + n]
+
+    ids_big, ids = guarded_ids(n_ids)
+    ids = ids.view(bs, nhk, n_pages)
     for which in ("flush", "encode_small", "encode_bulk"):
+        nn = cap if which == "encode_bulk" else ps          # rows per call
+        # items 4 .. 9: IMAX; IMAX - 31 (wraps in the middle of a wave); 2^31 - ps; IMAX - n; 2^31 - n + 1 (only the last
+        # lane of the last block wraps); INT_MIN
+        bad = [[n_pages * ps + 5000, cap, 0, 0], [-64, cap, 0, 0], [ps, cap, cap + 40, 0], [ps, 10, -3, 0],
+               [IMAX, cap, 0, 0], [IMAX - 31, cap, 0, 0], [2 ** 31 - ps, cap, 0, 0], [IMAX - nn, cap, 0, 0],
+               [2 ** 31 - nn + 1, cap, 0, 0], [-2 ** 31, cap, 0, 0]]
+        assert len(bad) == bs
         kpool = torch.zeros((bs * nhk * n_pages + 2 * guard), ps, M, dtype=torch.uint8, device="cuda")
         vpool = torch.zeros((bs * nhk * n_pages + 2 * guard), M, ps, dtype=torch.uint8, device="cuda")
         kin, vin = kpool[guard:-guard], vpool[guard:-guard]
@@ -1160,13 +1178,13 @@ def test_flush_device_lengths_are_clamped_not_trusted(env, oracle):
         if which == "flush":
             ops.pq_flush(kwd, kwd, ck, ck, kin, vin, ids, n=ps, page_size=ps, dev_lengths=dl)
         else:
-            nn = ps if which == "encode_small" else cap
             src = kwd if which == "encode_small" else kwd.repeat(1, 8, 1, 1)[:, :nhk * 8]
             idw = ids if which == "encode_small" else ids.repeat(1, 8, 1)
             if which == "encode_bulk":      # 16 kv heads x 128 rows: enough waves for the bulk kernel
                 kin = torch.zeros(bs * nhk * 8 * n_pages, ps, M, dtype=torch.uint8, device="cuda")
                 vin = torch.zeros(bs * nhk * 8 * n_pages, M, ps, dtype=torch.uint8, device="cuda")
-                idw = torch.arange(bs * nhk * 8 * n_pages, dtype=torch.int32).reshape(bs, nhk * 8, n_pages).cuda()
+                idw_big, idw = guarded_ids(n_ids * 8)
+                idw = idw.view(bs, nhk * 8, n_pages)
             kw_ = dict(n=nn, page_ids=idw, page_size=ps, x_row_start=0, x_row_mod=cap, dev_lengths=dl)
             ops.pq_encode_into(src, ck, kin, layout=L.MILLION_CODES_KPAGES, **kw_)
             ops.pq_encode_into(src, ck, vin, layout=L.MILLION_CODES_VPAGES, **kw_)
@@ -1174,12 +1192,18 @@ def test_flush_device_lengths_are_clamped_not_trusted(env, oracle):
         kp = kpool.cpu().numpy()
         assert not kp[:guard].any() and not kp[-guard:].any() and not vpool.cpu().numpy()[:guard].any()
         kn = kin.cpu().numpy()
+        vn = vin.cpu().numpy()
+        assert not vpool.cpu().numpy()[-guard:].any()
+        for big in (ids_big,) + ((idw_big,) if which == "encode_bulk" else ()):
+            bn = big.cpu().numpy()
+            assert not bn[:gi].any() and not bn[-gi:].any() and np.array_equal(bn[gi:-gi], np.arange(bn.size - 2 * gi)), which
         idn = (ids if which != "encode_bulk" else idw).cpu().numpy()
-        nn = ps if which != "encode_bulk" else cap
         srcn = kw if which != "encode_bulk" else np.tile(kw, (1, 8, 1, 1))
         # items 0, 1: destination outside the table / negative -> nothing stored
-        for b in (0, 1):
-            assert not kn[idn[b].ravel()].any(), (which, b)
+        # items 4 ..: tok0 + lane wraps / tok0 = INT_MIN -> nothing stored either, on either side
+        for b in (0, 1) + tuple(range(4, bs)):
+            assert not kn[idn[b].ravel()].any(), (which, b, bad[b])
+            assert not vn[idn[b].ravel()].any(), (which, b, bad[b])
         # items 2, 3: ring start outside the window -> rows from start 0, stored at token ps
         gold = oracle.pq_encode(srcn[:, :, :nn], ck.cpu().numpy())
         for b in (2, 3):
@@ -1194,6 +1218,9 @@ def test_flush_device_lengths_are_clamped_not_trusted(env, oracle):
             assert (out[:, 3] == 0).all()
             assert (out[:, 0] >= 0).all() and (out[:, 0] <= n_pages * ps).all()
             assert (out[:, 1] >= 0).all() and (out[:, 2] >= 0).all() and (out[:, 2] < cap).all()
+            # the clamps, exactly: T < 0 -> 0, then min(T + n, table); r - n, not below 0
+            want_T = [n_pages * ps, ps, 2 * ps, 2 * ps] + [n_pages * ps] * 5 + [ps]
+            assert out[:, 0].tolist() == want_T and out[:, 1].tolist() == [cap - ps] * 3 + [0] + [cap - ps] * 6, out.tolist()
 
 
 def test_rowmajor_v_shadow_reuse_and_invalidation(env, oracle):
@@ -1466,15 +1493,16 @@ def test_device_lengths_are_clamped_not_trusted(policy, env, oracle):
     capacity, negative values) must become a shorter context / window, never an out-of-bounds read: the kernels clamp
     T to [0, host bound], r to [0, cap] (cap - 1 with a fused append) and an out-of-range start to 0."""
     torch, ops = env
-    bs, nh, nhk, ps, cap, T = 4, 8, 2, 64, 128, 1500
+    bs, nh, nhk, ps, cap, T = 6, 8, 2, 64, 128, 1500
     c = synth.attn_case(9700, bs, nh, nhk, 128, 64, 256, T, cap)
     t = _dev(torch, c)
     kp, vp = ops.prepare_cents(t["k_cents"], cache=False), ops.prepare_cents(t["v_cents"], cache=False)
     vpool, ids = oracle.v_rowmajor_to_pool(c["v_codes"], ps)
     kpool, _ = oracle.k_rowmajor_to_pool(c["k_codes"], ps)
     ids_t = torch.from_numpy(ids.astype(np.int32)).cuda()
-    bad = [[T + 100000, cap + 77, 0, 0], [-5, -3, 0, 0], [700, 40, cap + 9, 0], [T, 20, -1, 0]]
-    eff = [(T, cap, 0), (0, 0, 0), (700, 40, 0), (T, 20, 0)]        # what the clamps make of them
+    bad = [[T + 100000, cap + 77, 0, 0], [-5, -3, 0, 0], [700, 40, cap + 9, 0], [T, 20, -1, 0],
+           [2 ** 31 - 1, 2 ** 31 - 1, 2 ** 31 - 1, 0], [-2 ** 31, -2 ** 31, -2 ** 31, 0]]      # the ends of int
+    eff = [(T, cap, 0), (0, 0, 0), (700, 40, 0), (T, 20, 0), (T, cap, 0), (0, 0, 0)]        # what the clamps make of them
     lengths = torch.tensor(bad, dtype=torch.int32, device="cuda")
     ops.set_force_generic(policy)
     try:
