@@ -694,6 +694,47 @@ int million_attn_tree_merge(const million_block_merge_desc *desc, const void *q 
                             float *lse_out /* may be NULL */, void *k_stage, void *v_stage /* may be NULL */,
                             million_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Sink rows: the first tokens of a sequence kept as exact fp16 rows beside the code store (attention sinks: outlier keys that no
+ * codebook represents, and a large share of every later row's softmax mass).  n query rows per (b, head) have attended to the
+ * cache - a decode, chunk or verify call with its lse: (out_a, lse_a) - and million_attn_sink_merge finishes them in one launch:
+ * their attention over the request's s_b live sink rows, merged with the past part.  Every sink row is visible to every query
+ * row: the caller guarantees that each query position lies behind the sinks.  Per row (b, h, i) with i < n_b:
+ *   s_j = q_i . k_j / sqrt(d) for j < s_b, fp32;  L = max(lse_a, max_j s_j);  w = exp(lse_a - L) (0 for -inf);  p_j = exp(s_j - L);
+ *   out = (w out_a + sum_j p_j v_j) / (w + sum_j p_j) in fp32, rounded once to fp16;  lse_out = L + ln(w + sum_j p_j).
+ * This is million_attn_merge's contract with the second part computed in the kernel, and the edge cases are
+ * million_attn_block_merge's: a NaN lse_a makes the row NaN; lse_a = -inf with s_b = 0 gives out = 0 and lse_out = -inf; rows
+ * i >= n_b get out = 0 and lse_out = -inf, and whatever q / out_a hold there, NaN included, reaches no live row.  s_b = 0 is the
+ * identity: out is out_a bit for bit (w = 1; fp16 -> fp32 -> fp16) and lse_out is lse_a.
+ * k_sink / v_sink are (bs, nh_k, s_cap, d) fp16 with rows of d side by side (row stride d) and element strides sink_stride_b /
+ * sink_stride_h.  s_b = dev_s[b] (device (bs,) int32) clamped into [0, s_cap] on the device; dev_s = NULL: s_b = n_sink for every
+ * request (n_sink is validated either way).  n_b = dev_n[b] clamped into [0, n]; NULL: n_b = n.  Sink rows at or past s_b may
+ * hold anything, NaN included: they reach no product (the key loops run under the wave-uniform bound s_b).
+ * q, out_a and out have element strides (b, h, n) and rows of d contiguous fp16; lse_a and lse_out are (bs, nh, n) contiguous
+ * fp32; lse_out may be NULL.  `out` may be out_a (same pointer and strides) and lse_out may be lse_a: the one wave that writes a
+ * row has read its out_a and lse_a before.  d = 64 or 128, any nh / nh_k, any n >= 1.  One plain launch of single-wave workgroups - n <= 4: bs * nh of them,
+ * lane = sink row for the scores and lane = 2 dims for the value sum; n > 4: bs * nh * ceil(n / 16), lane = (row, quarter of d) -
+ * no atomics, no workspace, legal inside stream capture; the counts' contents may change between replays.  Validation precedes
+ * any HIP call: struct size (MILLION_ERR_ARG); n, d, s_cap, n_sink, nh % nh_k, more than 2^31 - 1 workgroups (MILLION_ERR_SHAPE);
+ * null pointers (MILLION_ERR_ARG); 16-byte fp16 pointers, 4-byte int32 / fp32 pointers, strides in multiples of 8 elements
+ * (MILLION_ERR_ALIGN). */
+typedef struct {
+    uint32_t struct_size;          /* = sizeof(million_sink_merge_desc) */
+    int32_t  bs, nh, nh_k;
+    int32_t  n;                    /* query rows per (b, head), >= 1: 1 for decode, <= 16 for verify, n_q for a chunk */
+    int32_t  d;                    /* 64 or 128 */
+    int32_t  s_cap;                /* rows of the sink buffers, 1 .. 64 */
+    int32_t  n_sink;               /* live sink rows when dev_s is NULL, 0 .. s_cap */
+    int64_t  q_stride[3], a_stride[3], o_stride[3];   /* element strides (b, h, n) of q, out_a, out; multiples of 8 */
+    int64_t  sink_stride_b, sink_stride_h;            /* k_sink / v_sink (bs, nh_k, s_cap, d): row stride d */
+} million_sink_merge_desc;
+
+int million_attn_sink_merge(const million_sink_merge_desc *desc, const void *q /* (bs, nh, n, d) */,
+                            const void *k_sink, const void *v_sink /* (bs, nh_k, s_cap, d) */,
+                            const void *out_a /* (bs, nh, n, d) */, const float *lse_a /* (bs, nh, n) */,
+                            const int32_t *dev_s /* (bs,), may be NULL */, const int32_t *dev_n /* (bs,), may be NULL */,
+                            void *out, float *lse_out /* may be NULL */, million_stream_t stream);
+
 /* Append the first a_b = dev_n[b] rows of k_new / v_new (layers, bs, nh_k, n_bound, d) to request b's residual window in every
  * layer of a paged cache, exactly as a_b decode steps would have: a decode step flushes the oldest page_size window rows into
  * the pages when the window is full and then appends.  a_b is clamped into [0, n_bound]; n_bound <= 16 and n_bound <= page_size,

@@ -87,6 +87,13 @@ class BlockMergeDesc(ctypes.Structure):
                 ("stage_stride_b", c_i64), ("stage_stride_h", c_i64)]
 
 
+class SinkMergeDesc(ctypes.Structure):
+    _fields_ = [("struct_size", c_u32), ("bs", c_i32), ("nh", c_i32), ("nh_k", c_i32), ("n", c_i32), ("d", c_i32),
+                ("s_cap", c_i32), ("n_sink", c_i32),
+                ("q_stride", c_i64 * 3), ("a_stride", c_i64 * 3), ("o_stride", c_i64 * 3),
+                ("sink_stride_b", c_i64), ("sink_stride_h", c_i64)]
+
+
 class WindowCommitDesc(ctypes.Structure):
     _fields_ = [("struct_size", c_u32), ("n_layers", c_i32), ("bs", c_i32), ("nh_k", c_i32), ("d", c_i32), ("M", c_i32), ("C", c_i32),
                 ("n_bound", c_i32), ("page_size", c_i32), ("n_pages_cap", c_i32), ("n_pool", c_i32), ("resid_cap", c_i32),
@@ -149,6 +156,7 @@ SYMBOLS = {
     "million_pq_chunk_attn_lse": (c_i32, [ctypes.POINTER(ChunkAttnDesc)] + [c_vp] * 14 + [c_sz, c_vp]),
     "million_attn_merge": (c_i32, [ctypes.POINTER(AttnMergeDesc), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_vp, c_vp]),
     "million_attn_block_merge": (c_i32, [ctypes.POINTER(BlockMergeDesc)] + [c_vp] * 11),
+    "million_attn_sink_merge": (c_i32, [ctypes.POINTER(SinkMergeDesc)] + [c_vp] * 10),
     "million_window_commit": (c_i32, [ctypes.POINTER(WindowCommitDesc)] + [c_vp] * 12),
     "million_attn_tree_merge": (c_i32, [ctypes.POINTER(BlockMergeDesc)] + [c_vp] * 12),
     "million_window_commit_rows": (c_i32, [ctypes.POINTER(WindowCommitDesc)] + [c_vp] * 13),

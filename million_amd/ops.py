@@ -1049,6 +1049,67 @@ def attn_block_merge(q: torch.Tensor, k_blk: torch.Tensor, v_blk: torch.Tensor, 
     return (out, lse_out) if (return_lse or lse_out is not None) else out
 
 
+SINK_MAX_ROWS = 64
+
+
+def attn_sink_merge(q: torch.Tensor, k_sink: torch.Tensor, v_sink: torch.Tensor, out_a: torch.Tensor, lse_a: torch.Tensor, *,
+                    n_sink: Optional[int] = None, dev_s: Optional[torch.Tensor] = None, dev_n: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None, lse_out: Optional[torch.Tensor] = None, return_lse: bool = False):
+    """Attend n query rows per (b, head) to the exact fp16 sink rows of their request and merge that with their attention over
+    the past, in one launch (million_attn_sink_merge): (out_a, lse_a), fp16 (bs, nh, n, d) and contiguous fp32 (bs, nh, n), is a
+    decode / chunk / verify result with its lse; k_sink / v_sink are fp16 (bs, nh_k, s_cap <= 64, d) with dense rows.  Every
+    live sink row is visible to every query row.  The live rows of request b: dev_s[b] (device int32 (bs,), clamped into
+    [0, s_cap] on the device), or n_sink for all (a host int; default s_cap); not both.  dev_n, device int32 (bs,): the live
+    query rows, clamped into [0, n]; the rows past them get out = 0 and lse = -inf.  Zero sink rows are the identity on
+    (out_a, lse_a), bit for bit.  q, out_a and out may be any views with contiguous rows of d and the other strides multiples
+    of 8 elements; `out` may be out_a itself.  Returns out, or (out, lse_out) with return_lse (or an lse_out buffer)."""
+    _need_cuda(q, k_sink, v_sink, out_a, lse_a, dev_s, dev_n, out, lse_out)
+    if q.dim() != 4 or any(t.dtype != torch.float16 for t in (q, k_sink, v_sink, out_a)):
+        raise RuntimeError("attn_sink_merge: q, k_sink, v_sink and out_a must be fp16 (bs, nh | nh_k, n | s_cap, d)")
+    bs, nh, n, d = q.shape
+    if (k_sink.dim() != 4 or k_sink.shape[0] != bs or k_sink.shape[3] != d or v_sink.shape != k_sink.shape or nh % k_sink.shape[1]
+            or not 1 <= k_sink.shape[2] <= SINK_MAX_ROWS):
+        raise RuntimeError(f"attn_sink_merge: k_sink / v_sink must be (bs, nh_k, s_cap, d) = ({bs}, nh_k, 1 .. {SINK_MAX_ROWS}, {d}), "
+                           "nh a multiple of nh_k")
+    nh_k, s_cap = k_sink.shape[1], k_sink.shape[2]
+    for t in (k_sink, v_sink):
+        if t.stride(3) != 1 or t.stride(2) != d or t.stride() != k_sink.stride():
+            raise RuntimeError("attn_sink_merge: k_sink / v_sink must have dense rows (row stride d), alike")
+    if dev_s is not None and n_sink is not None:
+        raise RuntimeError("attn_sink_merge: n_sink (host) or dev_s (device), not both")
+    if dev_s is not None:
+        _check_dev_n("attn_sink_merge", dev_s, bs)
+    n_sink = (0 if dev_s is not None else s_cap) if n_sink is None else int(n_sink)
+    if not 0 <= n_sink <= s_cap:
+        raise RuntimeError(f"attn_sink_merge: n_sink={n_sink} outside [0, {s_cap}]")
+    fix = lambda t: t if (t.stride(3) == 1 and all(s_ % 8 == 0 for s_ in t.stride()[:3])) else t.contiguous()
+    q = fix(q)
+    if tuple(out_a.shape) != (bs, nh, n, d) or out_a.stride(3) != 1:
+        raise RuntimeError("attn_sink_merge: out_a must be (bs, nh, n, d) with contiguous rows")
+    if lse_a.dtype != torch.float32 or tuple(lse_a.shape) != (bs, nh, n) or not lse_a.is_contiguous():
+        raise RuntimeError("attn_sink_merge: lse_a must be contiguous fp32 (bs, nh, n)")
+    if dev_n is not None:
+        _check_dev_n("attn_sink_merge", dev_n, bs)
+    if out is None:
+        out = torch.empty(bs, nh, n, d, dtype=torch.float16, device=q.device)
+    elif out.dtype != torch.float16 or tuple(out.shape) != (bs, nh, n, d) or out.stride(3) != 1:
+        raise RuntimeError("attn_sink_merge: out must be fp16 (bs, nh, n, d) with contiguous rows")
+    if lse_out is None and return_lse:
+        lse_out = torch.empty(bs, nh, n, dtype=torch.float32, device=q.device)
+    if lse_out is not None and (lse_out.dtype != torch.float32 or tuple(lse_out.shape) != (bs, nh, n) or not lse_out.is_contiguous()):
+        raise RuntimeError("attn_sink_merge: lse_out must be contiguous fp32 (bs, nh, n)")
+    desc = L.SinkMergeDesc()
+    desc.struct_size = ctypes.sizeof(L.SinkMergeDesc)
+    desc.bs, desc.nh, desc.nh_k, desc.n, desc.d, desc.s_cap, desc.n_sink = bs, nh, nh_k, n, d, s_cap, n_sink
+    for k in range(3):
+        desc.q_stride[k], desc.a_stride[k], desc.o_stride[k] = q.stride(k), out_a.stride(k), out.stride(k)
+    desc.sink_stride_b, desc.sink_stride_h = k_sink.stride(0), k_sink.stride(1)
+    L.check(L.load().million_attn_sink_merge(ctypes.byref(desc), q.data_ptr(), k_sink.data_ptr(), v_sink.data_ptr(), out_a.data_ptr(),
+                                             lse_a.data_ptr(), _ptr(dev_s), _ptr(dev_n), out.data_ptr(), _ptr(lse_out), _stream()),
+            "million_attn_sink_merge")
+    return (out, lse_out) if (return_lse or lse_out is not None) else out
+
+
 def window_commit(k_new: torch.Tensor, v_new: torch.Tensor, k_res: torch.Tensor, v_res: torch.Tensor, k_prep: torch.Tensor,
                   v_prep: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, page_ids: torch.Tensor,
                   dev_lengths: torch.Tensor, dev_n: torch.Tensor, *, M: int, C: int, n_bound: Optional[int] = None,

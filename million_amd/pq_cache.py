@@ -230,7 +230,9 @@ class DynamicPQCache(_CacheBase):
     (reference pq_utils.py:98-328).  `max_tokens` bounds the preallocated store."""
 
     def __init__(self, *, bs, nh, num_key_value_heads, M, layer_num, dtype=None, nbits=8, d=128,
-                 scalar_t=torch.float16, max_tokens=32768 + 1024, device="cuda"):
+                 scalar_t=torch.float16, max_tokens=32768 + 1024, device="cuda", sink_tokens=0):
+        if sink_tokens:
+            raise NotImplementedError("DynamicPQCache: sink_tokens is a property of PagedPQCache (DESIGN.md 4.13)")
         # nbits <= 8: uint8 codes, every path.  nbits 9..16: uint16 codes (nbits2dtype, pq_utils.py:542-552) on the
         # dequantise-then-attend paths (update, prefill); the fused decode kernels are uint8-only, as the reference's
         # are (KernelRegistry raises NotImplementedError, pq_utils.py:50-52).
@@ -422,13 +424,20 @@ class PagedPQCache(_CacheBase):
     (bs, 4)) - so that a batch slot can finish and be recycled while the others keep decoding: `release(b)` returns the
     slot's pages and zeroes its lengths, `prefill_request(b, ...)` encodes a new prompt into it (`prefill_ragged`: several
     slots' prompts of different lengths, one attention launch).  Requests of different
-    lengths share every launch through the device-resident lengths (`use_dev_lengths=True`)."""
+    lengths share every launch through the device-resident lengths (`use_dev_lengths=True`).
+
+    `sink_tokens=S` (0 .. 64; 0: nothing is allocated and every call launches what it always did): the first min(S, n) rows of
+    a request's first store step (prefill*, extend*) stay exact fp16 rows beside the pages - the attention sinks - and only the
+    rows behind them are encoded; decoding_with_pages, the extend forms and verify merge them into their result with one more
+    launch (ops.attn_sink_merge), the live count read on the device.  `seen` counts them, T does not.  DESIGN.md 4.13."""
 
     def __init__(self, *, bs, nh, num_key_value_heads, M, layer_num, dtype=torch.uint8, nbits=8, d=128,
                  scalar_t=torch.float16, page_size=64, extended_residual_size=128, max_pages_per_layer=None,
-                 max_tokens=32768 + 1024, preallocate=True, device="cuda"):
+                 max_tokens=32768 + 1024, preallocate=True, device="cuda", sink_tokens=0):
         if nbits != 8 or dtype != torch.uint8:
             raise NotImplementedError("Only uint8 code type is supported for now")
+        if isinstance(sink_tokens, bool) or int(sink_tokens) != sink_tokens or not 0 <= sink_tokens <= ops.SINK_MAX_ROWS:
+            raise ValueError(f"sink_tokens must be an integer in 0 .. {ops.SINK_MAX_ROWS}")
         if page_size not in (32, 64, 128):
             raise ValueError("page_size must be 32, 64 or 128")
         if extended_residual_size < page_size:
@@ -443,6 +452,7 @@ class PagedPQCache(_CacheBase):
             self.n_pages_cap = min(self.n_pages_cap, max_pages_per_layer // max(bs * num_key_value_heads, 1))
         self.max_tokens = self.n_pages_cap * page_size
         self.preallocate = preallocate
+        self.sink_tokens = int(sink_tokens)
         self.registery = KernelRegistry(M=M, d=d, nbits=nbits, nh=nh, scalar_t=scalar_t, device=device)
         self.init_cache()
 
@@ -466,6 +476,14 @@ class PagedPQCache(_CacheBase):
         # host mirrors, (layers, requests)
         zi = lambda: np.zeros((self.layer_num, self.bs), dtype=np.int64)
         self._seen_a, self._r_a, self._T_a, self._rs_a, self._pages_a = zi(), zi(), zi(), zi(), zi()
+        # sink rows (sink_tokens = S > 0): the first min(S, prompt) tokens of every request as exact fp16 rows beside the pages, the
+        # live count per (layer, request) on the device (every attention call reads it there) and in a host mirror (_note_sinks)
+        S = self.sink_tokens
+        self._ksink_all = z(self.layer_num, self.bs, nk, S, self.d, dt=self.scalar_t) if S else None
+        self._vsink_all = z(self.layer_num, self.bs, nk, S, self.d, dt=self.scalar_t) if S else None
+        self._sink_all = z(self.layer_num, self.bs, dt=torch.int32) if S else None
+        self._sink_a, self._sink_lse = zi(), None
+        self._sink_views = [(self._ksink_all[l], self._vsink_all[l], self._sink_all[l]) for l in range(self.layer_num)] if S else None
         self._pre_a = zi()      # 1: the oldest page_size window rows are already encoded at tokens [T, T + page_size) (begin_step)
         self._pre_join = False
         self._dev_rows_stale = False      # a host-length step moved the mirror and not the device rows (_refresh_device_rows)
@@ -540,6 +558,28 @@ class PagedPQCache(_CacheBase):
         self._r_a[layer_idx, b] = 0
         self._rs_a[layer_idx, b] = 0
 
+    def _note_sinks(self, layer_idx, b, s):
+        """Request(s) b of a layer (slice(None): of every layer) keep s sink rows from now on - s an int, or an array that
+        broadcasts over the entries: the host count and the device count the attention calls read move here, together, and
+        nowhere else.  Sink rows are tokens the request has seen and the pages do not hold."""
+        if not self.sink_tokens:
+            return
+        self._seen_a[layer_idx, b] += s - self._sink_a[layer_idx, b]
+        self._sink_a[layer_idx, b] = s
+        self._sink_all[layer_idx, b] = s if np.isscalar(s) else torch.from_numpy(np.asarray(s, np.int32)).to(self.device)
+
+    def _sink_merge(self, layer_idx, q, out, lse, sel=slice(None), dev_n=None):
+        """The sink part of an attention call, in place on its (out, lse): ops.attn_sink_merge over the sink rows of the layer
+        (of the requests `sel`), the live counts read on the device."""
+        ks, vs, cnt = self._sink_views[layer_idx]
+        if sel != slice(None):
+            ks, vs, cnt = ks[sel], vs[sel], cnt[sel]
+        ops.attn_sink_merge(q, ks, vs, out, lse, dev_s=cnt, dev_n=dev_n, out=out, lse_out=lse)
+
+    def _no_sinks(self, what):
+        if self.sink_tokens:
+            raise NotImplementedError(f"PagedPQCache: {what} of a cache with sink_tokens > 0 is not built yet (DESIGN.md 4.13)")
+
     def _sync_lengths(self, layer_idx, b=None):
         """The device rows of a layer - of request b alone: the others' are not touched - written from the mirror."""
         sel = slice(None) if b is None else slice(b, b + 1)
@@ -591,8 +631,16 @@ class PagedPQCache(_CacheBase):
             self._encode_to_pages(self.key_residual_cache[layer_idx][sel], self.value_residual_cache[layer_idx][sel], layer_idx, r,
                                   b=b, x_row_start=int(self._rs_a[layer_idx, i]), x_row_mod=self.extended_residual_size)
             self._note_window_emptied(layer_idx, sel)
-        self._encode_to_pages(K, V, layer_idx, n, b=b)
-        self._note_stored(layer_idx, n, sel)
+        s = 0
+        if self.sink_tokens and not self._seen_a[layer_idx, sel].any():      # the request's first rows: its sinks stay fp16
+            s = min(self.sink_tokens, n)
+            self._ksink_all[layer_idx][sel, :, :s].copy_(K[:, :, :s])
+            self._vsink_all[layer_idx][sel, :, :s].copy_(V[:, :, :s])
+            self._note_sinks(layer_idx, sel, s)
+            K, V = K[:, :, s:], V[:, :, s:]
+        if n - s:
+            self._encode_to_pages(K, V, layer_idx, n - s, b=b)
+        self._note_stored(layer_idx, n - s, sel)
         self._sync_lengths(layer_idx, None if all_rows else b)
 
     def _reserve_ragged(self, layer_idx, n_new):
@@ -628,7 +676,7 @@ class PagedPQCache(_CacheBase):
     def prefill_request(self, b, query_states, key_states, value_states, layer_idx):
         """The prompt of ONE request (tensors of batch 1) into batch slot b, the other slots untouched - a recycled slot
         (release) starts its next request while the rest of the batch keeps decoding."""
-        if key_states.size(0) != 1 or self._T_a[layer_idx, b] or self._r_a[layer_idx, b]:
+        if key_states.size(0) != 1 or self._T_a[layer_idx, b] or self._r_a[layer_idx, b] or self._sink_a[layer_idx, b]:
             raise RuntimeError("prefill_request: tensors of batch 1 into an empty slot (release it first)")
         self._store(key_states, value_states, layer_idx, key_states.size(2), b, all_rows=True)      # (every device row: as ever)
         return self._prefill_attention(query_states, key_states, value_states)
@@ -651,8 +699,10 @@ class PagedPQCache(_CacheBase):
         if any(x < 0 or x > n for x in n_new):
             raise RuntimeError(f"prefill_ragged: n_new outside [0, {n}]")
         who = [b for b in range(self.bs) if n_new[b] > 0]
+        if device_store:
+            self._no_sinks("prefill_ragged(device_store=True)")
         for b in who:      # every slot's precondition and capacity before anything is launched
-            if self._T_a[layer_idx, b] or self._r_a[layer_idx, b]:
+            if self._T_a[layer_idx, b] or self._r_a[layer_idx, b] or self._sink_a[layer_idx, b]:
                 raise RuntimeError(f"prefill_ragged: slot {b} holds tokens (release it first, or use extend_ragged)")
             if n_new[b] > self.max_tokens:
                 raise RuntimeError(f"PagedPQCache: {n_new[b]} tokens exceed max_tokens={self.max_tokens}")
@@ -697,10 +747,14 @@ class PagedPQCache(_CacheBase):
         if T + r + n > self.max_tokens:
             raise RuntimeError(f"PagedPQCache: {T + r + n} tokens exceed max_tokens={self.max_tokens}")
         ids = self.page_ids[layer_idx][sel]
+        sinks = bool(self.sink_tokens)
         out = ops.pq_chunk_attn(query_states, key_states, value_states, self.key_page_pool, self.value_page_pool, self._kprep,
                                 self._vprep, self.key_residual_cache[layer_idx][sel], self.value_residual_cache[layer_idx][sel], r,
                                 M=self.M, C=self.C, n_tokens=T, resid_start=rs, k_page_ids=ids, v_page_ids=ids,
-                                page_size=self.page_size, **({"return_lse": True} if return_lse else {}))
+                                page_size=self.page_size, **({"return_lse": True} if return_lse or sinks else {}))
+        if sinks:      # before the store: a request's first chunk has its sinks among the chunk rows, and none kept yet
+            self._sink_merge(layer_idx, query_states, out[0], out[1], sel)
+            out = out if return_lse else out[0]
         self._store(key_states, value_states, layer_idx, n, b, all_rows=all_rows)      # the window in ring order, then the new rows
         return out
 
@@ -715,7 +769,7 @@ class PagedPQCache(_CacheBase):
         if not self._lockstep(layer_idx):
             raise RuntimeError("PagedPQCache.extend: requests are at different lengths; use extend_request(b, ...)")
         self._join_side(layer_idx)
-        if self._T_a[layer_idx, 0] == 0 and self._r_a[layer_idx, 0] == 0:
+        if self._T_a[layer_idx, 0] == 0 and self._r_a[layer_idx, 0] == 0 and not self._sink_a[layer_idx].any():
             return self.prefill(query_states, key_states, value_states, layer_idx)
         return self._extend_slot(query_states, key_states, value_states, layer_idx, None)
 
@@ -728,7 +782,7 @@ class PagedPQCache(_CacheBase):
         if key_states.size(0) != 1 or query_states.size(0) != 1:
             raise RuntimeError("extend_request: tensors of batch 1")
         self._join_side(layer_idx, b)
-        if self._T_a[layer_idx, b] == 0 and self._r_a[layer_idx, b] == 0:
+        if self._T_a[layer_idx, b] == 0 and self._r_a[layer_idx, b] == 0 and not self._sink_a[layer_idx, b]:
             if return_lse:
                 return self._extend_slot(query_states, key_states, value_states, layer_idx, b, return_lse=True, all_rows=True)
             return self.prefill_request(b, query_states, key_states, value_states, layer_idx)
@@ -751,6 +805,8 @@ class PagedPQCache(_CacheBase):
             raise RuntimeError(f"extend_ragged: tensors of batch {self.bs} and one n_new per slot")
         if any(n < 0 or n > n_q for n in n_new):
             raise RuntimeError(f"extend_ragged: n_new outside [0, {n_q}]")
+        if device_store:
+            self._no_sinks("extend_ragged(device_store=True)")
         who = [b for b in range(self.bs) if n_new[b] > 0]
         for b in who:      # capacity of every slot before anything is launched
             tot = int(self._T_a[layer_idx, b] + self._r_a[layer_idx, b]) + n_new[b]
@@ -766,7 +822,11 @@ class PagedPQCache(_CacheBase):
         bound = int(self._T_a[layer_idx].max())
         out = ops.pq_chunk_attn(query_states, key_states, value_states, self.key_page_pool, self.value_page_pool, self._kprep,
                                 self._vprep, kres, vres, 0, M=self.M, C=self.C, n_tokens=bound, k_page_ids=ids, v_page_ids=ids,
-                                page_size=self.page_size, dev_lengths=self.lengths[layer_idx], dev_n_q=dev_n)
+                                page_size=self.page_size, dev_lengths=self.lengths[layer_idx], dev_n_q=dev_n,
+                                **({"return_lse": True} if self.sink_tokens else {}))
+        if self.sink_tokens:      # before the stores, as _extend_slot
+            out, lse = out
+            self._sink_merge(layer_idx, query_states, out, lse, dev_n=dev_n)
         if device_store:
             self._store_ragged(key_states, value_states, layer_idx, n_new, dev_n)
             return out
@@ -784,6 +844,13 @@ class PagedPQCache(_CacheBase):
             self._T_a[:, dsts] = self._seen_a[:, dsts] = n_tokens
             self._r_a[:, dsts] = self._rs_a[:, dsts] = 0
         self._pre_a[:, dsts] = 0
+        if self.sink_tokens:      # the source's sink rows, all of them whatever n_tokens says: they precede every coded token
+            self._sink_a[:, dsts] = 0
+            if n_tokens is None:
+                self._seen_a[:, dsts] -= self._sink_a[:, [src]]      # (_note_sinks counts them as seen)
+            self._ksink_all[:, dsts] = self._ksink_all[:, src:src + 1]
+            self._vsink_all[:, dsts] = self._vsink_all[:, src:src + 1]
+            self._note_sinks(slice(None), dsts, self._sink_a[:, [src]])
 
     def _note_restored(self, b, meta):
         """Slot b holds, in every layer, the request a snapshot describes (swap_in): T coded tokens, r window rows from ring
@@ -869,6 +936,7 @@ class PagedPQCache(_CacheBase):
                         self.page_manager.free_page(pid)
                     self._host_pids[l][b][h] = []
                 self._pages_a[l, b] = 0
+            self._note_sinks(l, b, 0)
             self._T_a[l, b] = self._r_a[l, b] = self._rs_a[l, b] = self._seen_a[l, b] = self._pre_a[l, b] = 0
             self.lengths[l][b].zero_()
 
@@ -902,6 +970,7 @@ class PagedPQCache(_CacheBase):
         other owners.  swap_in() of the snapshot - into any empty slot of any cache of the same geometry and codebooks, on any
         GPU, in any process (formats.save_request) - decodes on with the bits this slot would have produced.  Call it between
         steps, as fork: the slot must be at the same lengths in every layer (its pending encode-ahead work is joined)."""
+        self._no_sinks("swap_out / snapshot_request")
         one = np.isscalar(b)
         slots = [int(b)] if one else [int(x) for x in b]
         nk, nl = self.num_key_value_heads, self.layer_num
@@ -954,6 +1023,7 @@ class PagedPQCache(_CacheBase):
         device lengths rows.  Refused, before anything changes (RuntimeError): a slot that holds tokens, a snapshot of another
         format version or geometry, more tokens than max_tokens, fewer free pages than the request needs (on demand), a blob of
         the wrong size, and - unless check_codebooks=False - codebooks other than the ones the codes were made with."""
+        self._no_sinks("swap_in")
         b = int(b)
         meta, blob = snap.meta, snap.blob
         nk, nl, ps = self.num_key_value_heads, self.layer_num, self.page_size
@@ -1012,6 +1082,9 @@ class PagedPQCache(_CacheBase):
         for l in range(self.layer_num):
             self.key_residual_cache[l].zero_()
             self.value_residual_cache[l].zero_()
+        if self.sink_tokens:
+            self._ksink_all.zero_()
+            self._vsink_all.zero_()
 
     def _codes_rowmajor(self, layer_idx, T):
         """(bs, nh_k, T, M) row-major K and V codes gathered from the pages (dequantise-then-attend path only)."""
@@ -1026,6 +1099,7 @@ class PagedPQCache(_CacheBase):
         store the new K/V rows into pages, return the full-length fp16 K/V for a dense attention - the dequantised past
         followed by the new rows as they are (or dequantised too with distort_recent).  No residual window on this path.
         extend() attends a block of new tokens to the codes and the window without the fp16 past."""
+        self._no_sinks("update (the dequantise-then-attend path)")
         if not self._lockstep(layer_idx) or self._r_a[layer_idx, 0]:
             raise RuntimeError("PagedPQCache.update: lockstep requests and an empty residual window expected")
         n = key_states.size(2)
@@ -1223,6 +1297,11 @@ class PagedPQCache(_CacheBase):
             self._ws = torch.zeros(need, dtype=torch.uint8, device=self.device)
         self._note_appended(layer_idx)
         self._dev_rows_stale |= not use_dev_lengths
+        want_lse = return_lse or lse is not None
+        if self.sink_tokens and not want_lse:      # the sink merge needs the past part's lse: one buffer per cache
+            if self._sink_lse is None:
+                self._sink_lse = torch.empty(self.bs, self.nh, 1, dtype=torch.float32, device=self.device)
+            lse = self._sink_lse
         # append (:377-380) + attention (:386) in ONE launch: the new row is attended to and parked in the window
         res = ops.pq_decode_attn(query_states, self.key_page_pool, self.value_page_pool, self._kprep, self._vprep,
                                  self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx], r,
@@ -1232,6 +1311,9 @@ class PagedPQCache(_CacheBase):
                                  v_page_ids=self.page_ids[layer_idx], page_size=self.page_size, out=out,
                                  dev_lengths=dl, workspace=self._ws,
                                  **({"return_lse": True, "lse": lse} if return_lse or lse is not None else {}))
+        if self.sink_tokens:      # the count is read on the device: a captured step follows release and a new prompt
+            self._sink_merge(layer_idx, query_states, res[0].view(query_states.shape), res[1])
+            res = res if want_lse else res[0]
         if self._pre_join and layer_idx == self.layer_num - 1:
             torch.cuda.current_stream().wait_stream(self._side)      # the step's encode-ahead launch ends with the step
             self._pre_join = False
@@ -1321,6 +1403,8 @@ class PagedPQCache(_CacheBase):
         dl = self.lengths[layer_idx] if use_dev_lengths else None
         ids = self.page_ids[layer_idx]
         kres, vres = self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx]
+        sinks = bool(self.sink_tokens)
+        want_lse = return_lse or sinks
         if route == "heads":
             qv = query_states.contiguous()
             qh = qv.view(bs, nh * n, 1, d)
@@ -1333,7 +1417,7 @@ class PagedPQCache(_CacheBase):
                                               k_page_ids=ids, v_page_ids=ids, page_size=self.page_size, dev_lengths=dl,
                                               workspace=ws[n], return_lse=True)
             out_a, lse_a = out_a.view(bs, nh, n, d), lse_a.view(bs, nh, n)
-            res = ops.attn_block_merge(qv, key_states, value_states, out_a, lse_a, dev_n, out=out_a, return_lse=return_lse,
+            res = ops.attn_block_merge(qv, key_states, value_states, out_a, lse_a, dev_n, out=out_a, return_lse=want_lse,
                                        k_stage=ks, v_stage=vs, **masked)
         elif trees is not None:      # chunk attention over the past only (the chunk kernel knows chains), then the masked block
             bound = int(self._T_a[layer_idx].max()) if use_dev_lengths else T
@@ -1341,16 +1425,19 @@ class PagedPQCache(_CacheBase):
                                              self._vprep, kres, vres, r, M=self.M, C=self.C, n_tokens=bound, resid_start=rs,
                                              k_page_ids=ids, v_page_ids=ids, page_size=self.page_size, dev_lengths=dl, dev_n_q=dev_n,
                                              return_lse=True)
-            res = ops.attn_block_merge(query_states, key_states, value_states, out_a, lse_a, dev_n, out=out_a, return_lse=return_lse,
+            res = ops.attn_block_merge(query_states, key_states, value_states, out_a, lse_a, dev_n, out=out_a, return_lse=want_lse,
                                        k_stage=ks, v_stage=vs, **masked)
         else:
             bound = int(self._T_a[layer_idx].max()) if use_dev_lengths else T
             res = ops.pq_chunk_attn(query_states, key_states, value_states, self.key_page_pool, self.value_page_pool, self._kprep,
                                     self._vprep, kres, vres, r, M=self.M, C=self.C, n_tokens=bound, resid_start=rs, k_page_ids=ids,
                                     v_page_ids=ids, page_size=self.page_size, dev_lengths=dl, dev_n_q=dev_n,
-                                    **({"return_lse": True} if return_lse else {}))
+                                    **({"return_lse": True} if want_lse else {}))
             ks[:, :, :n].copy_(key_states)
             vs[:, :, :n].copy_(value_states)
+        if sinks:      # behind the block / tree merge, on its (out, lse): every draft row lies behind the sinks
+            self._sink_merge(layer_idx, query_states, res[0], res[1], dev_n=dev_n)
+            res = res if return_lse else res[0]
         rec["layers"].add(layer_idx)
         return res
 
@@ -1496,7 +1583,9 @@ class PagedPQCache(_CacheBase):
         mb = 1024 * 1024
         cache_mb = float(2 * self.num_key_value_heads * self.M * self._T_a.sum()) / mb
         resid_mb = sum(c.numel() * c.element_size() for c in self.key_residual_cache + self.value_residual_cache) / mb
-        return {"layer_stats": layer_stats, "total_memory_usage_mb": cache_mb + resid_mb,
-                "memory_breakdown": {"cache_memory_mb": cache_mb, "residual_memory_mb": resid_mb,
-                                     "prefill_residual_memory_mb": 0.0, "total_memory_mb": cache_mb + resid_mb},
+        sink_mb = 2 * self.layer_num * self.bs * self.num_key_value_heads * self.sink_tokens * self.d * 2 / mb      # K and V buffers, fp16
+        return {"layer_stats": layer_stats, "total_memory_usage_mb": cache_mb + resid_mb + sink_mb,
+                "memory_breakdown": {"cache_memory_mb": cache_mb, "residual_memory_mb": resid_mb, "sink_memory_mb": sink_mb,
+                                     "prefill_residual_memory_mb": 0.0, "total_memory_mb": cache_mb + resid_mb + sink_mb},
+                "sink_tokens": self.sink_tokens, "sink_rows_live": int(self._sink_a.sum()),
                 "page_manager": self.page_manager.get_stats()}

@@ -28,6 +28,8 @@ class SharedPrefix:
         life: decode, flush, extend_request, release.  Both caches must agree in heads, d, M, C, device and codebooks; the
         prefix slot must be between steps (the same rule as fork: every layer at the same lengths, no encode-ahead pending)."""
         p, c = prefix_cache, cont_cache
+        if getattr(p, "sink_tokens", 0) or getattr(c, "sink_tokens", 0):
+            raise NotImplementedError("SharedPrefix: caches with sink_tokens > 0 are not served yet (DESIGN.md 4.13)")
         slot = int(slot)
         if not 0 <= slot < p.bs:
             raise RuntimeError(f"SharedPrefix: slot {slot} outside [0, {p.bs})")
