@@ -9,7 +9,8 @@
 // early passes as memory and moved the scalar allocation of 28 of 32 instances).  A kernel expands them in the order in which
 // the loads must be issued - the CU's load path takes ~28 cycles per 1-KiB wave request, in order: what is requested first is
 // there first:
-//     LAUNCH_FRONT_PLACE | (LDS base check, stamps) | LAUNCH_FRONT_PAGE_IDS | (the kernel's own query operand) |
+//     LAUNCH_FRONT_PLACE | (LDS base check, stamps) | LAUNCH_FRONT_PAGE_IDS | (the kernel's own query operand; lean kernel: ONE
+//     request of wave 0 for the workgroup's query rows, which go to LDS with the codebook images) |
 //     LAUNCH_FRONT_NEW_ROW_AND_TABLES | LAUNCH_FRONT_LENGTHS | ... LDS images, barrier ... | LAUNCH_FRONT_APPEND_STORE
 // They expect the kernel's p (AttnParams), tid, lane, wave and kNW / kResRows, and leave:
 //   split, bh, b, hk        hk, bh: VIRTUAL when the launch splits the query heads of a kv head into parts
@@ -34,8 +35,11 @@
 // Units are dealt to (split, wave) by PAGE, strided: page (j * ppr + wave / upp) * nsplit + split goes to round j of the wave
 // (upp = units per page, ppr = 8 / upp pages per workgroup and round), so where a wave reads does not depend on the context
 // length T - only HOW MANY units it has does.  A page is never shared between workgroups, so rows past T - 1 of the last unit
-// stay inside an allocated page: no row clamping on paged K.  Rounds past a wave's last unit re-request that unit
-// (LAUNCH_FRONT_ROUND: L2 hits, never consumed), so that no code load sits in a conditional.
+// stay inside an allocated page: no row clamping on paged K.  A request for a round past a wave's last unit re-requests that unit
+// (LAUNCH_FRONT_ROUND: L2 hits, never consumed), so that no code load sits in a conditional.  Such a request still takes its
+// ~28 cycles per wave request of the CU's in-order load path, so a loop should not issue it where it can know better: the lean
+// kernel's last block requests nothing (attn_lean.h: BLOCK_LAST; its only clamped requests are the prologue's round 1 in waves
+// with fewer than two units); the streaming kernel's blocks still re-request.
 
 // C = 128: the V col image is written to LDS a second time kVDup128 bytes above the first (code c at kVBase + 256 c in every
 // form), where the code bytes 128 .. 255 of masked tokens land (the gathers take the byte unmasked): they gather row c - 128, a

@@ -158,6 +158,14 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
     // any order of the groups will do
     const f16 *qrow = p.q + ((long long)b * p.nh + head0(p, hk)) * DR;
     v2u Q[NK / 4];
+#if !(MILLION_EXP & 4096)
+    // The workgroup's G query rows (G x DR fp16, <= 1 KiB, contiguous) are requested ONCE, by wave 0 (lane = 16-byte piece), here -
+    // in front of the codebooks in the CU's in-order load path - written to LDS at kQOff beside the codebook images and published
+    // by the codebook barrier; every wave reads its Q[] pairs (and, with window rows, qb) from there behind it.  (Per wave: four
+    // 16-byte-per-lane requests of the same 1 KiB, each piece replicated over four lanes - 32 wave requests per CU for 1.)
+    v4u qimg = {0, 0, 0, 0};
+    if (wave == 0 && 8 * lane < G * DR) qimg = *(const v4u *)(qrow + 8 * lane);
+#else      // (A/B: every wave loads its own operand, profiles/ab_decode_loadpath.txt)
 #pragma unroll
     for (int v = 0; v < DD / 32; ++v) {
         v4u t;
@@ -171,6 +179,7 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
         Q[2 * v] = v2u{t[0], t[1]};
         Q[2 * v + 1] = v2u{t[2], t[3]};
     }
+#endif
     // (128 centroids: the same codebook loads - the second half of them reads the image that follows in the prepared buffer and is
     // dropped by the copy into LDS below, which spreads the K rows to the 256-entry row stride the gathers use)
     LAUNCH_FRONT_NEW_ROW_AND_TABLES(DR, NT)
@@ -180,6 +189,7 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
                             // d_m = 4: head c16 & 3 - the four column groups carry copies of the heads, as in the streaming kernel's form)
     if (has_res) {
         lean_load_res_tile<DD, DM2, DR>(p, bhr, kr, vr, wave, rcnt, split, rstart, r_old, lane, rt);
+#if MILLION_EXP & 4096
         const int hq = DM2 ? n16 : hj;
         const f16 *qv = qrow + (hq < G ? hq : 0) * DR + (DR / 4) * kg;
 #pragma unroll
@@ -188,6 +198,7 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
             if (hq >= G) t = v4u{0, 0, 0, 0};
             qb[s] = __builtin_bit_cast(v8f16, t);
         }
+#endif
     }
 
     // ---- one unit's 16-byte requests into ring slot SL ----
@@ -227,6 +238,9 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
     // no difference, profiles/r05_ab_unit0_coalesced.txt.)
     UNIT_REQ(0, 0)
     STAMP(7);
+#if !(MILLION_EXP & 4096)
+    if (wave == 0) *(v4u *)(smem + kQOff + 16 * lane) = qimg;      // the query image: the oldest of the wave's table-sized loads
+#endif
     {
         v4u *ld = (v4u *)smem;
         v4u *ldv = (v4u *)(smem + kVBase);
@@ -282,6 +296,24 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
     STAMP(8);
     __syncthreads();
     STAMP(1);
+#if !(MILLION_EXP & 4096)
+    {      // the query operand, from the image: the layout of the per-wave loads it replaces (heads >= G: zeros; padded form: (q, 0))
+        const unsigned qo = (unsigned)kQOff + (unsigned)((hj < G ? hj : 0) * DR) * 2u;
+#pragma unroll
+        for (int v = 0; v < DD / 32; ++v) {
+            v4u t;
+            if constexpr (PAD) {
+                const v2u t2 = lds64(qo + (16u * v + 4u * kg) * 2u);
+                t = v4u{t2[0] & 0xffffu, t2[0] >> 16, t2[1] & 0xffffu, t2[1] >> 16};
+            } else {
+                t = lds128(qo + (32u * v + 8u * kg) * 2u);
+            }
+            if (hj >= G) t = v4u{0, 0, 0, 0};
+            Q[2 * v] = v2u{t[0], t[1]};
+            Q[2 * v + 1] = v2u{t[2], t[3]};
+        }
+    }
+#endif
 
     // O.t[j][g]: head g; d_m = 2: lane (rg, n): dim 64 j + 32 (rg >> 1) + 2 n + (rg & 1); d_m = 4: lane (dq, n): dim 4 (n + 16 j) + dq
     Acc8 O;
@@ -304,6 +336,18 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
     float s_m = -INFINITY, s_l = 0.f;
     if (has_res) {      // residual tile of this wave first: it needs neither codebook
         float scr[4], m_run = -INFINITY, l_run = 0.f;
+#if !(MILLION_EXP & 4096)
+        {
+            const int hq = DM2 ? n16 : hj;
+            const unsigned qbo = (unsigned)kQOff + (unsigned)((hq < G ? hq : 0) * DR + (DR / 4) * kg) * 2u;
+#pragma unroll
+            for (int s = 0; s < DR / 32; ++s) {
+                v4u t = lds128(qbo + 16u * s);
+                if (hq >= G) t = v4u{0, 0, 0, 0};
+                qb[s] = __builtin_bit_cast(v8f16, t);
+            }
+        }
+#endif
         {
             v4f32 Dr = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -492,10 +536,34 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
         if ((I) == NV - 3) UNIT_REQ_V(BL_SL, bl_j + RING)                                                          \
     }
 #define BLOCK() { UNIT_REQ_K(BL_SL, bl_j + RING) FOR_NV(BL_STEP) SOFTMAX(bl_j + 1) ++bl_j; }
+    // BLOCK_LAST: the wave's last block - there is no round bl_j + 2, so it requests nothing and does not start that round's K
+    // gathers; every product, gather and swizzle of rounds bl_j and bl_j + 1 is where BLOCK has it.  (Until this form existed the
+    // last block re-requested the wave's last unit through LAUNCH_FRONT_ROUND's clamp: 8 KiB per wave at M = 64 that nobody read -
+    // at two units per wave a third of the code requests of the CU's in-order load path.)
+#define BL_STEP_LAST(I)                                                                                            \
+    if constexpr ((I) < NV) {                                                                                      \
+        VS(I)                                                                                                      \
+        __builtin_amdgcn_sched_barrier(0);                                                                         \
+        VG(((I) + 2 < NV ? BL_SL : BL_SLN), ((I) + 2) & (NV - 1))                                                  \
+        __builtin_amdgcn_sched_barrier(0);                                                                         \
+        KM(2 * (I))                                                                                                \
+        if constexpr (2 * (I) + 3 < NK) KG(BL_SLN, 2 * (I) + 3)                                                    \
+        __builtin_amdgcn_sched_barrier(0);                                                                         \
+        KM(2 * (I) + 1)                                                                                            \
+        if constexpr (2 * (I) + 4 < NK) KG(BL_SLN, 2 * (I) + 4)                                                    \
+        __builtin_amdgcn_sched_barrier(0);                                                                         \
+    }
+#if MILLION_EXP & 128      // (A/B: the last block is a BLOCK, as it was - it re-requests the last unit; profiles/ab_decode_loadpath.txt)
+#define BLOCK_LAST() BLOCK()
+#else
+#define BLOCK_LAST() { FOR_NV(BL_STEP_LAST) SOFTMAX(bl_j + 1) ++bl_j; }
+#endif
     // the value products of the unit in slot VA_SL alone (gathers 0 .. 2 are in flight; 3 steps ahead)
 #define VA_STEP(I) if constexpr ((I) < NV) { if constexpr ((I) + 3 < NV) VG(VA_SL, (I) + 3) VS(I) __builtin_amdgcn_sched_barrier(0); }
     // A wave with n units runs: scores of unit 0 | n - 1 blocks (values of unit j beside the scores of unit j + 1) | values of unit
-    // n - 1.  Blocks alternate between the two ring slots (unit j lives in slot j & 1): one block, pairs in a loop, one more when n is odd.
+    // n - 1.  Blocks alternate between the two ring slots (unit j lives in slot j & 1): requesting blocks in pairs in a loop, then
+    // the last block, which requests nothing.  Every unit j < n is requested exactly once (units 0 and 1 by the prologue, unit j + 2
+    // by block j) and no block requests a unit >= n (tests/test_decode_schedule_host.py restates this loop).
     const int nb = n_mine > 1 ? n_mine - 1 : 0;
     TailReq treq;
     treq.idx = 0; treq.gen = 0; treq.cen = 0; treq.base = 0; treq.done = false;
@@ -511,23 +579,31 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
         VG(0, 0) VG(0, 1)
         if (nb > 0) {
             KG(1, 0) KG(1, 1) KG(1, 2)
+            // blocks 0 .. nb - 2 request round bl_j + 2, which exists; block nb - 1 is a BLOCK_LAST.  Pairs (slot 0, slot 1) while
+            // two requesting blocks remain; the odd one out (slot 0) leaves the loop in the middle.  (hipcc joins the wait state
+            // of that exit into BLOCK_LAST<0>, which then opens with vmcnt(2) / vmcnt(0) - the V bytes of its second unit, which
+            // it reads at its end.  The odd block as a copy of its own behind the loop moves one of the two waits to the end,
+            // costs a fifth block of text and measured no faster: profiles/ab_decode_loadpath.txt, 7.)
+            for (int rq = nb - 1; rq > 0; rq -= 2) {
 #define BL_SL 0
 #define BL_SLN 1
-            BLOCK()
+                BLOCK()
 #undef BL_SL
 #undef BL_SLN
-            for (int w = 0; w < (nb - 1) >> 1; ++w) {
+                if (rq == 1) break;
 #define BL_SL 1
 #define BL_SLN 0
                 BLOCK()
 #undef BL_SL
 #undef BL_SLN
+                if (rq == nb - 1) STAMP(17);
+            }
+            if (!(n_mine & 1)) {      // an even number of units: the last block works in slot 0
 #define BL_SL 0
 #define BL_SLN 1
-                BLOCK()
+                BLOCK_LAST()
 #undef BL_SL
 #undef BL_SLN
-                if (w == 0) STAMP(17);
             }
         }
         tail_request(p, bh, p.nslots, wave, lane, treq);      // ~3 us ahead of the point where the tail needs the answers
@@ -536,7 +612,7 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
             if (nb > 0) {
 #define BL_SL 1
 #define BL_SLN 0
-                BLOCK()
+                BLOCK_LAST()
 #undef BL_SL
 #undef BL_SLN
             }
@@ -552,7 +628,9 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
         }
     }
 #undef BLOCK
+#undef BLOCK_LAST
 #undef BL_STEP
+#undef BL_STEP_LAST
 #undef VA_STEP
 #undef SA_STEP
 #undef FOR_NK

@@ -48,7 +48,8 @@ constexpr int kTabBytes = 64 * 1024;         // one codebook image (M*C*dm*2)
 constexpr int kVBase = kTabBytes;            // V col image behind the K row image
 constexpr int kPartOff = 2 * kTabBytes;      // [128K,136K): final partial, flag
 constexpr int kStampOff = kPartOff + 8192;   // [136K,138K): diagnostic stamps (only touched when a stamp buffer is set)
-constexpr int kLdsBytes = kStampOff + kStampWaves * kStampSlots * 8;  // 138 KiB
+constexpr int kQOff = kStampOff + kStampWaves * kStampSlots * 8;      // [138K,139K): the (b, kv head)'s query rows (lean kernel: G x d fp16, <= 1 KiB)
+constexpr int kLdsBytes = kQOff + 1024;      // 139 KiB
 constexpr int kResRows = 16;                 // residual-window rows per wave (one MFMA tile): 8 waves x 16 = 128 rows per split
 
 #include "decode_wave.h"     // wave helpers, online softmax, the residual-window tile: both kernels and the tail

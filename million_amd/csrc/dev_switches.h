@@ -10,7 +10,11 @@
 //     attn_mfma.hip   2  the last-arriving workgroup merges alone (no helpers)                    profiles/r04_ab_merge.txt
 //     attn_tail.h    64  a fused append with device-resident lengths does not advance r: no second-level ticket, no bump
 //                        (timing only - what the step form pays for the advance; tools/advance_probe.py)  profiles/ab_decode_advance.txt
-//     attn_stream.h  32  "the launch without arithmetic": every request, wait, barrier and the tail stay, a unit's bytes are
+//     attn_lean.h   128  a wave's last block is a requesting BLOCK again: it re-requests the wave's last unit (the clamp of
+//                        LAUNCH_FRONT_ROUND), as every build did before BLOCK_LAST                  profiles/ab_decode_loadpath.txt
+//                  4096  every wave loads its own query operand (Q[], qb) from global memory instead of reading the
+//                        workgroup's image in LDS (kQOff)                                           profiles/ab_decode_loadpath.txt
+//     attn_stream.h  32"the launch without arithmetic": every request, wait, barrier and the tail stay, a unit's bytes are
 //                        xor-ed into a sink instead of gathered, multiplied and soft-maxed         profiles/r04_launch_floor.txt
 //     prefill.hip   (the pipelined kernel only; the plain loop's round 3-4 bits are in profiles/r03_prefill.txt, r04_prefill.txt)
 //                     4  no value products, 8 no score products

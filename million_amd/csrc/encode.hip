@@ -165,10 +165,10 @@ __global__ __launch_bounds__(kEncBlock) void pq_encode_small_kernel(EncParams p)
 // behind five dependent cold round trips: 18.8 us per launch inside a decode step.  Round 3, first form: 16-wave
 // workgroups (wave = head x centroid part), everything independent of the lengths requested first, early ticket: 9.5 us
 // in situ - but a 16-wave workgroup needs a CU to itself, and a decode step has none to spare: every attention launch puts
-// one 138-KiB workgroup on each CU, so each flush launch on the side stream (PagedPQCache.flush_ahead) held some
+// one 139-KiB workgroup on each CU, so each flush launch on the side stream (PagedPQCache.flush_ahead) held some
 // attention workgroups back for its own duration (flush step = 1.21 x a plain step).
 // Now the flush is built to run BESIDE the attention workgroups instead of between them: 4 waves (one per SIMD),
-// <= 32 VGPRs, 5 KiB of LDS.  An attention workgroup holds 2 x 240 of a SIMD's 512 registers and 138 of the CU's 160 KiB,
+// <= 32 VGPRs, 5 KiB of LDS.  An attention workgroup holds 2 x 240 of a SIMD's 512 registers and 139 of the CU's 160 KiB,
 // so one flush workgroup fits on every CU while attention runs, and a new attention workgroup fits while a flush
 // workgroup is resident: neither waits for the other; the flush's ~2300 vector instructions per wave fill issue slots
 // the latency-bound front and tail of the attention kernel leave empty.
