@@ -489,6 +489,32 @@ int million_attn_kernel_kind(const million_attn_desc *desc);
  * tile loop at d = 128 instead of the pipelined one (csrc/prefill.hip; A/B and the tests of both forms).  Any other value means auto. */
 void million_set_force_generic(int on);
 
+/* The decode step over 16-bit codes (nbits 9 .. 12; the reference stores them as one uint16 each, pq_utils.py:542-552, and has
+ * no fused kernel for them: its only route is sa_decode_4d + scaled_dot_product_attention).  One launch (csrc/attn_wide.hip) with
+ * the job, the `out`, lse, fused-append and device-length semantics of million_pq_decode_attn_lse above, word for word: nothing
+ * to attend to gives zeros and -inf, `out` with lse is bitwise `out` without, the window row an append writes may hold anything.
+ *   desc       million_attn_desc as above; C in {512, 1024, 2048, 4096}; d in {128, 64}; d / M in {2, 4}; nh / nh_k <= 16
+ *              (one launch; no several-launch form); k_layout = v_layout = MILLION_KV_PAGED, v_pages_dense = 0; resid_cap as
+ *              above.  Anything else: MILLION_ERR_SHAPE before any launch.
+ *   k_codes    K pool (n_pool, page_size, M) uint16;  v_codes: V pool (n_pool, M, page_size) uint16 (transposed pages).
+ *   k_cents    the PLAIN (M, C, d_m) fp16 codebooks, read from global memory (a table is 128 KiB .. 1 MiB: none fits in LDS).
+ *   v_cents    Aligned to one entry: 4 bytes at d_m = 2, 8 bytes at d_m = 4.  million_prepare_cents keeps refusing C > 256.
+ *   lse        (bs, nh) fp32 or NULL.  k_new = v_new = NULL: no append.
+ * Every index the kernel gathers with is code & (C - 1): codes past n_tokens (or the device length) in the last page, pages no
+ * live entry names and poisoned memory may hold any 16 bits and change no bit of the output.  Page ids are trusted.
+ * The workspace has the layout of million_attn_workspace_bytes' (zeroed once, left at rest by every call; calls of the uint8
+ * entries may share it when it is large enough for both).  million_attn_wide_splits: the code splits per (b, kv head) the call
+ * would launch (its grid is splits + 1 workgroups per pair), -1 for a descriptor the entry refuses.
+ * million_attn_kernel_kind does not know this kernel: it answers for the uint8 entries only. */
+size_t million_attn_wide_workspace_bytes(const million_attn_desc *desc);      /* 0 for a descriptor the entry refuses */
+int million_attn_wide_splits(const million_attn_desc *desc);
+int million_pq_decode_attn_wide(const million_attn_desc *desc, const void *q,
+                                const void *k_new, const void *v_new,         /* both NULL: no append */
+                                const void *k_codes, const void *v_codes, const void *k_page_ids, const void *v_page_ids,
+                                const void *k_cents, const void *v_cents,
+                                void *k_resid, void *v_resid, void *out, float *lse /* may be NULL */,
+                                void *workspace, size_t workspace_bytes, million_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Prompt (prefill) attention on fp16 K/V.
  * Replaces: scaled_dot_product_attention(q, repeat_kv(k), repeat_kv(v), is_causal=True) of the reference's prompt pass

@@ -150,6 +150,10 @@ SYMBOLS = {
     "million_pq_decode_attn_lse": (c_i32, [ctypes.POINTER(AttnDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                            c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "million_attn_kernel_kind": (c_i32, [ctypes.POINTER(AttnDesc)]),
+    "million_attn_wide_workspace_bytes": (c_sz, [ctypes.POINTER(AttnDesc)]),
+    "million_attn_wide_splits": (c_i32, [ctypes.POINTER(AttnDesc)]),
+    "million_pq_decode_attn_wide": (c_i32, [ctypes.POINTER(AttnDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                            c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "million_prefill_attn": (c_i32, [ctypes.POINTER(PrefillDesc), c_vp, c_vp, c_vp, c_vp, c_vp]),
     "million_chunk_attn_workspace_bytes": (c_sz, [ctypes.POINTER(ChunkAttnDesc)]),
     "million_pq_chunk_attn": (c_i32, [ctypes.POINTER(ChunkAttnDesc)] + [c_vp] * 13 + [c_sz, c_vp]),

@@ -503,6 +503,10 @@ struct AttnPlan {
 bool plan_attn_mfma(const AttnParams &p, AttnPlan &plan);    // attn_mfma.hip: the lean and streaming kernels
 bool plan_attn_tile(const AttnParams &p, AttnPlan &plan);    // attn_tile.hip
 int plan_attn_generic(const AttnParams &p, AttnPlan &plan);  // attn_generic.hip: the scalar kernel, up to kMaxG query heads
+// attn_wide.hip: 16-bit codes (million_pq_decode_attn_wide only: no other entry asks it).  k_tab / v_tab are the plain
+// (M, C, d_m) codebooks, k_codes / v_codes the uint16 pools.  wide_geometry: the (d, M, C, nh / nh_k) that kernel is built for
+bool plan_attn_wide(const AttnParams &p, AttnPlan &plan);
+bool wide_geometry(int d, int M, int C, int G);
 int launch_encode(const EncParams &p, hipStream_t s);
 int launch_decode(const void *codes, const f16 *cents, f16 *out, long long n_rows, int M, int C, int dm, hipStream_t s);
 struct FlushLayers { int n_layers; long long x_ls, ids_ls, len_ls; int advance; };      // one layer: {1, 0, 0, 0, 1}

@@ -164,7 +164,8 @@ static size_t attn_partial_bytes(int bs, int nh_k, int G, int d) {
     return (b + 255) / 256 * 256;
 }
 
-static int fill_attn_params(const million_attn_desc *desc, AttnParams &p) {
+// wide: the call is million_pq_decode_attn_wide's (uint16 codes: attn_wide.hip); the geometry check is then that kernel's
+static int fill_attn_params(const million_attn_desc *desc, AttnParams &p, bool wide = false) {
     if (!desc || desc->struct_size != sizeof(million_attn_desc)) { set_error("attn: bad desc / struct_size"); return MILLION_ERR_ARG; }
     memset(&p, 0, sizeof(p));
     p.bs = desc->bs; p.nh = desc->nh; p.nh_k = desc->nh_k; p.d = desc->d; p.M = desc->M; p.C = desc->C;
@@ -176,7 +177,12 @@ static int fill_attn_params(const million_attn_desc *desc, AttnParams &p) {
     p.nhk_real = 1 << 28; p.nhk_mul = 0; p.hparts_m1 = 0; p.G_all = 0;      // no query-head parts (attn_mfma.hip mfma_virtual sets them)
     if (p.M <= 0 || p.d <= 0 || p.d % p.M || p.M % 4) { set_error("attn: d=%d M=%d", p.d, p.M); return MILLION_ERR_SHAPE; }
     p.dm = p.d / p.M;
-    if (p.C < 2 || p.C > 256) { set_error("attn: C=%d (uint8 codes)", p.C); return MILLION_ERR_SHAPE; }
+    if (wide) {
+        if (!wide_geometry(p.d, p.M, p.C, p.Gt)) {
+            set_error("attn_wide: d=%d M=%d C=%d nh/nh_k=%d (d 64 / 128, d/M 2 / 4, C 512 / 1024 / 2048 / 4096: uint16 codes, up to %d query heads per kv head)", p.d, p.M, p.C, p.Gt, kMaxGMfma);
+            return MILLION_ERR_SHAPE;
+        }
+    } else if (p.C < 2 || p.C > 256) { set_error("attn: C=%d (uint8 codes)", p.C); return MILLION_ERR_SHAPE; }
     p.T = desc->n_tokens; p.r = desc->r; p.rstart = desc->resid_start; p.rcap = desc->resid_cap;
     if (p.T < 0 || p.rcap <= 0 || p.r < 0 || p.r > p.rcap || p.rstart < 0 || p.rstart >= p.rcap) {
         set_error("attn: T=%d r=%d resid_start=%d resid_cap=%d", p.T, p.r, p.rstart, p.rcap);
@@ -201,6 +207,7 @@ static int fill_attn_params(const million_attn_desc *desc, AttnParams &p) {
     p.dev_lengths = desc->dev_lengths;
     p.scale_log2e = 1.4426950408889634f / sqrtf((float)p.d);
     p.slot_floats = (int)slot_floats_for(p.G, p.d);
+    if (wide && (!p.k_paged || !p.v_paged || p.v_identity)) { set_error("attn_wide: K and V codes must be in page pools (k_layout = v_layout = MILLION_KV_PAGED, no dense V run)"); return MILLION_ERR_SHAPE; }
     return MILLION_OK;
 }
 
@@ -551,6 +558,67 @@ int million_pq_decode_attn_lse(const million_attn_desc *desc, const void *q, con
     if ((uintptr_t)lse & 3) { set_error("attn_lse: lse must be 4-byte aligned"); return MILLION_ERR_ALIGN; }
     return attn_impl(desc, q, k_new, v_new, k_codes, v_codes, k_page_ids, v_page_ids, k_cents_prepared,
                      v_cents_prepared, k_resid, v_resid, out, lse, workspace, workspace_bytes, stream);
+}
+
+/* ---- 16-bit codes: one entry, one kernel (attn_wide.hip) ---- */
+size_t million_attn_wide_workspace_bytes(const million_attn_desc *desc) {
+    AttnParams p;
+    if (fill_attn_params(desc, p, true) != MILLION_OK) return 0;
+    return attn_partial_bytes(p.bs, p.nh_k, p.G, p.d);
+}
+
+int million_attn_wide_splits(const million_attn_desc *desc) {
+    AttnParams p;
+    AttnPlan plan;
+    if (fill_attn_params(desc, p, true) != MILLION_OK || !plan_attn_wide(p, plan)) return -1;
+    return plan.p.nsplit;
+}
+
+int million_pq_decode_attn_wide(const million_attn_desc *desc, const void *q, const void *k_new, const void *v_new,
+                                const void *k_codes, const void *v_codes, const void *k_page_ids, const void *v_page_ids,
+                                const void *k_cents, const void *v_cents, void *k_resid, void *v_resid, void *out, float *lse,
+                                void *workspace, size_t workspace_bytes, million_stream_t stream) {
+    AttnParams p;
+    const int rc = fill_attn_params(desc, p, true);
+    if (rc != MILLION_OK) return rc;
+    if ((k_new == nullptr) != (v_new == nullptr)) { set_error("attn_wide: k_new and v_new must both be given"); return MILLION_ERR_ARG; }
+    if (k_new) {
+        if (!p.dev_lengths && p.r >= p.rcap) { set_error("attn_wide: fused append into a full window (r=%d, cap=%d)", p.r, p.rcap); return MILLION_ERR_ARG; }
+        if (((uintptr_t)k_new | (uintptr_t)v_new) & 15) { set_error("attn_wide: k_new / v_new must be 16-byte aligned"); return MILLION_ERR_ALIGN; }
+    }
+    if (!q || !k_cents || !v_cents || !k_resid || !v_resid || !out || !workspace) { set_error("attn_wide: null pointer"); return MILLION_ERR_ARG; }
+    if (p.T > 0 && (!k_codes || !v_codes)) { set_error("attn_wide: null code pointer with n_tokens=%d", p.T); return MILLION_ERR_ARG; }
+    if (p.T > 0 && (!k_page_ids || !v_page_ids)) { set_error("attn_wide: paged layout without page ids"); return MILLION_ERR_ARG; }
+    const size_t need = attn_partial_bytes(p.bs, p.nh_k, p.G, p.d);
+    if (workspace_bytes < need) { set_error("attn_wide: workspace %zu < %zu bytes", workspace_bytes, need); return MILLION_ERR_WORKSPACE; }
+    if (((uintptr_t)q | (uintptr_t)k_codes | (uintptr_t)v_codes | (uintptr_t)k_resid | (uintptr_t)v_resid | (uintptr_t)out | (uintptr_t)workspace) & 15) {
+        set_error("attn_wide: q, codes, residuals, out and workspace must be 16-byte aligned");
+        return MILLION_ERR_ALIGN;
+    }
+    if (((uintptr_t)k_cents | (uintptr_t)v_cents) & (uintptr_t)(p.dm * 2 - 1)) { set_error("attn_wide: codebooks must be aligned to one entry (%d bytes)", p.dm * 2); return MILLION_ERR_ALIGN; }
+    if ((uintptr_t)lse & 3) { set_error("attn_wide: lse must be 4-byte aligned"); return MILLION_ERR_ALIGN; }
+    if ((p.res_sb | p.res_sh) & 7) { set_error("attn_wide: residual strides must be multiples of 8 elements"); return MILLION_ERR_ALIGN; }
+    p.q = (const f16 *)q; p.k_codes = (const uint8_t *)k_codes; p.v_codes = (const uint8_t *)v_codes;
+    p.k_ids32 = (const int *)k_page_ids; p.k_ids64 = (const long long *)k_page_ids;
+    p.v_ids32 = (const int *)v_page_ids; p.v_ids64 = (const long long *)v_page_ids;
+    p.k_tab = (const f16 *)k_cents; p.v_tab = (const f16 *)v_cents;      // the plain (M, C, d_m) tensors: no prepared image
+    p.k_res = (const f16 *)k_resid; p.v_res = (const f16 *)v_resid; p.out = (f16 *)out;
+    p.lse = lse;
+    p.k_new = (const f16 *)k_new; p.v_new = (const f16 *)v_new;
+    p.k_res_w = (f16 *)k_resid; p.v_res_w = (f16 *)v_resid;
+    p.dev_lengths_w = (int *)desc->dev_lengths;
+    p.ws_cnt = (unsigned long long *)workspace;
+    p.ws_cnt2 = (int *)((unsigned *)workspace + head_pairs(p.bs, p.nh_k) * kRecWords);
+    p.ws_flags = (unsigned *)((char *)workspace + attn_cnt_bytes(p.bs, p.nh_k));
+    p.ws_part = (float *)((char *)workspace + attn_cnt_bytes(p.bs, p.nh_k) + attn_flag_bytes(p.bs, p.nh_k));
+    p.dbg = g_dbg;
+    p.k_pool_pages = desc->k_pool_pages; p.v_pool_pages = desc->v_pool_pages;
+#ifdef MILLION_DEBUG_CHECK_IDS
+    p.bad_ids = bad_ids_counter();
+#endif
+    AttnPlan plan;
+    if (!plan_attn_wide(p, plan)) { set_error("attn_wide: no kernel for this call"); return MILLION_ERR_SHAPE; }
+    return launch_plan(plan, (hipStream_t)stream);
 }
 
 int million_residual_append(const void *k_new, const void *v_new, void *k_resid, void *v_resid, int bs, int nh_k,

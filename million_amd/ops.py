@@ -573,6 +573,104 @@ def pq_decode_attn(q: torch.Tensor, k_codes: torch.Tensor, v_codes: torch.Tensor
     return out
 
 
+WIDE_CENTROIDS = (512, 1024, 2048, 4096)
+
+
+def wide_attn_desc(who, q, k_pool, v_pool, k_cents, v_cents, k_res, v_res, r, n_tokens, page_ids, page_size, resid_start,
+               dev_lengths) -> L.AttnDesc:
+    """Every check of a wide decode call that needs no library, and its descriptor."""
+    _need_cuda(q, k_pool, v_pool, k_cents, v_cents, k_res, v_res, page_ids, dev_lengths)
+    if q.dtype != torch.float16 or k_res.dtype != torch.float16 or v_res.dtype != torch.float16:
+        raise RuntimeError(f"{who}: q and residuals must be fp16")
+    if k_pool.dtype != torch.uint16 or v_pool.dtype != torch.uint16:
+        raise RuntimeError(f"{who}: codes must be uint16 (uint8 codes: pq_decode_attn)")
+    if k_cents.dtype != torch.float16 or v_cents.dtype != torch.float16 or k_cents.dim() != 3 or k_cents.shape != v_cents.shape:
+        raise RuntimeError(f"{who}: k_cents / v_cents must be the plain fp16 (M, C, d_m) codebooks of one shape")
+    if not k_cents.is_contiguous() or not v_cents.is_contiguous():
+        raise RuntimeError(f"{who}: codebooks must be contiguous")
+    if q.dim() != 4 or q.shape[2] != 1 or not q.is_contiguous():
+        raise RuntimeError(f"{who}: q must be contiguous (bs, nh, 1, d)")
+    if (k_res.dim() != 4 or k_res.shape != v_res.shape or k_res.stride() != v_res.stride() or k_res.stride(3) != 1
+            or k_res.stride(2) != k_res.shape[3]):
+        raise RuntimeError(f"{who}: residual buffers must share shape/strides with dense rows")
+    M, C, dm = k_cents.shape
+    if M * dm != q.shape[3]:
+        raise RuntimeError(f"{who}: codebooks of {M} x {dm} dims for d={q.shape[3]}")
+    if page_ids is None or page_ids.dtype not in (torch.int32, torch.int64) or not page_ids.is_contiguous() or page_ids.dim() != 3:
+        raise RuntimeError(f"{who}: page_ids must be contiguous int32/int64 (bs, nh_k, n_pages)")
+    if not k_pool.is_contiguous() or not v_pool.is_contiguous():
+        raise RuntimeError(f"{who}: page pools must be contiguous")
+    if k_pool.dim() != 3 or tuple(k_pool.shape[1:]) != (page_size, M) or v_pool.dim() != 3 or tuple(v_pool.shape[1:]) != (M, page_size):
+        raise RuntimeError(f"{who}: pools must be K (n_pool, page_size, M) and V (n_pool, M, page_size)")
+    if dev_lengths is not None and (dev_lengths.dtype != torch.int32 or tuple(dev_lengths.shape) != (q.shape[0], 4)
+                                    or not dev_lengths.is_contiguous()):
+        raise RuntimeError(f"{who}: dev_lengths must be contiguous int32 (bs, 4)")
+    return make_attn_desc(q, k_res, nh_k=k_res.shape[1], M=M, C=C, n_tokens=n_tokens, r=r, resid_start=resid_start, k_paged=True,
+                          v_paged=True, page_size=page_size, n_pages_cap=page_ids.shape[2],
+                          page_ids_i64=page_ids.dtype == torch.int64, k_codes=k_pool, v_codes=v_pool, dev_lengths=dev_lengths)
+
+
+def decode_wide_workspace_bytes(q, k_res, *, M, C, page_size=64) -> int:
+    """million_attn_wide_workspace_bytes of a wide decode call of this shape: what a cache allocates (zeroed) once and hands to
+    every pq_decode_attn_wide(workspace=)."""
+    desc = make_attn_desc(q, k_res, nh_k=k_res.shape[1], M=M, C=C, n_tokens=0, r=0, k_paged=True, v_paged=True,
+                          page_size=page_size, n_pages_cap=1)
+    lib = L.load()
+    need = int(lib.million_attn_wide_workspace_bytes(ctypes.byref(desc)))
+    if not need:      # 0: the entry refuses the shape, and has said why
+        raise RuntimeError(f"decode_wide_workspace_bytes: {lib.million_last_error().decode(errors='replace')}")
+    return need
+
+
+def attn_wide_splits(desc: L.AttnDesc) -> int:
+    """Code splits per (b, kv head) a wide decode call of this descriptor launches; -1: the entry refuses it."""
+    return int(L.load().million_attn_wide_splits(ctypes.byref(desc)))
+
+
+def pq_decode_attn_wide(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_cents: torch.Tensor,
+                        v_cents: torch.Tensor, k_res: torch.Tensor, v_res: torch.Tensor, r: int, *, n_tokens: int,
+                        page_ids: torch.Tensor, page_size: int, resid_start: int = 0, out: Optional[torch.Tensor] = None,
+                        dev_lengths: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                        k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None,
+                        return_lse: bool = False, lse: Optional[torch.Tensor] = None):
+    """pq_decode_attn over uint16 codes (512 .. 4096 centroids): one fused launch (million_pq_decode_attn_wide) over the paged
+    code store + residual window + merge, the fused append and the lse included, with pq_decode_attn's semantics.
+
+    K pool (n_pool, page_size, M) u16, V pool (n_pool, M, page_size) u16, one page-id table (bs, nh_k, n_pages_cap) int32/int64
+    for both sides; k_cents / v_cents are the plain (M, C, d_m) fp16 codebooks (there is no prepared image)."""
+    _need_cuda(out, lse, k_new, v_new, workspace)
+    desc = wide_attn_desc("pq_decode_attn_wide", q, k_pool, v_pool, k_cents, v_cents, k_res, v_res, r, n_tokens, page_ids, page_size,
+                      resid_start, dev_lengths)
+    if out is None:
+        out = torch.empty_like(q)
+    elif out.dtype != torch.float16 or out.numel() != q.numel() or not out.is_contiguous():
+        raise RuntimeError("pq_decode_attn_wide: out must be contiguous fp16 of q's size")
+    if k_new is not None or v_new is not None:
+        if k_new is None or v_new is None or tuple(k_new.shape) != (q.shape[0], k_res.shape[1], 1, q.shape[3]) or v_new.shape != k_new.shape:
+            raise RuntimeError("pq_decode_attn_wide: k_new / v_new must be (bs, nh_k, 1, d)")
+        if k_new.dtype != torch.float16 or v_new.dtype != torch.float16:
+            raise RuntimeError("pq_decode_attn_wide: k_new / v_new must be fp16")
+        k_new, v_new = k_new.contiguous(), v_new.contiguous()
+    want_lse = return_lse or lse is not None
+    if want_lse:
+        if lse is None:
+            lse = torch.empty(q.shape[0], q.shape[1], 1, dtype=torch.float32, device=q.device)
+        elif lse.dtype != torch.float32 or tuple(lse.shape) != (q.shape[0], q.shape[1], 1) or not lse.is_contiguous():
+            raise RuntimeError("pq_decode_attn_wide: lse must be contiguous fp32 (bs, nh, 1)")
+    lib = L.load()
+    if workspace is None:
+        need = int(lib.million_attn_wide_workspace_bytes(ctypes.byref(desc)))
+        key = (q.device.index, torch.cuda.current_stream().cuda_stream, "wide")
+        workspace = _ws_cache.get(key)
+        if workspace is None or workspace.numel() < need:      # zeroed once; every call leaves it ready (need = 0: the call is refused below)
+            workspace = _ws_cache[key] = torch.zeros(max(need, 256), dtype=torch.uint8, device=q.device)
+    L.check(lib.million_pq_decode_attn_wide(ctypes.byref(desc), q.data_ptr(), _ptr(k_new), _ptr(v_new), k_pool.data_ptr(),
+                                            v_pool.data_ptr(), page_ids.data_ptr(), page_ids.data_ptr(), k_cents.data_ptr(),
+                                            v_cents.data_ptr(), k_res.data_ptr(), v_res.data_ptr(), out.data_ptr(), _ptr(lse),
+                                            workspace.data_ptr(), workspace.numel(), _stream()), "million_pq_decode_attn_wide")
+    return (out, lse) if want_lse else out
+
+
 def prefill_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, causal: bool = True, q_pos0: int = 0,
                  out: Optional[torch.Tensor] = None, dev_spans: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Prompt attention on fp16 K/V (million_prefill_attn): q (bs, nh, n_q, d), k / v (bs, nh_k, n_kv, d) -> (bs, nh, n_q, d).

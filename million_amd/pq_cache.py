@@ -429,15 +429,24 @@ class PagedPQCache(_CacheBase):
     `sink_tokens=S` (0 .. 64; 0: nothing is allocated and every call launches what it always did): the first min(S, n) rows of
     a request's first store step (prefill*, extend*) stay exact fp16 rows beside the pages - the attention sinks - and only the
     rows behind them are encoded; decoding_with_pages, the extend forms and verify merge them into their result with one more
-    launch (ops.attn_sink_merge), the live count read on the device.  `seen` counts them, T does not.  DESIGN.md 4.13."""
+    launch (ops.attn_sink_merge), the live count read on the device.  `seen` counts them, T does not.  DESIGN.md 4.13.
+
+    `nbits` 9 .. 12 with `dtype=torch.uint16` (uint16 pools, codebooks of 2**nbits centroids): the core life - prefill,
+    prefill_request, decoding_with_pages (ops.pq_decode_attn_wide), the in-line flush of requests in lockstep, release, cleanup -
+    and NotImplementedError naming nbits for the rest (extend*, prefill_ragged, fork, swap, verify / commit, update, sinks).
+    DESIGN.md 4.14."""
 
     def __init__(self, *, bs, nh, num_key_value_heads, M, layer_num, dtype=torch.uint8, nbits=8, d=128,
                  scalar_t=torch.float16, page_size=64, extended_residual_size=128, max_pages_per_layer=None,
                  max_tokens=32768 + 1024, preallocate=True, device="cuda", sink_tokens=0):
-        if nbits != 8 or dtype != torch.uint8:
-            raise NotImplementedError("Only uint8 code type is supported for now")
+        if nbits not in (8, 9, 10, 11, 12) or dtype != nbits2dtype(nbits):
+            raise NotImplementedError(f"PagedPQCache: nbits=8 with dtype=torch.uint8, or nbits 9 .. 12 with dtype=torch.uint16 "
+                                      f"(DESIGN.md 4.14), are the code types that exist; got nbits={nbits}, dtype={dtype}")
         if isinstance(sink_tokens, bool) or int(sink_tokens) != sink_tokens or not 0 <= sink_tokens <= ops.SINK_MAX_ROWS:
             raise ValueError(f"sink_tokens must be an integer in 0 .. {ops.SINK_MAX_ROWS}")
+        if nbits > 8 and sink_tokens:
+            raise NotImplementedError(f"PagedPQCache: sink_tokens > 0 on a cache with nbits={nbits} (uint16 codes) is not built yet "
+                                      "(DESIGN.md 4.14)")
         if page_size not in (32, 64, 128):
             raise ValueError("page_size must be 32, 64 or 128")
         if extended_residual_size < page_size:
@@ -460,8 +469,8 @@ class PagedPQCache(_CacheBase):
         nk, cap = self.num_key_value_heads, self.extended_residual_size
         total = self.layer_num * self.bs * nk * self.n_pages_cap
         z = lambda *s, dt: torch.zeros(*s, dtype=dt, device=self.device)
-        self.key_page_pool = z(total, self.page_size, self.M, dt=torch.uint8)
-        self.value_page_pool = z(total, self.M, self.page_size, dt=torch.uint8)
+        self.key_page_pool = z(total, self.page_size, self.M, dt=self.dtype)      # uint8; uint16 at nbits 9 .. 12
+        self.value_page_pool = z(total, self.M, self.page_size, dt=self.dtype)
         self.page_manager = PageManager(self.page_size, initial_pages=total, max_pages=total, M=self.M)
         # the layers' page tables, windows and length rows lie side by side (one allocation each; the per-layer lists are
         # views): one launch can then serve every layer (begin_step: encode-ahead, commit)
@@ -580,6 +589,13 @@ class PagedPQCache(_CacheBase):
         if self.sink_tokens:
             raise NotImplementedError(f"PagedPQCache: {what} of a cache with sink_tokens > 0 is not built yet (DESIGN.md 4.13)")
 
+    def _no_wide(self, what):
+        """nbits 9 .. 12 (uint16 codes): the core life is built - prefill, prefill_request, decoding_with_pages, the in-line
+        flush, release - and the rest refused by name, before any state changes."""
+        if self.nbits > 8:
+            raise NotImplementedError(f"PagedPQCache: {what} of a cache with nbits={self.nbits} (uint16 codes) is not built yet "
+                                      "(DESIGN.md 4.14)")
+
     def _sync_lengths(self, layer_idx, b=None):
         """The device rows of a layer - of request b alone: the others' are not touched - written from the mirror."""
         sel = slice(None) if b is None else slice(b, b + 1)
@@ -691,6 +707,7 @@ class PagedPQCache(_CacheBase):
         n_new[b] = 0 takes no part: host and device lengths, pages and window stay as they are (it may be mid-decode).
         device_store=True: the per-slot encodes and length copies are ONE ops.pq_store_ragged call behind the attention launch
         (an int32 device copy of n_new beside `lengths[layer_idx]`): same pages, same codes, same host and device lengths."""
+        self._no_wide("prefill_ragged")
         n_new = [int(x) for x in n_new]
         n = query_states.size(2)
         if (len(n_new) != self.bs or query_states.size(0) != self.bs or key_states.size(0) != self.bs or key_states.size(2) != n
@@ -766,6 +783,7 @@ class PagedPQCache(_CacheBase):
         behind T, the window is emptied (r = 0, resid_start = 0), host and device lengths advance.  Pending encode-ahead
         work of the layer (begin_step, flush_ahead) is joined first and its flags cleared: rows encoded ahead are encoded
         again into the same pages with the same codes.  On an empty cache this is prefill()."""
+        self._no_wide("extend")
         if not self._lockstep(layer_idx):
             raise RuntimeError("PagedPQCache.extend: requests are at different lengths; use extend_request(b, ...)")
         self._join_side(layer_idx)
@@ -779,6 +797,7 @@ class PagedPQCache(_CacheBase):
         return_lse=True: returns (out, lse), lse fp32 (1, nh, n) - every row's log-sum-exp over the keys it saw
         (ops.pq_chunk_attn).  The prompt kernel has none, so an empty slot is then served by chunk attention over the chunk
         alone, followed by the same store: the slot, the pages and every length are left as prefill_request leaves them."""
+        self._no_wide("extend_request")
         if key_states.size(0) != 1 or query_states.size(0) != 1:
             raise RuntimeError("extend_request: tensors of batch 1")
         self._join_side(layer_idx, b)
@@ -799,6 +818,7 @@ class PagedPQCache(_CacheBase):
         lengths, pages and window stay as they are.  device_store=True: the per-slot encodes and length copies are ONE
         ops.pq_store_ragged call behind the attention launch, on the same `lengths[layer_idx]` and device copy of n_new - same
         pages, same codes, same host and device lengths; the device rows are advanced by the call, not written from the host."""
+        self._no_wide("extend_ragged")
         n_new = [int(x) for x in n_new]
         n_q = query_states.size(2)
         if len(n_new) != self.bs or query_states.size(0) != self.bs or key_states.size(0) != self.bs or key_states.size(2) != n_q:
@@ -869,6 +889,7 @@ class PagedPQCache(_CacheBase):
         T, so a shared page never changes under its owners.  A preallocated table keeps its fixed ids and gets a copy of
         every live page.  Call it between steps: the source must be at the same lengths in every layer (its pending
         encode-ahead work is joined, as extend does); every destination must be empty (release it first)."""
+        self._no_wide("fork")
         dsts = [int(dst)] if np.isscalar(dst) else [int(x) for x in dst]
         src = int(src)
         nk, ps, nl = self.num_key_value_heads, self.page_size, self.layer_num
@@ -971,6 +992,7 @@ class PagedPQCache(_CacheBase):
         GPU, in any process (formats.save_request) - decodes on with the bits this slot would have produced.  Call it between
         steps, as fork: the slot must be at the same lengths in every layer (its pending encode-ahead work is joined)."""
         self._no_sinks("swap_out / snapshot_request")
+        self._no_wide("swap_out / snapshot_request")
         one = np.isscalar(b)
         slots = [int(b)] if one else [int(x) for x in b]
         nk, nl = self.num_key_value_heads, self.layer_num
@@ -1024,6 +1046,7 @@ class PagedPQCache(_CacheBase):
         format version or geometry, more tokens than max_tokens, fewer free pages than the request needs (on demand), a blob of
         the wrong size, and - unless check_codebooks=False - codebooks other than the ones the codes were made with."""
         self._no_sinks("swap_in")
+        self._no_wide("swap_in")
         b = int(b)
         meta, blob = snap.meta, snap.blob
         nk, nl, ps = self.num_key_value_heads, self.layer_num, self.page_size
@@ -1100,6 +1123,7 @@ class PagedPQCache(_CacheBase):
         followed by the new rows as they are (or dequantised too with distort_recent).  No residual window on this path.
         extend() attends a block of new tokens to the codes and the window without the fp16 past."""
         self._no_sinks("update (the dequantise-then-attend path)")
+        self._no_wide("update (the dequantise-then-attend path)")
         if not self._lockstep(layer_idx) or self._r_a[layer_idx, 0]:
             raise RuntimeError("PagedPQCache.update: lockstep requests and an empty residual window expected")
         n = key_states.size(2)
@@ -1125,6 +1149,8 @@ class PagedPQCache(_CacheBase):
         cap, ps = self.extended_residual_size, self.page_size
         full = self._r_a[layer_idx] >= cap
         lock = self._lockstep(layer_idx)
+        if self.nbits > 8:
+            return self._flush_wide(layer_idx, use_dev_lengths, lock, full)
         # lockstep: the host flushes at r >= page_size, the device (min_r = cap with device lengths) only full windows - the
         # host mirror must not move when the device will not (a direct call with page_size <= r < cap)
         if lock and self._r_a[layer_idx, 0] < (cap if use_dev_lengths else ps):
@@ -1143,6 +1169,26 @@ class PagedPQCache(_CacheBase):
         self._dev_rows_stale |= not use_dev_lengths
         self._note_flushed(layer_idx if lock else (layer_idx, full))
 
+    def _flush_wide(self, layer_idx, use_dev_lengths, lock, full):
+        """flush_to_pages of a cache with uint16 codes (million_pq_flush is uint8-only): the two encodes of the in-line flush as
+        two ops.pq_encode_into launches - K pages and V pages out of the ring window (x_row_start / x_row_mod) - and, with
+        device-resident lengths, million_lengths_advance.  Lockstep requests only: the encodes take T and the ring start from
+        the host mirror.  Codes, pages, window and lengths afterwards are the uint8 rule's with a wider code."""
+        cap, ps = self.extended_residual_size, self.page_size
+        if not lock:
+            if not full.any():
+                return
+            raise RuntimeError(f"PagedPQCache: the flush of a cache with nbits={self.nbits} serves requests in lockstep only "
+                               "(requests at different lengths: DESIGN.md 4.14)")
+        if self._r_a[layer_idx, 0] < (cap if use_dev_lengths else ps):      # as the uint8 flush: the mirror moves when the device does
+            return
+        self._encode_to_pages(self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx], layer_idx, ps,
+                              x_row_start=int(self._rs_a[layer_idx, 0]), x_row_mod=cap)
+        if use_dev_lengths:
+            ops.lengths_advance(self.lengths[layer_idx], ps, cap)
+        self._dev_rows_stale |= not use_dev_lengths
+        self._note_flushed(layer_idx)
+
     # ---- encode-ahead: the flush without a flush step ---------------------------------------------------------------
     # The reference flushes the oldest page_size window rows when the window is full (paged_pq_utils.py:359-361).  Those
     # rows are complete page_size steps after the previous flush - extended_residual_size - page_size steps BEFORE they
@@ -1157,6 +1203,8 @@ class PagedPQCache(_CacheBase):
         """'plain' | 'pre' (encode-ahead rides along) | 'commit' (flush step, codes already there) | 'flush' (flush step)."""
         cap = self.extended_residual_size
         full = self._r_a >= cap
+        if self.nbits > 8:      # uint16 codes: the in-line flush is the only flush, nothing is encoded ahead
+            return "flush" if full.any() else "plain"
         if full.any():
             return "commit" if full.all() and self._pre_a.all() else "flush"
         if (not self._pre_a.all() and self._r_a[0, 0] >= self.encode_ahead_at() and self._r_a[0, 0] >= self.page_size
@@ -1190,6 +1238,8 @@ class PagedPQCache(_CacheBase):
         the step (next_step_kind).  Without it decoding_with_pages flushes in line, as the reference does."""
         kind = self.next_step_kind()
         cap, ps = self.extended_residual_size, self.page_size
+        if self.nbits > 8:      # reported only: decoding_with_pages flushes in line
+            return kind
         if kind == "commit":
             if use_dev_lengths:
                 ops.lengths_advance(self._lengths_all.view(-1, 4), ps, cap)      # every layer, every request: one launch
@@ -1241,6 +1291,8 @@ class PagedPQCache(_CacheBase):
         first attention launch gets out - measured: the main branch of the replayed step started ~300 us late.
         Results are identical to the in-line flush."""
         cap = self.extended_residual_size
+        if self.nbits > 8:      # uint16 codes: decoding_with_pages flushes in line
+            return
         todo = [l for l in range(self.layer_num) if (self._r_a[l] >= cap).any()]
         if not todo:
             return
@@ -1291,9 +1343,14 @@ class PagedPQCache(_CacheBase):
             raise RuntimeError("PagedPQCache: requests at different lengths need use_dev_lengths=True")
         r, rs = int(self._r_a[layer_idx, 0]), int(self._rs_a[layer_idx, 0])
         dl = self.lengths[layer_idx] if use_dev_lengths else None
+        wide = self.nbits > 8
         if self._ws is None:      # one workspace per cache (calls of one cache are stream-ordered)
-            need = ops.decode_workspace_bytes(query_states, self.key_residual_cache[layer_idx], nh_k=self.num_key_value_heads,
-                                              M=self.M, C=self.C)
+            if wide:
+                need = ops.decode_wide_workspace_bytes(query_states, self.key_residual_cache[layer_idx], M=self.M, C=self.C,
+                                                       page_size=self.page_size)
+            else:
+                need = ops.decode_workspace_bytes(query_states, self.key_residual_cache[layer_idx], nh_k=self.num_key_value_heads,
+                                                  M=self.M, C=self.C)
             self._ws = torch.zeros(need, dtype=torch.uint8, device=self.device)
         self._note_appended(layer_idx)
         self._dev_rows_stale |= not use_dev_lengths
@@ -1302,6 +1359,14 @@ class PagedPQCache(_CacheBase):
             if self._sink_lse is None:
                 self._sink_lse = torch.empty(self.bs, self.nh, 1, dtype=torch.float32, device=self.device)
             lse = self._sink_lse
+        if wide:      # the same launch over uint16 codes, the codebooks as they are (csrc/attn_wide.hip)
+            return ops.pq_decode_attn_wide(query_states, self.key_page_pool, self.value_page_pool, self.key_cent, self.value_cent,
+                                           self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx], r,
+                                           k_new=key_states, v_new=value_states,
+                                           n_tokens=self.max_tokens if use_dev_lengths else int(self._T_a[layer_idx, 0]),
+                                           resid_start=rs, page_ids=self.page_ids[layer_idx], page_size=self.page_size, out=out,
+                                           dev_lengths=dl, workspace=self._ws,
+                                           **({"return_lse": True, "lse": lse} if want_lse else {}))
         # append (:377-380) + attention (:386) in ONE launch: the new row is attended to and parked in the window
         res = ops.pq_decode_attn(query_states, self.key_page_pool, self.value_page_pool, self._kprep, self._vprep,
                                  self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx], r,
@@ -1366,6 +1431,7 @@ class PagedPQCache(_CacheBase):
         are a prefix of the tree.  The attention over the past is the chain's launch - it never looks at the order among the
         rows - on either route; "chunk" then runs chunk attention over the past only and the same masked block merge.  A
         malformed tree is refused (RuntimeError) before anything runs; commit() then takes path=."""
+        self._no_wide("verify")
         bs, nh, n, d = query_states.shape
         nk = self.num_key_value_heads
         if bs != self.bs or nh != self.nh or d != self.d or key_states.shape != (bs, nk, n, d) or value_states.shape != key_states.shape:
@@ -1465,6 +1531,7 @@ class PagedPQCache(_CacheBase):
         a root - parents[p[0]] == -1, parents[p[k]] == p[k - 1], every node below n_draft[b]; the rows of the path are appended
         in its order (ops.window_commit(dev_rows=)) and n_accept[b] = len(path[b]) (an n_accept given too must say the same).
         After a verify() without a tree, path[b] can only be range(a)."""
+        self._no_wide("commit")
         rec = self._verify_rec
         if path is not None:
             try:
@@ -1581,7 +1648,7 @@ class PagedPQCache(_CacheBase):
         layer_stats = [{"layer_idx": l, "seen_tokens": self.seen_tokens[l], "residual_tokens": self.residualed_tokens[l],
                         "key_cache_tokens": self._T[l], "value_cache_tokens": self._T[l]} for l in range(self.layer_num)]
         mb = 1024 * 1024
-        cache_mb = float(2 * self.num_key_value_heads * self.M * self._T_a.sum()) / mb
+        cache_mb = float(2 * self.num_key_value_heads * self.M * self.key_page_pool.element_size() * self._T_a.sum()) / mb
         resid_mb = sum(c.numel() * c.element_size() for c in self.key_residual_cache + self.value_residual_cache) / mb
         sink_mb = 2 * self.layer_num * self.bs * self.num_key_value_heads * self.sink_tokens * self.d * 2 / mb      # K and V buffers, fp16
         return {"layer_stats": layer_stats, "total_memory_usage_mb": cache_mb + resid_mb + sink_mb,

@@ -30,6 +30,9 @@ class SharedPrefix:
         p, c = prefix_cache, cont_cache
         if getattr(p, "sink_tokens", 0) or getattr(c, "sink_tokens", 0):
             raise NotImplementedError("SharedPrefix: caches with sink_tokens > 0 are not served yet (DESIGN.md 4.13)")
+        for x in (p, c):
+            if getattr(x, "nbits", 8) > 8:
+                raise NotImplementedError(f"SharedPrefix: caches with nbits={x.nbits} (uint16 codes) are not served yet (DESIGN.md 4.14)")
         slot = int(slot)
         if not 0 <= slot < p.bs:
             raise RuntimeError(f"SharedPrefix: slot {slot} outside [0, {p.bs})")
