@@ -21,52 +21,20 @@
 //          d/16 accumulator tiles as before, the running rescale is lane-local;
 //     M/4 + M/4 gathers, d/8 packs and d/32 + d/16 MFMAs per tile and wave; up to 16 query heads per launch (the 16 columns);
 //   * the residual window keeps the LDS tile (one extra workgroup per (b, kv head), as in attn_generic.hip: K rows -> K^ tile ->
-//     scores, V rows -> transposed V^T tile -> values), the fused append included;
-//   * the waves' partials are merged through LDS, the workgroups' through the workspace by the last arriver
-//     (common.h: publish_and_merge), exactly as in the other two kernels.
+//     scores, V rows -> transposed V^T tile -> values), the fused append included (tile_wave.h: window_pass, park_new_row);
+//   * the waves' partials are merged through LDS (tile_wave.h: merge_waves), the workgroups' through the workspace by the last
+//     arriver (common.h: publish_and_merge), exactly as in the other two kernels.
 // Code bytes are read once per kv head (all G = nh / nh_k query heads share a workgroup) straight into registers,
 // kPF tiles ahead; page ids 2 kPF tiles ahead.  V must be in transposed pages (the reference's 10-argument row-major call
 // is transposed first, million_api.hip).
-#include "common.h"
+#include "tile_wave.h"         // the wave-tile skeleton shared with attn_wide.hip: softmax step, window pass, wave merge, split rule
 #include "dev_switches.h"      // MILLION_TILE_PROF (per-tile stamps) is a development switch: never in the product build
 
 namespace million {
 
-typedef _Float16 t8f16 __attribute__((ext_vector_type(8)));
-typedef _Float16 t4f16 __attribute__((ext_vector_type(4)));
-typedef float t4f32 __attribute__((ext_vector_type(4)));
-typedef unsigned t4u __attribute__((ext_vector_type(4)));
-
-// Waves per workgroup (template parameter TW): see plan_attn_tile.  Only the residual-window workgroup uses LDS wave tiles.
-constexpr int kTT = 16;    // tokens per wave tile
-
-template <int D>
-struct TileGeom {
-    static constexpr int kKRow = D * 2 + 16;                    // K^ row stride (bytes): 16 tokens x (d halves + pad)
-    static constexpr int kVRow = kTT * 2 + 16;                  // V^T row stride (bytes): d rows x (16 halves + pad)
-    static constexpr int kTile = (kTT * kKRow > D * kVRow) ? kTT * kKRow : D * kVRow;
-};
-
-// LDS: [region][partial of the workgroup][flag].  region = the two codebooks (code workgroups), reused after the loop as the
-// waves' merge scratch; the residual workgroup (no codebooks) keeps its K^ / V^T wave tiles there.
-static size_t tile_region_bytes(int d, int C, int G, int waves) {
-    const size_t tile = d == 128 ? TileGeom<128>::kTile : TileGeom<64>::kTile;
-    size_t r = 2 * (size_t)d * C * 2;
-    if (waves * tile > r) r = waves * tile;
-    const size_t wf = (size_t)waves * (G * d + 2 * G) * 4;
-    if (wf > r) r = wf;
-    return (r + 15) / 16 * 16;
-}
+// Waves per workgroup (template parameter TW): see plan_attn_tile.  LDS: tile_wave.h, tile_region_bytes.
 static size_t tile_lds_bytes(int d, int C, int slot_floats, int waves, int G) {
-    return tile_region_bytes(d, C, G, waves) + (size_t)slot_floats * 4 + 16;
-}
-
-__device__ __forceinline__ float fast_exp2_tile(float x) { return __builtin_amdgcn_exp2f(x); }   // v_exp_f32: exp2(-inf) = 0
-
-__device__ __forceinline__ void lds_phase() {      // LDS writes of this wave before, LDS reads of this wave after
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");
+    return (size_t)tile_region_bytes(d, C, G, waves) + (size_t)slot_floats * 4 + 16;
 }
 
 template <int D, int DM, int TW, bool LSE = false>      // LSE: common.h, "Log-sum-exp"
@@ -74,12 +42,9 @@ __global__ __launch_bounds__(TW * 64, TW / 4) void attn_tile_kernel(AttnParams p
     constexpr int kTW = TW;
     constexpr int M = D / DM;
     constexpr int NS = D / 32;                 // score stages (32 dims each)
-    constexpr int NC = D / 16;                 // output tiles of 16 dims
     constexpr int KD = M / 16;                 // K code dwords per lane and tile: lane (token, quarter) owns M/4 bytes
     constexpr int CG = M / 16;                 // column groups of 16 subspaces: V code dwords per lane and tile (4 tokens each)
     constexpr int EW = DM >= 2 ? DM / 2 : 1;   // dwords per gathered codebook entry
-    constexpr int NTASK = D / 64;              // residual window: V tasks per lane and tile: (d/2 dim pairs) x (2 token octets) / 64
-    constexpr int kKRow = TileGeom<D>::kKRow, kVRow = TileGeom<D>::kVRow, kTile = TileGeom<D>::kTile;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     MILLION_DEBUG_FILL_LDS(smem, p.lds_fill);
 
@@ -96,12 +61,7 @@ __global__ __launch_bounds__(TW * 64, TW / 4) void attn_tile_kernel(AttnParams p
 
     const int tab_bytes = D * C * 2;
     char *tk = smem, *tv = smem + tab_bytes;
-    char *tile = smem + wave * kTile;          // residual workgroup only (it loads no codebook)
-    int region = 2 * tab_bytes;
-    if (kTW * kTile > region) region = kTW * kTile;
-    if (kTW * (G * D + 2 * G) * 4 > region) region = kTW * (G * D + 2 * G) * 4;
-    region = (region + 15) / 16 * 16;
-    float *part = (float *)(smem + region);
+    float *part = (float *)(smem + tile_region_bytes(D, C, G, kTW));
     int *flag = (int *)(part + p.slot_floats);
 
     const bool is_resid = slot == p.nsplit;
@@ -109,11 +69,7 @@ __global__ __launch_bounds__(TW * 64, TW / 4) void attn_tile_kernel(AttnParams p
     const int t_end = is_resid ? r : min(t_begin + p.split_len, T);
     const int n_tiles = (t_end - t_begin + kTT - 1) / kTT;
 
-    if (p.k_new && is_resid && tid < D) {      // fused append: park the new row in the window (read back from k_new below)
-        const long long o = b * p.res_sb + hk * p.res_sh + (long long)((rstart + r_old) % p.rcap) * D + tid;
-        p.k_res_w[o] = p.k_new[(long long)bh * D + tid];
-        p.v_res_w[o] = p.v_new[(long long)bh * D + tid];
-    }
+    if (p.k_new && is_resid && tid < D) park_new_row<D>(p, b, hk, bh, rstart, r_old, tid);
     if (!is_resid && n_tiles > 0) {
         for (int i = tid * 16; i < tab_bytes; i += kTW * 64 * 16) {
             *(t4u *)(tk + i) = *(const t4u *)((const char *)p.k_tab + i);
@@ -121,74 +77,10 @@ __global__ __launch_bounds__(TW * 64, TW / 4) void attn_tile_kernel(AttnParams p
         }
     }
     t8f16 qb[NS];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        t4u z = {0u, 0u, 0u, 0u};
-        // stage s of lane quarter q4 = dims q4 * D/4 + 8 s .. + 8: the dims of the lane's own code bytes (direct gathers)
-        if (c16 < G) z = *(const t4u *)(p.q + ((long long)b * p.nh + head0(p, hk) + c16) * D + q4 * (D / 4) + 8 * s);
-        qb[s] = __builtin_bit_cast(t8f16, z);
-    }
+    load_query<D>(qb, p.q, (long long)b * p.nh + head0(p, hk), G, q4, c16);
     __syncthreads();
 
-    float m_run = -INFINITY, l_run = 0.f;
-    t4f32 O[NC];
-#pragma unroll
-    for (int n = 0; n < NC; ++n) O[n] = t4f32{0.f, 0.f, 0.f, 0.f};
-
-    // ---- residual window: scores of the K^ tile in LDS ----
-    auto scores_lds = [&]() -> t4f32 {
-        t4f32 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const t4u a = *(const t4u *)(tile + c16 * kKRow + (q4 * (D / 4) + 8 * s) * 2);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(t8f16, a), qb[s], acc, 0, 0, 0);
-        }
-        return acc;
-    };
-    auto softmax_tile = [&](t4f32 acc, int n_valid) -> t4f16 {
-        float sc[4], mx = -INFINITY;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {          // acc[v] = S[token 4*q4 + v][head c16]
-            sc[v] = (4 * q4 + v < n_valid) ? acc[v] * p.scale_log2e : -INFINITY;
-            mx = fmaxf(mx, sc[v]);
-        }
-        // m_run is the softmax reference of head c16, moved (with the cross-lane maximum and the rescale of O, l) only
-        // when a score exceeds it by more than 2^8: the common tile needs no reduction (decode_wave.h: softmax_online_raw)
-        if (__builtin_amdgcn_ballot_w64(mx > m_run + 8.0f)) {      // also the first tile: m_run = -inf, mx finite
-            const float m_new = fmaxf(m_run, rows_max(mx));        // over the four lane rows: all 16 tokens of head c16
-            const float alpha = fast_exp2_tile(m_run - m_new);
-            l_run *= alpha;
-            m_run = m_new;
-            if (__builtin_amdgcn_ballot_w64(alpha != 1.0f)) {
-#pragma unroll
-                for (int n = 0; n < NC; ++n) O[n] *= alpha;        // O^T[dim][head c16]: this lane's own head
-            }
-        }
-        float pe[4], ls = 0.f;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) { pe[v] = fast_exp2_tile(sc[v] - m_run); ls += pe[v]; }
-        l_run += ls;                           // per-lane partial sum; the four lane rows are added once, at the end
-        return t4f16{(_Float16)pe[0], (_Float16)pe[1], (_Float16)pe[2], (_Float16)pe[3]};
-    };
-    // ---- step 5: O^T += V^T P ----
-    auto values = [&](t4f16 P) {
-#pragma unroll
-        for (int n = 0; n < NC; ++n) {
-            const v2u a = *(const v2u *)(tile + (16 * n + c16) * kVRow + (4 * q4) * 2);
-            O[n] = __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(t4f16, a), P, O[n], 0, 0, 0);
-        }
-    };
-    // eight (d0, d1) pairs of consecutive tokens -> the two V^T rows of that dim pair
-    auto store_vt = [&](int dp, int oct, const unsigned (&e)[8]) {
-        t4u lo, hi;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            lo[i] = __builtin_amdgcn_perm(e[2 * i + 1], e[2 * i], 0x05040100u);
-            hi[i] = __builtin_amdgcn_perm(e[2 * i + 1], e[2 * i], 0x07060302u);
-        }
-        *(t4u *)(tile + (2 * dp) * kVRow + oct * 16) = lo;
-        *(t4u *)(tile + (2 * dp + 1) * kVRow + oct * 16) = hi;
-    };
+    WaveAcc<D> run;
 
 #ifdef MILLION_TILE_PROF
     unsigned long long prof_t[5] = {0, 0, 0, 0, 0}, prof_acc[5] = {0, 0, 0, 0, 0};
@@ -204,12 +96,7 @@ __global__ __launch_bounds__(TW * 64, TW / 4) void attn_tile_kernel(AttnParams p
         const int tl = c16, mq = q4;           // step 1 lane roles: token, quarter of the code row
         const int ps_mask = p.page_size - 1;
         struct Codes { unsigned k[KD]; unsigned v[CG]; };      // K: the lane's quarter of its token's code row; V: 4 tokens of subspace 16 cg + c16
-        struct Pids { long long k, v; };
-        auto tile_t0 = [&](int j) {            // first token of this wave's j-th tile (clamped: re-request, never past the split)
-            int ti = wave + kTW * j;
-            if (ti > n_tiles - 1) ti = n_tiles - 1;
-            return t_begin + kTT * ti;
-        };
+        auto tile_t0 = [&](int j) { return wave_tile_t0<kTW>(j, wave, n_tiles, t_begin); };
         // Page ids without a branch around the load (hipcc answers a load in a conditional with s_waitcnt vmcnt(0),
         // which would drain the code prefetch every tile): one 4-byte load of the low dword of the id (ids are < 2^31)
         // from a table chosen before the loop; a side without a table reads a dummy word and ignores it.
@@ -310,7 +197,7 @@ __global__ __launch_bounds__(TW * 64, TW / 4) void attn_tile_kernel(AttnParams p
                     const unsigned sel = (e & 1) ? 0x07060302u : 0x05040100u;
                     const v2u a = {__builtin_amdgcn_perm(v.e[cg][1][e >> 1], v.e[cg][0][e >> 1], sel),
                                    __builtin_amdgcn_perm(v.e[cg][3][e >> 1], v.e[cg][2][e >> 1], sel)};
-                    O[cg * DM + e] = __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(t4f16, a), P, O[cg * DM + e], 0, 0, 0);
+                    run.O[cg * DM + e] = __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(t4f16, a), P, run.O[cg * DM + e], 0, 0, 0);
                 }
         };
 
@@ -342,7 +229,7 @@ __global__ __launch_bounds__(TW * 64, TW / 4) void attn_tile_kernel(AttnParams p
                         const t4f32 acc = scores_direct(cur);
                         const VEnt ve = gather_v(cur);
                         TILE_PROF_T(1);
-                        const t4f16 P = softmax_tile(acc, min(kTT, t_end - t0));
+                        const t4f16 P = softmax_tile(run, acc, min(kTT, t_end - t0), p.scale_log2e, q4);
                         TILE_PROF_T(2);
                         values_direct(ve, P);
                         TILE_PROF_T(3);
@@ -353,38 +240,7 @@ __global__ __launch_bounds__(TW * 64, TW / 4) void attn_tile_kernel(AttnParams p
             }
         }
     } else {
-        // ================= residual window: the same steps, tiles filled from the fp16 rows =================
-        const int tl = c16, mq = q4;
-        const f16 *kres = p.k_res + b * p.res_sb + hk * p.res_sh;
-        const f16 *vres = p.v_res + b * p.res_sb + hk * p.res_sh;
-        auto row_of = [&](int i, const f16 *base, const f16 *fresh) -> const f16 * {      // window row i (clamped to a valid one)
-            if (i > r - 1) i = r - 1;
-            if (fresh && i == r_old) return fresh + (long long)bh * D;
-            return base + (long long)((rstart + i) % p.rcap) * D;
-        };
-        for (int ti = wave; ti < n_tiles; ti += kTW) {
-            const int t0 = kTT * ti;
-            {
-                const f16 *src = row_of(t0 + tl, kres, p.k_new) + mq * (D / 4);
-                char *dst = tile + tl * kKRow + mq * (D / 2);
-#pragma unroll
-                for (int i = 0; i < D / 32; ++i) *(t4u *)(dst + 16 * i) = *(const t4u *)((const char *)src + 16 * i);
-            }
-            lds_phase();
-            const t4f16 P = softmax_tile(scores_lds(), min(kTT, t_end - t0));
-            lds_phase();
-#pragma unroll
-            for (int j = 0; j < NTASK; ++j) {
-                const int task = j * 64 + lane, dp = task >> 1, oct = task & 1;
-                unsigned e[8];
-#pragma unroll
-                for (int t = 0; t < 8; ++t) e[t] = *(const unsigned *)(row_of(t0 + 8 * oct + t, vres, p.v_new) + 2 * dp);
-                store_vt(dp, oct, e);
-            }
-            lds_phase();
-            values(P);
-            lds_phase();
-        }
+        window_pass<D, kTW>(run, qb, p, smem + wave * TileGeom<D>::kTile, b, hk, bh, r, r_old, rstart, wave, lane);
     }
 
 #ifdef MILLION_TILE_PROF
@@ -394,43 +250,7 @@ __global__ __launch_bounds__(TW * 64, TW / 4) void attn_tile_kernel(AttnParams p
         o[5] = __builtin_amdgcn_s_memtime() - prof_start;
     }
 #endif
-    // ---- merge the waves' partials through LDS, then hand the workgroup's partial over ----
-    __syncthreads();
-    {
-        const int wf = G * D + 2 * G;                         // floats per wave
-        const float l_sum = rows_sum(l_run);
-        float *ws = (float *)smem + wave * wf;                 // the codebooks / wave tiles are dead (barrier above)
-        if (c16 < G) {
-#pragma unroll
-            for (int n = 0; n < NC; ++n)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    // code workgroups: tile n = (column group n / d_m, dim e = n % d_m), row = subspace 16 cg + 4 q4 + v;
-                    // residual workgroup: tile n = dims 16 n .. 16 n + 15
-                    const int dim = is_resid ? 16 * n + 4 * q4 + v : (16 * (n / DM) + 4 * q4 + v) * DM + n % DM;
-                    ws[c16 * D + dim] = O[n][v];
-                }
-            if (q4 == 0) { ws[G * D + c16] = m_run; ws[G * D + G + c16] = l_sum; }
-        }
-        __syncthreads();
-        const float *w0 = (const float *)smem;
-        for (int e = tid; e < wf; e += kTW * 64) {            // e: O[g][dim], then m[g], then l[g]
-            const int g = e < G * D ? e / D : (e - G * D) % G;
-            float mm = -INFINITY;
-#pragma unroll
-            for (int w = 0; w < kTW; ++w) mm = fmaxf(mm, w0[w * wf + G * D + g]);
-            const float ms = mm > -INFINITY ? mm : 0.f;
-            float o = mm;
-            if (e < G * D || e >= G * D + G) {
-                o = 0.f;
-#pragma unroll
-                for (int w = 0; w < kTW; ++w) o += w0[w * wf + e] * exp2f(w0[w * wf + G * D + g] - ms);
-            }
-            part[e] = o;
-        }
-        __syncthreads();
-    }
-    // merge scratch of the last arriver: the waves' partials above are dead once `part` is complete (barrier above)
+    merge_waves<D, DM, kTW>(run, (float *)smem, part, G, is_resid, tid);
     publish_and_merge<LSE>(p, b, hk, slot, part, (float *)smem, flag);
 }
 
@@ -459,26 +279,13 @@ bool plan_attn_tile(const AttnParams &p_in, AttnPlan &plan) {
     // workgroups fit - one per CU at d = 128 - and the registers how many waves: 16 where the kernel stays within 128
     // registers (d = 64; d = 128 with 16-byte entries), 8 otherwise).  More waves = fewer 16-token tiles per wave and more
     // LDS round trips in flight.
-    const int bh = p.bs * p.nh_k;
-    const int cus = device_cus();
     const int waves = (p.d == 64 || p.dm == 8) ? 16 : 8;
     // split policy: one workgroup per CU - the residual-window workgroup of every (b, kv head) included (rounds 2-3 sized the
     // splits for all CUs and launched bh more workgroups than the chip holds at d = 128: the last ones started when the first
-    // finished); a split is a multiple of 64 tokens and at least 256 tokens long
-    int ns = cus > 2 * bh ? (cus - bh) / bh : (cus + bh - 1) / bh;
-    if (ns > kMaxSplits) ns = kMaxSplits;
-    int by_len = (p.T + 255) / 256;
-    if (by_len < 1) by_len = 1;
-    if (ns > by_len) ns = by_len;
-    int len = (p.T + ns - 1) / ns;
-    len = (len + 63) / 64 * 64;
-    if (len < 64) len = 64;
-    ns = p.T > 0 ? (p.T + len - 1) / len : 1;
-    p.nsplit = ns;
-    p.split_len = len;
-    p.nslots = ns + 1;
+    // finished)
+    split_by_room(p, device_cus());
     const size_t lds = tile_lds_bytes(p.d, p.C, p.slot_floats, waves, p.G);
-    plan = {(p.lse ? kTileKernelsLse : kTileKernels)[p.d == 64][p.M == 16 ? 0 : p.M == 32 ? 1 : 2], dim3(p.nslots, bh), dim3(waves * 64), lds, p, 3, tile_setup};
+    plan = {(p.lse ? kTileKernelsLse : kTileKernels)[p.d == 64][p.M == 16 ? 0 : p.M == 32 ? 1 : 2], dim3(p.nslots, p.bs * p.nh_k), dim3(waves * 64), lds, p, 3, tile_setup};
     return true;
 }
 

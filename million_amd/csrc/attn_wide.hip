@@ -1,12 +1,10 @@
 // attn_wide.hip — fused decode attention over 16-bit PQ codes (512 .. 4096 centroids per subspace) in page pools, gfx950 / CDNA4.
 //
-// Same job and same single launch as attn_tile.hip, whose structure this kernel keeps: a wave walks 16-token tiles on its own,
-// a lane's gathered codebook entries ARE the MFMA operands (scores: v_mfma_f32_16x16x32_f16, A = 8 dims of the lane's quarter
-// of the K^ row; values: v_mfma_f32_16x16x16_f16, A = one dim of 16 subspaces x 16 tokens, B = the probabilities), up to 16
-// query heads are the 16 columns, the residual window runs as one more workgroup per (b, kv head) through an LDS tile, the
-// waves' partials merge through LDS and the workgroups' through the workspace (common.h: publish_and_merge, unchanged).
+// Same job and same single launch as attn_tile.hip, and the same wave-tile skeleton (tile_wave.h: lane roles, softmax step,
+// residual-window pass, wave merge, split rule): a lane's gathered codebook entries ARE the MFMA operands (scores: A = 8 dims of
+// the lane's quarter of the K^ row; values: A = one dim of 16 subspaces x 16 tokens, B = the probabilities).
 //
-// The one structural difference: a table is C * d * 2 bytes = 128 KiB .. 1 MiB, so no codebook is in LDS.  Both tables are the
+// What is this kernel's own: a table is C * d * 2 bytes = 128 KiB .. 1 MiB, so no codebook is in LDS.  Both tables are the
 // plain (M, C, d_m) fp16 tensors in global memory (resident in L2 / the Infinity Cache: every workgroup gathers from the same
 // two) and every entry is one global load of the whole sub-vector: 4 bytes at d_m = 2, 8 bytes at d_m = 4.  The gathers of
 // tile j + 1 are issued before tile j is computed (its entries were requested one iteration earlier), the code words kPF
@@ -20,53 +18,20 @@
 //   K  lane (token c16, quarter q4): the M/4 codes [q4 M/4, (q4 + 1) M/4) of its token's row = dims [q4 d/4, (q4 + 1) d/4)
 //   V  lane (tokens 4 q4 .. 4 q4 + 3, subspace 16 cg + c16): 4 codes (8 bytes of a transposed page row) per column group cg
 //   O  tile n = (cg = n / d_m, e = n % d_m): O^T[(16 cg + 4 q4 + v) d_m + e][head c16]
-#include "common.h"
+#include "tile_wave.h"
 
 namespace million {
 
-typedef _Float16 w8f16 __attribute__((ext_vector_type(8)));
-typedef _Float16 w4f16 __attribute__((ext_vector_type(4)));
-typedef float w4f32 __attribute__((ext_vector_type(4)));
-typedef unsigned w4u __attribute__((ext_vector_type(4)));
-
-constexpr int kWT = 16;     // tokens per wave tile
 constexpr int kWW = 8;      // waves per workgroup
 constexpr int kWidePF = 2;  // code tiles in flight per wave
-
-template <int D>
-struct WideGeom {
-    static constexpr int kKRow = D * 2 + 16;                    // window K^ row stride (bytes)
-    static constexpr int kVRow = kWT * 2 + 16;                  // window V^T row stride (bytes)
-    static constexpr int kTile = (kWT * kKRow > D * kVRow) ? kWT * kKRow : D * kVRow;
-};
-
-// LDS: [region][partial of the workgroup][flag].  region = the window workgroup's K^ / V^T wave tiles, then the waves' merge
-// scratch, then the last arriver's (common.h merge_vec4: 512 weights + 2048 floats)
-__host__ __device__ inline int wide_region_bytes(int d, int G) {
-    int r = kWW * (d == 128 ? WideGeom<128>::kTile : WideGeom<64>::kTile);
-    const int wf = kWW * (G * d + 2 * G) * 4;
-    if (wf > r) r = wf;
-    if (r < 16 * 1024) r = 16 * 1024;
-    return (r + 15) / 16 * 16;
-}
-
-__device__ __forceinline__ float wide_exp2(float x) { return __builtin_amdgcn_exp2f(x); }      // exp2(-inf) = 0
-__device__ __forceinline__ void wide_lds_phase() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");
-}
 
 template <int D, int DM, bool LSE = false>
 __global__ __launch_bounds__(kWW * 64, 2) void attn_wide_kernel(AttnParams p) {
     constexpr int M = D / DM;
     constexpr int NS = D / 32;                 // score stages (32 dims each)
-    constexpr int NC = D / 16;                 // output tiles of 16 dims
     constexpr int KD = M / 8;                  // K code dwords per lane and tile (M/4 codes of 16 bits)
     constexpr int CG = M / 16;                 // column groups of 16 subspaces
     constexpr int EW = DM / 2;                 // dwords per codebook entry
-    constexpr int NTASK = D / 64;
-    constexpr int kKRow = WideGeom<D>::kKRow, kVRow = WideGeom<D>::kVRow, kTile = WideGeom<D>::kTile;
     static_assert(DM == 2 || DM == 4, "entries of 4 or 8 bytes");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     MILLION_DEBUG_FILL_LDS(smem, p.lds_fill);
@@ -82,70 +47,26 @@ __global__ __launch_bounds__(kWW * 64, 2) void attn_wide_kernel(AttnParams p) {
     const int r_old = r;
     if (p.k_new) r += 1;                           // fused append: the new token is window row r_old
 
-    char *tile = smem + wave * kTile;              // window workgroup only
-    float *part = (float *)(smem + wide_region_bytes(D, G));
+    float *part = (float *)(smem + wide_region_bytes(D, G, kWW));
     int *flag = (int *)(part + p.slot_floats);
 
     const bool is_resid = slot == p.nsplit;
     const int t_begin = is_resid ? 0 : min(slot * p.split_len, T);
     const int t_end = is_resid ? r : min(t_begin + p.split_len, T);
-    const int n_tiles = (t_end - t_begin + kWT - 1) / kWT;
+    const int n_tiles = (t_end - t_begin + kTT - 1) / kTT;
 
-    if (p.k_new && is_resid && tid < D) {          // fused append: park the new row in the window (read back from k_new below)
-        const long long o = b * p.res_sb + hk * p.res_sh + (long long)((rstart + r_old) % p.rcap) * D + tid;
-        p.k_res_w[o] = p.k_new[(long long)bh * D + tid];
-        p.v_res_w[o] = p.v_new[(long long)bh * D + tid];
-    }
-    w8f16 qb[NS];
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        w4u z = {0u, 0u, 0u, 0u};
-        if (c16 < G) z = *(const w4u *)(p.q + ((long long)b * p.nh + head0(p, hk) + c16) * D + q4 * (D / 4) + 8 * s);
-        qb[s] = __builtin_bit_cast(w8f16, z);
-    }
-
-    float m_run = -INFINITY, l_run = 0.f;
-    w4f32 O[NC];
-#pragma unroll
-    for (int n = 0; n < NC; ++n) O[n] = w4f32{0.f, 0.f, 0.f, 0.f};
-
-    auto softmax_tile = [&](w4f32 acc, int n_valid) -> w4f16 {
-        float sc[4], mx = -INFINITY;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {              // acc[v] = S[token 4 q4 + v][head c16]
-            sc[v] = (4 * q4 + v < n_valid) ? acc[v] * p.scale_log2e : -INFINITY;
-            mx = fmaxf(mx, sc[v]);
-        }
-        // the reference maximum of head c16 moves only when a score exceeds it by more than 2^8 (attn_tile.hip)
-        if (__builtin_amdgcn_ballot_w64(mx > m_run + 8.0f)) {
-            const float m_new = fmaxf(m_run, rows_max(mx));
-            const float alpha = wide_exp2(m_run - m_new);
-            l_run *= alpha;
-            m_run = m_new;
-            if (__builtin_amdgcn_ballot_w64(alpha != 1.0f)) {
-#pragma unroll
-                for (int n = 0; n < NC; ++n) O[n] *= alpha;
-            }
-        }
-        float pe[4], ls = 0.f;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) { pe[v] = wide_exp2(sc[v] - m_run); ls += pe[v]; }
-        l_run += ls;
-        return w4f16{(_Float16)pe[0], (_Float16)pe[1], (_Float16)pe[2], (_Float16)pe[3]};
-    };
+    if (p.k_new && is_resid && tid < D) park_new_row<D>(p, b, hk, bh, rstart, r_old, tid);
+    t8f16 qb[NS];
+    load_query<D>(qb, p.q, (long long)b * p.nh + head0(p, hk), G, q4, c16);
+    WaveAcc<D> run;
 
     if (!is_resid) {
         // ================= code tiles =================
         const int ps_mask = p.page_size - 1;
         struct Codes { unsigned k[KD]; unsigned v[CG][2]; };
-        struct Pids { long long k, v; };
         struct Ent { unsigned k[D / 8]; unsigned v[CG][4][EW]; };      // the lane's d/4 dims of K^; 4 tokens x CG sub-vectors of V^
         const unsigned short *kc = (const unsigned short *)p.k_codes, *vc = (const unsigned short *)p.v_codes;
-        auto tile_t0 = [&](int j) {                // first token of this wave's j-th tile (clamped: re-request, never past the split)
-            int ti = wave + kWW * j;
-            if (ti > n_tiles - 1) ti = n_tiles - 1;
-            return t_begin + kWT * ti;
-        };
+        auto tile_t0 = [&](int j) { return wave_tile_t0<kWW>(j, wave, n_tiles, t_begin); };
         const int *kid_base = p.ids64 ? (const int *)p.k_ids64 : p.k_ids32;      // low dword of an id (ids are < 2^31)
         const int *vid_base = p.ids64 ? (const int *)p.v_ids64 : p.v_ids32;
         const int id_stride = p.ids64 ? 2 : 1;
@@ -164,7 +85,7 @@ __global__ __launch_bounds__(kWW * 64, 2) void attn_wide_kernel(AttnParams p) {
             else {
 #pragma unroll
                 for (int i = 0; i < KD / 4; ++i) {
-                    const w4u w = *(const w4u *)(krow + 8 * i);
+                    const t4u w = *(const t4u *)(krow + 8 * i);
                     c.k[4 * i] = w[0]; c.k[4 * i + 1] = w[1]; c.k[4 * i + 2] = w[2]; c.k[4 * i + 3] = w[3];
                 }
             }
@@ -199,16 +120,16 @@ __global__ __launch_bounds__(kWW * 64, 2) void attn_wide_kernel(AttnParams p) {
                 }
             return e;
         };
-        auto scores_direct = [&](const Ent &e) -> w4f32 {
-            w4f32 acc = {0.f, 0.f, 0.f, 0.f};
+        auto scores_direct = [&](const Ent &e) -> t4f32 {
+            t4f32 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int st = 0; st < NS; ++st) {      // stage st = dims q4 d/4 + 8 st .. + 8 = dwords 4 st .. 4 st + 3 of the lane's K^ quarter
-                const w4u a = {e.k[4 * st], e.k[4 * st + 1], e.k[4 * st + 2], e.k[4 * st + 3]};
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(w8f16, a), qb[st], acc, 0, 0, 0);
+                const t4u a = {e.k[4 * st], e.k[4 * st + 1], e.k[4 * st + 2], e.k[4 * st + 3]};
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(t8f16, a), qb[st], acc, 0, 0, 0);
             }
             return acc;
         };
-        auto values_direct = [&](const Ent &e, w4f16 P) {
+        auto values_direct = [&](const Ent &e, t4f16 P) {
 #pragma unroll
             for (int cg = 0; cg < CG; ++cg)
 #pragma unroll
@@ -216,7 +137,7 @@ __global__ __launch_bounds__(kWW * 64, 2) void attn_wide_kernel(AttnParams p) {
                     const unsigned sel = (x & 1) ? 0x07060302u : 0x05040100u;
                     const v2u a = {__builtin_amdgcn_perm(e.v[cg][1][x >> 1], e.v[cg][0][x >> 1], sel),
                                    __builtin_amdgcn_perm(e.v[cg][3][x >> 1], e.v[cg][2][x >> 1], sel)};
-                    O[cg * DM + x] = __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(w4f16, a), P, O[cg * DM + x], 0, 0, 0);
+                    run.O[cg * DM + x] = __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(t4f16, a), P, run.O[cg * DM + x], 0, 0, 0);
                 }
         };
 
@@ -243,98 +164,17 @@ __global__ __launch_bounds__(kWW * 64, 2) void attn_wide_kernel(AttnParams p) {
                     ent = gather(ring[(k + 1) % kPF]);                    // tile j + 1 (a clamped re-request past the last one)
                     if (j < my_tiles) {                                   // wave-uniform; no global load inside
                         const int t0 = tile_t0(j);
-                        const w4f32 acc = scores_direct(cur);
-                        const w4f16 P = softmax_tile(acc, min(kWT, t_end - t0));
+                        const t4f32 acc = scores_direct(cur);
+                        const t4f16 P = softmax_tile(run, acc, min(kTT, t_end - t0), p.scale_log2e, q4);
                         values_direct(cur, P);
                     }
                 }
             }
         }
     } else {
-        // ================= residual window: the LDS tile of attn_tile.hip, filled from the fp16 rows =================
-        const f16 *kres = p.k_res + b * p.res_sb + hk * p.res_sh;
-        const f16 *vres = p.v_res + b * p.res_sb + hk * p.res_sh;
-        auto row_of = [&](int i, const f16 *base, const f16 *fresh) -> const f16 * {      // window row i (clamped to a valid one)
-            if (i > r - 1) i = r - 1;
-            if (fresh && i == r_old) return fresh + (long long)bh * D;
-            return base + (long long)((rstart + i) % p.rcap) * D;
-        };
-        for (int ti = wave; ti < n_tiles; ti += kWW) {
-            const int t0 = kWT * ti;
-            {
-                const f16 *src = row_of(t0 + c16, kres, p.k_new) + q4 * (D / 4);
-                char *dst = tile + c16 * kKRow + q4 * (D / 2);
-#pragma unroll
-                for (int i = 0; i < D / 32; ++i) *(w4u *)(dst + 16 * i) = *(const w4u *)((const char *)src + 16 * i);
-            }
-            wide_lds_phase();
-            w4f32 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                const w4u a = *(const w4u *)(tile + c16 * kKRow + (q4 * (D / 4) + 8 * s) * 2);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(w8f16, a), qb[s], acc, 0, 0, 0);
-            }
-            const w4f16 P = softmax_tile(acc, min(kWT, t_end - t0));
-            wide_lds_phase();
-#pragma unroll
-            for (int j = 0; j < NTASK; ++j) {      // eight (d0, d1) pairs of consecutive tokens -> the two V^T rows of that dim pair
-                const int task = j * 64 + lane, dp = task >> 1, oct = task & 1;
-                unsigned e[8];
-#pragma unroll
-                for (int t = 0; t < 8; ++t) e[t] = *(const unsigned *)(row_of(t0 + 8 * oct + t, vres, p.v_new) + 2 * dp);
-                w4u lo, hi;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    lo[i] = __builtin_amdgcn_perm(e[2 * i + 1], e[2 * i], 0x05040100u);
-                    hi[i] = __builtin_amdgcn_perm(e[2 * i + 1], e[2 * i], 0x07060302u);
-                }
-                *(w4u *)(tile + (2 * dp) * kVRow + oct * 16) = lo;
-                *(w4u *)(tile + (2 * dp + 1) * kVRow + oct * 16) = hi;
-            }
-            wide_lds_phase();
-#pragma unroll
-            for (int n = 0; n < NC; ++n) {
-                const v2u a = *(const v2u *)(tile + (16 * n + c16) * kVRow + (4 * q4) * 2);
-                O[n] = __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(w4f16, a), P, O[n], 0, 0, 0);
-            }
-            wide_lds_phase();
-        }
+        window_pass<D, kWW>(run, qb, p, smem + wave * TileGeom<D>::kTile, b, hk, bh, r, r_old, rstart, wave, lane);
     }
-
-    // ---- merge the waves' partials through LDS, then hand the workgroup's partial over ----
-    __syncthreads();
-    {
-        const int wf = G * D + 2 * G;                         // floats per wave
-        const float l_sum = rows_sum(l_run);
-        float *ws = (float *)smem + wave * wf;                 // the wave tiles are dead (barrier above)
-        if (c16 < G) {
-#pragma unroll
-            for (int n = 0; n < NC; ++n)
-#pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const int dim = is_resid ? 16 * n + 4 * q4 + v : (16 * (n / DM) + 4 * q4 + v) * DM + n % DM;
-                    ws[c16 * D + dim] = O[n][v];
-                }
-            if (q4 == 0) { ws[G * D + c16] = m_run; ws[G * D + G + c16] = l_sum; }
-        }
-        __syncthreads();
-        const float *w0 = (const float *)smem;
-        for (int e = tid; e < wf; e += kWW * 64) {            // e: O[g][dim], then m[g], then l[g]
-            const int g = e < G * D ? e / D : (e - G * D) % G;
-            float mm = -INFINITY;
-#pragma unroll
-            for (int w = 0; w < kWW; ++w) mm = fmaxf(mm, w0[w * wf + G * D + g]);
-            const float ms = mm > -INFINITY ? mm : 0.f;
-            float o = mm;
-            if (e < G * D || e >= G * D + G) {
-                o = 0.f;
-#pragma unroll
-                for (int w = 0; w < kWW; ++w) o += w0[w * wf + e] * exp2f(w0[w * wf + G * D + g] - ms);
-            }
-            part[e] = o;
-        }
-        __syncthreads();
-    }
+    merge_waves<D, DM, kWW>(run, (float *)smem, part, G, is_resid, tid);
     publish_and_merge<LSE>(p, b, hk, slot, part, (float *)smem, flag);
 }
 
@@ -363,22 +203,9 @@ bool plan_attn_wide(const AttnParams &p_in, AttnPlan &plan) {
     // split policy: the registers decide how many workgroups of 8 waves a CU holds (no codebook is in LDS): one at d = 128
     // (two tiles of entries in flight: ~200 VGPRs), two at d = 64; the splits of all (b, kv head) pairs and their window
     // workgroups fill that once.  A split is a multiple of 64 tokens and at least 256 tokens long.
-    const int bh = p.bs * p.nh_k;
-    const int room = (p.d == 64 ? 2 : 1) * device_cus();
-    int ns = room > 2 * bh ? (room - bh) / bh : (room + bh - 1) / bh;
-    if (ns > kMaxSplits) ns = kMaxSplits;
-    int by_len = (p.T + 255) / 256;
-    if (by_len < 1) by_len = 1;
-    if (ns > by_len) ns = by_len;
-    int len = (p.T + ns - 1) / ns;
-    len = (len + 63) / 64 * 64;
-    if (len < 64) len = 64;
-    ns = p.T > 0 ? (p.T + len - 1) / len : 1;
-    p.nsplit = ns;
-    p.split_len = len;
-    p.nslots = ns + 1;
-    const size_t lds = (size_t)wide_region_bytes(p.d, p.G) + (size_t)p.slot_floats * 4 + 16;
-    plan = {kWideKernels[p.d == 64][p.dm == 4][p.lse ? 1 : 0], dim3(p.nslots, bh), dim3(kWW * 64), lds, p, 6, wide_setup};
+    split_by_room(p, (p.d == 64 ? 2 : 1) * device_cus());
+    const size_t lds = (size_t)wide_region_bytes(p.d, p.G, kWW) + (size_t)p.slot_floats * 4 + 16;
+    plan = {kWideKernels[p.d == 64][p.dm == 4][p.lse ? 1 : 0], dim3(p.nslots, p.bs * p.nh_k), dim3(kWW * 64), lds, p, 6, wide_setup};
     return true;
 }
 
