@@ -21,6 +21,9 @@
 //                   256  no exponentials, 512 no tile DMA behind the prologue, 1024 no tile wait/barrier  profiles/r05_prefill.txt
 //                  2048  per-phase shader-clock sums of workgroup 0's waves, written into their own query rows (tools/prefill_prof.py)
 //                 16384  only waves 0 - 3 compute (one computing wave per SIMD; its partner issues DMA and joins barriers)
+//                 32768  a computing wave sleeps about 17 us (five s_sleep 127; no loop, no memory) between the prologue barrier and
+//                        its first read of K half 0: a request into quarter 0 that no barrier holds back lands first, every
+//                        time                                                                      profiles/prefill_prologue_race.txt
 //   MILLION_TILE_PROF      attn_tile.hip: per-tile shader-clock stamps (tools/tile_prof.py)
 //   MILLION_DEV_M32_PACKED() run-time A/B (environment MILLION_M32_PACKED=1, dev builds only): M = 32 keeps the packed value form
 //                          at up to 4 query heads per kv head too (the product build takes the d_m = 4 form there and the

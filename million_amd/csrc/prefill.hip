@@ -32,7 +32,8 @@
 
 #include "dev_switches.h"  // MILLION_EXP: development ablation switches of the pipelined kernel (tools/ab_build.py, tools/pf_ab.sh);
                            // 0 in the product build: 4 no value products, 8 no score products, 256 no exponentials, 512 no tile
-                           // DMA, 1024 no tile wait / barrier, 2048 phase clock, 16384 one computing wave per SIMD
+                           // DMA, 1024 no tile wait / barrier, 2048 phase clock, 16384 one computing wave per SIMD, 32768 computing
+                           // waves sleep behind the prologue barrier
 
 namespace million {
 
@@ -362,6 +363,11 @@ __global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_pipe_kernel(Prefi
     __syncthreads();
     v16f SA, SB;      // raw scores: of the current half / accumulating the next one (roles swap every half-step)
     bool cur_live = live(0);
+#if MILLION_EXP & 32768
+    // diagnostic: a computing wave reaches its first read of K half 0 some 17 us behind the prologue barrier (5 x 8128 clocks;
+    // no loop, no memory) - whatever an idle wave may write into quarter 0 before that read has landed by then
+    if (cur_live) asm volatile("s_sleep 127\n\ts_sleep 127\n\ts_sleep 127\n\ts_sleep 127\n\ts_sleep 127" ::: "memory");
+#endif
     if (cur_live) {      // scores of half 0 (plain), mask, reference
 #pragma unroll
         for (int s = 0; s < DS; ++s)
@@ -373,9 +379,19 @@ __global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_pipe_kernel(Prefi
         for (int j = 1; j < 16; ++j) mx = fmaxf(mx, SA[j]);
         decide(mx, SA);
     }
+    // The prologue's read of quarter 0 (K half 0) and the first burst's write into it (K half 4) need a barrier of their own: a
+    // wave without rows skips the scores above (and any wave may be through them first) and would otherwise request half 4 while
+    // its neighbours still multiply against half 0 (profiles/prefill_prologue_race.txt).  Every wave joins: nothing above
+    // leaves the kernel but the workgroup-uniform wg_live exit.
+    __syncthreads();
     // One half-step: half h (scores in C, reference decided; its V rows: buffer HQ >> 1, half HQ & 1) and half h + 1 (scores into N;
     // its K rows: quarter (HQ + 1) & 3).  HQ = h & 3 is a compile-time constant: the tile loop is unrolled by two.
-    // iteration t: half-steps 2 t and 2 t + 1; its DMA: K halves 2 t + 3, 2 t + 4 (quarters last read in iteration t - 1) and V tile t + 1
+    // iteration t: half-steps 2 t and 2 t + 1; its DMA: K halves 2 t + 3, 2 t + 4 and V tile t + 1.  The rule: between the last read
+    // of a region (a K quarter, a V buffer) and the next request into it stands a barrier that every wave joins.  Quarter (2 t + 3) & 3
+    // was last read by half-step 2 t - 2 (half 2 t - 1), quarter (2 t + 4) & 3 by half-step 2 t - 1 (half 2 t) and V buffer (t + 1) & 1
+    // by both (tile t - 1): all in iteration t - 1, in front of its PF_SYNC.  For t = 0 there is no such iteration: quarter 3 and V
+    // buffer 1 have never been read, and quarter 0 was read by the prologue's scores of half 0 - in front of the barrier above.
+    // (tests/test_prefill_schedule_host.py restates this schedule and checks the rule for every tile count.)
 #if MILLION_EXP & 512
 #define PF_DMA(T) (void)0
 #else

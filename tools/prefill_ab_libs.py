@@ -68,7 +68,8 @@ def timed(fn, reps):
 
 
 lines = [f"A = {args.lib_a}   B = {args.lib_b}   (TFLOP/s = 2 d nh n (n + 1) / time; rounds alternate A, B)"]
-for (bs, nh, nhk, n) in ((1, 32, 8, 4096), (1, 32, 8, 32768), (1, 32, 32, 32768), (1, 32, 8, 131072)):
+# n = 512: short prompts, where what a workgroup does once (prologue, barriers outside the tile loop) weighs most
+for (bs, nh, nhk, n) in ((1, 32, 8, 512), (16, 32, 8, 512), (1, 32, 8, 4096), (1, 32, 8, 32768), (1, 32, 32, 32768), (1, 32, 8, 131072)):
     if args.n is not None and n != args.n:
         continue
     d = 128
@@ -78,11 +79,11 @@ for (bs, nh, nhk, n) in ((1, 32, 8, 4096), (1, 32, 8, 32768), (1, 32, 32, 32768)
     ms = [[], []]
     for _ in range(args.rounds):
         for i, lib in enumerate(libs):
-            ms[i].append(timed(lambda: call(lib, q, k, v, outs[i]), 20 if n <= 4096 else 5 if n <= 32768 else 3))
+            ms[i].append(timed(lambda: call(lib, q, k, v, outs[i]), 100 if n <= 512 else 20 if n <= 4096 else 5 if n <= 32768 else 3))
     diff = (outs[0].float() - outs[1].float()).abs().max().item()
     tf = [[flops / t / 1e9 for t in m] for m in ms]
     best = [max(t) for t in tf]
-    lines.append(f"n={n:6d} nh_k={nhk:2d}:  A best {best[0]:7.1f} ({' '.join('%.0f' % x for x in tf[0])})   B best {best[1]:7.1f} "
+    lines.append(f"n={n:6d} bs={bs:2d} nh_k={nhk:2d}:  A best {best[0]:7.1f} ({' '.join('%.0f' % x for x in tf[0])})   B best {best[1]:7.1f} "
                  f"({' '.join('%.0f' % x for x in tf[1])})   B / A {best[1] / best[0] - 1:+.1%}   max |A - B| {diff:.2e}   "
                  f"bands A {min(tf[0]):.1f} .. {max(tf[0]):.1f}  B {min(tf[1]):.1f} .. {max(tf[1]):.1f}")
     print(lines[-1], flush=True)
