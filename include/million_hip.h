@@ -636,6 +636,32 @@ int million_pq_chunk_attn_lse(const million_chunk_attn_desc *desc, const void *q
                               const void *v_resid, void *out, float *lse, void *workspace, size_t workspace_bytes,
                               million_stream_t stream);
 
+/* Chunk attention over 16-bit PQ codes (nbits 9 .. 12): million_pq_chunk_attn's job, word for word - the same descriptor, the
+ * same Kall, masks, ragged fields (dev_lengths / dev_n_q), split rule, workspace formula and merge - with another code producer.
+ *   Codes:     uint16.  Each side row-major (bs, nh_k, T_cap, M) or a page pool (K (n_pool, page_size, M), V (n_pool, M,
+ *              page_size) transposed; pages of 32 / 64 / 128 tokens; int32 or int64 ids); the sides may differ.  Row-major
+ *              k_stride_* / v_stride_* stay in BYTES; rows are 2 M bytes.
+ *   Codebooks: k_cents / v_cents are the plain (M, C, d_m) fp16 tensors in global memory (there is no prepared image and no
+ *              codebook in LDS); every entry is one aligned load of 2 d_m bytes, and the dequantised tile is the gather of
+ *              million_pq_decode, bit for bit.
+ *   Shapes:    C in {512, 1024, 2048, 4096}, d in {128, 64}, d_m = d / M in {2, 4}.  Anything else - C <= 256 (that is
+ *              million_pq_chunk_attn's), another C, d_m 1 or 8, another d - is MILLION_ERR_SHAPE before any launch.
+ *   Mask:      EVERY gathered index is code & (C - 1); this is part of the contract.  Code words at or past T_b, row-major
+ *              padding, page tails, pool pages that no live table entry names and page-table entries past a request's live
+ *              pages may hold any bits (with everything the uint8 entry lists: window rows outside the ring span, q and chunk
+ *              rows at or past n_q[b], the workspace, out): none of them changes a bit of out or lse, and none sends a load
+ *              outside a table.  Page ids of live pages are trusted.
+ *   Pointer, alignment, capacity and workspace checks (MILLION_ERR_ARG / _ALIGN / _WORKSPACE) are the uint8 entry's.  lse may
+ *   be NULL; out with lse is bitwise out without it.  S and the workspace are million_chunk_attn_workspace_bytes' function of
+ *   the descriptor (C is not read by it): with codes < 256 and a table whose first 256 entries per subspace are a C = 256
+ *   table, out and lse are bitwise those of million_pq_chunk_attn.  0 from the workspace function: the descriptor is refused. */
+size_t million_chunk_attn_wide_workspace_bytes(const million_chunk_attn_desc *desc);
+int million_pq_chunk_attn_wide(const million_chunk_attn_desc *desc, const void *q, const void *k_chunk, const void *v_chunk,
+                               const void *k_codes, const void *v_codes, const void *k_page_ids, const void *v_page_ids,
+                               const void *k_cents, const void *v_cents, const void *k_resid, const void *v_resid,
+                               void *out, float *lse /* may be NULL */, void *workspace, size_t workspace_bytes,
+                               million_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Merge of partial attentions: n_parts results (out_i, lse_i) of one query over disjoint key sets -> the result over
  * their union.  Per row:  L = max_i lse_i,  w_i = exp(lse_i - L) (0 for -inf),  out = sum w_i out_i / sum w_i in fp32,

@@ -1,5 +1,5 @@
 // flash_tile.h — the flash-attention tile step shared by the prompt-attention kernels (prefill.hip: prefill_attn_kernel, and in
-// part prefill_attn_pipe_kernel) and the chunk-attention kernel (chunk_attn.hip), gfx950.
+// part prefill_attn_pipe_kernel) and the chunk-attention kernels (chunk_attn.h: chunk_attn.hip, chunk_attn_wide.hip), gfx950.
 //
 // Everything is computed TRANSPOSED so that a query row lives on a lane: S^T = K Q^T (A = K rows from LDS, B = Q^T from
 // registers, v_mfma_f32_32x32x16_f16): lane (q, h) = lane 32 h + q holds 16 of a 32-key block's scores of query row q; the

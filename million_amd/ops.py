@@ -916,9 +916,9 @@ def chunk_attn_desc(q, k_res, *, nh_k, M, C, n_tokens, r, n_c, resid_start=0, k_
     desc.v_layout = L.MILLION_KV_PAGED if v_paged else L.MILLION_KV_ROWMAJOR
     desc.page_size, desc.n_pages_cap, desc.page_ids_i64 = page_size, n_pages_cap, int(page_ids_i64)
     if not k_paged and k_codes is not None:
-        desc.k_stride_b, desc.k_stride_h = k_codes.stride(0), k_codes.stride(1)
+        desc.k_stride_b, desc.k_stride_h = (k_codes.stride(i) * k_codes.element_size() for i in (0, 1))      # bytes
     if not v_paged and v_codes is not None:
-        desc.v_stride_b, desc.v_stride_h = v_codes.stride(0), v_codes.stride(1)
+        desc.v_stride_b, desc.v_stride_h = (v_codes.stride(i) * v_codes.element_size() for i in (0, 1))
     desc.q_stride_b, desc.q_stride_h, desc.q_stride_n = q.stride(0), q.stride(1), q.stride(2)
     if k_chunk is not None:
         desc.kc_stride_b, desc.kc_stride_h, desc.kc_stride_n = k_chunk.stride(0), k_chunk.stride(1), k_chunk.stride(2)
@@ -934,6 +934,117 @@ def chunk_attn_desc(q, k_res, *, nh_k, M, C, n_tokens, r, n_c, resid_start=0, k_
 
 def chunk_attn_workspace_bytes(desc: L.ChunkAttnDesc) -> int:
     return int(L.load().million_chunk_attn_workspace_bytes(ctypes.byref(desc)))
+
+
+def chunk_attn_wide_workspace_bytes(desc: L.ChunkAttnDesc) -> int:
+    """Workspace of a pq_chunk_attn_wide call of this descriptor (chunk_attn_desc): chunk_attn_workspace_bytes' function of the
+    same shape; 0 also for a descriptor the wide entry refuses."""
+    return int(L.load().million_chunk_attn_wide_workspace_bytes(ctypes.byref(desc)))
+
+
+def _chunk_attn_call(who, wide, q, k_chunk, v_chunk, k_codes, v_codes, k_prep, v_prep, k_res, v_res, r, M, C, n_tokens, resid_start,
+                     k_page_ids, v_page_ids, page_size, out, workspace, dev_lengths, dev_n_q, return_lse, lse):
+    """pq_chunk_attn (wide = False: uint8 codes, prepared codebooks) and pq_chunk_attn_wide (uint16 codes, the plain codebooks in
+    k_prep / v_prep): one set of checks, one descriptor, the entry point of the width."""
+    _need_cuda(q, k_chunk, v_chunk, k_codes, v_codes, k_prep, v_prep, k_res, v_res, k_page_ids, v_page_ids, out, workspace,
+               dev_lengths, dev_n_q, lse)
+    if q.dtype != torch.float16 or k_res.dtype != torch.float16 or v_res.dtype != torch.float16:
+        raise RuntimeError(f"{who}: q and window buffers must be fp16")
+    if wide:
+        if k_codes.dtype != torch.uint16 or v_codes.dtype != torch.uint16:
+            raise RuntimeError(f"{who}: codes must be uint16 (uint8 codes: pq_chunk_attn)")
+        for t in (k_prep, v_prep):
+            if t.dtype != torch.float16 or t.dim() != 3 or not t.is_contiguous():
+                raise RuntimeError(f"{who}: k_cents / v_cents must be the plain contiguous fp16 (M, C, d_m) codebooks")
+        if C not in WIDE_CENTROIDS:
+            raise RuntimeError(f"{who}: C={C} (one of {WIDE_CENTROIDS})")
+    elif k_codes.dtype != torch.uint8 or v_codes.dtype != torch.uint8:
+        raise RuntimeError(f"{who}: codes must be uint8")
+    if q.dim() != 4:
+        raise RuntimeError(f"{who}: q must be (bs, nh, n_q, d)")
+    bs, nh, n_q, d = q.shape
+    if (k_res.dim() != 4 or k_res.shape != v_res.shape or k_res.stride() != v_res.stride() or k_res.stride(3) != 1
+            or k_res.stride(2) != d or k_res.shape[0] != bs or k_res.shape[3] != d):
+        raise RuntimeError(f"{who}: window buffers must be (bs, nh_k, cap, d), share shape / strides, dense rows")
+    nh_k = k_res.shape[1]
+    if wide and (M <= 0 or d % M or tuple(k_prep.shape) != (M, C, d // M) or v_prep.shape != k_prep.shape):
+        raise RuntimeError(f"{who}: codebooks {tuple(k_prep.shape)} {tuple(v_prep.shape)} are not (M, C, d / M) for M={M} C={C} d={d}")
+    fix = lambda t: t if (t.stride(3) == 1 and all(s_ % 8 == 0 for s_ in t.stride()[:3])) else t.contiguous()
+    q = fix(q)
+    n_c = 0
+    if k_chunk is not None or v_chunk is not None:
+        if k_chunk is None or v_chunk is None:
+            raise RuntimeError(f"{who}: k_chunk and v_chunk go together")
+        if k_chunk.dtype != torch.float16 or v_chunk.dtype != torch.float16:
+            raise RuntimeError(f"{who}: chunk K/V must be fp16")
+        if k_chunk.shape != (bs, nh_k, n_q, d) or v_chunk.shape != k_chunk.shape:
+            raise RuntimeError(f"{who}: chunk K/V must be (bs, nh_k, n_q, d) = {(bs, nh_k, n_q, d)}, got "
+                               f"{tuple(k_chunk.shape)} {tuple(v_chunk.shape)}")
+        k_chunk, v_chunk = fix(k_chunk), fix(v_chunk)
+        n_c = n_q
+    k_paged, v_paged = k_page_ids is not None, v_page_ids is not None
+    n_pages_cap, ids64 = 0, False
+    for ids in (k_page_ids, v_page_ids):
+        if ids is None:
+            continue
+        if ids.dtype not in (torch.int32, torch.int64) or not ids.is_contiguous() or ids.dim() != 3 or ids.shape[:2] != (bs, nh_k):
+            raise RuntimeError(f"{who}: page ids must be contiguous int32/int64 (bs, nh_k, n_pages)")
+        if n_pages_cap and (ids.shape[2] != n_pages_cap or (ids.dtype == torch.int64) != ids64):
+            raise RuntimeError(f"{who}: K and V page ids must agree in dtype and length")
+        n_pages_cap, ids64 = ids.shape[2], ids.dtype == torch.int64
+    if (k_paged or v_paged) and page_size is None:
+        raise RuntimeError(f"{who}: paged codes need page_size")
+    for name, codes, paged in (("k_codes", k_codes, k_paged), ("v_codes", v_codes, v_paged)):
+        if paged:
+            if not codes.is_contiguous() or codes.dim() != 3:
+                raise RuntimeError(f"{who}: {name} page pool must be contiguous (n_pool, ., .)")
+        else:
+            if codes.dim() != 4 or codes.shape[3] != M or codes.shape[:2] != (bs, nh_k):
+                raise RuntimeError(f"{who}: {name} must be (bs, nh_k, T, M)")
+            if codes.shape[2] and (codes.stride(3) != 1 or codes.stride(2) != M):
+                raise RuntimeError(f"{who}: {name} rows must be dense (stride M)")
+            if n_tokens > codes.shape[2]:
+                raise RuntimeError(f"{who}: n_tokens exceeds {name}")
+    if dev_lengths is None and not 0 <= r <= k_res.shape[2]:
+        raise RuntimeError(f"{who}: r={r} outside [0, {k_res.shape[2]}]")
+    for name, t, shape in (("dev_lengths", dev_lengths, (bs, 4)), ("dev_n_q", dev_n_q, (bs,))):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous() or tuple(t.shape) != shape):
+            raise RuntimeError(f"{who}: {name} must be contiguous int32 {shape}")
+    if out is None:
+        out = torch.empty(bs, n_q, nh, d, dtype=torch.float16, device=q.device).transpose(1, 2)
+    elif out.shape != (bs, nh, n_q, d) or out.dtype != torch.float16 or out.stride(3) != 1:
+        raise RuntimeError(f"{who}: out must be fp16 (bs, nh, n_q, d) with contiguous rows")
+    desc = chunk_attn_desc(q, k_res, nh_k=nh_k, M=M, C=C, n_tokens=int(n_tokens), r=0 if dev_lengths is not None else int(r),
+                           n_c=n_c, resid_start=int(resid_start), k_paged=k_paged, v_paged=v_paged, page_size=int(page_size or 0),
+                           n_pages_cap=n_pages_cap, page_ids_i64=ids64, k_codes=k_codes, v_codes=v_codes, k_chunk=k_chunk,
+                           v_chunk=v_chunk, out=out, dev_lengths=dev_lengths, dev_n_q=dev_n_q)
+    lib = L.load()
+    need = (lib.million_chunk_attn_wide_workspace_bytes if wide else lib.million_chunk_attn_workspace_bytes)(ctypes.byref(desc))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=q.device) if need else None
+    if return_lse or lse is not None:
+        if lse is None:
+            lse = torch.empty(bs, nh, n_q, dtype=torch.float32, device=q.device)
+        elif lse.dtype != torch.float32 or tuple(lse.shape) != (bs, nh, n_q) or not lse.is_contiguous():
+            raise RuntimeError(f"{who}: lse must be contiguous fp32 (bs, nh, n_q)")
+        L.check((lib.million_pq_chunk_attn_wide if wide else lib.million_pq_chunk_attn_lse)(ctypes.byref(desc), q.data_ptr(), _ptr(k_chunk), _ptr(v_chunk), k_codes.data_ptr(),
+                                              v_codes.data_ptr(), _ptr(k_page_ids), _ptr(v_page_ids), k_prep.data_ptr(),
+                                              v_prep.data_ptr(), k_res.data_ptr(), v_res.data_ptr(), out.data_ptr(), lse.data_ptr(),
+                                              _ptr(workspace), 0 if workspace is None else workspace.numel(), _stream()),
+                "million_pq_chunk_attn_wide" if wide else "million_pq_chunk_attn_lse")
+        return out, lse
+    if wide:
+        L.check(lib.million_pq_chunk_attn_wide(ctypes.byref(desc), q.data_ptr(), _ptr(k_chunk), _ptr(v_chunk), k_codes.data_ptr(),
+                                               v_codes.data_ptr(), _ptr(k_page_ids), _ptr(v_page_ids), k_prep.data_ptr(),
+                                               v_prep.data_ptr(), k_res.data_ptr(), v_res.data_ptr(), out.data_ptr(), None,
+                                               _ptr(workspace), 0 if workspace is None else workspace.numel(), _stream()),
+                "million_pq_chunk_attn_wide")
+        return out
+    L.check(lib.million_pq_chunk_attn(ctypes.byref(desc), q.data_ptr(), _ptr(k_chunk), _ptr(v_chunk), k_codes.data_ptr(),
+                                      v_codes.data_ptr(), _ptr(k_page_ids), _ptr(v_page_ids), k_prep.data_ptr(), v_prep.data_ptr(),
+                                      k_res.data_ptr(), v_res.data_ptr(), out.data_ptr(), _ptr(workspace),
+                                      0 if workspace is None else workspace.numel(), _stream()), "million_pq_chunk_attn")
+    return out
 
 
 def pq_chunk_attn(q: torch.Tensor, k_chunk: Optional[torch.Tensor], v_chunk: Optional[torch.Tensor], k_codes: torch.Tensor,
@@ -957,88 +1068,24 @@ def pq_chunk_attn(q: torch.Tensor, k_chunk: Optional[torch.Tensor], v_chunk: Opt
     return_lse=True (or an lse= buffer): returns (out, lse), lse fp32 (bs, nh, n_q) contiguous - the natural-log sum of exp of
     every row's scaled scores over the keys it sees (million_pq_chunk_attn_lse); -inf for a row that sees none and for the rows
     past a request's dev_n_q."""
-    _need_cuda(q, k_chunk, v_chunk, k_codes, v_codes, k_prep, v_prep, k_res, v_res, k_page_ids, v_page_ids, out, workspace,
-               dev_lengths, dev_n_q, lse)
-    if q.dtype != torch.float16 or k_res.dtype != torch.float16 or v_res.dtype != torch.float16:
-        raise RuntimeError("pq_chunk_attn: q and window buffers must be fp16")
-    if k_codes.dtype != torch.uint8 or v_codes.dtype != torch.uint8:
-        raise RuntimeError("pq_chunk_attn: codes must be uint8")
-    if q.dim() != 4:
-        raise RuntimeError("pq_chunk_attn: q must be (bs, nh, n_q, d)")
-    bs, nh, n_q, d = q.shape
-    if (k_res.dim() != 4 or k_res.shape != v_res.shape or k_res.stride() != v_res.stride() or k_res.stride(3) != 1
-            or k_res.stride(2) != d or k_res.shape[0] != bs or k_res.shape[3] != d):
-        raise RuntimeError("pq_chunk_attn: window buffers must be (bs, nh_k, cap, d), share shape / strides, dense rows")
-    nh_k = k_res.shape[1]
-    fix = lambda t: t if (t.stride(3) == 1 and all(s_ % 8 == 0 for s_ in t.stride()[:3])) else t.contiguous()
-    q = fix(q)
-    n_c = 0
-    if k_chunk is not None or v_chunk is not None:
-        if k_chunk is None or v_chunk is None:
-            raise RuntimeError("pq_chunk_attn: k_chunk and v_chunk go together")
-        if k_chunk.dtype != torch.float16 or v_chunk.dtype != torch.float16:
-            raise RuntimeError("pq_chunk_attn: chunk K/V must be fp16")
-        if k_chunk.shape != (bs, nh_k, n_q, d) or v_chunk.shape != k_chunk.shape:
-            raise RuntimeError(f"pq_chunk_attn: chunk K/V must be (bs, nh_k, n_q, d) = {(bs, nh_k, n_q, d)}, got "
-                               f"{tuple(k_chunk.shape)} {tuple(v_chunk.shape)}")
-        k_chunk, v_chunk = fix(k_chunk), fix(v_chunk)
-        n_c = n_q
-    k_paged, v_paged = k_page_ids is not None, v_page_ids is not None
-    n_pages_cap, ids64 = 0, False
-    for ids in (k_page_ids, v_page_ids):
-        if ids is None:
-            continue
-        if ids.dtype not in (torch.int32, torch.int64) or not ids.is_contiguous() or ids.dim() != 3 or ids.shape[:2] != (bs, nh_k):
-            raise RuntimeError("pq_chunk_attn: page ids must be contiguous int32/int64 (bs, nh_k, n_pages)")
-        if n_pages_cap and (ids.shape[2] != n_pages_cap or (ids.dtype == torch.int64) != ids64):
-            raise RuntimeError("pq_chunk_attn: K and V page ids must agree in dtype and length")
-        n_pages_cap, ids64 = ids.shape[2], ids.dtype == torch.int64
-    if (k_paged or v_paged) and page_size is None:
-        raise RuntimeError("pq_chunk_attn: paged codes need page_size")
-    for name, codes, paged in (("k_codes", k_codes, k_paged), ("v_codes", v_codes, v_paged)):
-        if paged:
-            if not codes.is_contiguous() or codes.dim() != 3:
-                raise RuntimeError(f"pq_chunk_attn: {name} page pool must be contiguous (n_pool, ., .)")
-        else:
-            if codes.dim() != 4 or codes.shape[3] != M or codes.shape[:2] != (bs, nh_k):
-                raise RuntimeError(f"pq_chunk_attn: {name} must be (bs, nh_k, T, M)")
-            if codes.shape[2] and (codes.stride(3) != 1 or codes.stride(2) != M):
-                raise RuntimeError(f"pq_chunk_attn: {name} rows must be dense (stride M)")
-            if n_tokens > codes.shape[2]:
-                raise RuntimeError(f"pq_chunk_attn: n_tokens exceeds {name}")
-    if dev_lengths is None and not 0 <= r <= k_res.shape[2]:
-        raise RuntimeError(f"pq_chunk_attn: r={r} outside [0, {k_res.shape[2]}]")
-    for name, t, shape in (("dev_lengths", dev_lengths, (bs, 4)), ("dev_n_q", dev_n_q, (bs,))):
-        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous() or tuple(t.shape) != shape):
-            raise RuntimeError(f"pq_chunk_attn: {name} must be contiguous int32 {shape}")
-    if out is None:
-        out = torch.empty(bs, n_q, nh, d, dtype=torch.float16, device=q.device).transpose(1, 2)
-    elif out.shape != (bs, nh, n_q, d) or out.dtype != torch.float16 or out.stride(3) != 1:
-        raise RuntimeError("pq_chunk_attn: out must be fp16 (bs, nh, n_q, d) with contiguous rows")
-    desc = chunk_attn_desc(q, k_res, nh_k=nh_k, M=M, C=C, n_tokens=int(n_tokens), r=0 if dev_lengths is not None else int(r),
-                           n_c=n_c, resid_start=int(resid_start), k_paged=k_paged, v_paged=v_paged, page_size=int(page_size or 0),
-                           n_pages_cap=n_pages_cap, page_ids_i64=ids64, k_codes=k_codes, v_codes=v_codes, k_chunk=k_chunk,
-                           v_chunk=v_chunk, out=out, dev_lengths=dev_lengths, dev_n_q=dev_n_q)
-    lib = L.load()
-    need = lib.million_chunk_attn_workspace_bytes(ctypes.byref(desc))
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=q.device) if need else None
-    if return_lse or lse is not None:
-        if lse is None:
-            lse = torch.empty(bs, nh, n_q, dtype=torch.float32, device=q.device)
-        elif lse.dtype != torch.float32 or tuple(lse.shape) != (bs, nh, n_q) or not lse.is_contiguous():
-            raise RuntimeError("pq_chunk_attn: lse must be contiguous fp32 (bs, nh, n_q)")
-        L.check(lib.million_pq_chunk_attn_lse(ctypes.byref(desc), q.data_ptr(), _ptr(k_chunk), _ptr(v_chunk), k_codes.data_ptr(),
-                                              v_codes.data_ptr(), _ptr(k_page_ids), _ptr(v_page_ids), k_prep.data_ptr(),
-                                              v_prep.data_ptr(), k_res.data_ptr(), v_res.data_ptr(), out.data_ptr(), lse.data_ptr(),
-                                              _ptr(workspace), 0 if workspace is None else workspace.numel(), _stream()),
-                "million_pq_chunk_attn_lse")
-        return out, lse
-    L.check(lib.million_pq_chunk_attn(ctypes.byref(desc), q.data_ptr(), _ptr(k_chunk), _ptr(v_chunk), k_codes.data_ptr(),
-                                      v_codes.data_ptr(), _ptr(k_page_ids), _ptr(v_page_ids), k_prep.data_ptr(), v_prep.data_ptr(),
-                                      k_res.data_ptr(), v_res.data_ptr(), out.data_ptr(), _ptr(workspace),
-                                      0 if workspace is None else workspace.numel(), _stream()), "million_pq_chunk_attn")
-    return out
+    return _chunk_attn_call("pq_chunk_attn", False, q, k_chunk, v_chunk, k_codes, v_codes, k_prep, v_prep, k_res, v_res, r, M, C, n_tokens, resid_start,
+                            k_page_ids, v_page_ids, page_size, out, workspace, dev_lengths, dev_n_q, return_lse, lse)
+
+
+def pq_chunk_attn_wide(q: torch.Tensor, k_chunk: Optional[torch.Tensor], v_chunk: Optional[torch.Tensor], k_codes: torch.Tensor,
+                  v_codes: torch.Tensor, k_cents: torch.Tensor, v_cents: torch.Tensor, k_res: torch.Tensor, v_res: torch.Tensor,
+                  r: int, *, M: int, C: int, n_tokens: int, resid_start: int = 0, k_page_ids: Optional[torch.Tensor] = None,
+                  v_page_ids: Optional[torch.Tensor] = None, page_size: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                  workspace: Optional[torch.Tensor] = None, dev_lengths: Optional[torch.Tensor] = None,
+                  dev_n_q: Optional[torch.Tensor] = None, return_lse: bool = False, lse: Optional[torch.Tensor] = None):
+    """pq_chunk_attn over uint16 codes (C in 512 / 1024 / 2048 / 4096, d / M in {2, 4}): million_pq_chunk_attn_wide.  The same
+    arguments, checks, defaults, ragged fields and lse as pq_chunk_attn, with torch.uint16 code tensors (row-major
+    (bs, nh_k, T_cap, M) or page pools, per side) and k_cents / v_cents the plain contiguous fp16 (M, C, d_m) codebooks: there
+    is no prepared image.  Every gathered index is code & (C - 1), so code words past n_tokens, page tails and pages no live
+    entry names may hold anything.  With out=, workspace= (chunk_attn_wide_workspace_bytes) and, when asked for, lse= the call
+    allocates nothing and can be captured into a graph."""
+    return _chunk_attn_call("pq_chunk_attn_wide", True, q, k_chunk, v_chunk, k_codes, v_codes, k_cents, v_cents, k_res, v_res, r, M, C, n_tokens, resid_start,
+                            k_page_ids, v_page_ids, page_size, out, workspace, dev_lengths, dev_n_q, return_lse, lse)
 
 
 def attn_merge(outs, lses, out: Optional[torch.Tensor] = None, lse_out: Optional[torch.Tensor] = None, return_lse: bool = False):

@@ -234,8 +234,9 @@ class DynamicPQCache(_CacheBase):
         if sink_tokens:
             raise NotImplementedError("DynamicPQCache: sink_tokens is a property of PagedPQCache (DESIGN.md 4.13)")
         # nbits <= 8: uint8 codes, every path.  nbits 9..16: uint16 codes (nbits2dtype, pq_utils.py:542-552) on the
-        # dequantise-then-attend paths (update, prefill); the fused decode kernels are uint8-only, as the reference's
-        # are (KernelRegistry raises NotImplementedError, pq_utils.py:50-52).
+        # dequantise-then-attend paths (update, prefill) and, at nbits 9..12, extend (million_pq_chunk_attn_wide); the fused
+        # decode kernels of this cache are uint8-only, as the reference's are (KernelRegistry raises NotImplementedError,
+        # pq_utils.py:50-52).
         if not 1 <= nbits <= 16:
             raise NotImplementedError("nbits must be in 1..16")
         dtype = nbits2dtype(nbits) if dtype is None else dtype
@@ -346,16 +347,22 @@ class DynamicPQCache(_CacheBase):
         of a prompt): returns their attention over [the PQ codes; the residual window; the new rows, causally]
         (million_pq_chunk_attn: the past is read as codes, never as fp16), then leaves the cache as prefill() of the
         whole sequence would have - the window rows and then the new rows are encoded behind T, the window is empty.
-        On an empty cache this is prefill()."""
-        if self.nbits > 8:
-            raise NotImplementedError("extend: uint8 codes only (the chunk-attention kernel reads uint8 codes)")
+        On an empty cache this is prefill().  nbits 9 .. 12: the same over the uint16 store and the codebooks as they are
+        (million_pq_chunk_attn_wide); nbits 13 .. 16 have no chunk kernel."""
+        if self.nbits > 12:
+            raise NotImplementedError(f"extend: nbits={self.nbits}: the chunk-attention kernels read uint8 codes (nbits <= 8) or "
+                                      "uint16 codes of nbits 9 .. 12")
         T, r = self._T[layer_idx], self.residualed_tokens[layer_idx]
         if T == 0 and r == 0:
             return self.prefill(query_states, key_states, value_states, layer_idx)
         n = key_states.size(2)
         kres, vres = self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx]
-        out = ops.pq_chunk_attn(query_states, key_states, value_states, self._k_store[layer_idx], self._v_store[layer_idx],
-                                self._kprep, self._vprep, kres, vres, r, M=self.M, C=self.C, n_tokens=T)
+        if self.nbits > 8:
+            out = ops.pq_chunk_attn_wide(query_states, key_states, value_states, self._k_store[layer_idx], self._v_store[layer_idx],
+                                         self.key_cent, self.value_cent, kres, vres, r, M=self.M, C=self.C, n_tokens=T)
+        else:
+            out = ops.pq_chunk_attn(query_states, key_states, value_states, self._k_store[layer_idx], self._v_store[layer_idx],
+                                    self._kprep, self._vprep, kres, vres, r, M=self.M, C=self.C, n_tokens=T)
         if T + r + n > self.max_tokens:
             raise RuntimeError(f"DynamicPQCache: {T + r + n} tokens exceed max_tokens={self.max_tokens}")
         if r:
