@@ -557,6 +557,17 @@ typedef struct {
 int million_prefill_attn(const million_prefill_desc *desc, const void *q /* (bs, nh, n_q, d) */,
                          const void *k /* (bs, nh_k, n_kv, d) */, const void *v, void *out /* (bs, nh, n_q, d) */,
                          million_stream_t stream);
+/* The same with the log-sum-exp of every query row ("Log-sum-exp" above): float *lse (bs, nh, n_q) contiguous, after out:
+ *   lse[b,h,i] = ln sum_j exp( q[b,h,i,:] . k[b,hk,j,:] / sqrt(d) )  over exactly the keys j of the row's softmax above.
+ * -inf (with out = 0) where a row has no key: under dev_spans a request with n_kv_b = 0 and the rows i >= n_q_b below the bound
+ * n_q (rows at or past the bound are not written).  lse is required here (NULL: MILLION_ERR_ARG; 4-byte aligned); every other
+ * check, the grid and the ragged contract are million_prefill_attn's.  Separate kernel instances: out is bitwise the out of
+ * million_prefill_attn on the same arguments, in both forms (pipelined and plain) and with or without dev_spans.  The value
+ * comes from the softmax state the output was divided by - in the pipelined kernel the lazy reference in force at the end, not
+ * the row maximum.  A prompt pass over K/V held in blocks is then one call per block (non-causal over a past block, causal
+ * with q_pos0 counted from the block's first key over the last) and one million_attn_merge of the (out, lse) pairs. */
+int million_prefill_attn_lse(const million_prefill_desc *desc, const void *q, const void *k, const void *v, void *out,
+                             float *lse /* (bs, nh, n_q) */, million_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Chunk attention: a block of n_q new query tokens against the PQ-coded cache (chunked prefill, a second turn on an existing
@@ -661,6 +672,57 @@ int million_pq_chunk_attn_wide(const million_chunk_attn_desc *desc, const void *
                                const void *k_cents, const void *v_cents, const void *k_resid, const void *v_resid,
                                void *out, float *lse /* may be NULL */, void *workspace, size_t workspace_bytes,
                                million_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Gather of rows: a token range of every request dequantised straight from its code store, then its window rows in ring order,
+ * as fp16 rows in a caller's buffer - the K/V block a million_prefill_attn_lse call attends to, in memory that does not grow with
+ * the context.  For every (b, kv head), for K and for V (one launch does both):
+ *   out[b,hk,j,:]              = dequant(codes[b,hk,t0 + j])                         0 <= j < t1 - t0
+ *   out[b,hk,(t1 - t0) + i,:]  = resid[b,hk,(resid_start + i) % resid_cap,:]         0 <= i < r
+ * Either part may be empty (t1 = t0, r = 0); nothing to write: MILLION_OK without a launch.  Rows of out at or past
+ * (t1 - t0) + r are not written.
+ * Codes: code_bytes = 1: uint8, any C in 1 .. 256; code_bytes = 2: uint16, C in {512, 1024, 2048, 4096}; a C the code type
+ *   cannot hold is MILLION_ERR_SHAPE.  Each side row-major (bs, nh_k, T_cap, M) (k_stride_* / v_stride_* in BYTES, rows of
+ *   M * code_bytes bytes) or a page pool (K (n_pool, page_size, M), V (n_pool, M, page_size) transposed; pages of 32 / 64 / 128
+ *   tokens) behind int32 page ids (bs, nh_k, n_pages_cap).  d in {128, 64}, d / M in {1, 2, 4, 8}.
+ * Codebooks: the plain (M, C, d_m) fp16 tensors (no prepared image).  The dequantised rows are the gather of million_pq_decode,
+ *   bit for bit, for EVERY code word: an index is c < C ? c : 0.
+ * What is read: code words of tokens t0 <= t < t1, page-table entries of those tokens' pages, window rows of the ring's valid
+ *   span.  Code bytes at or past t1, page tails, unused pool pages, page-table entries past ceil(t1 / page_size) and window rows
+ *   outside the span may hold anything.  Page ids of the pages read are trusted.
+ * Lengths are host values (t0, t1, r, resid_start); there is no device-length form.
+ * Validation precedes any HIP call: struct size, d, M, C against code_bytes, the lengths (0 <= t0 <= t1, 0 <= r <= resid_cap,
+ *   resid_start inside the ring, (t1 - t0) + r <= rows_cap), layouts, page_size, the table (bs * nh_k * n_pages_cap and
+ *   n_pages_cap * page_size within 31 bits - the limits of the attention entries - and n_pages_cap * page_size >= t1:
+ *   MILLION_ERR_ARG), null pointers for whatever part is not empty, 16-byte alignment of out, window and codebook pointers and
+ *   strides that are multiples of 8 elements (MILLION_ERR_ALIGN).  Every byte offset on the device is 64-bit.
+ * One plain launch, no workspace, no atomics: legal inside stream capture. */
+typedef struct {
+    uint32_t struct_size;         /* = sizeof(million_gather_rows_desc) */
+    int32_t bs, nh_k, d, M, C;
+    int32_t code_bytes;           /* 1: uint8 codes, 2: uint16 codes */
+    int32_t t0, t1;               /* tokens [t0, t1) of every request */
+    int32_t r;                    /* valid window rows, 0 <= r <= resid_cap */
+    int32_t resid_start;          /* first valid window row (ring buffer) */
+    int32_t resid_cap;            /* rows of the window buffers (0: no window) */
+    int64_t resid_stride_b, resid_stride_h;   /* fp16 elements; row stride is d */
+    int32_t k_layout, v_layout;   /* MILLION_KV_* */
+    int32_t page_size;            /* PAGED: 32, 64 or 128 */
+    int32_t n_pages_cap;          /* PAGED: row length of the page-id arrays */
+    int64_t k_stride_b, k_stride_h;   /* ROWMAJOR: bytes between batches / kv heads of k_codes */
+    int64_t v_stride_b, v_stride_h;
+    int32_t rows_cap;             /* rows of the out buffers */
+    int32_t reserved;             /* 0 */
+    int64_t o_stride_b, o_stride_h;   /* out (bs, nh_k, rows_cap, d): fp16 elements; row stride is d */
+} million_gather_rows_desc;
+
+int million_pq_gather_rows(const million_gather_rows_desc *desc,
+                           const void *k_codes, const void *v_codes,           /* ROWMAJOR tensors or page pools */
+                           const int32_t *k_page_ids, const int32_t *v_page_ids, /* PAGED sides (may alias) */
+                           const void *k_cents, const void *v_cents,           /* (M, C, d_m) fp16 */
+                           const void *k_resid, const void *v_resid,           /* (bs, nh_k, resid_cap, d) fp16; NULL when r = 0 */
+                           void *k_out, void *v_out,                           /* (bs, nh_k, rows_cap, d) fp16 */
+                           million_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Merge of partial attentions: n_parts results (out_i, lse_i) of one query over disjoint key sets -> the result over

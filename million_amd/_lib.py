@@ -61,6 +61,15 @@ class ChunkAttnDesc(ctypes.Structure):
                 ("dev_lengths", c_vp), ("dev_n_q", c_vp)]
 
 
+class GatherRowsDesc(ctypes.Structure):
+    _fields_ = [("struct_size", c_u32), ("bs", c_i32), ("nh_k", c_i32), ("d", c_i32), ("M", c_i32), ("C", c_i32), ("code_bytes", c_i32),
+                ("t0", c_i32), ("t1", c_i32), ("r", c_i32), ("resid_start", c_i32), ("resid_cap", c_i32),
+                ("resid_stride_b", c_i64), ("resid_stride_h", c_i64),
+                ("k_layout", c_i32), ("v_layout", c_i32), ("page_size", c_i32), ("n_pages_cap", c_i32),
+                ("k_stride_b", c_i64), ("k_stride_h", c_i64), ("v_stride_b", c_i64), ("v_stride_h", c_i64),
+                ("rows_cap", c_i32), ("reserved", c_i32), ("o_stride_b", c_i64), ("o_stride_h", c_i64)]
+
+
 MILLION_MERGE_MAX_PARTS = 8
 
 
@@ -155,11 +164,13 @@ SYMBOLS = {
     "million_pq_decode_attn_wide": (c_i32, [ctypes.POINTER(AttnDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                             c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
     "million_prefill_attn": (c_i32, [ctypes.POINTER(PrefillDesc), c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "million_prefill_attn_lse": (c_i32, [ctypes.POINTER(PrefillDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "million_chunk_attn_workspace_bytes": (c_sz, [ctypes.POINTER(ChunkAttnDesc)]),
     "million_pq_chunk_attn": (c_i32, [ctypes.POINTER(ChunkAttnDesc)] + [c_vp] * 13 + [c_sz, c_vp]),
     "million_pq_chunk_attn_lse": (c_i32, [ctypes.POINTER(ChunkAttnDesc)] + [c_vp] * 14 + [c_sz, c_vp]),
     "million_chunk_attn_wide_workspace_bytes": (c_sz, [ctypes.POINTER(ChunkAttnDesc)]),
     "million_pq_chunk_attn_wide": (c_i32, [ctypes.POINTER(ChunkAttnDesc)] + [c_vp] * 14 + [c_sz, c_vp]),
+    "million_pq_gather_rows": (c_i32, [ctypes.POINTER(GatherRowsDesc)] + [c_vp] * 11),
     "million_attn_merge": (c_i32, [ctypes.POINTER(AttnMergeDesc), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_vp, c_vp]),
     "million_attn_block_merge": (c_i32, [ctypes.POINTER(BlockMergeDesc)] + [c_vp] * 11),
     "million_attn_sink_merge": (c_i32, [ctypes.POINTER(SinkMergeDesc)] + [c_vp] * 10),

@@ -109,9 +109,20 @@ __device__ __forceinline__ PrefillRows prefill_rows(const PrefillParams &p, int 
 // RAGGED: zeros into the lane's output row if it lies below the bound p.n_q - for a row at or past its request's n_q, and for
 // every row of a workgroup without work (wg_live = false), which leaves through this before the first load of q, the first DMA
 // and the first barrier (workgroup-uniform).
-template <int NB>
-__device__ __forceinline__ void prefill_store_dead(const PrefillParams &p, const PrefillRows &w, int hh) {
-    if (w.q_row < p.n_q) flash_store_zero_row<NB>(p.out + w.b * p.o_sb + w.head * p.o_sh + (long long)w.q_row * p.o_sn, hh);
+// LSE: such a row has no key - its log-sum-exp is -inf (prefill_store_lse).
+template <int NB, bool LSE = false>
+__device__ __forceinline__ void prefill_store_dead(const PrefillParams &p, const PrefillRows &w, int hh, float *lse = nullptr) {
+    if (w.q_row < p.n_q) {
+        flash_store_zero_row<NB>(p.out + w.b * p.o_sb + w.head * p.o_sh + (long long)w.q_row * p.o_sn, hh);
+        if (LSE && hh == 0) lse[((long long)w.b * p.nh + w.head) * p.n_q + w.q_row] = -INFINITY;
+    }
+}
+
+// LSE instances: ln sum_j exp(q . k_j / sqrt(d)) of the lane's row from the softmax state the output was divided by: ref2 = the
+// reference of the exponentials in exp2 units (scale log2 e x raw score), l = the row's total of exp2(score2 - ref2) over both
+// half-waves (after flash_l_total).  No visible key (l = 0): -inf, whatever the reference.  One store per row (half-wave 0).
+__device__ __forceinline__ void prefill_store_lse(const PrefillParams &p, const PrefillRows &w, int hh, float ref2, float l, float *lse) {
+    if (hh == 0) lse[((long long)w.b * p.nh + w.head) * p.n_q + w.q_row] = l > 0.f ? 0.6931471805599453f * (ref2 + __builtin_amdgcn_logf(l)) : -INFINITY;
 }
 
 // the lane's query row of Q (rows past the end read the last one: their output is not stored)
@@ -122,8 +133,11 @@ __device__ __forceinline__ const f16 *prefill_q_row(const PrefillParams &p, cons
 
 // D = 128 (the Llama head size of every BASELINE config) and D = 64 (the other head size the reference builds, setup.py:12).
 // RAGGED (both kernels): the instances behind desc->dev_spans; the lockstep instances (RAGGED = false) are the kernels without any of it.
-template <int D, bool RAGGED>
-__global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_kernel(PrefillParams p) {
+// LSE (both kernels): the instances behind million_prefill_attn_lse - the same body plus one fp32 store per row at the end; they are
+// kernels of their own names (prefill_lse_kernel, prefill_lse_pipe_kernel below) with lse (bs, nh, n_q) as a second argument, so the
+// six prefill_attn_* instances and their arguments are what they were.
+template <int D, bool RAGGED, bool LSE>
+__device__ __forceinline__ void prefill_attn_body(const PrefillParams p, float *lse) {
     constexpr int DS = D / 16;                 // k-steps of the score product
     constexpr int NB = D / 32;                 // 32-row blocks of O^T
     constexpr int kTileBytes = kKV * 2 * D;    // one [64][D] fp16 tile
@@ -133,7 +147,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_kernel(PrefillPar
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r32 = lane & 31, hh = lane >> 5;
     const PrefillRows w = prefill_rows<RAGGED>(p, wave, r32);
-    if (RAGGED && !w.wg_live) { prefill_store_dead<NB>(p, w, hh); return; }
+    if (RAGGED && !w.wg_live) { prefill_store_dead<NB, LSE>(p, w, hh, lse); return; }
     const int nt = w.nt, n_q = w.n_q, n_kv = w.n_kv;
     const bool wave_live = w.q_lo < n_q;                                                   // wave-uniform
     v8h qf[DS];
@@ -211,8 +225,10 @@ __global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_kernel(PrefillPar
         if (t + 1 < nt) tile(std::integral_constant<int, 1>{}, t + 1);
     }
     l_run = flash_l_total(l_run);
-    if (wave_live && w.q_row < n_q) flash_store_row(O, l_run, p.out + w.b * p.o_sb + w.head * p.o_sh + (long long)w.q_row * p.o_sn, hh);
-    else if (RAGGED) prefill_store_dead<NB>(p, w, hh);      // rows between the request's n_q and the bound
+    if (wave_live && w.q_row < n_q) {
+        flash_store_row(O, l_run, p.out + w.b * p.o_sb + w.head * p.o_sh + (long long)w.q_row * p.o_sn, hh);
+        if (LSE) prefill_store_lse(p, w, hh, m_run, l_run, lse);      // m_run: already in exp2 units (-inf only with l = 0)
+    } else if (RAGGED) prefill_store_dead<NB, LSE>(p, w, hh, lse);      // rows between the request's n_q and the bound
 }
 
 // =====================================================================================================
@@ -236,8 +252,8 @@ __global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_kernel(PrefillPar
 // every product and behind every softmax slice fixes the order: M, 7 vector, M, 7 vector ... as written.
 // =====================================================================================================
 #define PF_PIN(x) asm volatile("" : "+v"(x))
-template <bool RAGGED>
-__global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_pipe_kernel(PrefillParams p) {
+template <bool RAGGED, bool LSE>
+__device__ __forceinline__ void prefill_attn_pipe_body(const PrefillParams p, float *lse) {
     constexpr int D = 128, DS = D / 16, NB = D / 32, kTileBytes = kKV * 2 * D;
     extern __shared__ __attribute__((aligned(16))) char pf_smem[];
     if ((unsigned)(size_t)(__attribute__((address_space(3))) char *)pf_smem != 0u) __builtin_trap();
@@ -245,7 +261,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_pipe_kernel(Prefi
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r32 = lane & 31, hh = lane >> 5;
     const PrefillRows w = prefill_rows<RAGGED>(p, wave, r32);
-    if (RAGGED && !w.wg_live) { prefill_store_dead<NB>(p, w, hh); return; }
+    if (RAGGED && !w.wg_live) { prefill_store_dead<NB, LSE>(p, w, hh, lse); return; }
     const int q_pos = w.q_pos, nt = w.nt, w_pos_lo = w.w_pos_lo, w_pos_hi = w.w_pos_hi, n_q = w.n_q, n_kv = w.n_kv;
     v8h qf[DS];
     flash_load_q<D>(qf, prefill_q_row(p, w), hh);
@@ -504,21 +520,42 @@ __global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_pipe_kernel(Prefi
 #undef PF_KFRAG
 #undef PF_VFRAG
     l_run = flash_l_total(l_run);
-    if (wave_live && w.q_row < n_q) flash_store_row(O, l_run, p.out + w.b * p.o_sb + w.head * p.o_sh + (long long)w.q_row * p.o_sn, hh);
-    else if (RAGGED) prefill_store_dead<NB>(p, w, hh);      // rows between the request's n_q and the bound
+    if (wave_live && w.q_row < n_q) {
+        flash_store_row(O, l_run, p.out + w.b * p.o_sb + w.head * p.o_sh + (long long)w.q_row * p.o_sn, hh);
+        // the lazy reference: every probability of l_run is exp2(cs (s + neg_ref)) with the neg_ref in force now - decide() moved
+        // l_run along with each earlier one - so the reference is -neg_ref raw (0 while the row has seen no key: l = 0 then),
+        // not the row's maximum
+        if (LSE) prefill_store_lse(p, w, hh, -neg_ref * cs, l_run, lse);
+    } else if (RAGGED) prefill_store_dead<NB, LSE>(p, w, hh, lse);      // rows between the request's n_q and the bound
 }
 #undef PF_PIN
 
-template <int D>
-static void launch_prefill_t(const PrefillParams &p, long long blocks, int lds, hipStream_t s) {
-    if (p.dev_spans) hipLaunchKernelGGL((prefill_attn_kernel<D, true>), dim3((unsigned)blocks), dim3(kWaves * 64), lds, s, p);
+template <int D, bool RAGGED>
+__global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_kernel(PrefillParams p) { prefill_attn_body<D, RAGGED, false>(p, nullptr); }
+template <bool RAGGED>
+__global__ __launch_bounds__(kWaves * 64, 2) void prefill_attn_pipe_kernel(PrefillParams p) { prefill_attn_pipe_body<RAGGED, false>(p, nullptr); }
+template <int D, bool RAGGED>
+__global__ __launch_bounds__(kWaves * 64, 2) void prefill_lse_kernel(PrefillParams p, float *lse) { prefill_attn_body<D, RAGGED, true>(p, lse); }
+template <bool RAGGED>
+__global__ __launch_bounds__(kWaves * 64, 2) void prefill_lse_pipe_kernel(PrefillParams p, float *lse) { prefill_attn_pipe_body<RAGGED, true>(p, lse); }
+
+template <int D, bool LSE>
+static void launch_prefill_t(const PrefillParams &p, float *lse, long long blocks, int lds, hipStream_t s) {
+    if (LSE) {
+        if (p.dev_spans) hipLaunchKernelGGL((prefill_lse_kernel<D, true>), dim3((unsigned)blocks), dim3(kWaves * 64), lds, s, p, lse);
+        else hipLaunchKernelGGL((prefill_lse_kernel<D, false>), dim3((unsigned)blocks), dim3(kWaves * 64), lds, s, p, lse);
+    } else if (p.dev_spans) hipLaunchKernelGGL((prefill_attn_kernel<D, true>), dim3((unsigned)blocks), dim3(kWaves * 64), lds, s, p);
     else hipLaunchKernelGGL((prefill_attn_kernel<D, false>), dim3((unsigned)blocks), dim3(kWaves * 64), lds, s, p);
 }
-static void launch_prefill_pipe(const PrefillParams &p, long long blocks, int lds, hipStream_t s) {
-    if (p.dev_spans) hipLaunchKernelGGL(prefill_attn_pipe_kernel<true>, dim3((unsigned)blocks), dim3(kWaves * 64), lds, s, p);
+template <bool LSE>
+static void launch_prefill_pipe(const PrefillParams &p, float *lse, long long blocks, int lds, hipStream_t s) {
+    if (LSE) {
+        if (p.dev_spans) hipLaunchKernelGGL(prefill_lse_pipe_kernel<true>, dim3((unsigned)blocks), dim3(kWaves * 64), lds, s, p, lse);
+        else hipLaunchKernelGGL(prefill_lse_pipe_kernel<false>, dim3((unsigned)blocks), dim3(kWaves * 64), lds, s, p, lse);
+    } else if (p.dev_spans) hipLaunchKernelGGL(prefill_attn_pipe_kernel<true>, dim3((unsigned)blocks), dim3(kWaves * 64), lds, s, p);
     else hipLaunchKernelGGL(prefill_attn_pipe_kernel<false>, dim3((unsigned)blocks), dim3(kWaves * 64), lds, s, p);
 }
-// dynamic-LDS attribute of the three kernels (lockstep and ragged instances): once per device, under the library's per-device mutex (common.h: device_once)
+// dynamic-LDS attribute of the three kernels (lockstep and ragged instances, each without and with LSE): once per device, under the library's per-device mutex (common.h: device_once)
 static bool g_prefill_plain = false;      // A/B and tests (million_set_force_generic(64)): the plain form at d = 128 too
 void set_prefill_policy(bool plain) { g_prefill_plain = plain; }
 static void prefill_attrs_once() {
@@ -530,9 +567,15 @@ static void prefill_attrs_once() {
     lds_attr((const void *)prefill_attn_kernel<128, true>, 4 * kKV * 2 * 128);
     lds_attr((const void *)prefill_attn_kernel<64, false>, 4 * kKV * 2 * 64);
     lds_attr((const void *)prefill_attn_kernel<64, true>, 4 * kKV * 2 * 64);
+    lds_attr((const void *)prefill_lse_pipe_kernel<false>, 4 * kKV * 2 * 128);
+    lds_attr((const void *)prefill_lse_pipe_kernel<true>, 4 * kKV * 2 * 128);
+    lds_attr((const void *)prefill_lse_kernel<128, false>, 4 * kKV * 2 * 128);
+    lds_attr((const void *)prefill_lse_kernel<128, true>, 4 * kKV * 2 * 128);
+    lds_attr((const void *)prefill_lse_kernel<64, false>, 4 * kKV * 2 * 64);
+    lds_attr((const void *)prefill_lse_kernel<64, true>, 4 * kKV * 2 * 64);
 }
 
-int launch_prefill(const PrefillParams &p_in, hipStream_t s) {
+int launch_prefill(const PrefillParams &p_in, float *lse, hipStream_t s) {
     PrefillParams p = p_in;
     int hpw = 1;
     for (int c = kWaves; c >= 1; c >>= 1)
@@ -545,9 +588,13 @@ int launch_prefill(const PrefillParams &p_in, hipStream_t s) {
     if (blocks > 0x7fffffffLL) { set_error("prefill: %lld workgroups", blocks); return MILLION_ERR_SHAPE; }
     const int lds = 4 * kKV * 2 * p.d;      // two buffers of (K tile, V tile)
     prefill_attrs_once();
-    if (p.d == 128 && !g_prefill_plain) launch_prefill_pipe(p, blocks, lds, s);
-    else if (p.d == 128) launch_prefill_t<128>(p, blocks, lds, s);
-    else launch_prefill_t<64>(p, blocks, lds, s);
+    if (lse) {
+        if (p.d == 128 && !g_prefill_plain) launch_prefill_pipe<true>(p, lse, blocks, lds, s);
+        else if (p.d == 128) launch_prefill_t<128, true>(p, lse, blocks, lds, s);
+        else launch_prefill_t<64, true>(p, lse, blocks, lds, s);
+    } else if (p.d == 128 && !g_prefill_plain) launch_prefill_pipe<false>(p, nullptr, blocks, lds, s);
+    else if (p.d == 128) launch_prefill_t<128, false>(p, nullptr, blocks, lds, s);
+    else launch_prefill_t<64, false>(p, nullptr, blocks, lds, s);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("prefill launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
     return MILLION_OK;
@@ -557,8 +604,9 @@ int launch_prefill(const PrefillParams &p_in, hipStream_t s) {
 
 using namespace million;
 
-extern "C" int million_prefill_attn(const million_prefill_desc *desc, const void *q, const void *k, const void *v, void *out,
-                                    million_stream_t stream) {
+// both entries: lse = null is million_prefill_attn (the instances without LSE), anything else million_prefill_attn_lse
+static int prefill_entry(const million_prefill_desc *desc, const void *q, const void *k, const void *v, void *out, float *lse,
+                         million_stream_t stream) {
     if (!desc || desc->struct_size != sizeof(million_prefill_desc)) { set_error("prefill: bad desc / struct_size"); return MILLION_ERR_ARG; }
     if (!q || !k || !v || !out) { set_error("prefill: null pointer"); return MILLION_ERR_ARG; }
     PrefillParams p;
@@ -582,5 +630,17 @@ extern "C" int million_prefill_attn(const million_prefill_desc *desc, const void
     }
     p.scale_log2e = 1.4426950408889634f / sqrtf((float)p.d);
     p.dev_spans = desc->dev_spans;      // non-null: n_q and n_kv above are the bounds, q_pos0 is not read (validated all the same)
-    return launch_prefill(p, (hipStream_t)stream);
+    return launch_prefill(p, lse, (hipStream_t)stream);
+}
+
+extern "C" int million_prefill_attn(const million_prefill_desc *desc, const void *q, const void *k, const void *v, void *out,
+                                    million_stream_t stream) {
+    return prefill_entry(desc, q, k, v, out, nullptr, stream);
+}
+
+extern "C" int million_prefill_attn_lse(const million_prefill_desc *desc, const void *q, const void *k, const void *v, void *out,
+                                        float *lse, million_stream_t stream) {
+    if (!lse) { set_error("prefill: null lse (million_prefill_attn is the entry without it)"); return MILLION_ERR_ARG; }
+    if ((uintptr_t)lse & 3) { set_error("prefill: lse must be 4-byte aligned"); return MILLION_ERR_ALIGN; }
+    return prefill_entry(desc, q, k, v, out, lse, stream);
 }

@@ -672,7 +672,8 @@ def pq_decode_attn_wide(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Ten
 
 
 def prefill_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, causal: bool = True, q_pos0: int = 0,
-                 out: Optional[torch.Tensor] = None, dev_spans: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 out: Optional[torch.Tensor] = None, dev_spans: Optional[torch.Tensor] = None, return_lse: bool = False,
+                 lse: Optional[torch.Tensor] = None):
     """Prompt attention on fp16 K/V (million_prefill_attn): q (bs, nh, n_q, d), k / v (bs, nh_k, n_kv, d) -> (bs, nh, n_q, d).
     Replaces scaled_dot_product_attention(q, repeat_kv(k), repeat_kv(v), is_causal=True) of the reference's prompt pass
     (pq_utils.py:249-260) without materialising repeat_kv.  Row strides are free (transposed (bs, n, h, d) projections are
@@ -680,7 +681,11 @@ def prefill_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, causal: b
     dev_spans: a ragged batch - int32 (bs, 4) rows {n_q, n_kv, q_pos0, reserved} on q's device, read by the kernel when it runs
     (a captured call follows them).  The tensors' n_q and n_kv are then the bounds of the padded layout, `q_pos0` is not used,
     each request attends with its own three values (clamped into the bounds); rows past a request's n_q come back as zeros, a
-    request without keys as zeros, and q rows past n_q[b], K / V rows past n_kv[b] and `out` may hold anything before the call."""
+    request without keys as zeros, and q rows past n_q[b], K / V rows past n_kv[b] and `out` may hold anything before the call.
+    return_lse (or lse=, contiguous fp32 (bs, nh, n_q)): returns (out, lse) through million_prefill_attn_lse - lse = ln sum_j
+    exp(q . k_j / sqrt(d)) over the keys of the row's softmax, -inf where a row has none; `out` is bitwise the call without it.
+    Parts over disjoint key ranges (non-causal over a past block, causal with q_pos0 counted from the block's first key over
+    the last one) combine exactly with attn_merge."""
     if dev_spans is not None:      # first: what is wrong with the rows is said before anything about the tensors beside them
         if not isinstance(dev_spans, torch.Tensor) or dev_spans.dtype != torch.int32:
             raise RuntimeError("prefill_attn: dev_spans must be an int32 tensor")
@@ -688,7 +693,7 @@ def prefill_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, causal: b
             raise RuntimeError(f"prefill_attn: dev_spans must be contiguous, of shape (bs, 4) = ({q.shape[0] if q.dim() == 4 else '?'}, 4)")
         if not dev_spans.is_cuda or dev_spans.device != q.device:
             raise RuntimeError("prefill_attn: dev_spans must live on the device of q (the kernel reads it there)")
-    _need_cuda(q, k, v, out)
+    _need_cuda(q, k, v, out, lse)
     if q.dtype != torch.float16 or k.dtype != torch.float16 or v.dtype != torch.float16:
         raise RuntimeError("prefill_attn: q, k, v must be fp16")
     if q.dim() != 4 or k.dim() != 4 or k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[3] != k.shape[3]:
@@ -714,6 +719,14 @@ def prefill_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, causal: b
     desc.v_stride_b, desc.v_stride_h, desc.v_stride_n = v.stride(0), v.stride(1), v.stride(2)
     desc.o_stride_b, desc.o_stride_h, desc.o_stride_n = out.stride(0), out.stride(1), out.stride(2)
     desc.dev_spans = _ptr(dev_spans)
+    if return_lse or lse is not None:
+        if lse is None:
+            lse = torch.empty(bs, nh, n_q, dtype=torch.float32, device=q.device)
+        elif lse.dtype != torch.float32 or tuple(lse.shape) != (bs, nh, n_q) or not lse.is_contiguous():
+            raise RuntimeError("prefill_attn: lse must be contiguous fp32 (bs, nh, n_q)")
+        L.check(L.load().million_prefill_attn_lse(ctypes.byref(desc), q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(),
+                                                  lse.data_ptr(), _stream()), "million_prefill_attn_lse")
+        return out, lse
     L.check(L.load().million_prefill_attn(ctypes.byref(desc), q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), _stream()),
             "million_prefill_attn")
     return out
@@ -1127,6 +1140,248 @@ def attn_merge(outs, lses, out: Optional[torch.Tensor] = None, lse_out: Optional
     pl = (L.c_vp * P)(*[l.data_ptr() for l in lses])
     L.check(L.load().million_attn_merge(ctypes.byref(desc), po, pl, out.data_ptr(), _ptr(lse_out), _stream()), "million_attn_merge")
     return (out, lse_out) if (return_lse or lse_out is not None) else out
+
+
+def pq_gather_rows(k_codes: torch.Tensor, v_codes: torch.Tensor, k_cents: torch.Tensor, v_cents: torch.Tensor,
+                   k_out: torch.Tensor, v_out: torch.Tensor, *, t0: int, t1: int, k_res: Optional[torch.Tensor] = None,
+                   v_res: Optional[torch.Tensor] = None, r: int = 0, resid_start: int = 0,
+                   k_page_ids: Optional[torch.Tensor] = None, v_page_ids: Optional[torch.Tensor] = None,
+                   page_size: Optional[int] = None) -> int:
+    """Tokens [t0, t1) of every request dequantised from its code store, then its r window rows in ring order from resid_start, as
+    fp16 rows from row 0 of k_out / v_out (bs, nh_k, rows_cap, d) (million_pq_gather_rows; one launch does K and V).  Returns the
+    rows written, (t1 - t0) + r; the rows behind them are not touched.  A code side is row-major (bs, nh_k, T_cap, M) when its
+    page ids are None, else a page pool (K (n_pool, page_size, M), V (n_pool, M, page_size)) behind int32 ids (bs, nh_k, n_pages).
+    uint8 codes with any C <= 256, uint16 codes with C in 512 / 1024 / 2048 / 4096; k_cents / v_cents are the plain contiguous
+    fp16 (M, C, d_m) codebooks.  The coded rows are pq_decode's, bit for bit.  Host lengths only.  Nothing is allocated."""
+    _need_cuda(k_codes, v_codes, k_cents, v_cents, k_out, v_out, k_res, v_res, k_page_ids, v_page_ids)
+    who = "pq_gather_rows"
+    for t in (k_cents, v_cents):
+        if t.dtype != torch.float16 or t.dim() != 3 or not t.is_contiguous() or t.shape != k_cents.shape:
+            raise RuntimeError(f"{who}: k_cents / v_cents must be the plain contiguous fp16 (M, C, d_m) codebooks, alike")
+    M, C, dm = k_cents.shape
+    d = M * dm
+    if k_codes.dtype != v_codes.dtype or k_codes.dtype not in (torch.uint8, torch.uint16):
+        raise RuntimeError(f"{who}: codes must be uint8 or uint16, both sides alike")
+    code_bytes = k_codes.element_size()
+    if (code_bytes == 1 and C > 256) or (code_bytes == 2 and C not in WIDE_CENTROIDS):
+        raise RuntimeError(f"{who}: C={C} does not go with {k_codes.dtype} codes (uint8: C <= 256; uint16: C in {WIDE_CENTROIDS})")
+    for t in (k_out, v_out):
+        if (t.dtype != torch.float16 or t.dim() != 4 or t.shape[3] != d or t.stride(3) != 1 or t.stride(2) != d
+                or t.shape != k_out.shape or t.stride() != k_out.stride()):
+            raise RuntimeError(f"{who}: k_out / v_out must be fp16 (bs, nh_k, rows_cap, d = {d}) with dense rows, alike")
+    bs, nh_k, rows_cap = k_out.shape[:3]
+    resid_cap = 0
+    if k_res is not None or v_res is not None:
+        if (k_res is None or v_res is None or k_res.dtype != torch.float16 or v_res.dtype != torch.float16 or k_res.dim() != 4
+                or k_res.shape != v_res.shape or k_res.stride() != v_res.stride() or k_res.stride(3) != 1 or k_res.stride(2) != d
+                or k_res.shape[:2] != (bs, nh_k) or k_res.shape[3] != d):
+            raise RuntimeError(f"{who}: window buffers must be fp16 (bs, nh_k, cap, d), share shape / strides, dense rows")
+        resid_cap = k_res.shape[2]
+    if not 0 <= r <= resid_cap:
+        raise RuntimeError(f"{who}: r={r} outside [0, {resid_cap}]")
+    k_paged, v_paged = k_page_ids is not None, v_page_ids is not None
+    n_pages_cap = 0
+    for ids in (k_page_ids, v_page_ids):
+        if ids is None:
+            continue
+        if ids.dtype != torch.int32 or not ids.is_contiguous() or ids.dim() != 3 or ids.shape[:2] != (bs, nh_k):
+            raise RuntimeError(f"{who}: page ids must be contiguous int32 (bs, nh_k, n_pages)")
+        if n_pages_cap and ids.shape[2] != n_pages_cap:
+            raise RuntimeError(f"{who}: K and V page ids must agree in length")
+        n_pages_cap = ids.shape[2]
+    if (k_paged or v_paged) and page_size is None:
+        raise RuntimeError(f"{who}: paged codes need page_size")
+    for name, codes, paged in (("k_codes", k_codes, k_paged), ("v_codes", v_codes, v_paged)):
+        if paged:
+            if not codes.is_contiguous() or codes.dim() != 3:
+                raise RuntimeError(f"{who}: {name} page pool must be contiguous (n_pool, ., .)")
+        else:
+            if codes.dim() != 4 or codes.shape[3] != M or codes.shape[:2] != (bs, nh_k):
+                raise RuntimeError(f"{who}: {name} must be (bs, nh_k, T, M)")
+            if codes.shape[2] and (codes.stride(3) != 1 or codes.stride(2) != M):
+                raise RuntimeError(f"{who}: {name} rows must be dense (stride M)")
+            if t1 > codes.shape[2]:
+                raise RuntimeError(f"{who}: t1={t1} exceeds {name}")
+    desc = L.GatherRowsDesc()
+    desc.struct_size = ctypes.sizeof(L.GatherRowsDesc)
+    desc.bs, desc.nh_k, desc.d, desc.M, desc.C, desc.code_bytes = bs, nh_k, d, M, C, code_bytes
+    desc.t0, desc.t1, desc.r, desc.resid_start, desc.resid_cap = int(t0), int(t1), int(r), int(resid_start), resid_cap
+    if resid_cap:
+        desc.resid_stride_b, desc.resid_stride_h = k_res.stride(0), k_res.stride(1)
+    desc.k_layout = L.MILLION_KV_PAGED if k_paged else L.MILLION_KV_ROWMAJOR
+    desc.v_layout = L.MILLION_KV_PAGED if v_paged else L.MILLION_KV_ROWMAJOR
+    desc.page_size, desc.n_pages_cap = int(page_size or 0), n_pages_cap
+    if not k_paged:
+        desc.k_stride_b, desc.k_stride_h = (k_codes.stride(i) * code_bytes for i in (0, 1))      # bytes
+    if not v_paged:
+        desc.v_stride_b, desc.v_stride_h = (v_codes.stride(i) * code_bytes for i in (0, 1))
+    desc.rows_cap, desc.o_stride_b, desc.o_stride_h = rows_cap, k_out.stride(0), k_out.stride(1)
+    L.check(L.load().million_pq_gather_rows(ctypes.byref(desc), k_codes.data_ptr(), v_codes.data_ptr(), _ptr(k_page_ids), _ptr(v_page_ids),
+                                            k_cents.data_ptr(), v_cents.data_ptr(), _ptr(k_res), _ptr(v_res), k_out.data_ptr(),
+                                            v_out.data_ptr(), _stream()), "million_pq_gather_rows")
+    return int(t1) - int(t0) + int(r)
+
+
+# ---- the block route of chunk attention: a long chunk at the prompt kernel's rate, in memory that does not grow with T ----------
+# ceil(128 Ki / 7) rounded up to a multiple of 64: seven blocks and the chunk are eight parts - one merge - up to T = 128 Ki
+CHUNK_BLOCK_TOKENS = 18752
+CHUNK_BLOCKS_MAX_PARTS = L.MILLION_MERGE_MAX_PARTS ** 2      # two merge levels
+
+
+def chunk_blocks_plan(n_tokens: int, r: int, has_chunk: bool, block_tokens: Optional[int] = None) -> dict:
+    """The plan of pq_chunk_attn_blocks, a pure function of host ints.  The past [0, n_tokens) is cut into blocks of block_tokens
+    (the last may be shorter); the r window rows ride behind the LAST block's rows in the scratch (alone when n_tokens = 0); the
+    chunk is a part of its own.  -> {"parts": [("block", t0, t1, r_here) | ("chunk",)], "groups": [[part indices]]}: one group
+    when there are at most MILLION_MERGE_MAX_PARTS (8) parts - one attn_merge into the result - else groups of up to 8 in order,
+    each merged into an intermediate pair, and one more merge of those.  No part: out = 0, lse = -inf.  More than 64 parts are
+    refused (RuntimeError): raise block_tokens."""
+    bt = CHUNK_BLOCK_TOKENS if block_tokens is None else int(block_tokens)
+    if bt < 1 or n_tokens < 0 or r < 0:
+        raise RuntimeError(f"chunk_blocks_plan: n_tokens={n_tokens} r={r} block_tokens={bt}")
+    parts = [("block", t0, min(t0 + bt, n_tokens), 0) for t0 in range(0, n_tokens, bt)]
+    if r:
+        if parts:
+            parts[-1] = parts[-1][:3] + (r,)
+        else:
+            parts.append(("block", 0, 0, r))
+    if has_chunk:
+        parts.append(("chunk",))
+    P = L.MILLION_MERGE_MAX_PARTS
+    if len(parts) > CHUNK_BLOCKS_MAX_PARTS:
+        raise RuntimeError(f"chunk_blocks_plan: {len(parts)} parts (n_tokens={n_tokens}, block_tokens={bt}) exceed {CHUNK_BLOCKS_MAX_PARTS}: "
+                           "raise block_tokens")
+    idx = list(range(len(parts)))
+    return {"parts": parts, "groups": [idx[i:i + P] for i in range(0, len(idx), P)]}
+
+
+def _chunk_blocks_layout(bs, nh, nh_k, n_q, d, resid_cap, block_tokens):
+    """(total bytes, offsets) of the workspace: K scratch, V scratch, then 2 x 8 (out, lse) pairs - the parts of one group and the
+    groups' results - every segment on a 256-byte boundary."""
+    bt = CHUNK_BLOCK_TOKENS if block_tokens is None else int(block_tokens)
+    if d not in (64, 128):
+        raise RuntimeError(f"chunk_blocks_workspace_bytes: d={d} (64 or 128)")
+    if min(bs, nh, nh_k) <= 0 or nh % nh_k or n_q < 0 or resid_cap < 0 or bt < 1:
+        raise RuntimeError(f"chunk_blocks_workspace_bytes: bs={bs} nh={nh} nh_k={nh_k} n_q={n_q} resid_cap={resid_cap} block_tokens={bt}")
+    if bt + resid_cap > 0x7fffffff or bs * nh * n_q > 0x7fffffff:
+        raise RuntimeError(f"chunk_blocks_workspace_bytes: block_tokens + resid_cap = {bt + resid_cap}, bs * nh * n_q = {bs * nh * n_q} "
+                           "do not fit 31 bits")
+    up = lambda x: (x + 255) // 256 * 256
+    P = L.MILLION_MERGE_MAX_PARTS
+    scratch = up(bs * nh_k * (bt + resid_cap) * d * 2)
+    o, l = up(bs * nh * n_q * d * 2), up(bs * nh * n_q * 4)
+    off = {"k": 0, "v": scratch, "out": 2 * scratch, "lse": 2 * scratch + 2 * P * o, "o": o, "l": l, "rows": bt + resid_cap}
+    return 2 * scratch + 2 * P * (o + l), off
+
+
+def chunk_blocks_workspace_bytes(bs: int, nh: int, nh_k: int, n_q: int, d: int, resid_cap: int, block_tokens: Optional[int] = None) -> int:
+    """Bytes of the workspace= of pq_chunk_attn_blocks: the fp16 K and V scratch of ONE block plus the window,
+    2 * bs * nh_k * (block_tokens + resid_cap) * d * 2, and sixteen partial (out, lse) pairs of (bs, nh, n_q, d) fp16 +
+    (bs, nh, n_q) fp32 (the parts of one merge group and the groups' results), each segment rounded up to 256 bytes.  A function
+    of the shapes and block_tokens - never of the context length.  No initialisation is needed."""
+    return _chunk_blocks_layout(bs, nh, nh_k, n_q, d, resid_cap, block_tokens)[0]
+
+
+def pq_chunk_attn_blocks(q: torch.Tensor, k_chunk: Optional[torch.Tensor], v_chunk: Optional[torch.Tensor], k_codes: torch.Tensor,
+                         v_codes: torch.Tensor, k_prep: torch.Tensor, v_prep: torch.Tensor, k_res: torch.Tensor, v_res: torch.Tensor,
+                         r: int, *, M: int, C: int, n_tokens: int, resid_start: int = 0, k_page_ids: Optional[torch.Tensor] = None,
+                         v_page_ids: Optional[torch.Tensor] = None, page_size: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                         workspace: Optional[torch.Tensor] = None, dev_lengths: Optional[torch.Tensor] = None,
+                         dev_n_q: Optional[torch.Tensor] = None, return_lse: bool = False, lse: Optional[torch.Tensor] = None,
+                         block_tokens: Optional[int] = None):
+    """Chunk attention by blocks - pq_chunk_attn's meaning (n_q rows against [the codes of n_tokens tokens; r window rows; the chunk,
+    causally]) and arguments, uint8 codes with prepared codebooks as pq_chunk_attn or uint16 codes with the plain codebooks as
+    pq_chunk_attn_wide (the code dtype selects), served by the prompt kernel: per block of block_tokens past tokens one
+    pq_gather_rows into a bounded fp16 scratch (the window behind the last block's rows) and one non-causal
+    prefill_attn(return_lse=True) over it, one causal prefill_attn over k_chunk / v_chunk themselves, and attn_merge of the parts
+    (chunk_blocks_plan).  For long chunks this runs at the prompt kernel's rate where the chunk kernel does not
+    (profiles/chunk_blocks.txt); its transient memory, chunk_blocks_workspace_bytes, does not grow with n_tokens.
+    Host lengths only: dev_lengths / dev_n_q raise.  With out=, workspace= and, when asked for, lse= the call allocates nothing
+    and is a chain of launches on the current stream: it can be captured into a graph.  Each part's out is rounded to fp16
+    before the merge: the result is within the attention bar of pq_chunk_attn's, not bitwise equal to it."""
+    who = "pq_chunk_attn_blocks"
+    if dev_lengths is not None or dev_n_q is not None:
+        raise RuntimeError(f"{who}: host lengths only - dev_lengths / dev_n_q are pq_chunk_attn's (the chunk route)")
+    _need_cuda(q, k_chunk, v_chunk, k_codes, v_codes, k_prep, v_prep, k_res, v_res, k_page_ids, v_page_ids, out, workspace, lse)
+    if q.dim() != 4 or q.dtype != torch.float16:
+        raise RuntimeError(f"{who}: q must be fp16 (bs, nh, n_q, d)")
+    bs, nh, n_q, d = q.shape
+    if k_res.dim() != 4 or k_res.shape[0] != bs or k_res.shape[3] != d or nh % k_res.shape[1]:
+        raise RuntimeError(f"{who}: window buffers must be (bs, nh_k, cap, d), nh a multiple of nh_k")
+    nh_k, cap = k_res.shape[1], k_res.shape[2]
+    if M <= 0 or d % M:
+        raise RuntimeError(f"{who}: d={d} M={M}")
+    dm = d // M
+    if k_codes.dtype == torch.uint16:      # the plain codebooks, as pq_chunk_attn_wide takes them
+        k_cents, v_cents = k_prep, v_prep
+    elif k_codes.dtype == torch.uint8:     # prepared codebooks, as pq_chunk_attn takes them: their first image is the plain [m][c][d_m] table
+        _check_prepared(who, k_prep, v_prep, M, C, d)
+        k_cents, v_cents = (t.reshape(-1)[:M * C * dm].view(M, C, dm) for t in (k_prep, v_prep))
+    else:
+        raise RuntimeError(f"{who}: codes must be uint8 (prepared codebooks) or uint16 (plain codebooks)")
+    if (k_chunk is None) != (v_chunk is None):
+        raise RuntimeError(f"{who}: k_chunk and v_chunk go together")
+    if k_chunk is not None and (k_chunk.shape != (bs, nh_k, n_q, d) or v_chunk.shape != k_chunk.shape):
+        raise RuntimeError(f"{who}: chunk K/V must be (bs, nh_k, n_q, d) = {(bs, nh_k, n_q, d)}, got {tuple(k_chunk.shape)} {tuple(v_chunk.shape)}")
+    n_tokens, r = int(n_tokens), int(r)
+    if not 0 <= r <= cap:
+        raise RuntimeError(f"{who}: r={r} outside [0, {cap}]")
+    plan = chunk_blocks_plan(n_tokens, r, k_chunk is not None, block_tokens)
+    need, off = _chunk_blocks_layout(bs, nh, nh_k, n_q, d, cap, block_tokens)
+    if out is None:
+        out = torch.empty(bs, n_q, nh, d, dtype=torch.float16, device=q.device).transpose(1, 2)
+    elif out.shape != (bs, nh, n_q, d) or out.dtype != torch.float16 or out.stride(3) != 1:
+        raise RuntimeError(f"{who}: out must be fp16 (bs, nh, n_q, d) with contiguous rows")
+    want_lse = return_lse or lse is not None
+    if lse is not None and (lse.dtype != torch.float32 or tuple(lse.shape) != (bs, nh, n_q) or not lse.is_contiguous()):
+        raise RuntimeError(f"{who}: lse must be contiguous fp32 (bs, nh, n_q)")
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
+    elif workspace.dtype != torch.uint8 or workspace.dim() != 1 or workspace.numel() < need or workspace.data_ptr() % 256:
+        raise RuntimeError(f"{who}: workspace must be a 256-byte aligned uint8 tensor of at least {need} bytes (chunk_blocks_workspace_bytes)")
+    parts, groups = plan["parts"], plan["groups"]
+    if n_q == 0:
+        return (out, lse if lse is not None else torch.empty(bs, nh, 0, dtype=torch.float32, device=q.device)) if want_lse else out
+    if lse is None and want_lse:
+        lse = torch.empty(bs, nh, n_q, dtype=torch.float32, device=q.device)
+    if not parts:
+        out.zero_()
+        if want_lse:
+            lse.fill_(float("-inf"))
+        return (out, lse) if want_lse else out
+    P = L.MILLION_MERGE_MAX_PARTS
+    kscr = workspace[off["k"]:off["k"] + bs * nh_k * off["rows"] * d * 2].view(torch.float16).view(bs, nh_k, off["rows"], d)
+    vscr = workspace[off["v"]:off["v"] + bs * nh_k * off["rows"] * d * 2].view(torch.float16).view(bs, nh_k, off["rows"], d)
+    slot_o = lambda i: workspace[off["out"] + i * off["o"]:off["out"] + i * off["o"] + bs * nh * n_q * d * 2].view(torch.float16).view(bs, nh, n_q, d)
+    slot_l = lambda i: workspace[off["lse"] + i * off["l"]:off["lse"] + i * off["l"] + bs * nh * n_q * 4].view(torch.float32).view(bs, nh, n_q)
+
+    def run_part(part, o, l):
+        if part[0] == "chunk":
+            prefill_attn(q, k_chunk, v_chunk, causal=True, out=o, lse=l)
+            return
+        _, t0, t1, r_here = part
+        n = pq_gather_rows(k_codes, v_codes, k_cents, v_cents, kscr, vscr, t0=t0, t1=t1, k_res=k_res, v_res=v_res, r=r_here,
+                           resid_start=resid_start if r_here else 0, k_page_ids=k_page_ids, v_page_ids=v_page_ids, page_size=page_size)
+        prefill_attn(q, kscr[:, :, :n], vscr[:, :, :n], causal=False, out=o, lse=l)
+
+    if len(parts) == 1:      # one part is the result
+        l = lse if lse is not None else slot_l(0)
+        run_part(parts[0], out, l)
+        return (out, lse) if want_lse else out
+    tops_o, tops_l = [], []
+    for g, group in enumerate(groups):
+        res_o, res_l = (out, lse) if len(groups) == 1 else (slot_o(P + g), slot_l(P + g))
+        if len(group) == 1:      # a last group of one part is its own result
+            run_part(parts[group[0]], res_o, res_l)
+        else:
+            for j, i in enumerate(group):
+                run_part(parts[i], slot_o(j), slot_l(j))
+            attn_merge([slot_o(j) for j in range(len(group))], [slot_l(j) for j in range(len(group))], out=res_o, lse_out=res_l)
+        if len(groups) == 1:
+            return (out, lse) if want_lse else out
+        tops_o.append(res_o)
+        tops_l.append(res_l)
+    attn_merge(tops_o, tops_l, out=out, lse_out=lse)
+    return (out, lse) if want_lse else out
 
 
 def attn_block_merge(q: torch.Tensor, k_blk: torch.Tensor, v_blk: torch.Tensor, out_a: torch.Tensor, lse_a: torch.Tensor,

@@ -218,11 +218,25 @@ class _CacheBase:
         else:
             self._kprep = self._vprep = None
 
-    def _prefill_attention(self, q, k, v, dev_spans=None):
+    def _prefill_attention(self, q, k, v, dev_spans=None, return_lse=False):
         """Causal attention of the prompt on its own fp16 K/V (reference: repeat_kv + torch SDPA, pq_utils.py:249-260):
         the MFMA flash kernel of this library (csrc/prefill.hip), the G query heads of a kv head sharing its K/V tiles.
-        dev_spans: the per-request lengths of a ragged batch (ops.prefill_attn)."""
+        dev_spans: the per-request lengths of a ragged batch (ops.prefill_attn).  return_lse: (out, lse), lse fp32 (bs, nh, n) -
+        every row's log-sum-exp over the keys it saw (million_prefill_attn_lse; `out` is bitwise the call without it)."""
+        if return_lse:
+            return ops.prefill_attn(q, k, v, causal=True, dev_spans=dev_spans, return_lse=True)
         return ops.prefill_attn(q, k, v, causal=True, dev_spans=dev_spans)
+
+    @staticmethod
+    def _chunk_op(who, route, wide=False):
+        """The chunk-attention op of an extend call.  route None / "chunk": chunk attention over the codes (ops.pq_chunk_attn, or
+        pq_chunk_attn_wide for uint16 codes); "blocks": the block route (ops.pq_chunk_attn_blocks: the past dequantised block by block
+        into a bounded scratch and attended by the prompt kernel - for long chunks, profiles/chunk_blocks.txt)."""
+        if route is None or route == "chunk":
+            return ops.pq_chunk_attn_wide if wide else ops.pq_chunk_attn
+        if route == "blocks":
+            return ops.pq_chunk_attn_blocks
+        raise ValueError(f"{who}: route={route!r} (None, 'chunk' or 'blocks')")
 
 
 class DynamicPQCache(_CacheBase):
@@ -279,10 +293,10 @@ class DynamicPQCache(_CacheBase):
         ops.pq_encode_into(X[1], self.value_cent, self._v_store[layer_idx], token_start=T, n=n, prepared=self._vprep)
         self._T[layer_idx] = T + n
 
-    def prefill(self, query_states, key_states, value_states, layer_idx, distort_recent=False):
+    def prefill(self, query_states, key_states, value_states, layer_idx, distort_recent=False, return_lse=False):
         """distort_recent=True attends to the DEQUANTISED prompt (perplexity-style evaluation of the quantiser,
         pq_utils.py:222-260 docstring); leave it False when serving.  The attention sees the prompt only: on a cache that
-        already holds tokens use extend()."""
+        already holds tokens use extend().  return_lse: (out, lse) (_prefill_attention)."""
         n = key_states.size(2)
         T0 = self._T[layer_idx]
         self._append_codes((key_states, value_states), layer_idx, n)       # pq_utils.py:235-240
@@ -290,7 +304,7 @@ class DynamicPQCache(_CacheBase):
         if distort_recent:                                                 # :242-246
             key_states = ops.pq_decode(self._k_store[layer_idx][:, :, T0:T0 + n], self.key_cent)
             value_states = ops.pq_decode(self._v_store[layer_idx][:, :, T0:T0 + n], self.value_cent)
-        return self._prefill_attention(query_states, key_states, value_states)
+        return self._prefill_attention(query_states, key_states, value_states, **({"return_lse": True} if return_lse else {}))
 
     def update(self, key_states, value_states, layer_idx, distort_recent=False):
         """The reference's non-kernel path (pq_utils.py:166-220), DynamicCache-compatible: encode and store the new
@@ -342,13 +356,15 @@ class DynamicPQCache(_CacheBase):
                                   r, M=self.M, C=self.C, n_tokens=self._T[layer_idx], k_new=key_states,
                                   v_new=value_states, workspace=self._ws)
 
-    def extend(self, query_states, key_states, value_states, layer_idx):
+    def extend(self, query_states, key_states, value_states, layer_idx, route=None):
         """n new tokens of one layer on a cache that may already hold tokens (a later turn of a conversation, the next chunk
         of a prompt): returns their attention over [the PQ codes; the residual window; the new rows, causally]
         (million_pq_chunk_attn: the past is read as codes, never as fp16), then leaves the cache as prefill() of the
         whole sequence would have - the window rows and then the new rows are encoded behind T, the window is empty.
         On an empty cache this is prefill().  nbits 9 .. 12: the same over the uint16 store and the codebooks as they are
-        (million_pq_chunk_attn_wide); nbits 13 .. 16 have no chunk kernel."""
+        (million_pq_chunk_attn_wide); nbits 13 .. 16 have no chunk kernel.  route="blocks": the attention by
+        blocks through the prompt kernel (_chunk_op) - at nbits 9 .. 12 too - followed by the same store."""
+        attend = self._chunk_op("extend", route, wide=self.nbits > 8)
         if self.nbits > 12:
             raise NotImplementedError(f"extend: nbits={self.nbits}: the chunk-attention kernels read uint8 codes (nbits <= 8) or "
                                       "uint16 codes of nbits 9 .. 12")
@@ -358,11 +374,11 @@ class DynamicPQCache(_CacheBase):
         n = key_states.size(2)
         kres, vres = self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx]
         if self.nbits > 8:
-            out = ops.pq_chunk_attn_wide(query_states, key_states, value_states, self._k_store[layer_idx], self._v_store[layer_idx],
-                                         self.key_cent, self.value_cent, kres, vres, r, M=self.M, C=self.C, n_tokens=T)
+            out = attend(query_states, key_states, value_states, self._k_store[layer_idx], self._v_store[layer_idx],
+                         self.key_cent, self.value_cent, kres, vres, r, M=self.M, C=self.C, n_tokens=T)
         else:
-            out = ops.pq_chunk_attn(query_states, key_states, value_states, self._k_store[layer_idx], self._v_store[layer_idx],
-                                    self._kprep, self._vprep, kres, vres, r, M=self.M, C=self.C, n_tokens=T)
+            out = attend(query_states, key_states, value_states, self._k_store[layer_idx], self._v_store[layer_idx],
+                         self._kprep, self._vprep, kres, vres, r, M=self.M, C=self.C, n_tokens=T)
         if T + r + n > self.max_tokens:
             raise RuntimeError(f"DynamicPQCache: {T + r + n} tokens exceed max_tokens={self.max_tokens}")
         if r:
@@ -687,24 +703,25 @@ class PagedPQCache(_CacheBase):
             self._note_window_emptied(layer_idx, sel)
             self._note_stored(layer_idx, n_new[b], sel)
 
-    def prefill(self, query_states, key_states, value_states, layer_idx, distort_recent=False):
+    def prefill(self, query_states, key_states, value_states, layer_idx, distort_recent=False, return_lse=False):
         """Bulk encode of the prompt straight into pages (reference paged_pq_utils.py:216-320: encode,
         torch.cat, per-page permute+contiguous); the residual window stays empty.  The attention sees the
-        prompt only: on a cache that already holds tokens use extend()."""
+        prompt only: on a cache that already holds tokens use extend().  return_lse: (out, lse), lse fp32 (bs, nh, n) over the
+        whole prompt - with sinks too: they lie inside the prompt."""
         if not self._lockstep(layer_idx):
             raise RuntimeError("PagedPQCache.prefill: requests are at different lengths; use prefill_request(b, ...)")
         self._store(key_states, value_states, layer_idx, key_states.size(2))
-        return self._prefill_attention(query_states, key_states, value_states)
+        return self._prefill_attention(query_states, key_states, value_states, **({"return_lse": True} if return_lse else {}))
 
-    def prefill_request(self, b, query_states, key_states, value_states, layer_idx):
+    def prefill_request(self, b, query_states, key_states, value_states, layer_idx, return_lse=False):
         """The prompt of ONE request (tensors of batch 1) into batch slot b, the other slots untouched - a recycled slot
-        (release) starts its next request while the rest of the batch keeps decoding."""
+        (release) starts its next request while the rest of the batch keeps decoding.  return_lse: (out, lse) as prefill()."""
         if key_states.size(0) != 1 or self._T_a[layer_idx, b] or self._r_a[layer_idx, b] or self._sink_a[layer_idx, b]:
             raise RuntimeError("prefill_request: tensors of batch 1 into an empty slot (release it first)")
         self._store(key_states, value_states, layer_idx, key_states.size(2), b, all_rows=True)      # (every device row: as ever)
-        return self._prefill_attention(query_states, key_states, value_states)
+        return self._prefill_attention(query_states, key_states, value_states, **({"return_lse": True} if return_lse else {}))
 
-    def prefill_ragged(self, query_states, key_states, value_states, layer_idx, n_new, device_store=False):
+    def prefill_ragged(self, query_states, key_states, value_states, layer_idx, n_new, device_store=False, return_lse=False):
         """prefill_request() for every slot in ONE attention launch - the counterpart of extend_ragged for empty slots, at
         the prompt kernel's rate: tensors of batch bs padded to n = max(n_new) rows, slot b owns the first n_new[b] of them
         (n_new: bs host ints in [0, n]).  A slot with n_new[b] > 0 must be empty (T = r = 0; a slot that holds tokens takes
@@ -713,7 +730,8 @@ class PagedPQCache(_CacheBase):
         exactly as prefill_request(b, ...) with its own rows leaves it (pages, host lengths, its device row).  A slot with
         n_new[b] = 0 takes no part: host and device lengths, pages and window stay as they are (it may be mid-decode).
         device_store=True: the per-slot encodes and length copies are ONE ops.pq_store_ragged call behind the attention launch
-        (an int32 device copy of n_new beside `lengths[layer_idx]`): same pages, same codes, same host and device lengths."""
+        (an int32 device copy of n_new beside `lengths[layer_idx]`): same pages, same codes, same host and device lengths.
+        return_lse: (out, lse), lse fp32 (bs, nh, n); -inf in the rows past n_new[b]."""
         self._no_wide("prefill_ragged")
         n_new = [int(x) for x in n_new]
         n = query_states.size(2)
@@ -733,7 +751,7 @@ class PagedPQCache(_CacheBase):
         if device_store:
             self._reserve_ragged(layer_idx, n_new)
         spans = torch.tensor([[x, x, 0, 0] for x in n_new], dtype=torch.int32).to(self.device)
-        out = self._prefill_attention(query_states, key_states, value_states, dev_spans=spans)
+        out = self._prefill_attention(query_states, key_states, value_states, dev_spans=spans, **({"return_lse": True} if return_lse else {}))
         if device_store:
             self._store_ragged(key_states, value_states, layer_idx, n_new, torch.tensor(n_new, dtype=torch.int32).to(self.device))
             return out
@@ -762,9 +780,11 @@ class PagedPQCache(_CacheBase):
             torch.cuda.current_stream().wait_stream(self._side)
         self._pre_a[layer_idx, slice(None) if b is None else b] = 0
 
-    def _extend_slot(self, query_states, key_states, value_states, layer_idx, b, return_lse=False, all_rows=False):
+    def _extend_slot(self, query_states, key_states, value_states, layer_idx, b, return_lse=False, all_rows=False, route=None):
         """b = None: every request (lockstep); else request b with batch-1 tensors.  return_lse: (out, lse) of the chunk
-        attention (ops.pq_chunk_attn); all_rows: every device row of the layer is rewritten, as prefill_request does."""
+        attention (ops.pq_chunk_attn); all_rows: every device row of the layer is rewritten, as prefill_request does.
+        route: the attention op (_chunk_op); its (out, lse) goes into the sink merge and the store follows, whichever it is."""
+        attend = self._chunk_op("extend", route)
         i, sel = (0, slice(None)) if b is None else (b, slice(b, b + 1))
         T, r, rs = int(self._T_a[layer_idx, i]), int(self._r_a[layer_idx, i]), int(self._rs_a[layer_idx, i])
         n = key_states.size(2)
@@ -772,39 +792,44 @@ class PagedPQCache(_CacheBase):
             raise RuntimeError(f"PagedPQCache: {T + r + n} tokens exceed max_tokens={self.max_tokens}")
         ids = self.page_ids[layer_idx][sel]
         sinks = bool(self.sink_tokens)
-        out = ops.pq_chunk_attn(query_states, key_states, value_states, self.key_page_pool, self.value_page_pool, self._kprep,
-                                self._vprep, self.key_residual_cache[layer_idx][sel], self.value_residual_cache[layer_idx][sel], r,
-                                M=self.M, C=self.C, n_tokens=T, resid_start=rs, k_page_ids=ids, v_page_ids=ids,
-                                page_size=self.page_size, **({"return_lse": True} if return_lse or sinks else {}))
+        out = attend(query_states, key_states, value_states, self.key_page_pool, self.value_page_pool, self._kprep,
+                     self._vprep, self.key_residual_cache[layer_idx][sel], self.value_residual_cache[layer_idx][sel], r,
+                     M=self.M, C=self.C, n_tokens=T, resid_start=rs, k_page_ids=ids, v_page_ids=ids,
+                     page_size=self.page_size, **({"return_lse": True} if return_lse or sinks else {}))
         if sinks:      # before the store: a request's first chunk has its sinks among the chunk rows, and none kept yet
             self._sink_merge(layer_idx, query_states, out[0], out[1], sel)
             out = out if return_lse else out[0]
         self._store(key_states, value_states, layer_idx, n, b, all_rows=all_rows)      # the window in ring order, then the new rows
         return out
 
-    def extend(self, query_states, key_states, value_states, layer_idx):
+    def extend(self, query_states, key_states, value_states, layer_idx, route=None):
         """n new tokens of one layer, every request in lockstep (a later turn of the conversations, the next chunk of their
         prompts): returns their attention over [the PQ codes in the pages; the residual window; the new rows, causally]
         (million_pq_chunk_attn: the past is read as codes, never as fp16), then leaves the cache exactly as prefill() of
         the whole sequence would have - the window rows (in ring order) and then the new rows are encoded into the pages
         behind T, the window is emptied (r = 0, resid_start = 0), host and device lengths advance.  Pending encode-ahead
         work of the layer (begin_step, flush_ahead) is joined first and its flags cleared: rows encoded ahead are encoded
-        again into the same pages with the same codes.  On an empty cache this is prefill()."""
+        again into the same pages with the same codes.  On an empty cache this is prefill().
+        route: None / "chunk": chunk attention as above; "blocks": the same attention by blocks through the prompt kernel
+        (ops.pq_chunk_attn_blocks, DESIGN.md 4.16: for long chunks), followed by the same store."""
         self._no_wide("extend")
+        self._chunk_op("extend", route)      # a route that does not exist is said first
         if not self._lockstep(layer_idx):
             raise RuntimeError("PagedPQCache.extend: requests are at different lengths; use extend_request(b, ...)")
         self._join_side(layer_idx)
         if self._T_a[layer_idx, 0] == 0 and self._r_a[layer_idx, 0] == 0 and not self._sink_a[layer_idx].any():
             return self.prefill(query_states, key_states, value_states, layer_idx)
-        return self._extend_slot(query_states, key_states, value_states, layer_idx, None)
+        return self._extend_slot(query_states, key_states, value_states, layer_idx, None, route=route)
 
-    def extend_request(self, b, query_states, key_states, value_states, layer_idx, return_lse=False):
+    def extend_request(self, b, query_states, key_states, value_states, layer_idx, return_lse=False, route=None):
         """extend() for ONE request (tensors of batch 1) in slot b; the other slots, their host and device lengths, are not
         touched (they may keep decoding with use_dev_lengths=True).  On an empty slot this is prefill_request().
         return_lse=True: returns (out, lse), lse fp32 (1, nh, n) - every row's log-sum-exp over the keys it saw
         (ops.pq_chunk_attn).  The prompt kernel has none, so an empty slot is then served by chunk attention over the chunk
-        alone, followed by the same store: the slot, the pages and every length are left as prefill_request leaves them."""
+        alone, followed by the same store: the slot, the pages and every length are left as prefill_request leaves them.
+        route: as extend(); an empty slot keeps its present routes whatever it says."""
         self._no_wide("extend_request")
+        self._chunk_op("extend_request", route)
         if key_states.size(0) != 1 or query_states.size(0) != 1:
             raise RuntimeError("extend_request: tensors of batch 1")
         self._join_side(layer_idx, b)
@@ -812,7 +837,7 @@ class PagedPQCache(_CacheBase):
             if return_lse:
                 return self._extend_slot(query_states, key_states, value_states, layer_idx, b, return_lse=True, all_rows=True)
             return self.prefill_request(b, query_states, key_states, value_states, layer_idx)
-        return self._extend_slot(query_states, key_states, value_states, layer_idx, b, return_lse=return_lse)
+        return self._extend_slot(query_states, key_states, value_states, layer_idx, b, return_lse=return_lse, route=route)
 
     def extend_ragged(self, query_states, key_states, value_states, layer_idx, n_new, device_store=False):
         """extend_request() for every slot in ONE attention launch: tensors of batch bs padded to n_q = max(n_new) rows,
