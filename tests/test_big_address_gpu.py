@@ -98,8 +98,9 @@ def _far_table(torch, ids_c, page_bytes, seed, i64=False):
     return fid, _cu(torch, tab.astype(np.int64 if i64 else np.int32))
 
 
-def _far_pools(torch, far, ps, M, kpool_c, vpool_c, fid):
-    kbig, vbig = BA.pool_view(far[0], ps * M, (ps, M)), BA.pool_view(far[1], ps * M, (M, ps))
+def _far_pools(torch, far, ps, M, kpool_c, vpool_c, fid, code_bytes=1):
+    B = ps * M * code_bytes
+    kbig, vbig = BA.pool_view(far[0], B, (ps, M), code_bytes=code_bytes), BA.pool_view(far[1], B, (M, ps), code_bytes=code_bytes)
     BA.scatter_pool(kbig, kpool_c, fid)
     BA.scatter_pool(vbig, vpool_c, fid)
     return kbig, vbig
