@@ -122,8 +122,12 @@ __device__ __forceinline__ void lean_load_res_tile(const AttnParams &p, int bh, 
 // FL: which run-time extras the instance carries (the BASELINE shapes' instances carry none: this code runs from a cold instruction
 // cache and every branch of its prologue is on the launch's critical path - 0.25 us per launch with both compiled in everywhere):
 //   1 = may be given 128 centroids (p.C): the LDS copy spreads the K rows;  2 = may run as query-head parts (AttnParams::nhk_real)
-template <int MODE, int MS = 64, int DD = 128, int DR = DD, int FL = 0, bool LSE = false>      // LSE: common.h, "Log-sum-exp"
+// MODE_: the layout mode of the launch front (attn_front.h), or 3 = mode 0 as a READ-ONCE launch: 64-token pages and one part per
+// kv head (plan_attn_mfma) - whole-line code requests with the non-temporal hint, see `once` below
+template <int MODE_, int MS = 64, int DD = 128, int DR = DD, int FL = 0, bool LSE = false>      // LSE: common.h, "Log-sum-exp"
 __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
+    constexpr int MODE = MODE_ == 3 ? 0 : MODE_;
+    constexpr bool once = MODE_ == 3;
     static_assert((DD == 128 && (MS == 64 || MS == 32)) || (DD == 64 && (MS == 32 || MS == 16)), "lean kernel: d_m = 2 or 4 at d = 128 / 64");
     static_assert(DR == DD || (DR == 64 && DD == 128 && MS == 64), "lean kernel: the padded form is d = 64 / M = 64 only");
     constexpr bool PAD = DR != DD;
@@ -204,10 +208,41 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
     // ---- one unit's 16-byte requests into ring slot SL ----
     LeanUnit<NQ> ring[RING];
     const unsigned k_lane_off = (unsigned)lane << kLog2M;
-    // V, d_m = 2: x even reads subspace row 16 (kg & 1) + n, x odd the other 16 of the pair's 32; + 32 subspace rows per pi
+    // Read-once launches (`once`: an instance of its own - behind a run-time branch hipcc either joins the two request forms into
+    // one load of a selected per-lane address, without the hint, or orders them behind each other with vmcnt(0 .. 3) waits that
+    // drain the ring): fully paged codes in 64-token pages, one part per kv head.  A unit is then a K page
+    // and a V page of 64 M bytes each that this wave alone reads, once per step, and every wave request takes 1 KiB of it whole -
+    // eight 128-byte lines that no other request touches - with the non-temporal hint: the lines bypass the L1, which has no partial
+    // requests left to merge (the hint on the lane = token requests doubles the L1 -> L2 requests of a launch: 549 k -> 1074 k).
+    // Measured, not explained in full: back-to-back launches over rotating layers are 7 - 11 % shorter with shape + hint and
+    // unchanged with the shape alone, L2 hits / misses and HBM bytes per launch do not move, and ONE launch at a time is not shorter
+    // (profiles/ab_decode_code_stream.txt).  The codebooks, page ids, query, window rows and the tail keep the default policy.
+    //   K: request q takes tokens (64 / NQ) q .. whole: lane (j, a = lane % (64 / NQ)) bytes [16 j, 16 j + 16) of token (64 / NQ) q + a;
+    //      LEAN_K_LANE_IS_TOKEN turns the slot into the lane = token form (register q = bytes [16 q, 16 q + 16) of token `lane`)
+    //      where it is first consumed: the exchange of the register index with lane bits 5:4 (NQ = 2: bit 5) by row swaps;
+    //   V, d_m = 2: x even takes subspace rows n of the pair's 32, x odd rows 16 + n, for every token group; VG picks the register
+    //      of the lane's parity (v_sel) - the word the other shape loaded into ring.v[x].  d_m = 4 requests are whole rows already.
+    // 128-token pages (a line belongs to two waves' units), query-head parts (the second part re-reads the page from L2) and
+    // row-major K keep the lane = token requests and the default policy.
+#if MILLION_EXP & 8192       // (A/B: the hint on the lane = token requests)
+    constexpr bool kWhole = false;
+#else
+    constexpr bool kWhole = true;
+#endif
+#if MILLION_EXP & 65536      // (A/B: no hint)
+#define LEAN_LD_ONCE(P) (*(P))
+#else
+#define LEAN_LD_ONCE(P) __builtin_nontemporal_load(P)
+#endif
+    constexpr unsigned kReqStep = kWhole ? 1024u : 16u;      // bytes between a unit's K requests
+    const unsigned k_once_off = kWhole ? (((unsigned)lane & (64 / NQ - 1)) << kLog2M) + 16u * ((unsigned)lane / (64 / NQ)) : k_lane_off;
+    const bool v_sel = (kg & 1) != 0;
+    // V, d_m = 2: x even reads subspace row 16 (kg & 1) + n, x odd the other 16 of the pair's 32 (whole-line requests: n and
+    //    16 + n in every token group); + 32 subspace rows per pi
     //    d_m = 4: tile x reads subspace row n + 16 x
-    const unsigned v_lane_off1 = ((unsigned)(n16 + (DM2 ? 16 * (kg & 1) : 0)) << p.ps_shift) + 16u * kg;
-    const unsigned v_lane_off2 = ((unsigned)(n16 + (DM2 ? 16 * (1 - (kg & 1)) : 16)) << p.ps_shift) + 16u * kg;
+    constexpr bool v_rows = kWhole && once;
+    const unsigned v_lane_off1 = ((unsigned)(n16 + (DM2 && !v_rows ? 16 * (kg & 1) : 0)) << p.ps_shift) + 16u * kg;
+    const unsigned v_lane_off2 = ((unsigned)(n16 + (DM2 && !v_rows ? 16 * (1 - (kg & 1)) : 16)) << p.ps_shift) + 16u * kg;
 #define UNIT_REQ_K(SL, J)                                                                                          \
     {                                                                                                              \
         const int jc_ = LAUNCH_FRONT_ROUND(J);                                                                     \
@@ -215,7 +250,11 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
         if (k_paged) {                                                                                             \
             const long long pk_ = (long long)__builtin_amdgcn_readlane(vpk, jc_);                                  \
             kb_ = uniform_ptr(p.k_codes + (((pk_ << p.ps_shift) + tin) << kLog2M));                                \
-            _Pragma("unroll") for (int q_ = 0; q_ < NQ; ++q_) ring[SL].k[q_] = *(gptr_v4u)(kb_ + k_lane_off + 16u * q_); \
+            if constexpr (once) {                                                                                  \
+                _Pragma("unroll") for (int q_ = 0; q_ < NQ; ++q_) ring[SL].k[q_] = LEAN_LD_ONCE((gptr_v4u)(kb_ + k_once_off + kReqStep * q_)); \
+            } else {                                                                                               \
+                _Pragma("unroll") for (int q_ = 0; q_ < NQ; ++q_) ring[SL].k[q_] = *(gptr_v4u)(kb_ + k_lane_off + 16u * q_); \
+            }                                                                                                      \
         } else {      /* row-major K: absolute row per lane, rows past T - 1 re-read it (masked later) */          \
             const int tu_ = t0 + jc_ * t_step;                                                                     \
             kb_ = uniform_ptr(p.k_codes + b * p.k_sb + hkr * p.k_sh);                                              \
@@ -228,10 +267,33 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
         const int jc_ = LAUNCH_FRONT_ROUND(J);                                                                     \
         const long long pv_ = (long long)__builtin_amdgcn_readlane(vpv, jc_);                                      \
         const gptr_u8 vb_ = uniform_ptr(p.v_codes + (pv_ << (kLog2M + p.ps_shift)) + tin);                         \
-        _Pragma("unroll") for (int x_ = 0; x_ < NQ; ++x_)                                                          \
-            ring[SL].v[x_] = *(gptr_v4u)(vb_ + ((x_ & 1) ? v_lane_off2 : v_lane_off1) + ((32u * (x_ >> 1)) << p.ps_shift)); \
+        if constexpr (once) {      /* 64-token pages: 32 subspace rows = 2 KiB */                                  \
+            _Pragma("unroll") for (int x_ = 0; x_ < NQ; ++x_)                                                      \
+                ring[SL].v[x_] = LEAN_LD_ONCE((gptr_v4u)(vb_ + ((x_ & 1) ? v_lane_off2 : v_lane_off1) + 2048u * (x_ >> 1))); \
+        } else {                                                                                                   \
+            _Pragma("unroll") for (int x_ = 0; x_ < NQ; ++x_)                                                      \
+                ring[SL].v[x_] = *(gptr_v4u)(vb_ + ((x_ & 1) ? v_lane_off2 : v_lane_off1) + ((32u * (x_ >> 1)) << p.ps_shift)); \
+        }                                                                                                          \
     }
 #define UNIT_REQ(SL, J) { UNIT_REQ_K(SL, J) UNIT_REQ_V(SL, J) }
+    // whole-line K requests -> lane = token: register q of lane row j <-> register j of lane row q (rows of 16 lanes; NQ = 2:
+    // halves of 32).  v_permlane32_swap exchanges the upper half of its first operand with the lower half of its second,
+    // v_permlane16_swap the odd rows of the first with the even rows of the second: one swap per dword and register pair
+#define LEAN_K_LANE_IS_TOKEN(SL)                                                                                   \
+    if constexpr (kWhole && NQ > 1 && once) {                                                                      \
+        _Pragma("unroll") for (int c_ = 0; c_ < 4; ++c_) {                                                         \
+            _Pragma("unroll") for (int q_ = 0; q_ < NQ / 2; ++q_) {                                                \
+                const auto r_ = __builtin_amdgcn_permlane32_swap(ring[SL].k[q_][c_], ring[SL].k[(q_ + NQ / 2) & (NQ - 1)][c_], false, false); \
+                ring[SL].k[q_][c_] = r_[0]; ring[SL].k[(q_ + NQ / 2) & (NQ - 1)][c_] = r_[1];                      \
+            }                                                                                                      \
+            if constexpr (NQ == 4) {                                                                               \
+                _Pragma("unroll") for (int q_ = 0; q_ < 4; q_ += 2) {                                              \
+                    const auto r_ = __builtin_amdgcn_permlane16_swap(ring[SL].k[q_][c_], ring[SL].k[(q_ + 1) & (NQ - 1)][c_], false, false); \
+                    ring[SL].k[q_][c_] = r_[0]; ring[SL].k[(q_ + 1) & (NQ - 1)][c_] = r_[1];                       \
+                }                                                                                                  \
+            }                                                                                                      \
+        }                                                                                                          \
+    }
     // only unit 0 (8 KiB per wave at M = 64 - what the streaming kernel asks for up front) goes out before the codebooks are in LDS:
     // the CU's request queue is in order, and what is asked for in front of the barrier delays it (both units up front: +1.3 us at
     // one request).  (Its K bytes in the coalesced shape of the streaming kernel + a 4 x 4 in-register transpose by row swaps:
@@ -431,7 +493,8 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
 #define VG(SL, I)                                                                                                  \
     {                                                                                                              \
         if constexpr (DM2) {                                                                                       \
-            const unsigned w_ = ring[SL].v[(2 * V_LO(I) + V_MID(I)) & (NQ - 1)][V_S(I)];                           \
+            unsigned w_ = ring[SL].v[(2 * V_LO(I) + V_MID(I)) & (NQ - 1)][V_S(I)];                                 \
+            if constexpr (v_rows) w_ = v_sel ? ring[SL].v[((2 * V_LO(I) + V_MID(I)) ^ 1) & (NQ - 1)][V_S(I)] : w_; \
             const unsigned vc_ = V_MID(I) ? vcz1 : vcz0;                                                           \
             e[(I) & 3][0] = lds32(__builtin_amdgcn_perm(w_, vc_, 0x03020400u) + 128u * V_LO(I));                   \
             e[(I) & 3][1] = lds32(__builtin_amdgcn_perm(w_, vc_, 0x03020500u) + 128u * V_LO(I));                   \
@@ -531,6 +594,7 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
         KG((2 * (I) + 3 < NK ? BL_SLN : BL_SL), (2 * (I) + 3) & (NK - 1))                                          \
         __builtin_amdgcn_sched_barrier(0);                                                                         \
         KM(2 * (I) + 1)                                                                                            \
+        if constexpr (2 * (I) + 4 == NK) LEAN_K_LANE_IS_TOKEN(BL_SL)      /* round bl_j + 2: its first gather follows */ \
         KG((2 * (I) + 4 < NK ? BL_SLN : BL_SL), (2 * (I) + 4) & (NK - 1))                                          \
         __builtin_amdgcn_sched_barrier(0);                                                                         \
         if ((I) == NV - 3) UNIT_REQ_V(BL_SL, bl_j + RING)                                                          \
@@ -570,6 +634,7 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
     tail_mark_xcd(p, bh, split, wave, lane);      // this split's slot of the XCD census
     int bl_j = 0;
     {
+        LEAN_K_LANE_IS_TOKEN(0)
         KG(0, 0) KG(0, 1) KG(0, 2) KG(0, 3) KG(0, 4) KG(0, 5)
         FOR_NK(SA_STEP)
         SOFTMAX(0)      // (a wave without units: every score is masked to -inf, every probability 0)
@@ -578,6 +643,7 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
     if (n_mine > 0) {
         VG(0, 0) VG(0, 1)
         if (nb > 0) {
+            LEAN_K_LANE_IS_TOKEN(1)
             KG(1, 0) KG(1, 1) KG(1, 2)
             // blocks 0 .. nb - 2 request round bl_j + 2, which exists; block nb - 1 is a BLOCK_LAST.  Pairs (slot 0, slot 1) while
             // two requesting blocks remain; the odd one out (slot 0) leaves the loop in the middle.  (hipcc joins the wait state
@@ -653,6 +719,8 @@ __global__ __launch_bounds__(kNW * 64, 2) void attn_lean_kernel(AttnParams p) {
 #undef UNIT_REQ
 #undef UNIT_REQ_K
 #undef UNIT_REQ_V
+#undef LEAN_K_LANE_IS_TOKEN
+#undef LEAN_LD_ONCE
     STAMP(3);
     // the tail wants head g's reference in lane g and row sums that rows_sum() completes: add up the head's four lanes of a row
     float l_row = s_l;

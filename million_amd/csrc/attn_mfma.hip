@@ -157,7 +157,9 @@ static int mfma_splits(const AttnParams &p, int cus) {
 static bool mfma_stream_ok(const AttnParams &p, int ns) { return p.T > 0 && (p.T + ns * 256 - 1) / (ns * 256) <= 64; }
 
 // The instances this file launches, by form and layout mode (0: paged K with int32 ids and V through its id table, 1: row-major
-// K with dense V pages, 2: anything else).  The C = 128 forms have one instance for every mode.  The rows
+// K with dense V pages, 2: anything else, 3: mode 0 as a read-once launch - 64-token pages, one part per kv head: the lean kernel's
+// whole-line code requests with the non-temporal hint, attn_lean.h; the streaming kernel has no such form: its mode 0 instance).
+// The C = 128 forms have one instance for every mode.  The rows
 // keep the order in which the instances were first named before this table: it is their order in the code object.
 enum MfmaForm {
     kStream64, kStream32, kStream32D4, kStream16,                       // streaming kernel (D4: the d_m = 4 form of M = 32; M = 16: d_m = 8)
@@ -166,39 +168,39 @@ enum MfmaForm {
     kLeanD64M32, kLeanD64M16, kLeanD64M64,                              // lean kernel, d = 64
     kMfmaForms
 };
-#define MFMA_ONE(...) {(const void *)__VA_ARGS__, (const void *)__VA_ARGS__, (const void *)__VA_ARGS__}
-static const void *const kMfmaKernels[kMfmaForms][3] = {
-    {(const void *)attn_stream_kernel<64, 0>, (const void *)attn_stream_kernel<64, 1>, (const void *)attn_stream_kernel<64, 2>},
-    {(const void *)attn_stream_kernel<32, 0>, (const void *)attn_stream_kernel<32, 1>, (const void *)attn_stream_kernel<32, 2>},
-    {(const void *)attn_stream_kernel<320, 0>, (const void *)attn_stream_kernel<320, 1>, (const void *)attn_stream_kernel<320, 2>},
-    {(const void *)attn_stream_kernel<16, 0>, (const void *)attn_stream_kernel<16, 1>, (const void *)attn_stream_kernel<16, 2>},
+#define MFMA_ONE(...) {(const void *)__VA_ARGS__, (const void *)__VA_ARGS__, (const void *)__VA_ARGS__, (const void *)__VA_ARGS__}
+static const void *const kMfmaKernels[kMfmaForms][4] = {
+    {(const void *)attn_stream_kernel<64, 0>, (const void *)attn_stream_kernel<64, 1>, (const void *)attn_stream_kernel<64, 2>, (const void *)attn_stream_kernel<64, 0>},
+    {(const void *)attn_stream_kernel<32, 0>, (const void *)attn_stream_kernel<32, 1>, (const void *)attn_stream_kernel<32, 2>, (const void *)attn_stream_kernel<32, 0>},
+    {(const void *)attn_stream_kernel<320, 0>, (const void *)attn_stream_kernel<320, 1>, (const void *)attn_stream_kernel<320, 2>, (const void *)attn_stream_kernel<320, 0>},
+    {(const void *)attn_stream_kernel<16, 0>, (const void *)attn_stream_kernel<16, 1>, (const void *)attn_stream_kernel<16, 2>, (const void *)attn_stream_kernel<16, 0>},
     MFMA_ONE(attn_stream_kernel<16, 2, 7>),
     MFMA_ONE(attn_stream_kernel<64, 2, 7>),
     MFMA_ONE(attn_stream_kernel<32, 2, 7>),
-    {(const void *)attn_lean_kernel<0>, (const void *)attn_lean_kernel<1>, (const void *)attn_lean_kernel<2>},
+    {(const void *)attn_lean_kernel<0>, (const void *)attn_lean_kernel<1>, (const void *)attn_lean_kernel<2>, (const void *)attn_lean_kernel<3>},
     MFMA_ONE(attn_lean_kernel<2, 64, 128, 128, 1>),
-    {(const void *)attn_lean_kernel<0, 32>, (const void *)attn_lean_kernel<1, 32>, (const void *)attn_lean_kernel<2, 32>},
+    {(const void *)attn_lean_kernel<0, 32>, (const void *)attn_lean_kernel<1, 32>, (const void *)attn_lean_kernel<2, 32>, (const void *)attn_lean_kernel<3, 32>},
     MFMA_ONE(attn_lean_kernel<2, 32, 128, 128, 1>),
-    {(const void *)attn_lean_kernel<0, 32, 64, 64, 3>, (const void *)attn_lean_kernel<1, 32, 64, 64, 3>, (const void *)attn_lean_kernel<2, 32, 64, 64, 3>},
-    {(const void *)attn_lean_kernel<0, 16, 64, 64, 3>, (const void *)attn_lean_kernel<1, 16, 64, 64, 3>, (const void *)attn_lean_kernel<2, 16, 64, 64, 3>},
-    {(const void *)attn_lean_kernel<0, 64, 128, 64, 3>, (const void *)attn_lean_kernel<1, 64, 128, 64, 3>, (const void *)attn_lean_kernel<2, 64, 128, 64, 3>},
+    {(const void *)attn_lean_kernel<0, 32, 64, 64, 3>, (const void *)attn_lean_kernel<1, 32, 64, 64, 3>, (const void *)attn_lean_kernel<2, 32, 64, 64, 3>, (const void *)attn_lean_kernel<3, 32, 64, 64, 3>},
+    {(const void *)attn_lean_kernel<0, 16, 64, 64, 3>, (const void *)attn_lean_kernel<1, 16, 64, 64, 3>, (const void *)attn_lean_kernel<2, 16, 64, 64, 3>, (const void *)attn_lean_kernel<3, 16, 64, 64, 3>},
+    {(const void *)attn_lean_kernel<0, 64, 128, 64, 3>, (const void *)attn_lean_kernel<1, 64, 128, 64, 3>, (const void *)attn_lean_kernel<2, 64, 128, 64, 3>, (const void *)attn_lean_kernel<3, 64, 128, 64, 3>},
 };
 // the same instances with LSE = true (common.h, "Log-sum-exp"): behind the others in the code object
-static const void *const kMfmaKernelsLse[kMfmaForms][3] = {
-    {(const void *)attn_stream_kernel<64, 0, 8, true>, (const void *)attn_stream_kernel<64, 1, 8, true>, (const void *)attn_stream_kernel<64, 2, 8, true>},
-    {(const void *)attn_stream_kernel<32, 0, 8, true>, (const void *)attn_stream_kernel<32, 1, 8, true>, (const void *)attn_stream_kernel<32, 2, 8, true>},
-    {(const void *)attn_stream_kernel<320, 0, 8, true>, (const void *)attn_stream_kernel<320, 1, 8, true>, (const void *)attn_stream_kernel<320, 2, 8, true>},
-    {(const void *)attn_stream_kernel<16, 0, 8, true>, (const void *)attn_stream_kernel<16, 1, 8, true>, (const void *)attn_stream_kernel<16, 2, 8, true>},
+static const void *const kMfmaKernelsLse[kMfmaForms][4] = {
+    {(const void *)attn_stream_kernel<64, 0, 8, true>, (const void *)attn_stream_kernel<64, 1, 8, true>, (const void *)attn_stream_kernel<64, 2, 8, true>, (const void *)attn_stream_kernel<64, 0, 8, true>},
+    {(const void *)attn_stream_kernel<32, 0, 8, true>, (const void *)attn_stream_kernel<32, 1, 8, true>, (const void *)attn_stream_kernel<32, 2, 8, true>, (const void *)attn_stream_kernel<32, 0, 8, true>},
+    {(const void *)attn_stream_kernel<320, 0, 8, true>, (const void *)attn_stream_kernel<320, 1, 8, true>, (const void *)attn_stream_kernel<320, 2, 8, true>, (const void *)attn_stream_kernel<320, 0, 8, true>},
+    {(const void *)attn_stream_kernel<16, 0, 8, true>, (const void *)attn_stream_kernel<16, 1, 8, true>, (const void *)attn_stream_kernel<16, 2, 8, true>, (const void *)attn_stream_kernel<16, 0, 8, true>},
     MFMA_ONE(attn_stream_kernel<16, 2, 7, true>),
     MFMA_ONE(attn_stream_kernel<64, 2, 7, true>),
     MFMA_ONE(attn_stream_kernel<32, 2, 7, true>),
-    {(const void *)attn_lean_kernel<0, 64, 128, 128, 0, true>, (const void *)attn_lean_kernel<1, 64, 128, 128, 0, true>, (const void *)attn_lean_kernel<2, 64, 128, 128, 0, true>},
+    {(const void *)attn_lean_kernel<0, 64, 128, 128, 0, true>, (const void *)attn_lean_kernel<1, 64, 128, 128, 0, true>, (const void *)attn_lean_kernel<2, 64, 128, 128, 0, true>, (const void *)attn_lean_kernel<3, 64, 128, 128, 0, true>},
     MFMA_ONE(attn_lean_kernel<2, 64, 128, 128, 1, true>),
-    {(const void *)attn_lean_kernel<0, 32, 128, 128, 0, true>, (const void *)attn_lean_kernel<1, 32, 128, 128, 0, true>, (const void *)attn_lean_kernel<2, 32, 128, 128, 0, true>},
+    {(const void *)attn_lean_kernel<0, 32, 128, 128, 0, true>, (const void *)attn_lean_kernel<1, 32, 128, 128, 0, true>, (const void *)attn_lean_kernel<2, 32, 128, 128, 0, true>, (const void *)attn_lean_kernel<3, 32, 128, 128, 0, true>},
     MFMA_ONE(attn_lean_kernel<2, 32, 128, 128, 1, true>),
-    {(const void *)attn_lean_kernel<0, 32, 64, 64, 3, true>, (const void *)attn_lean_kernel<1, 32, 64, 64, 3, true>, (const void *)attn_lean_kernel<2, 32, 64, 64, 3, true>},
-    {(const void *)attn_lean_kernel<0, 16, 64, 64, 3, true>, (const void *)attn_lean_kernel<1, 16, 64, 64, 3, true>, (const void *)attn_lean_kernel<2, 16, 64, 64, 3, true>},
-    {(const void *)attn_lean_kernel<0, 64, 128, 64, 3, true>, (const void *)attn_lean_kernel<1, 64, 128, 64, 3, true>, (const void *)attn_lean_kernel<2, 64, 128, 64, 3, true>},
+    {(const void *)attn_lean_kernel<0, 32, 64, 64, 3, true>, (const void *)attn_lean_kernel<1, 32, 64, 64, 3, true>, (const void *)attn_lean_kernel<2, 32, 64, 64, 3, true>, (const void *)attn_lean_kernel<3, 32, 64, 64, 3, true>},
+    {(const void *)attn_lean_kernel<0, 16, 64, 64, 3, true>, (const void *)attn_lean_kernel<1, 16, 64, 64, 3, true>, (const void *)attn_lean_kernel<2, 16, 64, 64, 3, true>, (const void *)attn_lean_kernel<3, 16, 64, 64, 3, true>},
+    {(const void *)attn_lean_kernel<0, 64, 128, 64, 3, true>, (const void *)attn_lean_kernel<1, 64, 128, 64, 3, true>, (const void *)attn_lean_kernel<2, 64, 128, 64, 3, true>, (const void *)attn_lean_kernel<3, 64, 128, 64, 3, true>},
 };
 #undef MFMA_ONE
 static void mfma_setup() {
@@ -230,7 +232,10 @@ bool plan_attn_mfma(const AttnParams &p_in, AttnPlan &plan) {
         // d_m = 4 form at M = 32 and up to 4 query heads: query heads replicated over the column groups of the score tile
         form = p.M == 64 ? kStream64 : (p.G <= 4 && !(g_mfma_form & 1)) ? kStream32D4 : kStream32;
     }
-    const int mode = (p.k_paged && !p.v_identity && !p.ids64) ? 0 : (!p.k_paged && p.v_identity) ? 1 : 2;
+    int mode = (p.k_paged && !p.v_identity && !p.ids64) ? 0 : (!p.k_paged && p.v_identity) ? 1 : 2;
+    // read-once: a unit is a whole page that one wave reads once per step (128-token pages: a line belongs to two waves' units;
+    // query-head parts: the second part re-reads the page from L2 - both keep the default policy)
+    if (mode == 0 && form >= kLean64 && p.page_size == 64 && !p.nhk_mul) mode = 3;
     const int bh = p.bs * p.nh_k;
     const int units = (p.T + 31) / 32;
     p.nsplit = ns;

@@ -14,6 +14,10 @@
 //                        LAUNCH_FRONT_ROUND), as every build did before BLOCK_LAST                  profiles/ab_decode_loadpath.txt
 //                  4096  every wave loads its own query operand (Q[], qb) from global memory instead of reading the
 //                        workgroup's image in LDS (kQOff)                                           profiles/ab_decode_loadpath.txt
+//                  8192  the read-once instances keep the lane = token code requests (partial lines, merged by the L1)
+//                 65536  the read-once instances request without the non-temporal hint
+//                        (8192: the hint on the old requests - the L1 -> L2 request blow-up, for counters only; 65536: the
+//                        whole-line requests alone; 8192 | 65536: the parent's requests in the new instances)  profiles/ab_decode_code_stream.txt
 //     attn_stream.h  32"the launch without arithmetic": every request, wait, barrier and the tail stay, a unit's bytes are
 //                        xor-ed into a sink instead of gathered, multiplied and soft-maxed         profiles/r04_launch_floor.txt
 //     prefill.hip   (the pipelined kernel only; the plain loop's round 3-4 bits are in profiles/r03_prefill.txt, r04_prefill.txt)
