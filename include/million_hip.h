@@ -516,6 +516,57 @@ int million_pq_decode_attn_wide(const million_attn_desc *desc, const void *q,
                                 void *workspace, size_t workspace_bytes, million_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Packed code pages: codes of 512 .. 4096 centroids in 10 or 12 bits instead of a uint16 each.
+ *
+ * The format.  A code is split into its low byte and h high bits: h = 2 for C in {512, 1024}, h = 4 for C in {2048, 4096} - a
+ * function of C alone (no descriptor carries it).  A page of page_size tokens and M subspaces is
+ *     page_bytes = page_size * M * (8 + h) / 8
+ * bytes: its low plane first, its high plane behind it.  A pool is a contiguous uint8 array (n_pool, page_bytes); one page id
+ * names both planes, and page pid starts at byte pid * page_bytes (no power of two: 64-bit arithmetic).
+ *   K page  low plane  (page_size, M) uint8: exactly a uint8 K page - byte (t, m) is the low byte of token t's code for subspace m;
+ *           high plane (page_size, M * h / 8) uint8: byte j of token t's row holds the subspaces j * 8/h .. j * 8/h + 8/h - 1;
+ *           bits [8, 8 + h) of subspace m's code sit at bit h * (m mod 8/h) of byte m / (8/h).
+ *   V page  low plane  (M, page_size) uint8: the transposed uint8 page - byte (m, t);
+ *           high plane (M * h / 8, page_size) uint8: byte (j, t) holds token t's fields for the subspaces j * 8/h .., in the
+ *           same bit order.
+ * Every high byte belongs to ONE token on both sides: a store of the tokens [t0, t0 + n) never reads, modifies or zeroes a byte
+ * of another token, and the bytes of tokens past the live ones may hold anything.  At C = 512 / 2048 the top bit of a field is
+ * not part of a code: the encoder writes it as 0, the readers mask it (code & (C - 1)).
+ * page_size in {32, 64, 128} and M in {16, 32, 64} keep every plane a multiple of 16 bytes.  True 9- / 11-bit packing, packed
+ * row-major codes, and chunk attention / million_pq_gather_rows / million_pq_decode over packed pages do not exist:
+ * million_pq_repack_pages is their way to and from packed pages.
+ *
+ * million_pq_encode_packed: million_pq_encode's contract - descriptor, codes bit for bit (the same scan), ring source,
+ * dev_lengths, page-table clamps - with dst_layout MILLION_CODES_KPAGES / MILLION_CODES_VPAGES meaning packed pages of the pool
+ * dst.  MILLION_CODES_ROWMAJOR, C outside {512, 1024, 2048, 4096}, M no multiple of 4, page_size not 32 / 64 / 128:
+ * MILLION_ERR_SHAPE.  dst 16-byte aligned.
+ *
+ * million_pq_decode_attn_packed: the arguments and every semantic of million_pq_decode_attn_wide - out, lse, fused append,
+ * device lengths, code & (C - 1) on every gathered index, the workspace - with k_codes / v_codes the packed pools.  The same
+ * launch shape: million_attn_wide_splits and million_attn_wide_workspace_bytes answer for it too.  `out` and lse are bitwise
+ * those of million_pq_decode_attn_wide over uint16 pools that hold the same codes.
+ *
+ * million_pq_repack_pages: n_pages whole pages, page for page, in one launch.  MILLION_REPACK_PACK: src uint16 pages ->
+ * dst packed pages (bits of a code above 8 + h are dropped); MILLION_REPACK_UNPACK: src packed pages -> dst uint16 pages.
+ * side 0: K pages ((page_size, M) uint16), side 1: V pages ((M, page_size) uint16).  Shapes as above (MILLION_ERR_SHAPE), a
+ * bad direction / side or n_pages < 0: MILLION_ERR_ARG; src and dst 16-byte aligned; n_pages = 0: MILLION_OK.  src and dst
+ * must not overlap. */
+enum {
+    MILLION_REPACK_PACK = 0,      /* uint16 pages -> packed pages */
+    MILLION_REPACK_UNPACK = 1     /* packed pages -> uint16 pages */
+};
+int million_pq_encode_packed(const million_encode_desc *desc, const void *x, const void *cents /* (M,C,d_m) fp16 */,
+                             void *dst, const int32_t *page_ids, million_stream_t stream);
+int million_pq_decode_attn_packed(const million_attn_desc *desc, const void *q,
+                                  const void *k_new, const void *v_new,       /* both NULL: no append */
+                                  const void *k_codes, const void *v_codes, const void *k_page_ids, const void *v_page_ids,
+                                  const void *k_cents, const void *v_cents,
+                                  void *k_resid, void *v_resid, void *out, float *lse /* may be NULL */,
+                                  void *workspace, size_t workspace_bytes, million_stream_t stream);
+int million_pq_repack_pages(int direction, const void *src, void *dst, int64_t n_pages, int page_size, int M, int C, int side,
+                            million_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Prompt (prefill) attention on fp16 K/V.
  * Replaces: scaled_dot_product_attention(q, repeat_kv(k), repeat_kv(v), is_causal=True) of the reference's prompt pass
  * (scripts/utils/pq_utils.py:249-260 DynamicPQCache.prefill, scripts/utils/paged_pq_utils.py:216-320

@@ -121,6 +121,7 @@ class ForkDesc(ctypes.Structure):
 
 
 MILLION_SWAP_PACK, MILLION_SWAP_UNPACK = 0, 1
+MILLION_REPACK_PACK, MILLION_REPACK_UNPACK = 0, 1
 
 
 class SwapDesc(ctypes.Structure):
@@ -163,6 +164,10 @@ SYMBOLS = {
     "million_attn_wide_splits": (c_i32, [ctypes.POINTER(AttnDesc)]),
     "million_pq_decode_attn_wide": (c_i32, [ctypes.POINTER(AttnDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                             c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "million_pq_encode_packed": (c_i32, [ctypes.POINTER(EncodeDesc), c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "million_pq_decode_attn_packed": (c_i32, [ctypes.POINTER(AttnDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                              c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_sz, c_vp]),
+    "million_pq_repack_pages": (c_i32, [c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "million_prefill_attn": (c_i32, [ctypes.POINTER(PrefillDesc), c_vp, c_vp, c_vp, c_vp, c_vp]),
     "million_prefill_attn_lse": (c_i32, [ctypes.POINTER(PrefillDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "million_chunk_attn_workspace_bytes": (c_sz, [ctypes.POINTER(ChunkAttnDesc)]),

@@ -18,6 +18,10 @@
 //   K  lane (token c16, quarter q4): the M/4 codes [q4 M/4, (q4 + 1) M/4) of its token's row = dims [q4 d/4, (q4 + 1) d/4)
 //   V  lane (tokens 4 q4 .. 4 q4 + 3, subspace 16 cg + c16): 4 codes (8 bytes of a transposed page row) per column group cg
 //   O  tile n = (cg = n / d_m, e = n % d_m): O^T[(16 cg + 4 q4 + v) d_m + e][head c16]
+//
+// Packed pages (million_hip.h, "Packed code pages"; million_pq_decode_attn_packed): the same kernel, HB = 2 / 4 high bits per
+// code beside a low byte.  The K lane loads M/4 low bytes and M HB / 32 high bytes of its token, the V lane the low dword of its 4
+// tokens and the dword of their high bytes (shared by 8 / HB lanes); a code is two shifts and an or in front of the same mask.
 #include "tile_wave.h"
 
 namespace million {
@@ -25,14 +29,19 @@ namespace million {
 constexpr int kWW = 8;      // waves per workgroup
 constexpr int kWidePF = 2;  // code tiles in flight per wave
 
-template <int D, int DM, bool LSE = false>
+// HB = 0: one uint16 per code.  HB = 2 / 4: packed pages (million_hip.h, "Packed code pages": a low-byte plane and a plane of HB
+// high bits per code) - other load_codes / kcode / vcode and a smaller Codes ring; every other line is shared.
+template <int D, int DM, bool LSE = false, int HB = 0>
 __global__ __launch_bounds__(kWW * 64, 2) void attn_wide_kernel(AttnParams p) {
     constexpr int M = D / DM;
     constexpr int NS = D / 32;                 // score stages (32 dims each)
     constexpr int KD = M / 8;                  // K code dwords per lane and tile (M/4 codes of 16 bits)
     constexpr int CG = M / 16;                 // column groups of 16 subspaces
     constexpr int EW = DM / 2;                 // dwords per codebook entry
+    constexpr int KLO = M / 16;                // packed: dwords of low bytes per K lane and tile (M/4 codes)
+    constexpr int KHB = M * HB / 32;           // packed: bytes of high bits per K lane and tile (1, 2, 4 or 8)
     static_assert(DM == 2 || DM == 4, "entries of 4 or 8 bytes");
+    static_assert(HB == 0 || HB == 2 || HB == 4, "uint16 codes, or 2 / 4 high bits beside a low byte");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     MILLION_DEBUG_FILL_LDS(smem, p.lds_fill);
 
@@ -63,7 +72,9 @@ __global__ __launch_bounds__(kWW * 64, 2) void attn_wide_kernel(AttnParams p) {
     if (!is_resid) {
         // ================= code tiles =================
         const int ps_mask = p.page_size - 1;
-        struct Codes { unsigned k[KD]; unsigned v[CG][2]; };
+        // uint16: k = the lane's M/4 codes, v[cg] = 4 tokens' codes.  Packed: k = KLO dwords of low bytes then the high bits
+        // (<= 2 dwords), v[cg] = {4 tokens' low bytes, the 4 bytes of their high fields}
+        struct Codes { unsigned k[HB ? KLO + (KHB + 3) / 4 : KD]; unsigned v[CG][2]; };
         struct Ent { unsigned k[D / 8]; unsigned v[CG][4][EW]; };      // the lane's d/4 dims of K^; 4 tokens x CG sub-vectors of V^
         const unsigned short *kc = (const unsigned short *)p.k_codes, *vc = (const unsigned short *)p.v_codes;
         auto tile_t0 = [&](int j) { return wave_tile_t0<kWW>(j, wave, n_tiles, t_begin); };
@@ -77,27 +88,70 @@ __global__ __launch_bounds__(kWW * 64, 2) void attn_wide_kernel(AttnParams p) {
             o.v = MILLION_CHECK_VID(p, (long long)vid_base[idx * id_stride]);
             return o;
         };
+        // packed pages: a page is page_size * M * (8 + HB) / 8 bytes - no power of two, so a page's offset is a 64-bit multiply
+        const long long page_bytes = (long long)p.page_size * (M * (8 + HB) / 8);
         auto load_codes = [&](int t0, Pids id) -> Codes {
             Codes c;
             const int tk_ = min(t0 + c16, t_end - 1);
-            const unsigned short *krow = kc + ((id.k << p.ps_shift) + (tk_ & ps_mask)) * M + q4 * (M / 4);
-            if constexpr (KD == 2) { const v2u w = *(const v2u *)krow; c.k[0] = w[0]; c.k[1] = w[1]; }
-            else {
+            if constexpr (HB != 0) {
+                const uint8_t *kpage = p.k_codes + id.k * page_bytes, *vpage = p.v_codes + id.v * page_bytes;
+                const uint8_t *klo = kpage + (tk_ & ps_mask) * M + q4 * (M / 4);
+                const uint8_t *khi = kpage + (p.page_size * M + (tk_ & ps_mask) * (M * HB / 8) + q4 * KHB);
+                if constexpr (KLO == 4) { const t4u w = *(const t4u *)klo; c.k[0] = w[0]; c.k[1] = w[1]; c.k[2] = w[2]; c.k[3] = w[3]; }
+                else if constexpr (KLO == 2) { const v2u w = *(const v2u *)klo; c.k[0] = w[0]; c.k[1] = w[1]; }
+                else c.k[0] = *(const unsigned *)klo;
+                if constexpr (KHB == 8) { const v2u w = *(const v2u *)khi; c.k[KLO] = w[0]; c.k[KLO + 1] = w[1]; }
+                else if constexpr (KHB == 4) c.k[KLO] = *(const unsigned *)khi;
+                else if constexpr (KHB == 2) c.k[KLO] = *(const unsigned short *)khi;
+                else c.k[KLO] = *khi;
+                // V: the low dword of 4 tokens of the lane's subspace, and the dword of their high bytes, which 8 / HB
+                // neighbouring lanes share
+                const int tv = (t0 & ps_mask) + 4 * q4;
 #pragma unroll
-                for (int i = 0; i < KD / 4; ++i) {
-                    const t4u w = *(const t4u *)(krow + 8 * i);
-                    c.k[4 * i] = w[0]; c.k[4 * i + 1] = w[1]; c.k[4 * i + 2] = w[2]; c.k[4 * i + 3] = w[3];
+                for (int cg = 0; cg < CG; ++cg) {
+                    const int m = 16 * cg + c16;
+                    c.v[cg][0] = *(const unsigned *)(vpage + ((m << p.ps_shift) + tv));
+                    c.v[cg][1] = *(const unsigned *)(vpage + (((M + m / (8 / HB)) << p.ps_shift) + tv));
                 }
-            }
-            // V: a tile never straddles a page (16 | page_size); codes of tokens >= T inside the page are whatever the page holds
+                return c;
+            } else {
+                const unsigned short *krow = kc + ((id.k << p.ps_shift) + (tk_ & ps_mask)) * M + q4 * (M / 4);
+                if constexpr (KD == 2) { const v2u w = *(const v2u *)krow; c.k[0] = w[0]; c.k[1] = w[1]; }
+                else {
 #pragma unroll
-            for (int cg = 0; cg < CG; ++cg) {
-                const v2u w = *(const v2u *)(vc + ((id.v * M + 16 * cg + c16) << p.ps_shift) + (t0 & ps_mask) + 4 * q4);
-                c.v[cg][0] = w[0]; c.v[cg][1] = w[1];
+                    for (int i = 0; i < KD / 4; ++i) {
+                        const t4u w = *(const t4u *)(krow + 8 * i);
+                        c.k[4 * i] = w[0]; c.k[4 * i + 1] = w[1]; c.k[4 * i + 2] = w[2]; c.k[4 * i + 3] = w[3];
+                    }
+                }
+                // V: a tile never straddles a page (16 | page_size); codes of tokens >= T inside the page are whatever the page holds
+#pragma unroll
+                for (int cg = 0; cg < CG; ++cg) {
+                    const v2u w = *(const v2u *)(vc + ((id.v * M + 16 * cg + c16) << p.ps_shift) + (t0 & ps_mask) + 4 * q4);
+                    c.v[cg][0] = w[0]; c.v[cg][1] = w[1];
+                }
+                return c;
             }
-            return c;
         };
         auto code_of = [&](unsigned w, int i) -> unsigned { return (w >> (16 * (i & 1))) & cmask; };
+        // code j of the lane's M/4 K codes; code of token t (0 .. 3) of column group cg.  Packed: the high field of the lane's
+        // j-th subspace sits at bit HB j of its high bytes (the lane's first subspace is a multiple of 8 / HB), a V field at
+        // the lane-constant bit HB (c16 mod 8 / HB) of its token's byte; `& cmask` drops the unused top bit at C = 512 / 2048
+        const unsigned vsh = HB ? (unsigned)(HB * (c16 % (HB ? 8 / HB : 1))) : 0u;
+        auto kcode = [&](const Codes &c, int j) -> unsigned {
+            if constexpr (HB != 0) {
+                const unsigned lo = (c.k[j >> 2] >> (8 * (j & 3))) & 0xffu;
+                const unsigned hi = c.k[KLO + ((HB * j) >> 5)] >> ((HB * j) & 31);      // (what lies above the field: masked with the code)
+                return ((hi << 8) | lo) & cmask;
+            } else return code_of(c.k[j >> 1], j);
+        };
+        auto vcode = [&](const Codes &c, int cg, int t) -> unsigned {
+            if constexpr (HB != 0) {
+                const unsigned lo = (c.v[cg][0] >> (8 * t)) & 0xffu;
+                const unsigned hi = c.v[cg][1] >> (8 * t + vsh);
+                return ((hi << 8) | lo) & cmask;
+            } else return code_of(c.v[cg][t >> 1], t);
+        };
         const char *ktab = (const char *)p.k_tab, *vtab = (const char *)p.v_tab;
         const unsigned esz = DM * 2;
         const unsigned kbase = (unsigned)(q4 * (M / 4)) * (unsigned)p.C;          // entry index of the lane's first K subspace
@@ -106,7 +160,7 @@ __global__ __launch_bounds__(kWW * 64, 2) void attn_wide_kernel(AttnParams p) {
             Ent e;
 #pragma unroll
             for (int j = 0; j < M / 4; ++j) {
-                const char *ep = ktab + (kbase + (unsigned)j * (unsigned)p.C + code_of(c.k[j >> 1], j)) * esz;
+                const char *ep = ktab + (kbase + (unsigned)j * (unsigned)p.C + kcode(c, j)) * esz;
                 if constexpr (DM == 4) { const v2u x = *(const v2u *)ep; e.k[2 * j] = x[0]; e.k[2 * j + 1] = x[1]; }
                 else e.k[j] = *(const unsigned *)ep;
             }
@@ -114,7 +168,7 @@ __global__ __launch_bounds__(kWW * 64, 2) void attn_wide_kernel(AttnParams p) {
             for (int cg = 0; cg < CG; ++cg)
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
-                    const char *ep = vtab + ((unsigned)(16 * cg + c16) * (unsigned)p.C + code_of(c.v[cg][t >> 1], t)) * esz;
+                    const char *ep = vtab + ((unsigned)(16 * cg + c16) * (unsigned)p.C + vcode(c, cg, t)) * esz;
                     if constexpr (DM == 4) { const v2u x = *(const v2u *)ep; e.v[cg][t][0] = x[0]; e.v[cg][t][1] = x[1]; }
                     else e.v[cg][t][0] = *(const unsigned *)ep;
                 }
@@ -185,11 +239,23 @@ static const void *const kWideKernels[2][2][2] = {
     {{(const void *)attn_wide_kernel<64, 2>, (const void *)attn_wide_kernel<64, 2, true>},
      {(const void *)attn_wide_kernel<64, 4>, (const void *)attn_wide_kernel<64, 4, true>}},
 };
+// ... and over packed pages, by the high bits of a code too (2: C = 512 / 1024, 4: C = 2048 / 4096)
+#define MILLION_PACKED_PAIR(D, DM, HB) {(const void *)attn_wide_kernel<D, DM, false, HB>, (const void *)attn_wide_kernel<D, DM, true, HB>}
+static const void *const kPackedKernels[2][2][2][2] = {
+    {{MILLION_PACKED_PAIR(128, 2, 2), MILLION_PACKED_PAIR(128, 4, 2)}, {MILLION_PACKED_PAIR(64, 2, 2), MILLION_PACKED_PAIR(64, 4, 2)}},
+    {{MILLION_PACKED_PAIR(128, 2, 4), MILLION_PACKED_PAIR(128, 4, 4)}, {MILLION_PACKED_PAIR(64, 2, 4), MILLION_PACKED_PAIR(64, 4, 4)}},
+};
+#undef MILLION_PACKED_PAIR
 static void wide_setup() {
-    if (device_once(5))
+    if (device_once(5)) {
         for (const auto &by_d : kWideKernels)
             for (const auto &by_dm : by_d)
                 for (const void *k : by_dm) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        for (const auto &by_hb : kPackedKernels)
+            for (const auto &by_d : by_hb)
+                for (const auto &by_dm : by_d)
+                    for (const void *k : by_dm) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    }
 }
 
 bool wide_geometry(int d, int M, int C, int G) {
@@ -197,7 +263,7 @@ bool wide_geometry(int d, int M, int C, int G) {
     return (d == 128 || d == 64) && M > 0 && d % M == 0 && (d / M == 2 || d / M == 4) && c_ok && G >= 1 && G <= kMaxGMfma;
 }
 
-bool plan_attn_wide(const AttnParams &p_in, AttnPlan &plan) {
+bool plan_attn_wide(const AttnParams &p_in, AttnPlan &plan, bool packed) {
     AttnParams p = p_in;
     if (!wide_geometry(p.d, p.M, p.C, p.Gt) || !p.k_paged || !p.v_paged || p.v_identity) return false;
     // split policy: the registers decide how many workgroups of 8 waves a CU holds (no codebook is in LDS): one at d = 128
@@ -205,7 +271,9 @@ bool plan_attn_wide(const AttnParams &p_in, AttnPlan &plan) {
     // workgroups fill that once.  A split is a multiple of 64 tokens and at least 256 tokens long.
     split_by_room(p, (p.d == 64 ? 2 : 1) * device_cus());
     const size_t lds = (size_t)wide_region_bytes(p.d, p.G, kWW) + (size_t)p.slot_floats * 4 + 16;
-    plan = {kWideKernels[p.d == 64][p.dm == 4][p.lse ? 1 : 0], dim3(p.nslots, p.bs * p.nh_k), dim3(kWW * 64), lds, p, 6, wide_setup};
+    const void *kernel = packed ? kPackedKernels[packed_hi_bits(p.C) == 4][p.d == 64][p.dm == 4][p.lse ? 1 : 0]
+                                : kWideKernels[p.d == 64][p.dm == 4][p.lse ? 1 : 0];
+    plan = {kernel, dim3(p.nslots, p.bs * p.nh_k), dim3(kWW * 64), lds, p, 6, wide_setup};
     return true;
 }
 

@@ -505,9 +505,15 @@ bool plan_attn_tile(const AttnParams &p, AttnPlan &plan);    // attn_tile.hip
 int plan_attn_generic(const AttnParams &p, AttnPlan &plan);  // attn_generic.hip: the scalar kernel, up to kMaxG query heads
 // attn_wide.hip: 16-bit codes (million_pq_decode_attn_wide only: no other entry asks it).  k_tab / v_tab are the plain
 // (M, C, d_m) codebooks, k_codes / v_codes the uint16 pools.  wide_geometry: the (d, M, C, nh / nh_k) that kernel is built for
-bool plan_attn_wide(const AttnParams &p, AttnPlan &plan);
+// packed: k_codes / v_codes are pools of packed pages (million_hip.h, "Packed code pages"); same grid, splits and workspace
+bool plan_attn_wide(const AttnParams &p, AttnPlan &plan, bool packed = false);
 bool wide_geometry(int d, int M, int C, int G);
+// Packed code pages: the high bits stored beside a code's low byte - a function of C alone (C in 512 .. 4096)
+__host__ __device__ inline int packed_hi_bits(int C) { return C <= 1024 ? 2 : 4; }
+__host__ __device__ inline long long packed_page_bytes(int page_size, int M, int C) { return (long long)page_size * M * (8 + packed_hi_bits(C)) / 8; }
 int launch_encode(const EncParams &p, hipStream_t s);
+int launch_encode_packed(const EncParams &p, hipStream_t s);      // encode.hip: KPAGES / VPAGES of packed pages, C in 512 .. 4096, 4 | M
+int launch_repack_pages(int direction, const void *src, void *dst, long long n_pages, int page_size, int M, int C, int side, hipStream_t s);
 int launch_decode(const void *codes, const f16 *cents, f16 *out, long long n_rows, int M, int C, int dm, hipStream_t s);
 struct FlushLayers { int n_layers; long long x_ls, ids_ls, len_ls; int advance; };      // one layer: {1, 0, 0, 0, 1}
 int launch_flush(const EncParams &k, const EncParams &v, int *dev_lengths_w, int rcap, int min_r, const FlushLayers &ly, hipStream_t s);

@@ -30,7 +30,9 @@ constexpr int kEncBlock = 256;
 constexpr int kEncSub = 4;      // subspaces per wave
 
 // CodeT = uint8_t (C <= 256) or uint16_t (nbits 9..16: reference nbits2dtype, pq_utils.py:542-552).
-template <int DM, bool F32TAB, typename CodeT>
+// PACKED (uint16_t, C 512 .. 4096, 4 | M: million_pq_encode_packed): the same codes into packed pages (million_hip.h, "Packed
+// code pages") - the store below is the only difference.
+template <int DM, bool F32TAB, typename CodeT, bool PACKED = false>
 __global__ __launch_bounds__(kEncBlock) void pq_encode_kernel(EncParams p) {
     constexpr int kCB = sizeof(CodeT) * 8;      // bits per stored code
     const int lane = threadIdx.x & 63;
@@ -70,6 +72,36 @@ __global__ __launch_bounds__(kEncBlock) void pq_encode_kernel(EncParams p) {
     // near INT_MAX would wrap it); the product fits an int (host check, fill_enc_params)
     if (tok0 < 0 || (p.layout != MILLION_CODES_ROWMAJOR && tok0 > p.n_pages_cap * p.page_size - 1 - t)) return;
     const int tok = tok0 + t;
+    if constexpr (PACKED) {
+        // the lane's 4 subspaces of one token: 4 low bytes, and one whole byte (2 high bits per code) or two (4 high bits) of
+        // the high plane - every byte written belongs to this token alone
+        const int hb = packed_hi_bits(p.C);
+        const long long pid = p.page_ids[(long long)bh * p.n_pages_cap + tok / p.page_size];
+        const int off = tok % p.page_size;
+        uint8_t *page = p.dst + pid * packed_page_bytes(p.page_size, p.M, p.C);      // 64-bit (no power of two: a multiply)
+        uint8_t *hi_plane = page + p.page_size * p.M;
+        unsigned c4[kEncSub], lo = 0, hi = 0;
+#pragma unroll
+        for (int j = 0; j < kEncSub; ++j) {
+            c4[j] = (unsigned)(codes >> (kCB * j)) & 0xffffu;
+            lo |= (c4[j] & 0xffu) << (8 * j);
+            hi |= ((c4[j] >> 8) & ((1u << hb) - 1u)) << (hb * j);
+        }
+        if (p.layout == MILLION_CODES_KPAGES) {
+            *(unsigned *)(page + off * p.M + m0) = lo;
+            if (hb == 2) hi_plane[off * (p.M / 4) + m0 / 4] = (uint8_t)hi;
+            else *(unsigned short *)(hi_plane + off * (p.M / 2) + m0 / 2) = (unsigned short)hi;
+        } else {
+#pragma unroll
+            for (int j = 0; j < kEncSub; ++j) page[(m0 + j) * p.page_size + off] = (uint8_t)c4[j];
+            if (hb == 2) hi_plane[(m0 / 4) * p.page_size + off] = (uint8_t)hi;
+            else {
+                hi_plane[(m0 / 2) * p.page_size + off] = (uint8_t)hi;
+                hi_plane[(m0 / 2 + 1) * p.page_size + off] = (uint8_t)(hi >> 8);
+            }
+        }
+        return;
+    }
     CodeT *dst = (CodeT *)p.dst;      // strides dsb / dsh are in bytes
     if (p.layout == MILLION_CODES_VPAGES) {
         const long long pid = p.page_ids[(long long)bh * p.n_pages_cap + tok / p.page_size];
@@ -402,6 +434,94 @@ int launch_encode(const EncParams &p, hipStream_t s) {
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("encode launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
+    return MILLION_OK;
+}
+
+int launch_encode_packed(const EncParams &p, hipStream_t s) {
+    if (p.n <= 0 || p.bs * p.nh_k <= 0) return MILLION_OK;
+    const int groups = p.M / kEncSub;
+    dim3 grid((p.n + 63) / 64, (groups + kEncBlock / 64 - 1) / (kEncBlock / 64), p.bs * p.nh_k);
+    if (!dispatch_dm(p.dm, [&](auto dm) { hipLaunchKernelGGL((pq_encode_kernel<dm(), false, uint16_t, true>), grid, dim3(kEncBlock), 0, s, p); })) {
+        set_error("encode_packed: d/M=%d unsupported (1,2,4,8)", p.dm);
+        return MILLION_ERR_SHAPE;
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("encode_packed launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
+    return MILLION_OK;
+}
+
+// ---- uint16 pages <-> packed pages, page for page (million_pq_repack_pages): a thread moves the 4 codes of one (page, token,
+// group of 4 subspaces) - 8 bytes of a uint16 K row, or one code of 4 rows of a transposed V page - as the encoder's lane does.
+// Threads run along a K row's groups and along a V row's tokens, so neighbouring threads touch neighbouring bytes.
+template <bool VSIDE, bool UNPACK>
+__global__ __launch_bounds__(256) void repack_pages_kernel(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, long long n_pages,
+                                                           int page_size, int M, int C) {
+    const int hb = packed_hi_bits(C);
+    const unsigned hmask = (1u << hb) - 1u;
+    const long long pbytes = packed_page_bytes(page_size, M, C);
+    const int groups = M / 4;
+    const long long per_page = (long long)page_size * groups, total = n_pages * per_page;
+    for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long long)gridDim.x * 256) {
+        const long long pg = idx / per_page;
+        const int w = (int)(idx % per_page);
+        const int t = VSIDE ? w % page_size : w / groups, m0 = 4 * (VSIDE ? w / page_size : w % groups);
+        const uint8_t *ppage = (UNPACK ? src : dst) + pg * pbytes;      // the packed page, the uint16 page
+        const unsigned short *upage = (const unsigned short *)(UNPACK ? dst : src) + pg * page_size * M;
+        uint8_t *pw = const_cast<uint8_t *>(ppage);
+        unsigned short *uw = const_cast<unsigned short *>(upage);
+        const long long hi0 = (long long)page_size * M;
+        unsigned c4[4];
+        if constexpr (!UNPACK) {
+            unsigned lo = 0, hi = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                c4[j] = VSIDE ? upage[(m0 + j) * page_size + t] : upage[t * M + m0 + j];
+                lo |= (c4[j] & 0xffu) << (8 * j);
+                hi |= ((c4[j] >> 8) & hmask) << (hb * j);
+            }
+            if constexpr (VSIDE) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) pw[(m0 + j) * page_size + t] = (uint8_t)c4[j];
+                pw[hi0 + (m0 * hb / 8) * page_size + t] = (uint8_t)hi;
+                if (hb == 4) pw[hi0 + (m0 / 2 + 1) * page_size + t] = (uint8_t)(hi >> 8);
+            } else {
+                *(unsigned *)(pw + t * M + m0) = lo;
+                pw[hi0 + t * (M * hb / 8) + m0 * hb / 8] = (uint8_t)hi;
+                if (hb == 4) pw[hi0 + t * (M / 2) + m0 / 2 + 1] = (uint8_t)(hi >> 8);
+            }
+        } else {
+            unsigned hi;
+            if constexpr (VSIDE) {
+                hi = ppage[hi0 + (m0 * hb / 8) * page_size + t];
+                if (hb == 4) hi |= (unsigned)ppage[hi0 + (m0 / 2 + 1) * page_size + t] << 8;
+            } else {
+                hi = ppage[hi0 + t * (M * hb / 8) + m0 * hb / 8];
+                if (hb == 4) hi |= (unsigned)ppage[hi0 + t * (M / 2) + m0 / 2 + 1] << 8;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const unsigned lo = VSIDE ? ppage[(m0 + j) * page_size + t] : ppage[t * M + m0 + j];
+                const unsigned short c = (unsigned short)(lo | (((hi >> (hb * j)) & hmask) << 8));
+                if (VSIDE) uw[(m0 + j) * page_size + t] = c;
+                else uw[t * M + m0 + j] = c;
+            }
+        }
+    }
+}
+
+int launch_repack_pages(int direction, const void *src, void *dst, long long n_pages, int page_size, int M, int C, int side, hipStream_t s) {
+    if (n_pages <= 0) return MILLION_OK;
+    long long blocks = (n_pages * page_size * (M / 4) + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    const dim3 grid((unsigned)blocks), block(256);
+    const uint8_t *sp = (const uint8_t *)src;
+    uint8_t *dp = (uint8_t *)dst;
+    if (side == 0 && direction == 0) hipLaunchKernelGGL((repack_pages_kernel<false, false>), grid, block, 0, s, sp, dp, n_pages, page_size, M, C);
+    else if (side == 0) hipLaunchKernelGGL((repack_pages_kernel<false, true>), grid, block, 0, s, sp, dp, n_pages, page_size, M, C);
+    else if (direction == 0) hipLaunchKernelGGL((repack_pages_kernel<true, false>), grid, block, 0, s, sp, dp, n_pages, page_size, M, C);
+    else hipLaunchKernelGGL((repack_pages_kernel<true, true>), grid, block, 0, s, sp, dp, n_pages, page_size, M, C);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("repack_pages launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
     return MILLION_OK;
 }
 

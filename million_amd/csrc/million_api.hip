@@ -309,6 +309,36 @@ int million_pq_encode(const million_encode_desc *desc, const void *x, const void
     return launch_encode(p, (hipStream_t)stream);
 }
 
+static bool packed_centroids(int C) { return C == 512 || C == 1024 || C == 2048 || C == 4096; }
+
+int million_pq_encode_packed(const million_encode_desc *desc, const void *x, const void *cents, void *dst,
+                             const int32_t *page_ids, million_stream_t stream) {
+    EncParams p;
+    const int rc = fill_enc_params("encode_packed", desc, x, cents, dst, page_ids, p);
+    if (rc != MILLION_OK) return rc;
+    int ps_shift;
+    if (p.layout == MILLION_CODES_ROWMAJOR) { set_error("encode_packed: dst_layout must be MILLION_CODES_KPAGES or MILLION_CODES_VPAGES (there are no packed row-major codes)"); return MILLION_ERR_SHAPE; }
+    if (!packed_centroids(p.C) || p.M % 4) { set_error("encode_packed: C=%d M=%d (C 512 / 1024 / 2048 / 4096, M a multiple of 4)", p.C, p.M); return MILLION_ERR_SHAPE; }
+    if (!page_shift("encode_packed", p.page_size, ps_shift)) return MILLION_ERR_SHAPE;
+    if ((uintptr_t)dst & 15) { set_error("encode_packed: the pool must be 16-byte aligned"); return MILLION_ERR_ALIGN; }
+    return launch_encode_packed(p, (hipStream_t)stream);
+}
+
+int million_pq_repack_pages(int direction, const void *src, void *dst, int64_t n_pages, int page_size, int M, int C, int side,
+                            million_stream_t stream) {
+    int ps_shift;
+    if ((direction != MILLION_REPACK_PACK && direction != MILLION_REPACK_UNPACK) || (side != 0 && side != 1) || n_pages < 0) {
+        set_error("repack_pages: direction=%d side=%d n_pages=%lld", direction, side, (long long)n_pages);
+        return MILLION_ERR_ARG;
+    }
+    if (!packed_centroids(C) || M <= 0 || M % 4) { set_error("repack_pages: C=%d M=%d (C 512 / 1024 / 2048 / 4096, M a multiple of 4)", C, M); return MILLION_ERR_SHAPE; }
+    if (!page_shift("repack_pages", page_size, ps_shift)) return MILLION_ERR_SHAPE;
+    if (n_pages == 0) return MILLION_OK;
+    if (!src || !dst) { set_error("repack_pages: null pointer"); return MILLION_ERR_ARG; }
+    if (((uintptr_t)src | (uintptr_t)dst) & 15) { set_error("repack_pages: src and dst must be 16-byte aligned"); return MILLION_ERR_ALIGN; }
+    return launch_repack_pages(direction, src, dst, (long long)n_pages, page_size, M, C, side, (hipStream_t)stream);
+}
+
 int million_pq_flush(const million_encode_desc *desc, const void *k_rows, const void *v_rows, const void *k_cents,
                      const void *v_cents, void *k_pool, void *v_pool, const int32_t *page_ids, int32_t *dev_lengths,
                      int resid_cap, int min_r, million_stream_t stream) {
@@ -574,10 +604,11 @@ int million_attn_wide_splits(const million_attn_desc *desc) {
     return plan.p.nsplit;
 }
 
-int million_pq_decode_attn_wide(const million_attn_desc *desc, const void *q, const void *k_new, const void *v_new,
-                                const void *k_codes, const void *v_codes, const void *k_page_ids, const void *v_page_ids,
-                                const void *k_cents, const void *v_cents, void *k_resid, void *v_resid, void *out, float *lse,
-                                void *workspace, size_t workspace_bytes, million_stream_t stream) {
+// packed: the pools hold packed pages (million_pq_decode_attn_packed); every check, the plan and the workspace are the same
+static int attn_wide_call(bool packed, const million_attn_desc *desc, const void *q, const void *k_new, const void *v_new,
+                          const void *k_codes, const void *v_codes, const void *k_page_ids, const void *v_page_ids,
+                          const void *k_cents, const void *v_cents, void *k_resid, void *v_resid, void *out, float *lse,
+                          void *workspace, size_t workspace_bytes, million_stream_t stream) {
     AttnParams p;
     const int rc = fill_attn_params(desc, p, true);
     if (rc != MILLION_OK) return rc;
@@ -617,8 +648,24 @@ int million_pq_decode_attn_wide(const million_attn_desc *desc, const void *q, co
     p.bad_ids = bad_ids_counter();
 #endif
     AttnPlan plan;
-    if (!plan_attn_wide(p, plan)) { set_error("attn_wide: no kernel for this call"); return MILLION_ERR_SHAPE; }
+    if (!plan_attn_wide(p, plan, packed)) { set_error("attn_wide: no kernel for this call"); return MILLION_ERR_SHAPE; }
     return launch_plan(plan, (hipStream_t)stream);
+}
+
+int million_pq_decode_attn_wide(const million_attn_desc *desc, const void *q, const void *k_new, const void *v_new,
+                                const void *k_codes, const void *v_codes, const void *k_page_ids, const void *v_page_ids,
+                                const void *k_cents, const void *v_cents, void *k_resid, void *v_resid, void *out, float *lse,
+                                void *workspace, size_t workspace_bytes, million_stream_t stream) {
+    return attn_wide_call(false, desc, q, k_new, v_new, k_codes, v_codes, k_page_ids, v_page_ids, k_cents, v_cents, k_resid, v_resid, out,
+                          lse, workspace, workspace_bytes, stream);
+}
+
+int million_pq_decode_attn_packed(const million_attn_desc *desc, const void *q, const void *k_new, const void *v_new,
+                                  const void *k_codes, const void *v_codes, const void *k_page_ids, const void *v_page_ids,
+                                  const void *k_cents, const void *v_cents, void *k_resid, void *v_resid, void *out, float *lse,
+                                  void *workspace, size_t workspace_bytes, million_stream_t stream) {
+    return attn_wide_call(true, desc, q, k_new, v_new, k_codes, v_codes, k_page_ids, v_page_ids, k_cents, v_cents, k_resid, v_resid, out,
+                          lse, workspace, workspace_bytes, stream);
 }
 
 int million_residual_append(const void *k_new, const void *v_new, void *k_resid, void *v_resid, int bs, int nh_k,

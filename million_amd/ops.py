@@ -577,12 +577,16 @@ WIDE_CENTROIDS = (512, 1024, 2048, 4096)
 
 
 def wide_attn_desc(who, q, k_pool, v_pool, k_cents, v_cents, k_res, v_res, r, n_tokens, page_ids, page_size, resid_start,
-               dev_lengths) -> L.AttnDesc:
-    """Every check of a wide decode call that needs no library, and its descriptor."""
+               dev_lengths, packed=False) -> L.AttnDesc:
+    """Every check of a wide decode call that needs no library, and its descriptor.  packed: the pools hold packed pages
+    (uint8 (n_pool, packed_page_bytes)); every other check is the same."""
     _need_cuda(q, k_pool, v_pool, k_cents, v_cents, k_res, v_res, page_ids, dev_lengths)
     if q.dtype != torch.float16 or k_res.dtype != torch.float16 or v_res.dtype != torch.float16:
         raise RuntimeError(f"{who}: q and residuals must be fp16")
-    if k_pool.dtype != torch.uint16 or v_pool.dtype != torch.uint16:
+    if packed:
+        if k_pool.dtype != torch.uint8 or v_pool.dtype != torch.uint8:
+            raise RuntimeError(f"{who}: packed pools must be uint8 (uint16 codes: pq_decode_attn_wide)")
+    elif k_pool.dtype != torch.uint16 or v_pool.dtype != torch.uint16:
         raise RuntimeError(f"{who}: codes must be uint16 (uint8 codes: pq_decode_attn)")
     if k_cents.dtype != torch.float16 or v_cents.dtype != torch.float16 or k_cents.dim() != 3 or k_cents.shape != v_cents.shape:
         raise RuntimeError(f"{who}: k_cents / v_cents must be the plain fp16 (M, C, d_m) codebooks of one shape")
@@ -600,7 +604,10 @@ def wide_attn_desc(who, q, k_pool, v_pool, k_cents, v_cents, k_res, v_res, r, n_
         raise RuntimeError(f"{who}: page_ids must be contiguous int32/int64 (bs, nh_k, n_pages)")
     if not k_pool.is_contiguous() or not v_pool.is_contiguous():
         raise RuntimeError(f"{who}: page pools must be contiguous")
-    if k_pool.dim() != 3 or tuple(k_pool.shape[1:]) != (page_size, M) or v_pool.dim() != 3 or tuple(v_pool.shape[1:]) != (M, page_size):
+    if packed:
+        _check_packed_pool(who, k_pool, page_size, M, C)
+        _check_packed_pool(who, v_pool, page_size, M, C)
+    elif k_pool.dim() != 3 or tuple(k_pool.shape[1:]) != (page_size, M) or v_pool.dim() != 3 or tuple(v_pool.shape[1:]) != (M, page_size):
         raise RuntimeError(f"{who}: pools must be K (n_pool, page_size, M) and V (n_pool, M, page_size)")
     if dev_lengths is not None and (dev_lengths.dtype != torch.int32 or tuple(dev_lengths.shape) != (q.shape[0], 4)
                                     or not dev_lengths.is_contiguous()):
@@ -638,25 +645,32 @@ def pq_decode_attn_wide(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Ten
 
     K pool (n_pool, page_size, M) u16, V pool (n_pool, M, page_size) u16, one page-id table (bs, nh_k, n_pages_cap) int32/int64
     for both sides; k_cents / v_cents are the plain (M, C, d_m) fp16 codebooks (there is no prepared image)."""
+    return _decode_attn_wide_call("pq_decode_attn_wide", False, q, k_pool, v_pool, k_cents, v_cents, k_res, v_res, r, n_tokens, page_ids,
+                                  page_size, resid_start, out, dev_lengths, workspace, k_new, v_new, return_lse, lse)
+
+
+def _decode_attn_wide_call(who, packed, q, k_pool, v_pool, k_cents, v_cents, k_res, v_res, r, n_tokens, page_ids, page_size, resid_start,
+                           out, dev_lengths, workspace, k_new, v_new, return_lse, lse):
+    """pq_decode_attn_wide (uint16 pools) and pq_decode_attn_packed (packed pools): one set of checks, one workspace, two entries."""
     _need_cuda(out, lse, k_new, v_new, workspace)
-    desc = wide_attn_desc("pq_decode_attn_wide", q, k_pool, v_pool, k_cents, v_cents, k_res, v_res, r, n_tokens, page_ids, page_size,
-                      resid_start, dev_lengths)
+    desc = wide_attn_desc(who, q, k_pool, v_pool, k_cents, v_cents, k_res, v_res, r, n_tokens, page_ids, page_size,
+                      resid_start, dev_lengths, packed)
     if out is None:
         out = torch.empty_like(q)
     elif out.dtype != torch.float16 or out.numel() != q.numel() or not out.is_contiguous():
-        raise RuntimeError("pq_decode_attn_wide: out must be contiguous fp16 of q's size")
+        raise RuntimeError(f"{who}: out must be contiguous fp16 of q's size")
     if k_new is not None or v_new is not None:
         if k_new is None or v_new is None or tuple(k_new.shape) != (q.shape[0], k_res.shape[1], 1, q.shape[3]) or v_new.shape != k_new.shape:
-            raise RuntimeError("pq_decode_attn_wide: k_new / v_new must be (bs, nh_k, 1, d)")
+            raise RuntimeError(f"{who}: k_new / v_new must be (bs, nh_k, 1, d)")
         if k_new.dtype != torch.float16 or v_new.dtype != torch.float16:
-            raise RuntimeError("pq_decode_attn_wide: k_new / v_new must be fp16")
+            raise RuntimeError(f"{who}: k_new / v_new must be fp16")
         k_new, v_new = k_new.contiguous(), v_new.contiguous()
     want_lse = return_lse or lse is not None
     if want_lse:
         if lse is None:
             lse = torch.empty(q.shape[0], q.shape[1], 1, dtype=torch.float32, device=q.device)
         elif lse.dtype != torch.float32 or tuple(lse.shape) != (q.shape[0], q.shape[1], 1) or not lse.is_contiguous():
-            raise RuntimeError("pq_decode_attn_wide: lse must be contiguous fp32 (bs, nh, 1)")
+            raise RuntimeError(f"{who}: lse must be contiguous fp32 (bs, nh, 1)")
     lib = L.load()
     if workspace is None:
         need = int(lib.million_attn_wide_workspace_bytes(ctypes.byref(desc)))
@@ -664,11 +678,112 @@ def pq_decode_attn_wide(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Ten
         workspace = _ws_cache.get(key)
         if workspace is None or workspace.numel() < need:      # zeroed once; every call leaves it ready (need = 0: the call is refused below)
             workspace = _ws_cache[key] = torch.zeros(max(need, 256), dtype=torch.uint8, device=q.device)
-    L.check(lib.million_pq_decode_attn_wide(ctypes.byref(desc), q.data_ptr(), _ptr(k_new), _ptr(v_new), k_pool.data_ptr(),
-                                            v_pool.data_ptr(), page_ids.data_ptr(), page_ids.data_ptr(), k_cents.data_ptr(),
-                                            v_cents.data_ptr(), k_res.data_ptr(), v_res.data_ptr(), out.data_ptr(), _ptr(lse),
-                                            workspace.data_ptr(), workspace.numel(), _stream()), "million_pq_decode_attn_wide")
+    entry = "million_pq_decode_attn_packed" if packed else "million_pq_decode_attn_wide"
+    L.check(getattr(lib, entry)(ctypes.byref(desc), q.data_ptr(), _ptr(k_new), _ptr(v_new), k_pool.data_ptr(),
+                                v_pool.data_ptr(), page_ids.data_ptr(), page_ids.data_ptr(), k_cents.data_ptr(),
+                                v_cents.data_ptr(), k_res.data_ptr(), v_res.data_ptr(), out.data_ptr(), _ptr(lse),
+                                workspace.data_ptr(), workspace.numel(), _stream()), entry)
     return (out, lse) if want_lse else out
+
+
+# ---- packed code pages (include/million_hip.h, "Packed code pages") ----
+def packed_hi_bits(C: int) -> int:
+    """High bits stored beside the low byte of a packed code: 2 for C in 512 / 1024, 4 for C in 2048 / 4096."""
+    if C not in WIDE_CENTROIDS:
+        raise RuntimeError(f"packed codes: C={C} (packed pages hold codes of {WIDE_CENTROIDS} centroids; C <= 256 is a uint8 already)")
+    return 2 if C <= 1024 else 4
+
+
+def packed_page_bytes(page_size: int, M: int, C: int) -> int:
+    """Bytes of one packed page: page_size * M * (8 + h) / 8, the low plane then the high plane."""
+    return page_size * M * (8 + packed_hi_bits(C)) // 8
+
+
+def _check_packed_pool(who, pool, page_size, M, C):
+    if pool.dtype != torch.uint8 or pool.dim() != 2 or pool.shape[1] != packed_page_bytes(page_size, M, C) or not pool.is_contiguous():
+        raise RuntimeError(f"{who}: a packed pool must be contiguous uint8 (n_pool, {packed_page_bytes(page_size, M, C)}) "
+                           f"for page_size={page_size}, M={M}, C={C}")
+
+
+def pq_encode_into_packed(X: torch.Tensor, cents: torch.Tensor, dst: torch.Tensor, *, layout: int, token_start: int = 0,
+                          n: Optional[int] = None, page_ids: torch.Tensor = None, page_size: int = 0, x_row_start: int = 0,
+                          x_row_mod: int = 0, dev_lengths: Optional[torch.Tensor] = None) -> None:
+    """pq_encode_into with a packed pool as destination (million_pq_encode_packed): layout MILLION_CODES_KPAGES / VPAGES, the
+    same codes bit for bit; the plain codebook (C in 512 .. 4096 has no prepared image)."""
+    who = "pq_encode_into_packed"
+    _need_cuda(X, cents, dst, page_ids, dev_lengths)
+    if X.dtype != torch.float16 or cents.dtype != torch.float16 or cents.dim() != 3:
+        raise RuntimeError(f"{who}: X and cents must be fp16, cents (M, C, d_m)")
+    if X.dim() != 4 or X.stride(3) != 1:
+        raise RuntimeError(f"{who}: X must be (bs, nh_k, n, d) with a contiguous last dim")
+    if layout not in (L.MILLION_CODES_KPAGES, L.MILLION_CODES_VPAGES):
+        raise RuntimeError(f"{who}: layout must be MILLION_CODES_KPAGES or MILLION_CODES_VPAGES (there are no packed row-major codes)")
+    cents = cents.contiguous()
+    bs, nhk, n_rows, d = X.shape
+    M, C, dm = cents.shape
+    _check_packed_pool(who, dst, page_size, M, C)
+    if page_ids is None or page_ids.dtype != torch.int32 or not page_ids.is_contiguous() or page_ids.dim() != 3:
+        raise RuntimeError(f"{who}: contiguous int32 page_ids (bs, nh_k, n_pages_cap) needed")
+    n = n_rows if n is None else n
+    desc = L.EncodeDesc()
+    desc.struct_size = ctypes.sizeof(L.EncodeDesc)
+    desc.bs, desc.nh_k, desc.n, desc.d, desc.M, desc.C = bs, nhk, n, d, M, C
+    desc.x_stride_b, desc.x_stride_h, desc.x_stride_n = X.stride(0), X.stride(1), X.stride(2)
+    desc.x_row_start, desc.x_row_mod = x_row_start, x_row_mod
+    desc.dst_layout, desc.dst_token_start = layout, token_start
+    desc.page_size, desc.n_pages_cap = page_size, page_ids.shape[2]
+    desc.dev_lengths = _ptr(dev_lengths)
+    L.check(L.load().million_pq_encode_packed(ctypes.byref(desc), X.data_ptr(), cents.data_ptr(), dst.data_ptr(), page_ids.data_ptr(),
+                                              _stream()), "million_pq_encode_packed")
+
+
+def pq_decode_attn_packed(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_cents: torch.Tensor,
+                          v_cents: torch.Tensor, k_res: torch.Tensor, v_res: torch.Tensor, r: int, *, n_tokens: int,
+                          page_ids: torch.Tensor, page_size: int, resid_start: int = 0, out: Optional[torch.Tensor] = None,
+                          dev_lengths: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                          k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None,
+                          return_lse: bool = False, lse: Optional[torch.Tensor] = None):
+    """pq_decode_attn_wide over packed pools (million_pq_decode_attn_packed): K and V pool uint8 (n_pool, packed_page_bytes),
+    everything else - arguments, checks, workspace (decode_wide_workspace_bytes), results bit for bit - as pq_decode_attn_wide."""
+    return _decode_attn_wide_call("pq_decode_attn_packed", True, q, k_pool, v_pool, k_cents, v_cents, k_res, v_res, r, n_tokens, page_ids,
+                                  page_size, resid_start, out, dev_lengths, workspace, k_new, v_new, return_lse, lse)
+
+
+def _repack(who, direction, src, side, page_size, M, C, out):
+    _need_cuda(src, out)
+    if side not in ("k", "v"):
+        raise RuntimeError(f"{who}: side must be 'k' or 'v'")
+    pb = packed_page_bytes(page_size, M, C)
+    u16_shape = (page_size, M) if side == "k" else (M, page_size)
+    if direction == L.MILLION_REPACK_PACK:
+        if src.dtype != torch.uint16 or src.dim() != 3 or tuple(src.shape[1:]) != u16_shape or not src.is_contiguous():
+            raise RuntimeError(f"{who}: pages must be contiguous uint16 (n_pages, {u16_shape[0]}, {u16_shape[1]})")
+        want = (torch.uint8, (src.shape[0], pb))
+    else:
+        _check_packed_pool(who, src, page_size, M, C)
+        want = (torch.uint16, (src.shape[0],) + u16_shape)
+    if out is None:
+        out = torch.empty(want[1], dtype=want[0], device=src.device)
+    elif out.dtype != want[0] or tuple(out.shape) != want[1] or not out.is_contiguous():
+        raise RuntimeError(f"{who}: out must be contiguous {want[0]} {want[1]}")
+    L.check(L.load().million_pq_repack_pages(direction, src.data_ptr(), out.data_ptr(), src.shape[0], page_size, M, C,
+                                             0 if side == "k" else 1, _stream()), "million_pq_repack_pages")
+    return out
+
+
+def pq_pack_pages(pages: torch.Tensor, *, side: str, C: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint16 pages -> packed pages, page for page (million_pq_repack_pages): K pages (n, page_size, M) with side="k", transposed
+    V pages (n, M, page_size) with side="v" -> uint8 (n, packed_page_bytes)."""
+    if pages.dim() != 3:
+        raise RuntimeError("pq_pack_pages: pages must be contiguous uint16 (n_pages, page_size, M) or (n_pages, M, page_size)")
+    page_size, M = (pages.shape[1], pages.shape[2]) if side == "k" else (pages.shape[2], pages.shape[1])
+    return _repack("pq_pack_pages", L.MILLION_REPACK_PACK, pages, side, page_size, M, C, out)
+
+
+def pq_unpack_pages(packed: torch.Tensor, *, side: str, page_size: int, M: int, C: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Packed pages uint8 (n, packed_page_bytes) -> uint16 K pages (n, page_size, M) or V pages (n, M, page_size): the way of
+    everything that reads uint16 pages (chunk attention, pq_gather_rows, pq_decode) to codes held in packed pages."""
+    return _repack("pq_unpack_pages", L.MILLION_REPACK_UNPACK, packed, side, page_size, M, C, out)
 
 
 def prefill_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, causal: bool = True, q_pos0: int = 0,

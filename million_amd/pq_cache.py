@@ -457,14 +457,21 @@ class PagedPQCache(_CacheBase):
     `nbits` 9 .. 12 with `dtype=torch.uint16` (uint16 pools, codebooks of 2**nbits centroids): the core life - prefill,
     prefill_request, decoding_with_pages (ops.pq_decode_attn_wide), the in-line flush of requests in lockstep, release, cleanup -
     and NotImplementedError naming nbits for the rest (extend*, prefill_ragged, fork, swap, verify / commit, update, sinks).
-    DESIGN.md 4.14."""
+    DESIGN.md 4.14.
+
+    `packed=True` (nbits 9 .. 12 only; nbits = 8: ValueError): the same cache over packed pools - uint8 (n_pool,
+    ops.packed_page_bytes), 10 bits per code at nbits 9 / 10 and 12 at nbits 11 / 12 instead of 16 (include/million_hip.h,
+    "Packed code pages") - through ops.pq_encode_into_packed and ops.pq_decode_attn_packed: the same codes, the same outputs bit
+    for bit, the same refusals, (8 + h) / 16 of the pool bytes.  DESIGN.md 4.17."""
 
     def __init__(self, *, bs, nh, num_key_value_heads, M, layer_num, dtype=torch.uint8, nbits=8, d=128,
                  scalar_t=torch.float16, page_size=64, extended_residual_size=128, max_pages_per_layer=None,
-                 max_tokens=32768 + 1024, preallocate=True, device="cuda", sink_tokens=0):
+                 max_tokens=32768 + 1024, preallocate=True, device="cuda", sink_tokens=0, packed=False):
         if nbits not in (8, 9, 10, 11, 12) or dtype != nbits2dtype(nbits):
             raise NotImplementedError(f"PagedPQCache: nbits=8 with dtype=torch.uint8, or nbits 9 .. 12 with dtype=torch.uint16 "
                                       f"(DESIGN.md 4.14), are the code types that exist; got nbits={nbits}, dtype={dtype}")
+        if packed and nbits == 8:
+            raise ValueError("PagedPQCache: packed=True needs nbits 9 .. 12 (a code of nbits=8 is one byte already)")
         if isinstance(sink_tokens, bool) or int(sink_tokens) != sink_tokens or not 0 <= sink_tokens <= ops.SINK_MAX_ROWS:
             raise ValueError(f"sink_tokens must be an integer in 0 .. {ops.SINK_MAX_ROWS}")
         if nbits > 8 and sink_tokens:
@@ -485,6 +492,7 @@ class PagedPQCache(_CacheBase):
         self.max_tokens = self.n_pages_cap * page_size
         self.preallocate = preallocate
         self.sink_tokens = int(sink_tokens)
+        self.packed = bool(packed)
         self.registery = KernelRegistry(M=M, d=d, nbits=nbits, nh=nh, scalar_t=scalar_t, device=device)
         self.init_cache()
 
@@ -492,8 +500,13 @@ class PagedPQCache(_CacheBase):
         nk, cap = self.num_key_value_heads, self.extended_residual_size
         total = self.layer_num * self.bs * nk * self.n_pages_cap
         z = lambda *s, dt: torch.zeros(*s, dtype=dt, device=self.device)
-        self.key_page_pool = z(total, self.page_size, self.M, dt=self.dtype)      # uint8; uint16 at nbits 9 .. 12
-        self.value_page_pool = z(total, self.M, self.page_size, dt=self.dtype)
+        if self.packed:      # packed pages: a low-byte plane and a plane of 2 / 4 high bits per code, one page id for both
+            page_bytes = ops.packed_page_bytes(self.page_size, self.M, self.C)
+            self.key_page_pool = z(total, page_bytes, dt=torch.uint8)
+            self.value_page_pool = z(total, page_bytes, dt=torch.uint8)
+        else:
+            self.key_page_pool = z(total, self.page_size, self.M, dt=self.dtype)      # uint8; uint16 at nbits 9 .. 12
+            self.value_page_pool = z(total, self.M, self.page_size, dt=self.dtype)
         self.page_manager = PageManager(self.page_size, initial_pages=total, max_pages=total, M=self.M)
         # the layers' page tables, windows and length rows lie side by side (one allocation each; the per-layer lists are
         # views): one launch can then serve every layer (begin_step: encode-ahead, commit)
@@ -657,6 +670,10 @@ class PagedPQCache(_CacheBase):
         self._reserve(layer_idx, n, b)
         kw = dict(token_start=T, n=n, page_ids=self.page_ids[layer_idx][sel], page_size=self.page_size,
                   x_row_start=x_row_start, x_row_mod=x_row_mod)
+        if self.packed:
+            ops.pq_encode_into_packed(K, self.key_cent, self.key_page_pool, layout=L.MILLION_CODES_KPAGES, **kw)
+            ops.pq_encode_into_packed(V, self.value_cent, self.value_page_pool, layout=L.MILLION_CODES_VPAGES, **kw)
+            return
         ops.pq_encode_into(K, self.key_cent, self.key_page_pool, layout=L.MILLION_CODES_KPAGES, prepared=self._kprep, **kw)
         ops.pq_encode_into(V, self.value_cent, self.value_page_pool, layout=L.MILLION_CODES_VPAGES, prepared=self._vprep, **kw)
 
@@ -1391,8 +1408,9 @@ class PagedPQCache(_CacheBase):
             if self._sink_lse is None:
                 self._sink_lse = torch.empty(self.bs, self.nh, 1, dtype=torch.float32, device=self.device)
             lse = self._sink_lse
-        if wide:      # the same launch over uint16 codes, the codebooks as they are (csrc/attn_wide.hip)
-            return ops.pq_decode_attn_wide(query_states, self.key_page_pool, self.value_page_pool, self.key_cent, self.value_cent,
+        if wide:      # the same launch over uint16 codes - or packed pages -, the codebooks as they are (csrc/attn_wide.hip)
+            attend = ops.pq_decode_attn_packed if self.packed else ops.pq_decode_attn_wide
+            return attend(query_states, self.key_page_pool, self.value_page_pool, self.key_cent, self.value_cent,
                                            self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx], r,
                                            k_new=key_states, v_new=value_states,
                                            n_tokens=self.max_tokens if use_dev_lengths else int(self._T_a[layer_idx, 0]),
@@ -1675,12 +1693,23 @@ class PagedPQCache(_CacheBase):
                 self._pre_a[g0:g1] = 1
         self._note_appended()
 
+    def code_bytes_per_token(self) -> float:
+        """Bytes one token's codes take per kv head and side: M codes of 1 byte (nbits 8), 2 bytes (nbits 9 .. 12), or
+        (8 + h) / 8 bytes in packed pages."""
+        if self.packed:
+            return self.M * (8 + ops.packed_hi_bits(self.C)) / 8
+        return float(self.M * self.key_page_pool.element_size())
+
+    def pq_cache_size(self):
+        """Bytes of the codes the live tokens hold in the pools, K and V."""
+        return 2 * self.num_key_value_heads * self.code_bytes_per_token() * float(self._T_a.sum())
+
     def get_cache_stats(self) -> Dict:
         """paged_pq_utils.py:898-939 (same keys) + the page-manager counters."""
         layer_stats = [{"layer_idx": l, "seen_tokens": self.seen_tokens[l], "residual_tokens": self.residualed_tokens[l],
                         "key_cache_tokens": self._T[l], "value_cache_tokens": self._T[l]} for l in range(self.layer_num)]
         mb = 1024 * 1024
-        cache_mb = float(2 * self.num_key_value_heads * self.M * self.key_page_pool.element_size() * self._T_a.sum()) / mb
+        cache_mb = float(self.pq_cache_size()) / mb
         resid_mb = sum(c.numel() * c.element_size() for c in self.key_residual_cache + self.value_residual_cache) / mb
         sink_mb = 2 * self.layer_num * self.bs * self.num_key_value_heads * self.sink_tokens * self.d * 2 / mb      # K and V buffers, fp16
         return {"layer_stats": layer_stats, "total_memory_usage_mb": cache_mb + resid_mb + sink_mb,

@@ -5,7 +5,7 @@ instruction-class sequence of one kernel - what hipcc made of a schedule.
   python tools/kernel_meta.py [lib.so] [substring of the kernel name] [--seq]
 
 Reads the .hip_fatbin section of the library (llvm-objcopy), splits it into its gfx950 code objects and prints
-.vgpr_count / .agpr_count / .group_segment_fixed_size (static LDS; dynamic LDS is the launch's) / .vgpr_spill_count /
+.vgpr_count / .agpr_count / .sgpr_count / .group_segment_fixed_size (static LDS; dynamic LDS is the launch's) / .vgpr_spill_count /
 .sgpr_spill_count / .private_segment_fixed_size from the notes.  With
 --seq the kernel is disassembled and every instruction mapped to one letter: M mfma, E v_exp, v other VALU, D ds_read,
 d other LDS, G global / buffer, S scratch, w s_waitcnt, | s_barrier, J branch, n s_nop, a v_accvgpr, s other scalar."""
@@ -42,7 +42,7 @@ with tempfile.TemporaryDirectory() as td:
         notes = subprocess.run([LLVM + "llvm-readelf", "--notes", str(co)], capture_output=True, text=True).stdout
         cur, row, hit = None, {}, []
         for line in notes.split("\n"):
-            m = re.match(r"\s+\.(name|vgpr_count|agpr_count|group_segment_fixed_size|vgpr_spill_count|sgpr_spill_count|private_segment_fixed_size):\s+(\S+)", line)
+            m = re.match(r"\s+\.(name|vgpr_count|agpr_count|sgpr_count|group_segment_fixed_size|vgpr_spill_count|sgpr_spill_count|private_segment_fixed_size):\s+(\S+)", line)
             if not m:
                 continue
             key, val = m.groups()
@@ -51,7 +51,7 @@ with tempfile.TemporaryDirectory() as td:
             else:
                 row[key] = val
             if key == "vgpr_spill_count" and pat in row.get("name", ""):
-                print(f"{row['name'][:90]:90s} vgpr {row.get('vgpr_count')} agpr {row.get('agpr_count')} lds {row.get('group_segment_fixed_size')} B vgpr_spill {row.get('vgpr_spill_count')} "
+                print(f"{row['name'][:90]:90s} vgpr {row.get('vgpr_count')} agpr {row.get('agpr_count')} sgpr {row.get('sgpr_count')} lds {row.get('group_segment_fixed_size')} B vgpr_spill {row.get('vgpr_spill_count')} "
                       f"sgpr_spill {row.get('sgpr_spill_count')} scratch {row.get('private_segment_fixed_size')} B")
                 hit.append(row["name"])
         if seq and hit and pat:
