@@ -532,9 +532,10 @@ int million_pq_decode_attn_wide(const million_attn_desc *desc, const void *q,
  * Every high byte belongs to ONE token on both sides: a store of the tokens [t0, t0 + n) never reads, modifies or zeroes a byte
  * of another token, and the bytes of tokens past the live ones may hold anything.  At C = 512 / 2048 the top bit of a field is
  * not part of a code: the encoder writes it as 0, the readers mask it (code & (C - 1)).
- * page_size in {32, 64, 128} and M in {16, 32, 64} keep every plane a multiple of 16 bytes.  True 9- / 11-bit packing, packed
- * row-major codes, and chunk attention / million_pq_gather_rows / million_pq_decode over packed pages do not exist:
- * million_pq_repack_pages is their way to and from packed pages.
+ * page_size in {32, 64, 128} and M in {16, 32, 64} keep every plane a multiple of 16 bytes.  Packed pages are read by decode
+ * attention (million_pq_decode_attn_packed), chunk attention (million_pq_chunk_attn_packed) and the row gather
+ * (million_pq_gather_rows_packed).  True 9- / 11-bit packing, packed row-major codes and million_pq_decode over packed pages do
+ * not exist: million_pq_repack_pages is the way from packed pages to uint16 pages and back.
  *
  * million_pq_encode_packed: million_pq_encode's contract - descriptor, codes bit for bit (the same scan), ring source,
  * dev_lengths, page-table clamps - with dst_layout MILLION_CODES_KPAGES / MILLION_CODES_VPAGES meaning packed pages of the pool
@@ -550,7 +551,21 @@ int million_pq_decode_attn_wide(const million_attn_desc *desc, const void *q,
  * dst packed pages (bits of a code above 8 + h are dropped); MILLION_REPACK_UNPACK: src packed pages -> dst uint16 pages.
  * side 0: K pages ((page_size, M) uint16), side 1: V pages ((M, page_size) uint16).  Shapes as above (MILLION_ERR_SHAPE), a
  * bad direction / side or n_pages < 0: MILLION_ERR_ARG; src and dst 16-byte aligned; n_pages = 0: MILLION_OK.  src and dst
- * must not overlap. */
+ * must not overlap.
+ *
+ * million_pq_chunk_attn_packed (declared behind million_pq_chunk_attn_wide below): the arguments and every semantic of
+ * million_pq_chunk_attn_wide - out, lse (may be NULL), the ragged dev_lengths / dev_n_q, code & (C - 1) on every gathered index
+ * - with k_codes / v_codes the packed pools.  The same split count and workspace: million_chunk_attn_wide_workspace_bytes
+ * answers for it too.  Both layouts must be MILLION_KV_PAGED (a row-major side: MILLION_ERR_SHAPE before any launch - there is
+ * no packed row-major format); page_size 32 / 64 / 128; pools 16-byte aligned.  `out` and lse are bitwise those of
+ * million_pq_chunk_attn_wide over uint16 pools that hold the same codes: same tile order, same split cut, same merge.  Bytes of
+ * tokens past n_tokens (or the device length), of page tails and of pages no live entry names may hold anything.
+ *
+ * million_pq_gather_rows_packed (declared behind million_pq_gather_rows below): million_pq_gather_rows' job with the same
+ * descriptor - code_bytes = 2, the logical width of a code; both layouts MILLION_KV_PAGED; d / M 2 or 4; anything else is
+ * MILLION_ERR_SHAPE before any launch - over the packed K and V pools.  The index rule c < C ? c : 0 is applied to the raw
+ * (8 + h)-bit field, so the rows are bit for bit those of million_pq_gather_rows over the MILLION_REPACK_UNPACK image of the same
+ * pools.  Only bytes of the tokens t0 <= t < t1 are read. */
 enum {
     MILLION_REPACK_PACK = 0,      /* uint16 pages -> packed pages */
     MILLION_REPACK_UNPACK = 1     /* packed pages -> uint16 pages */
@@ -723,6 +738,12 @@ int million_pq_chunk_attn_wide(const million_chunk_attn_desc *desc, const void *
                                const void *k_cents, const void *v_cents, const void *k_resid, const void *v_resid,
                                void *out, float *lse /* may be NULL */, void *workspace, size_t workspace_bytes,
                                million_stream_t stream);
+/* The same over pools of packed pages ("Packed code pages" above): k_codes / v_codes uint8 (n_pool, page_bytes), both PAGED */
+int million_pq_chunk_attn_packed(const million_chunk_attn_desc *desc, const void *q, const void *k_chunk, const void *v_chunk,
+                                 const void *k_codes, const void *v_codes, const void *k_page_ids, const void *v_page_ids,
+                                 const void *k_cents, const void *v_cents, const void *k_resid, const void *v_resid,
+                                 void *out, float *lse /* may be NULL */, void *workspace, size_t workspace_bytes,
+                                 million_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Gather of rows: a token range of every request dequantised straight from its code store, then its window rows in ring order,
@@ -774,6 +795,12 @@ int million_pq_gather_rows(const million_gather_rows_desc *desc,
                            const void *k_resid, const void *v_resid,           /* (bs, nh_k, resid_cap, d) fp16; NULL when r = 0 */
                            void *k_out, void *v_out,                           /* (bs, nh_k, rows_cap, d) fp16 */
                            million_stream_t stream);
+/* The same over pools of packed pages ("Packed code pages" above): code_bytes = 2, both layouts PAGED, d / M 2 or 4 */
+int million_pq_gather_rows_packed(const million_gather_rows_desc *desc,
+                                  const void *k_pool, const void *v_pool,             /* uint8 (n_pool, page_bytes) */
+                                  const int32_t *k_page_ids, const int32_t *v_page_ids,
+                                  const void *k_cents, const void *v_cents, const void *k_resid, const void *v_resid,
+                                  void *k_out, void *v_out, million_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Merge of partial attentions: n_parts results (out_i, lse_i) of one query over disjoint key sets -> the result over

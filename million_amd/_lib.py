@@ -175,7 +175,9 @@ SYMBOLS = {
     "million_pq_chunk_attn_lse": (c_i32, [ctypes.POINTER(ChunkAttnDesc)] + [c_vp] * 14 + [c_sz, c_vp]),
     "million_chunk_attn_wide_workspace_bytes": (c_sz, [ctypes.POINTER(ChunkAttnDesc)]),
     "million_pq_chunk_attn_wide": (c_i32, [ctypes.POINTER(ChunkAttnDesc)] + [c_vp] * 14 + [c_sz, c_vp]),
+    "million_pq_chunk_attn_packed": (c_i32, [ctypes.POINTER(ChunkAttnDesc)] + [c_vp] * 14 + [c_sz, c_vp]),
     "million_pq_gather_rows": (c_i32, [ctypes.POINTER(GatherRowsDesc)] + [c_vp] * 11),
+    "million_pq_gather_rows_packed": (c_i32, [ctypes.POINTER(GatherRowsDesc)] + [c_vp] * 11),
     "million_attn_merge": (c_i32, [ctypes.POINTER(AttnMergeDesc), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp, c_vp, c_vp]),
     "million_attn_block_merge": (c_i32, [ctypes.POINTER(BlockMergeDesc)] + [c_vp] * 11),
     "million_attn_sink_merge": (c_i32, [ctypes.POINTER(SinkMergeDesc)] + [c_vp] * 10),

@@ -1,9 +1,9 @@
 // chunk_attn.h — what the chunk-attention kernels share: chunk_attn.hip (uint8 codes, both codebooks in LDS) and
-// chunk_attn_wide.hip (uint16 codes, the codebooks gathered from global memory), gfx950.
+// chunk_attn_wide.hip (uint16 codes or packed 10- / 12-bit pages, the codebooks gathered from global memory), gfx950.
 //
-// ONE body, chunk_attn_body<D, DM, RAGGED, LSE, WIDE>: the tile loop over flash_tile.h's step, the mask, the cut of a query
-// block's visible tiles into the S split ranges, the ragged clamps and the epilogue are the same text for both code widths;
-// WIDE selects the code producer and nothing else (the design notes are at the top of the two .hip files).  The host half -
+// ONE body, chunk_attn_body<D, DM, RAGGED, LSE, WIDE, PACKED>: the tile loop over flash_tile.h's step, the mask, the cut of a query
+// block's visible tiles into the S split ranges, the ragged clamps and the epilogue are the same text for every code format;
+// WIDE / PACKED select the code producer and nothing else (the design notes are at the top of the two .hip files).  The host half -
 // validation, chunk_splits, the workspace, chunk_merge_kernel - is chunk_attn.hip's for both.
 #pragma once
 
@@ -39,6 +39,7 @@ struct ChunkParams {
     const int *dev_n_q;                       // RAGGED: (bs,) valid query rows per request, or null (n_q)
     float *lse;                               // LSE instances: (bs, nh, n_q) fp32 log-sum-exp of each row's visible scores (million_hip.h); last, so
                                               // that no other argument moves: the instances without it are the code they were
+    int hb;                                   // PACKED instances: high bits of a code beside its low byte (2 / 4; packed_hi_bits(C)), else 0
 #ifdef MILLION_DEBUG_CHECK_IDS
     int lds_fill;                             // dynamic LDS bytes of the launch: debug_fill_lds (common.h)
 #endif
@@ -128,6 +129,45 @@ __device__ __forceinline__ unsigned long long ca_load_codes16(const ChunkParams 
     return *(const unsigned *)src;
 }
 
+// PACKED: ca_load_codes16's word from packed pages (million_hip.h, "Packed code pages"; both sides paged): the NM low bytes
+// - one load of NM bytes from a K page, NM byte loads page_size apart from a transposed V page - and the token's high-plane
+// byte(s) of the same subspaces.  m0 is a multiple of NM, so the NM fields of h = p.hb bits start at bit (m0 h) mod 8 of high
+// byte m0 h / 8: a whole byte (h 2, NM 4; h 4, NM 2), a nibble (h 2, NM 2) or two bytes (h 4, NM 4).  Exactly those bytes are
+// loaded.  A page is page_size M (8 + h) / 8 bytes, no power of two: its offset is a 64-bit multiply.
+template <int NM>
+__device__ __forceinline__ unsigned long long ca_load_codes_packed(const ChunkParams &p, bool is_v, int b, int hk, int tok, int m0) {
+    static_assert(NM == 2 || NM == 4, "d / M 4 or 2");
+    const int h = p.hb;                                 // wave-uniform: 2 or 4
+    const bool two = NM == 4 && h == 4;                 // 16 high bits
+    const long long pg = ca_page(p, is_v ? p.vids : p.kids, b, hk, tok / p.ps);
+    const int o = tok - (tok / p.ps) * p.ps;
+    const uint8_t *page = (is_v ? p.vcodes : p.kcodes) + pg * ((long long)p.ps * ((p.M * (8 + h)) >> 3));
+    const uint8_t *hi_plane = page + p.ps * p.M;
+    const int hb0 = (m0 * h) >> 3;
+    unsigned lo, hi;
+    if (is_v) {      // transposed planes: low (M, ps), high (M h / 8, ps)
+        const uint8_t *src = page + m0 * p.ps + o;
+        lo = 0;
+#pragma unroll
+        for (int e = 0; e < NM; ++e) lo |= (unsigned)src[e * p.ps] << (8 * e);
+        const uint8_t *hs = hi_plane + hb0 * p.ps + o;
+        hi = hs[0];
+        if (two) hi |= (unsigned)hs[p.ps] << 8;
+    } else {         // low (ps, M), high (ps, M h / 8)
+        const uint8_t *src = page + o * p.M + m0;
+        lo = NM == 4 ? *(const unsigned *)src : (unsigned)*(const unsigned short *)src;
+        const uint8_t *hs = hi_plane + o * ((p.M * h) >> 3) + hb0;
+        hi = two ? (unsigned)*(const unsigned short *)hs : (unsigned)*hs;
+    }
+    hi >>= (m0 * h) & 7;
+    const unsigned fmask = (1u << h) - 1u;
+    unsigned long long w = 0;
+#pragma unroll
+    for (int e = 0; e < NM; ++e)
+        w |= (unsigned long long)(((lo >> (8 * e)) & 0xffu) | (((hi >> (h * e)) & fmask) << 8)) << (16 * e);
+    return w;
+}
+
 // WIDE: 8 fp16 of one 16-byte chunk from NM codes through the plain (M, C, d_m) codebook in global memory: NM loads of one whole
 // entry (4 bytes at d_m = 2, 8 at d_m = 4).  EVERY index is code & (C - 1) (C is a power of two): whatever 16 bits a code word
 // holds, the load stays inside its subspace's C entries.
@@ -168,7 +208,9 @@ __device__ __forceinline__ float *ca_lse_at(const ChunkParams &p, int b, int hea
 // codes through the codebooks in global memory - a code tile's entries are gathered straight into the registers that hold a
 // window or chunk tile's rows (an entry group IS a 16-byte chunk of the dequantised row), one tile ahead of the products, and
 // its code words one tile ahead of that; LDS holds the K + V tile only.
-template <int D, int DM, bool RAGGED, bool LSE, bool WIDE>
+// PACKED (with WIDE): the code words come from packed 10- / 12-bit pages (ca_load_codes_packed) instead of uint16 pages; the
+// word is the same, so nothing behind cwk / cwv differs and the result is the uint16 instance's bit for bit.
+template <int D, int DM, bool RAGGED, bool LSE, bool WIDE, bool PACKED = false>
 __device__ __forceinline__ void chunk_attn_body(const ChunkParams &p) {
     constexpr int DS = D / 16;                    // k-steps of the score product
     constexpr int NB = D / 32;                    // 32-row blocks of O^T
@@ -248,8 +290,13 @@ __device__ __forceinline__ void chunk_attn_body(const ChunkParams &p) {
             cwk[k] = 0;
             cwv[k] = 0;
             if (kind == 0 && row < nv) {
-                cwk[k] = ca_load_codes16<NM>(p, false, b, hk, j0 + row, ch * NM);
-                cwv[k] = ca_load_codes16<NM>(p, true, b, hk, j0 + row, ch * NM);
+                if constexpr (PACKED) {
+                    cwk[k] = ca_load_codes_packed<NM>(p, false, b, hk, j0 + row, ch * NM);
+                    cwv[k] = ca_load_codes_packed<NM>(p, true, b, hk, j0 + row, ch * NM);
+                } else {
+                    cwk[k] = ca_load_codes16<NM>(p, false, b, hk, j0 + row, ch * NM);
+                    cwv[k] = ca_load_codes16<NM>(p, true, b, hk, j0 + row, ch * NM);
+                }
             }
         }
     };
@@ -383,8 +430,9 @@ inline void launch_chunk_kernel(Kernel kernel, const ChunkParams &p, long long b
 #endif
 }
 
-// chunk_attn_wide.hip: launches chunk_attn_wide_kernel<d, d / p.M, ragged, lse> (ragged and lse as the fields of p say); the
-// descriptor was validated and p filled by chunk_attn.hip, which also launches the merge
+// chunk_attn_wide.hip: launches chunk_attn_wide_kernel<d, d / p.M, ragged, lse> (ragged and lse as the fields of p say) or, with
+// p.hb != 0, chunk_attn_packed_kernel of the same four; the descriptor was validated and p filled by chunk_attn.hip, which also
+// launches the merge
 void launch_chunk_wide(const ChunkParams &p, int d, long long blocks, int lds, hipStream_t s);
 
 }  // namespace million

@@ -173,7 +173,8 @@ extern "C" size_t million_chunk_attn_wide_workspace_bytes(const million_chunk_at
 
 // `wide`: million_pq_chunk_attn_wide - uint16 codes (row-major rows of 2 M bytes) and the plain codebooks; every other check,
 // the geometry, the workspace and the merge are the same lines for both widths
-static int chunk_attn_impl(bool wide, const million_chunk_attn_desc *desc, const void *q, const void *k_chunk, const void *v_chunk,
+// `packed` (with wide): million_pq_chunk_attn_packed - both sides are pools of packed pages (million_hip.h, "Packed code pages")
+static int chunk_attn_impl(bool wide, bool packed, const million_chunk_attn_desc *desc, const void *q, const void *k_chunk, const void *v_chunk,
                            const void *k_codes, const void *v_codes, const void *k_page_ids, const void *v_page_ids,
                            const void *k_cents_prepared, const void *v_cents_prepared, const void *k_resid,
                            const void *v_resid, void *out, float *lse, void *workspace, size_t workspace_bytes,
@@ -181,7 +182,15 @@ static int chunk_attn_impl(bool wide, const million_chunk_attn_desc *desc, const
     if (!desc || desc->struct_size != sizeof(million_chunk_attn_desc)) { set_error("chunk_attn: bad desc / struct_size"); return MILLION_ERR_ARG; }
     const million_chunk_attn_desc &d = *desc;
     if (d.bs <= 0 || d.nh <= 0 || d.nh_k <= 0 || d.nh % d.nh_k) { set_error("chunk_attn: bs=%d nh=%d nh_k=%d", d.bs, d.nh, d.nh_k); return MILLION_ERR_SHAPE; }
-    if (wide ? !chunk_wide_geometry("chunk_attn_wide", d.d, d.M, d.C) : !u8_geometry("chunk_attn", d.d, d.M, d.C)) return MILLION_ERR_SHAPE;
+    if (wide ? !chunk_wide_geometry(packed ? "chunk_attn_packed" : "chunk_attn_wide", d.d, d.M, d.C) : !u8_geometry("chunk_attn", d.d, d.M, d.C)) return MILLION_ERR_SHAPE;
+    if (packed) {      // there is no packed row-major format, and a packed page exists for pages of 32 / 64 / 128 tokens only
+        int ps_shift;
+        if (d.k_layout != MILLION_KV_PAGED || d.v_layout != MILLION_KV_PAGED) {
+            set_error("chunk_attn_packed: k_layout=%d v_layout=%d (both MILLION_KV_PAGED: packed codes live in pages only)", d.k_layout, d.v_layout);
+            return MILLION_ERR_SHAPE;
+        }
+        if (!page_shift("chunk_attn_packed", d.page_size, ps_shift)) return MILLION_ERR_SHAPE;
+    }
     if (d.n_q < 0 || (d.n_c != 0 && d.n_c != d.n_q)) { set_error("chunk_attn: n_q=%d n_c=%d (n_c must be 0 or n_q)", d.n_q, d.n_c); return MILLION_ERR_SHAPE; }
     const bool dev_len = d.dev_lengths != nullptr;      // n_tokens is then the bound; r and resid_start are not read
     if (d.n_tokens < 0 || d.resid_cap < 0 ||
@@ -258,6 +267,7 @@ static int chunk_attn_impl(bool wide, const million_chunk_attn_desc *desc, const
     p.ntT = (d.n_tokens + kKeys - 1) / kKeys;
     p.ntR = (p.r + kKeys - 1) / kKeys;
     p.cb_bytes = d.n_tokens > 0 && !wide ? d.C * d.d * 2 : 0;
+    p.hb = packed ? packed_hi_bits(d.C) : 0;
     p.scale_log2e = 1.4426950408889634f / sqrtf((float)d.d);
     if (S > 1) {
         p.ws_o = (float *)workspace;
@@ -299,7 +309,7 @@ extern "C" int million_pq_chunk_attn(const million_chunk_attn_desc *desc, const 
                                      const void *k_cents_prepared, const void *v_cents_prepared, const void *k_resid,
                                      const void *v_resid, void *out, void *workspace, size_t workspace_bytes,
                                      million_stream_t stream) {
-    return chunk_attn_impl(false, desc, q, k_chunk, v_chunk, k_codes, v_codes, k_page_ids, v_page_ids, k_cents_prepared, v_cents_prepared,
+    return chunk_attn_impl(false, false, desc, q, k_chunk, v_chunk, k_codes, v_codes, k_page_ids, v_page_ids, k_cents_prepared, v_cents_prepared,
                            k_resid, v_resid, out, nullptr, workspace, workspace_bytes, stream);
 }
 
@@ -310,7 +320,7 @@ extern "C" int million_pq_chunk_attn_lse(const million_chunk_attn_desc *desc, co
                                          million_stream_t stream) {
     if (!lse) { set_error("chunk_attn_lse: lse null"); return MILLION_ERR_ARG; }
     if ((uintptr_t)lse & 3) { set_error("chunk_attn_lse: lse must be 4-byte aligned"); return MILLION_ERR_ALIGN; }
-    return chunk_attn_impl(false, desc, q, k_chunk, v_chunk, k_codes, v_codes, k_page_ids, v_page_ids, k_cents_prepared, v_cents_prepared,
+    return chunk_attn_impl(false, false, desc, q, k_chunk, v_chunk, k_codes, v_codes, k_page_ids, v_page_ids, k_cents_prepared, v_cents_prepared,
                            k_resid, v_resid, out, lse, workspace, workspace_bytes, stream);
 }
 
@@ -319,6 +329,15 @@ extern "C" int million_pq_chunk_attn_wide(const million_chunk_attn_desc *desc, c
                                           const void *k_cents, const void *v_cents, const void *k_resid, const void *v_resid,
                                           void *out, float *lse, void *workspace, size_t workspace_bytes, million_stream_t stream) {
     if ((uintptr_t)lse & 3) { set_error("chunk_attn_wide: lse must be 4-byte aligned"); return MILLION_ERR_ALIGN; }
-    return chunk_attn_impl(true, desc, q, k_chunk, v_chunk, k_codes, v_codes, k_page_ids, v_page_ids, k_cents, v_cents, k_resid,
+    return chunk_attn_impl(true, false, desc, q, k_chunk, v_chunk, k_codes, v_codes, k_page_ids, v_page_ids, k_cents, v_cents, k_resid,
+                           v_resid, out, lse, workspace, workspace_bytes, stream);
+}
+
+extern "C" int million_pq_chunk_attn_packed(const million_chunk_attn_desc *desc, const void *q, const void *k_chunk, const void *v_chunk,
+                                            const void *k_codes, const void *v_codes, const void *k_page_ids, const void *v_page_ids,
+                                            const void *k_cents, const void *v_cents, const void *k_resid, const void *v_resid,
+                                            void *out, float *lse, void *workspace, size_t workspace_bytes, million_stream_t stream) {
+    if ((uintptr_t)lse & 3) { set_error("chunk_attn_packed: lse must be 4-byte aligned"); return MILLION_ERR_ALIGN; }
+    return chunk_attn_impl(true, true, desc, q, k_chunk, v_chunk, k_codes, v_codes, k_page_ids, v_page_ids, k_cents, v_cents, k_resid,
                            v_resid, out, lse, workspace, workspace_bytes, stream);
 }

@@ -18,6 +18,10 @@
 // EVERY gathered index is code & (C - 1).  Code words past T, in page tails, in pages no live entry names and in poisoned
 // memory may hold any 16 bits: they are either never loaded (rows past a tile's valid count are written as zeros and masked)
 // or, loaded, index inside the table.  Page ids are trusted, as in every other kernel.
+//
+// Packed pages (million_hip.h, "Packed code pages"): chunk_attn_packed_kernel is this kernel with a third code producer,
+// ca_load_codes_packed (chunk_attn.h), which assembles the SAME word of 8 / d_m sixteen-bit fields from a token's low bytes and
+// its own high-plane byte(s).  Tile order, split cut, gathers, merge: unchanged, so out and lse are the uint16 launch's bits.
 #include "chunk_attn.h"
 
 namespace million {
@@ -29,10 +33,24 @@ __global__ __launch_bounds__(kThreads, 1) void chunk_attn_wide_kernel(ChunkParam
     chunk_attn_body<D, DM, RAGGED, LSE, true>(p);
 }
 
+// Packed pages (million_pq_chunk_attn_packed): the same body with ca_load_codes_packed as the code producer.  The high bits
+// per code, h = p.hb, are a wave-uniform field read when the kernel runs, not a template parameter: 16 more instances of this
+// body, not 32, for two variable shifts per code word.
+template <int D, int DM, bool RAGGED, bool LSE>
+__global__ __launch_bounds__(kThreads, 1) void chunk_attn_packed_kernel(ChunkParams p) {
+    chunk_attn_body<D, DM, RAGGED, LSE, true, true>(p);
+}
+
 template <int D, int DM>
 void launch_wide_t(const ChunkParams &p, long long blocks, int lds, hipStream_t s) {
     const bool ragged = p.dev_lengths || p.dev_n_q;
-    if (p.lse) {
+    if (p.hb) {
+        if (p.lse) {
+            if (ragged) launch_chunk_kernel(chunk_attn_packed_kernel<D, DM, true, true>, p, blocks, lds, s);
+            else launch_chunk_kernel(chunk_attn_packed_kernel<D, DM, false, true>, p, blocks, lds, s);
+        } else if (ragged) launch_chunk_kernel(chunk_attn_packed_kernel<D, DM, true, false>, p, blocks, lds, s);
+        else launch_chunk_kernel(chunk_attn_packed_kernel<D, DM, false, false>, p, blocks, lds, s);
+    } else if (p.lse) {
         if (ragged) launch_chunk_kernel(chunk_attn_wide_kernel<D, DM, true, true>, p, blocks, lds, s);
         else launch_chunk_kernel(chunk_attn_wide_kernel<D, DM, false, true>, p, blocks, lds, s);
     } else if (ragged) launch_chunk_kernel(chunk_attn_wide_kernel<D, DM, true, false>, p, blocks, lds, s);

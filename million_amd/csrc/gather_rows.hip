@@ -48,6 +48,7 @@ struct GatherParams {
     int t0, n_t, r, rstart, rcap;     // tokens [t0, t0 + n_t), r window rows from rstart in a ring of rcap
     long long res_sb, res_sh, o_sb, o_sh;      // fp16 elements
     int ps_shift, n_pages_cap;
+    int hb;                           // gather_rows_packed_kernel: high bits of a code beside its low byte (2 / 4)
 };
 
 // CodeT: uint8_t or uint16_t code words.  DM = d / M.
@@ -120,6 +121,87 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(GatherParams p) {
     }
 }
 
+// Packed pages (million_pq_gather_rows_packed; million_hip.h, "Packed code pages"): the same two phases.  Phase 1 copies the
+// tile's low-plane bytes and then its high-plane bytes to LDS, each plane in the order the store holds it (subspace / high byte
+// fastest for K pages, token fastest for the transposed V planes), one byte per thread: a wave's loads are consecutive bytes.
+// The LDS image is [token][M low bytes | M h / 8 high bytes], the row pitch an odd number of dwords.  Phase 2 assembles the raw
+// (8 + h)-bit field of a subspace from its two bytes and is gather_rows_kernel's from there: index c < C ? c : 0.  h is a
+// wave-uniform field, not a template parameter.  Only bytes of tokens t0 <= t < t1 are read.
+__host__ __device__ inline int gather_packed_pitch(int M, int h) {
+    const int dw = (M * (8 + h)) >> 5;      // a token's bytes are a multiple of 4 (M a multiple of 16)
+    return 4 * (dw | 1);
+}
+
+template <int DM>
+__global__ __launch_bounds__(256) void gather_rows_packed_kernel(GatherParams p) {
+    constexpr int NM = 8 / DM;
+    typedef struct { f16 v[DM]; } __attribute__((aligned(2 * DM))) Entry;
+    typedef f16 h8 __attribute__((ext_vector_type(8)));
+    extern __shared__ __attribute__((aligned(16))) char lds_codes[];
+    const int tid = threadIdx.x;
+    const int sidx = blockIdx.z;
+    const GatherSide &s = p.side[sidx];
+    const int b = blockIdx.y / p.nh_k, hk = blockIdx.y % p.nh_k;
+    const int M = p.M, C = p.C, d = p.d, h = p.hb;
+    const int HM = (M * h) >> 3;                     // high bytes of a token
+    const int pitch = gather_packed_pitch(M, h);
+    const Entry *tab = (const Entry *)s.cents;
+    const bool v_pages = sidx == 1;                  // transposed planes: token fastest
+    const long long bh = (long long)b * p.nh_k + hk;
+    const int *ids = s.page_ids + bh * p.n_pages_cap;
+    const int page = 1 << p.ps_shift;
+    const long long page_bytes = (long long)page * ((M * (8 + h)) >> 3);      // no power of two
+    const uint8_t *pool = (const uint8_t *)s.codes;
+    f16 *out = s.out + b * p.o_sb + hk * p.o_sh;
+    const f16 *resid = s.resid ? s.resid + b * p.res_sb + hk * p.res_sh : nullptr;
+    const int tpr = d / 8;
+    const int j0 = blockIdx.x * kGatherRows;
+    int n_code = p.n_t - j0;
+    n_code = n_code < 0 ? 0 : (n_code > kGatherRows ? kGatherRows : n_code);
+    // ---- phase 1: low plane, then high plane -> LDS [row][M | HM] ----
+    for (int e = tid; e < kGatherRows * (M + HM); e += 256) {
+        const bool hi = e >= kGatherRows * M;        // wave-uniform: 64 M is a multiple of 256
+        const int f = hi ? e - kGatherRows * M : e;
+        const int W = hi ? HM : M;                   // bytes of a token in this plane
+        const int row = v_pages ? f % kGatherRows : f / W;
+        const int m = v_pages ? f / kGatherRows : f % W;
+        if (row < n_code) {
+            const int t = p.t0 + j0 + row;           // < t1
+            const long long pid = ids[t >> p.ps_shift];
+            const int tin = t & (page - 1);
+            const int off = (hi ? page * M : 0) + (v_pages ? m * page + tin : tin * W + m);
+            lds_codes[row * pitch + (hi ? M : 0) + m] = (char)pool[pid * page_bytes + off];
+        }
+    }
+    __syncthreads();
+    // ---- phase 2: thread = (row, 16-byte piece) ----
+    const unsigned fmask = (1u << h) - 1u;
+    for (int it = tid; it < kGatherRows * tpr; it += 256) {
+        const int row = it / tpr, ch = it - row * tpr;
+        const int j = j0 + row;
+        if (row < n_code) {
+            const uint8_t *rowc = (const uint8_t *)lds_codes + row * pitch;
+            Entry en[NM];
+#pragma unroll
+            for (int i = 0; i < NM; ++i) {
+                const int m = ch * NM + i;
+                const unsigned c = (unsigned)rowc[m] | ((((unsigned)rowc[M + ((m * h) >> 3)] >> ((m * h) & 7)) & fmask) << 8);
+                en[i] = tab[(long long)m * C + (c < (unsigned)C ? c : 0u)];
+            }
+            h8 o;
+#pragma unroll
+            for (int i = 0; i < NM; ++i)
+#pragma unroll
+                for (int k = 0; k < DM; ++k) o[i * DM + k] = en[i].v[k];
+            *(h8 *)(out + (long long)j * d + 8 * ch) = o;
+        } else if (j - p.n_t < p.r) {
+            int rr = p.rstart + (j - p.n_t);
+            rr = rr >= p.rcap ? rr - p.rcap : rr;
+            *(h8 *)(out + (long long)j * d + 8 * ch) = *(const h8 *)(resid + (long long)rr * d + 8 * ch);
+        }
+    }
+}
+
 template <typename CodeT, int DM>
 void launch_gather_t(const GatherParams &p, dim3 grid, int lds, hipStream_t s) {
     hipLaunchKernelGGL((gather_rows_kernel<CodeT, DM>), grid, dim3(256), lds, s, p);
@@ -131,10 +213,11 @@ void launch_gather_t(const GatherParams &p, dim3 grid, int lds, hipStream_t s) {
 
 using namespace million;
 
-extern "C" int million_pq_gather_rows(const million_gather_rows_desc *desc, const void *k_codes, const void *v_codes,
-                                      const int32_t *k_page_ids, const int32_t *v_page_ids, const void *k_cents,
-                                      const void *v_cents, const void *k_resid, const void *v_resid, void *k_out, void *v_out,
-                                      million_stream_t stream) {
+// `packed`: million_pq_gather_rows_packed - both sides pools of packed pages, code_bytes = 2 (the logical width of a code)
+static int gather_rows_impl(bool packed, const million_gather_rows_desc *desc, const void *k_codes, const void *v_codes,
+                            const int32_t *k_page_ids, const int32_t *v_page_ids, const void *k_cents,
+                            const void *v_cents, const void *k_resid, const void *v_resid, void *k_out, void *v_out,
+                            million_stream_t stream) {
     if (!desc || desc->struct_size != sizeof(million_gather_rows_desc)) { set_error("gather_rows: bad desc / struct_size"); return MILLION_ERR_ARG; }
     const million_gather_rows_desc &d = *desc;
     if (d.bs <= 0 || d.nh_k <= 0 || (long long)d.bs * d.nh_k > 65535) { set_error("gather_rows: bs=%d nh_k=%d (bs * nh_k <= 65535)", d.bs, d.nh_k); return MILLION_ERR_SHAPE; }
@@ -148,6 +231,14 @@ extern "C" int million_pq_gather_rows(const million_gather_rows_desc *desc, cons
     } else if (d.code_bytes == 2) {
         if (d.C != 512 && d.C != 1024 && d.C != 2048 && d.C != 4096) { set_error("gather_rows: C=%d with uint16 codes (512, 1024, 2048 or 4096)", d.C); return MILLION_ERR_SHAPE; }
     } else { set_error("gather_rows: code_bytes=%d (1: uint8, 2: uint16)", d.code_bytes); return MILLION_ERR_SHAPE; }
+    if (packed) {
+        if (d.code_bytes != 2) { set_error("gather_rows_packed: code_bytes=%d (2: packed pages hold codes of 512 .. 4096 centroids)", d.code_bytes); return MILLION_ERR_SHAPE; }
+        if (!wide_geometry(d.d, d.M, d.C, 1)) { set_error("gather_rows_packed: d=%d M=%d C=%d (d 64 / 128, d / M 2 or 4, C 512 / 1024 / 2048 / 4096)", d.d, d.M, d.C); return MILLION_ERR_SHAPE; }
+        if (d.k_layout != MILLION_KV_PAGED || d.v_layout != MILLION_KV_PAGED) {
+            set_error("gather_rows_packed: k_layout=%d v_layout=%d (both MILLION_KV_PAGED: packed codes live in pages only)", d.k_layout, d.v_layout);
+            return MILLION_ERR_SHAPE;
+        }
+    }
     if (d.t0 < 0 || d.t1 < d.t0 || d.r < 0 || d.resid_cap < 0 || d.r > d.resid_cap || d.resid_start < 0 || (d.resid_cap > 0 && d.resid_start >= d.resid_cap) ||
         (d.resid_cap == 0 && d.resid_start != 0)) {
         set_error("gather_rows: t0=%d t1=%d r=%d resid_start=%d resid_cap=%d", d.t0, d.t1, d.r, d.resid_start, d.resid_cap);
@@ -179,6 +270,7 @@ extern "C" int million_pq_gather_rows(const million_gather_rows_desc *desc, cons
         return MILLION_ERR_ALIGN;
     }
     if ((d.o_stride_b | d.o_stride_h | d.resid_stride_b | d.resid_stride_h) & 7) { set_error("gather_rows: out and window strides must be multiples of 8 elements (16-byte rows)"); return MILLION_ERR_ALIGN; }
+    if (packed && (((uintptr_t)k_codes | (uintptr_t)v_codes) & 15)) { set_error("gather_rows_packed: the pools must be 16-byte aligned"); return MILLION_ERR_ALIGN; }
     if (d.code_bytes == 2 && ((((uintptr_t)k_codes | (uintptr_t)v_codes) & 1) || ((d.k_stride_b | d.k_stride_h | d.v_stride_b | d.v_stride_h) & 1))) {
         set_error("gather_rows: uint16 codes need 2-byte aligned pointers and strides");
         return MILLION_ERR_ALIGN;
@@ -191,11 +283,13 @@ extern "C" int million_pq_gather_rows(const million_gather_rows_desc *desc, cons
     p.t0 = d.t0; p.n_t = d.t1 - d.t0; p.r = d.r; p.rstart = d.resid_start; p.rcap = d.resid_cap;
     p.res_sb = d.resid_stride_b; p.res_sh = d.resid_stride_h; p.o_sb = d.o_stride_b; p.o_sh = d.o_stride_h;
     p.ps_shift = ps_shift; p.n_pages_cap = d.n_pages_cap;
+    p.hb = packed ? packed_hi_bits(d.C) : 0;
     const long long n_tiles = (n_rows + kGatherRows - 1) / kGatherRows;      // < 2^26: n_rows fits an int
     const dim3 grid((unsigned)n_tiles, (unsigned)(d.bs * d.nh_k), 2);
-    const int lds = kGatherRows * (d.M * d.code_bytes + 4);
+    const int lds = packed ? kGatherRows * gather_packed_pitch(d.M, p.hb) : kGatherRows * (d.M * d.code_bytes + 4);
     const hipStream_t s = (hipStream_t)stream;
     const bool ok = dispatch_dm(d.d / d.M, [&](auto w) {
+        if constexpr (w() == 2 || w() == 4) if (packed) { hipLaunchKernelGGL((gather_rows_packed_kernel<w()>), grid, dim3(256), lds, s, p); return; }
         if (d.code_bytes == 1) launch_gather_t<uint8_t, w()>(p, grid, lds, s);
         else launch_gather_t<uint16_t, w()>(p, grid, lds, s);
     });
@@ -203,4 +297,18 @@ extern "C" int million_pq_gather_rows(const million_gather_rows_desc *desc, cons
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("gather_rows launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
     return MILLION_OK;
+}
+
+extern "C" int million_pq_gather_rows(const million_gather_rows_desc *desc, const void *k_codes, const void *v_codes,
+                                      const int32_t *k_page_ids, const int32_t *v_page_ids, const void *k_cents,
+                                      const void *v_cents, const void *k_resid, const void *v_resid, void *k_out, void *v_out,
+                                      million_stream_t stream) {
+    return gather_rows_impl(false, desc, k_codes, v_codes, k_page_ids, v_page_ids, k_cents, v_cents, k_resid, v_resid, k_out, v_out, stream);
+}
+
+extern "C" int million_pq_gather_rows_packed(const million_gather_rows_desc *desc, const void *k_pool, const void *v_pool,
+                                             const int32_t *k_page_ids, const int32_t *v_page_ids, const void *k_cents,
+                                             const void *v_cents, const void *k_resid, const void *v_resid, void *k_out, void *v_out,
+                                             million_stream_t stream) {
+    return gather_rows_impl(true, desc, k_pool, v_pool, k_page_ids, v_page_ids, k_cents, v_cents, k_resid, v_resid, k_out, v_out, stream);
 }

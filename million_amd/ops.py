@@ -782,7 +782,8 @@ def pq_pack_pages(pages: torch.Tensor, *, side: str, C: int, out: Optional[torch
 
 def pq_unpack_pages(packed: torch.Tensor, *, side: str, page_size: int, M: int, C: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Packed pages uint8 (n, packed_page_bytes) -> uint16 K pages (n, page_size, M) or V pages (n, M, page_size): the way of
-    everything that reads uint16 pages (chunk attention, pq_gather_rows, pq_decode) to codes held in packed pages."""
+    what reads uint16 pages only (pq_decode) to codes held in packed pages; chunk attention and pq_gather_rows read packed pages
+    themselves (pq_chunk_attn_packed, pq_gather_rows(packed=True))."""
     return _repack("pq_unpack_pages", L.MILLION_REPACK_UNPACK, packed, side, page_size, M, C, out)
 
 
@@ -1071,15 +1072,23 @@ def chunk_attn_wide_workspace_bytes(desc: L.ChunkAttnDesc) -> int:
 
 
 def _chunk_attn_call(who, wide, q, k_chunk, v_chunk, k_codes, v_codes, k_prep, v_prep, k_res, v_res, r, M, C, n_tokens, resid_start,
-                     k_page_ids, v_page_ids, page_size, out, workspace, dev_lengths, dev_n_q, return_lse, lse):
-    """pq_chunk_attn (wide = False: uint8 codes, prepared codebooks) and pq_chunk_attn_wide (uint16 codes, the plain codebooks in
-    k_prep / v_prep): one set of checks, one descriptor, the entry point of the width."""
+                     k_page_ids, v_page_ids, page_size, out, workspace, dev_lengths, dev_n_q, return_lse, lse, packed=False):
+    """pq_chunk_attn (wide = False: uint8 codes, prepared codebooks), pq_chunk_attn_wide (uint16 codes, the plain codebooks in
+    k_prep / v_prep) and pq_chunk_attn_packed (wide and packed: pools of packed pages): one set of checks, one descriptor, the
+    entry point of the format."""
     _need_cuda(q, k_chunk, v_chunk, k_codes, v_codes, k_prep, v_prep, k_res, v_res, k_page_ids, v_page_ids, out, workspace,
                dev_lengths, dev_n_q, lse)
     if q.dtype != torch.float16 or k_res.dtype != torch.float16 or v_res.dtype != torch.float16:
         raise RuntimeError(f"{who}: q and window buffers must be fp16")
     if wide:
-        if k_codes.dtype != torch.uint16 or v_codes.dtype != torch.uint16:
+        if packed:
+            if k_page_ids is None or v_page_ids is None:
+                raise RuntimeError(f"{who}: packed codes live in pages only - k_page_ids and v_page_ids are both needed")
+            if page_size not in (32, 64, 128):
+                raise RuntimeError(f"{who}: page_size={page_size} (32, 64 or 128)")
+            _check_packed_pool(who, k_codes, page_size, M, C)
+            _check_packed_pool(who, v_codes, page_size, M, C)
+        elif k_codes.dtype != torch.uint16 or v_codes.dtype != torch.uint16:
             raise RuntimeError(f"{who}: codes must be uint16 (uint8 codes: pq_chunk_attn)")
         for t in (k_prep, v_prep):
             if t.dtype != torch.float16 or t.dim() != 3 or not t.is_contiguous():
@@ -1123,6 +1132,8 @@ def _chunk_attn_call(who, wide, q, k_chunk, v_chunk, k_codes, v_codes, k_prep, v
     if (k_paged or v_paged) and page_size is None:
         raise RuntimeError(f"{who}: paged codes need page_size")
     for name, codes, paged in (("k_codes", k_codes, k_paged), ("v_codes", v_codes, v_paged)):
+        if packed:
+            continue      # _check_packed_pool above
         if paged:
             if not codes.is_contiguous() or codes.dim() != 3:
                 raise RuntimeError(f"{who}: {name} page pool must be contiguous (n_pool, ., .)")
@@ -1147,6 +1158,8 @@ def _chunk_attn_call(who, wide, q, k_chunk, v_chunk, k_codes, v_codes, k_prep, v
                            n_pages_cap=n_pages_cap, page_ids_i64=ids64, k_codes=k_codes, v_codes=v_codes, k_chunk=k_chunk,
                            v_chunk=v_chunk, out=out, dev_lengths=dev_lengths, dev_n_q=dev_n_q)
     lib = L.load()
+    wide_name = "million_pq_chunk_attn_packed" if packed else "million_pq_chunk_attn_wide"
+    wide_entry = getattr(lib, wide_name) if wide else None
     need = (lib.million_chunk_attn_wide_workspace_bytes if wide else lib.million_chunk_attn_workspace_bytes)(ctypes.byref(desc))
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=q.device) if need else None
@@ -1155,18 +1168,17 @@ def _chunk_attn_call(who, wide, q, k_chunk, v_chunk, k_codes, v_codes, k_prep, v
             lse = torch.empty(bs, nh, n_q, dtype=torch.float32, device=q.device)
         elif lse.dtype != torch.float32 or tuple(lse.shape) != (bs, nh, n_q) or not lse.is_contiguous():
             raise RuntimeError(f"{who}: lse must be contiguous fp32 (bs, nh, n_q)")
-        L.check((lib.million_pq_chunk_attn_wide if wide else lib.million_pq_chunk_attn_lse)(ctypes.byref(desc), q.data_ptr(), _ptr(k_chunk), _ptr(v_chunk), k_codes.data_ptr(),
+        L.check((wide_entry if wide else lib.million_pq_chunk_attn_lse)(ctypes.byref(desc), q.data_ptr(), _ptr(k_chunk), _ptr(v_chunk), k_codes.data_ptr(),
                                               v_codes.data_ptr(), _ptr(k_page_ids), _ptr(v_page_ids), k_prep.data_ptr(),
                                               v_prep.data_ptr(), k_res.data_ptr(), v_res.data_ptr(), out.data_ptr(), lse.data_ptr(),
                                               _ptr(workspace), 0 if workspace is None else workspace.numel(), _stream()),
-                "million_pq_chunk_attn_wide" if wide else "million_pq_chunk_attn_lse")
+                wide_name if wide else "million_pq_chunk_attn_lse")
         return out, lse
     if wide:
-        L.check(lib.million_pq_chunk_attn_wide(ctypes.byref(desc), q.data_ptr(), _ptr(k_chunk), _ptr(v_chunk), k_codes.data_ptr(),
-                                               v_codes.data_ptr(), _ptr(k_page_ids), _ptr(v_page_ids), k_prep.data_ptr(),
-                                               v_prep.data_ptr(), k_res.data_ptr(), v_res.data_ptr(), out.data_ptr(), None,
-                                               _ptr(workspace), 0 if workspace is None else workspace.numel(), _stream()),
-                "million_pq_chunk_attn_wide")
+        L.check(wide_entry(ctypes.byref(desc), q.data_ptr(), _ptr(k_chunk), _ptr(v_chunk), k_codes.data_ptr(),
+                           v_codes.data_ptr(), _ptr(k_page_ids), _ptr(v_page_ids), k_prep.data_ptr(),
+                           v_prep.data_ptr(), k_res.data_ptr(), v_res.data_ptr(), out.data_ptr(), None,
+                           _ptr(workspace), 0 if workspace is None else workspace.numel(), _stream()), wide_name)
         return out
     L.check(lib.million_pq_chunk_attn(ctypes.byref(desc), q.data_ptr(), _ptr(k_chunk), _ptr(v_chunk), k_codes.data_ptr(),
                                       v_codes.data_ptr(), _ptr(k_page_ids), _ptr(v_page_ids), k_prep.data_ptr(), v_prep.data_ptr(),
@@ -1216,6 +1228,20 @@ def pq_chunk_attn_wide(q: torch.Tensor, k_chunk: Optional[torch.Tensor], v_chunk
                             k_page_ids, v_page_ids, page_size, out, workspace, dev_lengths, dev_n_q, return_lse, lse)
 
 
+def pq_chunk_attn_packed(q: torch.Tensor, k_chunk: Optional[torch.Tensor], v_chunk: Optional[torch.Tensor], k_codes: torch.Tensor,
+                  v_codes: torch.Tensor, k_cents: torch.Tensor, v_cents: torch.Tensor, k_res: torch.Tensor, v_res: torch.Tensor,
+                  r: int, *, M: int, C: int, n_tokens: int, resid_start: int = 0, k_page_ids: Optional[torch.Tensor] = None,
+                  v_page_ids: Optional[torch.Tensor] = None, page_size: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                  workspace: Optional[torch.Tensor] = None, dev_lengths: Optional[torch.Tensor] = None,
+                  dev_n_q: Optional[torch.Tensor] = None, return_lse: bool = False, lse: Optional[torch.Tensor] = None):
+    """pq_chunk_attn_wide over pools of packed pages (million_pq_chunk_attn_packed): k_codes / v_codes contiguous uint8
+    (n_pool, packed_page_bytes(page_size, M, C)), both page-id tensors required (there is no packed row-major format), page_size
+    32 / 64 / 128.  Everything else - arguments, checks, ragged fields, lse, workspace (chunk_attn_wide_workspace_bytes) - as
+    pq_chunk_attn_wide, and the result is that call's over uint16 pools holding the same codes, bit for bit."""
+    return _chunk_attn_call("pq_chunk_attn_packed", True, q, k_chunk, v_chunk, k_codes, v_codes, k_cents, v_cents, k_res, v_res, r, M, C, n_tokens, resid_start,
+                            k_page_ids, v_page_ids, page_size, out, workspace, dev_lengths, dev_n_q, return_lse, lse, packed=True)
+
+
 def attn_merge(outs, lses, out: Optional[torch.Tensor] = None, lse_out: Optional[torch.Tensor] = None, return_lse: bool = False):
     """Merge of partial attentions (million_attn_merge): outs[i] fp16 (bs, nh, n_q, d) and lses[i] fp32 (bs, nh, n_q) are the
     results of one query over DISJOINT key sets (pq_decode_attn / pq_chunk_attn with return_lse); returns their softmax over
@@ -1261,13 +1287,17 @@ def pq_gather_rows(k_codes: torch.Tensor, v_codes: torch.Tensor, k_cents: torch.
                    k_out: torch.Tensor, v_out: torch.Tensor, *, t0: int, t1: int, k_res: Optional[torch.Tensor] = None,
                    v_res: Optional[torch.Tensor] = None, r: int = 0, resid_start: int = 0,
                    k_page_ids: Optional[torch.Tensor] = None, v_page_ids: Optional[torch.Tensor] = None,
-                   page_size: Optional[int] = None) -> int:
+                   page_size: Optional[int] = None, packed: bool = False) -> int:
     """Tokens [t0, t1) of every request dequantised from its code store, then its r window rows in ring order from resid_start, as
     fp16 rows from row 0 of k_out / v_out (bs, nh_k, rows_cap, d) (million_pq_gather_rows; one launch does K and V).  Returns the
     rows written, (t1 - t0) + r; the rows behind them are not touched.  A code side is row-major (bs, nh_k, T_cap, M) when its
     page ids are None, else a page pool (K (n_pool, page_size, M), V (n_pool, M, page_size)) behind int32 ids (bs, nh_k, n_pages).
     uint8 codes with any C <= 256, uint16 codes with C in 512 / 1024 / 2048 / 4096; k_cents / v_cents are the plain contiguous
-    fp16 (M, C, d_m) codebooks.  The coded rows are pq_decode's, bit for bit.  Host lengths only.  Nothing is allocated."""
+    fp16 (M, C, d_m) codebooks.  The coded rows are pq_decode's, bit for bit.  Host lengths only.  Nothing is allocated.
+    packed=True (million_pq_gather_rows_packed): k_codes / v_codes are pools of packed pages, contiguous uint8
+    (n_pool, packed_page_bytes(page_size, M, C)), C in 512 / 1024 / 2048 / 4096, d / M 2 or 4, both page-id tensors required; the
+    rows are those of the call over the pq_unpack_pages image of the pools, bit for bit.  Without the flag a uint8 pool means
+    8-bit codes, as ever."""
     _need_cuda(k_codes, v_codes, k_cents, v_cents, k_out, v_out, k_res, v_res, k_page_ids, v_page_ids)
     who = "pq_gather_rows"
     for t in (k_cents, v_cents):
@@ -1275,9 +1305,18 @@ def pq_gather_rows(k_codes: torch.Tensor, v_codes: torch.Tensor, k_cents: torch.
             raise RuntimeError(f"{who}: k_cents / v_cents must be the plain contiguous fp16 (M, C, d_m) codebooks, alike")
     M, C, dm = k_cents.shape
     d = M * dm
-    if k_codes.dtype != v_codes.dtype or k_codes.dtype not in (torch.uint8, torch.uint16):
+    if packed:
+        if k_page_ids is None or v_page_ids is None:
+            raise RuntimeError(f"{who}: packed codes live in pages only - k_page_ids and v_page_ids are both needed")
+        if page_size not in (32, 64, 128):
+            raise RuntimeError(f"{who}: page_size={page_size} (32, 64 or 128)")
+        _check_packed_pool(who, k_codes, page_size, M, C)
+        _check_packed_pool(who, v_codes, page_size, M, C)
+        if dm not in (2, 4):
+            raise RuntimeError(f"{who}: d / M = {dm} over packed pages (2 or 4)")
+    elif k_codes.dtype != v_codes.dtype or k_codes.dtype not in (torch.uint8, torch.uint16):
         raise RuntimeError(f"{who}: codes must be uint8 or uint16, both sides alike")
-    code_bytes = k_codes.element_size()
+    code_bytes = 2 if packed else k_codes.element_size()
     if (code_bytes == 1 and C > 256) or (code_bytes == 2 and C not in WIDE_CENTROIDS):
         raise RuntimeError(f"{who}: C={C} does not go with {k_codes.dtype} codes (uint8: C <= 256; uint16: C in {WIDE_CENTROIDS})")
     for t in (k_out, v_out):
@@ -1307,6 +1346,8 @@ def pq_gather_rows(k_codes: torch.Tensor, v_codes: torch.Tensor, k_cents: torch.
     if (k_paged or v_paged) and page_size is None:
         raise RuntimeError(f"{who}: paged codes need page_size")
     for name, codes, paged in (("k_codes", k_codes, k_paged), ("v_codes", v_codes, v_paged)):
+        if packed:
+            continue      # _check_packed_pool above
         if paged:
             if not codes.is_contiguous() or codes.dim() != 3:
                 raise RuntimeError(f"{who}: {name} page pool must be contiguous (n_pool, ., .)")
@@ -1331,6 +1372,11 @@ def pq_gather_rows(k_codes: torch.Tensor, v_codes: torch.Tensor, k_cents: torch.
     if not v_paged:
         desc.v_stride_b, desc.v_stride_h = (v_codes.stride(i) * code_bytes for i in (0, 1))
     desc.rows_cap, desc.o_stride_b, desc.o_stride_h = rows_cap, k_out.stride(0), k_out.stride(1)
+    if packed:
+        L.check(L.load().million_pq_gather_rows_packed(ctypes.byref(desc), k_codes.data_ptr(), v_codes.data_ptr(), _ptr(k_page_ids),
+                                                       _ptr(v_page_ids), k_cents.data_ptr(), v_cents.data_ptr(), _ptr(k_res), _ptr(v_res),
+                                                       k_out.data_ptr(), v_out.data_ptr(), _stream()), "million_pq_gather_rows_packed")
+        return int(t1) - int(t0) + int(r)
     L.check(L.load().million_pq_gather_rows(ctypes.byref(desc), k_codes.data_ptr(), v_codes.data_ptr(), _ptr(k_page_ids), _ptr(v_page_ids),
                                             k_cents.data_ptr(), v_cents.data_ptr(), _ptr(k_res), _ptr(v_res), k_out.data_ptr(),
                                             v_out.data_ptr(), _stream()), "million_pq_gather_rows")
@@ -1402,7 +1448,7 @@ def pq_chunk_attn_blocks(q: torch.Tensor, k_chunk: Optional[torch.Tensor], v_chu
                          v_page_ids: Optional[torch.Tensor] = None, page_size: Optional[int] = None, out: Optional[torch.Tensor] = None,
                          workspace: Optional[torch.Tensor] = None, dev_lengths: Optional[torch.Tensor] = None,
                          dev_n_q: Optional[torch.Tensor] = None, return_lse: bool = False, lse: Optional[torch.Tensor] = None,
-                         block_tokens: Optional[int] = None):
+                         block_tokens: Optional[int] = None, packed: bool = False):
     """Chunk attention by blocks - pq_chunk_attn's meaning (n_q rows against [the codes of n_tokens tokens; r window rows; the chunk,
     causally]) and arguments, uint8 codes with prepared codebooks as pq_chunk_attn or uint16 codes with the plain codebooks as
     pq_chunk_attn_wide (the code dtype selects), served by the prompt kernel: per block of block_tokens past tokens one
@@ -1412,7 +1458,10 @@ def pq_chunk_attn_blocks(q: torch.Tensor, k_chunk: Optional[torch.Tensor], v_chu
     (profiles/chunk_blocks.txt); its transient memory, chunk_blocks_workspace_bytes, does not grow with n_tokens.
     Host lengths only: dev_lengths / dev_n_q raise.  With out=, workspace= and, when asked for, lse= the call allocates nothing
     and is a chain of launches on the current stream: it can be captured into a graph.  Each part's out is rounded to fp16
-    before the merge: the result is within the attention bar of pq_chunk_attn's, not bitwise equal to it."""
+    before the merge: the result is within the attention bar of pq_chunk_attn's, not bitwise equal to it.
+    packed=True: k_codes / v_codes are pools of packed pages (uint8 there cannot select: it already means prepared codebooks) and
+    k_prep / v_prep the plain codebooks; the flag goes to pq_gather_rows and nothing else in the route changes, so the result is
+    bitwise the uint16 route's over the same codes."""
     who = "pq_chunk_attn_blocks"
     if dev_lengths is not None or dev_n_q is not None:
         raise RuntimeError(f"{who}: host lengths only - dev_lengths / dev_n_q are pq_chunk_attn's (the chunk route)")
@@ -1426,7 +1475,7 @@ def pq_chunk_attn_blocks(q: torch.Tensor, k_chunk: Optional[torch.Tensor], v_chu
     if M <= 0 or d % M:
         raise RuntimeError(f"{who}: d={d} M={M}")
     dm = d // M
-    if k_codes.dtype == torch.uint16:      # the plain codebooks, as pq_chunk_attn_wide takes them
+    if packed or k_codes.dtype == torch.uint16:      # the plain codebooks, as pq_chunk_attn_wide / pq_chunk_attn_packed take them
         k_cents, v_cents = k_prep, v_prep
     elif k_codes.dtype == torch.uint8:     # prepared codebooks, as pq_chunk_attn takes them: their first image is the plain [m][c][d_m] table
         _check_prepared(who, k_prep, v_prep, M, C, d)
@@ -1475,7 +1524,8 @@ def pq_chunk_attn_blocks(q: torch.Tensor, k_chunk: Optional[torch.Tensor], v_chu
             return
         _, t0, t1, r_here = part
         n = pq_gather_rows(k_codes, v_codes, k_cents, v_cents, kscr, vscr, t0=t0, t1=t1, k_res=k_res, v_res=v_res, r=r_here,
-                           resid_start=resid_start if r_here else 0, k_page_ids=k_page_ids, v_page_ids=v_page_ids, page_size=page_size)
+                           resid_start=resid_start if r_here else 0, k_page_ids=k_page_ids, v_page_ids=v_page_ids, page_size=page_size,
+                           **({"packed": True} if packed else {}))
         prefill_attn(q, kscr[:, :, :n], vscr[:, :, :n], causal=False, out=o, lse=l)
 
     if len(parts) == 1:      # one part is the result

@@ -457,7 +457,7 @@ class PagedPQCache(_CacheBase):
     `nbits` 9 .. 12 with `dtype=torch.uint16` (uint16 pools, codebooks of 2**nbits centroids): the core life - prefill,
     prefill_request, decoding_with_pages (ops.pq_decode_attn_wide), the in-line flush of requests in lockstep, release, cleanup -
     and NotImplementedError naming nbits for the rest (extend*, prefill_ragged, fork, swap, verify / commit, update, sinks).
-    DESIGN.md 4.14.
+    DESIGN.md 4.14.  extend / extend_request of such a cache, packed or not: million_amd.paged_turns.
 
     `packed=True` (nbits 9 .. 12 only; nbits = 8: ValueError): the same cache over packed pools - uint8 (n_pool,
     ops.packed_page_bytes), 10 bits per code at nbits 9 / 10 and 12 at nbits 11 / 12 instead of 16 (include/million_hip.h,
