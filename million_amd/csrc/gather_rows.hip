@@ -19,6 +19,10 @@
 //     wave fall into different banks.  (2) thread = (row, 16-byte piece): it reads its 8 / d_m codes from LDS, fetches the
 //     entries and stores ONE 16-byte piece; the d / 8 threads of a row store consecutive pieces: token-major rows leave as
 //     16-byte stores whatever the layout of the codes.  Window rows are copied in phase 2, 16 bytes per thread.
+//   * one body, gather_rows_body<Codes, DM>, for every code format, as chunk_attn_body has a code producer per format: a code
+//     source (CodeWords<uint8_t>, CodeWords<uint16_t>, PackedPlanes) says the LDS row pitch, copies a tile's code bytes to LDS
+//     (phase 1) and reads the code of a subspace from an LDS row (phase 2); the prologue, the tile bounds, phase 2 and the window
+//     copy are shared.
 //   * an index is c < C ? c : 0, million_pq_decode's rule, so the result is that call's bit for bit - for every code word.
 //   * what is read: code words of tokens t0 <= t < t1 only, page ids of those tokens' pages only, window rows of the ring's
 //     valid span only.  Every byte offset is 64-bit.
@@ -48,52 +52,103 @@ struct GatherParams {
     int t0, n_t, r, rstart, rcap;     // tokens [t0, t0 + n_t), r window rows from rstart in a ring of rcap
     long long res_sb, res_sh, o_sb, o_sh;      // fp16 elements
     int ps_shift, n_pages_cap;
-    int hb;                           // gather_rows_packed_kernel: high bits of a code beside its low byte (2 / 4)
+    int hb;                           // packed pages: high bits of a code beside its low byte (2 / 4)
 };
 
-// CodeT: uint8_t or uint16_t code words.  DM = d / M.
-template <typename CodeT, int DM>
-__global__ __launch_bounds__(256) void gather_rows_kernel(GatherParams p) {
+// A code source: how a tile's code bytes reach LDS (phase 1) and how a code is read back from its LDS row (phase 2).
+//   pitch(M, h)          bytes of a token's LDS row: its code bytes rounded to an odd number of dwords
+//   load_tile(...)       the code bytes of tokens [t_first, t_first + n_code) of (b, hk) -> lds [row][pitch], read in the order the
+//                        store holds them: a wave's loads are consecutive bytes
+//   code(row, m, M, h)   the code of subspace m from an LDS row
+template <typename CodeT>
+struct CodeWords {      // one word per code: row-major (bs, nh_k, T, M) or K pages (n_pool, page, M) / V pages (n_pool, M, page)
+    __host__ __device__ static int pitch(int M, int) { return M * (int)sizeof(CodeT) + 4; }
+    __device__ static void load_tile(char *lds, const GatherParams &p, const GatherSide &s, int sidx, int b, int hk, int t_first, int n_code) {
+        const int M = p.M, row_pitch = pitch(M, 0);
+        const bool v_pages = s.paged && sidx == 1;       // transposed pages: token fastest
+        const long long bh = (long long)b * p.nh_k + hk;
+        const int *ids = s.paged ? s.page_ids + bh * p.n_pages_cap : nullptr;
+        const char *rm_base = (const char *)s.codes + b * s.sb + hk * s.sh;      // row-major
+        const int page = 1 << p.ps_shift;
+        for (int e = threadIdx.x; e < kGatherRows * M; e += 256) {
+            const int row = v_pages ? e % kGatherRows : e / M;
+            const int m = v_pages ? e / kGatherRows : e % M;
+            if (row < n_code) {
+                const int t = t_first + row;             // < t1: the host checked t1 against the store's capacity
+                long long off;                           // in code words
+                if (s.paged) {
+                    const long long pid = ids[t >> p.ps_shift];
+                    const int tin = t & (page - 1);
+                    off = v_pages ? (pid * M + m) * page + tin : (pid * page + tin) * M + m;
+                } else {
+                    off = (long long)t * M + m;
+                }
+                const CodeT c = s.paged ? ((const CodeT *)s.codes)[off] : ((const CodeT *)rm_base)[off];
+                *(CodeT *)(lds + row * row_pitch + m * (int)sizeof(CodeT)) = c;
+            }
+        }
+    }
+    __device__ static unsigned code(const char *row, int m, int, int) { return ((const CodeT *)row)[m]; }
+};
+
+// Packed pages (million_hip.h, "Packed code pages"), pages only: the low plane's bytes, then the high plane's, each plane in the
+// order the store holds it (subspace / high byte fastest for K pages, token fastest for the transposed V planes), one byte per
+// thread.  The LDS row is [M low bytes | M h / 8 high bytes]; h = GatherParams::hb is a wave-uniform field.
+struct PackedPlanes {
+    __host__ __device__ static int pitch(int M, int h) { return 4 * (((M * (8 + h)) >> 5) | 1); }      // a token's bytes are a multiple of 4 (16 | M)
+    __device__ static void load_tile(char *lds, const GatherParams &p, const GatherSide &s, int sidx, int b, int hk, int t_first, int n_code) {
+        const int M = p.M, h = p.hb, row_pitch = pitch(M, h);
+        const int HM = (M * h) >> 3;                     // high bytes of a token
+        const bool v_pages = sidx == 1;                  // transposed planes: token fastest
+        const long long bh = (long long)b * p.nh_k + hk;
+        const int *ids = s.page_ids + bh * p.n_pages_cap;
+        const int page = 1 << p.ps_shift;
+        const long long page_bytes = (long long)page * ((M * (8 + h)) >> 3);      // no power of two
+        const uint8_t *pool = (const uint8_t *)s.codes;
+        for (int e = threadIdx.x; e < kGatherRows * (M + HM); e += 256) {
+            const bool hi = e >= kGatherRows * M;        // wave-uniform: 64 M is a multiple of 256
+            const int f = hi ? e - kGatherRows * M : e;
+            const int W = hi ? HM : M;                   // bytes of a token in this plane
+            const int row = v_pages ? f % kGatherRows : f / W;
+            const int m = v_pages ? f / kGatherRows : f % W;
+            if (row < n_code) {
+                const int t = t_first + row;             // < t1
+                const long long pid = ids[t >> p.ps_shift];
+                const int tin = t & (page - 1);
+                const int off = (hi ? page * M : 0) + (v_pages ? m * page + tin : tin * W + m);
+                lds[row * row_pitch + (hi ? M : 0) + m] = (char)pool[pid * page_bytes + off];
+            }
+        }
+    }
+    // the raw (8 + h)-bit field of subspace m from its two bytes
+    __device__ static unsigned code(const char *row, int m, int M, int h) {
+        const uint8_t *r = (const uint8_t *)row;
+        return (unsigned)r[m] | ((((unsigned)r[M + ((m * h) >> 3)] >> ((m * h) & 7)) & ((1u << h) - 1u)) << 8);
+    }
+};
+
+// Codes: CodeWords<uint8_t>, CodeWords<uint16_t> or PackedPlanes.  DM = d / M.
+template <typename Codes, int DM>
+__global__ __launch_bounds__(256) void gather_rows_body(GatherParams p) {
     constexpr int NM = 8 / DM;                       // subspaces of a 16-byte piece
     typedef struct { f16 v[DM]; } __attribute__((aligned(2 * DM))) Entry;
     typedef f16 h8 __attribute__((ext_vector_type(8)));
-    extern __shared__ __attribute__((aligned(16))) char lds_codes[];      // the tile's code words: 64 rows of pitch bytes
+    extern __shared__ __attribute__((aligned(16))) char lds_codes[];      // the tile's code bytes: 64 rows of pitch bytes
     const int tid = threadIdx.x;
     const int sidx = blockIdx.z;
     const GatherSide &s = p.side[sidx];
     const int b = blockIdx.y / p.nh_k, hk = blockIdx.y % p.nh_k;
-    const int M = p.M, C = p.C, d = p.d;
-    const int pitch = M * (int)sizeof(CodeT) + 4;
+    const int M = p.M, C = p.C, d = p.d, h = p.hb;
+    const int pitch = Codes::pitch(M, h);
     const Entry *tab = (const Entry *)s.cents;
-    const bool v_pages = s.paged && sidx == 1;       // transposed pages: token fastest
-    const long long bh = (long long)b * p.nh_k + hk;
-    const int *ids = s.paged ? s.page_ids + bh * p.n_pages_cap : nullptr;
-    const char *rm_base = (const char *)s.codes + b * s.sb + hk * s.sh;      // row-major
-    const int page = 1 << p.ps_shift;
     f16 *out = s.out + b * p.o_sb + hk * p.o_sh;
     const f16 *resid = s.resid ? s.resid + b * p.res_sb + hk * p.res_sh : nullptr;
     const int tpr = d / 8;                           // threads (16-byte pieces) per row
     const int j0 = blockIdx.x * kGatherRows;         // this workgroup's tile
     int n_code = p.n_t - j0;                         // coded rows of this tile
     n_code = n_code < 0 ? 0 : (n_code > kGatherRows ? kGatherRows : n_code);
-    // ---- phase 1: the tile's code words -> LDS [row][M] ----
-    for (int e = tid; e < kGatherRows * M; e += 256) {
-        const int row = v_pages ? e % kGatherRows : e / M;
-        const int m = v_pages ? e / kGatherRows : e % M;
-        if (row < n_code) {
-            const int t = p.t0 + j0 + row;           // < t1: the host checked t1 against the store's capacity
-            long long off;                           // in code words
-            if (s.paged) {
-                const long long pid = ids[t >> p.ps_shift];
-                const int tin = t & (page - 1);
-                off = v_pages ? (pid * M + m) * page + tin : (pid * page + tin) * M + m;
-            } else {
-                off = (long long)t * M + m;
-            }
-            const CodeT c = s.paged ? ((const CodeT *)s.codes)[off] : ((const CodeT *)rm_base)[off];
-            *(CodeT *)(lds_codes + row * pitch + m * (int)sizeof(CodeT)) = c;
-        }
-    }
+    // ---- phase 1: the tile's code bytes -> LDS [row][pitch] ----
+    Codes::load_tile(lds_codes, p, s, sidx, b, hk, p.t0 + j0, n_code);
     __syncthreads();
     // ---- phase 2: thread = (row, 16-byte piece) ----
     for (int it = tid; it < kGatherRows * tpr; it += 256) {
@@ -104,7 +159,7 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(GatherParams p) {
 #pragma unroll
             for (int i = 0; i < NM; ++i) {
                 const int m = ch * NM + i;
-                const unsigned c = *(const CodeT *)(lds_codes + row * pitch + m * (int)sizeof(CodeT));
+                const unsigned c = Codes::code(lds_codes + row * pitch, m, M, h);
                 en[i] = tab[(long long)m * C + (c < (unsigned)C ? c : 0u)];
             }
             h8 o;
@@ -119,92 +174,6 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(GatherParams p) {
             *(h8 *)(out + (long long)j * d + 8 * ch) = *(const h8 *)(resid + (long long)rr * d + 8 * ch);
         }
     }
-}
-
-// Packed pages (million_pq_gather_rows_packed; million_hip.h, "Packed code pages"): the same two phases.  Phase 1 copies the
-// tile's low-plane bytes and then its high-plane bytes to LDS, each plane in the order the store holds it (subspace / high byte
-// fastest for K pages, token fastest for the transposed V planes), one byte per thread: a wave's loads are consecutive bytes.
-// The LDS image is [token][M low bytes | M h / 8 high bytes], the row pitch an odd number of dwords.  Phase 2 assembles the raw
-// (8 + h)-bit field of a subspace from its two bytes and is gather_rows_kernel's from there: index c < C ? c : 0.  h is a
-// wave-uniform field, not a template parameter.  Only bytes of tokens t0 <= t < t1 are read.
-__host__ __device__ inline int gather_packed_pitch(int M, int h) {
-    const int dw = (M * (8 + h)) >> 5;      // a token's bytes are a multiple of 4 (M a multiple of 16)
-    return 4 * (dw | 1);
-}
-
-template <int DM>
-__global__ __launch_bounds__(256) void gather_rows_packed_kernel(GatherParams p) {
-    constexpr int NM = 8 / DM;
-    typedef struct { f16 v[DM]; } __attribute__((aligned(2 * DM))) Entry;
-    typedef f16 h8 __attribute__((ext_vector_type(8)));
-    extern __shared__ __attribute__((aligned(16))) char lds_codes[];
-    const int tid = threadIdx.x;
-    const int sidx = blockIdx.z;
-    const GatherSide &s = p.side[sidx];
-    const int b = blockIdx.y / p.nh_k, hk = blockIdx.y % p.nh_k;
-    const int M = p.M, C = p.C, d = p.d, h = p.hb;
-    const int HM = (M * h) >> 3;                     // high bytes of a token
-    const int pitch = gather_packed_pitch(M, h);
-    const Entry *tab = (const Entry *)s.cents;
-    const bool v_pages = sidx == 1;                  // transposed planes: token fastest
-    const long long bh = (long long)b * p.nh_k + hk;
-    const int *ids = s.page_ids + bh * p.n_pages_cap;
-    const int page = 1 << p.ps_shift;
-    const long long page_bytes = (long long)page * ((M * (8 + h)) >> 3);      // no power of two
-    const uint8_t *pool = (const uint8_t *)s.codes;
-    f16 *out = s.out + b * p.o_sb + hk * p.o_sh;
-    const f16 *resid = s.resid ? s.resid + b * p.res_sb + hk * p.res_sh : nullptr;
-    const int tpr = d / 8;
-    const int j0 = blockIdx.x * kGatherRows;
-    int n_code = p.n_t - j0;
-    n_code = n_code < 0 ? 0 : (n_code > kGatherRows ? kGatherRows : n_code);
-    // ---- phase 1: low plane, then high plane -> LDS [row][M | HM] ----
-    for (int e = tid; e < kGatherRows * (M + HM); e += 256) {
-        const bool hi = e >= kGatherRows * M;        // wave-uniform: 64 M is a multiple of 256
-        const int f = hi ? e - kGatherRows * M : e;
-        const int W = hi ? HM : M;                   // bytes of a token in this plane
-        const int row = v_pages ? f % kGatherRows : f / W;
-        const int m = v_pages ? f / kGatherRows : f % W;
-        if (row < n_code) {
-            const int t = p.t0 + j0 + row;           // < t1
-            const long long pid = ids[t >> p.ps_shift];
-            const int tin = t & (page - 1);
-            const int off = (hi ? page * M : 0) + (v_pages ? m * page + tin : tin * W + m);
-            lds_codes[row * pitch + (hi ? M : 0) + m] = (char)pool[pid * page_bytes + off];
-        }
-    }
-    __syncthreads();
-    // ---- phase 2: thread = (row, 16-byte piece) ----
-    const unsigned fmask = (1u << h) - 1u;
-    for (int it = tid; it < kGatherRows * tpr; it += 256) {
-        const int row = it / tpr, ch = it - row * tpr;
-        const int j = j0 + row;
-        if (row < n_code) {
-            const uint8_t *rowc = (const uint8_t *)lds_codes + row * pitch;
-            Entry en[NM];
-#pragma unroll
-            for (int i = 0; i < NM; ++i) {
-                const int m = ch * NM + i;
-                const unsigned c = (unsigned)rowc[m] | ((((unsigned)rowc[M + ((m * h) >> 3)] >> ((m * h) & 7)) & fmask) << 8);
-                en[i] = tab[(long long)m * C + (c < (unsigned)C ? c : 0u)];
-            }
-            h8 o;
-#pragma unroll
-            for (int i = 0; i < NM; ++i)
-#pragma unroll
-                for (int k = 0; k < DM; ++k) o[i * DM + k] = en[i].v[k];
-            *(h8 *)(out + (long long)j * d + 8 * ch) = o;
-        } else if (j - p.n_t < p.r) {
-            int rr = p.rstart + (j - p.n_t);
-            rr = rr >= p.rcap ? rr - p.rcap : rr;
-            *(h8 *)(out + (long long)j * d + 8 * ch) = *(const h8 *)(resid + (long long)rr * d + 8 * ch);
-        }
-    }
-}
-
-template <typename CodeT, int DM>
-void launch_gather_t(const GatherParams &p, dim3 grid, int lds, hipStream_t s) {
-    hipLaunchKernelGGL((gather_rows_kernel<CodeT, DM>), grid, dim3(256), lds, s, p);
 }
 
 }  // namespace
@@ -286,12 +255,16 @@ static int gather_rows_impl(bool packed, const million_gather_rows_desc *desc, c
     p.hb = packed ? packed_hi_bits(d.C) : 0;
     const long long n_tiles = (n_rows + kGatherRows - 1) / kGatherRows;      // < 2^26: n_rows fits an int
     const dim3 grid((unsigned)n_tiles, (unsigned)(d.bs * d.nh_k), 2);
-    const int lds = packed ? kGatherRows * gather_packed_pitch(d.M, p.hb) : kGatherRows * (d.M * d.code_bytes + 4);
     const hipStream_t s = (hipStream_t)stream;
+    // the one place an instance is picked: (code source, d / M) - 8 over code words, 2 over packed pages
     const bool ok = dispatch_dm(d.d / d.M, [&](auto w) {
-        if constexpr (w() == 2 || w() == 4) if (packed) { hipLaunchKernelGGL((gather_rows_packed_kernel<w()>), grid, dim3(256), lds, s, p); return; }
-        if (d.code_bytes == 1) launch_gather_t<uint8_t, w()>(p, grid, lds, s);
-        else launch_gather_t<uint16_t, w()>(p, grid, lds, s);
+        auto launch = [&](auto codes) {
+            typedef decltype(codes) Codes;
+            hipLaunchKernelGGL((gather_rows_body<Codes, w()>), grid, dim3(256), kGatherRows * Codes::pitch(d.M, p.hb), s, p);
+        };
+        if constexpr (w() == 2 || w() == 4) if (packed) return launch(PackedPlanes());
+        if (d.code_bytes == 1) launch(CodeWords<uint8_t>());
+        else launch(CodeWords<uint16_t>());
     });
     if (!ok) { set_error("gather_rows: d/M=%d unsupported (1, 2, 4, 8)", d.d / d.M); return MILLION_ERR_SHAPE; }
     const hipError_t e = hipGetLastError();

@@ -8,8 +8,9 @@ from __future__ import annotations
 
 import collections
 import ctypes
+import dataclasses
 import weakref
-from typing import Optional
+from typing import Callable, Container, Optional
 
 import torch
 
@@ -71,6 +72,21 @@ def prepare_cents(cents: torch.Tensor, cache: bool = True) -> torch.Tensor:
     return out
 
 
+def _encode_desc(X, cents, n, layout, token_start, x_row_start, x_row_mod, dev_lengths) -> L.EncodeDesc:
+    """What the descriptor of every encode call says, whatever the destination: the rows of X (bs, nh_k, n_rows, d) - n of them,
+    default all -, the codebook's geometry, the destination layout and token.  The destination's own fields are the caller's."""
+    bs, nhk, n_rows, d = X.shape
+    M, C, dm = cents.shape
+    desc = L.EncodeDesc()
+    desc.struct_size = ctypes.sizeof(L.EncodeDesc)
+    desc.bs, desc.nh_k, desc.n, desc.d, desc.M, desc.C = bs, nhk, n_rows if n is None else n, d, M, C
+    desc.x_stride_b, desc.x_stride_h, desc.x_stride_n = X.stride(0), X.stride(1), X.stride(2)
+    desc.x_row_start, desc.x_row_mod = x_row_start, x_row_mod
+    desc.dst_layout, desc.dst_token_start = layout, token_start
+    desc.dev_lengths = _ptr(dev_lengths)
+    return desc
+
+
 def pq_encode_into(X: torch.Tensor, cents: torch.Tensor, dst: torch.Tensor, *, layout: int = L.MILLION_CODES_ROWMAJOR,
                    token_start: int = 0, n: Optional[int] = None, page_ids: Optional[torch.Tensor] = None,
                    page_size: int = 0, x_row_start: int = 0, x_row_mod: int = 0,
@@ -87,19 +103,12 @@ def pq_encode_into(X: torch.Tensor, cents: torch.Tensor, dst: torch.Tensor, *, l
     if X.dim() != 4 or X.stride(3) != 1:
         raise RuntimeError("pq_encode: X must be (bs, nh_k, n, d) with a contiguous last dim")
     cents = cents.contiguous()
-    bs, nhk, n_rows, d = X.shape
     M, C, dm = cents.shape
-    n = n_rows if n is None else n
-    desc = L.EncodeDesc()
-    desc.struct_size = ctypes.sizeof(L.EncodeDesc)
-    desc.bs, desc.nh_k, desc.n, desc.d, desc.M, desc.C = bs, nhk, n, d, M, C
-    desc.x_stride_b, desc.x_stride_h, desc.x_stride_n = X.stride(0), X.stride(1), X.stride(2)
-    desc.x_row_start, desc.x_row_mod = x_row_start, x_row_mod
-    desc.dst_layout, desc.dst_token_start = layout, token_start
+    desc = _encode_desc(X, cents, n, layout, token_start, x_row_start, x_row_mod, dev_lengths)
     if layout == L.MILLION_CODES_ROWMAJOR:
         if dst.dim() != 4 or dst.stride(3) != 1 or dst.stride(2) != M or dst.shape[3] != M:
             raise RuntimeError("pq_encode: row-major dst must be (bs, nh_k, T_cap, M) with dense rows")
-        if dst.shape[2] < token_start + n:
+        if dst.shape[2] < token_start + desc.n:
             raise RuntimeError("pq_encode: dst too short")
         desc.dst_stride_b, desc.dst_stride_h = dst.stride(0) * dst.element_size(), dst.stride(1) * dst.element_size()
     else:
@@ -108,7 +117,6 @@ def pq_encode_into(X: torch.Tensor, cents: torch.Tensor, dst: torch.Tensor, *, l
         if not dst.is_contiguous():
             raise RuntimeError("pq_encode: page pool must be contiguous")
         desc.page_size, desc.n_pages_cap = page_size, page_ids.shape[2]
-    desc.dev_lengths = _ptr(dev_lengths)
     if prepared is None and use_prepared and C <= 256:
         prepared = prepare_cents(cents)            # cached per codebook tensor; callers that own one pass it in
     desc.cents_prepared = _ptr(prepared)
@@ -145,6 +153,159 @@ def code_dtype_for(C: int):
     if C <= 65536:
         return torch.uint16
     raise RuntimeError(f"codebooks of {C} centroids are not supported (<= 65536)")
+
+
+# ---- the code formats: what the attention and gather ops and the paged cache need to know of one, in one place ----
+WIDE_CENTROIDS = (512, 1024, 2048, 4096)
+
+
+def packed_hi_bits(C: int) -> int:
+    """High bits stored beside the low byte of a packed code: 2 for C in 512 / 1024, 4 for C in 2048 / 4096."""
+    if C not in WIDE_CENTROIDS:
+        raise RuntimeError(f"packed codes: C={C} (packed pages hold codes of {WIDE_CENTROIDS} centroids; C <= 256 is a uint8 already)")
+    return 2 if C <= 1024 else 4
+
+
+def packed_page_bytes(page_size: int, M: int, C: int) -> int:
+    """Bytes of one packed page: page_size * M * (8 + h) / 8, the low plane then the high plane."""
+    return page_size * M * (8 + packed_hi_bits(C)) // 8
+
+
+def _check_packed_pool(who, pool, page_size, M, C):
+    if pool.dtype != torch.uint8 or pool.dim() != 2 or pool.shape[1] != packed_page_bytes(page_size, M, C) or not pool.is_contiguous():
+        raise RuntimeError(f"{who}: a packed pool must be contiguous uint8 (n_pool, {packed_page_bytes(page_size, M, C)}) "
+                           f"for page_size={page_size}, M={M}, C={C}")
+
+
+def _check_word_store(who, name, codes, paged, page_size, bs, nh_k, M, C, bound):
+    """One side's store of code words: a page pool (n_pool, ., .), or row-major (bs, nh_k, T, M) codes that hold the
+    bound = (tokens, what the message calls them) the call reads."""
+    if paged:
+        if not codes.is_contiguous() or codes.dim() != 3:
+            raise RuntimeError(f"{who}: {name} page pool must be contiguous (n_pool, ., .)")
+        return
+    if codes.dim() != 4 or codes.shape[3] != M or codes.shape[:2] != (bs, nh_k):
+        raise RuntimeError(f"{who}: {name} must be (bs, nh_k, T, M)")
+    if codes.shape[2] and (codes.stride(3) != 1 or codes.stride(2) != M):
+        raise RuntimeError(f"{who}: {name} rows must be dense (stride M)")
+    if bound[0] > codes.shape[2]:
+        raise RuntimeError(f"{who}: {bound[1]} exceeds {name}")
+
+
+def _check_packed_store(who, name, codes, paged, page_size, bs, nh_k, M, C, bound):
+    """One side's pool of packed pages: there is no packed row-major form, and the page size is part of the format."""
+    if not paged:
+        raise RuntimeError(f"{who}: packed codes live in pages only - k_page_ids and v_page_ids are both needed")
+    if page_size not in (32, 64, 128):
+        raise RuntimeError(f"{who}: page_size={page_size} (32, 64 or 128)")
+    _check_packed_pool(who, codes, page_size, M, C)
+
+
+def _word_page_shapes(page_size, M, C):
+    return (page_size, M), (M, page_size)      # V pages transposed
+
+
+def _packed_page_shapes(page_size, M, C):
+    return ((packed_page_bytes(page_size, M, C),),) * 2
+
+
+@dataclasses.dataclass(frozen=True)
+class CodeFormat:
+    """One way PQ codes are held.  FMT_U8, FMT_U16 and FMT_PACKED are all there are; code_format() picks one."""
+    name: str
+    centroids: Container               # the codebook sizes C it goes with
+    dtype: torch.dtype                 # of its stores
+    # its stores hold one code per word of `dtype`: a row-major (bs, nh_k, T, M) form exists beside the page pools, pq_encode_into
+    # writes both and the dtype selects the format.  False: planes of code bytes, in pages only, written by an op of their own; where
+    # an op picks the format from its code tensors, its packed=True says this one
+    rowmajor: bool
+    code_bytes: int                    # the logical width of a code (million_gather_rows_desc.code_bytes)
+    # the attention entries take the prepared blob (prepare_cents), which has no shape: pq_decode_attn is told M and C (and serves
+    # row-major sides too: a page table per side).  False: the plain (M, C, d_m) codebook, one table for the two pools
+    prepared: bool
+    page_shapes: Callable              # (page_size, M, C) -> the shapes of a K page and of a V page in its pools
+    check_store: Callable              # (who, name, codes, paged, page_size, bs, nh_k, M, C, bound): one side's store
+    # the C entries (include/million_hip.h)
+    encode: str
+    decode_attn: str
+    decode_ws: str
+    chunk_attn: str                    # without lse, and
+    chunk_attn_lse: str                # with it: one entry with an lse argument that may be null, except for 8-bit codes
+    chunk_ws: str
+    gather: str
+    # the functions of this module a paged cache calls, looked up by name when called
+    op_encode: str
+    op_decode_attn: str
+    op_decode_ws: str
+    op_chunk_attn: str
+
+
+FMT_U8 = CodeFormat(
+    "uint8", range(1, 257), torch.uint8, rowmajor=True, code_bytes=1, prepared=True, page_shapes=_word_page_shapes,
+    check_store=_check_word_store,
+    encode="million_pq_encode", decode_attn="million_pq_decode_attn", decode_ws="million_attn_workspace_bytes",
+    chunk_attn="million_pq_chunk_attn", chunk_attn_lse="million_pq_chunk_attn_lse", chunk_ws="million_chunk_attn_workspace_bytes",
+    gather="million_pq_gather_rows", op_encode="pq_encode_into", op_decode_attn="pq_decode_attn", op_decode_ws="decode_workspace_bytes",
+    op_chunk_attn="pq_chunk_attn")
+FMT_U16 = CodeFormat(
+    "uint16", WIDE_CENTROIDS, torch.uint16, rowmajor=True, code_bytes=2, prepared=False, page_shapes=_word_page_shapes,
+    check_store=_check_word_store,
+    encode="million_pq_encode", decode_attn="million_pq_decode_attn_wide", decode_ws="million_attn_wide_workspace_bytes",
+    chunk_attn="million_pq_chunk_attn_wide", chunk_attn_lse="million_pq_chunk_attn_wide", chunk_ws="million_chunk_attn_wide_workspace_bytes",
+    gather="million_pq_gather_rows", op_encode="pq_encode_into", op_decode_attn="pq_decode_attn_wide",
+    op_decode_ws="decode_wide_workspace_bytes", op_chunk_attn="pq_chunk_attn_wide")
+FMT_PACKED = CodeFormat(
+    "packed", WIDE_CENTROIDS, torch.uint8, rowmajor=False, code_bytes=2, prepared=False, page_shapes=_packed_page_shapes,
+    check_store=_check_packed_store,
+    encode="million_pq_encode_packed", decode_attn="million_pq_decode_attn_packed", decode_ws="million_attn_wide_workspace_bytes",
+    chunk_attn="million_pq_chunk_attn_packed", chunk_attn_lse="million_pq_chunk_attn_packed", chunk_ws="million_chunk_attn_wide_workspace_bytes",
+    gather="million_pq_gather_rows_packed", op_encode="pq_encode_into_packed", op_decode_attn="pq_decode_attn_packed",
+    op_decode_ws="decode_wide_workspace_bytes", op_chunk_attn="pq_chunk_attn_packed")
+CODE_FORMATS = (FMT_U8, FMT_U16, FMT_PACKED)
+
+
+def code_format(who: str, dtype, C: Optional[int], packed: bool = False) -> CodeFormat:
+    """The format of what a caller hands in: the dtype of its code tensors, its codebook size C and its `packed` flag.  Packed pools
+    are uint8 and cannot select: the flag does, and without it a uint8 tensor means 8-bit codes.  C = None: the dtype and the flag
+    alone (a caller that leaves the check of C to the op it calls)."""
+    if packed:
+        fmt = FMT_PACKED
+        if C is not None:
+            packed_hi_bits(C)      # says what packed pages hold
+    elif dtype == torch.uint8:
+        fmt = FMT_U8
+    elif dtype == torch.uint16:
+        fmt = FMT_U16
+    else:
+        raise RuntimeError(f"{who}: codes must be uint8 or uint16, both sides alike")
+    if C is not None and C not in fmt.centroids:
+        raise RuntimeError(f"{who}: C={C} does not go with {dtype} codes (uint8: C <= 256; uint16: C in {WIDE_CENTROIDS})")
+    return fmt
+
+
+def _check_stores(who, fmt, k_codes, v_codes, k_page_ids, v_page_ids, page_size, M, C, bs=None, nh_k=None, bound=None):
+    """The code store of each side of a chunk-attention or gather call, by the format's check.  A side is a page pool when it has
+    ids, else row-major.  Pools-only formats need nothing of the batch, and their callers check them first: a wrong M, C or
+    page_size is then said by the pool it does not fit, as ever.  bs, nh_k, bound: _check_word_store's."""
+    for name, codes, ids in (("k_codes", k_codes, k_page_ids), ("v_codes", v_codes, v_page_ids)):
+        fmt.check_store(who, name, codes, ids is not None, page_size, bs, nh_k, M, C, bound)
+
+
+def _check_page_ids(who, k_page_ids, v_page_ids, page_size, bs, nh_k, ids64_ok):
+    """The page ids of a chunk-attention or gather call -> (n_pages_cap, the ids are int64).  ids64_ok: int64 ids are served too."""
+    id_types = "int32/int64" if ids64_ok else "int32"
+    n_pages_cap, ids64 = 0, False
+    for ids in (k_page_ids, v_page_ids):
+        if ids is None:
+            continue
+        if (ids.dtype != torch.int32 and not (ids64_ok and ids.dtype == torch.int64)) or not ids.is_contiguous() or ids.dim() != 3 or ids.shape[:2] != (bs, nh_k):
+            raise RuntimeError(f"{who}: page ids must be contiguous {id_types} (bs, nh_k, n_pages)")
+        if n_pages_cap and (ids.shape[2] != n_pages_cap or (ids.dtype == torch.int64) != ids64):
+            raise RuntimeError(f"{who}: K and V page ids must agree in {'dtype and ' if ids64_ok else ''}length")
+        n_pages_cap, ids64 = ids.shape[2], ids.dtype == torch.int64
+    if (k_page_ids is not None or v_page_ids is not None) and page_size is None:
+        raise RuntimeError(f"{who}: paged codes need page_size")
+    return n_pages_cap, ids64
 
 
 def pq_encode(X: torch.Tensor, cents: torch.Tensor) -> torch.Tensor:
@@ -573,9 +734,6 @@ def pq_decode_attn(q: torch.Tensor, k_codes: torch.Tensor, v_codes: torch.Tensor
     return out
 
 
-WIDE_CENTROIDS = (512, 1024, 2048, 4096)
-
-
 def wide_attn_desc(who, q, k_pool, v_pool, k_cents, v_cents, k_res, v_res, r, n_tokens, page_ids, page_size, resid_start,
                dev_lengths, packed=False) -> L.AttnDesc:
     """Every check of a wide decode call that needs no library, and its descriptor.  packed: the pools hold packed pages
@@ -645,16 +803,16 @@ def pq_decode_attn_wide(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Ten
 
     K pool (n_pool, page_size, M) u16, V pool (n_pool, M, page_size) u16, one page-id table (bs, nh_k, n_pages_cap) int32/int64
     for both sides; k_cents / v_cents are the plain (M, C, d_m) fp16 codebooks (there is no prepared image)."""
-    return _decode_attn_wide_call("pq_decode_attn_wide", False, q, k_pool, v_pool, k_cents, v_cents, k_res, v_res, r, n_tokens, page_ids,
+    return _decode_attn_wide_call("pq_decode_attn_wide", FMT_U16, q, k_pool, v_pool, k_cents, v_cents, k_res, v_res, r, n_tokens, page_ids,
                                   page_size, resid_start, out, dev_lengths, workspace, k_new, v_new, return_lse, lse)
 
 
-def _decode_attn_wide_call(who, packed, q, k_pool, v_pool, k_cents, v_cents, k_res, v_res, r, n_tokens, page_ids, page_size, resid_start,
+def _decode_attn_wide_call(who, fmt, q, k_pool, v_pool, k_cents, v_cents, k_res, v_res, r, n_tokens, page_ids, page_size, resid_start,
                            out, dev_lengths, workspace, k_new, v_new, return_lse, lse):
-    """pq_decode_attn_wide (uint16 pools) and pq_decode_attn_packed (packed pools): one set of checks, one workspace, two entries."""
+    """pq_decode_attn_wide (FMT_U16) and pq_decode_attn_packed (FMT_PACKED): one set of checks, one workspace, the format's entry."""
     _need_cuda(out, lse, k_new, v_new, workspace)
     desc = wide_attn_desc(who, q, k_pool, v_pool, k_cents, v_cents, k_res, v_res, r, n_tokens, page_ids, page_size,
-                      resid_start, dev_lengths, packed)
+                      resid_start, dev_lengths, fmt is FMT_PACKED)
     if out is None:
         out = torch.empty_like(q)
     elif out.dtype != torch.float16 or out.numel() != q.numel() or not out.is_contiguous():
@@ -673,38 +831,19 @@ def _decode_attn_wide_call(who, packed, q, k_pool, v_pool, k_cents, v_cents, k_r
             raise RuntimeError(f"{who}: lse must be contiguous fp32 (bs, nh, 1)")
     lib = L.load()
     if workspace is None:
-        need = int(lib.million_attn_wide_workspace_bytes(ctypes.byref(desc)))
+        need = int(getattr(lib, fmt.decode_ws)(ctypes.byref(desc)))
         key = (q.device.index, torch.cuda.current_stream().cuda_stream, "wide")
         workspace = _ws_cache.get(key)
         if workspace is None or workspace.numel() < need:      # zeroed once; every call leaves it ready (need = 0: the call is refused below)
             workspace = _ws_cache[key] = torch.zeros(max(need, 256), dtype=torch.uint8, device=q.device)
-    entry = "million_pq_decode_attn_packed" if packed else "million_pq_decode_attn_wide"
-    L.check(getattr(lib, entry)(ctypes.byref(desc), q.data_ptr(), _ptr(k_new), _ptr(v_new), k_pool.data_ptr(),
-                                v_pool.data_ptr(), page_ids.data_ptr(), page_ids.data_ptr(), k_cents.data_ptr(),
-                                v_cents.data_ptr(), k_res.data_ptr(), v_res.data_ptr(), out.data_ptr(), _ptr(lse),
-                                workspace.data_ptr(), workspace.numel(), _stream()), entry)
+    L.check(getattr(lib, fmt.decode_attn)(ctypes.byref(desc), q.data_ptr(), _ptr(k_new), _ptr(v_new), k_pool.data_ptr(),
+                                          v_pool.data_ptr(), page_ids.data_ptr(), page_ids.data_ptr(), k_cents.data_ptr(),
+                                          v_cents.data_ptr(), k_res.data_ptr(), v_res.data_ptr(), out.data_ptr(), _ptr(lse),
+                                          workspace.data_ptr(), workspace.numel(), _stream()), fmt.decode_attn)
     return (out, lse) if want_lse else out
 
 
 # ---- packed code pages (include/million_hip.h, "Packed code pages") ----
-def packed_hi_bits(C: int) -> int:
-    """High bits stored beside the low byte of a packed code: 2 for C in 512 / 1024, 4 for C in 2048 / 4096."""
-    if C not in WIDE_CENTROIDS:
-        raise RuntimeError(f"packed codes: C={C} (packed pages hold codes of {WIDE_CENTROIDS} centroids; C <= 256 is a uint8 already)")
-    return 2 if C <= 1024 else 4
-
-
-def packed_page_bytes(page_size: int, M: int, C: int) -> int:
-    """Bytes of one packed page: page_size * M * (8 + h) / 8, the low plane then the high plane."""
-    return page_size * M * (8 + packed_hi_bits(C)) // 8
-
-
-def _check_packed_pool(who, pool, page_size, M, C):
-    if pool.dtype != torch.uint8 or pool.dim() != 2 or pool.shape[1] != packed_page_bytes(page_size, M, C) or not pool.is_contiguous():
-        raise RuntimeError(f"{who}: a packed pool must be contiguous uint8 (n_pool, {packed_page_bytes(page_size, M, C)}) "
-                           f"for page_size={page_size}, M={M}, C={C}")
-
-
 def pq_encode_into_packed(X: torch.Tensor, cents: torch.Tensor, dst: torch.Tensor, *, layout: int, token_start: int = 0,
                           n: Optional[int] = None, page_ids: torch.Tensor = None, page_size: int = 0, x_row_start: int = 0,
                           x_row_mod: int = 0, dev_lengths: Optional[torch.Tensor] = None) -> None:
@@ -719,20 +858,12 @@ def pq_encode_into_packed(X: torch.Tensor, cents: torch.Tensor, dst: torch.Tenso
     if layout not in (L.MILLION_CODES_KPAGES, L.MILLION_CODES_VPAGES):
         raise RuntimeError(f"{who}: layout must be MILLION_CODES_KPAGES or MILLION_CODES_VPAGES (there are no packed row-major codes)")
     cents = cents.contiguous()
-    bs, nhk, n_rows, d = X.shape
     M, C, dm = cents.shape
     _check_packed_pool(who, dst, page_size, M, C)
     if page_ids is None or page_ids.dtype != torch.int32 or not page_ids.is_contiguous() or page_ids.dim() != 3:
         raise RuntimeError(f"{who}: contiguous int32 page_ids (bs, nh_k, n_pages_cap) needed")
-    n = n_rows if n is None else n
-    desc = L.EncodeDesc()
-    desc.struct_size = ctypes.sizeof(L.EncodeDesc)
-    desc.bs, desc.nh_k, desc.n, desc.d, desc.M, desc.C = bs, nhk, n, d, M, C
-    desc.x_stride_b, desc.x_stride_h, desc.x_stride_n = X.stride(0), X.stride(1), X.stride(2)
-    desc.x_row_start, desc.x_row_mod = x_row_start, x_row_mod
-    desc.dst_layout, desc.dst_token_start = layout, token_start
+    desc = _encode_desc(X, cents, n, layout, token_start, x_row_start, x_row_mod, dev_lengths)
     desc.page_size, desc.n_pages_cap = page_size, page_ids.shape[2]
-    desc.dev_lengths = _ptr(dev_lengths)
     L.check(L.load().million_pq_encode_packed(ctypes.byref(desc), X.data_ptr(), cents.data_ptr(), dst.data_ptr(), page_ids.data_ptr(),
                                               _stream()), "million_pq_encode_packed")
 
@@ -745,7 +876,7 @@ def pq_decode_attn_packed(q: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.T
                           return_lse: bool = False, lse: Optional[torch.Tensor] = None):
     """pq_decode_attn_wide over packed pools (million_pq_decode_attn_packed): K and V pool uint8 (n_pool, packed_page_bytes),
     everything else - arguments, checks, workspace (decode_wide_workspace_bytes), results bit for bit - as pq_decode_attn_wide."""
-    return _decode_attn_wide_call("pq_decode_attn_packed", True, q, k_pool, v_pool, k_cents, v_cents, k_res, v_res, r, n_tokens, page_ids,
+    return _decode_attn_wide_call("pq_decode_attn_packed", FMT_PACKED, q, k_pool, v_pool, k_cents, v_cents, k_res, v_res, r, n_tokens, page_ids,
                                   page_size, resid_start, out, dev_lengths, workspace, k_new, v_new, return_lse, lse)
 
 
@@ -1071,32 +1202,25 @@ def chunk_attn_wide_workspace_bytes(desc: L.ChunkAttnDesc) -> int:
     return int(L.load().million_chunk_attn_wide_workspace_bytes(ctypes.byref(desc)))
 
 
-def _chunk_attn_call(who, wide, q, k_chunk, v_chunk, k_codes, v_codes, k_prep, v_prep, k_res, v_res, r, M, C, n_tokens, resid_start,
-                     k_page_ids, v_page_ids, page_size, out, workspace, dev_lengths, dev_n_q, return_lse, lse, packed=False):
-    """pq_chunk_attn (wide = False: uint8 codes, prepared codebooks), pq_chunk_attn_wide (uint16 codes, the plain codebooks in
-    k_prep / v_prep) and pq_chunk_attn_packed (wide and packed: pools of packed pages): one set of checks, one descriptor, the
-    entry point of the format."""
+def _chunk_attn_call(who, fmt, q, k_chunk, v_chunk, k_codes, v_codes, k_prep, v_prep, k_res, v_res, r, M, C, n_tokens, resid_start,
+                     k_page_ids, v_page_ids, page_size, out, workspace, dev_lengths, dev_n_q, return_lse, lse):
+    """pq_chunk_attn (FMT_U8: prepared codebooks), pq_chunk_attn_wide (FMT_U16: the plain codebooks in k_prep / v_prep) and
+    pq_chunk_attn_packed (FMT_PACKED: pools of packed pages, plain codebooks): one set of checks, one descriptor, the entry
+    point of the format."""
     _need_cuda(q, k_chunk, v_chunk, k_codes, v_codes, k_prep, v_prep, k_res, v_res, k_page_ids, v_page_ids, out, workspace,
                dev_lengths, dev_n_q, lse)
     if q.dtype != torch.float16 or k_res.dtype != torch.float16 or v_res.dtype != torch.float16:
         raise RuntimeError(f"{who}: q and window buffers must be fp16")
-    if wide:
-        if packed:
-            if k_page_ids is None or v_page_ids is None:
-                raise RuntimeError(f"{who}: packed codes live in pages only - k_page_ids and v_page_ids are both needed")
-            if page_size not in (32, 64, 128):
-                raise RuntimeError(f"{who}: page_size={page_size} (32, 64 or 128)")
-            _check_packed_pool(who, k_codes, page_size, M, C)
-            _check_packed_pool(who, v_codes, page_size, M, C)
-        elif k_codes.dtype != torch.uint16 or v_codes.dtype != torch.uint16:
-            raise RuntimeError(f"{who}: codes must be uint16 (uint8 codes: pq_chunk_attn)")
+    if not fmt.rowmajor:
+        _check_stores(who, fmt, k_codes, v_codes, k_page_ids, v_page_ids, page_size, M, C)
+    elif k_codes.dtype != fmt.dtype or v_codes.dtype != fmt.dtype:
+        raise RuntimeError(f"{who}: codes must be {fmt.name}" + ("" if fmt.prepared else " (uint8 codes: pq_chunk_attn)"))
+    if not fmt.prepared:
         for t in (k_prep, v_prep):
             if t.dtype != torch.float16 or t.dim() != 3 or not t.is_contiguous():
                 raise RuntimeError(f"{who}: k_cents / v_cents must be the plain contiguous fp16 (M, C, d_m) codebooks")
-        if C not in WIDE_CENTROIDS:
-            raise RuntimeError(f"{who}: C={C} (one of {WIDE_CENTROIDS})")
-    elif k_codes.dtype != torch.uint8 or v_codes.dtype != torch.uint8:
-        raise RuntimeError(f"{who}: codes must be uint8")
+        if C not in fmt.centroids:
+            raise RuntimeError(f"{who}: C={C} (one of {fmt.centroids})")
     if q.dim() != 4:
         raise RuntimeError(f"{who}: q must be (bs, nh, n_q, d)")
     bs, nh, n_q, d = q.shape
@@ -1104,7 +1228,7 @@ def _chunk_attn_call(who, wide, q, k_chunk, v_chunk, k_codes, v_codes, k_prep, v
             or k_res.stride(2) != d or k_res.shape[0] != bs or k_res.shape[3] != d):
         raise RuntimeError(f"{who}: window buffers must be (bs, nh_k, cap, d), share shape / strides, dense rows")
     nh_k = k_res.shape[1]
-    if wide and (M <= 0 or d % M or tuple(k_prep.shape) != (M, C, d // M) or v_prep.shape != k_prep.shape):
+    if not fmt.prepared and (M <= 0 or d % M or tuple(k_prep.shape) != (M, C, d // M) or v_prep.shape != k_prep.shape):
         raise RuntimeError(f"{who}: codebooks {tuple(k_prep.shape)} {tuple(v_prep.shape)} are not (M, C, d / M) for M={M} C={C} d={d}")
     fix = lambda t: t if (t.stride(3) == 1 and all(s_ % 8 == 0 for s_ in t.stride()[:3])) else t.contiguous()
     q = fix(q)
@@ -1119,31 +1243,9 @@ def _chunk_attn_call(who, wide, q, k_chunk, v_chunk, k_codes, v_codes, k_prep, v
                                f"{tuple(k_chunk.shape)} {tuple(v_chunk.shape)}")
         k_chunk, v_chunk = fix(k_chunk), fix(v_chunk)
         n_c = n_q
-    k_paged, v_paged = k_page_ids is not None, v_page_ids is not None
-    n_pages_cap, ids64 = 0, False
-    for ids in (k_page_ids, v_page_ids):
-        if ids is None:
-            continue
-        if ids.dtype not in (torch.int32, torch.int64) or not ids.is_contiguous() or ids.dim() != 3 or ids.shape[:2] != (bs, nh_k):
-            raise RuntimeError(f"{who}: page ids must be contiguous int32/int64 (bs, nh_k, n_pages)")
-        if n_pages_cap and (ids.shape[2] != n_pages_cap or (ids.dtype == torch.int64) != ids64):
-            raise RuntimeError(f"{who}: K and V page ids must agree in dtype and length")
-        n_pages_cap, ids64 = ids.shape[2], ids.dtype == torch.int64
-    if (k_paged or v_paged) and page_size is None:
-        raise RuntimeError(f"{who}: paged codes need page_size")
-    for name, codes, paged in (("k_codes", k_codes, k_paged), ("v_codes", v_codes, v_paged)):
-        if packed:
-            continue      # _check_packed_pool above
-        if paged:
-            if not codes.is_contiguous() or codes.dim() != 3:
-                raise RuntimeError(f"{who}: {name} page pool must be contiguous (n_pool, ., .)")
-        else:
-            if codes.dim() != 4 or codes.shape[3] != M or codes.shape[:2] != (bs, nh_k):
-                raise RuntimeError(f"{who}: {name} must be (bs, nh_k, T, M)")
-            if codes.shape[2] and (codes.stride(3) != 1 or codes.stride(2) != M):
-                raise RuntimeError(f"{who}: {name} rows must be dense (stride M)")
-            if n_tokens > codes.shape[2]:
-                raise RuntimeError(f"{who}: n_tokens exceeds {name}")
+    n_pages_cap, ids64 = _check_page_ids(who, k_page_ids, v_page_ids, page_size, bs, nh_k, ids64_ok=True)
+    if fmt.rowmajor:
+        _check_stores(who, fmt, k_codes, v_codes, k_page_ids, v_page_ids, page_size, M, C, bs, nh_k, (n_tokens, "n_tokens"))
     if dev_lengths is None and not 0 <= r <= k_res.shape[2]:
         raise RuntimeError(f"{who}: r={r} outside [0, {k_res.shape[2]}]")
     for name, t, shape in (("dev_lengths", dev_lengths, (bs, 4)), ("dev_n_q", dev_n_q, (bs,))):
@@ -1154,37 +1256,27 @@ def _chunk_attn_call(who, wide, q, k_chunk, v_chunk, k_codes, v_codes, k_prep, v
     elif out.shape != (bs, nh, n_q, d) or out.dtype != torch.float16 or out.stride(3) != 1:
         raise RuntimeError(f"{who}: out must be fp16 (bs, nh, n_q, d) with contiguous rows")
     desc = chunk_attn_desc(q, k_res, nh_k=nh_k, M=M, C=C, n_tokens=int(n_tokens), r=0 if dev_lengths is not None else int(r),
-                           n_c=n_c, resid_start=int(resid_start), k_paged=k_paged, v_paged=v_paged, page_size=int(page_size or 0),
-                           n_pages_cap=n_pages_cap, page_ids_i64=ids64, k_codes=k_codes, v_codes=v_codes, k_chunk=k_chunk,
-                           v_chunk=v_chunk, out=out, dev_lengths=dev_lengths, dev_n_q=dev_n_q)
+                           n_c=n_c, resid_start=int(resid_start), k_paged=k_page_ids is not None, v_paged=v_page_ids is not None,
+                           page_size=int(page_size or 0), n_pages_cap=n_pages_cap, page_ids_i64=ids64, k_codes=k_codes, v_codes=v_codes,
+                           k_chunk=k_chunk, v_chunk=v_chunk, out=out, dev_lengths=dev_lengths, dev_n_q=dev_n_q)
     lib = L.load()
-    wide_name = "million_pq_chunk_attn_packed" if packed else "million_pq_chunk_attn_wide"
-    wide_entry = getattr(lib, wide_name) if wide else None
-    need = (lib.million_chunk_attn_wide_workspace_bytes if wide else lib.million_chunk_attn_workspace_bytes)(ctypes.byref(desc))
+    need = getattr(lib, fmt.chunk_ws)(ctypes.byref(desc))
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=q.device) if need else None
-    if return_lse or lse is not None:
+    want_lse = return_lse or lse is not None
+    if want_lse:
         if lse is None:
             lse = torch.empty(bs, nh, n_q, dtype=torch.float32, device=q.device)
         elif lse.dtype != torch.float32 or tuple(lse.shape) != (bs, nh, n_q) or not lse.is_contiguous():
             raise RuntimeError(f"{who}: lse must be contiguous fp32 (bs, nh, n_q)")
-        L.check((wide_entry if wide else lib.million_pq_chunk_attn_lse)(ctypes.byref(desc), q.data_ptr(), _ptr(k_chunk), _ptr(v_chunk), k_codes.data_ptr(),
-                                              v_codes.data_ptr(), _ptr(k_page_ids), _ptr(v_page_ids), k_prep.data_ptr(),
-                                              v_prep.data_ptr(), k_res.data_ptr(), v_res.data_ptr(), out.data_ptr(), lse.data_ptr(),
-                                              _ptr(workspace), 0 if workspace is None else workspace.numel(), _stream()),
-                wide_name if wide else "million_pq_chunk_attn_lse")
-        return out, lse
-    if wide:
-        L.check(wide_entry(ctypes.byref(desc), q.data_ptr(), _ptr(k_chunk), _ptr(v_chunk), k_codes.data_ptr(),
-                           v_codes.data_ptr(), _ptr(k_page_ids), _ptr(v_page_ids), k_prep.data_ptr(),
-                           v_prep.data_ptr(), k_res.data_ptr(), v_res.data_ptr(), out.data_ptr(), None,
-                           _ptr(workspace), 0 if workspace is None else workspace.numel(), _stream()), wide_name)
-        return out
-    L.check(lib.million_pq_chunk_attn(ctypes.byref(desc), q.data_ptr(), _ptr(k_chunk), _ptr(v_chunk), k_codes.data_ptr(),
-                                      v_codes.data_ptr(), _ptr(k_page_ids), _ptr(v_page_ids), k_prep.data_ptr(), v_prep.data_ptr(),
-                                      k_res.data_ptr(), v_res.data_ptr(), out.data_ptr(), _ptr(workspace),
-                                      0 if workspace is None else workspace.numel(), _stream()), "million_pq_chunk_attn")
-    return out
+    # one entry with an lse argument (None: no lse) - except that 8-bit codes have an entry without the argument, too
+    entry = fmt.chunk_attn_lse if want_lse else fmt.chunk_attn
+    lse_arg = (lse.data_ptr() if want_lse else None,) if entry == fmt.chunk_attn_lse else ()
+    L.check(getattr(lib, entry)(ctypes.byref(desc), q.data_ptr(), _ptr(k_chunk), _ptr(v_chunk), k_codes.data_ptr(), v_codes.data_ptr(),
+                                _ptr(k_page_ids), _ptr(v_page_ids), k_prep.data_ptr(), v_prep.data_ptr(), k_res.data_ptr(),
+                                v_res.data_ptr(), out.data_ptr(), *lse_arg, _ptr(workspace),
+                                0 if workspace is None else workspace.numel(), _stream()), entry)
+    return (out, lse) if want_lse else out
 
 
 def pq_chunk_attn(q: torch.Tensor, k_chunk: Optional[torch.Tensor], v_chunk: Optional[torch.Tensor], k_codes: torch.Tensor,
@@ -1208,7 +1300,7 @@ def pq_chunk_attn(q: torch.Tensor, k_chunk: Optional[torch.Tensor], v_chunk: Opt
     return_lse=True (or an lse= buffer): returns (out, lse), lse fp32 (bs, nh, n_q) contiguous - the natural-log sum of exp of
     every row's scaled scores over the keys it sees (million_pq_chunk_attn_lse); -inf for a row that sees none and for the rows
     past a request's dev_n_q."""
-    return _chunk_attn_call("pq_chunk_attn", False, q, k_chunk, v_chunk, k_codes, v_codes, k_prep, v_prep, k_res, v_res, r, M, C, n_tokens, resid_start,
+    return _chunk_attn_call("pq_chunk_attn", FMT_U8, q, k_chunk, v_chunk, k_codes, v_codes, k_prep, v_prep, k_res, v_res, r, M, C, n_tokens, resid_start,
                             k_page_ids, v_page_ids, page_size, out, workspace, dev_lengths, dev_n_q, return_lse, lse)
 
 
@@ -1224,7 +1316,7 @@ def pq_chunk_attn_wide(q: torch.Tensor, k_chunk: Optional[torch.Tensor], v_chunk
     is no prepared image.  Every gathered index is code & (C - 1), so code words past n_tokens, page tails and pages no live
     entry names may hold anything.  With out=, workspace= (chunk_attn_wide_workspace_bytes) and, when asked for, lse= the call
     allocates nothing and can be captured into a graph."""
-    return _chunk_attn_call("pq_chunk_attn_wide", True, q, k_chunk, v_chunk, k_codes, v_codes, k_cents, v_cents, k_res, v_res, r, M, C, n_tokens, resid_start,
+    return _chunk_attn_call("pq_chunk_attn_wide", FMT_U16, q, k_chunk, v_chunk, k_codes, v_codes, k_cents, v_cents, k_res, v_res, r, M, C, n_tokens, resid_start,
                             k_page_ids, v_page_ids, page_size, out, workspace, dev_lengths, dev_n_q, return_lse, lse)
 
 
@@ -1238,8 +1330,8 @@ def pq_chunk_attn_packed(q: torch.Tensor, k_chunk: Optional[torch.Tensor], v_chu
     (n_pool, packed_page_bytes(page_size, M, C)), both page-id tensors required (there is no packed row-major format), page_size
     32 / 64 / 128.  Everything else - arguments, checks, ragged fields, lse, workspace (chunk_attn_wide_workspace_bytes) - as
     pq_chunk_attn_wide, and the result is that call's over uint16 pools holding the same codes, bit for bit."""
-    return _chunk_attn_call("pq_chunk_attn_packed", True, q, k_chunk, v_chunk, k_codes, v_codes, k_cents, v_cents, k_res, v_res, r, M, C, n_tokens, resid_start,
-                            k_page_ids, v_page_ids, page_size, out, workspace, dev_lengths, dev_n_q, return_lse, lse, packed=True)
+    return _chunk_attn_call("pq_chunk_attn_packed", FMT_PACKED, q, k_chunk, v_chunk, k_codes, v_codes, k_cents, v_cents, k_res, v_res, r, M, C, n_tokens, resid_start,
+                            k_page_ids, v_page_ids, page_size, out, workspace, dev_lengths, dev_n_q, return_lse, lse)
 
 
 def attn_merge(outs, lses, out: Optional[torch.Tensor] = None, lse_out: Optional[torch.Tensor] = None, return_lse: bool = False):
@@ -1305,20 +1397,13 @@ def pq_gather_rows(k_codes: torch.Tensor, v_codes: torch.Tensor, k_cents: torch.
             raise RuntimeError(f"{who}: k_cents / v_cents must be the plain contiguous fp16 (M, C, d_m) codebooks, alike")
     M, C, dm = k_cents.shape
     d = M * dm
-    if packed:
-        if k_page_ids is None or v_page_ids is None:
-            raise RuntimeError(f"{who}: packed codes live in pages only - k_page_ids and v_page_ids are both needed")
-        if page_size not in (32, 64, 128):
-            raise RuntimeError(f"{who}: page_size={page_size} (32, 64 or 128)")
-        _check_packed_pool(who, k_codes, page_size, M, C)
-        _check_packed_pool(who, v_codes, page_size, M, C)
+    if not packed and k_codes.dtype != v_codes.dtype:
+        raise RuntimeError(f"{who}: codes must be uint8 or uint16, both sides alike")
+    fmt = code_format(who, k_codes.dtype, None if packed else C, packed)      # (packed: the pool check says a C it does not hold)
+    if not fmt.rowmajor:      # the gather over packed pages is built for d / M 2 and 4
+        _check_stores(who, fmt, k_codes, v_codes, k_page_ids, v_page_ids, page_size, M, C)
         if dm not in (2, 4):
             raise RuntimeError(f"{who}: d / M = {dm} over packed pages (2 or 4)")
-    elif k_codes.dtype != v_codes.dtype or k_codes.dtype not in (torch.uint8, torch.uint16):
-        raise RuntimeError(f"{who}: codes must be uint8 or uint16, both sides alike")
-    code_bytes = 2 if packed else k_codes.element_size()
-    if (code_bytes == 1 and C > 256) or (code_bytes == 2 and C not in WIDE_CENTROIDS):
-        raise RuntimeError(f"{who}: C={C} does not go with {k_codes.dtype} codes (uint8: C <= 256; uint16: C in {WIDE_CENTROIDS})")
     for t in (k_out, v_out):
         if (t.dtype != torch.float16 or t.dim() != 4 or t.shape[3] != d or t.stride(3) != 1 or t.stride(2) != d
                 or t.shape != k_out.shape or t.stride() != k_out.stride()):
@@ -1333,34 +1418,13 @@ def pq_gather_rows(k_codes: torch.Tensor, v_codes: torch.Tensor, k_cents: torch.
         resid_cap = k_res.shape[2]
     if not 0 <= r <= resid_cap:
         raise RuntimeError(f"{who}: r={r} outside [0, {resid_cap}]")
+    n_pages_cap, _ = _check_page_ids(who, k_page_ids, v_page_ids, page_size, bs, nh_k, ids64_ok=False)
+    if fmt.rowmajor:
+        _check_stores(who, fmt, k_codes, v_codes, k_page_ids, v_page_ids, page_size, M, C, bs, nh_k, (t1, f"t1={t1}"))
     k_paged, v_paged = k_page_ids is not None, v_page_ids is not None
-    n_pages_cap = 0
-    for ids in (k_page_ids, v_page_ids):
-        if ids is None:
-            continue
-        if ids.dtype != torch.int32 or not ids.is_contiguous() or ids.dim() != 3 or ids.shape[:2] != (bs, nh_k):
-            raise RuntimeError(f"{who}: page ids must be contiguous int32 (bs, nh_k, n_pages)")
-        if n_pages_cap and ids.shape[2] != n_pages_cap:
-            raise RuntimeError(f"{who}: K and V page ids must agree in length")
-        n_pages_cap = ids.shape[2]
-    if (k_paged or v_paged) and page_size is None:
-        raise RuntimeError(f"{who}: paged codes need page_size")
-    for name, codes, paged in (("k_codes", k_codes, k_paged), ("v_codes", v_codes, v_paged)):
-        if packed:
-            continue      # _check_packed_pool above
-        if paged:
-            if not codes.is_contiguous() or codes.dim() != 3:
-                raise RuntimeError(f"{who}: {name} page pool must be contiguous (n_pool, ., .)")
-        else:
-            if codes.dim() != 4 or codes.shape[3] != M or codes.shape[:2] != (bs, nh_k):
-                raise RuntimeError(f"{who}: {name} must be (bs, nh_k, T, M)")
-            if codes.shape[2] and (codes.stride(3) != 1 or codes.stride(2) != M):
-                raise RuntimeError(f"{who}: {name} rows must be dense (stride M)")
-            if t1 > codes.shape[2]:
-                raise RuntimeError(f"{who}: t1={t1} exceeds {name}")
     desc = L.GatherRowsDesc()
     desc.struct_size = ctypes.sizeof(L.GatherRowsDesc)
-    desc.bs, desc.nh_k, desc.d, desc.M, desc.C, desc.code_bytes = bs, nh_k, d, M, C, code_bytes
+    desc.bs, desc.nh_k, desc.d, desc.M, desc.C, desc.code_bytes = bs, nh_k, d, M, C, fmt.code_bytes
     desc.t0, desc.t1, desc.r, desc.resid_start, desc.resid_cap = int(t0), int(t1), int(r), int(resid_start), resid_cap
     if resid_cap:
         desc.resid_stride_b, desc.resid_stride_h = k_res.stride(0), k_res.stride(1)
@@ -1368,18 +1432,13 @@ def pq_gather_rows(k_codes: torch.Tensor, v_codes: torch.Tensor, k_cents: torch.
     desc.v_layout = L.MILLION_KV_PAGED if v_paged else L.MILLION_KV_ROWMAJOR
     desc.page_size, desc.n_pages_cap = int(page_size or 0), n_pages_cap
     if not k_paged:
-        desc.k_stride_b, desc.k_stride_h = (k_codes.stride(i) * code_bytes for i in (0, 1))      # bytes
+        desc.k_stride_b, desc.k_stride_h = (k_codes.stride(i) * fmt.code_bytes for i in (0, 1))      # bytes
     if not v_paged:
-        desc.v_stride_b, desc.v_stride_h = (v_codes.stride(i) * code_bytes for i in (0, 1))
+        desc.v_stride_b, desc.v_stride_h = (v_codes.stride(i) * fmt.code_bytes for i in (0, 1))
     desc.rows_cap, desc.o_stride_b, desc.o_stride_h = rows_cap, k_out.stride(0), k_out.stride(1)
-    if packed:
-        L.check(L.load().million_pq_gather_rows_packed(ctypes.byref(desc), k_codes.data_ptr(), v_codes.data_ptr(), _ptr(k_page_ids),
-                                                       _ptr(v_page_ids), k_cents.data_ptr(), v_cents.data_ptr(), _ptr(k_res), _ptr(v_res),
-                                                       k_out.data_ptr(), v_out.data_ptr(), _stream()), "million_pq_gather_rows_packed")
-        return int(t1) - int(t0) + int(r)
-    L.check(L.load().million_pq_gather_rows(ctypes.byref(desc), k_codes.data_ptr(), v_codes.data_ptr(), _ptr(k_page_ids), _ptr(v_page_ids),
-                                            k_cents.data_ptr(), v_cents.data_ptr(), _ptr(k_res), _ptr(v_res), k_out.data_ptr(),
-                                            v_out.data_ptr(), _stream()), "million_pq_gather_rows")
+    L.check(getattr(L.load(), fmt.gather)(ctypes.byref(desc), k_codes.data_ptr(), v_codes.data_ptr(), _ptr(k_page_ids), _ptr(v_page_ids),
+                                          k_cents.data_ptr(), v_cents.data_ptr(), _ptr(k_res), _ptr(v_res), k_out.data_ptr(),
+                                          v_out.data_ptr(), _stream()), fmt.gather)
     return int(t1) - int(t0) + int(r)
 
 
@@ -1475,13 +1534,13 @@ def pq_chunk_attn_blocks(q: torch.Tensor, k_chunk: Optional[torch.Tensor], v_chu
     if M <= 0 or d % M:
         raise RuntimeError(f"{who}: d={d} M={M}")
     dm = d // M
-    if packed or k_codes.dtype == torch.uint16:      # the plain codebooks, as pq_chunk_attn_wide / pq_chunk_attn_packed take them
-        k_cents, v_cents = k_prep, v_prep
-    elif k_codes.dtype == torch.uint8:     # prepared codebooks, as pq_chunk_attn takes them: their first image is the plain [m][c][d_m] table
+    if not packed and k_codes.dtype not in (torch.uint8, torch.uint16):
+        raise RuntimeError(f"{who}: codes must be uint8 (prepared codebooks) or uint16 (plain codebooks)")
+    if code_format(who, k_codes.dtype, None, packed).prepared:      # prepared codebooks, as pq_chunk_attn takes them: their first image is the plain [m][c][d_m] table
         _check_prepared(who, k_prep, v_prep, M, C, d)
         k_cents, v_cents = (t.reshape(-1)[:M * C * dm].view(M, C, dm) for t in (k_prep, v_prep))
-    else:
-        raise RuntimeError(f"{who}: codes must be uint8 (prepared codebooks) or uint16 (plain codebooks)")
+    else:      # the plain codebooks, as pq_chunk_attn_wide / pq_chunk_attn_packed take them
+        k_cents, v_cents = k_prep, v_prep
     if (k_chunk is None) != (v_chunk is None):
         raise RuntimeError(f"{who}: k_chunk and v_chunk go together")
     if k_chunk is not None and (k_chunk.shape != (bs, nh_k, n_q, d) or v_chunk.shape != k_chunk.shape):

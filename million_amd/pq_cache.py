@@ -21,6 +21,7 @@ row in the fallback (:888), the nested try/except fallbacks.
 """
 from __future__ import annotations
 
+import functools
 import heapq
 from typing import Dict, List, Optional, Set
 
@@ -212,7 +213,7 @@ class _CacheBase:
         self.value_cent = self.key_cent if value_cent is key_cent else value_cent.to(self.device, self.scalar_t).contiguous()
         if self.key_cent.shape[1] != self.C or self.value_cent.shape[1] != self.C:
             raise ValueError(f"codebooks must have 2**nbits = {self.C} centroids per subspace")
-        if self.C <= 256:      # LDS-ready images for the fused decode kernels and the fp32 image for the encoder
+        if self._fmt.prepared:      # LDS-ready images for the fused decode kernels and the fp32 image for the encoder
             self._kprep = ops.prepare_cents(self.key_cent, cache=False)
             self._vprep = self._kprep if self.value_cent is self.key_cent else ops.prepare_cents(self.value_cent, cache=False)
         else:
@@ -227,15 +228,21 @@ class _CacheBase:
             return ops.prefill_attn(q, k, v, causal=True, dev_spans=dev_spans, return_lse=True)
         return ops.prefill_attn(q, k, v, causal=True, dev_spans=dev_spans)
 
-    @staticmethod
-    def _chunk_op(who, route, wide=False):
-        """The chunk-attention op of an extend call.  route None / "chunk": chunk attention over the codes (ops.pq_chunk_attn, or
-        pq_chunk_attn_wide for uint16 codes); "blocks": the block route (ops.pq_chunk_attn_blocks: the past dequantised block by block
-        into a bounded scratch and attended by the prompt kernel - for long chunks, profiles/chunk_blocks.txt)."""
+    # self._fmt: the ops.CodeFormat of the cache's code stores, picked once by __init__
+    def _attn_cents(self):
+        """The codebook operands of the format's attention ops: the prepared blobs, or the codebooks as they are."""
+        return (self._kprep, self._vprep) if self._fmt.prepared else (self.key_cent, self.value_cent)
+
+    def _chunk_op(self, who, route):
+        """The chunk-attention op of an extend call, for the cache's format.  route None / "chunk": chunk attention over the codes
+        (ops.pq_chunk_attn, pq_chunk_attn_wide, pq_chunk_attn_packed); "blocks": the block route (ops.pq_chunk_attn_blocks: the
+        past dequantised block by block into a bounded scratch and attended by the prompt kernel - for long chunks,
+        profiles/chunk_blocks.txt), which picks the format from the code dtype and so is told packed=True where that cannot.
+        The ops are looked up here, when the call is made.  A route that does not exist is a ValueError."""
         if route is None or route == "chunk":
-            return ops.pq_chunk_attn_wide if wide else ops.pq_chunk_attn
+            return getattr(ops, self._fmt.op_chunk_attn)
         if route == "blocks":
-            return ops.pq_chunk_attn_blocks
+            return ops.pq_chunk_attn_blocks if self._fmt.rowmajor else functools.partial(ops.pq_chunk_attn_blocks, packed=True)
         raise ValueError(f"{who}: route={route!r} (None, 'chunk' or 'blocks')")
 
 
@@ -259,6 +266,7 @@ class DynamicPQCache(_CacheBase):
         self.bs, self.nh, self.num_key_value_heads, self.M, self.layer_num = bs, nh, num_key_value_heads, M, layer_num
         self.dtype, self.nbits, self.d, self.scalar_t, self.device = dtype, nbits, d, scalar_t, torch.device(device)
         self.C = 2 ** nbits
+        self._fmt = ops.code_format("DynamicPQCache", dtype, None)      # (nbits 13 .. 16: uint16 codes that no attention op reads)
         self.max_residual_length = d          # "Lt = d", pq_utils.py:110
         self.max_tokens = (max_tokens + d - 1) // d * d
         self.registery = KernelRegistry(M=M, d=d, nbits=nbits, nh=nh, scalar_t=scalar_t, device=device)
@@ -364,7 +372,7 @@ class DynamicPQCache(_CacheBase):
         On an empty cache this is prefill().  nbits 9 .. 12: the same over the uint16 store and the codebooks as they are
         (million_pq_chunk_attn_wide); nbits 13 .. 16 have no chunk kernel.  route="blocks": the attention by
         blocks through the prompt kernel (_chunk_op) - at nbits 9 .. 12 too - followed by the same store."""
-        attend = self._chunk_op("extend", route, wide=self.nbits > 8)
+        attend = self._chunk_op("extend", route)
         if self.nbits > 12:
             raise NotImplementedError(f"extend: nbits={self.nbits}: the chunk-attention kernels read uint8 codes (nbits <= 8) or "
                                       "uint16 codes of nbits 9 .. 12")
@@ -373,12 +381,8 @@ class DynamicPQCache(_CacheBase):
             return self.prefill(query_states, key_states, value_states, layer_idx)
         n = key_states.size(2)
         kres, vres = self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx]
-        if self.nbits > 8:
-            out = attend(query_states, key_states, value_states, self._k_store[layer_idx], self._v_store[layer_idx],
-                         self.key_cent, self.value_cent, kres, vres, r, M=self.M, C=self.C, n_tokens=T)
-        else:
-            out = attend(query_states, key_states, value_states, self._k_store[layer_idx], self._v_store[layer_idx],
-                         self._kprep, self._vprep, kres, vres, r, M=self.M, C=self.C, n_tokens=T)
+        out = attend(query_states, key_states, value_states, self._k_store[layer_idx], self._v_store[layer_idx],
+                     *self._attn_cents(), kres, vres, r, M=self.M, C=self.C, n_tokens=T)
         if T + r + n > self.max_tokens:
             raise RuntimeError(f"DynamicPQCache: {T + r + n} tokens exceed max_tokens={self.max_tokens}")
         if r:
@@ -493,6 +497,7 @@ class PagedPQCache(_CacheBase):
         self.preallocate = preallocate
         self.sink_tokens = int(sink_tokens)
         self.packed = bool(packed)
+        self._fmt = ops.code_format("PagedPQCache", dtype, self.C, self.packed)      # every later "which format?" reads this
         self.registery = KernelRegistry(M=M, d=d, nbits=nbits, nh=nh, scalar_t=scalar_t, device=device)
         self.init_cache()
 
@@ -500,13 +505,11 @@ class PagedPQCache(_CacheBase):
         nk, cap = self.num_key_value_heads, self.extended_residual_size
         total = self.layer_num * self.bs * nk * self.n_pages_cap
         z = lambda *s, dt: torch.zeros(*s, dtype=dt, device=self.device)
-        if self.packed:      # packed pages: a low-byte plane and a plane of 2 / 4 high bits per code, one page id for both
-            page_bytes = ops.packed_page_bytes(self.page_size, self.M, self.C)
-            self.key_page_pool = z(total, page_bytes, dt=torch.uint8)
-            self.value_page_pool = z(total, page_bytes, dt=torch.uint8)
-        else:
-            self.key_page_pool = z(total, self.page_size, self.M, dt=self.dtype)      # uint8; uint16 at nbits 9 .. 12
-            self.value_page_pool = z(total, self.M, self.page_size, dt=self.dtype)
+        # K pages (page_size, M), V pages (M, page_size), uint8 or uint16 at nbits 9 .. 12; packed: a low-byte plane and a plane of
+        # 2 / 4 high bits per code in one uint8 page, one page id for both
+        k_page, v_page = self._fmt.page_shapes(self.page_size, self.M, self.C)
+        self.key_page_pool = z(total, *k_page, dt=self._fmt.dtype)
+        self.value_page_pool = z(total, *v_page, dt=self._fmt.dtype)
         self.page_manager = PageManager(self.page_size, initial_pages=total, max_pages=total, M=self.M)
         # the layers' page tables, windows and length rows lie side by side (one allocation each; the per-layer lists are
         # views): one launch can then serve every layer (begin_step: encode-ahead, commit)
@@ -670,12 +673,10 @@ class PagedPQCache(_CacheBase):
         self._reserve(layer_idx, n, b)
         kw = dict(token_start=T, n=n, page_ids=self.page_ids[layer_idx][sel], page_size=self.page_size,
                   x_row_start=x_row_start, x_row_mod=x_row_mod)
-        if self.packed:
-            ops.pq_encode_into_packed(K, self.key_cent, self.key_page_pool, layout=L.MILLION_CODES_KPAGES, **kw)
-            ops.pq_encode_into_packed(V, self.value_cent, self.value_page_pool, layout=L.MILLION_CODES_VPAGES, **kw)
-            return
-        ops.pq_encode_into(K, self.key_cent, self.key_page_pool, layout=L.MILLION_CODES_KPAGES, prepared=self._kprep, **kw)
-        ops.pq_encode_into(V, self.value_cent, self.value_page_pool, layout=L.MILLION_CODES_VPAGES, prepared=self._vprep, **kw)
+        encode = getattr(ops, self._fmt.op_encode)
+        prep = lambda p: {"prepared": p} if self._fmt.op_encode == "pq_encode_into" else {}      # that op's keyword: the packed encoder has no such image
+        encode(K, self.key_cent, self.key_page_pool, layout=L.MILLION_CODES_KPAGES, **prep(self._kprep), **kw)
+        encode(V, self.value_cent, self.value_page_pool, layout=L.MILLION_CODES_VPAGES, **prep(self._vprep), **kw)
 
     def _store(self, K, V, layer_idx, n, b=None, all_rows=False):
         """The store step under every prefill / extend form, for request b (None: every request, in lockstep): the window
@@ -797,27 +798,62 @@ class PagedPQCache(_CacheBase):
             torch.cuda.current_stream().wait_stream(self._side)
         self._pre_a[layer_idx, slice(None) if b is None else b] = 0
 
-    def _extend_slot(self, query_states, key_states, value_states, layer_idx, b, return_lse=False, all_rows=False, route=None):
-        """b = None: every request (lockstep); else request b with batch-1 tensors.  return_lse: (out, lse) of the chunk
-        attention (ops.pq_chunk_attn); all_rows: every device row of the layer is rewritten, as prefill_request does.
-        route: the attention op (_chunk_op); its (out, lse) goes into the sink merge and the store follows, whichever it is."""
-        attend = self._chunk_op("extend", route)
+    def _extend_slot(self, attend, query_states, key_states, value_states, layer_idx, b, return_lse=False, all_rows=False):
+        """b = None: every request (lockstep); else request b with batch-1 tensors.  attend: the attention op of the cache's
+        format and the call's route (_chunk_op); its (out, lse) goes into the sink merge and the store follows, whichever it is.
+        return_lse: (out, lse) of that op; all_rows: every device row of the layer is rewritten, as prefill_request does.  The
+        callers checked the capacity."""
         i, sel = (0, slice(None)) if b is None else (b, slice(b, b + 1))
         T, r, rs = int(self._T_a[layer_idx, i]), int(self._r_a[layer_idx, i]), int(self._rs_a[layer_idx, i])
-        n = key_states.size(2)
-        if T + r + n > self.max_tokens:
-            raise RuntimeError(f"PagedPQCache: {T + r + n} tokens exceed max_tokens={self.max_tokens}")
         ids = self.page_ids[layer_idx][sel]
         sinks = bool(self.sink_tokens)
-        out = attend(query_states, key_states, value_states, self.key_page_pool, self.value_page_pool, self._kprep,
-                     self._vprep, self.key_residual_cache[layer_idx][sel], self.value_residual_cache[layer_idx][sel], r,
+        out = attend(query_states, key_states, value_states, self.key_page_pool, self.value_page_pool, *self._attn_cents(),
+                     self.key_residual_cache[layer_idx][sel], self.value_residual_cache[layer_idx][sel], r,
                      M=self.M, C=self.C, n_tokens=T, resid_start=rs, k_page_ids=ids, v_page_ids=ids,
                      page_size=self.page_size, **({"return_lse": True} if return_lse or sinks else {}))
         if sinks:      # before the store: a request's first chunk has its sinks among the chunk rows, and none kept yet
             self._sink_merge(layer_idx, query_states, out[0], out[1], sel)
             out = out if return_lse else out[0]
-        self._store(key_states, value_states, layer_idx, n, b, all_rows=all_rows)      # the window in ring order, then the new rows
+        self._store(key_states, value_states, layer_idx, key_states.size(2), b, all_rows=all_rows)      # the window in ring order, then the new rows
         return out
+
+    def _extend_room(self, layer_idx, i, n, to_prefill):
+        """Refuses n new tokens of request i (0: every request, in lockstep) that the pages cannot take behind its T coded and r
+        window tokens - before anything is joined or launched.  to_prefill: the rows go to prefill(), which keeps a request's
+        first sink_tokens rows outside the pages."""
+        need = int(self._T_a[layer_idx, i]) + int(self._r_a[layer_idx, i]) + n - (min(self.sink_tokens, n) if to_prefill else 0)
+        if need > self.max_tokens:
+            raise RuntimeError(f"PagedPQCache: {need} tokens exceed max_tokens={self.max_tokens}")
+
+    def _extend(self, who, out_of_step, query_states, key_states, value_states, layer_idx, route):
+        """extend() for a cache of any format: the public method refuses the wide ones first, million_amd.paged_turns serves them
+        from here.  Order: a route that does not exist, requests out of lockstep (out_of_step: the caller's words for it, which
+        name its own call for one request), the capacity, then the join and the launches."""
+        attend = self._chunk_op(who, route)
+        if not self._lockstep(layer_idx):
+            raise RuntimeError(out_of_step)
+        empty = self._T_a[layer_idx, 0] == 0 and self._r_a[layer_idx, 0] == 0 and not self._sink_a[layer_idx].any()
+        self._extend_room(layer_idx, 0, key_states.size(2), empty)
+        self._join_side(layer_idx)
+        if empty:
+            return self.prefill(query_states, key_states, value_states, layer_idx)
+        return self._extend_slot(attend, query_states, key_states, value_states, layer_idx, None)
+
+    def _extend_request(self, who, b, query_states, key_states, value_states, layer_idx, return_lse, route):
+        """extend_request() for a cache of any format, as _extend.  An empty slot is prefill_request() - with return_lse, which the
+        prompt kernel has not, chunk attention over the chunk alone (every device row rewritten, as prefill_request does) -
+        whatever `route` says."""
+        attend = self._chunk_op(who, route)
+        if key_states.size(0) != 1 or query_states.size(0) != 1:
+            raise RuntimeError(f"{who}: tensors of batch 1")
+        empty = self._T_a[layer_idx, b] == 0 and self._r_a[layer_idx, b] == 0 and not self._sink_a[layer_idx, b]
+        self._extend_room(layer_idx, b, key_states.size(2), empty and not return_lse)
+        self._join_side(layer_idx, b)
+        if empty and not return_lse:
+            return self.prefill_request(b, query_states, key_states, value_states, layer_idx)
+        if empty:
+            return self._extend_slot(self._chunk_op(who, None), query_states, key_states, value_states, layer_idx, b, return_lse=True, all_rows=True)
+        return self._extend_slot(attend, query_states, key_states, value_states, layer_idx, b, return_lse=return_lse)
 
     def extend(self, query_states, key_states, value_states, layer_idx, route=None):
         """n new tokens of one layer, every request in lockstep (a later turn of the conversations, the next chunk of their
@@ -830,13 +866,7 @@ class PagedPQCache(_CacheBase):
         route: None / "chunk": chunk attention as above; "blocks": the same attention by blocks through the prompt kernel
         (ops.pq_chunk_attn_blocks, DESIGN.md 4.16: for long chunks), followed by the same store."""
         self._no_wide("extend")
-        self._chunk_op("extend", route)      # a route that does not exist is said first
-        if not self._lockstep(layer_idx):
-            raise RuntimeError("PagedPQCache.extend: requests are at different lengths; use extend_request(b, ...)")
-        self._join_side(layer_idx)
-        if self._T_a[layer_idx, 0] == 0 and self._r_a[layer_idx, 0] == 0 and not self._sink_a[layer_idx].any():
-            return self.prefill(query_states, key_states, value_states, layer_idx)
-        return self._extend_slot(query_states, key_states, value_states, layer_idx, None, route=route)
+        return self._extend("extend", "PagedPQCache.extend: requests are at different lengths; use extend_request(b, ...)", query_states, key_states, value_states, layer_idx, route)
 
     def extend_request(self, b, query_states, key_states, value_states, layer_idx, return_lse=False, route=None):
         """extend() for ONE request (tensors of batch 1) in slot b; the other slots, their host and device lengths, are not
@@ -846,15 +876,7 @@ class PagedPQCache(_CacheBase):
         alone, followed by the same store: the slot, the pages and every length are left as prefill_request leaves them.
         route: as extend(); an empty slot keeps its present routes whatever it says."""
         self._no_wide("extend_request")
-        self._chunk_op("extend_request", route)
-        if key_states.size(0) != 1 or query_states.size(0) != 1:
-            raise RuntimeError("extend_request: tensors of batch 1")
-        self._join_side(layer_idx, b)
-        if self._T_a[layer_idx, b] == 0 and self._r_a[layer_idx, b] == 0 and not self._sink_a[layer_idx, b]:
-            if return_lse:
-                return self._extend_slot(query_states, key_states, value_states, layer_idx, b, return_lse=True, all_rows=True)
-            return self.prefill_request(b, query_states, key_states, value_states, layer_idx)
-        return self._extend_slot(query_states, key_states, value_states, layer_idx, b, return_lse=return_lse, route=route)
+        return self._extend_request("extend_request", b, query_states, key_states, value_states, layer_idx, return_lse, route)
 
     def extend_ragged(self, query_states, key_states, value_states, layer_idx, n_new, device_store=False):
         """extend_request() for every slot in ONE attention launch: tensors of batch bs padded to n_q = max(n_new) rows,
@@ -1392,14 +1414,10 @@ class PagedPQCache(_CacheBase):
             raise RuntimeError("PagedPQCache: requests at different lengths need use_dev_lengths=True")
         r, rs = int(self._r_a[layer_idx, 0]), int(self._rs_a[layer_idx, 0])
         dl = self.lengths[layer_idx] if use_dev_lengths else None
-        wide = self.nbits > 8
+        fmt, ids = self._fmt, self.page_ids[layer_idx]
         if self._ws is None:      # one workspace per cache (calls of one cache are stream-ordered)
-            if wide:
-                need = ops.decode_wide_workspace_bytes(query_states, self.key_residual_cache[layer_idx], M=self.M, C=self.C,
-                                                       page_size=self.page_size)
-            else:
-                need = ops.decode_workspace_bytes(query_states, self.key_residual_cache[layer_idx], nh_k=self.num_key_value_heads,
-                                                  M=self.M, C=self.C)
+            need = getattr(ops, fmt.op_decode_ws)(query_states, self.key_residual_cache[layer_idx], M=self.M, C=self.C,
+                                                  **({"nh_k": self.num_key_value_heads} if fmt.op_decode_ws == "decode_workspace_bytes" else {"page_size": self.page_size}))
             self._ws = torch.zeros(need, dtype=torch.uint8, device=self.device)
         self._note_appended(layer_idx)
         self._dev_rows_stale |= not use_dev_lengths
@@ -1408,24 +1426,16 @@ class PagedPQCache(_CacheBase):
             if self._sink_lse is None:
                 self._sink_lse = torch.empty(self.bs, self.nh, 1, dtype=torch.float32, device=self.device)
             lse = self._sink_lse
-        if wide:      # the same launch over uint16 codes - or packed pages -, the codebooks as they are (csrc/attn_wide.hip)
-            attend = ops.pq_decode_attn_packed if self.packed else ops.pq_decode_attn_wide
-            return attend(query_states, self.key_page_pool, self.value_page_pool, self.key_cent, self.value_cent,
-                                           self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx], r,
-                                           k_new=key_states, v_new=value_states,
-                                           n_tokens=self.max_tokens if use_dev_lengths else int(self._T_a[layer_idx, 0]),
-                                           resid_start=rs, page_ids=self.page_ids[layer_idx], page_size=self.page_size, out=out,
-                                           dev_lengths=dl, workspace=self._ws,
-                                           **({"return_lse": True, "lse": lse} if want_lse else {}))
-        # append (:377-380) + attention (:386) in ONE launch: the new row is attended to and parked in the window
-        res = ops.pq_decode_attn(query_states, self.key_page_pool, self.value_page_pool, self._kprep, self._vprep,
-                                 self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx], r,
-                                 k_new=key_states, v_new=value_states,
-                                 M=self.M, C=self.C, n_tokens=self.max_tokens if use_dev_lengths else int(self._T_a[layer_idx, 0]),
-                                 resid_start=rs, k_page_ids=self.page_ids[layer_idx],
-                                 v_page_ids=self.page_ids[layer_idx], page_size=self.page_size, out=out,
-                                 dev_lengths=dl, workspace=self._ws,
-                                 **({"return_lse": True, "lse": lse} if return_lse or lse is not None else {}))
+        # append (:377-380) + attention (:386) in ONE launch: the new row is attended to and parked in the window.  The format's op:
+        # pq_decode_attn, or the same launch over uint16 codes or packed pages with the codebooks as they are (csrc/attn_wide.hip)
+        res = getattr(ops, fmt.op_decode_attn)(
+            query_states, self.key_page_pool, self.value_page_pool, *self._attn_cents(),
+            self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx], r, k_new=key_states, v_new=value_states,
+            n_tokens=self.max_tokens if use_dev_lengths else int(self._T_a[layer_idx, 0]), resid_start=rs, page_size=self.page_size,
+            out=out, dev_lengths=dl, workspace=self._ws,
+            # pq_decode_attn serves row-major sides behind a blob without a shape: a table per side, M and C said; the ops over pools take one table
+            **({"M": self.M, "C": self.C, "k_page_ids": ids, "v_page_ids": ids} if fmt.op_decode_attn == "pq_decode_attn" else {"page_ids": ids}),
+            **({"return_lse": True, "lse": lse} if return_lse or lse is not None else {}))
         if self.sink_tokens:      # the count is read on the device: a captured step follows release and a new prompt
             self._sink_merge(layer_idx, query_states, res[0].view(query_states.shape), res[1])
             res = res if want_lse else res[0]
