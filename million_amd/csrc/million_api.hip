@@ -23,6 +23,20 @@ void set_error(const char *fmt, ...) {
     va_end(ap);
 }
 
+// The tail of every launch of this file: MILLION_OK, or MILLION_ERR_LAUNCH behind the error "<what>: <hip's words>" (what: a
+// printf format with its arguments, e.g. "prepare_cents launch")
+static int launch_tail(const char *what, ...) {
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return MILLION_OK;
+    char name[64];
+    va_list ap;
+    va_start(ap, what);
+    vsnprintf(name, sizeof(name), what, ap);
+    va_end(ap);
+    set_error("%s: %s", name, hipGetErrorString(e));
+    return MILLION_ERR_LAUNCH;
+}
+
 // ---- per-device state: the only mutable globals of the library besides the diagnostic knobs below ----
 constexpr int kMaxDevices = 64;
 static std::mutex g_dev_mutex;
@@ -163,6 +177,16 @@ static size_t attn_partial_bytes(int bs, int nh_k, int G, int d) {
                      (size_t)bs * nh_k * (kMaxSplits + 1) * slot_floats_sized(G, d) * sizeof(float);
     return (b + 255) / 256 * 256;
 }
+// The layout above, laid over a caller's workspace: the one place that computes these offsets.  Returns the end of the partials,
+// where the uint8 entries keep their transposed-V scratch (million_attn_workspace_bytes).
+static uint8_t *carve_workspace(AttnParams &p, void *workspace) {
+    char *w = (char *)workspace;
+    p.ws_cnt = (unsigned long long *)w;
+    p.ws_cnt2 = (int *)((unsigned *)w + head_pairs(p.bs, p.nh_k) * kRecWords);
+    p.ws_flags = (unsigned *)(w + attn_cnt_bytes(p.bs, p.nh_k));
+    p.ws_part = (float *)(w + attn_cnt_bytes(p.bs, p.nh_k) + attn_flag_bytes(p.bs, p.nh_k));
+    return (uint8_t *)w + attn_partial_bytes(p.bs, p.nh_k, p.G, p.d);
+}
 
 // wide: the call is million_pq_decode_attn_wide's (uint16 codes: attn_wide.hip); the geometry check is then that kernel's
 static int fill_attn_params(const million_attn_desc *desc, AttnParams &p, bool wide = false) {
@@ -263,9 +287,7 @@ int million_prepare_cents(const void *cents, int M, int C, int d_m, void *prepar
     const int n = M * C * d_m;
     hipLaunchKernelGGL(prepare_cents_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                        (const f16 *)cents, (f16 *)prepared, M, C, d_m);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("prepare_cents launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
-    return MILLION_OK;
+    return launch_tail("prepare_cents launch");
 }
 
 static int fill_enc_params(const char *who, const million_encode_desc *desc, const void *x, const void *cents, void *dst,
@@ -388,9 +410,7 @@ int million_transpose_v_codes(const void *v_codes, void *v_pages, int bs, int nh
     const int n_pages = (n_tokens + 63) / 64;
     hipLaunchKernelGGL(codes_transpose_kernel, dim3(n_pages, bs * nh_k), dim3(256), 0, (hipStream_t)stream,
                        (const uint8_t *)v_codes, (uint8_t *)v_pages, nh_k, n_tokens, M, (long long)v_stride_b, (long long)v_stride_h, n_pages);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("codes_transpose launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
-    return MILLION_OK;
+    return launch_tail("codes_transpose launch");
 }
 
 size_t million_attn_workspace_bytes(const million_attn_desc *desc) {
@@ -456,9 +476,7 @@ static int launch_plan(const AttnPlan &plan, hipStream_t stream) {
     void *args[] = {(void *)&plan.p};
 #endif
     (void)hipLaunchKernel(plan.kernel, plan.grid, plan.block, args, plan.lds, stream);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("attn launch (kind %d): %s", plan.kind, hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
-    return MILLION_OK;
+    return launch_tail("attn launch (kind %d)", plan.kind);
 }
 
 // not a silent cliff: the scalar kernel is ~60x slower than the MFMA kernels.  Said once per process on
@@ -488,19 +506,46 @@ int million_attn_kernel_kind(const million_attn_desc *desc) {
     return plan.kind;
 }
 
+// ---- what every decode-attention entry does alike; who: "attn" (uint8 codes) or "attn_wide" (uint16 codes, packed pages) ----
+// the fused append: k_new / v_new come together, into a window with room (device lengths: the kernel's to know), 16-byte aligned
+static int check_fused_append(const char *who, const AttnParams &p, const void *k_new, const void *v_new) {
+    if ((k_new == nullptr) != (v_new == nullptr)) { set_error("%s: k_new and v_new must both be given", who); return MILLION_ERR_ARG; }
+    if (!k_new) return MILLION_OK;
+    if (!p.dev_lengths && p.r >= p.rcap) { set_error("%s: fused append into a full window (r=%d, cap=%d)", who, p.r, p.rcap); return MILLION_ERR_ARG; }
+    if (((uintptr_t)k_new | (uintptr_t)v_new) & 15) { set_error("%s: k_new / v_new must be 16-byte aligned", who); return MILLION_ERR_ALIGN; }
+    return MILLION_OK;
+}
+
+// the operands of a checked call.  k_tab / v_tab: the prepared images (uint8: the caller adds their column images, *_tab_col)
+// or the plain (M, C, d_m) codebooks (wide)
+static void fill_operands(AttnParams &p, const million_attn_desc *desc, const void *q, const void *k_new, const void *v_new,
+                          const void *k_codes, const void *v_codes, const void *k_page_ids, const void *v_page_ids,
+                          const void *k_tab, const void *v_tab, const void *k_resid, const void *v_resid, void *out, float *lse) {
+    p.q = (const f16 *)q; p.k_codes = (const uint8_t *)k_codes; p.v_codes = (const uint8_t *)v_codes;
+    p.k_ids32 = (const int *)k_page_ids; p.k_ids64 = (const long long *)k_page_ids;
+    p.v_ids32 = (const int *)v_page_ids; p.v_ids64 = (const long long *)v_page_ids;
+    p.k_tab = (const f16 *)k_tab; p.v_tab = (const f16 *)v_tab;
+    p.k_res = (const f16 *)k_resid; p.v_res = (const f16 *)v_resid; p.out = (f16 *)out;
+    p.lse = lse;
+    p.k_new = (const f16 *)k_new; p.v_new = (const f16 *)v_new;
+    p.k_res_w = (f16 *)k_resid; p.v_res_w = (f16 *)v_resid;
+    p.dev_lengths_w = (int *)desc->dev_lengths;
+    p.dbg = g_dbg;
+    p.k_pool_pages = desc->k_pool_pages; p.v_pool_pages = desc->v_pool_pages;
+#ifdef MILLION_DEBUG_CHECK_IDS
+    p.bad_ids = bad_ids_counter();
+#endif
+}
+
 static int attn_impl(const million_attn_desc *desc, const void *q, const void *k_new, const void *v_new,
                      const void *k_codes, const void *v_codes,
                      const void *k_page_ids, const void *v_page_ids, const void *k_cents_prepared, const void *v_cents_prepared,
                      const void *k_resid, const void *v_resid, void *out, float *lse, void *workspace,
                      size_t workspace_bytes, million_stream_t stream) {
     AttnParams p;
-    const int rc = fill_attn_params(desc, p);
+    int rc = fill_attn_params(desc, p);
+    if (rc == MILLION_OK) rc = check_fused_append("attn", p, k_new, v_new);
     if (rc != MILLION_OK) return rc;
-    if ((k_new == nullptr) != (v_new == nullptr)) { set_error("attn: k_new and v_new must both be given"); return MILLION_ERR_ARG; }
-    if (k_new) {
-        if (!p.dev_lengths && p.r >= p.rcap) { set_error("attn: fused append into a full window (r=%d, cap=%d)", p.r, p.rcap); return MILLION_ERR_ARG; }
-        if (((uintptr_t)k_new | (uintptr_t)v_new) & 15) { set_error("attn: k_new / v_new must be 16-byte aligned"); return MILLION_ERR_ALIGN; }
-    }
     if (!q || !k_cents_prepared || !v_cents_prepared || !k_resid || !v_resid || !out || !workspace) { set_error("attn: null pointer"); return MILLION_ERR_ARG; }
     if (p.T > 0 && (!k_codes || !v_codes)) { set_error("attn: null code pointer with n_tokens=%d", p.T); return MILLION_ERR_ARG; }
     if (p.T > 0 && ((p.k_paged && !k_page_ids) || (p.v_paged && !p.v_identity && !v_page_ids))) { set_error("attn: paged layout without page ids"); return MILLION_ERR_ARG; }
@@ -512,27 +557,10 @@ static int attn_impl(const million_attn_desc *desc, const void *q, const void *k
     }
     if ((!p.k_paged && ((p.k_sb | p.k_sh) & 15)) || (!p.v_paged && ((p.v_sb | p.v_sh) & 15))) { set_error("attn: code strides must be multiples of 16 bytes"); return MILLION_ERR_ALIGN; }
     if ((p.res_sb | p.res_sh) & 7) { set_error("attn: residual strides must be multiples of 8 elements"); return MILLION_ERR_ALIGN; }
-    const size_t tab = (size_t)p.M * p.C * p.dm;
-    p.q = (const f16 *)q; p.k_codes = (const uint8_t *)k_codes; p.v_codes = (const uint8_t *)v_codes;
-    p.k_ids32 = (const int *)k_page_ids; p.k_ids64 = (const long long *)k_page_ids;
-    p.v_ids32 = (const int *)v_page_ids; p.v_ids64 = (const long long *)v_page_ids;
-    p.k_tab = (const f16 *)k_cents_prepared; p.k_tab_col = p.k_tab + tab;
-    p.v_tab = (const f16 *)v_cents_prepared; p.v_tab_col = p.v_tab + tab;
-    p.k_res = (const f16 *)k_resid; p.v_res = (const f16 *)v_resid; p.out = (f16 *)out;
-    p.lse = lse;
-    p.k_new = (const f16 *)k_new; p.v_new = (const f16 *)v_new;
-    p.k_res_w = (f16 *)k_resid; p.v_res_w = (f16 *)v_resid;
-    p.dev_lengths_w = (int *)desc->dev_lengths;
-    p.ws_cnt = (unsigned long long *)workspace;
-    p.ws_cnt2 = (int *)((unsigned *)workspace + head_pairs(p.bs, p.nh_k) * kRecWords);
-    p.ws_flags = (unsigned *)((char *)workspace + attn_cnt_bytes(p.bs, p.nh_k));
-    p.dbg = g_dbg;
-    p.k_pool_pages = desc->k_pool_pages; p.v_pool_pages = desc->v_pool_pages;
-#ifdef MILLION_DEBUG_CHECK_IDS
-    p.bad_ids = bad_ids_counter();
-#endif
-    p.ws_part = (float *)((char *)workspace + attn_cnt_bytes(p.bs, p.nh_k) + attn_flag_bytes(p.bs, p.nh_k));
-    uint8_t *scratch = (uint8_t *)workspace + attn_partial_bytes(p.bs, p.nh_k, p.G, p.d);
+    fill_operands(p, desc, q, k_new, v_new, k_codes, v_codes, k_page_ids, v_page_ids, k_cents_prepared, v_cents_prepared, k_resid, v_resid, out, lse);
+    const size_t tab = (size_t)p.M * p.C * p.dm;      // the column image lies behind the row image (prepare_cents_kernel)
+    p.k_tab_col = p.k_tab + tab; p.v_tab_col = p.v_tab + tab;
+    uint8_t *scratch = carve_workspace(p, workspace);
     const bool rowmajor = !p.k_paged && !p.v_paged;
     AttnParams pl = rowmajor ? with_v_pages(p, scratch) : p;
     AttnPlan plan;
@@ -543,8 +571,8 @@ static int attn_impl(const million_attn_desc *desc, const void *q, const void *k
     if (pl.v_paged && !p.v_paged && p.T > 0) {      // once per call, whatever the number of query-head groups below
         hipLaunchKernelGGL(codes_transpose_kernel, dim3(pl.n_pages_cap, p.bs * p.nh_k), dim3(256), 0, (hipStream_t)stream,
                            p.v_codes, scratch, p.nh_k, p.T, p.M, p.v_sb, p.v_sh, pl.n_pages_cap);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { set_error("codes_transpose launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
+        const int rc_t = launch_tail("codes_transpose launch");
+        if (rc_t != MILLION_OK) return rc_t;
     }
     // One launch of the MFMA and tile kernels serves up to 16 query heads per kv head (the 16 columns of the score tile:
     // Llama-3.1-405B's nh / nh_k = 16 reads its codes once), of the scalar kernel up to 8; bigger groups run as several
@@ -610,13 +638,9 @@ static int attn_wide_call(bool packed, const million_attn_desc *desc, const void
                           const void *k_cents, const void *v_cents, void *k_resid, void *v_resid, void *out, float *lse,
                           void *workspace, size_t workspace_bytes, million_stream_t stream) {
     AttnParams p;
-    const int rc = fill_attn_params(desc, p, true);
+    int rc = fill_attn_params(desc, p, true);
+    if (rc == MILLION_OK) rc = check_fused_append("attn_wide", p, k_new, v_new);
     if (rc != MILLION_OK) return rc;
-    if ((k_new == nullptr) != (v_new == nullptr)) { set_error("attn_wide: k_new and v_new must both be given"); return MILLION_ERR_ARG; }
-    if (k_new) {
-        if (!p.dev_lengths && p.r >= p.rcap) { set_error("attn_wide: fused append into a full window (r=%d, cap=%d)", p.r, p.rcap); return MILLION_ERR_ARG; }
-        if (((uintptr_t)k_new | (uintptr_t)v_new) & 15) { set_error("attn_wide: k_new / v_new must be 16-byte aligned"); return MILLION_ERR_ALIGN; }
-    }
     if (!q || !k_cents || !v_cents || !k_resid || !v_resid || !out || !workspace) { set_error("attn_wide: null pointer"); return MILLION_ERR_ARG; }
     if (p.T > 0 && (!k_codes || !v_codes)) { set_error("attn_wide: null code pointer with n_tokens=%d", p.T); return MILLION_ERR_ARG; }
     if (p.T > 0 && (!k_page_ids || !v_page_ids)) { set_error("attn_wide: paged layout without page ids"); return MILLION_ERR_ARG; }
@@ -629,24 +653,8 @@ static int attn_wide_call(bool packed, const million_attn_desc *desc, const void
     if (((uintptr_t)k_cents | (uintptr_t)v_cents) & (uintptr_t)(p.dm * 2 - 1)) { set_error("attn_wide: codebooks must be aligned to one entry (%d bytes)", p.dm * 2); return MILLION_ERR_ALIGN; }
     if ((uintptr_t)lse & 3) { set_error("attn_wide: lse must be 4-byte aligned"); return MILLION_ERR_ALIGN; }
     if ((p.res_sb | p.res_sh) & 7) { set_error("attn_wide: residual strides must be multiples of 8 elements"); return MILLION_ERR_ALIGN; }
-    p.q = (const f16 *)q; p.k_codes = (const uint8_t *)k_codes; p.v_codes = (const uint8_t *)v_codes;
-    p.k_ids32 = (const int *)k_page_ids; p.k_ids64 = (const long long *)k_page_ids;
-    p.v_ids32 = (const int *)v_page_ids; p.v_ids64 = (const long long *)v_page_ids;
-    p.k_tab = (const f16 *)k_cents; p.v_tab = (const f16 *)v_cents;      // the plain (M, C, d_m) tensors: no prepared image
-    p.k_res = (const f16 *)k_resid; p.v_res = (const f16 *)v_resid; p.out = (f16 *)out;
-    p.lse = lse;
-    p.k_new = (const f16 *)k_new; p.v_new = (const f16 *)v_new;
-    p.k_res_w = (f16 *)k_resid; p.v_res_w = (f16 *)v_resid;
-    p.dev_lengths_w = (int *)desc->dev_lengths;
-    p.ws_cnt = (unsigned long long *)workspace;
-    p.ws_cnt2 = (int *)((unsigned *)workspace + head_pairs(p.bs, p.nh_k) * kRecWords);
-    p.ws_flags = (unsigned *)((char *)workspace + attn_cnt_bytes(p.bs, p.nh_k));
-    p.ws_part = (float *)((char *)workspace + attn_cnt_bytes(p.bs, p.nh_k) + attn_flag_bytes(p.bs, p.nh_k));
-    p.dbg = g_dbg;
-    p.k_pool_pages = desc->k_pool_pages; p.v_pool_pages = desc->v_pool_pages;
-#ifdef MILLION_DEBUG_CHECK_IDS
-    p.bad_ids = bad_ids_counter();
-#endif
+    fill_operands(p, desc, q, k_new, v_new, k_codes, v_codes, k_page_ids, v_page_ids, k_cents, v_cents, k_resid, v_resid, out, lse);      // the plain codebooks: no prepared image
+    carve_workspace(p, workspace);
     AttnPlan plan;
     if (!plan_attn_wide(p, plan, packed)) { set_error("attn_wide: no kernel for this call"); return MILLION_ERR_SHAPE; }
     return launch_plan(plan, (hipStream_t)stream);
@@ -680,17 +688,13 @@ int million_residual_append(const void *k_new, const void *v_new, void *k_resid,
     hipLaunchKernelGGL(residual_append_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const f16 *)k_new,
                        (const f16 *)v_new, (f16 *)k_resid, (f16 *)v_resid, bs, nh_k, d, resid_cap,
                        (long long)resid_stride_b, (long long)resid_stride_h, r, resid_start, dev_lengths);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("residual_append launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
-    return MILLION_OK;
+    return launch_tail("residual_append launch");
 }
 
 int million_lengths_advance(int32_t *dev_lengths, int bs, int n_flushed, int resid_cap, million_stream_t stream) {
     if (!dev_lengths || bs <= 0 || resid_cap <= 0) { set_error("lengths_advance: bad argument"); return MILLION_ERR_ARG; }
     hipLaunchKernelGGL(lengths_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, dev_lengths, bs, n_flushed, resid_cap);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error("lengths_advance launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
-    return MILLION_OK;
+    return launch_tail("lengths_advance launch");
 }
 
 }  // extern "C"

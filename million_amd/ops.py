@@ -233,11 +233,43 @@ class CodeFormat:
     chunk_attn_lse: str                # with it: one entry with an lse argument that may be null, except for 8-bit codes
     chunk_ws: str
     gather: str
-    # the functions of this module a paged cache calls, looked up by name when called
-    op_encode: str
+    # the attention ops of this module over its stores, looked up by name when called (the methods below)
     op_decode_attn: str
-    op_decode_ws: str
     op_chunk_attn: str
+
+    # ---- what a paged cache asks of its format: one call shape per job, whichever the format.  cents, prepared: the (K, V) pairs
+    # of the codebooks as they are and of their prepared blobs (None where the format has none); the format takes what its op takes
+    def encode_pages(self, X, cent, prepared, pool, **kw):
+        """Rows of X into pages of `pool` (pq_encode_into's keywords); pq_encode_into takes the prepared image, the packed encoder has none."""
+        if self.rowmajor:
+            return pq_encode_into(X, cent, pool, prepared=prepared, **kw)
+        return pq_encode_into_packed(X, cent, pool, **kw)
+
+    def decode_workspace(self, q, k_res, *, M, C, page_size):
+        """Bytes of the (zeroed) workspace of decode_pages calls of this shape."""
+        if self.prepared:
+            return decode_workspace_bytes(q, k_res, nh_k=k_res.shape[1], M=M, C=C)
+        return decode_wide_workspace_bytes(q, k_res, M=M, C=C, page_size=page_size)
+
+    def decode_pages(self, q, k_pool, v_pool, cents, prepared, k_res, v_res, r, *, M, C, page_ids, **kw):
+        """Decode attention over the two pools through one page table; kw: what the three decode ops take alike."""
+        op = globals()[self.op_decode_attn]
+        if self.prepared:      # pq_decode_attn serves row-major sides too, behind a blob without a shape: a table per side, M and C said
+            return op(q, k_pool, v_pool, *prepared, k_res, v_res, r, M=M, C=C, k_page_ids=page_ids, v_page_ids=page_ids, **kw)
+        return op(q, k_pool, v_pool, *cents, k_res, v_res, r, page_ids=page_ids, **kw)
+
+    def chunk_op(self, who, route):
+        """The chunk attention of an extend call as attend(q, k_chunk, v_chunk, k_codes, v_codes, cents, prepared, k_res, v_res, r, **kw),
+        kw pq_chunk_attn's.  route None / "chunk": chunk attention over the codes (pq_chunk_attn, pq_chunk_attn_wide, pq_chunk_attn_packed);
+        "blocks": the block route (pq_chunk_attn_blocks: the past dequantised block by block into a bounded scratch and attended by the
+        prompt kernel - for long chunks, profiles/chunk_blocks.txt), which picks the format from the code dtype and so is told
+        packed=True where that cannot.  A route that does not exist is a ValueError, raised here: before the caller does anything."""
+        if route not in (None, "chunk", "blocks"):
+            raise ValueError(f"{who}: route={route!r} (None, 'chunk' or 'blocks')")
+        name = "pq_chunk_attn_blocks" if route == "blocks" else self.op_chunk_attn
+        said = {"packed": True} if route == "blocks" and not self.rowmajor else {}
+        return lambda q, k_chunk, v_chunk, k_codes, v_codes, cents, prepared, *window, **kw: globals()[name](
+            q, k_chunk, v_chunk, k_codes, v_codes, *(prepared if self.prepared else cents), *window, **said, **kw)
 
 
 FMT_U8 = CodeFormat(
@@ -245,22 +277,19 @@ FMT_U8 = CodeFormat(
     check_store=_check_word_store,
     encode="million_pq_encode", decode_attn="million_pq_decode_attn", decode_ws="million_attn_workspace_bytes",
     chunk_attn="million_pq_chunk_attn", chunk_attn_lse="million_pq_chunk_attn_lse", chunk_ws="million_chunk_attn_workspace_bytes",
-    gather="million_pq_gather_rows", op_encode="pq_encode_into", op_decode_attn="pq_decode_attn", op_decode_ws="decode_workspace_bytes",
-    op_chunk_attn="pq_chunk_attn")
+    gather="million_pq_gather_rows", op_decode_attn="pq_decode_attn", op_chunk_attn="pq_chunk_attn")
 FMT_U16 = CodeFormat(
     "uint16", WIDE_CENTROIDS, torch.uint16, rowmajor=True, code_bytes=2, prepared=False, page_shapes=_word_page_shapes,
     check_store=_check_word_store,
     encode="million_pq_encode", decode_attn="million_pq_decode_attn_wide", decode_ws="million_attn_wide_workspace_bytes",
     chunk_attn="million_pq_chunk_attn_wide", chunk_attn_lse="million_pq_chunk_attn_wide", chunk_ws="million_chunk_attn_wide_workspace_bytes",
-    gather="million_pq_gather_rows", op_encode="pq_encode_into", op_decode_attn="pq_decode_attn_wide",
-    op_decode_ws="decode_wide_workspace_bytes", op_chunk_attn="pq_chunk_attn_wide")
+    gather="million_pq_gather_rows", op_decode_attn="pq_decode_attn_wide", op_chunk_attn="pq_chunk_attn_wide")
 FMT_PACKED = CodeFormat(
     "packed", WIDE_CENTROIDS, torch.uint8, rowmajor=False, code_bytes=2, prepared=False, page_shapes=_packed_page_shapes,
     check_store=_check_packed_store,
     encode="million_pq_encode_packed", decode_attn="million_pq_decode_attn_packed", decode_ws="million_attn_wide_workspace_bytes",
     chunk_attn="million_pq_chunk_attn_packed", chunk_attn_lse="million_pq_chunk_attn_packed", chunk_ws="million_chunk_attn_wide_workspace_bytes",
-    gather="million_pq_gather_rows_packed", op_encode="pq_encode_into_packed", op_decode_attn="pq_decode_attn_packed",
-    op_decode_ws="decode_wide_workspace_bytes", op_chunk_attn="pq_chunk_attn_packed")
+    gather="million_pq_gather_rows_packed", op_decode_attn="pq_decode_attn_packed", op_chunk_attn="pq_chunk_attn_packed")
 CODE_FORMATS = (FMT_U8, FMT_U16, FMT_PACKED)
 
 
@@ -631,6 +660,38 @@ def _check_rowmajor(name, codes, M, n_tokens):
         raise RuntimeError(f"pq_decode_attn: n_tokens exceeds {name}")
 
 
+# ---- the checks every decode front makes (pq_decode_attn; pq_decode_attn_wide and _packed), each called where the front always made it ----
+def _check_fp16_q_window(who, q, k_res, v_res):
+    if q.dtype != torch.float16 or k_res.dtype != torch.float16 or v_res.dtype != torch.float16:
+        raise RuntimeError(f"{who}: q and residuals must be fp16")
+
+
+def _check_q_window(who, q, k_res, v_res, window_4d=False):
+    """window_4d: a window that is not 4-D is refused here too (the wide fronts; pq_decode_attn has no such check)."""
+    if q.dim() != 4 or q.shape[2] != 1 or not q.is_contiguous():
+        raise RuntimeError(f"{who}: q must be contiguous (bs, nh, 1, d)")
+    if ((window_4d and k_res.dim() != 4) or k_res.shape != v_res.shape or k_res.stride() != v_res.stride() or k_res.stride(3) != 1
+            or k_res.stride(2) != k_res.shape[3]):
+        raise RuntimeError(f"{who}: residual buffers must share shape/strides with dense rows")
+
+
+def _new_rows(who, q, nh_k, k_new, v_new):
+    """The rows of a fused append, checked and contiguous: r counts the valid rows BEFORE the call, the new row becomes row r."""
+    if k_new is None or v_new is None or tuple(k_new.shape) != (q.shape[0], nh_k, 1, q.shape[3]) or v_new.shape != k_new.shape:
+        raise RuntimeError(f"{who}: k_new / v_new must be (bs, nh_k, 1, d)")
+    if k_new.dtype != torch.float16 or v_new.dtype != torch.float16:
+        raise RuntimeError(f"{who}: k_new / v_new must be fp16")
+    return k_new.contiguous(), v_new.contiguous()
+
+
+def _lse_buffer(who, q, lse):
+    if lse is None:
+        return torch.empty(q.shape[0], q.shape[1], 1, dtype=torch.float32, device=q.device)
+    if lse.dtype != torch.float32 or tuple(lse.shape) != (q.shape[0], q.shape[1], 1) or not lse.is_contiguous():
+        raise RuntimeError(f"{who}: lse must be contiguous fp32 (bs, nh, 1)")
+    return lse
+
+
 def pq_decode_attn(q: torch.Tensor, k_codes: torch.Tensor, v_codes: torch.Tensor, k_prep: torch.Tensor,
                    v_prep: torch.Tensor, k_res: torch.Tensor, v_res: torch.Tensor, r: int, *, M: int, C: int,
                    n_tokens: Optional[int] = None, resid_start: int = 0,
@@ -651,15 +712,10 @@ def pq_decode_attn(q: torch.Tensor, k_codes: torch.Tensor, v_codes: torch.Tensor
     results over disjoint key sets combine with attn_merge.
     """
     _need_cuda(q, k_codes, v_codes, k_prep, v_prep, k_res, v_res, k_page_ids, v_page_ids, out, dev_lengths, lse)
-    if q.dtype != torch.float16 or k_res.dtype != torch.float16 or v_res.dtype != torch.float16:
-        raise RuntimeError("pq_decode_attn: q and residuals must be fp16")
+    _check_fp16_q_window("pq_decode_attn", q, k_res, v_res)
     if k_codes.dtype != torch.uint8 or v_codes.dtype != torch.uint8:
         raise RuntimeError("pq_decode_attn: codes must be uint8")
-    if q.dim() != 4 or q.shape[2] != 1 or not q.is_contiguous():
-        raise RuntimeError("pq_decode_attn: q must be contiguous (bs, nh, 1, d)")
-    if (k_res.shape != v_res.shape or k_res.stride() != v_res.stride() or k_res.stride(3) != 1
-            or k_res.stride(2) != k_res.shape[3]):
-        raise RuntimeError("pq_decode_attn: residual buffers must share shape/strides with dense rows")
+    _check_q_window("pq_decode_attn", q, k_res, v_res)
     nh_k = k_res.shape[1]
     k_paged, v_paged = k_page_ids is not None, v_page_ids is not None
     n_pages_cap, ids64 = 0, False
@@ -700,20 +756,11 @@ def pq_decode_attn(q: torch.Tensor, k_codes: torch.Tensor, v_codes: torch.Tensor
         out = torch.empty_like(q)
     ws = workspace if workspace is not None else attn_workspace(desc, q.device)
     lib = L.load()
-    if k_new is not None:
-        # fused residual-window append: r = valid rows BEFORE the call; the new row becomes row r
+    if k_new is not None:      # a v_new without k_new is the library's to refuse or ignore, as ever
         _need_cuda(k_new, v_new)
-        bs_, nh_ = q.shape[0], q.shape[1]
-        if k_new.shape != (bs_, nh_k, 1, q.shape[3]) or v_new is None or v_new.shape != k_new.shape:
-            raise RuntimeError("pq_decode_attn: k_new / v_new must be (bs, nh_k, 1, d)")
-        if k_new.dtype != torch.float16 or v_new.dtype != torch.float16:
-            raise RuntimeError("pq_decode_attn: k_new / v_new must be fp16")
-        k_new, v_new = k_new.contiguous(), v_new.contiguous()
+        k_new, v_new = _new_rows("pq_decode_attn", q, nh_k, k_new, v_new)
     if return_lse or lse is not None:
-        if lse is None:
-            lse = torch.empty(q.shape[0], q.shape[1], 1, dtype=torch.float32, device=q.device)
-        elif lse.dtype != torch.float32 or tuple(lse.shape) != (q.shape[0], q.shape[1], 1) or not lse.is_contiguous():
-            raise RuntimeError("pq_decode_attn: lse must be contiguous fp32 (bs, nh, 1)")
+        lse = _lse_buffer("pq_decode_attn", q, lse)
         L.check(lib.million_pq_decode_attn_lse(ctypes.byref(desc), q.data_ptr(), _ptr(k_new), _ptr(v_new), _ptr(k_codes),
                                                _ptr(v_codes), _ptr(k_page_ids), _ptr(v_page_ids), k_prep.data_ptr(),
                                                v_prep.data_ptr(), k_res.data_ptr(), v_res.data_ptr(), out.data_ptr(),
@@ -739,8 +786,7 @@ def wide_attn_desc(who, q, k_pool, v_pool, k_cents, v_cents, k_res, v_res, r, n_
     """Every check of a wide decode call that needs no library, and its descriptor.  packed: the pools hold packed pages
     (uint8 (n_pool, packed_page_bytes)); every other check is the same."""
     _need_cuda(q, k_pool, v_pool, k_cents, v_cents, k_res, v_res, page_ids, dev_lengths)
-    if q.dtype != torch.float16 or k_res.dtype != torch.float16 or v_res.dtype != torch.float16:
-        raise RuntimeError(f"{who}: q and residuals must be fp16")
+    _check_fp16_q_window(who, q, k_res, v_res)
     if packed:
         if k_pool.dtype != torch.uint8 or v_pool.dtype != torch.uint8:
             raise RuntimeError(f"{who}: packed pools must be uint8 (uint16 codes: pq_decode_attn_wide)")
@@ -750,11 +796,7 @@ def wide_attn_desc(who, q, k_pool, v_pool, k_cents, v_cents, k_res, v_res, r, n_
         raise RuntimeError(f"{who}: k_cents / v_cents must be the plain fp16 (M, C, d_m) codebooks of one shape")
     if not k_cents.is_contiguous() or not v_cents.is_contiguous():
         raise RuntimeError(f"{who}: codebooks must be contiguous")
-    if q.dim() != 4 or q.shape[2] != 1 or not q.is_contiguous():
-        raise RuntimeError(f"{who}: q must be contiguous (bs, nh, 1, d)")
-    if (k_res.dim() != 4 or k_res.shape != v_res.shape or k_res.stride() != v_res.stride() or k_res.stride(3) != 1
-            or k_res.stride(2) != k_res.shape[3]):
-        raise RuntimeError(f"{who}: residual buffers must share shape/strides with dense rows")
+    _check_q_window(who, q, k_res, v_res, window_4d=True)
     M, C, dm = k_cents.shape
     if M * dm != q.shape[3]:
         raise RuntimeError(f"{who}: codebooks of {M} x {dm} dims for d={q.shape[3]}")
@@ -818,17 +860,10 @@ def _decode_attn_wide_call(who, fmt, q, k_pool, v_pool, k_cents, v_cents, k_res,
     elif out.dtype != torch.float16 or out.numel() != q.numel() or not out.is_contiguous():
         raise RuntimeError(f"{who}: out must be contiguous fp16 of q's size")
     if k_new is not None or v_new is not None:
-        if k_new is None or v_new is None or tuple(k_new.shape) != (q.shape[0], k_res.shape[1], 1, q.shape[3]) or v_new.shape != k_new.shape:
-            raise RuntimeError(f"{who}: k_new / v_new must be (bs, nh_k, 1, d)")
-        if k_new.dtype != torch.float16 or v_new.dtype != torch.float16:
-            raise RuntimeError(f"{who}: k_new / v_new must be fp16")
-        k_new, v_new = k_new.contiguous(), v_new.contiguous()
+        k_new, v_new = _new_rows(who, q, k_res.shape[1], k_new, v_new)
     want_lse = return_lse or lse is not None
     if want_lse:
-        if lse is None:
-            lse = torch.empty(q.shape[0], q.shape[1], 1, dtype=torch.float32, device=q.device)
-        elif lse.dtype != torch.float32 or tuple(lse.shape) != (q.shape[0], q.shape[1], 1) or not lse.is_contiguous():
-            raise RuntimeError(f"{who}: lse must be contiguous fp32 (bs, nh, 1)")
+        lse = _lse_buffer(who, q, lse)
     lib = L.load()
     if workspace is None:
         need = int(getattr(lib, fmt.decode_ws)(ctypes.byref(desc)))

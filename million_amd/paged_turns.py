@@ -8,7 +8,7 @@ as shared_prefix.py serves a frozen prompt.
 The turn logic is the cache's, in one copy: PagedPQCache._extend / _extend_request check the route, the lockstep and the capacity
 before anything is joined or launched, join pending side work of the layer, prefill an empty cache or slot, and otherwise let the
 new rows attend [the codes in the pages; the residual window; themselves, causally] through the op of the cache's format
-(PagedPQCache._chunk_op, ops.CodeFormat) before cache._store() leaves the cache as prefill() of the whole sequence would.  The
+(ops.CodeFormat.chunk_op) before cache._store() leaves the cache as prefill() of the whole sequence would.  The
 cache's public methods are those bodies behind the refusal of wide caches; the two functions here are those bodies without it,
 and so mean, word for word, what PagedPQCache.extend / extend_request mean on an 8-bit cache.  A packed cache never sees a uint16
 copy of its pool.

@@ -21,7 +21,6 @@ row in the fallback (:888), the nested try/except fallbacks.
 """
 from __future__ import annotations
 
-import functools
 import heapq
 from typing import Dict, List, Optional, Set
 
@@ -228,22 +227,10 @@ class _CacheBase:
             return ops.prefill_attn(q, k, v, causal=True, dev_spans=dev_spans, return_lse=True)
         return ops.prefill_attn(q, k, v, causal=True, dev_spans=dev_spans)
 
-    # self._fmt: the ops.CodeFormat of the cache's code stores, picked once by __init__
-    def _attn_cents(self):
-        """The codebook operands of the format's attention ops: the prepared blobs, or the codebooks as they are."""
-        return (self._kprep, self._vprep) if self._fmt.prepared else (self.key_cent, self.value_cent)
-
-    def _chunk_op(self, who, route):
-        """The chunk-attention op of an extend call, for the cache's format.  route None / "chunk": chunk attention over the codes
-        (ops.pq_chunk_attn, pq_chunk_attn_wide, pq_chunk_attn_packed); "blocks": the block route (ops.pq_chunk_attn_blocks: the
-        past dequantised block by block into a bounded scratch and attended by the prompt kernel - for long chunks,
-        profiles/chunk_blocks.txt), which picks the format from the code dtype and so is told packed=True where that cannot.
-        The ops are looked up here, when the call is made.  A route that does not exist is a ValueError."""
-        if route is None or route == "chunk":
-            return getattr(ops, self._fmt.op_chunk_attn)
-        if route == "blocks":
-            return ops.pq_chunk_attn_blocks if self._fmt.rowmajor else functools.partial(ops.pq_chunk_attn_blocks, packed=True)
-        raise ValueError(f"{who}: route={route!r} (None, 'chunk' or 'blocks')")
+    # self._fmt: the ops.CodeFormat of the cache's code stores, picked once by __init__.  Its jobs (encode_pages,
+    # decode_workspace, decode_pages, chunk_op) take both forms of the codebooks and use the one their op takes
+    def _cents(self):
+        return (self.key_cent, self.value_cent), (self._kprep, self._vprep)
 
 
 class DynamicPQCache(_CacheBase):
@@ -371,8 +358,8 @@ class DynamicPQCache(_CacheBase):
         whole sequence would have - the window rows and then the new rows are encoded behind T, the window is empty.
         On an empty cache this is prefill().  nbits 9 .. 12: the same over the uint16 store and the codebooks as they are
         (million_pq_chunk_attn_wide); nbits 13 .. 16 have no chunk kernel.  route="blocks": the attention by
-        blocks through the prompt kernel (_chunk_op) - at nbits 9 .. 12 too - followed by the same store."""
-        attend = self._chunk_op("extend", route)
+        blocks through the prompt kernel (CodeFormat.chunk_op) - at nbits 9 .. 12 too - followed by the same store."""
+        attend = self._fmt.chunk_op("extend", route)
         if self.nbits > 12:
             raise NotImplementedError(f"extend: nbits={self.nbits}: the chunk-attention kernels read uint8 codes (nbits <= 8) or "
                                       "uint16 codes of nbits 9 .. 12")
@@ -382,7 +369,7 @@ class DynamicPQCache(_CacheBase):
         n = key_states.size(2)
         kres, vres = self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx]
         out = attend(query_states, key_states, value_states, self._k_store[layer_idx], self._v_store[layer_idx],
-                     *self._attn_cents(), kres, vres, r, M=self.M, C=self.C, n_tokens=T)
+                     *self._cents(), kres, vres, r, M=self.M, C=self.C, n_tokens=T)
         if T + r + n > self.max_tokens:
             raise RuntimeError(f"DynamicPQCache: {T + r + n} tokens exceed max_tokens={self.max_tokens}")
         if r:
@@ -673,10 +660,8 @@ class PagedPQCache(_CacheBase):
         self._reserve(layer_idx, n, b)
         kw = dict(token_start=T, n=n, page_ids=self.page_ids[layer_idx][sel], page_size=self.page_size,
                   x_row_start=x_row_start, x_row_mod=x_row_mod)
-        encode = getattr(ops, self._fmt.op_encode)
-        prep = lambda p: {"prepared": p} if self._fmt.op_encode == "pq_encode_into" else {}      # that op's keyword: the packed encoder has no such image
-        encode(K, self.key_cent, self.key_page_pool, layout=L.MILLION_CODES_KPAGES, **prep(self._kprep), **kw)
-        encode(V, self.value_cent, self.value_page_pool, layout=L.MILLION_CODES_VPAGES, **prep(self._vprep), **kw)
+        self._fmt.encode_pages(K, self.key_cent, self._kprep, self.key_page_pool, layout=L.MILLION_CODES_KPAGES, **kw)
+        self._fmt.encode_pages(V, self.value_cent, self._vprep, self.value_page_pool, layout=L.MILLION_CODES_VPAGES, **kw)
 
     def _store(self, K, V, layer_idx, n, b=None, all_rows=False):
         """The store step under every prefill / extend form, for request b (None: every request, in lockstep): the window
@@ -800,14 +785,14 @@ class PagedPQCache(_CacheBase):
 
     def _extend_slot(self, attend, query_states, key_states, value_states, layer_idx, b, return_lse=False, all_rows=False):
         """b = None: every request (lockstep); else request b with batch-1 tensors.  attend: the attention op of the cache's
-        format and the call's route (_chunk_op); its (out, lse) goes into the sink merge and the store follows, whichever it is.
+        format and the call's route (ops.CodeFormat.chunk_op); its (out, lse) goes into the sink merge and the store follows, whichever it is.
         return_lse: (out, lse) of that op; all_rows: every device row of the layer is rewritten, as prefill_request does.  The
         callers checked the capacity."""
         i, sel = (0, slice(None)) if b is None else (b, slice(b, b + 1))
         T, r, rs = int(self._T_a[layer_idx, i]), int(self._r_a[layer_idx, i]), int(self._rs_a[layer_idx, i])
         ids = self.page_ids[layer_idx][sel]
         sinks = bool(self.sink_tokens)
-        out = attend(query_states, key_states, value_states, self.key_page_pool, self.value_page_pool, *self._attn_cents(),
+        out = attend(query_states, key_states, value_states, self.key_page_pool, self.value_page_pool, *self._cents(),
                      self.key_residual_cache[layer_idx][sel], self.value_residual_cache[layer_idx][sel], r,
                      M=self.M, C=self.C, n_tokens=T, resid_start=rs, k_page_ids=ids, v_page_ids=ids,
                      page_size=self.page_size, **({"return_lse": True} if return_lse or sinks else {}))
@@ -829,7 +814,7 @@ class PagedPQCache(_CacheBase):
         """extend() for a cache of any format: the public method refuses the wide ones first, million_amd.paged_turns serves them
         from here.  Order: a route that does not exist, requests out of lockstep (out_of_step: the caller's words for it, which
         name its own call for one request), the capacity, then the join and the launches."""
-        attend = self._chunk_op(who, route)
+        attend = self._fmt.chunk_op(who, route)
         if not self._lockstep(layer_idx):
             raise RuntimeError(out_of_step)
         empty = self._T_a[layer_idx, 0] == 0 and self._r_a[layer_idx, 0] == 0 and not self._sink_a[layer_idx].any()
@@ -843,7 +828,7 @@ class PagedPQCache(_CacheBase):
         """extend_request() for a cache of any format, as _extend.  An empty slot is prefill_request() - with return_lse, which the
         prompt kernel has not, chunk attention over the chunk alone (every device row rewritten, as prefill_request does) -
         whatever `route` says."""
-        attend = self._chunk_op(who, route)
+        attend = self._fmt.chunk_op(who, route)
         if key_states.size(0) != 1 or query_states.size(0) != 1:
             raise RuntimeError(f"{who}: tensors of batch 1")
         empty = self._T_a[layer_idx, b] == 0 and self._r_a[layer_idx, b] == 0 and not self._sink_a[layer_idx, b]
@@ -852,7 +837,7 @@ class PagedPQCache(_CacheBase):
         if empty and not return_lse:
             return self.prefill_request(b, query_states, key_states, value_states, layer_idx)
         if empty:
-            return self._extend_slot(self._chunk_op(who, None), query_states, key_states, value_states, layer_idx, b, return_lse=True, all_rows=True)
+            return self._extend_slot(self._fmt.chunk_op(who, None), query_states, key_states, value_states, layer_idx, b, return_lse=True, all_rows=True)
         return self._extend_slot(attend, query_states, key_states, value_states, layer_idx, b, return_lse=return_lse)
 
     def extend(self, query_states, key_states, value_states, layer_idx, route=None):
@@ -1414,10 +1399,8 @@ class PagedPQCache(_CacheBase):
             raise RuntimeError("PagedPQCache: requests at different lengths need use_dev_lengths=True")
         r, rs = int(self._r_a[layer_idx, 0]), int(self._rs_a[layer_idx, 0])
         dl = self.lengths[layer_idx] if use_dev_lengths else None
-        fmt, ids = self._fmt, self.page_ids[layer_idx]
         if self._ws is None:      # one workspace per cache (calls of one cache are stream-ordered)
-            need = getattr(ops, fmt.op_decode_ws)(query_states, self.key_residual_cache[layer_idx], M=self.M, C=self.C,
-                                                  **({"nh_k": self.num_key_value_heads} if fmt.op_decode_ws == "decode_workspace_bytes" else {"page_size": self.page_size}))
+            need = self._fmt.decode_workspace(query_states, self.key_residual_cache[layer_idx], M=self.M, C=self.C, page_size=self.page_size)
             self._ws = torch.zeros(need, dtype=torch.uint8, device=self.device)
         self._note_appended(layer_idx)
         self._dev_rows_stale |= not use_dev_lengths
@@ -1428,13 +1411,11 @@ class PagedPQCache(_CacheBase):
             lse = self._sink_lse
         # append (:377-380) + attention (:386) in ONE launch: the new row is attended to and parked in the window.  The format's op:
         # pq_decode_attn, or the same launch over uint16 codes or packed pages with the codebooks as they are (csrc/attn_wide.hip)
-        res = getattr(ops, fmt.op_decode_attn)(
-            query_states, self.key_page_pool, self.value_page_pool, *self._attn_cents(),
-            self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx], r, k_new=key_states, v_new=value_states,
-            n_tokens=self.max_tokens if use_dev_lengths else int(self._T_a[layer_idx, 0]), resid_start=rs, page_size=self.page_size,
-            out=out, dev_lengths=dl, workspace=self._ws,
-            # pq_decode_attn serves row-major sides behind a blob without a shape: a table per side, M and C said; the ops over pools take one table
-            **({"M": self.M, "C": self.C, "k_page_ids": ids, "v_page_ids": ids} if fmt.op_decode_attn == "pq_decode_attn" else {"page_ids": ids}),
+        res = self._fmt.decode_pages(
+            query_states, self.key_page_pool, self.value_page_pool, *self._cents(),
+            self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx], r, M=self.M, C=self.C, page_ids=self.page_ids[layer_idx],
+            k_new=key_states, v_new=value_states, n_tokens=self.max_tokens if use_dev_lengths else int(self._T_a[layer_idx, 0]),
+            resid_start=rs, page_size=self.page_size, out=out, dev_lengths=dl, workspace=self._ws,
             **({"return_lse": True, "lse": lse} if return_lse or lse is not None else {}))
         if self.sink_tokens:      # the count is read on the device: a captured step follows release and a new prompt
             self._sink_merge(layer_idx, query_states, res[0].view(query_states.shape), res[1])

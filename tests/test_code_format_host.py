@@ -1,6 +1,8 @@
 """The code-format table of million_amd/ops.py, without a GPU: ops.code_format returns the instance each public op
 documents for what it is handed, refuses the mismatches the ops refuse, with their messages, and every C entry the table names is
 one that _lib.SYMBOLS prototypes."""
+import dataclasses
+
 import pytest
 import torch
 
@@ -67,9 +69,37 @@ def test_every_entry_of_the_table_is_prototyped():
     for f in ops.CODE_FORMATS:
         for field in ("encode", "decode_attn", "decode_ws", "chunk_attn", "chunk_attn_lse", "chunk_ws", "gather"):
             assert getattr(f, field) in L.SYMBOLS, (f.name, field)
-        for field in ("op_encode", "op_decode_attn", "op_decode_ws", "op_chunk_attn"):
+        for field in ("op_decode_attn", "op_chunk_attn"):
             assert callable(getattr(ops, getattr(f, field))), (f.name, field)
+        for job in ("encode_pages", "decode_workspace", "decode_pages", "chunk_op"):      # what a paged cache asks of its format
+            assert callable(getattr(f, job)), (f.name, job)
+    assert not [x.name for x in dataclasses.fields(ops.CodeFormat) if x.name.startswith("op_") and x.name not in ("op_decode_attn", "op_chunk_attn")]
     # one entry per format where the formats differ, one shared entry where they do not
     assert len({f.decode_attn for f in ops.CODE_FORMATS}) == len({f.chunk_attn for f in ops.CODE_FORMATS}) == 3
     assert ops.FMT_U8.gather == ops.FMT_U16.gather != ops.FMT_PACKED.gather and ops.FMT_U8.encode == ops.FMT_U16.encode != ops.FMT_PACKED.encode
     assert ops.FMT_U8.chunk_attn != ops.FMT_U8.chunk_attn_lse and all(f.chunk_attn == f.chunk_attn_lse for f in (ops.FMT_U16, ops.FMT_PACKED))
+
+
+def test_the_jobs_hand_each_op_its_own_keywords(monkeypatch):
+    """One call shape per job from the cache's side; the format adds what its op takes, and finds the op when it is called."""
+    log = []
+    for name in ("pq_encode_into", "pq_encode_into_packed", "pq_decode_attn", "pq_decode_attn_wide", "pq_decode_attn_packed", "pq_chunk_attn",
+                 "pq_chunk_attn_wide", "pq_chunk_attn_packed", "pq_chunk_attn_blocks", "decode_workspace_bytes", "decode_wide_workspace_bytes"):
+        monkeypatch.setattr(ops, name, lambda *a, _n=name, **k: log.append((_n, a, k)))
+    cents, prep, res = ("kc", "vc"), ("kp", "vp"), torch.zeros(1, 2, 8, 128)
+    for f, enc, dec, chunk in ((ops.FMT_U8, "pq_encode_into", "pq_decode_attn", "pq_chunk_attn"), (ops.FMT_U16, "pq_encode_into", "pq_decode_attn_wide", "pq_chunk_attn_wide"),
+                               (ops.FMT_PACKED, "pq_encode_into_packed", "pq_decode_attn_packed", "pq_chunk_attn_packed")):
+        del log[:]
+        f.encode_pages("X", "cent", "img", "pool", layout=1, n=3)
+        assert log[-1] == (enc, ("X", "cent", "pool"), dict(layout=1, n=3, **({"prepared": "img"} if f.rowmajor else {})))
+        f.decode_workspace("q", res, M=64, C=256, page_size=32)
+        assert log[-1] == (("decode_workspace_bytes", ("q", res), dict(nh_k=2, M=64, C=256)) if f.prepared else
+                           ("decode_wide_workspace_bytes", ("q", res), dict(M=64, C=256, page_size=32)))
+        f.decode_pages("q", "kpool", "vpool", cents, prep, "kres", "vres", 5, M=64, C=256, page_ids="ids", n_tokens=7, k_new="row")
+        said = dict(M=64, C=256, k_page_ids="ids", v_page_ids="ids") if f.prepared else dict(page_ids="ids")
+        assert log[-1] == (dec, ("q", "kpool", "vpool", *(prep if f.prepared else cents), "kres", "vres", 5), dict(n_tokens=7, k_new="row", **said))
+        for route, op, extra in ((None, chunk, {}), ("chunk", chunk, {}), ("blocks", "pq_chunk_attn_blocks", {} if f.rowmajor else {"packed": True})):
+            f.chunk_op("who", route)("q", "k", "v", "kpool", "vpool", cents, prep, "kres", "vres", 5, M=64, n_tokens=7)
+            assert log[-1] == (op, ("q", "k", "v", "kpool", "vpool", *(prep if f.prepared else cents), "kres", "vres", 5), dict(M=64, n_tokens=7, **extra))
+        with pytest.raises(ValueError, match=r"who: route='rows' \(None, 'chunk' or 'blocks'\)"):
+            f.chunk_op("who", "rows")
