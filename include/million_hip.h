@@ -172,6 +172,52 @@ int million_pq_store_ragged(const million_store_ragged_desc *desc, const void *k
                             int32_t *dev_lengths /* (bs, 4), advanced */, const int32_t *dev_n /* (bs,) */,
                             million_stream_t stream);
 
+/* The window flush of a cache with 9 .. 12-bit codes (C in 512 .. 4096), for uint16 pages and - packed != 0 - packed pages
+ * ("Packed code pages" below): million_pq_flush's arguments and meaning, one encode launch for both sides.
+ * desc describes the K side as for million_pq_flush (X = k_rows (bs, nh_k, resid_cap, d), the V window of the same shape and
+ * strides; dst_layout = MILLION_CODES_KPAGES; x_row_mod = resid_cap; n <= page_size rows).  The oldest n rows of every request's
+ * K and V ring window - rows (start + t) % resid_cap, t < n - become tokens [T, T + n) of its K pages (page_size, M) and
+ * transposed V pages (M, page_size) through the one page table page_ids (bs, nh_k, n_pages_cap) int32.  k_cents / v_cents are the
+ * plain (M, C, d_m) fp16 codebooks (wide formats have no prepared image; desc->cents_prepared is not read).  Codes are those of
+ * million_pq_encode / million_pq_encode_packed, bit for bit (same arithmetic contract).
+ * dev_lengths NULL (then desc->dev_lengths too): T = desc->dst_token_start and start = desc->x_row_start for every request - the
+ * lockstep, host-length form; both are checked against the table and the ring (MILLION_ERR_ARG), min_r is not read, nothing is
+ * advanced.  dev_lengths (bs, 4) (must equal desc->dev_lengths): every request's row {T, r, start, word 3} is read on the device
+ * and not trusted - T clamped into [0, n_pages_cap * page_size], r into [0, resid_cap], a start outside [0, resid_cap) reads as
+ * 0 - and everything below uses the clamped values.  A request with r < min_r takes no part: nothing of it is read beyond the row,
+ * nothing of it is written, its row stays as it is (pass resid_cap: only full windows flush; 0: every request).  A destination
+ * token whose page index is >= n_pages_cap drops its store; page ids are read only for pages that receive a token.  The rows of
+ * the requests that took part then advance: T <- min(T + n, n_pages_cap * page_size), r <- max(r - n, 0), start <- (start + n) %
+ * resid_cap; word 3 is neither read nor written (there is no ticket).
+ * Never read: window rows outside [start, start + n) of the ring, any row of a request that takes no part, page-table entries of
+ * pages that receive no token.  Never written: pool bytes outside the destination tokens (every byte written belongs to one
+ * token; all stores are plain vector stores), the windows, the page table.
+ * Shapes: d = 128 or 64 with d / M in {2, 4}, C in {512, 1024, 2048, 4096}, page_size 32 / 64 / 128, n <= page_size,
+ * bs * nh_k <= 32767 (packed: 4 | M); anything else: MILLION_ERR_SHAPE.  Null rows / codebooks / pools / page ids with n > 0:
+ * MILLION_ERR_ARG.  Rows, codebooks and pools 16-byte aligned, strides multiples of 8 elements: MILLION_ERR_ALIGN.  n = 0 returns
+ * MILLION_OK whatever the pointers.
+ * Capture: one encode launch on `stream` (ceil(n / 64) token blocks x M / 4 subspace groups x bs * nh_k x 2 sides, 16 waves per
+ * workgroup, 40 KiB of LDS) and, with dev_lengths, one thread per request for the advance; stream order is the only ordering.
+ * The call allocates nothing, synchronises nothing and is a pure function of its arguments: a captured call follows dev_lengths,
+ * the rows and the page table as they are when it is replayed. */
+int million_pq_flush_wide(const million_encode_desc *desc, const void *k_rows, const void *v_rows,
+                          const void *k_cents, const void *v_cents, void *k_pool, void *v_pool,
+                          const int32_t *page_ids, int32_t *dev_lengths, int resid_cap, int min_r, int packed,
+                          million_stream_t stream);
+
+/* million_pq_store_ragged over uint16 pages and - packed != 0 - packed pages: the same descriptor, meaning, clamps, grid rule and
+ * two launches (the advance kernel is the same), with plain (M, C, d_m) fp16 codebooks in place of the prepared ones and C in
+ * {512, 1024, 2048, 4096}.  What is read, what may hold anything and is never read, and what is never written are as stated there;
+ * codes are those of million_pq_encode / million_pq_encode_packed, bit for bit.  Shapes: d = 128 or 64 with d / M in {2, 4}
+ * (packed: 4 | M), page_size 32 / 64 / 128, bs * nh_k <= 32767: MILLION_ERR_SHAPE otherwise; nulls MILLION_ERR_ARG, alignment
+ * MILLION_ERR_ALIGN, n_bound = 0 MILLION_OK, capture behaviour as million_pq_store_ragged. */
+int million_pq_store_ragged_wide(const million_store_ragged_desc *desc, const void *k_new, const void *v_new,
+                                 const void *k_resid, const void *v_resid,
+                                 const void *k_cents, const void *v_cents,   /* (M, C, d_m) fp16 */
+                                 void *k_pool, void *v_pool, const int32_t *page_ids,
+                                 int32_t *dev_lengths /* (bs, 4), advanced */, const int32_t *dev_n /* (bs,) */,
+                                 int packed, million_stream_t stream);
+
 /* Fork a request of a paged cache: ONE call (one launch) makes n_dst batch slots a copy of slot `src`, for every layer.
  * Serves one long prompt with several questions or sampled continuations: the prompt is encoded once; the other requests
  * share its code pages (SHARE) or get a private copy of them (COPY), and each gets the window and the lengths row.

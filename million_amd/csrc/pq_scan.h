@@ -1,5 +1,6 @@
 // pq_scan.h — the nearest-centroid scan of the PQ encoder kernels: pq_encode_kernel and pq_encode_small_kernel (encode.hip),
-// kmeans_assign_kernel (train.hip), paged_store_kernel (paged_store.h: the ragged store and the window commit).  The scan is written here and nowhere else,
+// kmeans_assign_kernel (train.hip), paged_store_kernel (paged_store.h: the ragged store and the window commit), store_ragged_wide_kernel
+// (store_ragged.hip), pq_flush_wide_kernel (flush_wide.hip: pq_scan_lds_chunk).  The scan is written here and nowhere else,
 // with one exception: pq_flush_kernel (encode.hip) carries pq_scan_lds's loop in its own body (see there).
 //
 // Arithmetic contract (bit-exact with oracle/pq_oracle.c:pq_encode_direct): e = x - c, sq = e * e,
@@ -68,6 +69,26 @@ __device__ __forceinline__ void pq_scan_lds(const float *x, const float *rows, i
             acc = (k == 0) ? sq : acc + sq;
         }
         best_c = acc < best ? c : best_c;
+        best = fminf(best, acc);
+    }
+}
+
+// LDS form over a staged chunk: `rows` holds the n centroids [c_base, c_base + n) of one subspace as fp32 [i][DM] (a part of the
+// row that a wave widened from fp16 into LDS: pq_flush_wide_kernel, flush_wide.hip), read with wave-uniform ds_reads; centroid
+// i of the chunk is index c_base + i.  Same operations and the same strict '<' as the forms above, so chunks scanned in centroid
+// order over one running (best, best_c) give the codes of a scan of the whole range.
+template <int DM, int UNROLL>
+__device__ __forceinline__ void pq_scan_lds_chunk(const float *x, const float *rows, int n, int c_base, float &best, int &best_c) {
+#pragma unroll UNROLL
+    for (int i = 0; i < n; ++i) {
+        float acc = 0.f;
+#pragma unroll
+        for (int k = 0; k < DM; ++k) {
+            const float e = x[k] - rows[i * DM + k];
+            const float sq = e * e;
+            acc = (k == 0) ? sq : acc + sq;
+        }
+        best_c = acc < best ? c_base + i : best_c;
         best = fminf(best, acc);
     }
 }

@@ -233,6 +233,8 @@ class CodeFormat:
     chunk_attn_lse: str                # with it: one entry with an lse argument that may be null, except for 8-bit codes
     chunk_ws: str
     gather: str
+    flush: str                         # the one-launch window flush, and
+    store_ragged: str                  # the one-launch ragged store, into its pages
     # the attention ops of this module over its stores, looked up by name when called (the methods below)
     op_decode_attn: str
     op_chunk_attn: str
@@ -271,25 +273,44 @@ class CodeFormat:
         return lambda q, k_chunk, v_chunk, k_codes, v_codes, cents, prepared, *window, **kw: globals()[name](
             q, k_chunk, v_chunk, k_codes, v_codes, *(prepared if self.prepared else cents), *window, **said, **kw)
 
+    def flush_pages(self, k_rows, v_rows, cents, k_pool, v_pool, page_ids, **kw):
+        """The oldest n rows of the ring windows into pages, one encode launch (kw: pq_flush's n, page_size, token_start, x_row_start,
+        dev_lengths, min_r): pq_flush for 8-bit codes, pq_flush_wide - told whether the pages are packed - for the wide formats.  Both
+        take the codebooks as they are."""
+        if self.prepared:
+            return pq_flush(k_rows, v_rows, *cents, k_pool, v_pool, page_ids, **kw)
+        return pq_flush_wide(k_rows, v_rows, *cents, k_pool, v_pool, page_ids, packed=not self.rowmajor, **kw)
+
+    def store_ragged_pages(self, k_new, v_new, k_res, v_res, cents, prepared, k_pool, v_pool, page_ids, dev_lengths, dev_n, **kw):
+        """The store step of a ragged batch in one call (kw: M, C, page_size): pq_store_ragged over the prepared codebooks, or
+        pq_store_ragged_wide over the codebooks as they are."""
+        if self.prepared:
+            return pq_store_ragged(k_new, v_new, k_res, v_res, *prepared, k_pool, v_pool, page_ids, dev_lengths, dev_n, **kw)
+        return pq_store_ragged_wide(k_new, v_new, k_res, v_res, *cents, k_pool, v_pool, page_ids, dev_lengths, dev_n,
+                                    packed=not self.rowmajor, **kw)
+
 
 FMT_U8 = CodeFormat(
     "uint8", range(1, 257), torch.uint8, rowmajor=True, code_bytes=1, prepared=True, page_shapes=_word_page_shapes,
     check_store=_check_word_store,
     encode="million_pq_encode", decode_attn="million_pq_decode_attn", decode_ws="million_attn_workspace_bytes",
     chunk_attn="million_pq_chunk_attn", chunk_attn_lse="million_pq_chunk_attn_lse", chunk_ws="million_chunk_attn_workspace_bytes",
-    gather="million_pq_gather_rows", op_decode_attn="pq_decode_attn", op_chunk_attn="pq_chunk_attn")
+    gather="million_pq_gather_rows", flush="million_pq_flush_layers", store_ragged="million_pq_store_ragged",
+    op_decode_attn="pq_decode_attn", op_chunk_attn="pq_chunk_attn")
 FMT_U16 = CodeFormat(
     "uint16", WIDE_CENTROIDS, torch.uint16, rowmajor=True, code_bytes=2, prepared=False, page_shapes=_word_page_shapes,
     check_store=_check_word_store,
     encode="million_pq_encode", decode_attn="million_pq_decode_attn_wide", decode_ws="million_attn_wide_workspace_bytes",
     chunk_attn="million_pq_chunk_attn_wide", chunk_attn_lse="million_pq_chunk_attn_wide", chunk_ws="million_chunk_attn_wide_workspace_bytes",
-    gather="million_pq_gather_rows", op_decode_attn="pq_decode_attn_wide", op_chunk_attn="pq_chunk_attn_wide")
+    gather="million_pq_gather_rows", flush="million_pq_flush_wide", store_ragged="million_pq_store_ragged_wide",
+    op_decode_attn="pq_decode_attn_wide", op_chunk_attn="pq_chunk_attn_wide")
 FMT_PACKED = CodeFormat(
     "packed", WIDE_CENTROIDS, torch.uint8, rowmajor=False, code_bytes=2, prepared=False, page_shapes=_packed_page_shapes,
     check_store=_check_packed_store,
     encode="million_pq_encode_packed", decode_attn="million_pq_decode_attn_packed", decode_ws="million_attn_wide_workspace_bytes",
     chunk_attn="million_pq_chunk_attn_packed", chunk_attn_lse="million_pq_chunk_attn_packed", chunk_ws="million_chunk_attn_wide_workspace_bytes",
-    gather="million_pq_gather_rows_packed", op_decode_attn="pq_decode_attn_packed", op_chunk_attn="pq_chunk_attn_packed")
+    gather="million_pq_gather_rows_packed", flush="million_pq_flush_wide", store_ragged="million_pq_store_ragged_wide",
+    op_decode_attn="pq_decode_attn_packed", op_chunk_attn="pq_chunk_attn_packed")
 CODE_FORMATS = (FMT_U8, FMT_U16, FMT_PACKED)
 
 
@@ -445,6 +466,111 @@ def pq_store_ragged(k_new: torch.Tensor, v_new: torch.Tensor, k_res: Optional[to
                                              page_ids.data_ptr(), dev_lengths.data_ptr(), dev_n.data_ptr(), _stream()),
             "million_pq_store_ragged")
     _vshadow_drop(v_pool)
+
+
+def _check_wide_pools(who, k_cents, v_cents, k_pool, v_pool, page_size, bs, nh_k, d, packed):
+    """The codebooks and the two pools of a wide flush or ragged store -> (fmt, M, C): the format by code_format (the pools' dtype,
+    C, the packed flag), each pool by the format's check_store and its page shape."""
+    if k_cents.dtype != torch.float16 or v_cents.dtype != torch.float16 or k_cents.dim() != 3 or v_cents.shape != k_cents.shape:
+        raise RuntimeError(f"{who}: k_cents / v_cents must be fp16 (M, C, d_m) of one shape (the codebooks as they are: wide codes have no prepared image)")
+    M, C, dm = k_cents.shape
+    if M * dm != d:
+        raise RuntimeError(f"{who}: codebooks of M={M}, d_m={dm} do not go with rows of d={d}")
+    if C not in WIDE_CENTROIDS:
+        raise RuntimeError(f"{who}: C={C} (codes of {WIDE_CENTROIDS} centroids; C <= 256 takes {who.replace('_wide', '')})")
+    if k_pool.dtype != v_pool.dtype:
+        raise RuntimeError(f"{who}: codes must be uint8 or uint16, both sides alike")
+    if not packed and k_pool.dtype == torch.uint8:
+        raise RuntimeError(f"{who}: uint8 pools hold 8-bit codes, which take {who.replace('_wide', '')} (packed pools: packed=True)")
+    fmt = code_format(who, k_pool.dtype, C, packed)
+    shapes = fmt.page_shapes(page_size, M, C)
+    for name, pool, shape in (("k_pool", k_pool, shapes[0]), ("v_pool", v_pool, shapes[1])):
+        fmt.check_store(who, name, pool, True, page_size, bs, nh_k, M, C, None)
+        if tuple(pool.shape[1:]) != tuple(shape):
+            raise RuntimeError(f"{who}: {name} must be (n_pool, {', '.join(map(str, shape))}) for page_size={page_size}, M={M}")
+    return fmt, M, C
+
+
+def pq_flush_wide(k_rows: torch.Tensor, v_rows: torch.Tensor, k_cents: torch.Tensor, v_cents: torch.Tensor,
+                  k_pool: torch.Tensor, v_pool: torch.Tensor, page_ids: torch.Tensor, *, n: int, page_size: int,
+                  token_start: int = 0, x_row_start: int = 0, dev_lengths: Optional[torch.Tensor] = None, min_r: int = 0,
+                  packed: bool = False) -> None:
+    """pq_flush for codes of 512 .. 4096 centroids (million_pq_flush_wide): the oldest n <= page_size rows of the K and V windows
+    (bs, nh_k, cap, d) become tokens [T, T + n) of uint16 pages - K (n_pool, page_size, M), V (n_pool, M, page_size) - or, packed=True,
+    of packed pages (uint8 (n_pool, packed_page_bytes)), in one encode launch; the codes are pq_encode_into's / pq_encode_into_packed's
+    bit for bit.  dev_lengths (bs, 4) int32: every request's {T, r, start} is read on the device (clamped), requests with r < min_r
+    take no part, the rows of the others advance there (a second, one-thread-per-request launch; word 3 untouched).  None:
+    token_start / x_row_start for every request, nothing advances."""
+    who = "pq_flush_wide"
+    _need_cuda(k_rows, v_rows, k_cents, v_cents, k_pool, v_pool, page_ids, dev_lengths)
+    if k_rows.shape != v_rows.shape or k_rows.stride() != v_rows.stride() or k_rows.dtype != torch.float16 or v_rows.dtype != torch.float16:
+        raise RuntimeError(f"{who}: K and V windows must be fp16 with the same shape and strides")
+    if k_rows.dim() != 4 or k_rows.stride(3) != 1:
+        raise RuntimeError(f"{who}: windows must be (bs, nh_k, cap, d) with a contiguous last dim")
+    bs, nhk, cap, d = k_rows.shape
+    k_cents, v_cents = k_cents.contiguous(), v_cents.contiguous()
+    fmt, M, C = _check_wide_pools(who, k_cents, v_cents, k_pool, v_pool, page_size, bs, nhk, d, packed)
+    if page_ids.dtype != torch.int32 or not page_ids.is_contiguous() or page_ids.dim() != 3 or page_ids.shape[:2] != (bs, nhk):
+        raise RuntimeError(f"{who}: contiguous int32 page_ids (bs, nh_k, n_pages_cap) expected")
+    if dev_lengths is not None and (dev_lengths.dtype != torch.int32 or dev_lengths.shape != (bs, 4) or not dev_lengths.is_contiguous()):
+        raise RuntimeError(f"{who}: dev_lengths must be contiguous int32 (bs, 4)")
+    if not 0 <= n <= page_size:
+        raise RuntimeError(f"{who}: n={n} outside [0, page_size={page_size}]")
+    desc = _encode_desc(k_rows, k_cents, n, L.MILLION_CODES_KPAGES, token_start, x_row_start, cap, dev_lengths)
+    desc.page_size, desc.n_pages_cap = page_size, page_ids.shape[2]
+    L.check(getattr(L.load(), fmt.flush)(ctypes.byref(desc), k_rows.data_ptr(), v_rows.data_ptr(), k_cents.data_ptr(), v_cents.data_ptr(),
+                                         k_pool.data_ptr(), v_pool.data_ptr(), page_ids.data_ptr(), _ptr(dev_lengths), cap,
+                                         min_r if dev_lengths is not None else 0, int(bool(packed)), _stream()), fmt.flush)
+
+
+def pq_store_ragged_wide(k_new: torch.Tensor, v_new: torch.Tensor, k_res: Optional[torch.Tensor], v_res: Optional[torch.Tensor],
+                         k_cents: torch.Tensor, v_cents: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
+                         page_ids: torch.Tensor, dev_lengths: torch.Tensor, dev_n: torch.Tensor, *, M: int, C: int, page_size: int,
+                         packed: bool = False, n_bound: Optional[int] = None) -> None:
+    """pq_store_ragged for codes of 512 .. 4096 centroids (million_pq_store_ragged_wide): the same call - every request's window
+    rows in ring order and then its first dev_n[b] new rows behind its T_b tokens, its row of dev_lengths advanced on the device -
+    into uint16 pages or, packed=True, packed pages, with the codebooks as they are (fp16 (M, C, d_m)) in place of the prepared
+    ones.  Codes are pq_encode_into's / pq_encode_into_packed's bit for bit."""
+    who = "pq_store_ragged_wide"
+    _need_cuda(k_new, v_new, k_res, v_res, k_cents, v_cents, k_pool, v_pool, page_ids, dev_lengths, dev_n)
+    if k_new.dtype != torch.float16 or v_new.dtype != torch.float16:
+        raise RuntimeError(f"{who}: new rows must be fp16")
+    if k_new.dim() != 4 or k_new.stride(3) != 1 or v_new.shape != k_new.shape or v_new.stride(3) != 1:
+        raise RuntimeError(f"{who}: k_new / v_new must be (bs, nh_k, n, d) of one shape with a contiguous last dim")
+    bs, nhk, n_rows, d = k_new.shape
+    n_bound = n_rows if n_bound is None else int(n_bound)
+    if n_bound < 0 or n_bound > n_rows:
+        raise RuntimeError(f"{who}: n_bound={n_bound} outside [0, {n_rows}]")
+    if (k_res is None) != (v_res is None):
+        raise RuntimeError(f"{who}: K and V windows go together")
+    cap = 0
+    if k_res is not None:
+        if (k_res.dtype != torch.float16 or v_res.dtype != torch.float16 or k_res.dim() != 4 or k_res.shape != v_res.shape
+                or k_res.stride() != v_res.stride() or k_res.shape[:2] != (bs, nhk) or k_res.shape[3] != d
+                or k_res.stride(3) != 1 or k_res.stride(2) != d):
+            raise RuntimeError(f"{who}: windows must be fp16 (bs, nh_k, cap, d) with dense rows, K and V alike")
+        cap = k_res.shape[2]
+    k_cents, v_cents = k_cents.contiguous(), v_cents.contiguous()
+    fmt, M_c, C_c = _check_wide_pools(who, k_cents, v_cents, k_pool, v_pool, page_size, bs, nhk, d, packed)
+    if (M_c, C_c) != (M, C):
+        raise RuntimeError(f"{who}: M={M}, C={C} said, codebooks of M={M_c}, C={C_c}")
+    if page_ids.dtype != torch.int32 or not page_ids.is_contiguous() or page_ids.dim() != 3 or page_ids.shape[:2] != (bs, nhk):
+        raise RuntimeError(f"{who}: contiguous int32 page_ids (bs, nh_k, n_pages_cap) expected")
+    if dev_lengths.dtype != torch.int32 or dev_lengths.shape != (bs, 4) or not dev_lengths.is_contiguous():
+        raise RuntimeError(f"{who}: dev_lengths must be contiguous int32 (bs, 4)")
+    _check_dev_n(who, dev_n, bs)
+    desc = L.StoreRaggedDesc()
+    desc.struct_size = ctypes.sizeof(L.StoreRaggedDesc)
+    desc.bs, desc.nh_k, desc.d, desc.M, desc.C, desc.n_bound = bs, nhk, d, M, C, n_bound
+    desc.kn_stride_b, desc.kn_stride_h, desc.kn_stride_n = k_new.stride(0), k_new.stride(1), k_new.stride(2)
+    desc.vn_stride_b, desc.vn_stride_h, desc.vn_stride_n = v_new.stride(0), v_new.stride(1), v_new.stride(2)
+    desc.resid_cap, desc.page_size, desc.n_pages_cap = cap, page_size, page_ids.shape[2]
+    if k_res is not None:
+        desc.resid_stride_b, desc.resid_stride_h = k_res.stride(0), k_res.stride(1)
+    L.check(getattr(L.load(), fmt.store_ragged)(ctypes.byref(desc), k_new.data_ptr(), v_new.data_ptr(), _ptr(k_res), _ptr(v_res),
+                                                k_cents.data_ptr(), v_cents.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(),
+                                                page_ids.data_ptr(), dev_lengths.data_ptr(), dev_n.data_ptr(), int(bool(packed)), _stream()),
+            fmt.store_ragged)
 
 
 def cache_fork(page_ids: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_res: torch.Tensor, v_res: torch.Tensor,

@@ -17,7 +17,20 @@ copy of its pool.
     None / "chunk"   ops.pq_chunk_attn_packed                ops.pq_chunk_attn_wide
     "blocks"         ops.pq_chunk_attn_blocks(packed=True)   ops.pq_chunk_attn_blocks
 
-extend_ragged, prefill_ragged, fork, swap, verify / commit and sinks on wide caches stay refused by the cache."""
+Requests at different lengths.  The cache's own flush of a wide cache is two encode launches that take T and the
+ring start from the host, so it serves lockstep batches only, and its ragged calls are refused.  The functions below open the
+ragged life the same way - the bodies are the cache's (PagedPQCache._flush_ragged, _prefill_ragged, _extend_ragged), the launches
+the format's (ops.CodeFormat.flush_pages, store_ragged_pages, chunk_op):
+
+    call             packed cache                                   unpacked cache
+    flush / decode   ops.pq_flush_wide(packed=True)                 ops.pq_flush_wide
+    prefill_ragged   ops.prefill_attn(dev_spans=), then the store   the same
+    extend_ragged    ops.pq_chunk_attn_packed(dev_lengths=, dev_n_q=)   ops.pq_chunk_attn_wide(dev_lengths=, dev_n_q=)
+    device_store     ops.pq_store_ragged_wide(packed=True)          ops.pq_store_ragged_wide
+
+The cache's own methods keep doing on a wide cache exactly what they did: decoding_with_pages / flush_to_pages flush in lockstep
+only, prefill_ragged / extend_ragged raise NotImplementedError.  Encode-ahead (begin_step reports 'plain' / 'flush' only), fork,
+swap, verify / commit, sinks and SharedPrefix on wide caches stay refused by the cache."""
 from __future__ import annotations
 
 
@@ -39,3 +52,46 @@ def extend_request(cache, b, query_states, key_states, value_states, layer_idx, 
     if cache.nbits <= 8:
         return cache.extend_request(b, query_states, key_states, value_states, layer_idx, return_lse=return_lse, route=route)
     return cache._extend_request("paged_turns.extend_request", b, query_states, key_states, value_states, layer_idx, return_lse, route)
+
+
+def flush(cache, layer_idx, use_dev_lengths=False):
+    """PagedPQCache.flush_to_pages for a cache with nbits 9 .. 12 (packed or not), requests at different lengths included: the
+    8-bit rule word for word - lockstep with host lengths flushes at r >= page_size, with device lengths only the full windows
+    flush (the launch reads every request's row and skips the others), requests at different lengths need use_dev_lengths=True -
+    in one encode launch (ops.pq_flush_wide) plus, with device lengths, its one-thread-per-request advance.  A cache with
+    nbits = 8 is handed to its own method."""
+    if cache.nbits <= 8:
+        return cache.flush_to_pages(layer_idx, use_dev_lengths=use_dev_lengths)
+    return cache._flush_ragged(layer_idx, use_dev_lengths)
+
+
+def decode(cache, query_states, key_states, value_states, layer_idx, out=None, use_dev_lengths=False, return_lse=False, lse=None):
+    """PagedPQCache.decoding_with_pages for a cache with nbits 9 .. 12 (packed or not) whose requests may be at different
+    lengths: the full windows are flushed here first (flush() above), so none is full when the cache's own method runs - its
+    flush does nothing and the step is its unchanged fused launch.  Captured, a step is one graph per step kind
+    (cache.next_step_kind(): 'plain' / 'flush'), as for 8-bit caches: the flush launch of a captured 'flush' step is gated on the
+    device (min_r), so its replays follow the rows.  A cache with nbits = 8 is handed to its own method."""
+    if cache.nbits > 8 and (cache._r_a[layer_idx] >= cache.extended_residual_size).any():
+        cache._flush_ragged(layer_idx, use_dev_lengths)
+    return cache.decoding_with_pages(query_states, key_states, value_states, layer_idx, out=out, use_dev_lengths=use_dev_lengths,
+                                     return_lse=return_lse, lse=lse)
+
+
+def prefill_ragged(cache, query_states, key_states, value_states, layer_idx, n_new, device_store=False, return_lse=False):
+    """PagedPQCache.prefill_ragged for a cache with nbits 9 .. 12 (packed or not): the prompts of several empty slots, of
+    different lengths, in ONE attention launch; every slot with n_new[b] > 0 is left as cache.prefill_request(b, ...) with its
+    own rows leaves it.  device_store=True: the stores are ONE ops.pq_store_ragged_wide call behind the attention launch - same
+    pages, same codes, same lengths.  A cache with nbits = 8 is handed to its own method."""
+    if cache.nbits <= 8:
+        return cache.prefill_ragged(query_states, key_states, value_states, layer_idx, n_new, device_store=device_store, return_lse=return_lse)
+    return cache._prefill_ragged("paged_turns.prefill_ragged", query_states, key_states, value_states, layer_idx, n_new, device_store, return_lse)
+
+
+def extend_ragged(cache, query_states, key_states, value_states, layer_idx, n_new, device_store=False):
+    """PagedPQCache.extend_ragged for a cache with nbits 9 .. 12 (packed or not): extend_request() for every slot in ONE
+    attention launch (ops.pq_chunk_attn_wide / ops.pq_chunk_attn_packed with dev_lengths= / dev_n_q=); every slot with
+    n_new[b] > 0 is left as extend_request(cache, b, ...) above leaves it, the others are not touched.  device_store=True: the
+    stores are ONE ops.pq_store_ragged_wide call.  A cache with nbits = 8 is handed to its own method."""
+    if cache.nbits <= 8:
+        return cache.extend_ragged(query_states, key_states, value_states, layer_idx, n_new, device_store=device_store)
+    return cache._extend_ragged("paged_turns.extend_ragged", query_states, key_states, value_states, layer_idx, n_new, device_store)

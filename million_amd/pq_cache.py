@@ -448,7 +448,9 @@ class PagedPQCache(_CacheBase):
     `nbits` 9 .. 12 with `dtype=torch.uint16` (uint16 pools, codebooks of 2**nbits centroids): the core life - prefill,
     prefill_request, decoding_with_pages (ops.pq_decode_attn_wide), the in-line flush of requests in lockstep, release, cleanup -
     and NotImplementedError naming nbits for the rest (extend*, prefill_ragged, fork, swap, verify / commit, update, sinks).
-    DESIGN.md 4.14.  extend / extend_request of such a cache, packed or not: million_amd.paged_turns.
+    DESIGN.md 4.14.  extend / extend_request of such a cache, packed or not: million_amd.paged_turns.  Requests at
+    different lengths - a flush that reads every request's lengths on the device, prefill_ragged, extend_ragged -: million_amd.paged_turns
+    too (flush, decode, prefill_ragged, extend_ragged); the methods here keep the lockstep flush and the refusals.
 
     `packed=True` (nbits 9 .. 12 only; nbits = 8: ValueError): the same cache over packed pools - uint8 (n_pool,
     ops.packed_page_bytes), 10 bits per code at nbits 9 / 10 and 12 at nbits 11 / 12 instead of 16 (include/million_hip.h,
@@ -693,14 +695,15 @@ class PagedPQCache(_CacheBase):
                 self._reserve(layer_idx, int(self._r_a[layer_idx, b]) + n_new[b], b)
 
     def _store_ragged(self, K, V, layer_idx, n_new, dev_n):
-        """_store() for every slot with n_new[b] > 0 in ONE call (ops.pq_store_ragged): the windows in ring order and the
+        """_store() for every slot with n_new[b] > 0 in ONE call (the ragged store of the cache's format: ops.pq_store_ragged,
+        ops.pq_store_ragged_wide): the windows in ring order and the
         first n_new[b] rows of K, V (bs, nh_k, n, d) behind each T_b, every per-slot value read from `lengths[layer_idx]` and
         dev_n on the device, the device rows advanced there - no _sync_lengths.  The slots' pages were reserved before the
         attention launch (_reserve_ragged); the mirror moves through the same owners as _store."""
         who = [b for b in range(self.bs) if n_new[b] > 0]
-        ops.pq_store_ragged(K, V, self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx], self._kprep, self._vprep,
-                            self.key_page_pool, self.value_page_pool, self.page_ids[layer_idx], self.lengths[layer_idx], dev_n,
-                            M=self.M, C=self.C, page_size=self.page_size)
+        self._fmt.store_ragged_pages(K, V, self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx], *self._cents(),
+                                     self.key_page_pool, self.value_page_pool, self.page_ids[layer_idx], self.lengths[layer_idx], dev_n,
+                                     M=self.M, C=self.C, page_size=self.page_size)
         for b in who:
             sel = slice(b, b + 1)
             self._note_window_emptied(layer_idx, sel)
@@ -736,19 +739,25 @@ class PagedPQCache(_CacheBase):
         (an int32 device copy of n_new beside `lengths[layer_idx]`): same pages, same codes, same host and device lengths.
         return_lse: (out, lse), lse fp32 (bs, nh, n); -inf in the rows past n_new[b]."""
         self._no_wide("prefill_ragged")
+        return self._prefill_ragged("prefill_ragged", query_states, key_states, value_states, layer_idx, n_new, device_store, return_lse)
+
+    def _prefill_ragged(self, who_, query_states, key_states, value_states, layer_idx, n_new, device_store, return_lse):
+        """prefill_ragged() for a cache of any format, as _extend: the public method refuses the wide ones first,
+        million_amd.paged_turns serves them from here (who_: the caller's name in the messages).  The prompt kernel never sees
+        codes; the store is the format's (_store: encode_pages; _store_ragged: store_ragged_pages)."""
         n_new = [int(x) for x in n_new]
         n = query_states.size(2)
         if (len(n_new) != self.bs or query_states.size(0) != self.bs or key_states.size(0) != self.bs or key_states.size(2) != n
                 or value_states.shape != key_states.shape):
-            raise RuntimeError(f"prefill_ragged: tensors of batch {self.bs}, padded to the same rows, and one n_new per slot")
+            raise RuntimeError(f"{who_}: tensors of batch {self.bs}, padded to the same rows, and one n_new per slot")
         if any(x < 0 or x > n for x in n_new):
-            raise RuntimeError(f"prefill_ragged: n_new outside [0, {n}]")
+            raise RuntimeError(f"{who_}: n_new outside [0, {n}]")
         who = [b for b in range(self.bs) if n_new[b] > 0]
         if device_store:
-            self._no_sinks("prefill_ragged(device_store=True)")
+            self._no_sinks(f"{who_}(device_store=True)")
         for b in who:      # every slot's precondition and capacity before anything is launched
             if self._T_a[layer_idx, b] or self._r_a[layer_idx, b] or self._sink_a[layer_idx, b]:
-                raise RuntimeError(f"prefill_ragged: slot {b} holds tokens (release it first, or use extend_ragged)")
+                raise RuntimeError(f"{who_}: slot {b} holds tokens (release it first, or use extend_ragged)")
             if n_new[b] > self.max_tokens:
                 raise RuntimeError(f"PagedPQCache: {n_new[b]} tokens exceed max_tokens={self.max_tokens}")
         if device_store:
@@ -875,14 +884,21 @@ class PagedPQCache(_CacheBase):
         ops.pq_store_ragged call behind the attention launch, on the same `lengths[layer_idx]` and device copy of n_new - same
         pages, same codes, same host and device lengths; the device rows are advanced by the call, not written from the host."""
         self._no_wide("extend_ragged")
+        return self._extend_ragged("extend_ragged", query_states, key_states, value_states, layer_idx, n_new, device_store)
+
+    def _extend_ragged(self, who_, query_states, key_states, value_states, layer_idx, n_new, device_store):
+        """extend_ragged() for a cache of any format, as _extend: the public method refuses the wide ones first,
+        million_amd.paged_turns serves them from here (who_: the caller's name in the messages).  The attention is the chunk op
+        of the cache's format (ops.CodeFormat.chunk_op) with dev_lengths / dev_n_q, the store the format's."""
+        attend = self._fmt.chunk_op(who_, None)
         n_new = [int(x) for x in n_new]
         n_q = query_states.size(2)
         if len(n_new) != self.bs or query_states.size(0) != self.bs or key_states.size(0) != self.bs or key_states.size(2) != n_q:
-            raise RuntimeError(f"extend_ragged: tensors of batch {self.bs} and one n_new per slot")
+            raise RuntimeError(f"{who_}: tensors of batch {self.bs} and one n_new per slot")
         if any(n < 0 or n > n_q for n in n_new):
-            raise RuntimeError(f"extend_ragged: n_new outside [0, {n_q}]")
+            raise RuntimeError(f"{who_}: n_new outside [0, {n_q}]")
         if device_store:
-            self._no_sinks("extend_ragged(device_store=True)")
+            self._no_sinks(f"{who_}(device_store=True)")
         who = [b for b in range(self.bs) if n_new[b] > 0]
         for b in who:      # capacity of every slot before anything is launched
             tot = int(self._T_a[layer_idx, b] + self._r_a[layer_idx, b]) + n_new[b]
@@ -896,10 +912,10 @@ class PagedPQCache(_CacheBase):
         kres, vres = self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx]
         dev_n = torch.tensor(n_new, dtype=torch.int32).to(self.device)
         bound = int(self._T_a[layer_idx].max())
-        out = ops.pq_chunk_attn(query_states, key_states, value_states, self.key_page_pool, self.value_page_pool, self._kprep,
-                                self._vprep, kres, vres, 0, M=self.M, C=self.C, n_tokens=bound, k_page_ids=ids, v_page_ids=ids,
-                                page_size=self.page_size, dev_lengths=self.lengths[layer_idx], dev_n_q=dev_n,
-                                **({"return_lse": True} if self.sink_tokens else {}))
+        out = attend(query_states, key_states, value_states, self.key_page_pool, self.value_page_pool, *self._cents(),
+                     kres, vres, 0, M=self.M, C=self.C, n_tokens=bound, k_page_ids=ids, v_page_ids=ids,
+                     page_size=self.page_size, dev_lengths=self.lengths[layer_idx], dev_n_q=dev_n,
+                     **({"return_lse": True} if self.sink_tokens else {}))
         if self.sink_tokens:      # before the stores, as _extend_slot
             out, lse = out
             self._sink_merge(layer_idx, query_states, out, lse, dev_n=dev_n)
@@ -1222,6 +1238,30 @@ class PagedPQCache(_CacheBase):
                      n=ps, page_size=ps, token_start=int(self._T_a[layer_idx, 0]), x_row_start=int(self._rs_a[layer_idx, 0]),
                      dev_lengths=self.lengths[layer_idx] if use_dev_lengths else None,
                      min_r=cap if use_dev_lengths else 0)      # device lengths: only full windows flush (a captured step serves ragged batches too)
+        self._dev_rows_stale |= not use_dev_lengths
+        self._note_flushed(layer_idx if lock else (layer_idx, full))
+
+    def _flush_ragged(self, layer_idx, use_dev_lengths):
+        """flush_to_pages' 8-bit rule for a cache of any format, in one encode launch of the format (ops.CodeFormat.flush_pages:
+        ops.pq_flush, ops.pq_flush_wide): million_amd.paged_turns flushes wide caches through it, requests at different lengths
+        included; flush_to_pages itself keeps the lockstep-only _flush_wide for them.  Lockstep with host lengths flushes at
+        r >= page_size, with device lengths only full windows flush (min_r = cap); pages are reserved per flushing request."""
+        cap, ps = self.extended_residual_size, self.page_size
+        full = self._r_a[layer_idx] >= cap
+        lock = self._lockstep(layer_idx)
+        if lock and self._r_a[layer_idx, 0] < (cap if use_dev_lengths else ps):
+            return
+        if not lock and not full.any():
+            return
+        if not lock and not use_dev_lengths:
+            raise RuntimeError("PagedPQCache: requests at different lengths need use_dev_lengths=True")
+        for b in (None,) if lock else np.flatnonzero(full):
+            self._reserve(layer_idx, ps, b)
+        self._fmt.flush_pages(self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx], self._cents()[0],
+                              self.key_page_pool, self.value_page_pool, self.page_ids[layer_idx],
+                              n=ps, page_size=ps, token_start=int(self._T_a[layer_idx, 0]), x_row_start=int(self._rs_a[layer_idx, 0]),
+                              dev_lengths=self.lengths[layer_idx] if use_dev_lengths else None,
+                              min_r=cap if use_dev_lengths else 0)
         self._dev_rows_stale |= not use_dev_lengths
         self._note_flushed(layer_idx if lock else (layer_idx, full))
 
