@@ -19,7 +19,7 @@
 // Roofline: pure vector ALU.  32K tokens x 8 kv heads x 64 subspaces x 256 centroids = 4.3e9 tests per layer and
 // side; at 6 instructions per test and one 64-lane instruction per 4 cycles per SIMD (1024 SIMDs, ~2.4 GHz:
 // 39e12 lane-instructions/s) the floor is ~0.66 ms; HBM traffic (67 MB in, 17 MB out) is two orders below that.
-#include "common.h"
+#include "code_pages.h"
 #include "pq_scan.h"
 
 #pragma clang fp contract(off)
@@ -73,33 +73,13 @@ __global__ __launch_bounds__(kEncBlock) void pq_encode_kernel(EncParams p) {
     if (tok0 < 0 || (p.layout != MILLION_CODES_ROWMAJOR && tok0 > p.n_pages_cap * p.page_size - 1 - t)) return;
     const int tok = tok0 + t;
     if constexpr (PACKED) {
-        // the lane's 4 subspaces of one token: 4 low bytes, and one whole byte (2 high bits per code) or two (4 high bits) of
-        // the high plane - every byte written belongs to this token alone
-        const int hb = packed_hi_bits(p.C);
+        // the lane's 4 subspaces of one token (4 | M: no partial group)
         const long long pid = p.page_ids[(long long)bh * p.n_pages_cap + tok / p.page_size];
-        const int off = tok % p.page_size;
         uint8_t *page = p.dst + pid * packed_page_bytes(p.page_size, p.M, p.C);      // 64-bit (no power of two: a multiply)
-        uint8_t *hi_plane = page + p.page_size * p.M;
-        unsigned c4[kEncSub], lo = 0, hi = 0;
+        unsigned c4[kEncSub];
 #pragma unroll
-        for (int j = 0; j < kEncSub; ++j) {
-            c4[j] = (unsigned)(codes >> (kCB * j)) & 0xffffu;
-            lo |= (c4[j] & 0xffu) << (8 * j);
-            hi |= ((c4[j] >> 8) & ((1u << hb) - 1u)) << (hb * j);
-        }
-        if (p.layout == MILLION_CODES_KPAGES) {
-            *(unsigned *)(page + off * p.M + m0) = lo;
-            if (hb == 2) hi_plane[off * (p.M / 4) + m0 / 4] = (uint8_t)hi;
-            else *(unsigned short *)(hi_plane + off * (p.M / 2) + m0 / 2) = (unsigned short)hi;
-        } else {
-#pragma unroll
-            for (int j = 0; j < kEncSub; ++j) page[(m0 + j) * p.page_size + off] = (uint8_t)c4[j];
-            if (hb == 2) hi_plane[(m0 / 4) * p.page_size + off] = (uint8_t)hi;
-            else {
-                hi_plane[(m0 / 2) * p.page_size + off] = (uint8_t)hi;
-                hi_plane[(m0 / 2 + 1) * p.page_size + off] = (uint8_t)(hi >> 8);
-            }
-        }
+        for (int j = 0; j < kEncSub; ++j) c4[j] = (unsigned)(codes >> (kCB * j)) & 0xffffu;
+        store_codes4_packed(page, tok % p.page_size, m0, c4, p.layout != MILLION_CODES_KPAGES, p.page_size, p.M, packed_hi_bits(p.C));
         return;
     }
     CodeT *dst = (CodeT *)p.dst;      // strides dsb / dsh are in bytes
@@ -470,25 +450,11 @@ __global__ __launch_bounds__(256) void repack_pages_kernel(const uint8_t *__rest
         uint8_t *pw = const_cast<uint8_t *>(ppage);
         unsigned short *uw = const_cast<unsigned short *>(upage);
         const long long hi0 = (long long)page_size * M;
-        unsigned c4[4];
         if constexpr (!UNPACK) {
-            unsigned lo = 0, hi = 0;
+            unsigned c4[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                c4[j] = VSIDE ? upage[(m0 + j) * page_size + t] : upage[t * M + m0 + j];
-                lo |= (c4[j] & 0xffu) << (8 * j);
-                hi |= ((c4[j] >> 8) & hmask) << (hb * j);
-            }
-            if constexpr (VSIDE) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) pw[(m0 + j) * page_size + t] = (uint8_t)c4[j];
-                pw[hi0 + (m0 * hb / 8) * page_size + t] = (uint8_t)hi;
-                if (hb == 4) pw[hi0 + (m0 / 2 + 1) * page_size + t] = (uint8_t)(hi >> 8);
-            } else {
-                *(unsigned *)(pw + t * M + m0) = lo;
-                pw[hi0 + t * (M * hb / 8) + m0 * hb / 8] = (uint8_t)hi;
-                if (hb == 4) pw[hi0 + t * (M / 2) + m0 / 2 + 1] = (uint8_t)(hi >> 8);
-            }
+            for (int j = 0; j < 4; ++j) c4[j] = VSIDE ? upage[(m0 + j) * page_size + t] : upage[t * M + m0 + j];
+            store_codes4_packed(pw, t, m0, c4, VSIDE, page_size, M, hb);
         } else {
             unsigned hi;
             if constexpr (VSIDE) {

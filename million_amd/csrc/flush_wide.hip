@@ -11,9 +11,8 @@
 // Mapping.  A workgroup = (block of 64 tokens, side, kv head, group of 4 consecutive subspaces), 16 waves: wave = (subspace of
 // the group, quarter of the centroid range), lane = token.  The four subspaces of a token meet in one workgroup because a packed
 // page keeps the high bits of 4 (hb = 2) or 2 (hb = 4) consecutive subspaces of a token in one byte: wave 0 gathers the 16
-// candidates of its token through LDS and stores as pq_encode_kernel's lane does (one 64-bit store of 4 uint16 codes on K
-// pages, 16-bit lane-contiguous rows on V pages; packed: one 32-bit low store plus one byte or one 16-bit high store, byte rows
-// on V pages) - every byte written belongs to one token, all stores are plain vector stores.
+// candidates of its token through LDS and stores them with store_codes4_wide (code_pages.h), as every writer of wide pages does
+// - every byte written belongs to one token, all stores are plain vector stores.
 // A wave never scans more than C / 4 centroids, and it never reads the fp16 row through the scalar cache: it stages its quarter
 // chunk by chunk (128 centroids: one 8- or 16-byte vector load per lane, issued one chunk ahead, widened to fp32 by all 64 lanes
 // at once) in 2 KiB of LDS of its own and reads it back with wave-uniform (broadcast) ds_reads - pq_scan_lds_chunk (pq_scan.h):
@@ -24,7 +23,7 @@
 // table, and every workgroup of a request that takes no part, leaves before its first vector load and before any barrier.
 // Codes are those of million_pq_encode / million_pq_encode_packed bit for bit: the same IEEE operations in the same order per
 // (row, centroid), strict '<' over increasing c within a quarter, quarters combined in centroid order.
-#include "common.h"
+#include "code_pages.h"
 #include "pq_scan.h"
 
 #pragma clang fp contract(off)
@@ -130,45 +129,7 @@ __global__ __launch_bounds__(kFwWaves * 64) void pq_flush_wide_kernel(FlushWideP
         }
         c4[j] = (unsigned)bc;
     }
-    const int off = tok & (p.page_size - 1);
-    uint8_t *pool = vside ? p.v_pool : p.k_pool;
-    if (!p.packed) {
-        uint16_t *dst = (uint16_t *)pool;
-        if (!vside) {
-            // K page (page_size, M): the token's 4 codes are one aligned 64-bit store (M and m0 are multiples of 4)
-            const unsigned long long codes = (unsigned long long)c4[0] | (unsigned long long)c4[1] << 16 | (unsigned long long)c4[2] << 32 |
-                                             (unsigned long long)c4[3] << 48;
-            *(unsigned long long *)(dst + (pid * p.page_size + off) * p.M + m0) = codes;
-        } else {
-            // transposed V page (M, page_size): four lane-contiguous 16-bit rows
-#pragma unroll
-            for (int j = 0; j < kFwSub; ++j) dst[(pid * p.M + m0 + j) * p.page_size + off] = (uint16_t)c4[j];
-        }
-        return;
-    }
-    // packed page: 4 low bytes, and one whole byte (2 high bits per code) or two (4 high bits) of the high plane
-    const int hb = packed_hi_bits(p.C);
-    uint8_t *pg = pool + pid * packed_page_bytes(p.page_size, p.M, p.C);
-    uint8_t *hi_plane = pg + p.page_size * p.M;
-    unsigned lo = 0, hi = 0;
-#pragma unroll
-    for (int j = 0; j < kFwSub; ++j) {
-        lo |= (c4[j] & 0xffu) << (8 * j);
-        hi |= ((c4[j] >> 8) & ((1u << hb) - 1u)) << (hb * j);
-    }
-    if (!vside) {
-        *(unsigned *)(pg + off * p.M + m0) = lo;
-        if (hb == 2) hi_plane[off * (p.M / 4) + m0 / 4] = (uint8_t)hi;
-        else *(unsigned short *)(hi_plane + off * (p.M / 2) + m0 / 2) = (unsigned short)hi;
-    } else {
-#pragma unroll
-        for (int j = 0; j < kFwSub; ++j) pg[(m0 + j) * p.page_size + off] = (uint8_t)c4[j];
-        if (hb == 2) hi_plane[(m0 / 4) * p.page_size + off] = (uint8_t)hi;
-        else {
-            hi_plane[(m0 / 2) * p.page_size + off] = (uint8_t)hi;
-            hi_plane[(m0 / 2 + 1) * p.page_size + off] = (uint8_t)(hi >> 8);
-        }
-    }
+    store_codes4_wide(vside ? p.v_pool : p.k_pool, pid, tok & (p.page_size - 1), m0, c4, vside, p.page_size, p.M, p.C, p.packed);
 }
 
 // One thread per request, after the encode launch on the same stream: the rows of the requests that flushed (the same clamped

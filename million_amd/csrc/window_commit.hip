@@ -34,6 +34,7 @@ constexpr int kWcMaxRows = 16;      // new rows per request, at most
 struct WindowCommitParams {
     static constexpr bool kCommit = true;
     static constexpr bool kRows = false;
+    static constexpr bool kWide = false;
     const f16 *k_new, *v_new;       // (layers, bs, nh_k, n_bound, d)
     f16 *k_win, *v_win;             // (layers, bs, nh_k, rcap, d), each layer contiguous
     const float *k_cents32, *v_cents32;

@@ -368,6 +368,26 @@ def pq_encode(X: torch.Tensor, cents: torch.Tensor) -> torch.Tensor:
     return codes
 
 
+def _check_flush_windows(who, k_rows, v_rows):
+    """The K and V ring windows of a flush -> (bs, nh_k, cap, d)."""
+    if k_rows.shape != v_rows.shape or k_rows.stride() != v_rows.stride() or k_rows.dtype != torch.float16 or v_rows.dtype != torch.float16:
+        raise RuntimeError(f"{who}: K and V windows must be fp16 with the same shape and strides")
+    if k_rows.dim() != 4 or k_rows.stride(3) != 1:
+        raise RuntimeError(f"{who}: windows must be (bs, nh_k, cap, d) with a contiguous last dim")
+    return k_rows.shape
+
+
+def _check_table(who, page_ids, bs, nh_k):
+    """The one page table of a flush or ragged store (pq_flush words its own, together with its pools)."""
+    if page_ids.dtype != torch.int32 or not page_ids.is_contiguous() or page_ids.dim() != 3 or page_ids.shape[:2] != (bs, nh_k):
+        raise RuntimeError(f"{who}: contiguous int32 page_ids (bs, nh_k, n_pages_cap) expected")
+
+
+def _check_dev_lengths(who, dev_lengths, bs):
+    if dev_lengths.dtype != torch.int32 or dev_lengths.shape != (bs, 4) or not dev_lengths.is_contiguous():
+        raise RuntimeError(f"{who}: dev_lengths must be contiguous int32 (bs, 4)")
+
+
 def pq_flush(k_rows: torch.Tensor, v_rows: torch.Tensor, k_cents: torch.Tensor, v_cents: torch.Tensor,
              k_pool: torch.Tensor, v_pool: torch.Tensor, page_ids: torch.Tensor, *, n: int, page_size: int,
              token_start: int = 0, x_row_start: int = 0, dev_lengths: Optional[torch.Tensor] = None, min_r: int = 0,
@@ -390,14 +410,10 @@ def pq_flush(k_rows: torch.Tensor, v_rows: torch.Tensor, k_cents: torch.Tensor, 
         n_layers, x_ls, ids_ls = k_rows.shape[0], k_rows.stride(0), page_ids.stride(0)
         len_ls = dev_lengths.stride(0) if dev_lengths is not None else 0
         k_rows, v_rows, page_ids = k_rows[0], v_rows[0], page_ids[0]
-    if k_rows.shape != v_rows.shape or k_rows.stride() != v_rows.stride() or k_rows.dtype != torch.float16 or v_rows.dtype != torch.float16:
-        raise RuntimeError("pq_flush: K and V windows must be fp16 with the same shape and strides")
-    if k_rows.dim() != 4 or k_rows.stride(3) != 1:
-        raise RuntimeError("pq_flush: windows must be (bs, nh_k, cap, d) with a contiguous last dim")
+    bs, nhk, cap, d = _check_flush_windows("pq_flush", k_rows, v_rows)
     if page_ids.dtype != torch.int32 or not page_ids.is_contiguous() or not k_pool.is_contiguous() or not v_pool.is_contiguous():
         raise RuntimeError("pq_flush: contiguous pools and contiguous int32 page_ids (bs, nh_k, n_pages_cap) expected")
     k_cents, v_cents = k_cents.contiguous(), v_cents.contiguous()
-    bs, nhk, cap, d = k_rows.shape
     M, C, dm = k_cents.shape
     if v_cents.shape != k_cents.shape or C > 256 or k_pool.dtype != torch.uint8 or v_pool.dtype != torch.uint8:
         raise RuntimeError("pq_flush: uint8 codes, equal codebook shapes")
@@ -415,6 +431,46 @@ def pq_flush(k_rows: torch.Tensor, v_rows: torch.Tensor, k_cents: torch.Tensor, 
                                              n_layers, x_ls, ids_ls, len_ls, int(bool(advance)), _stream()), "million_pq_flush_layers")
 
 
+def _store_ragged(who, k_new, v_new, k_res, v_res, k_pool, v_pool, page_ids, dev_lengths, dev_n, M, C, page_size, n_bound, books,
+                  pools_behind_table=None):
+    """The body of pq_store_ragged and pq_store_ragged_wide: the checks of the new rows, the windows, n_bound, the page table, dev_lengths
+    and dev_n, the descriptor and the call.  What is an op's own is handed in and runs where it always ran: books(bs, nh_k, d) ->
+    (entry, k_cents, v_cents, extra arguments) checks the codebooks (the wide op: and the pools) behind the windows,
+    pools_behind_table() checks pools behind the page table."""
+    if k_new.dim() != 4 or k_new.stride(3) != 1 or v_new.shape != k_new.shape or v_new.stride(3) != 1:
+        raise RuntimeError(f"{who}: k_new / v_new must be (bs, nh_k, n, d) of one shape with a contiguous last dim")
+    bs, nhk, n_rows, d = k_new.shape
+    n_bound = n_rows if n_bound is None else int(n_bound)
+    if n_bound < 0 or n_bound > n_rows:
+        raise RuntimeError(f"{who}: n_bound={n_bound} outside [0, {n_rows}]")
+    if (k_res is None) != (v_res is None):
+        raise RuntimeError(f"{who}: K and V windows go together")
+    cap = 0
+    if k_res is not None:
+        if (k_res.dtype != torch.float16 or v_res.dtype != torch.float16 or k_res.dim() != 4 or k_res.shape != v_res.shape
+                or k_res.stride() != v_res.stride() or k_res.shape[:2] != (bs, nhk) or k_res.shape[3] != d
+                or k_res.stride(3) != 1 or k_res.stride(2) != d):
+            raise RuntimeError(f"{who}: windows must be fp16 (bs, nh_k, cap, d) with dense rows, K and V alike")
+        cap = k_res.shape[2]
+    entry, k_cents, v_cents, extra = books(bs, nhk, d)
+    _check_table(who, page_ids, bs, nhk)
+    if pools_behind_table is not None:
+        pools_behind_table()
+    _check_dev_lengths(who, dev_lengths, bs)
+    _check_dev_n(who, dev_n, bs)
+    desc = L.StoreRaggedDesc()
+    desc.struct_size = ctypes.sizeof(L.StoreRaggedDesc)
+    desc.bs, desc.nh_k, desc.d, desc.M, desc.C, desc.n_bound = bs, nhk, d, M, C, n_bound
+    desc.kn_stride_b, desc.kn_stride_h, desc.kn_stride_n = k_new.stride(0), k_new.stride(1), k_new.stride(2)
+    desc.vn_stride_b, desc.vn_stride_h, desc.vn_stride_n = v_new.stride(0), v_new.stride(1), v_new.stride(2)
+    desc.resid_cap, desc.page_size, desc.n_pages_cap = cap, page_size, page_ids.shape[2]
+    if k_res is not None:
+        desc.resid_stride_b, desc.resid_stride_h = k_res.stride(0), k_res.stride(1)
+    L.check(getattr(L.load(), entry)(ctypes.byref(desc), k_new.data_ptr(), v_new.data_ptr(), _ptr(k_res), _ptr(v_res), k_cents.data_ptr(),
+                                     v_cents.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(), page_ids.data_ptr(), dev_lengths.data_ptr(),
+                                     dev_n.data_ptr(), *extra, _stream()), entry)
+
+
 def pq_store_ragged(k_new: torch.Tensor, v_new: torch.Tensor, k_res: Optional[torch.Tensor], v_res: Optional[torch.Tensor],
                     k_prep: torch.Tensor, v_prep: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor,
                     page_ids: torch.Tensor, dev_lengths: torch.Tensor, dev_n: torch.Tensor, *, M: int, C: int, page_size: int,
@@ -427,44 +483,21 @@ def pq_store_ragged(k_new: torch.Tensor, v_new: torch.Tensor, k_res: Optional[to
     while dev_lengths, dev_n and the rows change.  k_prep / v_prep: the prepared codebooks (prepare_cents).  n_bound: the rows of
     k_new / v_new the grid is sized for (default: all of them); dev_n is clamped into [0, n_bound].  k_res = v_res = None: no
     window (every r reads as 0)."""
+    who = "pq_store_ragged"
     _need_cuda(k_new, v_new, k_res, v_res, k_prep, v_prep, k_pool, v_pool, page_ids, dev_lengths, dev_n)
     if k_new.dtype != torch.float16 or v_new.dtype != torch.float16 or k_pool.dtype != torch.uint8 or v_pool.dtype != torch.uint8:
-        raise RuntimeError("pq_store_ragged: new rows must be fp16, pools uint8")
-    if k_new.dim() != 4 or k_new.stride(3) != 1 or v_new.shape != k_new.shape or v_new.stride(3) != 1:
-        raise RuntimeError("pq_store_ragged: k_new / v_new must be (bs, nh_k, n, d) of one shape with a contiguous last dim")
-    bs, nhk, n_rows, d = k_new.shape
-    n_bound = n_rows if n_bound is None else int(n_bound)
-    if n_bound < 0 or n_bound > n_rows:
-        raise RuntimeError(f"pq_store_ragged: n_bound={n_bound} outside [0, {n_rows}]")
-    if (k_res is None) != (v_res is None):
-        raise RuntimeError("pq_store_ragged: K and V windows go together")
-    cap = 0
-    if k_res is not None:
-        if (k_res.dtype != torch.float16 or v_res.dtype != torch.float16 or k_res.dim() != 4 or k_res.shape != v_res.shape
-                or k_res.stride() != v_res.stride() or k_res.shape[:2] != (bs, nhk) or k_res.shape[3] != d
-                or k_res.stride(3) != 1 or k_res.stride(2) != d):
-            raise RuntimeError("pq_store_ragged: windows must be fp16 (bs, nh_k, cap, d) with dense rows, K and V alike")
-        cap = k_res.shape[2]
-    _check_prepared("pq_store_ragged", k_prep, v_prep, M, C, d)
-    if page_ids.dtype != torch.int32 or not page_ids.is_contiguous() or page_ids.dim() != 3 or page_ids.shape[:2] != (bs, nhk):
-        raise RuntimeError("pq_store_ragged: contiguous int32 page_ids (bs, nh_k, n_pages_cap) expected")
-    if not k_pool.is_contiguous() or not v_pool.is_contiguous():
-        raise RuntimeError("pq_store_ragged: page pools must be contiguous")
-    if dev_lengths.dtype != torch.int32 or dev_lengths.shape != (bs, 4) or not dev_lengths.is_contiguous():
-        raise RuntimeError("pq_store_ragged: dev_lengths must be contiguous int32 (bs, 4)")
-    _check_dev_n("pq_store_ragged", dev_n, bs)
-    desc = L.StoreRaggedDesc()
-    desc.struct_size = ctypes.sizeof(L.StoreRaggedDesc)
-    desc.bs, desc.nh_k, desc.d, desc.M, desc.C, desc.n_bound = bs, nhk, d, M, C, n_bound
-    desc.kn_stride_b, desc.kn_stride_h, desc.kn_stride_n = k_new.stride(0), k_new.stride(1), k_new.stride(2)
-    desc.vn_stride_b, desc.vn_stride_h, desc.vn_stride_n = v_new.stride(0), v_new.stride(1), v_new.stride(2)
-    desc.resid_cap, desc.page_size, desc.n_pages_cap = cap, page_size, page_ids.shape[2]
-    if k_res is not None:
-        desc.resid_stride_b, desc.resid_stride_h = k_res.stride(0), k_res.stride(1)
-    L.check(L.load().million_pq_store_ragged(ctypes.byref(desc), k_new.data_ptr(), v_new.data_ptr(), _ptr(k_res), _ptr(v_res),
-                                             k_prep.data_ptr(), v_prep.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(),
-                                             page_ids.data_ptr(), dev_lengths.data_ptr(), dev_n.data_ptr(), _stream()),
-            "million_pq_store_ragged")
+        raise RuntimeError(f"{who}: new rows must be fp16, pools uint8")
+
+    def books(bs, nh_k, d):
+        _check_prepared(who, k_prep, v_prep, M, C, d)
+        return FMT_U8.store_ragged, k_prep, v_prep, ()
+
+    def pools_behind_table():
+        if not k_pool.is_contiguous() or not v_pool.is_contiguous():
+            raise RuntimeError(f"{who}: page pools must be contiguous")
+
+    _store_ragged(who, k_new, v_new, k_res, v_res, k_pool, v_pool, page_ids, dev_lengths, dev_n, M, C, page_size, n_bound, books,
+                  pools_behind_table)
     _vshadow_drop(v_pool)
 
 
@@ -503,17 +536,12 @@ def pq_flush_wide(k_rows: torch.Tensor, v_rows: torch.Tensor, k_cents: torch.Ten
     token_start / x_row_start for every request, nothing advances."""
     who = "pq_flush_wide"
     _need_cuda(k_rows, v_rows, k_cents, v_cents, k_pool, v_pool, page_ids, dev_lengths)
-    if k_rows.shape != v_rows.shape or k_rows.stride() != v_rows.stride() or k_rows.dtype != torch.float16 or v_rows.dtype != torch.float16:
-        raise RuntimeError(f"{who}: K and V windows must be fp16 with the same shape and strides")
-    if k_rows.dim() != 4 or k_rows.stride(3) != 1:
-        raise RuntimeError(f"{who}: windows must be (bs, nh_k, cap, d) with a contiguous last dim")
-    bs, nhk, cap, d = k_rows.shape
+    bs, nhk, cap, d = _check_flush_windows(who, k_rows, v_rows)
     k_cents, v_cents = k_cents.contiguous(), v_cents.contiguous()
     fmt, M, C = _check_wide_pools(who, k_cents, v_cents, k_pool, v_pool, page_size, bs, nhk, d, packed)
-    if page_ids.dtype != torch.int32 or not page_ids.is_contiguous() or page_ids.dim() != 3 or page_ids.shape[:2] != (bs, nhk):
-        raise RuntimeError(f"{who}: contiguous int32 page_ids (bs, nh_k, n_pages_cap) expected")
-    if dev_lengths is not None and (dev_lengths.dtype != torch.int32 or dev_lengths.shape != (bs, 4) or not dev_lengths.is_contiguous()):
-        raise RuntimeError(f"{who}: dev_lengths must be contiguous int32 (bs, 4)")
+    _check_table(who, page_ids, bs, nhk)
+    if dev_lengths is not None:
+        _check_dev_lengths(who, dev_lengths, bs)
     if not 0 <= n <= page_size:
         raise RuntimeError(f"{who}: n={n} outside [0, page_size={page_size}]")
     desc = _encode_desc(k_rows, k_cents, n, L.MILLION_CODES_KPAGES, token_start, x_row_start, cap, dev_lengths)
@@ -535,42 +563,15 @@ def pq_store_ragged_wide(k_new: torch.Tensor, v_new: torch.Tensor, k_res: Option
     _need_cuda(k_new, v_new, k_res, v_res, k_cents, v_cents, k_pool, v_pool, page_ids, dev_lengths, dev_n)
     if k_new.dtype != torch.float16 or v_new.dtype != torch.float16:
         raise RuntimeError(f"{who}: new rows must be fp16")
-    if k_new.dim() != 4 or k_new.stride(3) != 1 or v_new.shape != k_new.shape or v_new.stride(3) != 1:
-        raise RuntimeError(f"{who}: k_new / v_new must be (bs, nh_k, n, d) of one shape with a contiguous last dim")
-    bs, nhk, n_rows, d = k_new.shape
-    n_bound = n_rows if n_bound is None else int(n_bound)
-    if n_bound < 0 or n_bound > n_rows:
-        raise RuntimeError(f"{who}: n_bound={n_bound} outside [0, {n_rows}]")
-    if (k_res is None) != (v_res is None):
-        raise RuntimeError(f"{who}: K and V windows go together")
-    cap = 0
-    if k_res is not None:
-        if (k_res.dtype != torch.float16 or v_res.dtype != torch.float16 or k_res.dim() != 4 or k_res.shape != v_res.shape
-                or k_res.stride() != v_res.stride() or k_res.shape[:2] != (bs, nhk) or k_res.shape[3] != d
-                or k_res.stride(3) != 1 or k_res.stride(2) != d):
-            raise RuntimeError(f"{who}: windows must be fp16 (bs, nh_k, cap, d) with dense rows, K and V alike")
-        cap = k_res.shape[2]
-    k_cents, v_cents = k_cents.contiguous(), v_cents.contiguous()
-    fmt, M_c, C_c = _check_wide_pools(who, k_cents, v_cents, k_pool, v_pool, page_size, bs, nhk, d, packed)
-    if (M_c, C_c) != (M, C):
-        raise RuntimeError(f"{who}: M={M}, C={C} said, codebooks of M={M_c}, C={C_c}")
-    if page_ids.dtype != torch.int32 or not page_ids.is_contiguous() or page_ids.dim() != 3 or page_ids.shape[:2] != (bs, nhk):
-        raise RuntimeError(f"{who}: contiguous int32 page_ids (bs, nh_k, n_pages_cap) expected")
-    if dev_lengths.dtype != torch.int32 or dev_lengths.shape != (bs, 4) or not dev_lengths.is_contiguous():
-        raise RuntimeError(f"{who}: dev_lengths must be contiguous int32 (bs, 4)")
-    _check_dev_n(who, dev_n, bs)
-    desc = L.StoreRaggedDesc()
-    desc.struct_size = ctypes.sizeof(L.StoreRaggedDesc)
-    desc.bs, desc.nh_k, desc.d, desc.M, desc.C, desc.n_bound = bs, nhk, d, M, C, n_bound
-    desc.kn_stride_b, desc.kn_stride_h, desc.kn_stride_n = k_new.stride(0), k_new.stride(1), k_new.stride(2)
-    desc.vn_stride_b, desc.vn_stride_h, desc.vn_stride_n = v_new.stride(0), v_new.stride(1), v_new.stride(2)
-    desc.resid_cap, desc.page_size, desc.n_pages_cap = cap, page_size, page_ids.shape[2]
-    if k_res is not None:
-        desc.resid_stride_b, desc.resid_stride_h = k_res.stride(0), k_res.stride(1)
-    L.check(getattr(L.load(), fmt.store_ragged)(ctypes.byref(desc), k_new.data_ptr(), v_new.data_ptr(), _ptr(k_res), _ptr(v_res),
-                                                k_cents.data_ptr(), v_cents.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(),
-                                                page_ids.data_ptr(), dev_lengths.data_ptr(), dev_n.data_ptr(), int(bool(packed)), _stream()),
-            fmt.store_ragged)
+
+    def books(bs, nh_k, d):
+        kc, vc = k_cents.contiguous(), v_cents.contiguous()
+        fmt, M_c, C_c = _check_wide_pools(who, kc, vc, k_pool, v_pool, page_size, bs, nh_k, d, packed)
+        if (M_c, C_c) != (M, C):
+            raise RuntimeError(f"{who}: M={M}, C={C} said, codebooks of M={M_c}, C={C_c}")
+        return fmt.store_ragged, kc, vc, (int(bool(packed)),)
+
+    _store_ragged(who, k_new, v_new, k_res, v_res, k_pool, v_pool, page_ids, dev_lengths, dev_n, M, C, page_size, n_bound, books)
 
 
 def cache_fork(page_ids: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_res: torch.Tensor, v_res: torch.Tensor,

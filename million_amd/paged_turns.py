@@ -19,8 +19,8 @@ copy of its pool.
 
 Requests at different lengths.  The cache's own flush of a wide cache is two encode launches that take T and the
 ring start from the host, so it serves lockstep batches only, and its ragged calls are refused.  The functions below open the
-ragged life the same way - the bodies are the cache's (PagedPQCache._flush_ragged, _prefill_ragged, _extend_ragged), the launches
-the format's (ops.CodeFormat.flush_pages, store_ragged_pages, chunk_op):
+ragged life the same way - the bodies are the cache's (PagedPQCache._flush_pages, which is flush_to_pages of an 8-bit cache;
+_prefill_ragged, _extend_ragged), the launches the format's (ops.CodeFormat.flush_pages, store_ragged_pages, chunk_op):
 
     call             packed cache                                   unpacked cache
     flush / decode   ops.pq_flush_wide(packed=True)                 ops.pq_flush_wide
@@ -56,13 +56,14 @@ def extend_request(cache, b, query_states, key_states, value_states, layer_idx, 
 
 def flush(cache, layer_idx, use_dev_lengths=False):
     """PagedPQCache.flush_to_pages for a cache with nbits 9 .. 12 (packed or not), requests at different lengths included: the
-    8-bit rule word for word - lockstep with host lengths flushes at r >= page_size, with device lengths only the full windows
-    flush (the launch reads every request's row and skips the others), requests at different lengths need use_dev_lengths=True -
+    8-bit cache's own body (PagedPQCache._flush_pages) - lockstep with host lengths flushes at r >= page_size, with device lengths
+    only the full windows flush (the launch reads every request's row and skips the others), requests at different lengths need
+    use_dev_lengths=True -
     in one encode launch (ops.pq_flush_wide) plus, with device lengths, its one-thread-per-request advance.  A cache with
     nbits = 8 is handed to its own method."""
     if cache.nbits <= 8:
         return cache.flush_to_pages(layer_idx, use_dev_lengths=use_dev_lengths)
-    return cache._flush_ragged(layer_idx, use_dev_lengths)
+    return cache._flush_pages(layer_idx, use_dev_lengths)
 
 
 def decode(cache, query_states, key_states, value_states, layer_idx, out=None, use_dev_lengths=False, return_lse=False, lse=None):
@@ -72,7 +73,7 @@ def decode(cache, query_states, key_states, value_states, layer_idx, out=None, u
     (cache.next_step_kind(): 'plain' / 'flush'), as for 8-bit caches: the flush launch of a captured 'flush' step is gated on the
     device (min_r), so its replays follow the rows.  A cache with nbits = 8 is handed to its own method."""
     if cache.nbits > 8 and (cache._r_a[layer_idx] >= cache.extended_residual_size).any():
-        cache._flush_ragged(layer_idx, use_dev_lengths)
+        cache._flush_pages(layer_idx, use_dev_lengths)
     return cache.decoding_with_pages(query_states, key_states, value_states, layer_idx, out=out, use_dev_lengths=use_dev_lengths,
                                      return_lse=return_lse, lse=lse)
 

@@ -1217,12 +1217,20 @@ class PagedPQCache(_CacheBase):
         """Encode the oldest page_size residual rows into a new K page and V page and move the window on
         (paged_pq_utils.py:130-210) - ONE launch (million_pq_flush): K encode, V encode and, with device-resident
         lengths, their advance.  Requests at different lengths (recycled slots): only those whose window is full flush -
-        the launch reads every request's lengths on the device and skips the others (min_r)."""
+        the launch reads every request's lengths on the device and skips the others (min_r).  A cache with wider codes keeps
+        the lockstep-only _flush_wide."""
+        if self.nbits > 8:
+            full = self._r_a[layer_idx] >= self.extended_residual_size
+            return self._flush_wide(layer_idx, use_dev_lengths, self._lockstep(layer_idx), full)
+        return self._flush_pages(layer_idx, use_dev_lengths)
+
+    def _flush_pages(self, layer_idx, use_dev_lengths):
+        """The flush in one encode launch of the cache's format (ops.CodeFormat.flush_pages: ops.pq_flush, ops.pq_flush_wide):
+        flush_to_pages of an 8-bit cache, and how million_amd.paged_turns flushes a cache of any format, requests at different
+        lengths included."""
         cap, ps = self.extended_residual_size, self.page_size
         full = self._r_a[layer_idx] >= cap
         lock = self._lockstep(layer_idx)
-        if self.nbits > 8:
-            return self._flush_wide(layer_idx, use_dev_lengths, lock, full)
         # lockstep: the host flushes at r >= page_size, the device (min_r = cap with device lengths) only full windows - the
         # host mirror must not move when the device will not (a direct call with page_size <= r < cap)
         if lock and self._r_a[layer_idx, 0] < (cap if use_dev_lengths else ps):
@@ -1232,36 +1240,12 @@ class PagedPQCache(_CacheBase):
         if not lock and not use_dev_lengths:
             raise RuntimeError("PagedPQCache: requests at different lengths need use_dev_lengths=True")
         for b in (None,) if lock else np.flatnonzero(full):
-            self._reserve(layer_idx, ps, b)
-        ops.pq_flush(self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx], self.key_cent,
-                     self.value_cent, self.key_page_pool, self.value_page_pool, self.page_ids[layer_idx],
-                     n=ps, page_size=ps, token_start=int(self._T_a[layer_idx, 0]), x_row_start=int(self._rs_a[layer_idx, 0]),
-                     dev_lengths=self.lengths[layer_idx] if use_dev_lengths else None,
-                     min_r=cap if use_dev_lengths else 0)      # device lengths: only full windows flush (a captured step serves ragged batches too)
-        self._dev_rows_stale |= not use_dev_lengths
-        self._note_flushed(layer_idx if lock else (layer_idx, full))
-
-    def _flush_ragged(self, layer_idx, use_dev_lengths):
-        """flush_to_pages' 8-bit rule for a cache of any format, in one encode launch of the format (ops.CodeFormat.flush_pages:
-        ops.pq_flush, ops.pq_flush_wide): million_amd.paged_turns flushes wide caches through it, requests at different lengths
-        included; flush_to_pages itself keeps the lockstep-only _flush_wide for them.  Lockstep with host lengths flushes at
-        r >= page_size, with device lengths only full windows flush (min_r = cap); pages are reserved per flushing request."""
-        cap, ps = self.extended_residual_size, self.page_size
-        full = self._r_a[layer_idx] >= cap
-        lock = self._lockstep(layer_idx)
-        if lock and self._r_a[layer_idx, 0] < (cap if use_dev_lengths else ps):
-            return
-        if not lock and not full.any():
-            return
-        if not lock and not use_dev_lengths:
-            raise RuntimeError("PagedPQCache: requests at different lengths need use_dev_lengths=True")
-        for b in (None,) if lock else np.flatnonzero(full):
-            self._reserve(layer_idx, ps, b)
+            self._reserve(layer_idx, ps, b)      # pages are reserved per flushing request
         self._fmt.flush_pages(self.key_residual_cache[layer_idx], self.value_residual_cache[layer_idx], self._cents()[0],
                               self.key_page_pool, self.value_page_pool, self.page_ids[layer_idx],
                               n=ps, page_size=ps, token_start=int(self._T_a[layer_idx, 0]), x_row_start=int(self._rs_a[layer_idx, 0]),
                               dev_lengths=self.lengths[layer_idx] if use_dev_lengths else None,
-                              min_r=cap if use_dev_lengths else 0)
+                              min_r=cap if use_dev_lengths else 0)      # device lengths: only full windows flush (a captured step serves ragged batches too)
         self._dev_rows_stale |= not use_dev_lengths
         self._note_flushed(layer_idx if lock else (layer_idx, full))
 

@@ -208,3 +208,53 @@ def test_store_ragged_wide_untrusted_values_are_clamped(packed, env, oracle):
     t, lengths = _store(torch, ops, sc, plans, rows)
     sc.check_pools(torch, ops, t, want, "hostile store")
     assert lengths.tolist() == [[104, 0, 0, WORD3], [512, 0, 0, WORD3], [512, 0, 0, WORD3]]
+
+
+# ---------------------------------------------------------------- every writer of wide pages ----------------------------------
+WRITER_SHAPES = [(64, 16, 10), (64, 32, 12)]      # d_m 4 with 2 high bits, d_m 2 with 4: the two combinations R.FORMATS does not hold
+
+
+@pytest.mark.parametrize("packed", [False, True])
+@pytest.mark.parametrize("d,M,nbits", WRITER_SHAPES)
+def test_four_writers_one_page_image(d, M, nbits, packed, env, oracle):
+    """The token store of wide pages is written once (csrc/code_pages.h) and has four users.  The same 32 source rows - ring rows
+    40 .. 7 of every request's window - go to tokens [45, 77), across pages 1 and 2, through each: two pq_encode_into[_packed]
+    launches, pq_flush_wide in its host-length form, pq_store_ragged_wide with r = 0 (the rows handed in as new rows) and, for packed
+    pools, pq_pack_pages of the uint16 pools a flush wrote.  Every pool is the oracle's codes inside 0xA5 fill, byte for byte."""
+    torch, ops, L = env
+    sc = Scene(7 * d + M + nbits, d, M, nbits, packed)
+    plans, want = _flush_expect(sc, oracle, [(45, CAP, 40)] * BS, PS, 0)
+    ring = plans[0].ring
+    assert ring[0] == 40 and ring[-1] == 7 and plans[0].tokens[0] // PS == 1 and plans[0].tokens[-1] // PS == 2
+    t = sc.tensors(torch, [ring] * BS)
+    fresh = lambda: [R.to_dev(torch, a) for a in R.fill_pools(sc.n_pool, M, sc.C, packed)]
+    images = {}
+
+    k, v = images["encode"] = fresh()
+    kw = dict(token_start=45, n=PS, page_ids=t["ids"], page_size=PS, x_row_start=40, x_row_mod=CAP)
+    enc = ops.pq_encode_into_packed if packed else ops.pq_encode_into
+    enc(t["k_win"], t["kc"], k, layout=L.MILLION_CODES_KPAGES, **kw)
+    enc(t["v_win"], t["vc"], v, layout=L.MILLION_CODES_VPAGES, **kw)
+
+    k, v = images["flush"] = fresh()
+    flush = dict(n=PS, page_size=PS, token_start=45, x_row_start=40)
+    ops.pq_flush_wide(t["k_win"], t["v_win"], t["kc"], t["vc"], k, v, t["ids"], packed=packed, **flush)
+
+    k, v = images["ragged store"] = fresh()
+    lengths = torch.tensor([[45, 0, 0, WORD3]] * BS, dtype=torch.int32).cuda()
+    dev_n = torch.full((BS,), PS, dtype=torch.int32).cuda()
+    ops.pq_store_ragged_wide(R.to_dev(torch, sc.k_win[:, :, ring]), R.to_dev(torch, sc.v_win[:, :, ring]), None, None, t["kc"], t["vc"],
+                             k, v, t["ids"], lengths, dev_n, M=M, C=sc.C, page_size=PS, packed=packed)
+
+    if packed:
+        # uint16 pools whose packed image is the 0xA5 fill, flushed into, then packed
+        from tests import packed_model as P
+        k, v = (R.to_dev(torch, P.unpack(a, side, PS, M, sc.C)) for a, side in zip(R.fill_pools(sc.n_pool, M, sc.C, True), "kv"))
+        ops.pq_flush_wide(t["k_win"], t["v_win"], t["kc"], t["vc"], k, v, t["ids"], packed=False, **flush)
+        images["pack"] = [ops.pq_pack_pages(k, side="k", C=sc.C), ops.pq_pack_pages(v, side="v", C=sc.C)]
+    torch.cuda.synchronize()
+    assert lengths.tolist() == [[77, 0, 0, WORD3]] * BS
+    for who, (k, v) in images.items():
+        for side, got, exp in (("k", k, want[0]), ("v", v, want[1])):
+            g = R.to_np(torch, got)
+            assert g.shape == exp.shape and np.array_equal(g, exp), f"{who}: {side} pool differs in {int((g != exp).sum())} places"

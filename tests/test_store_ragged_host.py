@@ -284,12 +284,13 @@ def test_model_rows_and_scatter():
 
 # ---------------------------------------------------------------- kernel metadata -------------------------------------------
 def test_every_store_ragged_instance_has_no_scratch_no_spills_no_lds(lib):
-    """paged_store_kernel<DM, P> (csrc/paged_store.h): the store's instances (P = StoreRaggedParams) and the commit's (WindowCommitParams)."""
+    """paged_store_kernel<DM, P> (csrc/paged_store.h): the store's instances (P = StoreRaggedParams), the commit's (WindowCommitParams)
+    and the wide store's two (StoreRaggedWideParams: d / M is 2 or 4)."""
     out = subprocess.run([sys.executable, str(ROOT / "tools" / "kernel_meta.py"), str(ROOT / "million_amd" / "libmillion_hip.so"), "paged_store_kernel"],
                          capture_output=True, text=True, check=True).stdout
-    for params in ("StoreRaggedParams", "WindowCommitParams"):
+    for params, dms in (("StoreRaggedParams", "1248"), ("WindowCommitParams", "1248"), ("StoreRaggedWideParams", "24")):
         rows = [l for l in out.splitlines() if "paged_store_kernel" in l and params in l]
-        assert sorted(l.split()[0][l.index("ILi"):][:5] for l in rows) == ["ILi1E", "ILi2E", "ILi4E", "ILi8E"], out
+        assert sorted(l.split()[0][l.index("ILi"):][:5] for l in rows) == [f"ILi{dm}E" for dm in dms], out
         for l in rows:
             assert l.rstrip().endswith("vgpr_spill 0 sgpr_spill 0 scratch 0 B"), l
             assert " lds 0 B " in l, l
