@@ -1016,6 +1016,25 @@ int million_window_commit_rows(const million_window_commit_desc *desc, const voi
                                void *v_pool, const int32_t *page_ids, int32_t *dev_lengths, const int32_t *dev_n,
                                const int32_t *dev_rows, million_stream_t stream);
 
+/* million_window_commit / million_window_commit_rows over uint16 pages or packed pages (codes of 512 .. 4096 centroids): the
+ * contract above, word for word - the closed form of a_b decode steps, at most one flush per request, n_bound <= 16 and
+ * n_bound <= page_size <= resid_cap, a request whose T + f would pass the page table left untouched - with these differences:
+ *   k_cents / v_cents   the PLAIN (M, C, d_m) fp16 codebooks (wide codes have no prepared image), 16-byte aligned;
+ *   C in {512, 1024, 2048, 4096}; d in {128, 64}; d / M in {2, 4}; page_size in {32, 64, 128};
+ *   packed              0: k_pool (n_pool, page_size, M) / v_pool (n_pool, M, page_size) uint16; else packed pages ("Packed code
+ *                       pages" above), M a multiple of 4.
+ * The codes are million_pq_encode's / million_pq_encode_packed's bit for bit (the scan of million_pq_flush_wide and
+ * million_pq_store_ragged_wide).  The first launch is the page writer of million_pq_store_ragged_wide with the commit's rows,
+ * the second the append launch of the entries above.  Validation precedes any HIP call and any look at a pointer's value. */
+int million_window_commit_wide(const million_window_commit_desc *desc, const void *k_new, const void *v_new, void *k_resid,
+                               void *v_resid, const void *k_cents, const void *v_cents, void *k_pool, void *v_pool,
+                               const int32_t *page_ids, int32_t *dev_lengths, const int32_t *dev_n, int packed,
+                               million_stream_t stream);
+int million_window_commit_rows_wide(const million_window_commit_desc *desc, const void *k_new, const void *v_new, void *k_resid,
+                                    void *v_resid, const void *k_cents, const void *v_cents, void *k_pool, void *v_pool,
+                                    const int32_t *page_ids, int32_t *dev_lengths, const int32_t *dev_n,
+                                    const int32_t *dev_rows, int packed, million_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Residual-window append.
  * Replaces: the two slice-assign copies of DynamicPQCache.decoding (pq_utils.py:304-312) /

@@ -184,6 +184,8 @@ SYMBOLS = {
     "million_window_commit": (c_i32, [ctypes.POINTER(WindowCommitDesc)] + [c_vp] * 12),
     "million_attn_tree_merge": (c_i32, [ctypes.POINTER(BlockMergeDesc)] + [c_vp] * 12),
     "million_window_commit_rows": (c_i32, [ctypes.POINTER(WindowCommitDesc)] + [c_vp] * 13),
+    "million_window_commit_wide": (c_i32, [ctypes.POINTER(WindowCommitDesc)] + [c_vp] * 11 + [c_i32, c_vp]),
+    "million_window_commit_rows_wide": (c_i32, [ctypes.POINTER(WindowCommitDesc)] + [c_vp] * 12 + [c_i32, c_vp]),
     "million_pq_store_ragged": (c_i32, [ctypes.POINTER(StoreRaggedDesc)] + [c_vp] * 12),
     "million_pq_store_ragged_wide": (c_i32, [ctypes.POINTER(StoreRaggedDesc)] + [c_vp] * 11 + [c_i32, c_vp]),
     "million_pq_flush_wide": (c_i32, [ctypes.POINTER(EncodeDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),

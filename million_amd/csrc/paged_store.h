@@ -27,6 +27,9 @@
 // A fourth parameter block, CommitRowsParams (window_commit.hip, million_window_commit_rows), is the commit's with P::kRows: new
 // row i of a request is staged row dev_rows[b][i], clamped into [0, n_bound) (ps_new_row below).  kRows is false in WindowCommitParams and
 // is not asked of the store's blocks; the instances of the 8-bit store and of both commits are compiled as before.
+// WindowCommitWideParams / CommitRowsWideParams (window_commit.hip, million_window_commit_wide / _rows_wide) are the two commit
+// blocks with P::kWide: kCommit and kWide are independent switches, so the commit over uint16 / packed pages is these blocks and
+// no further line of the kernel.
 // A parameter block P has: kCommit (the commit's also kRows), kWide; side(vside); page_ids, dev_lengths, dev_n; bs, nh_k, d, M, C, n_bound, rcap,
 // page_size, ps_shift, n_pages_cap, cap_tok (cap_tok = n_pages_cap * page_size); the stores wsb, wsh (window strides, row stride d), the
 // wide one packed; the commit nsl, ids_ls, win_ls, len_ls (layer strides), n_pool and groups_y (grid.y per layer).

@@ -20,6 +20,10 @@
 // A request whose T + f would pass the page table is left untouched by both launches.
 // million_window_commit_rows (the accepted path of a draft tree) is the same two launches with one indirection: new row i of
 // request b is staged row dev_rows[b][i], index and entry clamped on the device (ps_new_row, paged_store.h; CommitRowsParams).
+// million_window_commit_wide / million_window_commit_rows_wide are the same two launches over uint16 pages or packed pages (codes
+// of 512 .. 4096 centroids): launch 1 with the P::kWide blocks below - the scan over the plain fp16 codebook, the token store of
+// code_pages.h, so the codes are million_pq_flush_wide's - and launch 2 the append kernels above, which see fp16 rows and the
+// lengths rows only.
 #include "paged_store.h"
 
 #pragma clang fp contract(off)
@@ -55,6 +59,22 @@ struct WindowCommitParams {
 
 // million_window_commit_rows: new row i of request b is staged row dev_rows[b][i] (ps_new_row, paged_store.h)
 struct CommitRowsParams : WindowCommitParams {
+    static constexpr bool kRows = true;
+    const int *dev_rows;            // (bs, n_bound)
+};
+
+// million_window_commit_wide / million_window_commit_rows_wide: the first launch over uint16 pages or packed pages.  The sides
+// carry the plain (M, C, d_m) fp16 codebooks (P::kWide: the scan reads them, the token store is store_codes4_wide); every other
+// word is the commit's.  The append launch takes the WindowCommitParams / CommitRowsParams these blocks begin with.
+struct WindowCommitWideParams : WindowCommitParams {
+    static constexpr bool kWide = true;
+    const f16 *k_cents, *v_cents;
+    int packed;
+    __device__ __forceinline__ PagedStoreSideT<f16> side(bool vside) const {
+        return {vside ? v_new : k_new, vside ? v_win : k_win, vside ? v_cents : k_cents, vside ? v_pool : k_pool, nsb, nsh, nsn};
+    }
+};
+struct CommitRowsWideParams : WindowCommitWideParams {
     static constexpr bool kRows = true;
     const int *dev_rows;            // (bs, n_bound)
 };
@@ -102,14 +122,22 @@ __global__ __launch_bounds__(kWcBlock) void window_commit_rows_append_kernel(Com
 using namespace million;
 
 // Validation and parameter fill shared by the two entries; `who` names the entry in the messages.  No HIP call.
+// P::kWide: the codebooks are the plain fp16 ones and the geometry is the wide formats' (packed: the pools hold packed pages).
+template <class P>
 static int window_commit_fill(const char *who, const million_window_commit_desc *desc, const void *k_new, const void *v_new, void *k_resid,
                               void *v_resid, const void *k_cents_prepared, const void *v_cents_prepared, void *k_pool, void *v_pool,
-                              const int32_t *page_ids, int32_t *dev_lengths, const int32_t *dev_n, WindowCommitParams &p, int &dm) {
+                              const int32_t *page_ids, int32_t *dev_lengths, const int32_t *dev_n, P &p, int &dm, int packed = 0) {
     if (!desc || desc->struct_size != sizeof(million_window_commit_desc)) { set_error("%s: bad desc / struct_size", who); return MILLION_ERR_ARG; }
     const million_window_commit_desc &d = *desc;
     if (d.n_layers <= 0 || d.bs <= 0 || d.nh_k <= 0) { set_error("%s: n_layers=%d bs=%d nh_k=%d", who, d.n_layers, d.bs, d.nh_k); return MILLION_ERR_SHAPE; }
     int ps_shift;
-    if (!u8_geometry(who, d.d, d.M, d.C) || !page_shift(who, d.page_size, ps_shift)) return MILLION_ERR_SHAPE;
+    if constexpr (P::kWide) {
+        if (!wide_geometry(d.d, d.M, d.C, 1) || (packed && d.M % 4)) {
+            set_error("%s: d=%d M=%d C=%d (d 64 / 128, d / M 2 or 4, C 512 / 1024 / 2048 / 4096; packed pages: M a multiple of 4)", who, d.d, d.M, d.C);
+            return MILLION_ERR_SHAPE;
+        }
+    } else if (!u8_geometry(who, d.d, d.M, d.C)) return MILLION_ERR_SHAPE;
+    if (!page_shift(who, d.page_size, ps_shift)) return MILLION_ERR_SHAPE;
     if (d.n_bound < 1 || d.n_bound > kWcMaxRows || d.n_bound > d.page_size) {
         set_error("%s: n_bound=%d (1 .. %d, at most page_size=%d: one flush per request)", who, d.n_bound, kWcMaxRows, d.page_size);
         return MILLION_ERR_SHAPE;
@@ -136,7 +164,10 @@ static int window_commit_fill(const char *who, const million_window_commit_desc 
     }
     if (!dev_n || !dev_lengths) { set_error("%s: null dev_n / dev_lengths (every per-request value is read on the device)", who); return MILLION_ERR_ARG; }
     if (!k_new || !v_new || !k_resid || !v_resid) { set_error("%s: null new rows / windows", who); return MILLION_ERR_ARG; }
-    if (!k_cents_prepared || !v_cents_prepared) { set_error("%s: null prepared codebook (million_prepare_cents: the call needs both)", who); return MILLION_ERR_ARG; }
+    if (!k_cents_prepared || !v_cents_prepared) {
+        set_error(P::kWide ? "%s: null codebook (the plain (M, C, d_m) fp16 tensors: the call needs both)" : "%s: null prepared codebook (million_prepare_cents: the call needs both)", who);
+        return MILLION_ERR_ARG;
+    }
     if (!k_pool || !v_pool || !page_ids) { set_error("%s: null pools / page_ids", who); return MILLION_ERR_ARG; }
     const int rc = paged_store_fill(who, p, d.bs, d.nh_k, d.d, d.M, d.C, d.n_bound, d.resid_cap, d.page_size, ps_shift, d.n_pages_cap,
                                     (uintptr_t)k_new | (uintptr_t)v_new | (uintptr_t)k_resid | (uintptr_t)v_resid | (uintptr_t)k_cents_prepared |
@@ -149,8 +180,13 @@ static int window_commit_fill(const char *who, const million_window_commit_desc 
     }
     p.k_new = (const f16 *)k_new; p.v_new = (const f16 *)v_new;
     p.k_win = (f16 *)k_resid; p.v_win = (f16 *)v_resid;
-    p.k_cents32 = prepared_cents32(k_cents_prepared, d.M, d.C, dm);
-    p.v_cents32 = prepared_cents32(v_cents_prepared, d.M, d.C, dm);
+    if constexpr (P::kWide) {
+        p.k_cents = (const f16 *)k_cents_prepared; p.v_cents = (const f16 *)v_cents_prepared;
+        p.packed = packed ? 1 : 0;
+    } else {
+        p.k_cents32 = prepared_cents32(k_cents_prepared, d.M, d.C, dm);
+        p.v_cents32 = prepared_cents32(v_cents_prepared, d.M, d.C, dm);
+    }
     p.k_pool = (uint8_t *)k_pool; p.v_pool = (uint8_t *)v_pool;
     p.nsl = d.new_stride_l; p.nsb = d.new_stride_b; p.nsh = d.new_stride_h; p.nsn = d.new_stride_n; p.ids_ls = d.ids_layer_stride; p.win_ls = d.rows_layer_stride; p.len_ls = d.lengths_layer_stride;
     p.n_layers = d.n_layers; p.n_pool = d.n_pool;
@@ -201,4 +237,50 @@ extern "C" int million_window_commit_rows(const million_window_commit_desc *desc
     e = hipGetLastError();
     if (e != hipSuccess) { set_error("window_commit_rows append launch: %s", hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
     return MILLION_OK;
+}
+
+// The two launches of the wide entries: paged_store_kernel with the wide block (d / M is 2 or 4: wide_geometry), then the append
+// launch of the 8-bit entries over the block's WindowCommitParams / CommitRowsParams part.
+template <class P, class Append, class AppendParams>
+static int window_commit_wide_launch(const char *who, const million_window_commit_desc &d, const P &p, int dm, Append append, const AppendParams &pa,
+                                     hipStream_t s) {
+    const dim3 grid((d.page_size + 63) / 64, d.n_layers * p.groups_y, d.bs * d.nh_k * 2);
+    if (dm == 2) hipLaunchKernelGGL((paged_store_kernel<2, P>), grid, dim3(kWcBlock), 0, s, p);
+    else hipLaunchKernelGGL((paged_store_kernel<4, P>), grid, dim3(kWcBlock), 0, s, p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_error("%s encode launch: %s", who, hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
+    hipLaunchKernelGGL(append, dim3(d.n_layers * d.bs), dim3(kWcBlock), 0, s, pa);
+    e = hipGetLastError();
+    if (e != hipSuccess) { set_error("%s append launch: %s", who, hipGetErrorString(e)); return MILLION_ERR_LAUNCH; }
+    return MILLION_OK;
+}
+
+extern "C" int million_window_commit_wide(const million_window_commit_desc *desc, const void *k_new, const void *v_new, void *k_resid,
+                                          void *v_resid, const void *k_cents, const void *v_cents, void *k_pool, void *v_pool,
+                                          const int32_t *page_ids, int32_t *dev_lengths, const int32_t *dev_n, int packed,
+                                          million_stream_t stream) {
+    WindowCommitWideParams p;
+    int dm;
+    const int rc = window_commit_fill("window_commit_wide", desc, k_new, v_new, k_resid, v_resid, k_cents, v_cents, k_pool, v_pool, page_ids,
+                                      dev_lengths, dev_n, p, dm, packed);
+    if (rc != MILLION_OK) return rc;
+    return window_commit_wide_launch("window_commit_wide", *desc, p, dm, window_commit_append_kernel, (const WindowCommitParams &)p, (hipStream_t)stream);
+}
+
+extern "C" int million_window_commit_rows_wide(const million_window_commit_desc *desc, const void *k_new, const void *v_new, void *k_resid,
+                                               void *v_resid, const void *k_cents, const void *v_cents, void *k_pool, void *v_pool,
+                                               const int32_t *page_ids, int32_t *dev_lengths, const int32_t *dev_n,
+                                               const int32_t *dev_rows, int packed, million_stream_t stream) {
+    CommitRowsWideParams p;
+    int dm;
+    const int rc = window_commit_fill("window_commit_rows_wide", desc, k_new, v_new, k_resid, v_resid, k_cents, v_cents, k_pool, v_pool,
+                                      page_ids, dev_lengths, dev_n, p, dm, packed);
+    if (rc != MILLION_OK) return rc;
+    if (!dev_rows) { set_error("window_commit_rows_wide: null dev_rows (million_window_commit_wide is the entry without row indices)"); return MILLION_ERR_ARG; }
+    if ((uintptr_t)dev_rows & 3) { set_error("window_commit_rows_wide: dev_rows must be 4-byte aligned"); return MILLION_ERR_ALIGN; }
+    p.dev_rows = dev_rows;
+    CommitRowsParams pa;
+    (WindowCommitParams &)pa = (const WindowCommitParams &)p;
+    pa.dev_rows = dev_rows;
+    return window_commit_wide_launch("window_commit_rows_wide", *desc, p, dm, window_commit_rows_append_kernel, pa, (hipStream_t)stream);
 }

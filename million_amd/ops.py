@@ -235,6 +235,8 @@ class CodeFormat:
     gather: str
     flush: str                         # the one-launch window flush, and
     store_ragged: str                  # the one-launch ragged store, into its pages
+    commit: str                        # draft verification: the one-call commit of the accepted rows, every layer, and
+    commit_rows: str                   # ... of chosen rows (the accepted path of a draft tree)
     # the attention ops of this module over its stores, looked up by name when called (the methods below)
     op_decode_attn: str
     op_chunk_attn: str
@@ -273,6 +275,14 @@ class CodeFormat:
         return lambda q, k_chunk, v_chunk, k_codes, v_codes, cents, prepared, *window, **kw: globals()[name](
             q, k_chunk, v_chunk, k_codes, v_codes, *(prepared if self.prepared else cents), *window, **said, **kw)
 
+    def commit_pages(self, k_new, v_new, k_res, v_res, cents, prepared, k_pool, v_pool, page_ids, dev_lengths, dev_n, *, M, C, **kw):
+        """The accepted rows of a verification into the windows (and, where a window overflows, its oldest rows into the pages) of every
+        layer in one call (kw: n_bound, dev_rows): window_commit over the prepared codebooks, window_commit_wide over the codebooks as
+        they are."""
+        if self.prepared:
+            return window_commit(k_new, v_new, k_res, v_res, *prepared, k_pool, v_pool, page_ids, dev_lengths, dev_n, M=M, C=C, **kw)
+        return window_commit_wide(k_new, v_new, k_res, v_res, *cents, k_pool, v_pool, page_ids, dev_lengths, dev_n, packed=not self.rowmajor, **kw)
+
     def flush_pages(self, k_rows, v_rows, cents, k_pool, v_pool, page_ids, **kw):
         """The oldest n rows of the ring windows into pages, one encode launch (kw: pq_flush's n, page_size, token_start, x_row_start,
         dev_lengths, min_r): pq_flush for 8-bit codes, pq_flush_wide - told whether the pages are packed - for the wide formats.  Both
@@ -296,21 +306,23 @@ FMT_U8 = CodeFormat(
     encode="million_pq_encode", decode_attn="million_pq_decode_attn", decode_ws="million_attn_workspace_bytes",
     chunk_attn="million_pq_chunk_attn", chunk_attn_lse="million_pq_chunk_attn_lse", chunk_ws="million_chunk_attn_workspace_bytes",
     gather="million_pq_gather_rows", flush="million_pq_flush_layers", store_ragged="million_pq_store_ragged",
-    op_decode_attn="pq_decode_attn", op_chunk_attn="pq_chunk_attn")
+    commit="million_window_commit", commit_rows="million_window_commit_rows", op_decode_attn="pq_decode_attn", op_chunk_attn="pq_chunk_attn")
 FMT_U16 = CodeFormat(
     "uint16", WIDE_CENTROIDS, torch.uint16, rowmajor=True, code_bytes=2, prepared=False, page_shapes=_word_page_shapes,
     check_store=_check_word_store,
     encode="million_pq_encode", decode_attn="million_pq_decode_attn_wide", decode_ws="million_attn_wide_workspace_bytes",
     chunk_attn="million_pq_chunk_attn_wide", chunk_attn_lse="million_pq_chunk_attn_wide", chunk_ws="million_chunk_attn_wide_workspace_bytes",
     gather="million_pq_gather_rows", flush="million_pq_flush_wide", store_ragged="million_pq_store_ragged_wide",
-    op_decode_attn="pq_decode_attn_wide", op_chunk_attn="pq_chunk_attn_wide")
+    commit="million_window_commit_wide", commit_rows="million_window_commit_rows_wide", op_decode_attn="pq_decode_attn_wide",
+    op_chunk_attn="pq_chunk_attn_wide")
 FMT_PACKED = CodeFormat(
     "packed", WIDE_CENTROIDS, torch.uint8, rowmajor=False, code_bytes=2, prepared=False, page_shapes=_packed_page_shapes,
     check_store=_check_packed_store,
     encode="million_pq_encode_packed", decode_attn="million_pq_decode_attn_packed", decode_ws="million_attn_wide_workspace_bytes",
     chunk_attn="million_pq_chunk_attn_packed", chunk_attn_lse="million_pq_chunk_attn_packed", chunk_ws="million_chunk_attn_wide_workspace_bytes",
     gather="million_pq_gather_rows_packed", flush="million_pq_flush_wide", store_ragged="million_pq_store_ragged_wide",
-    op_decode_attn="pq_decode_attn_packed", op_chunk_attn="pq_chunk_attn_packed")
+    commit="million_window_commit_wide", commit_rows="million_window_commit_rows_wide", op_decode_attn="pq_decode_attn_packed",
+    op_chunk_attn="pq_chunk_attn_packed")
 CODE_FORMATS = (FMT_U8, FMT_U16, FMT_PACKED)
 
 
@@ -1939,14 +1951,71 @@ def window_commit(k_new: torch.Tensor, v_new: torch.Tensor, k_res: torch.Tensor,
     if dev_rows is not None:
         if dev_rows.dtype != torch.int32 or tuple(dev_rows.shape) != (bs, n_bound) or not dev_rows.is_contiguous() or dev_rows.device != k_new.device:
             raise RuntimeError(f"window_commit: dev_rows must be contiguous int32 (bs, n_bound) = ({bs}, {n_bound}) on the device of k_new")
-        L.check(L.load().million_window_commit_rows(ctypes.byref(desc), k_new.data_ptr(), v_new.data_ptr(), k_res.data_ptr(), v_res.data_ptr(),
-                                                    k_prep.data_ptr(), v_prep.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(),
-                                                    page_ids.data_ptr(), dev_lengths.data_ptr(), dev_n.data_ptr(), dev_rows.data_ptr(),
-                                                    _stream()), "million_window_commit_rows")
+        L.check(getattr(L.load(), FMT_U8.commit_rows)(ctypes.byref(desc), k_new.data_ptr(), v_new.data_ptr(), k_res.data_ptr(), v_res.data_ptr(),
+                                                      k_prep.data_ptr(), v_prep.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(),
+                                                      page_ids.data_ptr(), dev_lengths.data_ptr(), dev_n.data_ptr(), dev_rows.data_ptr(),
+                                                      _stream()), FMT_U8.commit_rows)
         _vshadow_drop(v_pool)
         return
-    L.check(L.load().million_window_commit(ctypes.byref(desc), k_new.data_ptr(), v_new.data_ptr(), k_res.data_ptr(), v_res.data_ptr(),
-                                           k_prep.data_ptr(), v_prep.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(),
-                                           page_ids.data_ptr(), dev_lengths.data_ptr(), dev_n.data_ptr(), _stream()),
-            "million_window_commit")
+    L.check(getattr(L.load(), FMT_U8.commit)(ctypes.byref(desc), k_new.data_ptr(), v_new.data_ptr(), k_res.data_ptr(), v_res.data_ptr(),
+                                             k_prep.data_ptr(), v_prep.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(),
+                                             page_ids.data_ptr(), dev_lengths.data_ptr(), dev_n.data_ptr(), _stream()),
+            FMT_U8.commit)
     _vshadow_drop(v_pool)
+
+
+def window_commit_wide(k_new: torch.Tensor, v_new: torch.Tensor, k_res: torch.Tensor, v_res: torch.Tensor, k_cents: torch.Tensor,
+                       v_cents: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, page_ids: torch.Tensor,
+                       dev_lengths: torch.Tensor, dev_n: torch.Tensor, *, n_bound: Optional[int] = None, packed: bool = False,
+                       dev_rows: Optional[torch.Tensor] = None) -> None:
+    """window_commit for codes of 512 .. 4096 centroids (million_window_commit_wide / million_window_commit_rows_wide): the same
+    call with the same meaning - the first dev_n[b] rows (dev_rows: the chosen rows) of k_new / v_new (layers, bs, nh_k, n, d) join
+    request b's window in every layer as that many decode steps would have, a window they overflow flushing its oldest page_size
+    rows first - into uint16 pages (K (n_pool, page_size, M), V (n_pool, M, page_size)) or, packed=True, packed pages (uint8
+    (n_pool, packed_page_bytes)), with the codebooks as they are (fp16 (M, C, d_m)) in place of the prepared ones.  The codes are
+    pq_encode_into's / pq_encode_into_packed's bit for bit."""
+    who = "window_commit_wide"
+    _need_cuda(k_new, v_new, k_res, v_res, k_cents, v_cents, k_pool, v_pool, page_ids, dev_lengths, dev_n, dev_rows)
+    if k_new.dtype != torch.float16 or v_new.dtype != torch.float16 or k_new.dim() != 5 or v_new.shape != k_new.shape or \
+            k_new.stride() != v_new.stride() or k_new.stride(4) != 1:
+        raise RuntimeError(f"{who}: k_new / v_new must be fp16 (layers, bs, nh_k, n, d) of one shape and strides, contiguous rows")
+    n_layers, bs, nhk, n_rows, d = k_new.shape
+    n_bound = n_rows if n_bound is None else int(n_bound)
+    if n_bound > n_rows:
+        raise RuntimeError(f"{who}: n_bound={n_bound} exceeds the {n_rows} rows of k_new")
+    if page_ids.dtype != torch.int32 or page_ids.dim() != 4 or page_ids.shape[:3] != (n_layers, bs, nhk) or not page_ids[0].is_contiguous():
+        raise RuntimeError(f"{who}: int32 page_ids (layers, bs, nh_k, n_pages_cap), each layer contiguous, expected")
+    if (k_res.dtype != torch.float16 or v_res.dtype != torch.float16 or k_res.dim() != 5 or k_res.shape != v_res.shape or k_res.stride() != v_res.stride()
+            or k_res.shape[:3] != (n_layers, bs, nhk) or k_res.shape[4] != d or not k_res[0].is_contiguous()):
+        raise RuntimeError(f"{who}: fp16 windows (layers, bs, nh_k, cap, d), each layer contiguous, K and V alike, expected")
+    k_cents, v_cents = k_cents.contiguous(), v_cents.contiguous()
+    if packed:      # a packed pool has no page_size axis: the one size whose page has the pool's bytes (page bytes grow with the size)
+        sizes = [ps for ps in (32, 64, 128) if k_pool.dim() == 2 and k_cents.dim() == 3 and k_cents.shape[1] in WIDE_CENTROIDS
+                 and k_pool.shape[1] == packed_page_bytes(ps, k_cents.shape[0], k_cents.shape[1])]
+        if not sizes:
+            raise RuntimeError(f"{who}: a packed pool must be contiguous uint8 (n_pool, packed_page_bytes) for page_size 32, 64 or 128")
+        page_size = sizes[0]
+    else:
+        if k_pool.dim() != 3:
+            raise RuntimeError(f"{who}: pools must be K (n_pool, page_size, M) and V (n_pool, M, page_size)")
+        page_size = k_pool.shape[1]
+    fmt, M, C = _check_wide_pools(who, k_cents, v_cents, k_pool, v_pool, page_size, bs, nhk, d, packed)      # the format names the entries
+    if k_pool.shape[0] != v_pool.shape[0]:
+        raise RuntimeError(f"{who}: K and V pools of one page count expected")
+    if dev_lengths.dtype != torch.int32 or dev_lengths.shape != (n_layers, bs, 4) or not dev_lengths[0].is_contiguous():
+        raise RuntimeError(f"{who}: int32 dev_lengths (layers, bs, 4) expected")
+    _check_dev_n(who, dev_n, bs)
+    desc = L.WindowCommitDesc()
+    desc.struct_size = ctypes.sizeof(L.WindowCommitDesc)
+    desc.n_layers, desc.bs, desc.nh_k, desc.d, desc.M, desc.C, desc.n_bound = n_layers, bs, nhk, d, M, C, n_bound
+    desc.page_size, desc.n_pages_cap, desc.n_pool, desc.resid_cap = page_size, page_ids.shape[3], k_pool.shape[0], k_res.shape[3]
+    desc.new_stride_l, desc.new_stride_b, desc.new_stride_h, desc.new_stride_n = k_new.stride()[:4]
+    desc.ids_layer_stride, desc.rows_layer_stride, desc.lengths_layer_stride = page_ids.stride(0), k_res.stride(0), dev_lengths.stride(0)
+    args = (ctypes.byref(desc), k_new.data_ptr(), v_new.data_ptr(), k_res.data_ptr(), v_res.data_ptr(), k_cents.data_ptr(), v_cents.data_ptr(),
+            k_pool.data_ptr(), v_pool.data_ptr(), page_ids.data_ptr(), dev_lengths.data_ptr(), dev_n.data_ptr())
+    if dev_rows is not None:
+        if dev_rows.dtype != torch.int32 or tuple(dev_rows.shape) != (bs, n_bound) or not dev_rows.is_contiguous() or dev_rows.device != k_new.device:
+            raise RuntimeError(f"{who}: dev_rows must be contiguous int32 (bs, n_bound) = ({bs}, {n_bound}) on the device of k_new")
+        L.check(getattr(L.load(), fmt.commit_rows)(*args, dev_rows.data_ptr(), int(bool(packed)), _stream()), fmt.commit_rows)
+        return
+    L.check(getattr(L.load(), fmt.commit)(*args, int(bool(packed)), _stream()), fmt.commit)

@@ -28,9 +28,20 @@ _prefill_ragged, _extend_ragged), the launches the format's (ops.CodeFormat.flus
     extend_ragged    ops.pq_chunk_attn_packed(dev_lengths=, dev_n_q=)   ops.pq_chunk_attn_wide(dev_lengths=, dev_n_q=)
     device_store     ops.pq_store_ragged_wide(packed=True)          ops.pq_store_ragged_wide
 
+Draft verification.  verify / commit below are PagedPQCache._verify / _commit, the bodies of the cache's own
+methods, with the launches of the cache's format (ops.CodeFormat.decode_pages, chunk_op, commit_pages); the block merge
+(ops.attn_block_merge, chain or dev_mask=) takes fp16 rows and (out, lse) and never sees a code:
+
+    call / route       packed cache                                  unpacked cache
+    verify "heads"     ops.pq_decode_attn_packed, no append          ops.pq_decode_attn_wide, no append   then ops.attn_block_merge
+                       (the kernel has 16 score columns: n nh / nh_k <= 16, else refused - "chunk" has no such limit)
+    verify "chunk"     ops.pq_chunk_attn_packed(dev_n_q=)            ops.pq_chunk_attn_wide(dev_n_q=)   (a tree: over the past only,
+                                                                                                    then the masked block merge)
+    commit             ops.window_commit_wide(packed=True)           ops.window_commit_wide         (dev_rows= for a tree's path)
+
 The cache's own methods keep doing on a wide cache exactly what they did: decoding_with_pages / flush_to_pages flush in lockstep
-only, prefill_ragged / extend_ragged raise NotImplementedError.  Encode-ahead (begin_step reports 'plain' / 'flush' only), fork,
-swap, verify / commit, sinks and SharedPrefix on wide caches stay refused by the cache."""
+only, prefill_ragged / extend_ragged, verify / commit raise NotImplementedError.  Encode-ahead (begin_step reports 'plain' /
+'flush' only), fork, swap, sinks and SharedPrefix on wide caches stay refused by the cache."""
 from __future__ import annotations
 
 
@@ -96,3 +107,30 @@ def extend_ragged(cache, query_states, key_states, value_states, layer_idx, n_ne
     if cache.nbits <= 8:
         return cache.extend_ragged(query_states, key_states, value_states, layer_idx, n_new, device_store=device_store)
     return cache._extend_ragged("paged_turns.extend_ragged", query_states, key_states, value_states, layer_idx, n_new, device_store)
+
+
+def verify(cache, query_states, key_states, value_states, layer_idx, n_draft=None, use_dev_lengths=True, route=None, return_lse=False,
+           tree=None):
+    """PagedPQCache.verify for a cache with nbits 9 .. 12 (packed or not): the attention of n <= 16 draft tokens per request over
+    [the codes; the window; the draft rows, causally - or, tree=, along their ancestors], one layer, q (bs, nh, n, d), K/V
+    (bs, nh_k, n, d) -> out (bs, nh, n, d) (and lse with return_lse).  Pure: pages, window, lengths and host mirror do not move;
+    the rows' K/V are parked for commit().  n_draft, tree, use_dev_lengths and return_lse mean what they mean there.  route:
+    "heads" - the decode launch of the format over the rows as query heads, then ops.attn_block_merge: one launch of a kernel with
+    16 score columns, so n nh / nh_k <= 16 or the call is refused before anything is joined or recorded;
+    "chunk" - the chunk attention of the cache's format with the rows as chunk; None: cache._verify_route(n), the wide rule.  A
+    cache with nbits = 8 is handed to its own method."""
+    if cache.nbits <= 8:
+        return cache.verify(query_states, key_states, value_states, layer_idx, n_draft=n_draft, use_dev_lengths=use_dev_lengths, route=route,
+                            return_lse=return_lse, tree=tree)
+    return cache._verify("paged_turns.verify", query_states, key_states, value_states, layer_idx, n_draft, use_dev_lengths, route, return_lse, tree)
+
+
+def commit(cache, n_accept=None, *, path=None):
+    """PagedPQCache.commit for a cache with nbits 9 .. 12 (packed or not): the first n_accept[b] rows (path=: the accepted chain of a
+    tree) that verify() above staged join the window of slot b in every layer in ONE call (ops.window_commit_wide), exactly as that
+    many decode() steps above would have left codes, pages, window rows, host and device lengths; decode, flush, extend* and
+    release go on as after those steps.  Every refusal of the 8-bit method holds, before anything moves.  A cache with nbits = 8
+    is handed to its own method."""
+    if cache.nbits <= 8:
+        return cache.commit(n_accept, path=path)
+    return cache._commit("paged_turns.commit", n_accept, path)
