@@ -339,6 +339,41 @@ int million_cache_swap(const million_swap_desc *desc, const int32_t *page_ids, v
                        const int32_t *slot_table /* (n_slots, 4) */, const int64_t *blob_offsets /* (n_slots,) */,
                        void *blob, million_stream_t stream);
 
+/* Fork and swap over wide code pages: pools of uint16 pages (packed == 0: K (n_pool, page_size, M), V (n_pool, M, page_size)
+ * uint16) or of packed pages (packed != 0: uint8 (n_pool, page_bytes), "Packed code pages" below) that hold codes of C in
+ * {512, 1024, 2048, 4096} centroids; h = 2 for C <= 1024, else 4.
+ *
+ * million_cache_fork_wide: million_cache_fork's contract, word for word - descriptor, SHARE and COPY, the clamps of the source
+ * row, prefix_tokens, ids outside [0, n_pool) dropping the copy, duplicate destinations and dst == src taking no part, the errors
+ * and their order, one launch whose grid is a function of the bounds alone, no atomics, flags or workspace, capturable - over pages
+ * of page_size * M * 2 bytes (uint16) or page_size * M * (8 + h) / 8 bytes (packed: both planes, copied as one byte string).  A
+ * page starts at id * page_bytes in 64-bit arithmetic; a page task owns 16384 / page_bytes pages (1 .. 32) of each side.
+ * C outside {512, 1024, 2048, 4096}: MILLION_ERR_SHAPE, checked behind M.
+ *
+ * million_cache_swap_wide: million_cache_swap's contract - entries, clamps, entries that take no part, ids outside the pool
+ * packing as zeros and skipped on unpack, the window rows in ring order, the lengths rows, layer ranges, errors (C as above), one
+ * launch, the bound-only grid - with blob format 2.
+ *
+ * Blob format, version 2: format 1 with PACKED pages in place of uint8 pages, whatever the pool's own format.  Each row is
+ * row_bytes = 2 * n_live * page_size * M * (8 + h) / 8 + 4 * r * d bytes (a multiple of 16) and holds, in this order:
+ *   K pages   n_live pages, each exactly a packed K page: low plane (page_size, M), then high plane (page_size, M * h / 8);
+ *   V pages   n_live pages, each a packed V page: low plane (M, page_size), then high plane (M * h / 8, page_size);
+ *   K window  r rows of d fp16 in ring order;   V window  the same.
+ * The blob is canonical: every byte of both planes that belongs to a token >= T is zero, and every field is code & (C - 1) - at
+ * C = 512 / 2048 the top bit of a field is zero, and from a uint16 pool the bits of a code at and above log2 C are dropped.  So
+ * PACK writes the same bytes from a uint16 pool and from a packed pool that hold the same codes, and a request packed from one
+ * restores into the other.  UNPACK writes both whole pages of every page j < n_live into the id the table row names: a packed
+ * pool gets the blob's bytes; a uint16 pool gets (low byte | field << 8) & (C - 1) per code and 0 for the codes of tokens >= T. */
+int million_cache_fork_wide(const million_fork_desc *desc, int32_t *page_ids, void *k_pool, void *v_pool,
+                            void *k_resid, void *v_resid, int32_t *dev_lengths /* (layers, bs, 4) */,
+                            const int32_t *dst_slots /* (n_dst,) */, const int32_t *tail_ids /* (n_dst, layers, nh_k) or NULL */,
+                            int C, int packed, million_stream_t stream);
+
+int million_cache_swap_wide(const million_swap_desc *desc, const int32_t *page_ids, void *k_pool, void *v_pool,
+                            void *k_resid, void *v_resid, int32_t *dev_lengths /* (layers, bs, 4) */,
+                            const int32_t *slot_table /* (n_slots, 4) */, const int64_t *blob_offsets /* (n_slots,) */,
+                            void *blob, int C, int packed, million_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * PQ codebook training.
  * Replaces: train_pq (scripts/utils/pq_utils.py:586-609), which wraps faiss-cpu's IndexPQ.train: ProductQuantizer's default

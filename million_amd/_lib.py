@@ -191,6 +191,8 @@ SYMBOLS = {
     "million_pq_flush_wide": (c_i32, [ctypes.POINTER(EncodeDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "million_cache_fork": (c_i32, [ctypes.POINTER(ForkDesc)] + [c_vp] * 9),
     "million_cache_swap": (c_i32, [ctypes.POINTER(SwapDesc)] + [c_vp] * 10),
+    "million_cache_fork_wide": (c_i32, [ctypes.POINTER(ForkDesc)] + [c_vp] * 8 + [c_i32, c_i32, c_vp]),
+    "million_cache_swap_wide": (c_i32, [ctypes.POINTER(SwapDesc)] + [c_vp] * 9 + [c_i32, c_i32, c_vp]),
     "million_set_force_generic": (None, [c_i32]),
     "million_debug_set_stamp_buffer": (None, [c_vp]),
     "million_debug_bad_page_ids": (c_i32, []),

@@ -15,7 +15,7 @@ HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 LIB = HERE / "libmillion_hip.so"
 LIB_DEBUG_IDS = HERE / "libmillion_hip_dbgids.so"      # same sources with -DMILLION_DEBUG_CHECK_IDS (page ids bounds-checked)
-SOURCES = ["million_api.hip", "encode.hip", "attn_generic.hip", "attn_tile.hip", "attn_wide.hip", "attn_mfma.hip", "prefill.hip", "chunk_attn.hip", "chunk_attn_wide.hip", "train.hip", "store_ragged.hip", "flush_wide.hip", "cache_fork.hip", "cache_swap.hip", "attn_merge.hip", "attn_block.hip", "window_commit.hip", "attn_sink.hip", "gather_rows.hip"]
+SOURCES = ["million_api.hip", "encode.hip", "attn_generic.hip", "attn_tile.hip", "attn_wide.hip", "attn_mfma.hip", "prefill.hip", "chunk_attn.hip", "chunk_attn_wide.hip", "train.hip", "store_ragged.hip", "flush_wide.hip", "cache_fork.hip", "cache_swap.hip", "cache_fork_wide.hip", "cache_swap_wide.hip", "attn_merge.hip", "attn_block.hip", "window_commit.hip", "attn_sink.hip", "gather_rows.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-value", "-Wno-tautological-bitwise-compare", "-Wno-inline-asm"]
 
 

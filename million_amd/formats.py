@@ -97,7 +97,8 @@ def write_fvecs(filename, vecs, mode: str = "ab") -> None:
 
 def save_request(path, snap) -> Path:
     """One request of a PagedPQCache (pq_cache.RequestSnapshot: swap_out / snapshot_request) as one file: `torch.save` of a
-    dict {"blob": the 1-D uint8 tensor (blob format 1, include/million_hip.h), "meta": plain ints and strings}."""
+    dict {"blob": the 1-D uint8 tensor (blob format 1 or 2, include/million_hip.h: meta["version"] says which and is carried
+    through unchecked - swap_in checks it), "meta": plain ints and strings}."""
     meta = {str(k): (v if isinstance(v, str) else int(v)) for k, v in snap.meta.items()}
     path = Path(path)
     torch.save({"blob": snap.blob.detach().cpu().contiguous(), "meta": meta}, path)

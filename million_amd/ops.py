@@ -237,6 +237,8 @@ class CodeFormat:
     store_ragged: str                  # the one-launch ragged store, into its pages
     commit: str                        # draft verification: the one-call commit of the accepted rows, every layer, and
     commit_rows: str                   # ... of chosen rows (the accepted path of a draft tree)
+    fork: str                          # a slot becomes a copy of another, and
+    swap: str                          # a request leaves its pages for a blob and comes back (blob format 1: uint8, 2: the wide formats)
     # the attention ops of this module over its stores, looked up by name when called (the methods below)
     op_decode_attn: str
     op_chunk_attn: str
@@ -283,6 +285,31 @@ class CodeFormat:
             return window_commit(k_new, v_new, k_res, v_res, *prepared, k_pool, v_pool, page_ids, dev_lengths, dev_n, M=M, C=C, **kw)
         return window_commit_wide(k_new, v_new, k_res, v_res, *cents, k_pool, v_pool, page_ids, dev_lengths, dev_n, packed=not self.rowmajor, **kw)
 
+    def fork_pages(self, page_ids, k_pool, v_pool, k_res, v_res, dev_lengths, dst_slots, tail_ids, *, M, C, page_size, **kw):
+        """Slots become a copy of another in one launch (kw: cache_fork's src, share, n_pages_bound, prefix_tokens): cache_fork, or
+        cache_fork_wide told C, whether the pages are packed and - a packed pool has no such shape - page_size and M."""
+        if self.prepared:
+            return cache_fork(page_ids, k_pool, v_pool, k_res, v_res, dev_lengths, dst_slots, tail_ids, **kw)
+        return cache_fork_wide(page_ids, k_pool, v_pool, k_res, v_res, dev_lengths, dst_slots, tail_ids, C=C, packed=not self.rowmajor,
+                               page_size=page_size, M=M, **kw)
+
+    def swap_pages(self, direction, page_ids, k_pool, v_pool, k_res, v_res, dev_lengths, slot_table, blob_offsets, blob, *, M, C, page_size, **kw):
+        """Requests into blobs or back in one launch (kw: cache_swap's layer0, n_layers, n_pages_bound): cache_swap (blob format 1) or
+        cache_swap_wide (format 2)."""
+        if self.prepared:
+            return cache_swap(direction, page_ids, k_pool, v_pool, k_res, v_res, dev_lengths, slot_table, blob_offsets, blob, **kw)
+        return cache_swap_wide(direction, page_ids, k_pool, v_pool, k_res, v_res, dev_lengths, slot_table, blob_offsets, blob, C=C,
+                               packed=not self.rowmajor, page_size=page_size, M=M, **kw)
+
+    def swap_row_bytes(self, T, r, page_size, M, d, C):
+        """Bytes of one (layer, kv head) row of a request blob of this format's version."""
+        return cache_swap_row_bytes(T, r, page_size, M, d) if self.prepared else cache_swap_row_bytes_wide(T, r, page_size, M, d, C)
+
+    @property
+    def blob_version(self):
+        """The blob format its swap entry reads and writes (include/million_hip.h): 1 for 8-bit codes, 2 for the wide formats."""
+        return 1 if self.prepared else 2
+
     def flush_pages(self, k_rows, v_rows, cents, k_pool, v_pool, page_ids, **kw):
         """The oldest n rows of the ring windows into pages, one encode launch (kw: pq_flush's n, page_size, token_start, x_row_start,
         dev_lengths, min_r): pq_flush for 8-bit codes, pq_flush_wide - told whether the pages are packed - for the wide formats.  Both
@@ -306,23 +333,24 @@ FMT_U8 = CodeFormat(
     encode="million_pq_encode", decode_attn="million_pq_decode_attn", decode_ws="million_attn_workspace_bytes",
     chunk_attn="million_pq_chunk_attn", chunk_attn_lse="million_pq_chunk_attn_lse", chunk_ws="million_chunk_attn_workspace_bytes",
     gather="million_pq_gather_rows", flush="million_pq_flush_layers", store_ragged="million_pq_store_ragged",
-    commit="million_window_commit", commit_rows="million_window_commit_rows", op_decode_attn="pq_decode_attn", op_chunk_attn="pq_chunk_attn")
+    commit="million_window_commit", commit_rows="million_window_commit_rows", fork="million_cache_fork", swap="million_cache_swap",
+    op_decode_attn="pq_decode_attn", op_chunk_attn="pq_chunk_attn")
 FMT_U16 = CodeFormat(
     "uint16", WIDE_CENTROIDS, torch.uint16, rowmajor=True, code_bytes=2, prepared=False, page_shapes=_word_page_shapes,
     check_store=_check_word_store,
     encode="million_pq_encode", decode_attn="million_pq_decode_attn_wide", decode_ws="million_attn_wide_workspace_bytes",
     chunk_attn="million_pq_chunk_attn_wide", chunk_attn_lse="million_pq_chunk_attn_wide", chunk_ws="million_chunk_attn_wide_workspace_bytes",
     gather="million_pq_gather_rows", flush="million_pq_flush_wide", store_ragged="million_pq_store_ragged_wide",
-    commit="million_window_commit_wide", commit_rows="million_window_commit_rows_wide", op_decode_attn="pq_decode_attn_wide",
-    op_chunk_attn="pq_chunk_attn_wide")
+    commit="million_window_commit_wide", commit_rows="million_window_commit_rows_wide", fork="million_cache_fork_wide",
+    swap="million_cache_swap_wide", op_decode_attn="pq_decode_attn_wide", op_chunk_attn="pq_chunk_attn_wide")
 FMT_PACKED = CodeFormat(
     "packed", WIDE_CENTROIDS, torch.uint8, rowmajor=False, code_bytes=2, prepared=False, page_shapes=_packed_page_shapes,
     check_store=_check_packed_store,
     encode="million_pq_encode_packed", decode_attn="million_pq_decode_attn_packed", decode_ws="million_attn_wide_workspace_bytes",
     chunk_attn="million_pq_chunk_attn_packed", chunk_attn_lse="million_pq_chunk_attn_packed", chunk_ws="million_chunk_attn_wide_workspace_bytes",
     gather="million_pq_gather_rows_packed", flush="million_pq_flush_wide", store_ragged="million_pq_store_ragged_wide",
-    commit="million_window_commit_wide", commit_rows="million_window_commit_rows_wide", op_decode_attn="pq_decode_attn_packed",
-    op_chunk_attn="pq_chunk_attn_packed")
+    commit="million_window_commit_wide", commit_rows="million_window_commit_rows_wide", fork="million_cache_fork_wide",
+    swap="million_cache_swap_wide", op_decode_attn="pq_decode_attn_packed", op_chunk_attn="pq_chunk_attn_packed")
 CODE_FORMATS = (FMT_U8, FMT_U16, FMT_PACKED)
 
 
@@ -586,6 +614,80 @@ def pq_store_ragged_wide(k_new: torch.Tensor, v_new: torch.Tensor, k_res: Option
     _store_ragged(who, k_new, v_new, k_res, v_res, k_pool, v_pool, page_ids, dev_lengths, dev_n, M, C, page_size, n_bound, books)
 
 
+def _u8_cache_pools(who, k_pool, v_pool):
+    """The two uint8 pools of a fork or swap call -> (n_pool, page_size, M)."""
+    if (k_pool.dtype != torch.uint8 or v_pool.dtype != torch.uint8 or k_pool.dim() != 3 or not k_pool.is_contiguous() or not v_pool.is_contiguous()
+            or v_pool.shape != (k_pool.shape[0], k_pool.shape[2], k_pool.shape[1])):
+        raise RuntimeError(f"{who}: contiguous uint8 pools (n_pool, page_size, M) and (n_pool, M, page_size) expected")
+    return tuple(k_pool.shape)
+
+
+def _wide_cache_pools(who, k_pool, v_pool, C, packed, page_size, M):
+    """The two pools of a wide fork or swap call -> (n_pool, page_size, M), by _check_wide_pools' rules without the codebooks (the
+    calls move codes and never look one up): C, the pools' dtype and the packed flag pick the format, the format checks each pool
+    and its page shape.  uint16 pools say page_size and M by their shape; packed pools (n_pool, page_bytes) cannot, so both are said."""
+    if C not in WIDE_CENTROIDS:
+        raise RuntimeError(f"{who}: C={C} (codes of {WIDE_CENTROIDS} centroids; C <= 256 takes {who.replace('_wide', '')})")
+    if k_pool.dtype != v_pool.dtype:
+        raise RuntimeError(f"{who}: codes must be uint8 or uint16, both sides alike")
+    if not packed and k_pool.dtype == torch.uint8:
+        raise RuntimeError(f"{who}: uint8 pools hold 8-bit codes, which take {who.replace('_wide', '')} (packed pools: packed=True)")
+    fmt = code_format(who, k_pool.dtype, C, packed)
+    if packed and (page_size is None or M is None):
+        raise RuntimeError(f"{who}: packed pools are (n_pool, page_bytes): page_size= and M= must be said")
+    if not packed:
+        if k_pool.dim() != 3:
+            raise RuntimeError(f"{who}: k_pool page pool must be contiguous (n_pool, page_size, M)")
+        if (page_size is not None and page_size != k_pool.shape[1]) or (M is not None and M != k_pool.shape[2]):
+            raise RuntimeError(f"{who}: page_size={page_size}, M={M} said, k_pool of pages {tuple(k_pool.shape[1:])}")
+        page_size, M = k_pool.shape[1:]
+    if page_size not in (32, 64, 128) or M not in (16, 32, 64):
+        raise RuntimeError(f"{who}: page_size={page_size} (32, 64 or 128), M={M} (16, 32 or 64)")
+    shapes = fmt.page_shapes(page_size, M, C)
+    for name, pool, shape in (("k_pool", k_pool, shapes[0]), ("v_pool", v_pool, shapes[1])):
+        fmt.check_store(who, name, pool, True, page_size, None, None, M, C, None)
+        if tuple(pool.shape[1:]) != tuple(shape):
+            raise RuntimeError(f"{who}: {name} must be (n_pool, {', '.join(map(str, shape))}) for page_size={page_size}, M={M}")
+    if k_pool.shape[0] != v_pool.shape[0]:
+        raise RuntimeError(f"{who}: k_pool and v_pool must hold the same number of pages")
+    return k_pool.shape[0], page_size, M
+
+
+def _cache_fork(who, entry, pools, extra, page_ids, k_pool, v_pool, k_res, v_res, dev_lengths, dst_slots, tail_ids, src, share,
+                n_pages_bound, prefix_tokens):
+    """cache_fork and cache_fork_wide: the checks of the cache arrays, the descriptor, the launch of `entry`.  pools():
+    (n_pool, page_size, M) of the two pools or the format's refusal; extra: the entry's arguments between tail_ids and the stream."""
+    _need_cuda(page_ids, k_pool, v_pool, k_res, v_res, dev_lengths, dst_slots, tail_ids)
+    if page_ids.dtype != torch.int32 or page_ids.dim() != 4 or page_ids[0].numel() and not page_ids[0].is_contiguous():
+        raise RuntimeError(f"{who}: int32 page_ids (layers, bs, nh_k, n_pages_cap), each layer contiguous, expected")
+    n_layers, bs, nhk, cap_pages = page_ids.shape
+    n_pool, page_size, M = pools()
+    if (k_res.dtype != torch.float16 or v_res.dtype != torch.float16 or k_res.dim() != 5 or k_res.shape != v_res.shape or k_res.stride() != v_res.stride()
+            or k_res.shape[:3] != (n_layers, bs, nhk) or not k_res[0].is_contiguous()):
+        raise RuntimeError(f"{who}: fp16 windows (layers, bs, nh_k, cap, d), each layer contiguous, K and V alike, expected")
+    cap, d = k_res.shape[3], k_res.shape[4]
+    if dev_lengths.dtype != torch.int32 or dev_lengths.shape != (n_layers, bs, 4) or not dev_lengths[0].is_contiguous():
+        raise RuntimeError(f"{who}: int32 dev_lengths (layers, bs, 4) expected")
+    if dst_slots.dtype != torch.int32 or dst_slots.dim() != 1 or not dst_slots.is_contiguous():
+        raise RuntimeError(f"{who}: dst_slots must be contiguous int32 (n_dst,)")
+    n_dst = dst_slots.numel()
+    if tail_ids is not None and (tail_ids.dtype != torch.int32 or tail_ids.shape != (n_dst, n_layers, nhk) or not tail_ids.is_contiguous()):
+        raise RuntimeError(f"{who}: tail_ids must be contiguous int32 (n_dst, layers, nh_k)")
+    if share and tail_ids is None:
+        raise RuntimeError(f"{who}: share=True needs tail_ids")
+    desc = L.ForkDesc()
+    desc.struct_size = ctypes.sizeof(L.ForkDesc)
+    desc.n_layers, desc.bs, desc.nh_k, desc.d, desc.M, desc.page_size = n_layers, bs, nhk, d, M, page_size
+    desc.n_pages_cap, desc.n_pool, desc.resid_cap = cap_pages, n_pool, cap
+    desc.ids_layer_stride, desc.rows_layer_stride, desc.lengths_layer_stride = page_ids.stride(0), k_res.stride(0), dev_lengths.stride(0)
+    desc.src, desc.n_dst, desc.mode = int(src), n_dst, L.MILLION_FORK_SHARE if share else L.MILLION_FORK_COPY
+    desc.n_pages_bound = cap_pages if n_pages_bound is None else int(n_pages_bound)
+    desc.prefix_tokens = int(prefix_tokens)
+    L.check(getattr(L.load(), entry)(ctypes.byref(desc), page_ids.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(), k_res.data_ptr(),
+                                     v_res.data_ptr(), dev_lengths.data_ptr(), dst_slots.data_ptr(), _ptr(tail_ids), *extra, _stream()), entry)
+    _vshadow_drop(v_pool)
+
+
 def cache_fork(page_ids: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_res: torch.Tensor, v_res: torch.Tensor,
                dev_lengths: torch.Tensor, dst_slots: torch.Tensor, tail_ids: Optional[torch.Tensor], *, src: int, share: bool,
                n_pages_bound: Optional[int] = None, prefix_tokens: int = -1) -> None:
@@ -596,39 +698,21 @@ def cache_fork(page_ids: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tenso
     (n_dst, layers, nh_k)) for the partial tail page, which alone is copied; share=False: every live page is copied into the
     ids the destinations' rows hold.  The window and the lengths row follow; prefix_tokens >= 0 copies the first tokens only and
     no window.  n_pages_bound (default: the table's row length) bounds the source's pages: it sizes the grid."""
-    _need_cuda(page_ids, k_pool, v_pool, k_res, v_res, dev_lengths, dst_slots, tail_ids)
-    if page_ids.dtype != torch.int32 or page_ids.dim() != 4 or page_ids[0].numel() and not page_ids[0].is_contiguous():
-        raise RuntimeError("cache_fork: int32 page_ids (layers, bs, nh_k, n_pages_cap), each layer contiguous, expected")
-    n_layers, bs, nhk, cap_pages = page_ids.shape
-    if (k_pool.dtype != torch.uint8 or v_pool.dtype != torch.uint8 or k_pool.dim() != 3 or not k_pool.is_contiguous() or not v_pool.is_contiguous()
-            or v_pool.shape != (k_pool.shape[0], k_pool.shape[2], k_pool.shape[1])):
-        raise RuntimeError("cache_fork: contiguous uint8 pools (n_pool, page_size, M) and (n_pool, M, page_size) expected")
-    n_pool, page_size, M = k_pool.shape
-    if (k_res.dtype != torch.float16 or v_res.dtype != torch.float16 or k_res.dim() != 5 or k_res.shape != v_res.shape or k_res.stride() != v_res.stride()
-            or k_res.shape[:3] != (n_layers, bs, nhk) or not k_res[0].is_contiguous()):
-        raise RuntimeError("cache_fork: fp16 windows (layers, bs, nh_k, cap, d), each layer contiguous, K and V alike, expected")
-    cap, d = k_res.shape[3], k_res.shape[4]
-    if dev_lengths.dtype != torch.int32 or dev_lengths.shape != (n_layers, bs, 4) or not dev_lengths[0].is_contiguous():
-        raise RuntimeError("cache_fork: int32 dev_lengths (layers, bs, 4) expected")
-    if dst_slots.dtype != torch.int32 or dst_slots.dim() != 1 or not dst_slots.is_contiguous():
-        raise RuntimeError("cache_fork: dst_slots must be contiguous int32 (n_dst,)")
-    n_dst = dst_slots.numel()
-    if tail_ids is not None and (tail_ids.dtype != torch.int32 or tail_ids.shape != (n_dst, n_layers, nhk) or not tail_ids.is_contiguous()):
-        raise RuntimeError("cache_fork: tail_ids must be contiguous int32 (n_dst, layers, nh_k)")
-    if share and tail_ids is None:
-        raise RuntimeError("cache_fork: share=True needs tail_ids")
-    desc = L.ForkDesc()
-    desc.struct_size = ctypes.sizeof(L.ForkDesc)
-    desc.n_layers, desc.bs, desc.nh_k, desc.d, desc.M, desc.page_size = n_layers, bs, nhk, d, M, page_size
-    desc.n_pages_cap, desc.n_pool, desc.resid_cap = cap_pages, n_pool, cap
-    desc.ids_layer_stride, desc.rows_layer_stride, desc.lengths_layer_stride = page_ids.stride(0), k_res.stride(0), dev_lengths.stride(0)
-    desc.src, desc.n_dst, desc.mode = int(src), n_dst, L.MILLION_FORK_SHARE if share else L.MILLION_FORK_COPY
-    desc.n_pages_bound = cap_pages if n_pages_bound is None else int(n_pages_bound)
-    desc.prefix_tokens = int(prefix_tokens)
-    L.check(L.load().million_cache_fork(ctypes.byref(desc), page_ids.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(), k_res.data_ptr(),
-                                        v_res.data_ptr(), dev_lengths.data_ptr(), dst_slots.data_ptr(), _ptr(tail_ids), _stream()),
-            "million_cache_fork")
-    _vshadow_drop(v_pool)
+    _cache_fork("cache_fork", "million_cache_fork", lambda: _u8_cache_pools("cache_fork", k_pool, v_pool), (), page_ids, k_pool, v_pool,
+                k_res, v_res, dev_lengths, dst_slots, tail_ids, src, share, n_pages_bound, prefix_tokens)
+
+
+def cache_fork_wide(page_ids: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_res: torch.Tensor, v_res: torch.Tensor,
+                    dev_lengths: torch.Tensor, dst_slots: torch.Tensor, tail_ids: Optional[torch.Tensor], *, src: int, share: bool,
+                    n_pages_bound: Optional[int] = None, prefix_tokens: int = -1, C: int, packed: bool = False,
+                    page_size: Optional[int] = None, M: Optional[int] = None) -> None:
+    """cache_fork over the pools of a wide cache (million_cache_fork_wide): uint16 pools (n_pool, page_size, M) / (n_pool, M,
+    page_size) or, packed=True, packed pools uint8 (n_pool, packed_page_bytes(page_size, M, C)) - then page_size= and M= are said,
+    the pools' shape cannot.  Every argument and every rule is cache_fork's; a packed page is copied whole, both planes."""
+    who = "cache_fork_wide"
+    _cache_fork(who, "million_cache_fork_wide", lambda: _wide_cache_pools(who, k_pool, v_pool, C, packed, page_size, M),
+                (int(C), int(bool(packed))), page_ids, k_pool, v_pool, k_res, v_res, dev_lengths, dst_slots, tail_ids, src, share,
+                n_pages_bound, prefix_tokens)
 
 
 def cache_swap_row_bytes(T: int, r: int, page_size: int, M: int, d: int) -> int:
@@ -638,37 +722,37 @@ def cache_swap_row_bytes(T: int, r: int, page_size: int, M: int, d: int) -> int:
     return 2 * n_live * page_size * M + 4 * int(r) * d
 
 
-def cache_swap(direction: int, page_ids: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_res: torch.Tensor,
-               v_res: torch.Tensor, dev_lengths: torch.Tensor, slot_table: torch.Tensor, blob_offsets: torch.Tensor,
-               blob: torch.Tensor, *, layer0: int = 0, n_layers: Optional[int] = None, n_pages_bound: Optional[int] = None) -> None:
-    """Pack requests into blobs (direction = L.MILLION_SWAP_PACK) or restore blobs into the pages the slots' table rows name
-    (L.MILLION_SWAP_UNPACK), for the layers [layer0, layer0 + n_layers) (default: from layer0 on), in one launch
-    (million_cache_swap).  The cache arrays are those of cache_fork; slot_table: device int32 (n_slots, 4) {slot, T, r, start};
-    blob_offsets: device int64 (n_slots,), the byte offset in `blob` (device uint8, 1-D) of each entry's first row of layer0.
-    n_pages_bound (default: the table's row length) bounds a request's pages: it sizes the grid and clamps T."""
+def cache_swap_row_bytes_wide(T: int, r: int, page_size: int, M: int, d: int, C: int) -> int:
+    """Bytes of one (layer, kv head) row of a request blob, format 2 (million_cache_swap_wide): format 1's row with packed pages -
+    packed_page_bytes(page_size, M, C) each - whatever the pool holds.  Always a multiple of 16."""
+    n_live = (int(T) + page_size - 1) // page_size
+    return 2 * n_live * packed_page_bytes(page_size, M, C) + 4 * int(r) * d
+
+
+def _cache_swap(who, entry, pools, extra, direction, page_ids, k_pool, v_pool, k_res, v_res, dev_lengths, slot_table, blob_offsets, blob,
+                layer0, n_layers, n_pages_bound):
+    """cache_swap and cache_swap_wide: the checks of the cache arrays, the descriptor, the launch of `entry` (pools, extra:
+    _cache_fork's)."""
     _need_cuda(page_ids, k_pool, v_pool, k_res, v_res, dev_lengths, slot_table, blob_offsets, blob)
     if direction not in (L.MILLION_SWAP_PACK, L.MILLION_SWAP_UNPACK):
-        raise RuntimeError("cache_swap: direction must be MILLION_SWAP_PACK or MILLION_SWAP_UNPACK")
+        raise RuntimeError(f"{who}: direction must be MILLION_SWAP_PACK or MILLION_SWAP_UNPACK")
     if page_ids.dtype != torch.int32 or page_ids.dim() != 4 or page_ids[0].numel() and not page_ids[0].is_contiguous():
-        raise RuntimeError("cache_swap: int32 page_ids (layers, bs, nh_k, n_pages_cap), each layer contiguous, expected")
+        raise RuntimeError(f"{who}: int32 page_ids (layers, bs, nh_k, n_pages_cap), each layer contiguous, expected")
     n_all, bs, nhk, cap_pages = page_ids.shape
-    if (k_pool.dtype != torch.uint8 or v_pool.dtype != torch.uint8 or k_pool.dim() != 3 or not k_pool.is_contiguous() or not v_pool.is_contiguous()
-            or v_pool.shape != (k_pool.shape[0], k_pool.shape[2], k_pool.shape[1])):
-        raise RuntimeError("cache_swap: contiguous uint8 pools (n_pool, page_size, M) and (n_pool, M, page_size) expected")
-    n_pool, page_size, M = k_pool.shape
+    n_pool, page_size, M = pools()
     if (k_res.dtype != torch.float16 or v_res.dtype != torch.float16 or k_res.dim() != 5 or k_res.shape != v_res.shape or k_res.stride() != v_res.stride()
             or k_res.shape[:3] != (n_all, bs, nhk) or not k_res[0].is_contiguous()):
-        raise RuntimeError("cache_swap: fp16 windows (layers, bs, nh_k, cap, d), each layer contiguous, K and V alike, expected")
+        raise RuntimeError(f"{who}: fp16 windows (layers, bs, nh_k, cap, d), each layer contiguous, K and V alike, expected")
     cap, d = k_res.shape[3], k_res.shape[4]
     if dev_lengths.dtype != torch.int32 or dev_lengths.shape != (n_all, bs, 4) or not dev_lengths[0].is_contiguous():
-        raise RuntimeError("cache_swap: int32 dev_lengths (layers, bs, 4) expected")
+        raise RuntimeError(f"{who}: int32 dev_lengths (layers, bs, 4) expected")
     if slot_table.dtype != torch.int32 or slot_table.dim() != 2 or slot_table.shape[1] != 4 or not slot_table.is_contiguous():
-        raise RuntimeError("cache_swap: slot_table must be contiguous int32 (n_slots, 4)")
+        raise RuntimeError(f"{who}: slot_table must be contiguous int32 (n_slots, 4)")
     n_slots = slot_table.shape[0]
     if blob_offsets.dtype != torch.int64 or blob_offsets.shape != (n_slots,) or not blob_offsets.is_contiguous():
-        raise RuntimeError("cache_swap: blob_offsets must be contiguous int64 (n_slots,)")
+        raise RuntimeError(f"{who}: blob_offsets must be contiguous int64 (n_slots,)")
     if blob.dtype != torch.uint8 or blob.dim() != 1 or not blob.is_contiguous():
-        raise RuntimeError("cache_swap: blob must be a contiguous 1-D uint8 tensor")
+        raise RuntimeError(f"{who}: blob must be a contiguous 1-D uint8 tensor")
     desc = L.SwapDesc()
     desc.struct_size = ctypes.sizeof(L.SwapDesc)
     desc.direction = int(direction)
@@ -679,11 +763,36 @@ def cache_swap(direction: int, page_ids: torch.Tensor, k_pool: torch.Tensor, v_p
     desc.blob_bytes = blob.numel()
     desc.n_slots = n_slots
     desc.n_pages_bound = cap_pages if n_pages_bound is None else int(n_pages_bound)
-    L.check(L.load().million_cache_swap(ctypes.byref(desc), page_ids.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(), k_res.data_ptr(),
-                                        v_res.data_ptr(), dev_lengths.data_ptr(), slot_table.data_ptr(), blob_offsets.data_ptr(),
-                                        blob.data_ptr(), _stream()), "million_cache_swap")
+    L.check(getattr(L.load(), entry)(ctypes.byref(desc), page_ids.data_ptr(), k_pool.data_ptr(), v_pool.data_ptr(), k_res.data_ptr(),
+                                     v_res.data_ptr(), dev_lengths.data_ptr(), slot_table.data_ptr(), blob_offsets.data_ptr(),
+                                     blob.data_ptr(), *extra, _stream()), entry)
     if direction == L.MILLION_SWAP_UNPACK:
         _vshadow_drop(v_pool)
+
+
+def cache_swap(direction: int, page_ids: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_res: torch.Tensor,
+               v_res: torch.Tensor, dev_lengths: torch.Tensor, slot_table: torch.Tensor, blob_offsets: torch.Tensor,
+               blob: torch.Tensor, *, layer0: int = 0, n_layers: Optional[int] = None, n_pages_bound: Optional[int] = None) -> None:
+    """Pack requests into blobs (direction = L.MILLION_SWAP_PACK) or restore blobs into the pages the slots' table rows name
+    (L.MILLION_SWAP_UNPACK), for the layers [layer0, layer0 + n_layers) (default: from layer0 on), in one launch
+    (million_cache_swap).  The cache arrays are those of cache_fork; slot_table: device int32 (n_slots, 4) {slot, T, r, start};
+    blob_offsets: device int64 (n_slots,), the byte offset in `blob` (device uint8, 1-D) of each entry's first row of layer0.
+    n_pages_bound (default: the table's row length) bounds a request's pages: it sizes the grid and clamps T."""
+    _cache_swap("cache_swap", "million_cache_swap", lambda: _u8_cache_pools("cache_swap", k_pool, v_pool), (), direction, page_ids, k_pool,
+                v_pool, k_res, v_res, dev_lengths, slot_table, blob_offsets, blob, layer0, n_layers, n_pages_bound)
+
+
+def cache_swap_wide(direction: int, page_ids: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_res: torch.Tensor,
+                    v_res: torch.Tensor, dev_lengths: torch.Tensor, slot_table: torch.Tensor, blob_offsets: torch.Tensor,
+                    blob: torch.Tensor, *, layer0: int = 0, n_layers: Optional[int] = None, n_pages_bound: Optional[int] = None,
+                    C: int, packed: bool = False, page_size: Optional[int] = None, M: Optional[int] = None) -> None:
+    """cache_swap over the pools of a wide cache (million_cache_swap_wide; the pools: cache_fork_wide's) with blob format 2: the
+    pages of the blob are packed pages whatever the pools hold, dead bytes zero and every field code & (C - 1), so a uint16 pool
+    and a packed pool that hold the same codes pack to the same bytes, and a blob restores into either."""
+    who = "cache_swap_wide"
+    _cache_swap(who, "million_cache_swap_wide", lambda: _wide_cache_pools(who, k_pool, v_pool, C, packed, page_size, M),
+                (int(C), int(bool(packed))), direction, page_ids, k_pool, v_pool, k_res, v_res, dev_lengths, slot_table, blob_offsets, blob,
+                layer0, n_layers, n_pages_bound)
 
 
 def transpose_v_codes(v_codes: torch.Tensor, n_tokens: Optional[int] = None) -> torch.Tensor:

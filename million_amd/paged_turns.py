@@ -39,9 +39,20 @@ methods, with the launches of the cache's format (ops.CodeFormat.decode_pages, c
                                                                                                     then the masked block merge)
     commit             ops.window_commit_wide(packed=True)           ops.window_commit_wide         (dev_rows= for a tree's path)
 
+Fork and swap.  fork / swap_out / snapshot_request / swap_in below are PagedPQCache._fork / _swap_out / _swap_in,
+the bodies of the cache's own methods - the same host-mirror transitions, page sharing and free-page accounting - with the
+launches of the cache's format (ops.CodeFormat.fork_pages, swap_pages, swap_row_bytes):
+
+    call                  packed cache                          unpacked cache
+    fork                  ops.cache_fork_wide(packed=True)      ops.cache_fork_wide
+    swap_out / swap_in    ops.cache_swap_wide(packed=True)      ops.cache_swap_wide       blob format 2, snapshot version 2
+
+Blob format 2 holds packed pages whatever the pool holds, so a snapshot of an unpacked cache is (8 + h) / 16 of its code bytes and
+restores into a packed cache of the same geometry, and the other way round: `packed` is no part of a snapshot's geometry.
+
 The cache's own methods keep doing on a wide cache exactly what they did: decoding_with_pages / flush_to_pages flush in lockstep
-only, prefill_ragged / extend_ragged, verify / commit raise NotImplementedError.  Encode-ahead (begin_step reports 'plain' /
-'flush' only), fork, swap, sinks and SharedPrefix on wide caches stay refused by the cache."""
+only, prefill_ragged / extend_ragged, verify / commit, fork, swap_out / snapshot_request / swap_in raise NotImplementedError.
+Encode-ahead (begin_step reports 'plain' / 'flush' only), sinks and SharedPrefix on wide caches stay refused by the cache."""
 from __future__ import annotations
 
 
@@ -134,3 +145,45 @@ def commit(cache, n_accept=None, *, path=None):
     if cache.nbits <= 8:
         return cache.commit(n_accept, path=path)
     return cache._commit("paged_turns.commit", n_accept, path)
+
+
+def fork(cache, src, dst, n_tokens=None):
+    """PagedPQCache.fork for a cache with nbits 9 .. 12 (packed or not): slot(s) dst become a copy of slot src - of its first
+    n_tokens coded tokens and no window, when n_tokens is given - in every layer and in ONE launch (ops.cache_fork_wide): what
+    prefill_request of the same prompt and the same decode steps would have left there, bit for bit, without the prompt pass.
+    Paging on demand shares the full code pages and copies the partial tail page into a fresh id; a preallocated table gets a copy
+    of every live page.  Shared pages are safe under the wide page writers as they are under the 8-bit ones: nothing ever writes a
+    token below a request's T, and in a packed page every high byte belongs to one token, so a store of the tokens from T on never
+    reads, modifies or zeroes a byte of a shared token.  The destinations go on with decode / flush / extend* / verify / commit
+    above.  Every refusal of the 8-bit method holds, before anything moves.  A cache with nbits = 8 is handed to its own method."""
+    if cache.nbits <= 8:
+        return cache.fork(src, dst, n_tokens=n_tokens)
+    return cache._fork(src, dst, n_tokens)
+
+
+def swap_out(cache, b, release=True, staging_bytes=64 << 20):
+    """PagedPQCache.swap_out for a cache with nbits 9 .. 12 (packed or not): slot(s) b as RequestSnapshot(s) in host memory - blob
+    format 2, meta["version"] = 2 -, packed by ONE launch per range of layers (ops.cache_swap_wide) through a staging buffer of at
+    most staging_bytes; release=True then releases the slot(s).  The blob holds packed pages whatever the cache's pools hold, so
+    the snapshot goes back into a packed or an unpacked cache of the same geometry and codebooks.  A cache with nbits = 8 is handed
+    to its own method."""
+    if cache.nbits <= 8:
+        return cache.swap_out(b, release=release, staging_bytes=staging_bytes)
+    cache._no_sinks("swap_out / snapshot_request")
+    return cache._swap_out(b, release, staging_bytes)
+
+
+def snapshot_request(cache, b):
+    """swap_out(cache, b, release=False): the slot keeps decoding, the snapshot is what it holds now."""
+    return swap_out(cache, b, release=False)
+
+
+def swap_in(cache, b, snap, check_codebooks=True, staging_bytes=64 << 20):
+    """PagedPQCache.swap_in for a cache with nbits 9 .. 12 (packed or not): a version-2 RequestSnapshot into the empty slot b -
+    pages allocated on demand or the fixed ids of a preallocated table, ONE launch per range of layers (ops.cache_swap_wide).
+    Every refusal of the 8-bit method holds, before anything changes; a version-1 snapshot is one of them (and a version-2
+    snapshot is refused by an 8-bit cache).  A cache with nbits = 8 is handed to its own method."""
+    if cache.nbits <= 8:
+        return cache.swap_in(b, snap, check_codebooks=check_codebooks, staging_bytes=staging_bytes)
+    cache._no_sinks("swap_in")
+    return cache._swap_in(b, snap, check_codebooks, staging_bytes)

@@ -388,13 +388,14 @@ class DynamicPQCache(_CacheBase):
         return sum(c.numel() * c.element_size() for c in self.key_residual_cache + self.value_residual_cache)
 
 
-SNAPSHOT_VERSION = 1
+SNAPSHOT_VERSION = 1      # of an 8-bit cache's snapshots; a wide cache writes and reads version 2 (ops.CodeFormat.blob_version)
 _SNAPSHOT_GEOMETRY = ("layer_num", "nh_k", "d", "M", "nbits", "page_size", "resid_cap")
 
 
 class RequestSnapshot:
     """One request of a PagedPQCache outside its pages (swap_out / swap_in, formats.save_request): `blob`, a 1-D uint8 host
-    tensor in blob format 1 (include/million_hip.h, million_cache_swap; pinned when it comes from swap_out), and `meta`, a dict
+    tensor in blob format 1 (include/million_hip.h, million_cache_swap; pinned when it comes from swap_out) - format 2
+    (million_cache_swap_wide) when it comes from a cache with nbits 9 .. 12 through paged_turns.swap_out -, and `meta`, a dict
     of plain ints and strings: "version", the geometry (layer_num, nh_k, d, M, nbits, page_size, resid_cap), the request (T
     coded tokens, r window rows, ring start `start`, `seen` tokens) and the sha256 of the key and value codebook bytes."""
 
@@ -447,7 +448,8 @@ class PagedPQCache(_CacheBase):
 
     `nbits` 9 .. 12 with `dtype=torch.uint16` (uint16 pools, codebooks of 2**nbits centroids): the core life - prefill,
     prefill_request, decoding_with_pages (ops.pq_decode_attn_wide), the in-line flush of requests in lockstep, release, cleanup -
-    and NotImplementedError naming nbits for the rest (extend*, prefill_ragged, fork, swap, verify / commit, update, sinks).
+    and NotImplementedError naming nbits for the rest (extend*, prefill_ragged, fork, swap, verify / commit, update, sinks;
+    fork and swap of such a cache: million_amd.paged_turns).
     DESIGN.md 4.14.  extend / extend_request of such a cache, packed or not: million_amd.paged_turns.  Requests at
     different lengths - a flush that reads every request's lengths on the device, prefill_ragged, extend_ragged -: million_amd.paged_turns
     too (flush, decode, prefill_ragged, extend_ragged); the methods here keep the lockstep flush and the refusals.
@@ -962,6 +964,10 @@ class PagedPQCache(_CacheBase):
         every live page.  Call it between steps: the source must be at the same lengths in every layer (its pending
         encode-ahead work is joined, as extend does); every destination must be empty (release it first)."""
         self._no_wide("fork")
+        return self._fork(src, dst, n_tokens)
+
+    def _fork(self, src, dst, n_tokens):
+        """fork() behind its refusal of wide caches: the launch is the format's (ops.CodeFormat.fork_pages; paged_turns.fork)."""
         dsts = [int(dst)] if np.isscalar(dst) else [int(x) for x in dst]
         src = int(src)
         nk, ps, nl = self.num_key_value_heads, self.page_size, self.layer_num
@@ -1009,9 +1015,9 @@ class PagedPQCache(_CacheBase):
         self._refresh_device_rows()      # the kernel reads the source's T, r, start from its device rows
         dev = torch.tensor(buf, dtype=torch.int32).to(self.device)
         tail_ids = dev[len(dsts):].view(len(dsts), nl, nk) if share else None
-        ops.cache_fork(self._page_ids_all, self.key_page_pool, self.value_page_pool, self._kres_all, self._vres_all,
-                       self._lengths_all, dev[:len(dsts)], tail_ids, src=src, share=share, n_pages_bound=n_live,
-                       prefix_tokens=-1 if n_tokens is None else T)
+        self._fmt.fork_pages(self._page_ids_all, self.key_page_pool, self.value_page_pool, self._kres_all, self._vres_all,
+                             self._lengths_all, dev[:len(dsts)], tail_ids, M=self.M, C=self.C, page_size=self.page_size, src=src,
+                             share=share, n_pages_bound=n_live, prefix_tokens=-1 if n_tokens is None else T)
         self._note_forked(src, dsts, None if n_tokens is None else T)
 
     def sharing_stats(self) -> Dict:
@@ -1065,6 +1071,11 @@ class PagedPQCache(_CacheBase):
         steps, as fork: the slot must be at the same lengths in every layer (its pending encode-ahead work is joined)."""
         self._no_sinks("swap_out / snapshot_request")
         self._no_wide("swap_out / snapshot_request")
+        return self._swap_out(b, release, staging_bytes)
+
+    def _swap_out(self, b, release, staging_bytes):
+        """swap_out() behind its refusals: the launch, the row bytes and the snapshot version are the format's
+        (ops.CodeFormat.swap_pages, swap_row_bytes, blob_version; paged_turns.swap_out)."""
         one = np.isscalar(b)
         slots = [int(b)] if one else [int(x) for x in b]
         nk, nl = self.num_key_value_heads, self.layer_num
@@ -1082,8 +1093,8 @@ class PagedPQCache(_CacheBase):
         snaps, rbs = [], []
         for s in slots:
             T, r, st = int(self._T_a[0, s]), int(self._r_a[0, s]), int(self._rs_a[0, s])
-            rb = ops.cache_swap_row_bytes(T, r, self.page_size, self.M, self.d)
-            meta = dict(version=SNAPSHOT_VERSION, **self._swap_geometry(), T=T, r=r, start=st, seen=int(self._seen_a[0, s]),
+            rb = self._fmt.swap_row_bytes(T, r, self.page_size, self.M, self.d, self.C)
+            meta = dict(version=self._fmt.blob_version, **self._swap_geometry(), T=T, r=r, start=st, seen=int(self._seen_a[0, s]),
                         key_cent_sha256=k_sha, value_cent_sha256=v_sha)
             snaps.append(RequestSnapshot(torch.empty(nl * nk * rb, dtype=torch.uint8, pin_memory=cuda), meta))
             rbs.append(rb)
@@ -1094,9 +1105,9 @@ class PagedPQCache(_CacheBase):
         staging = torch.empty(max(16, ranges[0][1] * layer_bytes), dtype=torch.uint8, device=self.device)
         for l0, n in ranges:
             offs = np.concatenate([[0], np.cumsum([n * nk * rb for rb in rbs])]).astype(np.int64)
-            ops.cache_swap(L.MILLION_SWAP_PACK, self._page_ids_all, self.key_page_pool, self.value_page_pool, self._kres_all, self._vres_all,
-                           self._lengths_all, table, torch.from_numpy(offs[:-1].copy()).to(self.device), staging, layer0=l0, n_layers=n,
-                           n_pages_bound=n_live)
+            self._fmt.swap_pages(L.MILLION_SWAP_PACK, self._page_ids_all, self.key_page_pool, self.value_page_pool, self._kres_all,
+                                 self._vres_all, self._lengths_all, table, torch.from_numpy(offs[:-1].copy()).to(self.device), staging,
+                                 M=self.M, C=self.C, page_size=self.page_size, layer0=l0, n_layers=n, n_pages_bound=n_live)
             for i, sn in enumerate(snaps):
                 sn.blob[l0 * nk * rbs[i]:(l0 + n) * nk * rbs[i]].copy_(staging[int(offs[i]):int(offs[i + 1])], non_blocking=True)
         if cuda:
@@ -1119,6 +1130,11 @@ class PagedPQCache(_CacheBase):
         the wrong size, and - unless check_codebooks=False - codebooks other than the ones the codes were made with."""
         self._no_sinks("swap_in")
         self._no_wide("swap_in")
+        return self._swap_in(b, snap, check_codebooks, staging_bytes)
+
+    def _swap_in(self, b, snap, check_codebooks, staging_bytes):
+        """swap_in() behind its refusals; it reads the snapshot version of the cache's format alone (1: 8-bit codes, 2: wide
+        codes, packed or not - `packed` is no part of the geometry; paged_turns.swap_in)."""
         b = int(b)
         meta, blob = snap.meta, snap.blob
         nk, nl, ps = self.num_key_value_heads, self.layer_num, self.page_size
@@ -1126,8 +1142,9 @@ class PagedPQCache(_CacheBase):
             raise RuntimeError(f"swap_in: slot {b} outside [0, {self.bs})")
         if self._T_a[:, b].any() or self._r_a[:, b].any():
             raise RuntimeError(f"swap_in: slot {b} holds tokens (release it first)")
-        if meta.get("version") != SNAPSHOT_VERSION:
-            raise RuntimeError(f"swap_in: snapshot format version {meta.get('version')}, this library reads {SNAPSHOT_VERSION}")
+        if meta.get("version") != self._fmt.blob_version:
+            raise RuntimeError(f"swap_in: snapshot format version {meta.get('version')}, this library reads {self._fmt.blob_version}"
+                               + (f" into a cache with nbits={self.nbits}" if self.nbits > 8 else ""))
         mine = self._swap_geometry()
         for key in _SNAPSHOT_GEOMETRY:
             if meta.get(key) != mine[key]:
@@ -1138,7 +1155,7 @@ class PagedPQCache(_CacheBase):
             raise RuntimeError(f"swap_in: inconsistent snapshot T={T} r={r} start={st} seen={seen}")
         if T > self.max_tokens:
             raise RuntimeError(f"swap_in: {T} tokens exceed max_tokens={self.max_tokens}")
-        rb = ops.cache_swap_row_bytes(T, r, ps, self.M, self.d)
+        rb = self._fmt.swap_row_bytes(T, r, ps, self.M, self.d, self.C)
         if blob.dtype != torch.uint8 or blob.dim() != 1 or blob.numel() != nl * nk * rb:
             raise RuntimeError(f"swap_in: a uint8 blob of {nl * nk * rb} bytes expected, got {blob.dtype} {tuple(blob.shape)}")
         n_live = -(-T // ps)
@@ -1165,8 +1182,9 @@ class PagedPQCache(_CacheBase):
         staging = torch.empty(max(16, ranges[0][1] * nk * rb), dtype=torch.uint8, device=self.device)
         for l0, n in ranges:
             staging[:n * nk * rb].copy_(blob[l0 * nk * rb:(l0 + n) * nk * rb], non_blocking=True)
-            ops.cache_swap(L.MILLION_SWAP_UNPACK, self._page_ids_all, self.key_page_pool, self.value_page_pool, self._kres_all,
-                           self._vres_all, self._lengths_all, table, offs, staging, layer0=l0, n_layers=n, n_pages_bound=n_live)
+            self._fmt.swap_pages(L.MILLION_SWAP_UNPACK, self._page_ids_all, self.key_page_pool, self.value_page_pool, self._kres_all,
+                                 self._vres_all, self._lengths_all, table, offs, staging, M=self.M, C=self.C, page_size=ps, layer0=l0,
+                                 n_layers=n, n_pages_bound=n_live)
         self._note_restored(b, meta)
 
     def cleanup(self):
