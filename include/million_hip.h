@@ -205,6 +205,30 @@ int million_pq_flush_wide(const million_encode_desc *desc, const void *k_rows, c
                           const int32_t *page_ids, int32_t *dev_lengths, int resid_cap, int min_r, int packed,
                           million_stream_t stream);
 
+/* million_pq_flush_wide for n_layers layers of a cache in one call, and optionally WITHOUT moving the window (encode-ahead):
+ * million_pq_flush_wide's contract with million_pq_flush_layers' extra arguments.  The layers' K / V windows, page tables and
+ * length rows lie rows_layer_stride fp16 elements (a multiple of 8), ids_layer_stride int32 and lengths_layer_stride int32 apart,
+ * layer 0 at the pointers given; pools and codebooks are shared.  Everything stated above holds per (layer, request).
+ * advance != 0: every (layer, request) is flushed by one encode grid of the 16-wave workgroups above (z = n_layers * bs * nh_k *
+ *   2 units), and with dev_lengths ONE more launch, a thread per (layer, request), advances the rows of those that took part.
+ * advance == 0 (encode-ahead): the rows become tokens [T, T + n) of the pages and nothing else changes: no advance launch, no
+ *   write to dev_lengths, word 3 included.  min_r (device lengths) then means "rows present": pass page_size; a request with
+ *   r < min_r takes no part.  The oldest page of window rows is complete resid_cap - page_size steps before it must be flushed,
+ *   so a cache encodes it during an earlier step beside that step's attention launches and commits the flush later with
+ *   million_lengths_advance alone; codes and final state are those of the flush at the flush step.  Built for that: one launch of
+ *   4-wave workgroups (wave = one of the group's 4 subspaces, scanning its whole centroid range; <= 72 registers, <= 9 KiB of LDS:
+ *   one fits on a CU beside a wide attention workgroup at d = 128).  Only `pairs_in_flight` (layer, request) pairs are in the grid
+ *   (z = pairs_in_flight * nh_k * 2) and the workgroups walk the other pairs; 0: the library's rule (about one workgroup per CU
+ *   in flight), a positive value is clamped into [1, n_layers * bs], a negative one is MILLION_ERR_ARG.  pairs_in_flight is not
+ *   read when advance != 0.
+ * Checks: million_pq_flush_wide's, in the same order with the same codes; n_layers < 0 or n_layers * bs * nh_k > 32767:
+ * MILLION_ERR_SHAPE; n = 0 or n_layers = 0: MILLION_OK whatever the pointers.  Capture as million_pq_flush_wide. */
+int million_pq_flush_wide_layers(const million_encode_desc *desc, const void *k_rows, const void *v_rows,
+                                 const void *k_cents, const void *v_cents, void *k_pool, void *v_pool,
+                                 const int32_t *page_ids, int32_t *dev_lengths, int resid_cap, int min_r,
+                                 int n_layers, int64_t rows_layer_stride, int64_t ids_layer_stride, int64_t lengths_layer_stride,
+                                 int advance, int packed, int pairs_in_flight, million_stream_t stream);
+
 /* million_pq_store_ragged over uint16 pages and - packed != 0 - packed pages: the same descriptor, meaning, clamps, grid rule and
  * two launches (the advance kernel is the same), with plain (M, C, d_m) fp16 codebooks in place of the prepared ones and C in
  * {512, 1024, 2048, 4096}.  What is read, what may hold anything and is never read, and what is never written are as stated there;

@@ -189,6 +189,8 @@ SYMBOLS = {
     "million_pq_store_ragged": (c_i32, [ctypes.POINTER(StoreRaggedDesc)] + [c_vp] * 12),
     "million_pq_store_ragged_wide": (c_i32, [ctypes.POINTER(StoreRaggedDesc)] + [c_vp] * 11 + [c_i32, c_vp]),
     "million_pq_flush_wide": (c_i32, [ctypes.POINTER(EncodeDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
+    "million_pq_flush_wide_layers": (c_i32, [ctypes.POINTER(EncodeDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32,
+                                             c_i32, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_vp]),
     "million_cache_fork": (c_i32, [ctypes.POINTER(ForkDesc)] + [c_vp] * 9),
     "million_cache_swap": (c_i32, [ctypes.POINTER(SwapDesc)] + [c_vp] * 10),
     "million_cache_fork_wide": (c_i32, [ctypes.POINTER(ForkDesc)] + [c_vp] * 8 + [c_i32, c_i32, c_vp]),

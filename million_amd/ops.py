@@ -233,7 +233,8 @@ class CodeFormat:
     chunk_attn_lse: str                # with it: one entry with an lse argument that may be null, except for 8-bit codes
     chunk_ws: str
     gather: str
-    flush: str                         # the one-launch window flush, and
+    flush: str                         # the one-launch window flush,
+    flush_layers: str                  # the same for several layers in one call, with or without the advance (encode-ahead), and
     store_ragged: str                  # the one-launch ragged store, into its pages
     commit: str                        # draft verification: the one-call commit of the accepted rows, every layer, and
     commit_rows: str                   # ... of chosen rows (the accepted path of a draft tree)
@@ -312,8 +313,9 @@ class CodeFormat:
 
     def flush_pages(self, k_rows, v_rows, cents, k_pool, v_pool, page_ids, **kw):
         """The oldest n rows of the ring windows into pages, one encode launch (kw: pq_flush's n, page_size, token_start, x_row_start,
-        dev_lengths, min_r): pq_flush for 8-bit codes, pq_flush_wide - told whether the pages are packed - for the wide formats.  Both
-        take the codebooks as they are."""
+        dev_lengths, min_r, advance): pq_flush for 8-bit codes, pq_flush_wide - told whether the pages are packed - for the wide
+        formats.  Both take the codebooks as they are, and the layers of a cache side by side (5-D windows: the format's
+        flush_layers entry); advance=False is encode-ahead."""
         if self.prepared:
             return pq_flush(k_rows, v_rows, *cents, k_pool, v_pool, page_ids, **kw)
         return pq_flush_wide(k_rows, v_rows, *cents, k_pool, v_pool, page_ids, packed=not self.rowmajor, **kw)
@@ -332,7 +334,7 @@ FMT_U8 = CodeFormat(
     check_store=_check_word_store,
     encode="million_pq_encode", decode_attn="million_pq_decode_attn", decode_ws="million_attn_workspace_bytes",
     chunk_attn="million_pq_chunk_attn", chunk_attn_lse="million_pq_chunk_attn_lse", chunk_ws="million_chunk_attn_workspace_bytes",
-    gather="million_pq_gather_rows", flush="million_pq_flush_layers", store_ragged="million_pq_store_ragged",
+    gather="million_pq_gather_rows", flush="million_pq_flush_layers", flush_layers="million_pq_flush_layers", store_ragged="million_pq_store_ragged",
     commit="million_window_commit", commit_rows="million_window_commit_rows", fork="million_cache_fork", swap="million_cache_swap",
     op_decode_attn="pq_decode_attn", op_chunk_attn="pq_chunk_attn")
 FMT_U16 = CodeFormat(
@@ -340,7 +342,8 @@ FMT_U16 = CodeFormat(
     check_store=_check_word_store,
     encode="million_pq_encode", decode_attn="million_pq_decode_attn_wide", decode_ws="million_attn_wide_workspace_bytes",
     chunk_attn="million_pq_chunk_attn_wide", chunk_attn_lse="million_pq_chunk_attn_wide", chunk_ws="million_chunk_attn_wide_workspace_bytes",
-    gather="million_pq_gather_rows", flush="million_pq_flush_wide", store_ragged="million_pq_store_ragged_wide",
+    gather="million_pq_gather_rows", flush="million_pq_flush_wide", flush_layers="million_pq_flush_wide_layers",
+    store_ragged="million_pq_store_ragged_wide",
     commit="million_window_commit_wide", commit_rows="million_window_commit_rows_wide", fork="million_cache_fork_wide",
     swap="million_cache_swap_wide", op_decode_attn="pq_decode_attn_wide", op_chunk_attn="pq_chunk_attn_wide")
 FMT_PACKED = CodeFormat(
@@ -348,7 +351,8 @@ FMT_PACKED = CodeFormat(
     check_store=_check_packed_store,
     encode="million_pq_encode_packed", decode_attn="million_pq_decode_attn_packed", decode_ws="million_attn_wide_workspace_bytes",
     chunk_attn="million_pq_chunk_attn_packed", chunk_attn_lse="million_pq_chunk_attn_packed", chunk_ws="million_chunk_attn_wide_workspace_bytes",
-    gather="million_pq_gather_rows_packed", flush="million_pq_flush_wide", store_ragged="million_pq_store_ragged_wide",
+    gather="million_pq_gather_rows_packed", flush="million_pq_flush_wide", flush_layers="million_pq_flush_wide_layers",
+    store_ragged="million_pq_store_ragged_wide",
     commit="million_window_commit_wide", commit_rows="million_window_commit_rows_wide", fork="million_cache_fork_wide",
     swap="million_cache_swap_wide", op_decode_attn="pq_decode_attn_packed", op_chunk_attn="pq_chunk_attn_packed")
 CODE_FORMATS = (FMT_U8, FMT_U16, FMT_PACKED)
@@ -567,28 +571,63 @@ def _check_wide_pools(who, k_cents, v_cents, k_pool, v_pool, page_size, bs, nh_k
 def pq_flush_wide(k_rows: torch.Tensor, v_rows: torch.Tensor, k_cents: torch.Tensor, v_cents: torch.Tensor,
                   k_pool: torch.Tensor, v_pool: torch.Tensor, page_ids: torch.Tensor, *, n: int, page_size: int,
                   token_start: int = 0, x_row_start: int = 0, dev_lengths: Optional[torch.Tensor] = None, min_r: int = 0,
-                  packed: bool = False) -> None:
+                  packed: bool = False, advance: bool = True, pairs_in_flight: Optional[int] = None) -> None:
     """pq_flush for codes of 512 .. 4096 centroids (million_pq_flush_wide): the oldest n <= page_size rows of the K and V windows
     (bs, nh_k, cap, d) become tokens [T, T + n) of uint16 pages - K (n_pool, page_size, M), V (n_pool, M, page_size) - or, packed=True,
     of packed pages (uint8 (n_pool, packed_page_bytes)), in one encode launch; the codes are pq_encode_into's / pq_encode_into_packed's
     bit for bit.  dev_lengths (bs, 4) int32: every request's {T, r, start} is read on the device (clamped), requests with r < min_r
     take no part, the rows of the others advance there (a second, one-thread-per-request launch; word 3 untouched).  None:
-    token_start / x_row_start for every request, nothing advances."""
+    token_start / x_row_start for every request, nothing advances.
+
+    Several layers in one call (million_pq_flush_wide_layers), as pq_flush takes them: k_rows / v_rows (layers, bs, nh_k, cap, d),
+    page_ids (layers, bs, nh_k, n_pages_cap), dev_lengths (layers, bs, 4) - the layers of one cache allocated side by side; one
+    encode launch and one advance launch for all of them.  advance=False: encode only (encode-ahead; nothing of dev_lengths is
+    written, min_r means "rows present", the window moves later: lengths_advance) - a launch of small workgroups built to run
+    beside a step's attention launches, `pairs_in_flight` (layer, request) pairs in its grid and the others walked (None: the
+    library's rule, about one workgroup per CU in flight)."""
     who = "pq_flush_wide"
     _need_cuda(k_rows, v_rows, k_cents, v_cents, k_pool, v_pool, page_ids, dev_lengths)
+    layered = k_rows.dim() == 5
+    n_layers, x_ls, ids_ls, len_ls = 1, 0, 0, 0
+    if layered:
+        if (v_rows.dim() != 5 or v_rows.shape[0] != k_rows.shape[0] or page_ids.dim() != 4 or page_ids.shape[0] != k_rows.shape[0]
+                or (dev_lengths is not None and (dev_lengths.dim() != 3 or dev_lengths.shape[0] != k_rows.shape[0]))):
+            raise RuntimeError(f"{who}: layered windows need layered page_ids (and dev_lengths) of as many layers")
+        if k_rows.stride(0) != v_rows.stride(0) or not page_ids.is_contiguous() or (dev_lengths is not None and not dev_lengths.is_contiguous()):
+            raise RuntimeError(f"{who}: layered windows must share the layer stride; contiguous page_ids / dev_lengths")
+        if k_rows.stride(0) % 8:
+            raise RuntimeError(f"{who}: the layer stride of the windows must be a multiple of 8 elements")
+        n_layers = k_rows.shape[0]
+        if n_layers:
+            x_ls, ids_ls = k_rows.stride(0), page_ids.stride(0)
+            len_ls = dev_lengths.stride(0) if dev_lengths is not None else 0
+            k_rows, v_rows, page_ids = k_rows[0], v_rows[0], page_ids[0]
+            lengths0 = dev_lengths[0] if dev_lengths is not None else None
+        else:
+            return
+    else:
+        lengths0 = dev_lengths
+    if pairs_in_flight is not None and (advance or int(pairs_in_flight) < 1):
+        raise RuntimeError(f"{who}: pairs_in_flight={pairs_in_flight} (a positive count, with advance=False only)")
     bs, nhk, cap, d = _check_flush_windows(who, k_rows, v_rows)
     k_cents, v_cents = k_cents.contiguous(), v_cents.contiguous()
     fmt, M, C = _check_wide_pools(who, k_cents, v_cents, k_pool, v_pool, page_size, bs, nhk, d, packed)
     _check_table(who, page_ids, bs, nhk)
-    if dev_lengths is not None:
-        _check_dev_lengths(who, dev_lengths, bs)
+    if lengths0 is not None:
+        _check_dev_lengths(who, lengths0, bs)
     if not 0 <= n <= page_size:
         raise RuntimeError(f"{who}: n={n} outside [0, page_size={page_size}]")
-    desc = _encode_desc(k_rows, k_cents, n, L.MILLION_CODES_KPAGES, token_start, x_row_start, cap, dev_lengths)
+    desc = _encode_desc(k_rows, k_cents, n, L.MILLION_CODES_KPAGES, token_start, x_row_start, cap, lengths0)
     desc.page_size, desc.n_pages_cap = page_size, page_ids.shape[2]
-    L.check(getattr(L.load(), fmt.flush)(ctypes.byref(desc), k_rows.data_ptr(), v_rows.data_ptr(), k_cents.data_ptr(), v_cents.data_ptr(),
-                                         k_pool.data_ptr(), v_pool.data_ptr(), page_ids.data_ptr(), _ptr(dev_lengths), cap,
-                                         min_r if dev_lengths is not None else 0, int(bool(packed)), _stream()), fmt.flush)
+    if not layered and advance:
+        L.check(getattr(L.load(), fmt.flush)(ctypes.byref(desc), k_rows.data_ptr(), v_rows.data_ptr(), k_cents.data_ptr(), v_cents.data_ptr(),
+                                             k_pool.data_ptr(), v_pool.data_ptr(), page_ids.data_ptr(), _ptr(dev_lengths), cap,
+                                             min_r if dev_lengths is not None else 0, int(bool(packed)), _stream()), fmt.flush)
+        return
+    L.check(getattr(L.load(), fmt.flush_layers)(ctypes.byref(desc), k_rows.data_ptr(), v_rows.data_ptr(), k_cents.data_ptr(), v_cents.data_ptr(),
+                                                k_pool.data_ptr(), v_pool.data_ptr(), page_ids.data_ptr(), _ptr(lengths0), cap,
+                                                min_r if lengths0 is not None else 0, n_layers, x_ls, ids_ls, len_ls, int(bool(advance)),
+                                                int(bool(packed)), int(pairs_in_flight or 0), _stream()), fmt.flush_layers)
 
 
 def pq_store_ragged_wide(k_new: torch.Tensor, v_new: torch.Tensor, k_res: Optional[torch.Tensor], v_res: Optional[torch.Tensor],

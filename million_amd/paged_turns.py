@@ -50,9 +50,22 @@ launches of the cache's format (ops.CodeFormat.fork_pages, swap_pages, swap_row_
 Blob format 2 holds packed pages whatever the pool holds, so a snapshot of an unpacked cache is (8 + h) / 16 of its code bytes and
 restores into a packed cache of the same geometry, and the other way round: `packed` is no part of a snapshot's geometry.
 
+Encode-ahead.  next_step_kind / begin_step / note_replayed_step below are PagedPQCache._next_step_kind /
+_begin_step / _note_replayed, the bodies of the cache's own methods: the oldest page of window rows is encoded a few steps after
+the previous flush by ONE launch per range of layers on a side stream beside that step's attention launches
+(ops.CodeFormat.flush_pages with advance=False: ops.pq_flush_wide -> million_pq_flush_wide_layers, 4-wave workgroups that walk the
+(layer, request) pairs), and the flush step is a 'commit': ops.lengths_advance over every layer's rows and the host mirror, no
+code computed.  decode() above needs nothing new: after a 'commit' no window is full, and on 'flush' - requests at different
+lengths, a begin_step that was skipped, flags cleared by fork / release / verify-commit - it flushes in line as before.
+
+    call               packed cache                                        unpacked cache
+    begin_step 'pre'   ops.pq_flush_wide(packed=True, advance=False)       ops.pq_flush_wide(advance=False)
+    begin_step 'commit'   ops.lengths_advance (device lengths) and the mirror, whatever the format
+
 The cache's own methods keep doing on a wide cache exactly what they did: decoding_with_pages / flush_to_pages flush in lockstep
-only, prefill_ragged / extend_ragged, verify / commit, fork, swap_out / snapshot_request / swap_in raise NotImplementedError.
-Encode-ahead (begin_step reports 'plain' / 'flush' only), sinks and SharedPrefix on wide caches stay refused by the cache."""
+only, prefill_ragged / extend_ragged, verify / commit, fork, swap_out / snapshot_request / swap_in raise NotImplementedError,
+next_step_kind / begin_step report 'plain' / 'flush' and launch nothing, flush_ahead does nothing.  Sinks, SharedPrefix, a
+side-stream flush_ahead and a wide backend of the lifecycle drivers stay unbuilt on wide caches."""
 from __future__ import annotations
 
 
@@ -92,12 +105,45 @@ def decode(cache, query_states, key_states, value_states, layer_idx, out=None, u
     """PagedPQCache.decoding_with_pages for a cache with nbits 9 .. 12 (packed or not) whose requests may be at different
     lengths: the full windows are flushed here first (flush() above), so none is full when the cache's own method runs - its
     flush does nothing and the step is its unchanged fused launch.  Captured, a step is one graph per step kind
-    (cache.next_step_kind(): 'plain' / 'flush'), as for 8-bit caches: the flush launch of a captured 'flush' step is gated on the
-    device (min_r), so its replays follow the rows.  A cache with nbits = 8 is handed to its own method."""
+    (cache.next_step_kind(): 'plain' / 'flush'; with begin_step() below in front of layer 0: next_step_kind() below), as for 8-bit
+    caches: the flush launch of a captured 'flush' step is gated on the device (min_r), so its replays follow the rows.  A cache
+    with nbits = 8 is handed to its own method."""
     if cache.nbits > 8 and (cache._r_a[layer_idx] >= cache.extended_residual_size).any():
         cache._flush_pages(layer_idx, use_dev_lengths)
     return cache.decoding_with_pages(query_states, key_states, value_states, layer_idx, out=out, use_dev_lengths=use_dev_lengths,
                                      return_lse=return_lse, lse=lse)
+
+
+def next_step_kind(cache) -> str:
+    """PagedPQCache.next_step_kind for a cache with nbits 9 .. 12 (packed or not), with the 8-bit method's meaning word for word:
+    'plain' | 'pre' / 'preN' (encode-ahead rides along; N: the layers are spread over several steps) | 'commit' (flush step, the
+    codes are already in their pages) | 'flush' (flush step: decode() flushes in line).  A cache with nbits = 8 is handed to its
+    own method."""
+    if cache.nbits <= 8:
+        return cache.next_step_kind()
+    return cache._next_step_kind()
+
+
+def begin_step(cache, use_dev_lengths=False) -> str:
+    """PagedPQCache.begin_step for a cache with nbits 9 .. 12 (packed or not): call at the start of every decode step, before
+    layer 0, then decode() every layer in order.  Returns the kind of the step (next_step_kind above).  'pre' / 'preN': the oldest
+    page of window rows of the step's layers is encoded into its pages by one ops.pq_flush_wide(advance=False) launch per range
+    of layers on a side stream, joined behind the last layer's attention; 'commit': the lengths move (with device lengths ONE
+    ops.lengths_advance over every layer's rows) and no code is computed; 'flush' launches nothing here: decode() flushes in line.
+    Without this call decode() flushes in line at every flush step, as before.  A cache with nbits = 8 is handed to its own
+    method."""
+    if cache.nbits <= 8:
+        return cache.begin_step(use_dev_lengths=use_dev_lengths)
+    return cache._begin_step(use_dev_lengths)
+
+
+def note_replayed_step(cache, kind=None):
+    """PagedPQCache.note_replayed_step for a cache with nbits 9 .. 12 (packed or not): the host-mirror transitions of one replayed
+    step (a hipGraph captured per kind from cache.capture_states()) of the given kind - default: next_step_kind(cache) above.
+    A cache with nbits = 8 is handed to its own method."""
+    if cache.nbits <= 8:
+        return cache.note_replayed_step(kind)
+    cache._note_replayed(next_step_kind(cache) if kind is None else kind)
 
 
 def prefill_ragged(cache, query_states, key_states, value_states, layer_idx, n_new, device_store=False, return_lse=False):

@@ -1299,10 +1299,14 @@ class PagedPQCache(_CacheBase):
     # flush; whatever cannot be served this way (requests at different lengths, a step that was skipped) falls back to it.
     def next_step_kind(self) -> str:
         """'plain' | 'pre' (encode-ahead rides along) | 'commit' (flush step, codes already there) | 'flush' (flush step)."""
+        if self.nbits > 8:      # uint16 codes: this method's flush is the in-line one (encode-ahead: paged_turns.next_step_kind)
+            return "flush" if (self._r_a >= self.extended_residual_size).any() else "plain"
+        return self._next_step_kind()
+
+    def _next_step_kind(self) -> str:
+        """next_step_kind of an 8-bit cache, and of a cache of any format through million_amd.paged_turns."""
         cap = self.extended_residual_size
         full = self._r_a >= cap
-        if self.nbits > 8:      # uint16 codes: the in-line flush is the only flush, nothing is encoded ahead
-            return "flush" if full.any() else "plain"
         if full.any():
             return "commit" if full.all() and self._pre_a.all() else "flush"
         if (not self._pre_a.all() and self._r_a[0, 0] >= self.encode_ahead_at() and self._r_a[0, 0] >= self.page_size
@@ -1313,13 +1317,27 @@ class PagedPQCache(_CacheBase):
                     return "pre" if len(groups) == 1 else f"pre{gi}"
         return "plain"
 
+    # (layer, request) pairs a step encodes ahead by default.  8-bit codes: 32 (below).  Wide codes: a pair is d x C units of work
+    # (a 'pre' launch is 16 x the uint8 one's work per pair and more, and a wave of it scans a whole codebook row), and a step hides
+    # EA_WIDE_UNITS of them per request up to 4 requests under its attention launches: measured at the Llama-3.1-8B shape
+    # (profiles/encode_ahead_wide.txt) - 4 pairs per step at (d 128, C 4096) and one request, 16 at eight, 64 at
+    # (C 1024) and eight; more pairs per step show in the step, fewer add steps, and every 'pre' step costs a fixed 50 - 100 us
+    EA_PAIRS, EA_WIDE_UNITS = 32, 1 << 21
+
+    def _ea_pairs(self) -> int:
+        """(layer, request) pairs one step encodes ahead by default."""
+        if self.nbits <= 8:
+            return self.EA_PAIRS
+        return max(1, self.EA_WIDE_UNITS * min(self.bs, 4) // (self.d * self.C))
+
     def _ea_groups(self):
         """Layer ranges encoded ahead per step: all layers in one step up to 32 (layer, request) pairs, else spread over
         consecutive steps (at 8 requests the attention launches leave few idle issue slots: all layers in one step made
-        that step 1.6 x a plain one; 4 layers per step over 8 steps: see DESIGN.md 4.4)."""
+        that step 1.6 x a plain one; 4 layers per step over 8 steps: see DESIGN.md 4.4).  A wide cache spreads by _ea_pairs()
+        pairs per step.  encode_ahead_steps overrides either; page_size - 16 steps is the cap on the spread."""
         n = self.encode_ahead_steps
         if n is None:
-            n = -(-self.bs * self.layer_num // 32)
+            n = -(-self.bs * self.layer_num // self._ea_pairs())
         n = max(1, min(int(n), self.layer_num, max(1, self.page_size - 16)))
         per = -(-self.layer_num // n)
         return [(g0, min(g0 + per, self.layer_num)) for g0 in range(0, self.layer_num, per)]
@@ -1334,10 +1352,15 @@ class PagedPQCache(_CacheBase):
     def begin_step(self, use_dev_lengths=False) -> str:
         """Call at the start of every decode step, before layer 0 (then decode every layer, in order).  Returns the kind of
         the step (next_step_kind).  Without it decoding_with_pages flushes in line, as the reference does."""
-        kind = self.next_step_kind()
+        if self.nbits > 8:      # reported only: decoding_with_pages flushes in line (encode-ahead: paged_turns.begin_step)
+            return self.next_step_kind()
+        return self._begin_step(use_dev_lengths)
+
+    def _begin_step(self, use_dev_lengths) -> str:
+        """begin_step of an 8-bit cache, and of a cache of any format through million_amd.paged_turns: the encode launch is the
+        format's (ops.CodeFormat.flush_pages with advance=False: ops.pq_flush, ops.pq_flush_wide)."""
+        kind = self._next_step_kind()
         cap, ps = self.extended_residual_size, self.page_size
-        if self.nbits > 8:      # reported only: decoding_with_pages flushes in line
-            return kind
         if kind == "commit":
             if use_dev_lengths:
                 ops.lengths_advance(self._lengths_all.view(-1, 4), ps, cap)      # every layer, every request: one launch
@@ -1362,17 +1385,19 @@ class PagedPQCache(_CacheBase):
                 nl_ = self.encode_ahead_launches
                 if nl_ is None:
                     # replayed from a hipGraph: one launch per layer (the work trickles through the whole step: measured
-                    # 1.04 x a plain step against 1.09 x for one long launch); eager: one launch (the host pays per launch)
+                    # 1.04 x a plain step against 1.09 x for one long launch); eager: one launch (the host pays per launch).
+                    # The rule was measured on the 8-bit kernel and is kept for the wide one, whose launches walk their
+                    # pairs themselves (profiles/encode_ahead_wide.txt)
                     nl_ = self.layer_num if torch.cuda.is_current_stream_capturing() else 1
                 nl_ = max(1, min(int(nl_), G1 - G0))
                 per = (G1 - G0 + nl_ - 1) // nl_
                 for g0 in range(G0, G1, per):
                     g1 = min(g0 + per, G1)
-                    ops.pq_flush(self._kres_all[g0:g1], self._vres_all[g0:g1], self.key_cent, self.value_cent, self.key_page_pool,
-                                 self.value_page_pool, self._page_ids_all[g0:g1], n=ps, page_size=ps, token_start=int(self._T_a[0, 0]),
-                                 x_row_start=int(self._rs_a[0, 0]),
-                                 dev_lengths=self._lengths_all[g0:g1] if use_dev_lengths else None,
-                                 min_r=ps if use_dev_lengths else 0, advance=False)
+                    self._fmt.flush_pages(self._kres_all[g0:g1], self._vres_all[g0:g1], self._cents()[0], self.key_page_pool,
+                                          self.value_page_pool, self._page_ids_all[g0:g1], n=ps, page_size=ps, token_start=int(self._T_a[0, 0]),
+                                          x_row_start=int(self._rs_a[0, 0]),
+                                          dev_lengths=self._lengths_all[g0:g1] if use_dev_lengths else None,
+                                          min_r=ps if use_dev_lengths else 0, advance=False)
             self._pre_a[G0:G1] = 1
             self._pre_join = True      # joined behind the last layer's attention (decoding_with_pages)
         return kind
@@ -1754,6 +1779,9 @@ class PagedPQCache(_CacheBase):
     def note_replayed_step(self, kind=None):
         """The host-mirror transitions of one replayed step of the given kind (default: next_step_kind())."""
         kind = self.next_step_kind() if kind is None else kind
+        self._note_replayed(kind)
+
+    def _note_replayed(self, kind):
         cap, ps = self.extended_residual_size, self.page_size
         if kind in ("commit", "flush"):
             self._note_flushed(self._r_a >= cap)
